@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — PPF pair-matches/s of the MI355X voting engine on BASELINE.json's workloads.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5] [--shard refs]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5] [--shard refs] [--full] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 starts N ranks BY ITSELF when it was not started under torch.distributed.run
 (no RANK/WORLD_SIZE in the environment): the parent process never imports torch or touches the GPU, it
@@ -30,6 +30,8 @@ The ONE line printed by rank 0 carries
                  more than 20 % away makes traffic_stale true and frac null; the ratio is reported as time_vs_collection) / its device time in this run (HIP events on
                  the launch stream); the SURVEY section 8d figure stays beside it as algorithmic_bytes_per_launch
   issue_roofline / lds_roofline   what actually bounds k_vote: LDS wave-instructions and atomic lane-operations per second
+                 (c5: null in a plain run, whose overlapped lanes stretch the kernel times; --full has them)
+A plain run stops there.  `--full` adds what takes runs of its own (--no-cpu-baseline / --no-other-configs leave parts out):
   host_entry     (N = 1, c2) the call the reference really makes: ppf_match from HOST memory, upload and read-back
                  included (SURVEY section 8d's "poses/s per crop"), on a warm context
   other_configs  (N = 1, c2) C4 and C5 measured in the same run, 2 steps each, with the same roofline fields, and c1_pipeline:
@@ -37,8 +39,17 @@ The ONE line printed by rank 0 carries
                  match_S2B, not presampled -> ICP of the top 5): frame_to_pose_ms with prep_ms / match_ms / icp_ms, the CPU
                  oracles' time for the same chain beside it
   pipelined      (N = 1, c2) throughput with two independent crops in flight (extra information, never `value`)
-  cpu_baseline   the CPU oracle (kind "port", -O3 -march=native build made on this box) on a bounded sample of the
-                 same workload: min and median of 5 repetitions on all usable cores plus a 1-thread figure; N = 1 only
+  cpu_baseline   the CPU oracle (kind "port", -O3 -march=native build made on the machine that runs the benchmark) on a
+                 bounded sample of the same workload: min and median of 5 repetitions on all usable cores plus a 1-thread
+                 figure; N = 1 only
+  c5 kernel_ms   one more step on a single lane, so that each kernel's time is its own (the rooflines are computed from it)
+
+`--dump-outputs DIR` writes, after the timed steps, what rank 0's last timed step computed, as DIR/<name>.npy in float64
+(the inputs are seeded, so two builds can be compared output for output):
+  top_poses, top_votes, top_model_index   the top-5 clustered poses the step hands back (c5: per crop x model, zero rows
+                                          past top_counts); at N > 1 the all_gathered block
+  vote_triples, raw_poses                 (c2 / c4) refIndMax / alphaIndMax / maxVotes and the pose of every reference point
+  counters                                c2 / c4: n_ref, n_poses, n_pairs, n_votes; c5: n_pairs, n_votes
 """
 from __future__ import annotations
 
@@ -82,7 +93,17 @@ def parse_args(argv=None):
                     help="c2 at N = 1: leave out the host-entry measurement and the C4 / C5 legs (profiling runs)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="ranks rendezvous (gloo, CPU), report RANK/WORLD_SIZE and stop before any device use")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline figure (CPU baseline, host entry, pipelined crops, the C4 / C5 / "
+                         "C1 legs of a c2 run, c5's single-lane kernel times); a plain run times the headline workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.no_cpu_baseline = args.no_other_configs = True
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -262,6 +283,30 @@ def counter_rooflines(workload, n_votes_per_step, k_vote_ms, abytes, atomics_per
         "source": "profiles/r01_ubench_valu_lds.txt; MI355X_MICROARCH.md (ds_write-class op: 16 lanes/clk/CU)",
     }
     return roofline, issue_roofline, lds_roofline
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def pose_block_arrays(block):
+    """A (n, 27) float64 block of ppf_pose records (a torch tensor) as arrays: the 4x4 poses, vote counts and model indices
+    (the two u32 fields share the record's last 8 bytes)."""
+    import numpy as np
+    b = np.ascontiguousarray(block.cpu().numpy())
+    words = b.view(np.uint32)
+    return {"top_poses": b[:, :16].reshape(-1, 4, 4), "top_votes": words[:, 53], "top_model_index": words[:, 52]}
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64 (exact for the u32 / u64 counts it carries)."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def cpu_baseline(model_step, bottle, scene, n_ref_total, seconds_per_rep, reps=5):
@@ -524,8 +569,9 @@ def main(argv=None):
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run_single(config, n_steps, n_warm, cells="auto", depth_arg=1, shard=False, scene=None):
-        """C2 / C3 / C4: one crop per rank through ppf_match_device, `depth` crops in flight.  Returns the raw figures."""
+    def run_single(config, n_steps, n_warm, cells="auto", depth_arg=1, shard=False, scene=None, outputs=False):
+        """C2 / C3 / C4: one crop per rank through ppf_match_device, `depth` crops in flight.  Returns the raw figures (and,
+        with `outputs`, what the last timed step computed)."""
         model_step = W.C2["model_step"] if config == "c2" else W.C4["model_step"]
         if scene is None:
             scene = (W.c2_scene() if world == 1 else W.c3_scene(rank)) if config == "c2" else W.c4_scene()
@@ -596,12 +642,19 @@ def main(argv=None):
         run(n_steps, True)
         sync()
         elapsed = time.perf_counter() - t0
+        out = None
+        if outputs:  # the last timed step's results are still in its workspace
+            r = wss[(n_steps - 1) % depth].results(n_ref_total, want_poses=False)
+            out = dict(pose_block_arrays(gathered["poses"]), vote_triples=r["triples"],
+                       raw_poses=np.array([p.pose for p in r["raw_poses"]]).reshape(-1, 4, 4),
+                       counters=np.array([last["n_ref"], last["n_poses"], last["n_pairs"], last["n_votes"]]))
         return {"elapsed": elapsed, "tally": tally, "kernel_ms": {k: float(np.mean(v)) for k, v in ms.items()}, "st": dict(last),
                 "info": info, "n_scene": n_scene, "n_ref_total": n_ref_total, "depth": depth, "det": det, "scene": scene,
-                "model_step": model_step}
+                "model_step": model_step, "outputs": out}
 
-    def run_c5(n_steps, n_warm):
-        """C5: four resident tables x 8 crops per rank through ppf_batch_run (timing on: kernel times summed over the matches)."""
+    def run_c5(n_steps, n_warm, single_lane=True, outputs=False):
+        """C5: four resident tables x 8 crops per rank through ppf_batch_run (timing on: kernel times summed over the matches).
+        `single_lane`: one more step on a single lane for each kernel's own time."""
         models = W.c5_models()
         dets = [PPF3DDetector(W.C5_MODEL_STEP, W.REL_DISTANCE).trainModel(m) for m in models]
         crops = W.c5_crops(rank, models=models)
@@ -609,14 +662,15 @@ def main(argv=None):
         bm = BatchMatcher(lanes=int(os.environ.get("PPF_BATCH_LANES", "4")), timing=True)
         tally = {"votes": 0, "pairs": 0, "atomics": 0}
         ms = {"k_pairs": [], "k_group": [], "k_vote": []}
+        last = {}
 
         def run(n, timed):
             for _ in range(n):
                 res = bm.run_device(dets, [t.data_ptr() for t in d_crops], [c.shape[0] for c in crops], 6, W.SCENE_STEP,
                                     W.REL_DISTANCE, presampled=True, top_k=W.TOP_K)
-                if world > 1:
-                    parallel.gather_device(res["d_top"], dist)
+                top = parallel.gather_device(res["d_top"], dist) if world > 1 else res["d_top"]
                 if timed:
+                    last.update(res, top=top)
                     tally["votes"] += res["n_votes"]; tally["pairs"] += res["n_pairs"]
                     tally["atomics"] += res.get("n_lds_atomics", 0)
                     ms["k_vote"].append(res["ms_vote_kernel"]); ms["k_pairs"].append(res["ms_pair_kernel"])
@@ -628,11 +682,15 @@ def main(argv=None):
         run(n_steps, True)
         sync()
         elapsed = time.perf_counter() - t0
+        out = None
+        if outputs:
+            out = dict(pose_block_arrays(last["top"]), top_counts=np.array(last["n_out"]),
+                       counters=np.array([last["n_pairs"], last["n_votes"]]))
         overlapped = {k: float(np.mean(v)) for k, v in ms.items()}
         # kernel times for the rooflines: the lanes of the timed steps overlap, which stretches every kernel's event time by
         # an amount that changes from run to run; one more step on a SINGLE lane gives each kernel's own time
         kernel_ms = overlapped
-        if bm.lanes > 1:
+        if bm.lanes > 1 and single_lane:
             bm1 = BatchMatcher(lanes=1, timing=True)
             one = {}
             for rep in range(2):  # the first run of a batch context sizes its pools
@@ -641,9 +699,9 @@ def main(argv=None):
                 one = {"k_vote": r1["ms_vote_kernel"], "k_pairs": r1["ms_pair_kernel"], "k_group": r1["ms_group_kernel"]}
             kernel_ms = dict(one, lanes_overlapped=overlapped)
             del bm1
-        return {"elapsed": elapsed, "tally": tally, "kernel_ms": kernel_ms,
+        return {"elapsed": elapsed, "tally": tally, "kernel_ms": kernel_ms, "kernel_ms_own": bm.lanes == 1 or single_lane,
                 "info": dets[0].info(), "n_models": len(dets), "n_crops": len(crops), "lanes": bm.lanes,
-                "n_scene": W.C2["n_points"]}
+                "n_scene": W.C2["n_points"], "outputs": out}
 
     def describe(config, shard=False):
         if config == "c2":
@@ -675,10 +733,14 @@ def main(argv=None):
 
     shard_refs = args.config == "c4" and args.shard == "refs" and world > 1
     scaling = "strong" if shard_refs else "weak"
+    want_outputs = bool(args.dump_outputs) and rank == 0
     if args.config == "c5":
-        res = run_c5(args.steps, args.warmup)
+        res = run_c5(args.steps, args.warmup, single_lane=args.full, outputs=want_outputs)
     else:
-        res = run_single(args.config, args.steps, args.warmup, cells=args.cells, depth_arg=args.pipeline_depth, shard=shard_refs)
+        res = run_single(args.config, args.steps, args.warmup, cells=args.cells, depth_arg=args.pipeline_depth, shard=shard_refs,
+                         outputs=want_outputs)
+    if want_outputs:
+        write_outputs(args.dump_outputs, res.pop("outputs"))
     if args.config != "c2":
         args.no_cpu_baseline = True
 
@@ -716,6 +778,8 @@ def main(argv=None):
             "kernel_source_hash": src_hash,
         }
         leg = leg_fields(args.config, res, args.steps)
+        if not res.get("kernel_ms_own", True):  # overlapped lanes stretch the event times the rooflines would divide by
+            leg["roofline"] = leg["issue_roofline"] = leg["lds_roofline"] = None
         line["votes_per_step_per_gpu"] = leg["votes_per_step_per_gpu"]
         line["kernel_ms"] = leg["kernel_ms"]
         if world == 1:

@@ -13,20 +13,20 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p "$ROOT/$OUT"
 cd "$ROOT"
 if [ "$WHAT" = lines ] || [ "$WHAT" = benchlines ]; then
-  python bench.py --steps 20 --warmup 5 > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
+  python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
   python bench.py --config c4 --cells 32 --steps 3 --warmup 1 > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
-  python bench.py --config c5 --steps 3 --warmup 1 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"
+  python bench.py --full --config c5 --steps 3 --warmup 1 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"
   echo "bench lines done"
   ( export PPF_BENCH_ONE_DEVICE=1 PPF_BENCH_BACKEND=gloo
     python bench.py --gpus 2 --steps 6 --warmup 2 --no-cpu-baseline > "$OUT/bench_c3_2ranks_one_device_gloo.json" 2> "$OUT/bench_n2.err"
     python bench.py --gpus 2 --config c4 --shard refs --steps 2 --warmup 1 > "$OUT/bench_c4_refs_2ranks_one_device_gloo.json" 2>> "$OUT/bench_n2.err"
-    python bench.py --gpus 2 --config c5 --steps 3 --warmup 1 > "$OUT/bench_c5_2ranks_one_device_gloo.json" 2>> "$OUT/bench_n2.err" )
+    python bench.py --gpus 2 --full --config c5 --steps 3 --warmup 1 > "$OUT/bench_c5_2ranks_one_device_gloo.json" 2>> "$OUT/bench_n2.err" )
   echo "2-rank rehearsals done"
   [ "$WHAT" = benchlines ] && exit 0   # after publishing the PMC summaries: the lines again, so that their roofline objects read them
   ( cd /tmp && export TMPDIR=/tmp
     rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/trace_c2" -o c2 -- python3 "$ROOT/bench.py" --steps 10 --warmup 2 --no-cpu-baseline --no-other-configs > "$ROOT/$OUT/trace_c2.log" 2>&1
     rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/trace_c4" -o c4 -- python3 "$ROOT/bench.py" --config c4 --cells 32 --steps 3 --warmup 1 > "$ROOT/$OUT/trace_c4.log" 2>&1
-    rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/trace_c5" -o c5 -- python3 "$ROOT/bench.py" --config c5 --steps 3 --warmup 1 > "$ROOT/$OUT/trace_c5.log" 2>&1 )
+    rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/trace_c5" -o c5 -- python3 "$ROOT/bench.py" --full --config c5 --steps 3 --warmup 1 > "$ROOT/$OUT/trace_c5.log" 2>&1 )
   echo "traces done"
   # the reference's real call and its ICP: timings and the ICP kernels' trace
   python tools/pipeline_timing.py > "$OUT/pipeline_timing.json" 2> "$OUT/pipeline_timing.err"

@@ -6,7 +6,7 @@ cd $ROOT
 OUT=gpurun_out/final; mkdir -p $OUT
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/pytest_final.log 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest_final.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-python bench.py --steps 20 --warmup 5 > $OUT/bench_c2_check.json 2> $OUT/bench_c2_check.err; echo "bench rc=$?"
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_c2_check.json 2> $OUT/bench_c2_check.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/final/bench_c2_check.json').read().strip().splitlines()[-1])
