@@ -8,6 +8,7 @@
  *   NormalEstimation   :381-405  ->  Cloud::normals(k)
  *   EdgeExtraction     :406-427  ->  Cloud::edges(curvatureThreshold)
  *   PointCloudXYZNormalToMat :163-190 -> Cloud::toMat()   (an N x 6 ppf_match_3d::Mat for PPF3DDetector / ICP)
+ *   all of the above for every box of a frame  ->  Cloud::prepareFrame(boxes, n, depth, ...)  (one (object, edge) pair per box)
  *
  * Every stage returns a new Cloud that stays in HBM; only toMat()/download() copy to the host.  A maintainer replaces
  * the bodies of those CloudProcessor methods by these one-liners; pcl::PointCloud<PointXYZ> goes
@@ -17,6 +18,7 @@
 #define PPF_CLOUD_STAGES_HPP
 
 #include <memory>
+#include <utility>
 #include <vector>
 
 #include "ppf_match_3d.hpp"
@@ -63,6 +65,30 @@ class Cloud {
   }
   Cloud normals(int k = 30) const { ppf_cloud* o = nullptr; ppf_match_3d::check(ppf_prep_normals(need(), k, &o)); return Cloud(o); }
   Cloud edges(float curvatureThreshold) const { ppf_cloud* o = nullptr; ppf_match_3d::check(ppf_prep_edges(need(), curvatureThreshold, &o)); return Cloud(o); }
+
+  static ppf_frame_params defaultFrameParams() {
+    ppf_frame_params p;
+    ppf_default_frame_params(&p);
+    return p;
+  }
+  /* every stage above for all nBoxes boxes {x, y, width, height} of a frame in one call (ppf_prep_frame): one (object,
+   * edge) pair of to-Mat clouds per box, still in HBM, bit-identical to crop -> ... -> toMat per box.  params NULL =
+   * defaultFrameParams(); stageRows (optional) receives [nBoxes][4] rows after crop, voxel grid, outlier removal, edges. */
+  std::vector<std::pair<Cloud, Cloud> > prepareFrame(const int* boxesXYWH, int nBoxes, const float* depth, int depthRows, int depthCols,
+                                                     double fx, double fy, double ppx, double ppy, const ppf_frame_params* params = 0,
+                                                     std::vector<int>* stageRows = 0, ppf_frame_stats* stats = 0) const {
+    const double intr[4] = {fx, fy, ppx, ppy};
+    const ppf_frame_params prm = params ? *params : defaultFrameParams();
+    const size_t nb = nBoxes > 0 ? (size_t)nBoxes : 0;
+    std::vector<ppf_cloud*> objs(nb + 1, (ppf_cloud*)0), edges(nb + 1, (ppf_cloud*)0);
+    std::vector<int32_t> rows(nb * 4 + 1, 0);
+    ppf_match_3d::check(ppf_prep_frame(need(), boxesXYWH, nBoxes, depth, depthRows, depthCols, intr, &prm, &objs[0], &edges[0], &rows[0],
+                                       stats));
+    std::vector<std::pair<Cloud, Cloud> > out;
+    for (size_t i = 0; i < nb; i++) out.push_back(std::make_pair(Cloud(objs[i]), Cloud(edges[i])));
+    if (stageRows) stageRows->assign(rows.begin(), rows.begin() + nb * 4);
+    return out;
+  }
 
   /* the N x 6 CV_32FC1-shaped Mat of PointCloudXYZNormalToMat (normals re-normalised) */
   ppf_match_3d::Mat toMat() const {

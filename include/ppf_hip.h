@@ -31,6 +31,8 @@
  *   ppf_prep_crop / _voxel_grid /   CloudProcessor::SceneCropping :263, Subsampling :361, OutlierProcessing :341,
  *   _outlier_removal / _normals /   NormalEstimation :381, EdgeExtraction :406, PointCloudXYZNormalToMat :163
  *   _edges / _to_mat (+ppf_cloud_*) (the PCL stages that produce the matcher's input)
+ *   ppf_prep_frame                  the same six stages for all of a frame's boxes at once (CloudProcessing.h:263-427
+ *                                   return one cloud per detection)
  *
  * Conventions
  *   - A cloud argument is (pointer, rows, stride, normal_offset): float32 rows whose first three floats
@@ -404,6 +406,38 @@ ppf_status ppf_icp_refine_clouds(const ppf_cloud* model, const ppf_cloud* scene,
                                  int n_poses, int* iterations_out);
 /* exact neighbour lists (parity surface): idx, d2 are [n][k], ascending (distance, index) */
 ppf_status ppf_prep_knn(const ppf_cloud* in, int k, int* idx, float* d2);
+
+/* ---- every detection of a frame in one segmented device pass ------------------------------------------------ */
+typedef struct ppf_frame_params {
+  double leaf;                /* Subsampling(leafsize), cubic voxel leaf */
+  int32_t mean_k;             /* OutlierProcessing(meanK, .) */
+  double stddev_mul;          /* OutlierProcessing(., Thresh) */
+  int32_t normal_k;           /* NormalEstimation(k) */
+  float curvature_threshold;  /* EdgeExtraction(thr) */
+  int32_t flags;              /* 0; reserved for later knobs */
+  int32_t reserved[4];
+} ppf_frame_params;
+
+typedef struct ppf_frame_stats {
+  int32_t n_boxes;
+  int32_t n_launches;   /* kernel launches enqueued by the call */
+  int32_t n_host_syncs; /* blocking D2H copies + stream/device synchronisations made by the call */
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_frame_stats;
+
+/* leaf 0.003, mean_k 50, stddev_mul 1.0, normal_k 30, curvature_threshold 0.03 */
+void ppf_default_frame_params(ppf_frame_params* p);
+/* SceneCropping -> Subsampling -> OutlierProcessing -> NormalEstimation -> EdgeExtraction -> PointCloudXYZNormalToMat
+ * for n_boxes (0..256) boxes {x, y, width, height} of one frame at once.  objects[i] / edges[i] (edges may be NULL)
+ * receive box i's to-Mat object and edge clouds (curvature kept), bit-identical to running the single-box ppf_prep_*
+ * chain on box i; overlapping boxes share scene rows as they would there.  stage_rows (may be NULL): [n_boxes][4] =
+ * rows after crop, voxel grid, outlier removal, edge extraction.  stats may be NULL.  The launch count and the (at
+ * most three) host synchronisations do not depend on n_boxes.  The outputs may share one device block: release them
+ * in any order.  On error no output is allocated and every output pointer is NULL. */
+ppf_status ppf_prep_frame(const ppf_cloud* scene, const int* boxes_xywh, int n_boxes, const float* depth, int depth_rows,
+                          int depth_cols, const double* intr, const ppf_frame_params* params, ppf_cloud** objects,
+                          ppf_cloud** edges, int32_t* stage_rows, ppf_frame_stats* stats);
 
 #ifdef __cplusplus
 }

@@ -88,6 +88,16 @@ class BatchStats(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class FrameParams(C.Structure):
+    _fields_ = [("leaf", C.c_double), ("mean_k", C.c_int32), ("stddev_mul", C.c_double), ("normal_k", C.c_int32),
+                ("curvature_threshold", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class FrameStats(C.Structure):
+    _fields_ = [("n_boxes", C.c_int32), ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32), ("ms_wall", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
 # every symbol include/ppf_hip.h declares (tests/test_capi_symbols.py checks the header against this)
 _SIGNATURES = {
     "ppf_default_train_params": (None, [C.POINTER(TrainParams)]),
@@ -170,6 +180,10 @@ _SIGNATURES = {
     "ppf_icp_refine_clouds": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(IcpParams), C.POINTER(Pose), C.c_int,
                                         C.POINTER(C.c_int)]),
     "ppf_prep_knn": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "ppf_default_frame_params": (None, [C.POINTER(FrameParams)]),
+    "ppf_prep_frame": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                 C.POINTER(FrameParams), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                                 C.POINTER(FrameStats)]),
     "ppf_icp_register": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }

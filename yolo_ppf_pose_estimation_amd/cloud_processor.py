@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _capi
-from ._capi import IcpParams, Pose, PPFError, check, lib
+from ._capi import FrameParams, FrameStats, IcpParams, Pose, PPFError, check, lib
 from .detector import ICP, PPF3DDetector, Pose3D
 
 
@@ -95,6 +95,31 @@ class DeviceCloud:
     def to_mat(self) -> "DeviceCloud":
         return self._stage(lib().ppf_prep_to_mat)
 
+    def prep_frame(self, boxes, depth: np.ndarray, intr, params=None, *, return_info: bool = False):
+        """every stage crop -> voxel grid -> outlier removal -> normals -> edges -> to-Mat for all boxes of the frame in one
+        call (ppf_prep_frame): a list of (object, edge) DeviceCloud pairs, one per box, bit-identical to the per-box chain.
+        params: a FrameParams, a dict of its fields (the rest default) or None (the defaults).  return_info=True also
+        returns the rows per box after crop / voxel grid / outlier removal / edges ((K, 4) int32) and the call's stats."""
+        b = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 4))
+        nb = b.shape[0]
+        prm = params
+        if not isinstance(prm, FrameParams):
+            prm = FrameParams()
+            lib().ppf_default_frame_params(C.byref(prm))
+            for key, v in (params or {}).items():
+                setattr(prm, key, v)
+        d = np.ascontiguousarray(depth, dtype=np.float32)
+        it = (C.c_double * 4)(*[float(v) for v in intr])
+        objs, edges = (C.c_void_p * max(nb, 1))(), (C.c_void_p * max(nb, 1))()
+        rows = np.zeros((nb, 4), dtype=np.int32)
+        st = FrameStats()
+        check(lib().ppf_prep_frame(self._ptr, b.ctypes.data_as(C.POINTER(C.c_int)), nb, d.ctypes.data, d.shape[0], d.shape[1], it,
+                                   C.byref(prm), objs, edges, rows.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st)))
+        pairs = [(DeviceCloud(C.c_void_p(objs[i])), DeviceCloud(C.c_void_p(edges[i]))) for i in range(nb)]
+        if return_info:
+            return pairs, rows, _capi.stats_dict(st)
+        return pairs
+
     def knn(self, k: int):
         n = len(self)
         idx = np.zeros((n, k), dtype=np.int32)
@@ -125,6 +150,11 @@ class CloudProcessor:
         self.id_to_label: Dict[int, str] = {}
         self._model_clouds: Dict[int, DeviceCloud] = {}
         self.timings: Dict[str, float] = {}  # seconds spent in the last resident match / ICP call
+        # PrepareFrame: one resident to-Mat (object, edge) pair per detection, rows per stage per detection
+        self.object_mats: List[DeviceCloud] = []
+        self.edge_mats: List[DeviceCloud] = []
+        self.stage_rows: Optional[np.ndarray] = None
+        self.frame_stats: Dict[str, object] = {}
 
     # ---- the PCL half -------------------------------------------------------------------------------------
     def SceneCropping(self, CameraIntr) -> List[DeviceCloud]:
@@ -157,6 +187,35 @@ class CloudProcessor:
         Matching / Matching_S2B accept directly, so no cloud crosses PCIe between the crop and the pose)"""
         mat = pcl_cloud.to_mat()
         return mat if resident else mat.rows()
+
+    def PrepareFrame(self, CameraIntr, leafsize: float = 0.003, meanK: int = 50, Thresh: float = 1.0, k: int = 30,
+                     curvThreshold: float = 0.03) -> List[tuple]:
+        """SceneCropping -> Subsampling -> OutlierProcessing -> NormalEstimation -> EdgeExtraction ->
+        PointCloudXYZNormalToMat for every box at once (one ppf_prep_frame call instead of a loop per box and stage).
+        Fills ``object_mats`` / ``edge_mats`` (device-resident, what MatchFrame consumes) and ``stage_rows``."""
+        K = np.asarray(CameraIntr, dtype=np.float64)
+        intr = (K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+        prm = {"leaf": float(leafsize), "mean_k": int(meanK), "stddev_mul": float(Thresh), "normal_k": int(k),
+               "curvature_threshold": float(curvThreshold)}
+        pairs, self.stage_rows, self.frame_stats = self.scene.prep_frame(self.boxes, self.depth, intr, prm, return_info=True)
+        self.object_mats = [o for o, _ in pairs]
+        self.edge_mats = [e for _, e in pairs]
+        return pairs
+
+    def MatchFrame(self, labels: Sequence[Optional[str]], relativeSceneSampleStep: float = 0.05,
+                   relativeSceneDistance: float = 0.05) -> List[Optional[Pose3D]]:
+        """Matching_S2B (+ ICP of the top 5) of every prepared detection against the model named by labels[i], on the
+        resident clouds of PrepareFrame; one pose per detection, None where the label is None, the detection kept no
+        points or no pose was found.  Detections are refined one after another."""
+        if len(labels) != len(self.object_mats):
+            raise PPFError(_capi.PPF_ERR_INVALID, f"{len(labels)} labels for {len(self.object_mats)} prepared detections")
+        out: List[Optional[Pose3D]] = []
+        for name, obj, edge in zip(labels, self.object_mats, self.edge_mats):
+            if name is None or len(obj) == 0:
+                out.append(None)
+                continue
+            out.append(self.Matching_S2B(name, obj, edge, relativeSceneSampleStep, relativeSceneDistance))
+        return out
 
     # ---- the PPF half -------------------------------------------------------------------------------------
     def LoadSingleModel(self, model_input: np.ndarray, label: str):

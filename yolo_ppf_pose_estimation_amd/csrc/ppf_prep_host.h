@@ -11,6 +11,15 @@ struct ppf_cloud {
   DevBuf<float> rows; /* n x 6: x y z nx ny nz */
   DevBuf<float> curv; /* n */
   int n = 0;
+  /* the outputs of ppf_prep_frame share one block: rows.p / curv.p then point into it and do not own it; the last
+   * cloud released returns it to the block cache */
+  std::shared_ptr<DevBuf<float>> shared;
+  ppf_cloud() = default;
+  ppf_cloud(const ppf_cloud&) = delete;
+  ppf_cloud& operator=(const ppf_cloud&) = delete;
+  ~ppf_cloud() {
+    if (shared) { rows.p = nullptr; curv.p = nullptr; }
+  }
 };
 
 /* cells per axis of the neighbour-search grid = sqrt(n) / PPF_KNN_GDIV.  Swept in round 4 (normals(30) / SOR(50) on the reference's
@@ -58,6 +67,42 @@ ppf_status prep_check(const char* who, const ppf_cloud* in, ppf_cloud** out) {
   if (!in) return fail(PPF_ERR_INVALID, "%s: cloud is NULL", who);
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
   return PPF_OK;
+}
+
+/* SceneCropping's five half-spaces for box {x, y, w, h} from the HOST depth image (CloudProcessing.h:263-339): +-30 px,
+ * mean corner depth, corners pushed 0.15 m back.  false: the box lies outside the image.  ppf_prep_crop and
+ * ppf_prep_frame both call it. */
+bool crop_planes(const int* box_xywh, const float* depth, int depth_rows, int depth_cols, const double* intr, CropPlanes* out) {
+  double left = box_xywh[0] - 30; if (left < 0) left = 0;
+  double top = box_xywh[1] - 30; if (top < 0) top = 0;
+  double right = box_xywh[0] + box_xywh[2] + 30; if (right >= depth_cols) right = depth_cols - 1;
+  double bottom = box_xywh[1] + box_xywh[3] + 30; if (bottom >= depth_rows) bottom = depth_rows - 1;
+  const int il = (int)left, it = (int)top, ir = (int)right, ib = (int)bottom;
+  if (il < 0 || it < 0 || ir >= depth_cols || ib >= depth_rows || il > ir || it > ib) return false;
+  const float d1 = depth[(size_t)it * depth_cols + il], d2 = depth[(size_t)it * depth_cols + ir],
+              d3 = depth[(size_t)ib * depth_cols + il], d4 = depth[(size_t)ib * depth_cols + ir];
+  const float davg = (d1 + d2 + d3 + d4) / 4;
+  const double fx = intr[0], fy = intr[1], ppx = intr[2], ppy = intr[3];
+  auto back_project = [&](int u, int v, float* o) { /* Camera::back_projection_bbox, Camera.h:50-61 */
+    o[0] = (float)((double)((float)((double)u - ppx) * davg) / fx);
+    o[1] = (float)((double)((float)((double)v - ppy) * davg) / fy);
+    o[2] = (float)((double)davg + 0.15); /* corners pushed 0.15 m back, :292-295 */
+  };
+  float c[4][3];
+  back_project(il, it, c[0]); back_project(il, ib, c[1]); back_project(ir, it, c[2]); back_project(ir, ib, c[3]);
+  CropPlanes& pl = *out;
+  pl.z_base = c[0][2];
+  const double ctr[3] = {((double)c[0][0] + c[1][0] + c[2][0] + c[3][0]) / 4, ((double)c[0][1] + c[1][1] + c[2][1] + c[3][1]) / 4, (double)pl.z_base};
+  const int face[4][2] = {{0, 1}, {1, 3}, {3, 2}, {2, 0}};
+  for (int f = 0; f < 4; f++) {
+    const float* a = c[face[f][0]]; const float* b = c[face[f][1]];
+    pl.n[f][0] = (double)a[1] * b[2] - (double)a[2] * b[1];
+    pl.n[f][1] = (double)a[2] * b[0] - (double)a[0] * b[2];
+    pl.n[f][2] = (double)a[0] * b[1] - (double)a[1] * b[0];
+    const double sgn = pl.n[f][0] * ctr[0] + pl.n[f][1] * ctr[1] + pl.n[f][2] * ctr[2];
+    if (sgn < 0) { pl.n[f][0] = -pl.n[f][0]; pl.n[f][1] = -pl.n[f][1]; pl.n[f][2] = -pl.n[f][2]; }
+  }
+  return true;
 }
 
 /* exact kNN lists of every point of the cloud: idx/d2 are [n][k], k <= min(n, KNN_MAX_K); q4 = xyz by original row */
@@ -171,35 +216,8 @@ ppf_status ppf_prep_crop(const ppf_cloud* in, const int* box_xywh, const float* 
   ppf_status s = prep_check("ppf_prep_crop", in, out);
   if (s != PPF_OK) return s;
   if (!box_xywh || !depth || !intr || depth_rows <= 0 || depth_cols <= 0) return fail(PPF_ERR_INVALID, "ppf_prep_crop: bad argument");
-  double left = box_xywh[0] - 30; if (left < 0) left = 0;
-  double top = box_xywh[1] - 30; if (top < 0) top = 0;
-  double right = box_xywh[0] + box_xywh[2] + 30; if (right >= depth_cols) right = depth_cols - 1;
-  double bottom = box_xywh[1] + box_xywh[3] + 30; if (bottom >= depth_rows) bottom = depth_rows - 1;
-  const int il = (int)left, it = (int)top, ir = (int)right, ib = (int)bottom;
-  if (il < 0 || it < 0 || ir >= depth_cols || ib >= depth_rows || il > ir || it > ib) return fail(PPF_ERR_INVALID, "ppf_prep_crop: box outside the depth image");
-  const float d1 = depth[(size_t)it * depth_cols + il], d2 = depth[(size_t)it * depth_cols + ir],
-              d3 = depth[(size_t)ib * depth_cols + il], d4 = depth[(size_t)ib * depth_cols + ir];
-  const float davg = (d1 + d2 + d3 + d4) / 4;
-  const double fx = intr[0], fy = intr[1], ppx = intr[2], ppy = intr[3];
-  auto back_project = [&](int u, int v, float* o) { /* Camera::back_projection_bbox, Camera.h:50-61 */
-    o[0] = (float)((double)((float)((double)u - ppx) * davg) / fx);
-    o[1] = (float)((double)((float)((double)v - ppy) * davg) / fy);
-    o[2] = (float)((double)davg + 0.15); /* corners pushed 0.15 m back, :292-295 */
-  };
-  float c[4][3];
-  back_project(il, it, c[0]); back_project(il, ib, c[1]); back_project(ir, it, c[2]); back_project(ir, ib, c[3]);
   CropPlanes pl;
-  pl.z_base = c[0][2];
-  const double ctr[3] = {((double)c[0][0] + c[1][0] + c[2][0] + c[3][0]) / 4, ((double)c[0][1] + c[1][1] + c[2][1] + c[3][1]) / 4, (double)pl.z_base};
-  const int face[4][2] = {{0, 1}, {1, 3}, {3, 2}, {2, 0}};
-  for (int f = 0; f < 4; f++) {
-    const float* a = c[face[f][0]]; const float* b = c[face[f][1]];
-    pl.n[f][0] = (double)a[1] * b[2] - (double)a[2] * b[1];
-    pl.n[f][1] = (double)a[2] * b[0] - (double)a[0] * b[2];
-    pl.n[f][2] = (double)a[0] * b[1] - (double)a[1] * b[0];
-    const double sgn = pl.n[f][0] * ctr[0] + pl.n[f][1] * ctr[1] + pl.n[f][2] * ctr[2];
-    if (sgn < 0) { pl.n[f][0] = -pl.n[f][0]; pl.n[f][1] = -pl.n[f][1]; pl.n[f][2] = -pl.n[f][2]; }
-  }
+  if (!crop_planes(box_xywh, depth, depth_rows, depth_cols, intr, &pl)) return fail(PPF_ERR_INVALID, "ppf_prep_crop: box outside the depth image");
   DevBuf<uint32_t> flags;
   HIPCHK(flags.reserve((size_t)in->n + 1));
   HIPCHK(hipMemset(flags.p + in->n, 0, sizeof(uint32_t)));
