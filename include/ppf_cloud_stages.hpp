@@ -9,6 +9,7 @@
  *   EdgeExtraction     :406-427  ->  Cloud::edges(curvatureThreshold)
  *   PointCloudXYZNormalToMat :163-190 -> Cloud::toMat()   (an N x 6 ppf_match_3d::Mat for PPF3DDetector / ICP)
  *   all of the above for every box of a frame  ->  Cloud::prepareFrame(boxes, n, depth, ...)  (one (object, edge) pair per box)
+ *   Matching_S2B + ICP for every detection     ->  Cloud::matchFrame(models, modelClouds, dets, ...)  (ICP in one launch sequence)
  *
  * Every stage returns a new Cloud that stays in HBM; only toMat()/download() copy to the host.  A maintainer replaces
  * the bodies of those CloudProcessor methods by these one-liners; pcl::PointCloud<PointXYZ> goes
@@ -90,6 +91,49 @@ class Cloud {
     return out;
   }
 
+  /* Matching_S2B (edge cloud given) or Matching, then the ICP of the top poses, for every detection of a frame in one call
+   * (ppf_match_frame): the ICP of all detections runs as one launch sequence.  models[i] == 0 or an empty object cloud
+   * skips detection i (its list stays empty); modelClouds[i] is the model's full cloud (ICP source, Cloud::fromMat of the
+   * trained Mat).  Returns per detection its refined poses in match rank order (the reference keeps element 0), each
+   * bit-identical to match + ICP of that detection alone.  Match parameters: ppf_default_match_params with the two
+   * relative steps; ICP: ppf_default_icp_params. */
+  static std::vector<std::vector<ppf_match_3d::Pose3D> > matchFrame(const std::vector<const ppf_model*>& models,
+                                                                     const std::vector<const Cloud*>& modelClouds,
+                                                                     const std::vector<std::pair<Cloud, Cloud> >& dets,
+                                                                     double relativeSceneSampleStep = 0.05, double relativeSceneDistance = 0.05,
+                                                                     int top = 5, std::vector<std::vector<int> >* iterations = 0,
+                                                                     ppf_match_frame_stats* stats = 0) {
+    const size_t nd = dets.size();
+    if (models.size() != nd || modelClouds.size() != nd)
+      throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::matchFrame: one model and one model cloud per detection");
+    std::vector<ppf_frame_detection> d(nd + 1);
+    for (size_t i = 0; i < nd; i++) {
+      const bool live = models[i] && modelClouds[i] && dets[i].first.handle();
+      d[i].model = live ? models[i] : 0;
+      d[i].model_cloud = live ? modelClouds[i]->handle() : 0;
+      d[i].scene = live ? dets[i].first.handle() : 0;
+      d[i].edge = live ? dets[i].second.handle() : 0;
+    }
+    ppf_match_params mp;
+    ppf_default_match_params(&mp);
+    mp.relative_scene_sample_step = relativeSceneSampleStep;
+    mp.relative_scene_distance = relativeSceneDistance;
+    ppf_icp_params ip;
+    ppf_default_icp_params(&ip);
+    const size_t t = top > 0 ? (size_t)top : 0;
+    std::vector<ppf_pose> poses(nd * t + 1);
+    std::vector<int> n(nd + 1, 0);
+    std::vector<int32_t> it(nd * t + 1, 0);
+    ppf_match_3d::check(ppf_match_frame(&d[0], (int)nd, &mp, &ip, top, &poses[0], &n[0], &it[0], stats));
+    std::vector<std::vector<ppf_match_3d::Pose3D> > out(nd);
+    if (iterations) iterations->assign(nd, std::vector<int>());
+    for (size_t i = 0; i < nd; i++)
+      for (int k = 0; k < n[i]; k++) {
+        out[i].push_back(ppf_match_3d::Pose3D(poses[i * t + (size_t)k]));
+        if (iterations) (*iterations)[i].push_back(it[i * t + (size_t)k]);
+      }
+    return out;
+  }
   /* the N x 6 CV_32FC1-shaped Mat of PointCloudXYZNormalToMat (normals re-normalised) */
   ppf_match_3d::Mat toMat() const {
     ppf_cloud* o = nullptr;

@@ -31,6 +31,8 @@
  *   ppf_prep_crop / _voxel_grid /   CloudProcessor::SceneCropping :263, Subsampling :361, OutlierProcessing :341,
  *   _outlier_removal / _normals /   NormalEstimation :381, EdgeExtraction :406, PointCloudXYZNormalToMat :163
  *   _edges / _to_mat (+ppf_cloud_*) (the PCL stages that produce the matcher's input)
+ *   ppf_match_frame                 match / match_S2B + ICP of every detection of a frame, ICP in one launch sequence
+ *                                   (YOLO_cropping_ppf_test.cpp:88-127, CloudProcessing.h:495-523)
  *   ppf_prep_frame                  the same six stages for all of a frame's boxes at once (CloudProcessing.h:263-427
  *                                   return one cloud per detection)
  *
@@ -438,6 +440,36 @@ void ppf_default_frame_params(ppf_frame_params* p);
 ppf_status ppf_prep_frame(const ppf_cloud* scene, const int* boxes_xywh, int n_boxes, const float* depth, int depth_rows,
                           int depth_cols, const double* intr, const ppf_frame_params* params, ppf_cloud** objects,
                           ppf_cloud** edges, int32_t* stage_rows, ppf_frame_stats* stats);
+
+/* ---- match + ICP for every detection of a frame, the ICP of all detections in one launch sequence ------------- */
+typedef struct ppf_frame_detection {
+  const ppf_model* model;       /* NULL: detection skipped (n_out[i] = 0) */
+  const ppf_cloud* model_cloud; /* ICP source: the model's full cloud (what registerModelToScene gets as models[id]) */
+  const ppf_cloud* scene;       /* the detection's object cloud, e.g. ppf_prep_frame objects[i] */
+  const ppf_cloud* edge;        /* NULL: match; else match_S2B against this edge cloud */
+} ppf_frame_detection;
+
+typedef struct ppf_match_frame_stats {
+  int32_t n_dets, n_matched, n_icp_jobs;
+  int32_t n_icp_launches;   /* kernel launches of the ICP phase */
+  int32_t n_icp_passes;     /* (neighbour search, tail) pairs launched, summed over levels */
+  int32_t n_host_syncs;     /* blocking read-backs + stream/device synchronisations of the whole call */
+  float ms_wall, ms_match, ms_icp;
+  int32_t reserved[4];
+} ppf_match_frame_stats;
+
+/* For every detection: match (or match_S2B) with `mp`, then ICP with `ip` of its first min(top, matches) clustered
+ * poses. out is [n_dets][top] poses in match rank order, refined (the reference returns row 0). n_out[i] is the
+ * count per detection. icp_iterations is [n_dets][top] and may be NULL; so may stats.
+ * Each detection's rows are bit-identical to ppf_match_clouds followed by ppf_icp_refine_clouds on the same clouds.
+ * Limits: n_dets 0..256, top 1..16.  A detection whose scene (or given edge cloud) has no rows is skipped like one
+ * without a model.  Argument errors are reported before any device work; on any error every n_out[i] is 0.
+ * The ICP poses of all detections advance through one launch sequence of up to 256 poses (its launch count does not
+ * depend on how many detections share it); a call with more poses runs sequences of 256 one after another.  The match
+ * phase reads back per detection.  ip->flags PPF_ICP_LEGACY: detection after detection, same results. */
+ppf_status ppf_match_frame(const ppf_frame_detection* dets, int n_dets, const ppf_match_params* mp,
+                           const ppf_icp_params* ip, int top, ppf_pose* out, int* n_out, int32_t* icp_iterations,
+                           ppf_match_frame_stats* stats);
 
 #ifdef __cplusplus
 }

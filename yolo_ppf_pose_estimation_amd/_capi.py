@@ -98,6 +98,16 @@ class FrameStats(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+class FrameDetection(C.Structure):
+    _fields_ = [("model", C.c_void_p), ("model_cloud", C.c_void_p), ("scene", C.c_void_p), ("edge", C.c_void_p)]
+
+
+class MatchFrameStats(C.Structure):
+    _fields_ = [("n_dets", C.c_int32), ("n_matched", C.c_int32), ("n_icp_jobs", C.c_int32), ("n_icp_launches", C.c_int32),
+                ("n_icp_passes", C.c_int32), ("n_host_syncs", C.c_int32), ("ms_wall", C.c_float), ("ms_match", C.c_float),
+                ("ms_icp", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
 # every symbol include/ppf_hip.h declares (tests/test_capi_symbols.py checks the header against this)
 _SIGNATURES = {
     "ppf_default_train_params": (None, [C.POINTER(TrainParams)]),
@@ -181,6 +191,8 @@ _SIGNATURES = {
                                         C.POINTER(C.c_int)]),
     "ppf_prep_knn": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ppf_default_frame_params": (None, [C.POINTER(FrameParams)]),
+    "ppf_match_frame": (C.c_int, [C.POINTER(FrameDetection), C.c_int, C.POINTER(MatchParams), C.POINTER(IcpParams), C.c_int,
+                                  C.POINTER(Pose), C.POINTER(C.c_int), C.POINTER(C.c_int32), C.POINTER(MatchFrameStats)]),
     "ppf_prep_frame": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
                                  C.POINTER(FrameParams), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
                                  C.POINTER(FrameStats)]),

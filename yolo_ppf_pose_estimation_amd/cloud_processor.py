@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _capi
-from ._capi import FrameParams, FrameStats, IcpParams, Pose, PPFError, check, lib
+from ._capi import FrameDetection, FrameParams, FrameStats, IcpParams, MatchFrameStats, Pose, PPFError, check, lib
 from .detector import ICP, PPF3DDetector, Pose3D
 
 
@@ -155,6 +155,7 @@ class CloudProcessor:
         self.edge_mats: List[DeviceCloud] = []
         self.stage_rows: Optional[np.ndarray] = None
         self.frame_stats: Dict[str, object] = {}
+        self.match_frame_stats: Dict[str, float] = {}  # ppf_match_frame counters of the last MatchFrame (summed over its calls)
 
     # ---- the PCL half -------------------------------------------------------------------------------------
     def SceneCropping(self, CameraIntr) -> List[DeviceCloud]:
@@ -203,18 +204,62 @@ class CloudProcessor:
         return pairs
 
     def MatchFrame(self, labels: Sequence[Optional[str]], relativeSceneSampleStep: float = 0.05,
-                   relativeSceneDistance: float = 0.05) -> List[Optional[Pose3D]]:
+                   relativeSceneDistance: float = 0.05, one_pass: bool = True) -> List[Optional[Pose3D]]:
         """Matching_S2B (+ ICP of the top 5) of every prepared detection against the model named by labels[i], on the
         resident clouds of PrepareFrame; one pose per detection, None where the label is None, the detection kept no
-        points or no pose was found.  Detections are refined one after another."""
+        points or no pose was found.  By default one ppf_match_frame call matches every detection and refines the top
+        poses of all of them in one ICP launch sequence (``timings["match_frame"]``, ``match_frame_stats``);
+        ``one_pass=False`` refines detections one after another through Matching_S2B.  Same poses either way."""
         if len(labels) != len(self.object_mats):
             raise PPFError(_capi.PPF_ERR_INVALID, f"{len(labels)} labels for {len(self.object_mats)} prepared detections")
+        if one_pass:
+            return self._match_frame(labels, relativeSceneSampleStep, relativeSceneDistance)
         out: List[Optional[Pose3D]] = []
         for name, obj, edge in zip(labels, self.object_mats, self.edge_mats):
             if name is None or len(obj) == 0:
                 out.append(None)
                 continue
             out.append(self.Matching_S2B(name, obj, edge, relativeSceneSampleStep, relativeSceneDistance))
+        return out
+
+    def _match_frame(self, labels, step, dist, top: int = 5) -> List[Optional[Pose3D]]:
+        dets = (FrameDetection * max(len(labels), 1))()
+        groups: Dict[bytes, tuple] = {}  # detections whose detectors share match parameters go into one call
+        for i, (name, obj, edge) in enumerate(zip(labels, self.object_mats, self.edge_mats)):
+            if name is None or len(obj) == 0:
+                continue
+            idx = self.label_to_id[name]
+            if not self.if_trained[idx]:
+                raise PPFError(_capi.PPF_ERR_NOT_TRAINED, f"Model [{name}] not trained yet.")
+            det = self.detectors[idx]
+            if idx not in self._model_clouds:
+                self._model_clouds[idx] = DeviceCloud.upload(self.models[idx])
+            dets[i].model = det._model.ptr
+            dets[i].model_cloud = self._model_clouds[idx]._ptr
+            dets[i].scene = obj._ptr
+            dets[i].edge = edge._ptr if edge is not None else None
+            mp = det._params(step, dist, False)
+            groups.setdefault(bytes(mp), (mp, []))[1].append(i)
+        prm = IcpParams()
+        lib().ppf_default_icp_params(C.byref(prm))
+        out: List[Optional[Pose3D]] = [None] * len(labels)
+        t0 = time.perf_counter()
+        self.match_frame_stats = {}
+        for mp, members in groups.values():
+            sub = (FrameDetection * len(labels))()
+            for i in members:
+                sub[i] = dets[i]
+            poses = (Pose * (len(labels) * top))()
+            n_out = (C.c_int * len(labels))()
+            st = MatchFrameStats()
+            check(lib().ppf_match_frame(sub, len(labels), C.byref(mp), C.byref(prm), top, poses, n_out, None, C.byref(st)))
+            for i in members:
+                if n_out[i] > 0:
+                    out[i] = Pose3D(poses[i * top])
+            for f, _ in MatchFrameStats._fields_:
+                if f != "reserved":
+                    self.match_frame_stats[f] = self.match_frame_stats.get(f, 0) + getattr(st, f)
+        self.timings["match_frame"] = time.perf_counter() - t0
         return out
 
     # ---- the PPF half -------------------------------------------------------------------------------------

@@ -25,6 +25,17 @@ ppf_status fail(ppf_status st, const char* fmt, ...) {
   return st;
 }
 
+/* blocking waits of the calling thread on the match path (ppf_match_frame reports the ones its call made) */
+thread_local int g_host_syncs = 0;
+inline hipError_t host_stream_sync(hipStream_t st) {
+  g_host_syncs++;
+  return hipStreamSynchronize(st);
+}
+inline hipError_t host_read(void* dst, const void* src, size_t bytes) {
+  g_host_syncs++;
+  return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+}
+
 #define HIPCHK(expr)                                                                                       \
   do {                                                                                                     \
     hipError_t e__ = (expr);                                                                               \

@@ -54,7 +54,7 @@ ppf_status device_exclusive_scan(const uint32_t* in, uint32_t* out, size_t n, hi
     if (s != PPF_OK) return s;
     k_scan_add<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(out, sums_scan.p, n);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st)); /* sums buffers die at scope exit */
+    HIPCHK(host_stream_sync(st)); /* sums buffers die at scope exit */
   }
   return PPF_OK;
 }
@@ -89,7 +89,7 @@ struct CloudDev {
     for (int i = 0; i < rows; i++)
       for (int k = 0; k < 6; k++) soa[(size_t)k * pitch + i] = h_src[(size_t)i * 6 + k];
     HIPCHK(hipMemcpyAsync(buf.p, soa.data(), soa.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(host_stream_sync(st));
     return PPF_OK;
   }
 };
@@ -124,11 +124,11 @@ ppf_status sort_segments(DevBuf<uint32_t>& keys, DevBuf<uint32_t>& vals, DevBuf<
   if (s != PPF_OK) return s;
   uint32_t n_rows = 0;
   HIPCHK(hipMemcpyAsync(&n_rows, segid.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(host_stream_sync(st));
   HIPCHK(starts.reserve(std::max<uint32_t>(n_rows, 1)));
   k_seg_starts<<<dim3(nb256), dim3(256), 0, st>>>(flags.p, segid.p, n, starts.p);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st)); /* flags/segid die at scope exit */
+  HIPCHK(host_stream_sync(st)); /* flags/segid die at scope exit */
   *vals_sorted = va;
   *n_runs = n_rows;
   return PPF_OK;
@@ -168,7 +168,7 @@ ppf_status device_sample_cloud(const float* d_src, int n, int stride, int noff, 
     host_rows->resize((size_t)n_rows * 6);
     if (n_rows) HIPCHK(hipMemcpyAsync(host_rows->data(), aos.p, host_rows->size() * sizeof(float), hipMemcpyDeviceToHost, st));
   }
-  HIPCHK(hipStreamSynchronize(st)); /* the scratch buffers above die at scope exit */
+  HIPCHK(host_stream_sync(st)); /* the scratch buffers above die at scope exit */
   return PPF_OK;
 }
 

@@ -267,53 +267,128 @@ struct IcpBatchScratch {
   DevBuf<uint32_t> g_start, g_cur, g_box1u, own_a;
   DevBuf<float> bb_parts;
   DevBuf<IcpState2> state;
+  DevBuf<unsigned char> tables;  /* the call's IcpJobDesc table, then its IcpLevelDesc table */
+  int host_jobs = 0, host_table_bytes = 0; /* capacity of the pinned buffers below */
   int* h_done = nullptr;        /* pinned: one flag per job, written by the kernels */
   IcpState2* h_state = nullptr; /* pinned: the jobs' loop states, written by the kernels when a level ends */
   unsigned long long* h_ticks = nullptr; /* pinned: finished k_icp2_tail workgroups of the running call */
+  unsigned char* h_tables = nullptr;     /* pinned staging of `tables` */
   ~IcpBatchScratch() {
     if (h_done) (void)hipHostFree(h_done);
     if (h_state) (void)hipHostFree(h_state);
     if (h_ticks) (void)hipHostFree(h_ticks);
+    if (h_tables) (void)hipHostFree(h_tables);
   }
 };
 
-/* registerModelToScene for `jobs` initial poses at once (init_poses NULL: one registration from the identity): every
- * launch covers all jobs, an iteration is two launches (k_icp2_nn, k_icp2_tail), the host keeps PPF_ICP_BATCH2 of them in
- * the stream ahead of the device and reads the jobs' done flags whenever one reports.  Everything runs on `st`. */
-ppf_status icp_register_batch(const float* d_src, int n, int sstride, int snoff, const float* d_dst, int nd_all, int dstride, int dnoff,
-                              const ppf_icp_params& prm, const double* const* init_poses, int jobs, IcpBatchScratch& sc, hipStream_t st,
-                              double* poses_out /* jobs x 16 */, double* residuals, int* iters_total) {
-  const size_t chunks_src = ((size_t)n + ICP_CHUNK - 1) / ICP_CHUNK, chunks_dst = ((size_t)nd_all + ICP_CHUNK - 1) / ICP_CHUNK;
+/* one registration of a batched call: its clouds (rows of stride floats, normal at noff) and its initial pose (NULL: the
+ * identity) */
+struct IcpJobSpec {
+  const float* src;
+  int n, sstride, snoff;
+  const float* dst;
+  int nd_all, dstride, dnoff;
+  const double* init;
+};
+
+/* what a batched call enqueued (ppf_match_frame_stats) */
+struct IcpRunCount {
+  int launches = 0, passes = 0, syncs = 0;
+};
+
+/* ICP::registerModelToScene's level schedule for a source of n rows and a destination of nd_all rows */
+IcpLevelDesc icp_level_desc(int n, int nd_all, int level) {
+  const double div = std::pow(2.0, (double)level);
+  const int num_samples = (int)icp_round((double)n / div);
+  const int step = std::max(1, (int)icp_round((double)n / (double)std::max(num_samples, 1)));
+  IcpLevelDesc L;
+  memset(&L, 0, sizeof(L));
+  L.step = step;
+  L.ns = (n + step - 1) / step;
+  L.nd = (nd_all + step - 1) / step;
+  L.step_shift = -1;
+  if ((step & (step - 1)) == 0) { L.step_shift = 0; while ((1 << L.step_shift) < step) L.step_shift++; }
+  L.staged = L.ns <= 32768 ? 1 : 0; /* the level's distances fit LDS (4 bytes each): the selection passes read them there */
+  return L;
+}
+
+/* registerModelToScene for `jobs` (<= ICP_GROUP_JOBS) registrations at once, each with its own clouds and initial pose:
+ * every launch covers all jobs (sized for the largest), an iteration is two launches (k_icp2_nn, k_icp2_tail), the host
+ * keeps PPF_ICP_BATCH2 of them in the stream ahead of the device and reads the jobs' done flags whenever one reports.  The
+ * level loop is lock-step over the jobs: a level ends when every job is done with it.  Everything runs on `st`. */
+ppf_status icp_register_group(const IcpJobSpec* specs, int jobs, const ppf_icp_params& prm, IcpBatchScratch& sc, hipStream_t st,
+                              double* poses_out /* jobs x 16 */, double* residuals, int* iters_total, IcpRunCount& cnt) {
+  const int nl_levels = std::max(prm.num_levels, 0);
   const size_t J = (size_t)jobs;
-  IcpBatch B;
-  memset(&B, 0, sizeof(B));
-  B.p_sel = (size_t)std::min(n, nd_all);
-  B.p_parts = ((size_t)std::min(n, nd_all) + ICP_CHUNK - 1) / ICP_CHUNK * ICP_ENTRIES;
-  B.p_sums = chunks_src * 3;
-  B.p_sumd = chunks_dst * 3;
-  HIPCHK(sc.src0.reserve(J * n * 6));
-  HIPCHK(sc.src_pct.reserve(J * n * 6));
-  HIPCHK(sc.dst0.reserve(J * nd_all * 6));
-  HIPCHK(sc.best.reserve(J * n));
-  HIPCHK(sc.owner.reserve(J * nd_all));
-  HIPCHK(sc.sel.reserve(J * B.p_sel));
-  HIPCHK(sc.parts.reserve(J * B.p_parts));
-  HIPCHK(sc.sum_src.reserve(J * B.p_sums));
-  HIPCHK(sc.sum_dst.reserve(J * B.p_sumd));
-  HIPCHK(sc.g_pts.reserve(J * nd_all));
+  const size_t levels_off = J * sizeof(IcpJobDesc);
+  const size_t table_bytes = levels_off + J * (size_t)std::max(nl_levels, 1) * sizeof(IcpLevelDesc);
+  static_assert(sizeof(IcpJobDesc) % 16 == 0, "the level table follows the job table 16-byte aligned");
+  if (sc.host_jobs < jobs) {
+    if (sc.h_done) { (void)hipHostFree(sc.h_done); sc.h_done = nullptr; }
+    if (sc.h_state) { (void)hipHostFree(sc.h_state); sc.h_state = nullptr; }
+    sc.host_jobs = 0;
+    HIPCHK(hipHostMalloc((void**)&sc.h_done, std::max(jobs, ICP_MAX_JOBS) * sizeof(int), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc((void**)&sc.h_state, std::max(jobs, ICP_MAX_JOBS) * sizeof(IcpState2), hipHostMallocDefault));
+    sc.host_jobs = std::max(jobs, ICP_MAX_JOBS);
+  }
+  if ((size_t)sc.host_table_bytes < table_bytes) {
+    if (sc.h_tables) { (void)hipHostFree(sc.h_tables); sc.h_tables = nullptr; }
+    sc.host_table_bytes = 0;
+    HIPCHK(hipHostMalloc((void**)&sc.h_tables, table_bytes, hipHostMallocDefault));
+    sc.host_table_bytes = (int)table_bytes;
+  }
+  if (!sc.h_ticks) HIPCHK(hipHostMalloc((void**)&sc.h_ticks, 64, hipHostMallocDefault));
+  /* the tables: every job's place in the shared scratch arrays, its initial pose, its level schedule */
+  IcpJobDesc* jd = reinterpret_cast<IcpJobDesc*>(sc.h_tables);
+  IcpLevelDesc* ld = reinterpret_cast<IcpLevelDesc*>(sc.h_tables + levels_off);
+  size_t t_src = 0, t_dst = 0, t_sel = 0, t_parts = 0, t_sums = 0, t_sumd = 0;
+  int max_n = 0, max_nd = 0, max_chunks = 0, max_rows_blocks = 0, max_dst_blocks = 0;
+  for (int j = 0; j < jobs; j++) {
+    const IcpJobSpec& S = specs[j];
+    IcpJobDesc& D = jd[j];
+    memset(&D, 0, sizeof(D));
+    D.src = S.src; D.dst = S.dst;
+    D.n = S.n; D.sstride = S.sstride; D.snoff = S.snoff; D.nd_all = S.nd_all; D.dstride = S.dstride; D.dnoff = S.dnoff;
+    D.has_init = S.init ? 1 : 0;
+    for (int k = 0; k < 16; k++) D.T0[k] = S.init ? S.init[k] : ((k % 5 == 0) ? 1.0 : 0.0);
+    const size_t chunks_src = ((size_t)S.n + ICP_CHUNK - 1) / ICP_CHUNK, chunks_dst = ((size_t)S.nd_all + ICP_CHUNK - 1) / ICP_CHUNK;
+    const size_t m = (size_t)std::min(S.n, S.nd_all);
+    D.o_src0 = t_src * 6; D.o_best = t_src; D.o_dst0 = t_dst * 6; D.o_owner = t_dst;
+    D.o_sel = t_sel; D.o_parts = t_parts; D.o_sums = t_sums; D.o_sumd = t_sumd;
+    t_src += (size_t)S.n; t_dst += (size_t)S.nd_all; t_sel += m; t_parts += (m + ICP_CHUNK - 1) / ICP_CHUNK * ICP_ENTRIES;
+    t_sums += chunks_src * 3; t_sumd += chunks_dst * 3;
+    max_n = std::max(max_n, S.n); max_nd = std::max(max_nd, S.nd_all);
+    max_chunks = std::max(max_chunks, (int)(chunks_src + chunks_dst));
+    const int nb_dst = (S.nd_all + ICP_ROWS_BLOCK - 1) / ICP_ROWS_BLOCK, nb_src = (S.n + ICP_ROWS_BLOCK - 1) / ICP_ROWS_BLOCK;
+    max_rows_blocks = std::max(max_rows_blocks, nb_dst + nb_src);
+    max_dst_blocks = std::max(max_dst_blocks, nb_dst);
+    for (int level = 0; level < nl_levels; level++) ld[(size_t)j * nl_levels + level] = icp_level_desc(S.n, S.nd_all, level);
+  }
+  HIPCHK(sc.src0.reserve(t_src * 6));
+  HIPCHK(sc.src_pct.reserve(t_src * 6));
+  HIPCHK(sc.dst0.reserve(t_dst * 6));
+  HIPCHK(sc.best.reserve(t_src));
+  HIPCHK(sc.owner.reserve(t_dst));
+  HIPCHK(sc.sel.reserve(t_sel));
+  HIPCHK(sc.parts.reserve(t_parts));
+  HIPCHK(sc.sum_src.reserve(t_sums));
+  HIPCHK(sc.sum_dst.reserve(t_sumd));
+  HIPCHK(sc.g_pts.reserve(t_dst));
   HIPCHK(sc.g_start.reserve(J * (ICP_LEAVES + 64)));
   HIPCHK(sc.g_cur.reserve(J * ICP_LEAVES));
   HIPCHK(sc.g_box2.reserve(J * ICP_LEAVES * 2));
   HIPCHK(sc.g_box1u.reserve(J * 64 * 8));
-  HIPCHK(sc.own_a.reserve(J * nd_all));
-  HIPCHK(sc.bb_parts.reserve(J * B.p_sumd * 2));
-  HIPCHK(sc.state.reserve(ICP_MAX_JOBS));
-  if (!sc.h_done) HIPCHK(hipHostMalloc((void**)&sc.h_done, ICP_MAX_JOBS * sizeof(int), hipHostMallocDefault));
-  if (!sc.h_state) HIPCHK(hipHostMalloc((void**)&sc.h_state, ICP_MAX_JOBS * sizeof(IcpState2), hipHostMallocDefault));
-  if (!sc.h_ticks) HIPCHK(hipHostMalloc((void**)&sc.h_ticks, 64, hipHostMallocDefault));
-  *sc.h_ticks = 0ull; /* no kernel of an earlier call is running: every call ends with all of its launches accounted for */
-  B.src = d_src; B.dst = d_dst;
-  B.n = n; B.sstride = sstride; B.snoff = snoff; B.nd_all = nd_all; B.dstride = dstride; B.dnoff = dnoff;
+  HIPCHK(sc.own_a.reserve(t_dst));
+  HIPCHK(sc.bb_parts.reserve(t_sumd * 2));
+  HIPCHK(sc.state.reserve(std::max<size_t>(J, ICP_MAX_JOBS)));
+  HIPCHK(sc.tables.reserve(table_bytes));
+  *sc.h_ticks = 0ull; /* no kernel of an earlier call is running: every call ends with all of its launches accounted for, and an
+                         error return drains the stream first (icp_batch_run) */
+  IcpBatch B;
+  memset(&B, 0, sizeof(B));
+  B.jobs = reinterpret_cast<const IcpJobDesc*>(sc.tables.p);
+  B.levels = reinterpret_cast<const IcpLevelDesc*>(sc.tables.p + levels_off);
+  B.num_levels = nl_levels;
   B.src0 = sc.src0.p; B.dst0 = sc.dst0.p; B.src_pct = sc.src_pct.p;
   B.best = sc.best.p; B.owner = sc.owner.p; B.sel = sc.sel.p;
   B.parts = sc.parts.p; B.sum_src = sc.sum_src.p; B.sum_dst = sc.sum_dst.p;
@@ -322,28 +397,38 @@ ppf_status icp_register_batch(const float* d_src, int n, int sstride, int snoff,
   B.h_done = sc.h_done;
   B.h_ticks = sc.h_ticks;
   B.h_state = sc.h_state;
-  B.has_init = init_poses ? 1 : 0;
-  for (int j = 0; j < jobs; j++)
-    for (int k = 0; k < 16; k++) B.T0[j][k] = init_poses && init_poses[j] ? init_poses[j][k] : ((k % 5 == 0) ? 1.0 : 0.0);
   static std::once_flag once_tail;
   static hipError_t attr_tail = hipSuccess;
   std::call_once(once_tail, [] {
-    attr_tail = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_icp2_tail), hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
+    attr_tail = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_icp2_tail<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
+    if (attr_tail == hipSuccess)
+      attr_tail = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_icp2_tail<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
   });
   HIPCHK(attr_tail);
+  /* one pair of clouds for every job: the per-pass kernels take the geometry from their arguments (IcpUniform) */
+  bool uniform = true;
+  for (int j = 1; j < jobs; j++)
+    uniform &= specs[j].src == specs[0].src && specs[j].n == specs[0].n && specs[j].sstride == specs[0].sstride &&
+               specs[j].snoff == specs[0].snoff && specs[j].dst == specs[0].dst && specs[j].nd_all == specs[0].nd_all &&
+               specs[j].dstride == specs[0].dstride && specs[j].dnoff == specs[0].dnoff;
+  /* the tables go up once, through k_icp2_reset; the pinned staging is not touched again before the call has finished */
+  static_assert(sizeof(IcpLevelDesc) % 16 == 0, "the tables are copied in 16-byte words");
+  B.table_words = (uint32_t)(table_bytes / 16);
+  B.h_tables = reinterpret_cast<const uint4*>(sc.h_tables);
+  B.d_tables = reinterpret_cast<uint4*>(sc.tables.p);
   const unsigned uj = (unsigned)jobs;
   /* the two clouds packed (the source moved by its job's initial pose), centred on the average of the two means, scaled to
    * unit average distance from the origin; the search grid over each job's scene */
   k_icp2_reset<<<dim3(uj, 32), dim3(256), 0, st>>>(B);
-  k_icp2_pack_sums<<<dim3((unsigned)(chunks_src + chunks_dst), uj), dim3(64), 0, st>>>(B);
+  k_icp2_pack_sums<<<dim3((unsigned)max_chunks, uj), dim3(64), 0, st>>>(B);
   k_icp2_mean<<<dim3(uj), dim3(256), 0, st>>>(B);
-  k_icp2_dist_sums<<<dim3((unsigned)(chunks_src + chunks_dst), uj), dim3(64), 0, st>>>(B);
+  k_icp2_dist_sums<<<dim3((unsigned)max_chunks, uj), dim3(64), 0, st>>>(B);
   k_icp2_scale<<<dim3(uj), dim3(256), 0, st>>>(B);
-  const unsigned nb_dst = (unsigned)((nd_all + ICP_ROWS_BLOCK - 1) / ICP_ROWS_BLOCK), nb_src = (unsigned)((n + ICP_ROWS_BLOCK - 1) / ICP_ROWS_BLOCK);
-  k_icp2_rows_count<<<dim3(nb_dst + nb_src, uj), dim3(1024), 0, st>>>(B);
+  k_icp2_rows_count<<<dim3((unsigned)max_rows_blocks, uj), dim3(1024), 0, st>>>(B);
   k_icp2_grid_scan<<<dim3(uj), dim3(1024), 0, st>>>(B);
-  k_icp2_grid_scatter<<<dim3(nb_dst, uj), dim3(1024), 0, st>>>(B);
+  k_icp2_grid_scatter<<<dim3((unsigned)max_dst_blocks, uj), dim3(1024), 0, st>>>(B);
   k_icp2_grid_boxes<<<dim3(ICP_LEAVES / 4, uj), dim3(256), 0, st>>>(B);
+  cnt.launches += 9;
   HIPCHK(hipGetLastError());
   const int robust = prm.rejection_scale > 0 ? 1 : 0;
   unsigned long long tails_launched = 0;
@@ -357,6 +442,7 @@ ppf_status icp_register_batch(const float* d_src, int n, int sstride, int snoff,
       if ((++spins & 0xFFFFu) == 0) {
         const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (waited > 0.05 && hipStreamQuery(st) != hipErrorNotReady) { /* the stream is idle (or broken): nothing more will come */
+          cnt.syncs++;
           HIPCHK(hipStreamSynchronize(st));
           if (*ticks < want) return fail(PPF_ERR_HIP, "ICP: %llu of %llu workgroups reported", (unsigned long long)*ticks, want);
         }
@@ -367,20 +453,32 @@ ppf_status icp_register_batch(const float* d_src, int n, int sstride, int snoff,
     return PPF_OK;
   };
   for (int level = prm.num_levels - 1; level >= 0; level--) {
-    const double div = std::pow(2.0, (double)level);
-    const int num_samples = (int)icp_round((double)n / div);
     const double tol_p = (double)prm.tolerance * (double)(level + 1) * (level + 1);
     const int max_iter = (int)icp_round((double)prm.iterations / (level + 1));
-    const int step = std::max(1, (int)icp_round((double)n / (double)std::max(num_samples, 1)));
-    const int ns = (n + step - 1) / step, nd = (nd_all + step - 1) / step;
-    int step_shift = -1;
-    if ((step & (step - 1)) == 0) { step_shift = 0; while ((1 << step_shift) < step) step_shift++; }
-    k_icp2_level_begin<<<dim3((unsigned)((ns + 255) / 256), uj), dim3(256), 0, st>>>(B, step, ns, tol_p, max_iter, robust, level == 0 ? 1 : 0);
-    const int staged = ns <= 32768 ? 1 : 0; /* the level's distances fit LDS (4 bytes each): the selection passes read them there */
-    const size_t tail_lds = std::max<size_t>(staged ? (size_t)ns * 4 : 0, (size_t)ICP_TAIL_VAL_BYTES);
+    /* launch shapes for the largest job of the level; the dynamic LDS of the tail is the most any job needs */
+    int max_ns = 0;
+    long long sum_ns = 0;
+    size_t tail_lds = (size_t)ICP_TAIL_VAL_BYTES;
+    for (int j = 0; j < jobs; j++) {
+      const IcpLevelDesc& L = ld[(size_t)j * nl_levels + level];
+      max_ns = std::max(max_ns, L.ns);
+      sum_ns += L.ns;
+      tail_lds = std::max(tail_lds, L.staged ? (size_t)L.ns * 4 : (size_t)0);
+    }
+    IcpUniform U;
+    memset(&U, 0, sizeof(U));
+    if (uniform) {
+      const IcpLevelDesc& L = ld[level];
+      U.ns = L.ns; U.nd = L.nd; U.step = L.step; U.step_shift = L.step_shift; U.staged = L.staged;
+      U.n = specs[0].n; U.nd_all = specs[0].nd_all;
+      U.p_sel = (size_t)std::min(specs[0].n, specs[0].nd_all);
+      U.p_parts = (U.p_sel + ICP_CHUNK - 1) / ICP_CHUNK * ICP_ENTRIES;
+    }
+    k_icp2_level_begin<<<dim3((unsigned)((max_ns + 255) / 256), uj), dim3(256), 0, st>>>(B, level, tol_p, max_iter, robust, level == 0 ? 1 : 0);
+    cnt.launches++;
     /* rows per wave of the neighbour search: one, unless that makes more waves than the chip holds several times over */
-    const int nn_rows = (int)std::min<long long>(ICP_NN_ROWS, std::max<long long>(1, ((long long)ns * jobs) / PPF_ICP_NN_WAVES));
-    const unsigned nn_blocks = (unsigned)((ns + 4 * nn_rows - 1) / (4 * nn_rows));
+    const int nn_rows = (int)std::min<long long>(ICP_NN_ROWS, std::max<long long>(1, sum_ns / PPF_ICP_NN_WAVES));
+    const unsigned nn_blocks = (unsigned)((max_ns + 4 * nn_rows - 1) / (4 * nn_rows));
     /* The passes of a level are launched ahead of the device: PPF_ICP_BATCH2 (neighbour search, tail) pairs are in the stream,
      * and every time the oldest of them reports, the next one is launched -- the device never waits for the host between
      * passes (with whole batches it idled ~11 us after every second pass).  Every k_icp2_tail workgroup, whatever it did,
@@ -392,15 +490,23 @@ ppf_status icp_register_batch(const float* d_src, int n, int sstride, int snoff,
     bool first_of_level = true;
     while (true) {
       while (launched < max_iter && launched - reported < (int)PPF_ICP_BATCH2) {
-        /* a pass is launched for the jobs that had not finished the level when the host last looked (all of them at its start) */
+        /* a pass is launched for the jobs that had not finished the level when the host last looked (all of them at its start);
+         * the list travels as a kernel argument, copied at the launch */
         IcpLive live;
         unsigned nl = 0;
         for (int j = 0; j < jobs; j++)
-          if (first_of_level || reinterpret_cast<volatile int*>(sc.h_done)[j] == 0) live.job[nl++] = j;
+          if (first_of_level || reinterpret_cast<volatile int*>(sc.h_done)[j] == 0) live.job[nl++] = (uint16_t)j;
         if (nl == 0) live.job[nl++] = 0; /* cannot happen: the loop ends when every job is done */
-        for (unsigned k = nl; k < (unsigned)ICP_MAX_JOBS; k++) live.job[k] = live.job[0];
-        k_icp2_nn<<<dim3(nn_blocks, nl), dim3(256), 0, st>>>(B, live, ns, nd, step, step_shift, nn_rows, (prm.flags & PPF_ICP_GRID_ALWAYS) ? 0 : ICP_BRUTE_ND);
-        k_icp2_tail<<<dim3(nl), dim3(1024), tail_lds, st>>>(B, live, ns, nd, step, prm.rejection_scale, staged, level == 0 ? 1 : 0);
+        const int brute_nd = (prm.flags & PPF_ICP_GRID_ALWAYS) ? 0 : ICP_BRUTE_ND;
+        if (uniform) {
+          k_icp2_nn<false><<<dim3(nn_blocks, nl), dim3(256), 0, st>>>(B, live, level, U, nn_rows, brute_nd);
+          k_icp2_tail<false><<<dim3(nl), dim3(1024), tail_lds, st>>>(B, live, level, U, prm.rejection_scale, level == 0 ? 1 : 0);
+        } else {
+          k_icp2_nn<true><<<dim3(nn_blocks, nl), dim3(256), 0, st>>>(B, live, level, U, nn_rows, brute_nd);
+          k_icp2_tail<true><<<dim3(nl), dim3(1024), tail_lds, st>>>(B, live, level, U, prm.rejection_scale, level == 0 ? 1 : 0);
+        }
+        cnt.launches += 2;
+        cnt.passes++;
         tails_launched += (unsigned long long)nl;
         due[launched % (PPF_ICP_BATCH2 + 1)] = tails_launched;
         launched++;
@@ -419,7 +525,10 @@ ppf_status icp_register_batch(const float* d_src, int n, int sstride, int snoff,
   /* the passes launched ahead of the last level's end are still in the stream and will report too: the scratch (and its
    * counter) goes back to the pool only when they have */
   if (ppf_status rc = wait_ticks(tails_launched)) return rc;
-  if (!last_level_waited) HIPCHK(hipStreamSynchronize(st)); /* nothing was polled after the last state went out */
+  if (!last_level_waited) { /* nothing was polled after the last state went out */
+    cnt.syncs++;
+    HIPCHK(hipStreamSynchronize(st));
+  }
   for (int j = 0; j < jobs; j++) {
     /* undo centring and scaling: t = t/scale + meanAvg - R*meanAvg */
     const IcpState2& h = sc.h_state[j];
@@ -439,6 +548,23 @@ ppf_status icp_register_batch(const float* d_src, int n, int sstride, int snoff,
   return PPF_OK;
 }
 
+/* all `count` jobs, ICP_GROUP_JOBS at a time (one launch sequence per group, one group after the other).  On an error the
+ * stream is drained before returning: passes launched ahead would otherwise still count into the scratch's pinned
+ * counter and write its flags and states after the scratch has gone back to its pool. */
+ppf_status icp_register_batch(const IcpJobSpec* specs, int count, const ppf_icp_params& prm, IcpBatchScratch& sc, hipStream_t st,
+                              double* poses_out, double* residuals, int* iters_total, IcpRunCount& cnt) {
+  for (int g0 = 0; g0 < count; g0 += ICP_GROUP_JOBS) {
+    const int g = std::min(ICP_GROUP_JOBS, count - g0);
+    const ppf_status s = icp_register_group(specs + g0, g, prm, sc, st, poses_out + (size_t)g0 * 16, residuals ? residuals + g0 : nullptr,
+                                            iters_total ? iters_total + g0 : nullptr, cnt);
+    if (s != PPF_OK) {
+      (void)hipStreamSynchronize(st);
+      return s;
+    }
+  }
+  return PPF_OK;
+}
+
 /* one process-wide scratch for the batched path (buffers only grow); a second concurrent caller works on a private one */
 struct IcpBatchPool {
   std::mutex mu;
@@ -447,22 +573,29 @@ struct IcpBatchPool {
 };
 IcpBatchPool& g_icp_batch_pool = *new IcpBatchPool(); /* never destroyed: nothing is freed after the HIP runtime has shut down */
 
-ppf_status icp_batch_run(const float* d_src, int n, int sstride, int snoff, const float* d_dst, int nd_all, int dstride, int dnoff,
-                         const ppf_icp_params& prm, const double* const* init_poses, int jobs, hipStream_t st, double* poses_out,
-                         double* residuals, int* iters_total) {
+ppf_status icp_batch_run_jobs(const IcpJobSpec* specs, int count, const ppf_icp_params& prm, hipStream_t st, double* poses_out,
+                              double* residuals, int* iters_total, IcpRunCount& cnt) {
   std::unique_lock<std::mutex> lock(g_icp_batch_pool.mu, std::try_to_lock);
   int dev = 0;
   HIPCHK(hipGetDevice(&dev));
   if (lock.owns_lock() && (g_icp_batch_pool.device == dev || g_icp_batch_pool.device < 0)) {
     g_icp_batch_pool.device = dev;
-    return icp_register_batch(d_src, n, sstride, snoff, d_dst, nd_all, dstride, dnoff, prm, init_poses, jobs, g_icp_batch_pool.sc, st,
-                              poses_out, residuals, iters_total);
+    return icp_register_batch(specs, count, prm, g_icp_batch_pool.sc, st, poses_out, residuals, iters_total, cnt);
   }
   IcpBatchScratch priv;
-  const ppf_status s = icp_register_batch(d_src, n, sstride, snoff, d_dst, nd_all, dstride, dnoff, prm, init_poses, jobs, priv, st, poses_out,
-                                          residuals, iters_total);
+  const ppf_status s = icp_register_batch(specs, count, prm, priv, st, poses_out, residuals, iters_total, cnt);
   (void)hipStreamSynchronize(st); /* the private scratch goes back to the block cache */
   return s;
+}
+
+/* `jobs` initial poses against one pair of clouds (init_poses NULL: one registration from the identity) */
+ppf_status icp_batch_run(const float* d_src, int n, int sstride, int snoff, const float* d_dst, int nd_all, int dstride, int dnoff,
+                         const ppf_icp_params& prm, const double* const* init_poses, int jobs, hipStream_t st, double* poses_out,
+                         double* residuals, int* iters_total) {
+  IcpJobSpec specs[ICP_MAX_JOBS];
+  for (int j = 0; j < jobs; j++) specs[j] = IcpJobSpec{d_src, n, sstride, snoff, d_dst, nd_all, dstride, dnoff, init_poses ? init_poses[j] : nullptr};
+  IcpRunCount cnt;
+  return icp_batch_run_jobs(specs, jobs, prm, st, poses_out, residuals, iters_total, cnt);
 }
 
 ppf_status icp_check(const char* who, const void* src, int n, int sstride, int snoff, const void* dst, int nd, int dstride, int dnoff,

@@ -672,9 +672,12 @@ __global__ __launch_bounds__(1024) void k_icp_level_small(const float* __restric
  *                whose owner passes it (clearing the keys as it goes), chunk sums, 6x6 solve (one column per lane), loop
  *                state; when the level ends it folds PoseX into the job's pose.  Same arithmetic and orders as the
  *                kernels above.
- * The host reads one flag per job (pinned memory, written by k_icp2_tail) after every batch of iterations.
+ * The host keeps PPF_ICP_BATCH2 passes in the stream ahead of the device and polls a pinned counter of finished tail
+ * workgroups; one flag per job (pinned memory, written by k_icp2_tail) says which jobs the next pass is launched for.
+ * The jobs of a call may have different clouds (IcpJobDesc below): ppf_match_frame refines the poses of every
+ * detection of a frame through one launch sequence.
  * ============================================================================================================ */
-constexpr int ICP_MAX_JOBS = 8;     /* poses refined per batch of launches */
+constexpr int ICP_MAX_JOBS = 8;     /* poses of one ppf_icp_refine* call refined per launch sequence (legacy path: one stream each) */
 constexpr int ICP_LEAVES = 4096;    /* 16 x 16 x 16 cells, grouped 4 x 4 x 4 under 64 nodes */
 constexpr int ICP_BRUTE_ND = 1024;  /* levels with at most this many scene rows scan them all (16 steps of a wave; C1 level 2, 2,599 rows: 58 us scanning them all, 25 us through the grid) */
 constexpr float ICP_LB_SHRINK = 0.9999f;
@@ -709,18 +712,46 @@ struct IcpState2 {
 __device__ __forceinline__ uint32_t icp_f2o(float f) { const uint32_t b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 __device__ __forceinline__ float icp_o2f(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o); }
 
-struct IcpBatch {
+/* Segmented jobs: each job has its own source and destination clouds.  Its geometry, its place in every scratch array and
+ * its initial pose come from a device table (IcpJobDesc, one per job), its level schedule from a second one (IcpLevelDesc,
+ * job-major, indexed by level): two jobs of one call may refine different models against different scenes.  Launches are
+ * sized for the largest job; the blocks past a job's own rows return.  Nothing a job computes depends on the other jobs. */
+constexpr int ICP_GROUP_JOBS = 256; /* jobs of one launch sequence (the live list of a pass is a kernel argument of 512 bytes) */
+struct IcpJobDesc {
   const float* src; /* the model as given (rows of sstride floats, normal at snoff) */
   const float* dst;
-  int n, sstride, snoff, nd_all, dstride, dnoff;
-  /* per-job arrays: job j starts at base + j * pitch */
-  float *src0, *dst0, *src_pct;       /* n*6, nd_all*6, n*6 */
-  unsigned long long *best, *owner;   /* n, nd_all */
-  int2* sel;                          /* min(n, nd_all) */
-  double *parts, *sum_src, *sum_dst;  /* p_parts, p_sums, p_sumd */
-  float* bb_parts;                    /* 6 per chunk of scene rows: its extent (pitch p_sumd * 2) */
-  uint32_t* own_a;                    /* nd_all: model row of a scene row's owner, between two phases of k_icp2_tail */
-  float4* g_pts;                      /* nd_all: x y z + original row index (bits) in leaf order */
+  int n, sstride, snoff, nd_all, dstride, dnoff, has_init, pad0;
+  /* where the job starts in the shared scratch arrays, in elements of each array */
+  size_t o_src0;   /* src0, src_pct: n * 6 floats */
+  size_t o_dst0;   /* dst0: nd_all * 6 floats */
+  size_t o_best;   /* best: n keys */
+  size_t o_owner;  /* owner, own_a, g_pts: nd_all each */
+  size_t o_sel;    /* sel: min(n, nd_all) */
+  size_t o_parts;  /* parts: chunks of min(n, nd_all) rows x ICP_ENTRIES */
+  size_t o_sums;   /* sum_src: chunks of n rows x 3 */
+  size_t o_sumd;   /* sum_dst: chunks of nd_all rows x 3; bb_parts: twice that */
+  double T0[16];   /* initial pose (has_init) */
+};
+/* one job's level: subsampling step, rows of either cloud it keeps, log2(step) or -1, distances staged in LDS */
+struct IcpLevelDesc {
+  int step, ns, nd, step_shift, staged, pad0, pad1, pad2;
+};
+
+struct IcpBatch {
+  const IcpJobDesc* jobs;             /* device: one per job */
+  const IcpLevelDesc* levels;         /* device: jobs x num_levels */
+  int num_levels;
+  uint32_t table_words;               /* 16-byte words of both tables (jobs, then levels) */
+  const uint4* h_tables;              /* pinned host memory: the tables as the host wrote them (k_icp2_reset copies them up) */
+  uint4* d_tables;                    /* = jobs */
+  /* per-job arrays: job j starts where its IcpJobDesc says (g_*: at j times a fixed pitch) */
+  float *src0, *dst0, *src_pct;
+  unsigned long long *best, *owner;
+  int2* sel;
+  double *parts, *sum_src, *sum_dst;
+  float* bb_parts;                    /* 6 per chunk of scene rows: its extent */
+  uint32_t* own_a;                    /* model row of a scene row's owner, between two phases of k_icp2_tail */
+  float4* g_pts;                      /* x y z + original row index (bits) in leaf order */
   uint32_t* g_start;                  /* ICP_LEAVES + 1 (pitch ICP_LEAVES + 64) */
   uint32_t* g_cur;                    /* ICP_LEAVES: rows per leaf, then the scatter cursors */
   float4* g_box2;                     /* 2 per leaf: lo, hi */
@@ -729,10 +760,10 @@ struct IcpBatch {
   int* h_done;                        /* pinned host memory: done flag per job */
   unsigned long long* h_ticks;        /* pinned: k_icp2_tail workgroups that have finished since the call began (the host waits on it) */
   IcpState2* h_state;                 /* pinned: a job's loop state, copied out by k_icp2_tail when a level ends */
-  size_t p_sel, p_parts, p_sums, p_sumd;
-  int has_init;
-  double T0[ICP_MAX_JOBS][16];        /* initial poses */
 };
+__device__ __forceinline__ const IcpLevelDesc& icp_level(const IcpBatch& B, int job, int level) {
+  return B.levels[(size_t)job * B.num_levels + level];
+}
 
 static_assert(sizeof(IcpState2) % 8 == 0, "the state is copied to the host in 8-byte words");
 /* the job's loop state to pinned host memory (one thread) */
@@ -781,25 +812,27 @@ __device__ __forceinline__ unsigned long long icp_wave_min64(unsigned long long 
 __global__ __launch_bounds__(64) void k_icp2_pack_sums(IcpBatch B) {
   __shared__ float xyz[64][3];
   const int job = blockIdx.y, lane = threadIdx.x;
-  const int chunks_src = (B.n + ICP_CHUNK - 1) / ICP_CHUNK;
+  const IcpJobDesc& D = B.jobs[job];
+  const int chunks_src = (D.n + ICP_CHUNK - 1) / ICP_CHUNK, chunks_dst = (D.nd_all + ICP_CHUNK - 1) / ICP_CHUNK;
+  if ((int)blockIdx.x >= chunks_src + chunks_dst) return; /* the grid is sized for the largest job */
   const bool is_dst = (int)blockIdx.x >= chunks_src;
   const int c = is_dst ? (int)blockIdx.x - chunks_src : (int)blockIdx.x;
-  const int rows_all = is_dst ? B.nd_all : B.n;
+  const int rows_all = is_dst ? D.nd_all : D.n;
   const int i = c * ICP_CHUNK + lane;
   float o[6] = {0, 0, 0, 0, 0, 0};
   if (i < rows_all) {
-    const float* p = is_dst ? B.dst + (size_t)i * B.dstride : B.src + (size_t)i * B.sstride;
-    const int noff = is_dst ? B.dnoff : B.snoff;
-    if (!is_dst && B.has_init) {
+    const float* p = is_dst ? D.dst + (size_t)i * D.dstride : D.src + (size_t)i * D.sstride;
+    const int noff = is_dst ? D.dnoff : D.snoff;
+    if (!is_dst && D.has_init) {
       double M[16];
 #pragma unroll
-      for (int k = 0; k < 16; k++) M[k] = B.T0[job][k];
+      for (int k = 0; k < 16; k++) M[k] = D.T0[k];
       icp_transform_row(p, p + noff, M, o);
     } else {
 #pragma unroll
       for (int k = 0; k < 3; k++) { o[k] = p[k]; o[3 + k] = p[noff + k]; }
     }
-    float* out = is_dst ? B.dst0 + ((size_t)job * B.nd_all + i) * 6 : B.src0 + ((size_t)job * B.n + i) * 6;
+    float* out = is_dst ? B.dst0 + D.o_dst0 + (size_t)i * 6 : B.src0 + D.o_src0 + (size_t)i * 6;
 #pragma unroll
     for (int k = 0; k < 6; k++) out[k] = o[k];
   }
@@ -809,7 +842,7 @@ __global__ __launch_bounds__(64) void k_icp2_pack_sums(IcpBatch B) {
     const int rows = min(ICP_CHUNK, rows_all - c * ICP_CHUNK);
     double s[3] = {0, 0, 0};
     for (int k = 0; k < rows; k++) { s[0] += (double)xyz[k][0]; s[1] += (double)xyz[k][1]; s[2] += (double)xyz[k][2]; }
-    double* parts = is_dst ? B.sum_dst + (size_t)job * B.p_sumd + (size_t)c * 3 : B.sum_src + (size_t)job * B.p_sums + (size_t)c * 3;
+    double* parts = is_dst ? B.sum_dst + D.o_sumd + (size_t)c * 3 : B.sum_src + D.o_sums + (size_t)c * 3;
     parts[0] = s[0]; parts[1] = s[1]; parts[2] = s[2];
   }
   if (is_dst) { /* extent of the scene rows (the centring and scaling that follow are monotone: the grid's extent follows from it) */
@@ -823,22 +856,28 @@ __global__ __launch_bounds__(64) void k_icp2_pack_sums(IcpBatch B) {
       for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], __shfl_xor(lo[k], sh)); hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], sh)); }
     }
     if (lane == 0) { /* per chunk; k_icp2_mean joins them (a thousand co-resident blocks all found the accumulator "unset" and queued their atomics on six addresses) */
-      float* bb = B.bb_parts + ((size_t)job * B.p_sumd * 2 + (size_t)c * 6);
+      float* bb = B.bb_parts + (D.o_sumd * 2 + (size_t)c * 6);
 #pragma unroll
       for (int k = 0; k < 3; k++) { bb[k] = lo[k]; bb[3 + k] = hi[k]; }
     }
   }
 }
 
-/* before the prologue: the extent accumulators and the leaf counters of every job */
+/* before the prologue: the call's tables from pinned host memory to the device (a copy in the stream costs a DMA round trip
+ * before the first kernel; the launches after this one read the device copy), the extent accumulators and the leaf
+ * counters of every job */
 __global__ __launch_bounds__(256) void k_icp2_reset(IcpBatch B) {
   const int job = blockIdx.x, tid = threadIdx.x;
+  for (uint32_t k = (blockIdx.y * gridDim.x + blockIdx.x) * 256u + tid; k < B.table_words; k += gridDim.x * gridDim.y * 256u) B.d_tables[k] = B.h_tables[k];
   uint32_t* cur = B.g_cur + (size_t)job * ICP_LEAVES;
   for (int k = tid; k < ICP_LEAVES; k += 256) cur[k] = 0u;
   for (int k = tid; k < 64 * 8; k += 256) B.g_box1u[(size_t)job * 64 * 8 + k] = (k & 4) ? icp_f2o(-__builtin_inff()) : icp_f2o(__builtin_inff());
   /* the ownership keys: all "no owner" from here on (k_icp2_tail clears the ones an iteration set) */
-  unsigned long long* owner = B.owner + (size_t)job * B.nd_all;
-  for (int b = blockIdx.y * 256 + tid; b < B.nd_all; b += gridDim.y * 256) owner[b] = ICP_NONE;
+  const IcpJobDesc& D = reinterpret_cast<const IcpJobDesc*>(B.h_tables)[job];
+  const size_t o_owner = D.o_owner;
+  const int nd_all = D.nd_all;
+  unsigned long long* owner = B.owner + o_owner;
+  for (int b = blockIdx.y * 256 + tid; b < nd_all; b += gridDim.y * 256) owner[b] = ICP_NONE;
 }
 
 /* sums of chunk partials (3 per chunk) in chunk order: thread c < 3 of the block returns the sum of component c.  The partials
@@ -863,14 +902,15 @@ __global__ __launch_bounds__(256) void k_icp2_mean(IcpBatch B) {
   __shared__ double m_parts[ICP_SUM_TILE * 3];
   __shared__ double tot[6];
   const int job = blockIdx.x, tid = threadIdx.x;
-  const double a_src = icp_sum_staged(B.sum_src + (size_t)job * B.p_sums, (B.n + ICP_CHUNK - 1) / ICP_CHUNK, m_parts, tid, 256);
-  const double a_dst = icp_sum_staged(B.sum_dst + (size_t)job * B.p_sumd, (B.nd_all + ICP_CHUNK - 1) / ICP_CHUNK, m_parts, tid, 256);
+  const IcpJobDesc& D = B.jobs[job];
+  const double a_src = icp_sum_staged(B.sum_src + D.o_sums, (D.n + ICP_CHUNK - 1) / ICP_CHUNK, m_parts, tid, 256);
+  const double a_dst = icp_sum_staged(B.sum_dst + D.o_sumd, (D.nd_all + ICP_CHUNK - 1) / ICP_CHUNK, m_parts, tid, 256);
   if (tid < 3) { tot[tid] = a_src; tot[3 + tid] = a_dst; }
   /* the scene's extent from its chunks' */
   float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-  const int chunks_dst = (B.nd_all + ICP_CHUNK - 1) / ICP_CHUNK;
+  const int chunks_dst = (D.nd_all + ICP_CHUNK - 1) / ICP_CHUNK;
   for (int c = tid; c < chunks_dst; c += 256) {
-    const float* bb = B.bb_parts + ((size_t)job * B.p_sumd * 2 + (size_t)c * 6);
+    const float* bb = B.bb_parts + (D.o_sumd * 2 + (size_t)c * 6);
 #pragma unroll
     for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], bb[k]); hi[k] = fmaxf(hi[k], bb[3 + k]); }
   }
@@ -885,7 +925,7 @@ __global__ __launch_bounds__(256) void k_icp2_mean(IcpBatch B) {
   if (tid == 0) {
     IcpState2* st = B.state + job;
     for (int k = 0; k < 3; k++) {
-      const double ms = tot[k] / (double)B.n, md = tot[3 + k] / (double)B.nd_all;
+      const double ms = tot[k] / (double)D.n, md = tot[3 + k] / (double)D.nd_all;
       st->mean_avg[k] = 0.5 * (ms + md);
       st->raw_lo[k] = fminf(fminf(ext[0][k], ext[1][k]), fminf(ext[2][k], ext[3][k]));
       st->raw_hi[k] = fmaxf(fmaxf(ext[0][3 + k], ext[1][3 + k]), fmaxf(ext[2][3 + k], ext[3][3 + k]));
@@ -903,15 +943,17 @@ __device__ __forceinline__ void icp_centred(const float* __restrict__ p, const d
 __global__ __launch_bounds__(64) void k_icp2_dist_sums(IcpBatch B) {
   __shared__ double dist[64];
   const int job = blockIdx.y, lane = threadIdx.x;
-  const int chunks_src = (B.n + ICP_CHUNK - 1) / ICP_CHUNK;
+  const IcpJobDesc& D = B.jobs[job];
+  const int chunks_src = (D.n + ICP_CHUNK - 1) / ICP_CHUNK, chunks_dst = (D.nd_all + ICP_CHUNK - 1) / ICP_CHUNK;
+  if ((int)blockIdx.x >= chunks_src + chunks_dst) return;
   const bool is_dst = (int)blockIdx.x >= chunks_src;
   const int c = is_dst ? (int)blockIdx.x - chunks_src : (int)blockIdx.x;
-  const int rows_all = is_dst ? B.nd_all : B.n;
+  const int rows_all = is_dst ? D.nd_all : D.n;
   const int i = c * ICP_CHUNK + lane;
   const IcpState2* st = B.state + job;
   double d = 0;
   if (i < rows_all) {
-    const float* p = is_dst ? B.dst0 + ((size_t)job * B.nd_all + i) * 6 : B.src0 + ((size_t)job * B.n + i) * 6;
+    const float* p = is_dst ? B.dst0 + D.o_dst0 + (size_t)i * 6 : B.src0 + D.o_src0 + (size_t)i * 6;
     float cf[3];
     icp_centred(p, st->mean_avg, cf);
     d = ppf_sqrt((double)cf[0] * (double)cf[0] + (double)cf[1] * (double)cf[1] + (double)cf[2] * (double)cf[2]);
@@ -922,7 +964,7 @@ __global__ __launch_bounds__(64) void k_icp2_dist_sums(IcpBatch B) {
     const int rows = min(ICP_CHUNK, rows_all - c * ICP_CHUNK);
     double s = 0;
     for (int k = 0; k < rows; k++) s += dist[k];
-    double* parts = is_dst ? B.sum_dst + (size_t)job * B.p_sumd + (size_t)c * 3 : B.sum_src + (size_t)job * B.p_sums + (size_t)c * 3;
+    double* parts = is_dst ? B.sum_dst + D.o_sumd + (size_t)c * 3 : B.sum_src + D.o_sums + (size_t)c * 3;
     parts[0] = s;
   }
 }
@@ -942,13 +984,14 @@ __global__ __launch_bounds__(256) void k_icp2_scale(IcpBatch B) {
   __shared__ double m_parts[ICP_SUM_TILE * 3];
   __shared__ double tot[2];
   const int job = blockIdx.x, tid = threadIdx.x;
-  const double a_src = icp_sum_staged(B.sum_src + (size_t)job * B.p_sums, (B.n + ICP_CHUNK - 1) / ICP_CHUNK, m_parts, tid, 256);
-  const double a_dst = icp_sum_staged(B.sum_dst + (size_t)job * B.p_sumd, (B.nd_all + ICP_CHUNK - 1) / ICP_CHUNK, m_parts, tid, 256);
+  const IcpJobDesc& D = B.jobs[job];
+  const double a_src = icp_sum_staged(B.sum_src + D.o_sums, (D.n + ICP_CHUNK - 1) / ICP_CHUNK, m_parts, tid, 256);
+  const double a_dst = icp_sum_staged(B.sum_dst + D.o_sumd, (D.nd_all + ICP_CHUNK - 1) / ICP_CHUNK, m_parts, tid, 256);
   if (tid == 0) { tot[0] = a_src; tot[1] = a_dst; } /* component 0: the distance sums */
   __syncthreads();
   if (tid != 0) return;
   IcpState2* st = B.state + job;
-  const double scale = (double)B.n / ((tot[0] + tot[1]) * 0.5);
+  const double scale = (double)D.n / ((tot[0] + tot[1]) * 0.5);
   st->scale = scale;
   float lo[3], hi[3];
   for (int k = 0; k < 3; k++) {
@@ -977,15 +1020,16 @@ constexpr int ICP_ROWS_BLOCK = 8192;
 __global__ __launch_bounds__(1024) void k_icp2_rows_count(IcpBatch B) {
   __shared__ uint32_t hist[ICP_LEAVES];
   const int job = blockIdx.y, tid = threadIdx.x;
+  const IcpJobDesc& D = B.jobs[job];
   const IcpState2* st = B.state + job;
   const double scale = st->scale;
-  const int nb_dst = (B.nd_all + ICP_ROWS_BLOCK - 1) / ICP_ROWS_BLOCK;
+  const int nb_dst = (D.nd_all + ICP_ROWS_BLOCK - 1) / ICP_ROWS_BLOCK;
   if ((int)blockIdx.x >= nb_dst) {
     const int r0 = ((int)blockIdx.x - nb_dst) * ICP_ROWS_BLOCK;
     for (int u = 0; u < ICP_ROWS_BLOCK / 1024; u++) {
       const int i = r0 + u * 1024 + tid;
-      if (i < B.n) {
-        float* p = B.src0 + ((size_t)job * B.n + i) * 6;
+      if (i < D.n) {
+        float* p = B.src0 + D.o_src0 + (size_t)i * 6;
         float cf[3];
         icp_centred(p, st->mean_avg, cf);
 #pragma unroll
@@ -1000,8 +1044,8 @@ __global__ __launch_bounds__(1024) void k_icp2_rows_count(IcpBatch B) {
   const float ox = st->org[0], oy = st->org[1], oz = st->org[2], inv_h = st->inv_h;
   for (int u = 0; u < ICP_ROWS_BLOCK / 1024; u++) {
     const int i = r0 + u * 1024 + tid;
-    if (i < B.nd_all) {
-      float* p = B.dst0 + ((size_t)job * B.nd_all + i) * 6;
+    if (i < D.nd_all) {
+      float* p = B.dst0 + D.o_dst0 + (size_t)i * 6;
       float cf[3], v[3];
       icp_centred(p, st->mean_avg, cf);
 #pragma unroll
@@ -1045,10 +1089,12 @@ __global__ __launch_bounds__(1024) void k_icp2_grid_scan(IcpBatch B) {
 __global__ __launch_bounds__(1024) void k_icp2_grid_scatter(IcpBatch B) {
   __shared__ uint32_t hist[ICP_LEAVES];
   const int job = blockIdx.y, tid = threadIdx.x;
+  const IcpJobDesc& D = B.jobs[job];
   const IcpState2* st = B.state + job;
+  const int r0 = (int)blockIdx.x * ICP_ROWS_BLOCK;
+  if (r0 >= D.nd_all) return; /* the grid is sized for the largest job */
   for (int k = tid; k < ICP_LEAVES; k += 1024) hist[k] = 0;
   __syncthreads();
-  const int r0 = (int)blockIdx.x * ICP_ROWS_BLOCK;
   const float ox = st->org[0], oy = st->org[1], oz = st->org[2], inv_h = st->inv_h;
   constexpr int U = ICP_ROWS_BLOCK / 1024;
   float x[U], y[U], z[U];
@@ -1058,8 +1104,8 @@ __global__ __launch_bounds__(1024) void k_icp2_grid_scatter(IcpBatch B) {
   for (int u = 0; u < U; u++) {
     const int i = r0 + u * 1024 + tid;
     leaf[u] = -1;
-    if (i < B.nd_all) {
-      const float* p = B.dst0 + ((size_t)job * B.nd_all + i) * 6;
+    if (i < D.nd_all) {
+      const float* p = B.dst0 + D.o_dst0 + (size_t)i * 6;
       x[u] = p[0]; y[u] = p[1]; z[u] = p[2];
       leaf[u] = icp_leaf_id(icp_cell_of(x[u], ox, inv_h), icp_cell_of(y[u], oy, inv_h), icp_cell_of(z[u], oz, inv_h));
       rank[u] = atomicAdd(&hist[leaf[u]], 1u);
@@ -1069,7 +1115,7 @@ __global__ __launch_bounds__(1024) void k_icp2_grid_scatter(IcpBatch B) {
   uint32_t* cur = B.g_cur + (size_t)job * ICP_LEAVES;
   for (int k = tid; k < ICP_LEAVES; k += 1024) { const uint32_t c = hist[k]; hist[k] = c ? atomicAdd(&cur[k], c) : 0u; }
   __syncthreads();
-  float4* g_pts = B.g_pts + (size_t)job * B.nd_all;
+  float4* g_pts = B.g_pts + D.o_owner;
 #pragma unroll
   for (int u = 0; u < U; u++)
     if (leaf[u] >= 0) g_pts[hist[leaf[u]] + rank[u]] = make_float4(x[u], y[u], z[u], __int_as_float(r0 + u * 1024 + tid));
@@ -1082,7 +1128,7 @@ __global__ __launch_bounds__(256) void k_icp2_grid_boxes(IcpBatch B) {
   const int job = blockIdx.y, lane = threadIdx.x & 63;
   const int leaf = blockIdx.x * 4 + (threadIdx.x >> 6); /* grid.x = ICP_LEAVES / 4 */
   const uint32_t* g_start = B.g_start + (size_t)job * (ICP_LEAVES + 64);
-  const float4* g_pts = B.g_pts + (size_t)job * B.nd_all;
+  const float4* g_pts = B.g_pts + B.jobs[job].o_owner;
   float l[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, h[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
   const uint32_t s = g_start[leaf], e = g_start[leaf + 1];
   for (uint32_t q = s + (uint32_t)lane; q < e; q += 64) {
@@ -1107,18 +1153,21 @@ __global__ __launch_bounds__(256) void k_icp2_grid_boxes(IcpBatch B) {
 }
 
 /* a level starts: its source rows = pose * src0[a * step]; block 0 resets the level's loop state */
-__global__ __launch_bounds__(256) void k_icp2_level_begin(IcpBatch B, int step, int ns, double tol_p, int max_iter, int robust, int last_level) {
+__global__ __launch_bounds__(256) void k_icp2_level_begin(IcpBatch B, int level, double tol_p, int max_iter, int robust, int last_level) {
   const int job = blockIdx.y;
   IcpState2* st = B.state + job;
+  const size_t o_src0 = B.jobs[job].o_src0;
+  const IcpLevelDesc& L = icp_level(B, job, level);
+  const int step = L.step, ns = L.ns;
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a < ns) {
     double M[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) M[k] = st->pose[k];
-    const float* p = B.src0 + ((size_t)job * B.n + (size_t)a * step) * 6;
+    const float* p = B.src0 + o_src0 + (size_t)a * step * 6;
     float o[6];
     icp_transform_row(p, p + 3, M, o);
-    float* out = B.src_pct + ((size_t)job * B.n + a) * 6;
+    float* out = B.src_pct + o_src0 + (size_t)a * 6;
 #pragma unroll
     for (int k = 0; k < 6; k++) out[k] = o[k];
   }
@@ -1151,17 +1200,50 @@ __device__ __forceinline__ float icp_box_lb2(const float4 lo, const float4 hi, f
 constexpr int ICP_NN_ROWS = 8; /* rows a wave takes in turn, at most */
 /* the jobs a pass is launched for: those that had not finished their level when the host last looked (a finished job's
  * workgroups return at once, but 20,000 of them per finished job and pass are 5 us) */
-struct IcpLive { int job[ICP_MAX_JOBS]; };
-__global__ __launch_bounds__(256) void k_icp2_nn(IcpBatch B, IcpLive live, int ns, int nd, int step, int step_shift, int rows, int brute_nd) {
+struct IcpLive { uint16_t job[ICP_GROUP_JOBS]; };
+/* The per-pass kernels come in two variants.  SEG: every job reads its geometry and its level from the device tables.
+ * !SEG (every job of the call has the same two clouds, what ppf_icp_refine* asks for): they come with the launch, as one
+ * IcpUniform, and job j's arrays start at j times a pitch -- the places the tables would give.  Reading them from memory
+ * put a dependent load in front of every pass and cost C1's top-5 ICP 1.6 % (50 us in 3.1 ms). */
+struct IcpUniform {
+  int ns, nd, step, step_shift, staged, n, nd_all, pad0;
+  size_t p_sel, p_parts; /* pitches of sel and parts */
+};
+struct IcpPassGeom {
+  int ns, nd, step, step_shift, staged, nd_all;
+  size_t o_src0, o_dst0, o_best, o_owner, o_sel, o_parts;
+};
+template <bool SEG>
+__device__ __forceinline__ IcpPassGeom icp_pass_geom(const IcpBatch& B, const IcpUniform& U, int job, int level) {
+  IcpPassGeom g;
+  if (SEG) {
+    const IcpJobDesc& D = B.jobs[job];
+    const IcpLevelDesc& L = icp_level(B, job, level);
+    g.ns = L.ns; g.nd = L.nd; g.step = L.step; g.step_shift = L.step_shift; g.staged = L.staged; g.nd_all = D.nd_all;
+    g.o_src0 = D.o_src0; g.o_dst0 = D.o_dst0; g.o_best = D.o_best; g.o_owner = D.o_owner; g.o_sel = D.o_sel; g.o_parts = D.o_parts;
+  } else {
+    g.ns = U.ns; g.nd = U.nd; g.step = U.step; g.step_shift = U.step_shift; g.staged = U.staged; g.nd_all = U.nd_all;
+    g.o_src0 = (size_t)job * U.n * 6; g.o_dst0 = (size_t)job * U.nd_all * 6; g.o_best = (size_t)job * U.n;
+    g.o_owner = (size_t)job * U.nd_all; g.o_sel = (size_t)job * U.p_sel; g.o_parts = (size_t)job * U.p_parts;
+  }
+  return g;
+}
+template <bool SEG>
+__global__ __launch_bounds__(256) void k_icp2_nn(IcpBatch B, IcpLive live, int level, IcpUniform U, int rows, int brute_nd) {
   const int job = live.job[blockIdx.y];
   const IcpState2* st = B.state + job;
+  /* the job's geometry is read before the done flag is tested: the loads then travel together */
+  const IcpPassGeom G = icp_pass_geom<SEG>(B, U, job, level);
+  const int ns = G.ns, nd = G.nd, step = G.step, step_shift = G.step_shift;
+  const size_t o_src0 = G.o_src0, o_owner = G.o_owner, o_best = G.o_best;
+  const int nd_all = G.nd_all;
+  const float* dst0 = B.dst0 + G.o_dst0;
   if (st->done) return;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int a0 = (blockIdx.x * 4 + wave) * rows;
-  if (a0 >= ns) return;
-  const float* dst0 = B.dst0 + (size_t)job * B.nd_all * 6;
-  const float4* __restrict__ pts = B.g_pts + (size_t)job * B.nd_all;
+  if (a0 >= ns) return; /* also the blocks past this job's rows: the grid is sized for the largest job */
+  const float4* __restrict__ pts = B.g_pts + o_owner;
   const float4* __restrict__ box2 = B.g_box2 + (size_t)job * ICP_LEAVES * 2;
   const uint32_t* __restrict__ box1u = B.g_box1u + ((size_t)job * 64 + lane) * 8;
   const float4 n_lo = make_float4(icp_o2f(box1u[0]), icp_o2f(box1u[1]), icp_o2f(box1u[2]), 0.f);
@@ -1179,7 +1261,7 @@ __global__ __launch_bounds__(256) void k_icp2_nn(IcpBatch B, IcpLive live, int n
     if (a >= ns) break;
     float qx, qy, qz;
     {
-      const float* p = B.src_pct + ((size_t)job * B.n + a) * 6;
+      const float* p = B.src_pct + o_src0 + (size_t)a * 6;
       if (first_pass) { /* the level's first pass searches from its rows as they are (`moved = srcPCT`) */
         qx = p[0]; qy = p[1]; qz = p[2];
       } else {          /* later passes from PoseX * row: the xyz of transformPCPose */
@@ -1246,7 +1328,7 @@ __global__ __launch_bounds__(256) void k_icp2_nn(IcpBatch B, IcpLive live, int n
         key = icp_wave_min64(key);
         ubest = __uint_as_float((uint32_t)(key >> 32));
       };
-      const uint32_t last_row = (uint32_t)B.nd_all - 1u;
+      const uint32_t last_row = (uint32_t)nd_all - 1u;
       /* one node: lane l tests child l (its box arrives with the child's row range: no second table to read); `first` (>= 0) is
        * scanned whatever its bound -- the query's own leaf, which gives the search a distance to prune with --, then the
        * children nearest first, two at a time: the first one whose bound exceeds the best distance ends the list (the second of
@@ -1293,7 +1375,7 @@ __global__ __launch_bounds__(256) void k_icp2_nn(IcpBatch B, IcpLive live, int n
         visit_node(k1, -1);
       }
     }
-    if (lane == 0) B.best[(size_t)job * B.n + a] = key;
+    if (lane == 0) B.best[o_best + a] = key;
     if (lane == q) mine = key;
   }
   /* picky ownership: the scene row each of the wave's rows chose gets atomicMin(distance bits, model row); rows that chose the
@@ -1317,7 +1399,7 @@ __global__ __launch_bounds__(256) void k_icp2_nn(IcpBatch B, IcpLive live, int n
     /* only a key that can lower the scene row's current one is sent (a stale read only lets a redundant atomic through): when a
      * model has been thrown off the data, twenty thousand rows name the same scene row */
     if (leader) {
-      unsigned long long* o = &B.owner[(size_t)job * B.nd_all + b_mine];
+      unsigned long long* o = &B.owner[o_owner + b_mine];
       if (k < __hip_atomic_load(o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(o, k);
     }
   }
@@ -1545,7 +1627,8 @@ __device__ uint32_t icp_block_select3(F val, const int n, const uint32_t rank, u
 /* everything of an iteration after the neighbour search, one workgroup per job (see the header of this section).
  * Dynamic LDS: max(ns * 4 when staged, 16 waves x 64 x 9 doubles of chunk rows). */
 constexpr int ICP_TAIL_VAL_BYTES = 16 * ICP_CHUNK * 9 * 8;
-__global__ __launch_bounds__(1024) void k_icp2_tail(IcpBatch B, IcpLive live, int ns, int nd, int step, float rej_scale, int staged, int last_level) {
+template <bool SEG>
+__global__ __launch_bounds__(1024) void k_icp2_tail(IcpBatch B, IcpLive live, int level, IcpUniform U, float rej_scale, int last_level) {
   extern __shared__ __align__(16) unsigned char t_dyn[];
   __shared__ __align__(16) uint32_t hist[264], s_list[264];
   __shared__ uint32_t sh[8], wsum[16];
@@ -1554,19 +1637,23 @@ __global__ __launch_bounds__(1024) void k_icp2_tail(IcpBatch B, IcpLive live, in
   __shared__ int s_done, s_nsel;
   const int job = live.job[blockIdx.x];
   IcpState2* st = B.state + job;
+  /* the job's geometry and its own level (the dynamic LDS is the largest any job of the pass needs), read before the done
+   * flag is tested: the loads then travel together */
+  const IcpPassGeom G = icp_pass_geom<SEG>(B, U, job, level);
+  const int ns = G.ns, nd = G.nd, step = G.step, staged = G.staged;
+  const unsigned long long* best = B.best + G.o_best;
+  unsigned long long* owner = B.owner + G.o_owner;
+  int2* sel = B.sel + G.o_sel;
+  uint32_t* own_a = B.own_a + G.o_owner;
+  double* parts = B.parts + G.o_parts;
+  const float* src_pct = B.src_pct + G.o_src0;
+  const float* dst0 = B.dst0 + G.o_dst0;
   if (st->done) { /* this job's level is over: only the host's count of finished workgroups moves */
     if (threadIdx.x == 0) icp_tick(B, false);
     return;
   }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int robust = st->robust;
-  const unsigned long long* best = B.best + (size_t)job * B.n;
-  unsigned long long* owner = B.owner + (size_t)job * B.nd_all;
-  int2* sel = B.sel + (size_t)job * B.p_sel;
-  uint32_t* own_a = B.own_a + (size_t)job * B.nd_all;
-  double* parts = B.parts + (size_t)job * B.p_parts;
-  const float* src_pct = B.src_pct + (size_t)job * B.n * 6;
-  const float* dst0 = B.dst0 + (size_t)job * B.nd_all * 6;
   uint32_t* s_bits = reinterpret_cast<uint32_t*>(t_dyn);
   ICP_PH_DECL;
   /* 1. rejection threshold */

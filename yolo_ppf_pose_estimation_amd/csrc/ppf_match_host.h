@@ -289,7 +289,7 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
     va.count_only = 0;
     std::vector<uint32_t> cw(CUR_SORTED);
     HIPCHK(hipMemcpyAsync(cw.data(), ws->cursors.p, cw.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(host_stream_sync(st));
     unsigned long long hits = 0;
     for (int sidx = 0; sidx < POOL_STRIPES; sidx++)
       hits += (unsigned long long)cw[sidx * CUR_STRIDE] | ((unsigned long long)cw[sidx * CUR_STRIDE + 1] << 32);
@@ -453,7 +453,7 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
  * hold every scene pair).  Also reads the counters and learns hit_frac for the next call. */
 static ppf_status workspace_finish(ppf_workspace* ws) {
   if (!ws->pending) return fail(PPF_ERR_INVALID, "no call in this workspace");
-  HIPCHK(hipStreamSynchronize(ws->stream));
+  HIPCHK(host_stream_sync(ws->stream));
   if (ws->checked || ws->n_ref == 0) { ws->checked = true; return PPF_OK; }
   for (;;) {
     const int T = ws->model->info.n_tiles;
@@ -463,8 +463,8 @@ static ppf_status workspace_finish(ppf_workspace* ws) {
       memcpy(tot, ws->h_sum, sizeof(tot));
       ovf = (uint32_t)ws->h_sum[16];
     } else {
-      HIPCHK(hipMemcpy(tot, ws->counters.p + (size_t)ws->n_ref * T + ws->n_ref, sizeof(tot), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(&ovf, ws->cursors.p + CUR_OVERFLOW, sizeof(ovf), hipMemcpyDeviceToHost));
+      HIPCHK(host_read(tot, ws->counters.p + (size_t)ws->n_ref * T + ws->n_ref, sizeof(tot)));
+      HIPCHK(host_read(&ovf, ws->cursors.p + CUR_OVERFLOW, sizeof(ovf)));
     }
     if (!ovf) {
       ws->stats.n_votes = tot[0];
@@ -479,7 +479,7 @@ static ppf_status workspace_finish(ppf_workspace* ws) {
       if (!ws->acc32 && ws->acc32_policy == 0 && (double)tot[6] > PPF_ACC32_SWITCH * (double)tot[0]) ws->acc32 = true;
       if (!ws->force_acc32 && ws->acc32_policy == 3) {
         unsigned long long hist[2 * ACC_HIST];
-        HIPCHK(hipMemcpy(hist, ws->need_hist.p, sizeof(hist), hipMemcpyDeviceToHost));
+        HIPCHK(host_read(hist, ws->need_hist.p, sizeof(hist)));
         double best = -1;
         int best_k = ACC_HIST;
         double above = 0, below = 0; /* cost of the classes >= k (sent to 32-bit cells) / < k (tried with 16-bit cells) */
@@ -510,7 +510,7 @@ static ppf_status workspace_finish(ppf_workspace* ws) {
       if (ws->clustered) {
         uint32_t nf = 0;
         if (ws->sum_valid) nf = (uint32_t)ws->h_sum[17];
-        else HIPCHK(hipMemcpy(&nf, ws->cl_u32.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        else HIPCHK(host_read(&nf, ws->cl_u32.p, sizeof(uint32_t)));
         ws->stats.n_poses = (int)nf;
       }
       if (ws->timing) {
@@ -544,7 +544,7 @@ static ppf_status workspace_finish(ppf_workspace* ws) {
     ppf_model* m = ws->model;
     ppf_status s = match_prepared(m, ws, &p, ws->stream, true);
     if (s != PPF_OK) return s;
-    HIPCHK(hipStreamSynchronize(ws->stream));
+    HIPCHK(host_stream_sync(ws->stream));
   }
 }
 
@@ -557,16 +557,16 @@ ppf_status ppf_workspace_results(ppf_workspace* ws, ppf_vote* votes, ppf_pose* r
   if (n_ref) *n_ref = nr;
   if ((votes || raw_poses) && cap_ref < nr) return fail(PPF_ERR_CAPACITY, "ppf_workspace_results: need room for %d reference points", nr);
   if (nr > 0) {
-    if (votes) HIPCHK(hipMemcpy(votes, ws->votes.p, (size_t)nr * sizeof(ppf_vote), hipMemcpyDeviceToHost));
-    if (raw_poses) HIPCHK(hipMemcpy(raw_poses, ws->raw_poses.p, (size_t)nr * sizeof(ppf_pose), hipMemcpyDeviceToHost));
+    if (votes) HIPCHK(host_read(votes, ws->votes.p, (size_t)nr * sizeof(ppf_vote)));
+    if (raw_poses) HIPCHK(host_read(raw_poses, ws->raw_poses.p, (size_t)nr * sizeof(ppf_pose)));
   }
   if ((poses || n_poses) && ws->clustered) {
     if (ws->final_poses.empty() && nr > 0) {
       uint32_t nf = 0;
       if (ws->sum_valid) nf = (uint32_t)ws->h_sum[17];
-      else HIPCHK(hipMemcpy(&nf, ws->cl_u32.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+      else HIPCHK(host_read(&nf, ws->cl_u32.p, sizeof(uint32_t)));
       ws->final_poses.resize(nf);
-      if (nf) HIPCHK(hipMemcpy(ws->final_poses.data(), ws->d_final.p, (size_t)nf * sizeof(ppf_pose), hipMemcpyDeviceToHost));
+      if (nf) HIPCHK(host_read(ws->final_poses.data(), ws->d_final.p, (size_t)nf * sizeof(ppf_pose)));
     }
     ws->stats.n_poses = (int)ws->final_poses.size();
     if (n_poses) *n_poses = (int)ws->final_poses.size();
