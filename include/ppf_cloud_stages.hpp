@@ -2,6 +2,7 @@
  * ppf_cloud_stages.hpp — header-only C++ wrapper of the device-resident cloud stages (ppf_cloud_* / ppf_prep_* in
  * ppf_hip.h): the PCL half of the reference's ppf::CloudProcessor (/root/reference/include/CloudProcessing.h)
  *
+ *   Deprojection       :262      ->  Cloud::fromDepth(depth, rows, cols, fx, fy, ppx, ppy) / fromDepthU16(..., scale, ...)
  *   SceneCropping      :263-339  ->  Cloud::crop(box, depth, rows, cols, fx, fy, ppx, ppy)
  *   Subsampling        :361-380  ->  Cloud::voxelGrid(leaf)
  *   OutlierProcessing  :341-360  ->  Cloud::outlierRemoval(meanK, stddevMul)
@@ -40,6 +41,20 @@ class Cloud {
   /* an N x 3 or N x 6 float32 Mat (cv::Mat when OpenCV is present: rows read through step1()) */
   static Cloud fromMat(const ppf_match_3d::Mat& m) {
     return fromRows(m.ptr<float>(0), m.rows, ppf_match_3d::detail::stride_of(m), m.cols >= 6 ? 6 : 3);
+  }
+
+  /* Deprojection (:262, an empty stub in the reference): the scene cloud of a HOST depth image, back-projected on the
+   * device (ppf_cloud_from_depth).  float32 metres; rows x y z 0 0 0 of every pixel with a finite z > 0 in [zMin, zMax]
+   * (zMax 0: no upper bound), row-major pixel order.  fp64: the fp64 formula instead of Camera::back_projection's
+   * rounding.  rowPitchBytes 0: packed rows. */
+  static Cloud fromDepth(const float* depth, int rows, int cols, double fx, double fy, double ppx, double ppy, float zMin = 0.f,
+                         float zMax = 0.f, bool fp64 = false, size_t rowPitchBytes = 0) {
+    return fromDepthImage(depth, PPF_DEPTH_F32, 0.001, rows, cols, fx, fy, ppx, ppy, zMin, zMax, fp64, rowPitchBytes);
+  }
+  /* the same from a 16-bit sensor image: z = d * scale metres (0.001 for millimetres) */
+  static Cloud fromDepthU16(const uint16_t* depth, int rows, int cols, double scale, double fx, double fy, double ppx, double ppy,
+                            float zMin = 0.f, float zMax = 0.f, bool fp64 = false, size_t rowPitchBytes = 0) {
+    return fromDepthImage(depth, PPF_DEPTH_U16, scale, rows, cols, fx, fy, ppx, ppy, zMin, zMax, fp64, rowPitchBytes);
   }
 
   bool empty() const { return size() == 0; }
@@ -154,6 +169,20 @@ class Cloud {
 
  private:
   explicit Cloud(ppf_cloud* c) : h_(c, [](ppf_cloud* p) { ppf_cloud_release(p); }) {}
+  static Cloud fromDepthImage(const void* depth, int format, double scale, int rows, int cols, double fx, double fy, double ppx,
+                              double ppy, float zMin, float zMax, bool fp64, size_t rowPitchBytes) {
+    ppf_depth_params p;
+    ppf_default_depth_params(&p);
+    p.format = format;
+    p.flags = fp64 ? PPF_DEPTH_FP64 : 0;
+    p.depth_scale = scale;
+    p.z_min = zMin;
+    p.z_max = zMax;
+    const double intr[4] = {fx, fy, ppx, ppy};
+    ppf_cloud* c = nullptr;
+    ppf_match_3d::check(ppf_cloud_from_depth(depth, rows, cols, rowPitchBytes, intr, &p, &c));
+    return Cloud(c);
+  }
   const ppf_cloud* need() const {
     if (!h_) throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud: empty handle");
     return h_.get();

@@ -35,6 +35,9 @@
  *                                   (YOLO_cropping_ppf_test.cpp:88-127, CloudProcessing.h:495-523)
  *   ppf_prep_frame                  the same six stages for all of a frame's boxes at once (CloudProcessing.h:263-427
  *                                   return one cloud per detection)
+ *   ppf_cloud_from_depth (+_device) CloudProcessor::Deprojection(CameraIntr), an empty stub in the reference
+ *                                   (CloudProcessing.h:262): the scene cloud from the depth image, Camera::back_projection
+ *                                   (Camera.h:44-46) per valid pixel
  *
  * Conventions
  *   - A cloud argument is (pointer, rows, stride, normal_offset): float32 rows whose first three floats
@@ -408,6 +411,35 @@ ppf_status ppf_icp_refine_clouds(const ppf_cloud* model, const ppf_cloud* scene,
                                  int n_poses, int* iterations_out);
 /* exact neighbour lists (parity surface): idx, d2 are [n][k], ascending (distance, index) */
 ppf_status ppf_prep_knn(const ppf_cloud* in, int k, int* idx, float* d2);
+
+/* ---- the organised scene cloud from a depth image, on the device (what CloudProcessor::Deprojection leaves empty) -- */
+#define PPF_DEPTH_F32 0  /* float32 metres: z = value (the reference's EXR frame) */
+#define PPF_DEPTH_U16 1  /* uint16 sensor units: z = (float)((double)d * depth_scale) (Azure Kinect, RealSense) */
+#define PPF_DEPTH_FP64 1 /* flags bit: x = (float)(((double)u - ppx) * (double)z / fx) in fp64 instead of Camera::back_projection's
+                            x = (float)((double)((float)((double)u - ppx) * z) / fx); y likewise with v, ppy, fy */
+typedef struct ppf_depth_params {
+  int32_t format;     /* PPF_DEPTH_F32 | PPF_DEPTH_U16 */
+  int32_t flags;      /* 0 | PPF_DEPTH_FP64 */
+  double depth_scale; /* U16: metres per unit, > 0; ignored for F32 */
+  float z_min, z_max; /* a pixel is kept iff z is finite, z > 0, z >= z_min and (z_max == 0 or z <= z_max); z_max 0: no upper bound */
+  int32_t reserved[4];
+} ppf_depth_params;
+/* PPF_DEPTH_F32, flags 0, depth_scale 0.001, z_min 0, z_max 0 */
+void ppf_default_depth_params(ppf_depth_params* p);
+/* Back-project every kept pixel of a rows x cols depth image, intr = {fx, fy, ppx, ppy} as ppf_prep_crop takes it.  The
+ * rows of *out are x y z 0 0 0 (curvature 0) in row-major pixel order (v, then u: the order of np.nonzero(depth > 0)),
+ * byte-identical to ppf_cloud_upload of the same xyz with cols = 3; an image without a kept pixel gives an empty cloud.
+ * depth: HOST image whose rows are row_pitch_bytes apart (0: packed).  Argument errors (NULL pointers, rows or cols
+ * <= 0, rows * cols > INT32_MAX, a pitch below cols * element size or not a multiple of it, a misaligned image, an
+ * unknown format or flag, a U16 scale <= 0, fx or fy zero or not finite, ppx, ppy, z_min or z_max not finite, z_max < 0)
+ * are PPF_ERR_INVALID before any device work; on any error *out is NULL. */
+ppf_status ppf_cloud_from_depth(const void* depth, int rows, int cols, size_t row_pitch_bytes, const double* intr,
+                                const ppf_depth_params* p, ppf_cloud** out);
+/* the same from DEVICE memory: the work is enqueued on `stream` (a hipStream_t, NULL: default stream) and the call returns
+ * when the cloud is complete.  A pointer the current device cannot read, or an image that runs past the end of its
+ * allocation, is PPF_ERR_INVALID before anything is launched. */
+ppf_status ppf_cloud_from_depth_device(const void* d_depth, int rows, int cols, size_t row_pitch_bytes, const double* intr,
+                                       const ppf_depth_params* p, void* stream, ppf_cloud** out);
 
 /* ---- every detection of a frame in one segmented device pass ------------------------------------------------ */
 typedef struct ppf_frame_params {

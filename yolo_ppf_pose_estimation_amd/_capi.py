@@ -108,6 +108,15 @@ class MatchFrameStats(C.Structure):
                 ("ms_icp", C.c_float), ("reserved", C.c_int32 * 4)]
 
 
+class DepthParams(C.Structure):
+    _fields_ = [("format", C.c_int32), ("flags", C.c_int32), ("depth_scale", C.c_double), ("z_min", C.c_float),
+                ("z_max", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+PPF_DEPTH_F32, PPF_DEPTH_U16 = 0, 1
+PPF_DEPTH_FP64 = 1  # DepthParams.flags bit
+
+
 # every symbol include/ppf_hip.h declares (tests/test_capi_symbols.py checks the header against this)
 _SIGNATURES = {
     "ppf_default_train_params": (None, [C.POINTER(TrainParams)]),
@@ -196,6 +205,11 @@ _SIGNATURES = {
     "ppf_prep_frame": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
                                  C.POINTER(FrameParams), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
                                  C.POINTER(FrameStats)]),
+    "ppf_default_depth_params": (None, [C.POINTER(DepthParams)]),
+    "ppf_cloud_from_depth": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_double), C.POINTER(DepthParams),
+                                       C.POINTER(C.c_void_p)]),
+    "ppf_cloud_from_depth_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_double),
+                                              C.POINTER(DepthParams), C.c_void_p, C.POINTER(C.c_void_p)]),
     "ppf_icp_register": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }

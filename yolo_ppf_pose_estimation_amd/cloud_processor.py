@@ -33,6 +33,50 @@ class DeviceCloud:
         check(lib().ppf_cloud_upload(a.ctypes.data, a.shape[0], a.shape[1], normal_offset, cols, C.byref(out)))
         return cls(out)
 
+    @classmethod
+    def from_depth(cls, depth, intr, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0,
+                   fp64: bool = False) -> "DeviceCloud":
+        """The organised scene cloud of a depth image, back-projected on the device (ppf_cloud_from_depth): rows
+        ``x y z 0 0 0`` of every pixel with a finite z > 0 inside [z_min, z_max] (z_max 0: no upper bound), in row-major
+        pixel order.  depth: a 2-D numpy float32 (metres) or uint16 (units of depth_scale metres) array, rows read at its
+        stride; or a float32 / uint16 torch tensor on the GPU, read in place on ``torch.cuda.current_stream()``.
+        intr: (fx, fy, ppx, ppy) or the 3x3 camera matrix.  fp64=True: the fp64 formula instead of
+        Camera::back_projection's rounding (DESIGN.md §13)."""
+        K = np.asarray(intr, dtype=np.float64)
+        it = (C.c_double * 4)(*([K[0, 0], K[1, 1], K[0, 2], K[1, 2]] if K.shape == (3, 3) else [float(v) for v in K.reshape(-1)[:4]]))
+        prm = _capi.DepthParams()
+        lib().ppf_default_depth_params(C.byref(prm))
+        prm.depth_scale, prm.z_min, prm.z_max = float(depth_scale), float(z_min), float(z_max)
+        prm.flags = _capi.PPF_DEPTH_FP64 if fp64 else 0
+        out = C.c_void_p()
+        if type(depth).__module__.startswith("torch"):
+            import torch
+            if not depth.is_cuda:
+                depth = depth.numpy()
+            else:
+                fmt = {torch.float32: _capi.PPF_DEPTH_F32, torch.uint16: _capi.PPF_DEPTH_U16}.get(depth.dtype)
+                if fmt is None or depth.dim() != 2:
+                    raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 or uint16 tensor")
+                if depth.stride(1) != 1 or depth.stride(0) < depth.shape[1]:
+                    depth = depth.contiguous()
+                prm.format = fmt
+                with torch.cuda.device(depth.device):
+                    stream = torch.cuda.current_stream(depth.device).cuda_stream
+                    check(lib().ppf_cloud_from_depth_device(C.c_void_p(depth.data_ptr()), depth.shape[0], depth.shape[1],
+                                                            depth.stride(0) * depth.element_size(), it, C.byref(prm),
+                                                            C.c_void_p(stream) if stream else None, C.byref(out)))
+                return cls(out)
+        a = np.asarray(depth)
+        fmt = {np.dtype(np.float32): _capi.PPF_DEPTH_F32, np.dtype(np.uint16): _capi.PPF_DEPTH_U16}.get(a.dtype)
+        if fmt is None or a.ndim != 2:
+            raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 or uint16 array")
+        if a.strides[1] != a.itemsize or a.strides[0] < a.shape[1] * a.itemsize or a.strides[0] % a.itemsize:
+            a = np.ascontiguousarray(a)
+        prm.format = fmt
+        check(lib().ppf_cloud_from_depth(C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1], a.strides[0], it, C.byref(prm),
+                                         C.byref(out)))
+        return cls(out)
+
     def __del__(self):
         try:
             if self._ptr:
@@ -158,6 +202,15 @@ class CloudProcessor:
         self.match_frame_stats: Dict[str, float] = {}  # ppf_match_frame counters of the last MatchFrame (summed over its calls)
 
     # ---- the PCL half -------------------------------------------------------------------------------------
+    def Deprojection(self, CameraIntr, fp64: bool = False) -> DeviceCloud:
+        """The scene cloud from ``self.depth`` (float32 metres), back-projected on the device -- the reference's
+        ``Deprojection(Mat CameraIntr)`` is an empty stub (CloudProcessing.h:262).  CameraIntr: the 3x3 matrix as
+        SceneCropping takes it.  Sets and returns ``self.scene``; fp64 as in ``DeviceCloud.from_depth``."""
+        if self.depth is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "Deprojection needs a depth image")
+        self.scene = DeviceCloud.from_depth(self.depth, np.asarray(CameraIntr, dtype=np.float64), fp64=fp64)
+        return self.scene
+
     def SceneCropping(self, CameraIntr) -> List[DeviceCloud]:
         """CameraIntr: 3x3 matrix (fx, fy on the diagonal, ppx, ppy in the last column), as the reference passes it"""
         K = np.asarray(CameraIntr, dtype=np.float64)
