@@ -219,7 +219,6 @@ struct ppf_workspace {
   DevBuf<uint2> chunk_desc;
   DevBuf<unsigned long long> hit_count;
   DevBuf<double> s_a64;
-  DevBuf<uint16_t> s_cell;
   DevBuf<uint4> runs;
   DevBuf<unsigned char> tables;          /* count tables of a batch's many-hit runs (k_tables -> k_vote), TBL_BYTES each */
   DevBuf<uint2> table_desc;              /* what each table covers: {first sorted hit, hits} */

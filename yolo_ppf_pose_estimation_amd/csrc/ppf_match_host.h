@@ -149,7 +149,8 @@ ppf_workspace::~ppf_workspace() {
   if (h_sum) (void)hipHostFree(h_sum);
 }
 
-/* bytes of hit scratch one hit costs: raw {bucket, j} + sorted payload (alpha_s, cell) + its share of the run table */
+/* bytes of hit scratch one hit costs: raw {bucket, j} + sorted payload alpha_s + its share of the run table (+ 2 bytes for the
+ * cell the payload no longer carries: kept, so that the batches of reference points stay the size they were tuned at) */
 constexpr double HIT_SCRATCH_BYTES = 8.0 + 8.0 + 2.0 + 16.0 / 6.0;
 
 /* k_pairs<pair feature, surface-to-boundary>: same_cloud == 0 is match_S2B (the paired points come from the edge cloud) */
@@ -323,7 +324,6 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
   HIPCHK(ws->chunk_desc.reserve((size_t)batch * va.pair_chunks));
   HIPCHK(ws->hit_count.reserve(batch));
   HIPCHK(ws->s_a64.fit(sorted_cap));
-  HIPCHK(ws->s_cell.fit(sorted_cap));
   /* count tables: a run of c >= agg_min_hits hits takes ceil(c / AGG_SUB), so TBL_FRAC_MAX per hit is the ceiling */
   const uint32_t table_cap = !va.agg_min_hits ? 1u : (uint32_t)std::min(1.0e9, std::max(est * (worst_case ? TBL_FRAC_MAX : tbl_frac), 4.0 * batch) + 256.0);
   HIPCHK(ws->runs.fit(run_cap));
@@ -336,12 +336,12 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
   HIPCHK(ws->ovf_list.reserve((size_t)batch * T));
   va.ovf_list = ws->ovf_list.p;
   ws->stats.scratch_bytes = ws->frames.bytes() + ws->raw.bytes() + ws->cursors.bytes() + ws->chunk_desc.bytes() + ws->hit_count.bytes() +
-                            ws->s_a64.bytes() + ws->s_cell.bytes() + ws->runs.bytes() + ws->run_blocks.bytes() + ws->tables.bytes() + ws->table_desc.bytes() +
+                            ws->s_a64.bytes() + ws->runs.bytes() + ws->run_blocks.bytes() + ws->tables.bytes() + ws->table_desc.bytes() +
                             ws->work.bytes() + ws->perm.bytes() + ws->perm_group.bytes();
   va.frames = ws->frames.p;
   va.raw = ws->raw.p; va.stripe_cap = stripe_cap; va.stripe_bits = stripe_bits;
   va.chunk_desc = ws->chunk_desc.p; va.hit_count = ws->hit_count.p;
-  va.s_a64 = ws->s_a64.p; va.s_cell = ws->s_cell.p; va.sorted_cap = sorted_cap;
+  va.s_a64 = ws->s_a64.p; va.sorted_cap = sorted_cap;
   va.runs = ws->runs.p; va.run_cap = run_cap; va.run_blocks = ws->run_blocks.p;
   va.tables = ws->tables.p; va.table_desc = ws->table_desc.p; va.table_cap = table_cap;
   va.work = ws->work.p; va.perm = ws->perm.p; va.perm_group = ws->perm_group.p;
@@ -382,6 +382,9 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
     va.n_ref = std::min(batch, n_ref - base);
     if (bi) HIPCHK(hipMemsetAsync(ws->cursors.p, 0, CUR_OVERFLOW * sizeof(uint32_t), st)); /* the overflow word lives on */
     if (va.agg_min_hits) HIPCHK(hipMemsetAsync(ws->table_desc.p, 0, (size_t)table_cap * sizeof(uint2), st));
+#if PPF_ABL_GROUP != 1 /* attribution builds of k_group store no payload: the later kernels read zeros, never stale values */
+    HIPCHK(hipMemsetAsync(ws->s_a64.p, 0, ws->s_a64.bytes(), st));
+#endif
     /* a thread per reference point, and enough threads for its look at the paired points (40 waves walking 50,000 points: 10 us) */
     k_frames<<<dim3(std::max((va.n_ref + 63) / 64, std::min((va.paired.n + 63) / 64, 1024))), dim3(64), 0, st>>>(va);
     HIPCHK(hipGetLastError());

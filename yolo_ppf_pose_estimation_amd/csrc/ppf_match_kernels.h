@@ -17,11 +17,11 @@
  *
  *   k_group    one workgroup per reference point: alpha_s of every hit, counting sort of the hits by
  *              bucket (one LDS counter per bucket), the run table {bucket, first hit, m hits} (runs with
- *              many hits first) and the per-hit payload in sorted order: (float)alpha_s, alpha_s, and the
- *              hit's cell (Y, p) in units of alpha bins (see "aggregated votes").  Also gives every run of many
+ *              many hits first) and the per-hit payload alpha_s in sorted order.  Also gives every run of many
  *              hits its count tables (one per 191 hits) out of the batch's table pool and writes down what each covers.
  *
- *   k_tables   one wave per count table: histogram of the table's hits by cell, the counts an entry in each cell adds
+ *   k_tables   one wave per count table: histogram of the table's hits by cell (Y, p) in units of alpha bins (see "aggregated
+ *              votes"; computed from alpha_s), the counts an entry in each cell adds
  *              to each bin, the hits' offsets in cell order; built in LDS, copied to the pool (HBM / L2).  Once per run:
  *              k_vote meets the run again for every chunk of the bucket's records, accumulator tile and half.
  *
@@ -98,7 +98,13 @@
 #ifndef PPF_MOCK_PAIRBINS
 #define PPF_MOCK_PAIRBINS 0
 #endif
-#define PPF_ABL_ANY (PPF_ABL_COUNTED != 1 || PPF_ABL_OWNCELL != 1 || PPF_ABL_DIRECT_SMALL != 1 || PPF_ABL_DIRECT_BIG != 1 || PPF_MOCK_PAIRBINS)
+/* Attribution builds of k_group (never the product; the payload is then zero, only k_group's own times and counters mean
+ * anything): PPF_ABL_GROUP=2 leaves out the scattered payload stores, 3 also the paired-point gathers, the alpha_s arithmetic and
+ * the LDS cursor atomics (the scatter pass only walks the raw pool), 4 the whole scatter pass (profiles/r08_group_variants.md) */
+#ifndef PPF_ABL_GROUP
+#define PPF_ABL_GROUP 1
+#endif
+#define PPF_ABL_ANY (PPF_ABL_GROUP != 1 || PPF_ABL_COUNTED != 1 || PPF_ABL_OWNCELL != 1 || PPF_ABL_DIRECT_SMALL != 1 || PPF_ABL_DIRECT_BIG != 1 || PPF_MOCK_PAIRBINS)
 /* one vote for bin k of the row at LDS address p */
 __device__ __forceinline__ void vote_one(const uint32_t p, const int k, const uint32_t inc);
 
@@ -333,8 +339,7 @@ struct MatchArgs {
   uint2* chunk_desc;       /* [n_ref][pair_chunks] {first raw hit, count} of each k_pairs workgroup */
   int pair_chunks;
   unsigned long long* hit_count; /* [n_ref] raw hits (also the k_rank key of k_group's launch order) */
-  double* s_a64;           /* sorted payload: alpha_s */
-  uint16_t* s_cell;        /*                 (Y + 8) * AGG_Q + p */
+  double* s_a64;           /* sorted payload: alpha_s (the count-table builds take a hit's cell (Y + 8) * AGG_Q + p from it: hit_cell) */
   uint32_t sorted_cap;
   uint4* runs;             /* {bucket, first sorted hit, m, first count table of the run (m >= agg_min_hits)} */
   unsigned char* tables;   /* count tables, TBL_BYTES each: built by k_tables, read by k_vote */
@@ -633,7 +638,6 @@ __global__ __launch_bounds__(GROUP_BLOCK) void k_group(MatchArgs a) {
   const bool ok = sh[1] != 0;
   const double* __restrict__ fr = a.frames + (size_t)r * 12;
   const double R10 = fr[3], R11 = fr[4], R12 = fr[5], R20 = fr[6], R21 = fr[7], R22 = fr[8], ty = fr[10], tz = fr[11];
-  const double s64 = (double)a.num_angles / (4 * PPF_PI);
   const uint32_t agg_min = a.agg_min_hits > 0 ? (uint32_t)a.agg_min_hits : 0xFFFFFFFFu;
   const uint32_t n_list = ok ? n_raw : 0u;
   const bool check_alpha = a.cursors[CUR_ODDVALUES] != 0u;
@@ -753,7 +757,7 @@ __global__ __launch_bounds__(GROUP_BLOCK) void k_group(MatchArgs a) {
       }
     }
     __syncthreads();
-    {
+    if (PPF_ABL_GROUP != 4) {
       int c = 0;
       for (uint32_t g0 = tid; g0 < n_list; g0 += GROUP_MLP * GROUP_BLOCK) {
         uint2 key[GROUP_MLP];
@@ -765,6 +769,13 @@ __global__ __launch_bounds__(GROUP_BLOCK) void k_group(MatchArgs a) {
           key[u] = a.raw[cbase[c] + (gc - cpre[c])];
           if (g >= n_list) key[u].x = 0xFFFFFFFFu;
         }
+#if PPF_ABL_GROUP == 3
+        uint32_t sink = 0;
+#pragma unroll
+        for (int u = 0; u < GROUP_MLP; u++) sink += key[u].x ^ key[u].y;
+        if (sink == 0xFFFFFFFEu && tid == GROUP_BLOCK) a.tally[13] = sink; /* never true: keeps the pool reads */
+        continue;
+#endif
         double as[GROUP_MLP];
         ppf_vec3 p2[GROUP_MLP];
         bool in[GROUP_MLP];
@@ -788,8 +799,11 @@ __global__ __launch_bounds__(GROUP_BLOCK) void k_group(MatchArgs a) {
 #pragma unroll
         for (int u = 0; u < GROUP_MLP; u++) {
           if (in[u]) {
-            a.s_a64[gi[u]] = as[u];
-            a.s_cell[gi[u]] = (uint16_t)hit_cell(as[u], s64);
+#if PPF_ABL_GROUP == 2
+            if (as[u] == -1234.5 && gi[u] == 0u) a.tally[13] = gi[u]; /* never true: keeps the arithmetic */
+#else
+            a.s_a64[gi[u]] = as[u]; /* the cell is not stored: the table builds recompute it from alpha_s (hit_cell) */
+#endif
           }
         }
       }
@@ -1081,8 +1095,8 @@ struct AggConsts {
  *                                   entry in cell q adds to its bin X + 8 - j (bytes; row AGG_Q stays zero)
  *   ce[p], ce[p+1]                  range of the hits of cell p in the cell-sorted copy (offsets / index): counters behind the
  *                                   table while it is built, two bytes of row p in the table itself */
-__device__ __forceinline__ void table_build(const uint32_t ws, const float S, const float Og, const double* __restrict__ g_a64,
-                                            const uint16_t* __restrict__ g_cell, const int ms, const int lane) {
+__device__ __forceinline__ void table_build(const uint32_t ws, const float S, const float Og, const double s64, const double* __restrict__ g_a64,
+                                            const int ms, const int lane) {
   constexpr int PER = AGG_Q / 4; /* cells of one Y a lane owns in the histogram pass */
 #pragma unroll
   for (int w = 0; w < PER / 4; w++) lds_st(ws + TBL_OFF_A32 + lane * PER + w * 4, 0u); /* byte counters cnt[Y][p]: 16 x AGG_Q bytes */
@@ -1093,8 +1107,11 @@ __device__ __forceinline__ void table_build(const uint32_t ws, const float S, co
   for (int t = 0; t < 3; t++) {
     const int i = lane + 64 * t;
     const bool v = i < ms;
-    cell[t] = v ? (uint32_t)g_cell[i] : 0xFFFFu;
-    a32[t] = v ? __float_as_uint(Og - (float)g_a64[i] * S) : 0u; /* Ohg = A/2 + G - alpha_s*S of the direct arithmetic */
+    const double as = v ? g_a64[i] : 0.0;
+    /* the hit's cell from alpha_s: one fp64 multiply and floor here instead of a scattered 2-byte store per hit in k_group and its
+     * read-back (profiles/r08_group_variants.md) */
+    cell[t] = v ? hit_cell(as, s64) : 0xFFFFu;
+    a32[t] = v ? __float_as_uint(Og - (float)as * S) : 0u; /* Ohg = A/2 + G - alpha_s*S of the direct arithmetic */
   }
   wave_lds_fence();
 #pragma unroll
@@ -1191,7 +1208,7 @@ __global__ __launch_bounds__(TABLE_BLOCK) void k_tables(MatchArgs a) {
   const int A = a.num_angles;
   const double s64 = (double)A / (4 * PPF_PI);
   const float S = (float)s64, Og = (float)(0.5 * (double)A + (double)vote_guard_band(A));
-  table_build(ws, S, Og, a.s_a64 + d.x, a.s_cell + d.x, (int)d.y, lane);
+  table_build(ws, S, Og, s64, a.s_a64 + d.x, (int)d.y, lane);
   const lds_u32x4* src = (const lds_u32x4*)(uintptr_t)ws;
   uint4* __restrict__ dst = reinterpret_cast<uint4*>(a.tables + (size_t)t * TBL_BYTES);
   for (int q = lane; q < TBL_BYTES / 16; q += 64) {
