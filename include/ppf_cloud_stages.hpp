@@ -11,6 +11,7 @@
  *   PointCloudXYZNormalToMat :163-190 -> Cloud::toMat()   (an N x 6 ppf_match_3d::Mat for PPF3DDetector / ICP)
  *   all of the above for every box of a frame  ->  Cloud::prepareFrame(boxes, n, depth, ...)  (one (object, edge) pair per box)
  *   Matching_S2B + ICP for every detection     ->  Cloud::matchFrame(models, modelClouds, dets, ...)  (ICP in one launch sequence)
+ *   `// TODO: Pose Validation` (:477-479, :530-532) -> Cloud::verifyFrame(modelClouds, dets, poses, depth, ...)  (scores, best pose)
  *
  * Every stage returns a new Cloud that stays in HBM; only toMat()/download() copy to the host.  A maintainer replaces
  * the bodies of those CloudProcessor methods by these one-liners; pcl::PointCloud<PointXYZ> goes
@@ -147,6 +148,48 @@ class Cloud {
         out[i].push_back(ppf_match_3d::Pose3D(poses[i * t + (size_t)k]));
         if (iterations) (*iterations)[i].push_back(it[i * t + (size_t)k]);
       }
+    return out;
+  }
+  /* Pose validation, the reference's TODO after `return *resultsSub[0];` (CloudProcessing.h:477-479, :530-532), for every
+   * detection of a frame in one call (ppf_verify_frame): each of poses[i] (what matchFrame returns) moves modelClouds[i] and
+   * is scored against dets[i].first and, with depth != 0, against the depth image (rows x cols float32 metres, the
+   * intrinsics prepareFrame took).  Returns per detection one ppf_pose_score per pose; best (optional) receives per
+   * detection the index of the highest score (the lowest index among equal ones, -1 without poses).  params == 0:
+   * ppf_default_verify_params.  A detection with no poses, no model cloud or no object cloud is not scored. */
+  static std::vector<std::vector<ppf_pose_score> > verifyFrame(const std::vector<const Cloud*>& modelClouds,
+                                                               const std::vector<std::pair<Cloud, Cloud> >& dets,
+                                                               const std::vector<std::vector<ppf_match_3d::Pose3D> >& poses,
+                                                               const float* depth, int rows, int cols, double fx, double fy, double ppx,
+                                                               double ppy, const ppf_verify_params* params = 0,
+                                                               std::vector<int>* best = 0, ppf_verify_stats* stats = 0) {
+    const size_t nd = dets.size();
+    if (modelClouds.size() != nd || poses.size() != nd)
+      throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::verifyFrame: one model cloud and one pose list per detection");
+    size_t top = 1;
+    for (size_t i = 0; i < nd; i++) top = poses[i].size() > top ? poses[i].size() : top;
+    std::vector<ppf_frame_detection> d(nd + 1);
+    std::vector<ppf_pose> recs(nd * top + 1);
+    std::vector<int> n(nd + 1, 0);
+    for (size_t i = 0; i < nd; i++) {
+      d[i].model = 0;
+      d[i].edge = 0;
+      const bool live = modelClouds[i] && modelClouds[i]->handle() && dets[i].first.handle() && !poses[i].empty();
+      d[i].model_cloud = live ? modelClouds[i]->handle() : 0;
+      d[i].scene = live ? dets[i].first.handle() : 0;
+      n[i] = live ? (int)poses[i].size() : 0;
+      for (int k = 0; k < n[i]; k++) recs[i * top + (size_t)k] = poses[i][(size_t)k].record();
+    }
+    ppf_verify_params p;
+    if (params) p = *params;
+    else ppf_default_verify_params(&p);
+    const double intr[4] = {fx, fy, ppx, ppy};
+    std::vector<ppf_pose_score> sc(nd * top + 1);
+    std::vector<int> b(nd + 1, -1);
+    ppf_match_3d::check(ppf_verify_frame(&d[0], (int)nd, &recs[0], &n[0], (int)top, depth, rows, cols, depth ? intr : 0, &p, &sc[0], &b[0],
+                                         stats));
+    std::vector<std::vector<ppf_pose_score> > out(nd);
+    for (size_t i = 0; i < nd; i++) out[i].assign(sc.begin() + (std::ptrdiff_t)(i * top), sc.begin() + (std::ptrdiff_t)(i * top + (size_t)n[i]));
+    if (best) best->assign(b.begin(), b.begin() + (std::ptrdiff_t)nd);
     return out;
   }
   /* the N x 6 CV_32FC1-shaped Mat of PointCloudXYZNormalToMat (normals re-normalised) */

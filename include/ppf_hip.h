@@ -38,6 +38,9 @@
  *   ppf_cloud_from_depth (+_device) CloudProcessor::Deprojection(CameraIntr), an empty stub in the reference
  *                                   (CloudProcessing.h:262): the scene cloud from the depth image, Camera::back_projection
  *                                   (Camera.h:44-46) per valid pixel
+ *   ppf_verify_frame                the `// TODO: Pose Validation` after `return *resultsSub[0];` of Matching and
+ *                                   Matching_S2B (CloudProcessing.h:477-479, :530-532): scores every refined pose of
+ *                                   every detection against its object cloud (and the depth image) and picks the best
  *
  * Conventions
  *   - A cloud argument is (pointer, rows, stride, normal_offset): float32 rows whose first three floats
@@ -502,6 +505,57 @@ typedef struct ppf_match_frame_stats {
 ppf_status ppf_match_frame(const ppf_frame_detection* dets, int n_dets, const ppf_match_params* mp,
                            const ppf_icp_params* ip, int top, ppf_pose* out, int* n_out, int32_t* icp_iterations,
                            ppf_match_frame_stats* stats);
+
+/* ---- pose verification: score and re-rank the refined poses of every detection of a frame --------------------- */
+#define PPF_VERIFY_ALL_ROWS 1 /* every finite model row counts, not only those facing the camera (scenes that are not one view) */
+#define PPF_VERIFY_NORMALS 2  /* a supporting scene row must also agree in normal: cos >= normal_cos */
+
+typedef struct ppf_verify_params {
+  float inlier_dist;  /* metres, finite, > 0 */
+  float normal_cos;   /* used with PPF_VERIFY_NORMALS, in [-1, 1] */
+  float depth_tol;    /* metres, finite, > 0 (checked only with a depth image) */
+  int32_t model_step; /* rows 0, s, 2s, ... of the model cloud are scored, >= 1 */
+  int32_t flags;      /* 0 | PPF_VERIFY_ALL_ROWS | PPF_VERIFY_NORMALS */
+  int32_t reserved[4];
+} ppf_verify_params;
+
+typedef struct ppf_pose_score {
+  int32_t n_rows;       /* model rows scored: ceil(n_model / model_step) */
+  int32_t n_considered; /* finite rows that face the camera (all finite rows with PPF_VERIFY_ALL_ROWS) */
+  int32_t n_inliers;    /* considered rows with a supporting scene row */
+  int32_t n_visible;    /* considered rows that land on a valid depth pixel (0 without a depth image) */
+  int32_t n_supported, n_occluded, n_violations; /* a partition of n_visible */
+  float inlier_rmse;    /* metres */
+  float fitness;        /* n_inliers / n_considered */
+  float support;        /* n_supported / (n_visible - n_occluded); 0 without a depth image */
+  float score;          /* support with a depth image, else fitness: what `best` ranks by */
+  int32_t reserved[3];
+} ppf_pose_score;
+
+typedef struct ppf_verify_stats {
+  int32_t n_dets, n_jobs; /* detections given, poses scored */
+  int32_t n_launches;     /* kernel launches of the call */
+  int32_t n_host_syncs;   /* blocking read-backs + synchronisations of the call (host-to-device uploads not counted) */
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_verify_stats;
+
+/* inlier_dist 0.005, normal_cos 0.5, depth_tol 0.01, model_step 1, flags 0 */
+void ppf_default_verify_params(ppf_verify_params* p);
+/* Scores pose k < n_poses[i] of detection i: the rows 0, s, 2s, ... of dets[i].model_cloud are moved by poses[i * top + k]
+ * (ppf_transform_pc_pose's arithmetic) and tested against dets[i].scene (cloud support: a scene row within inlier_dist)
+ * and, when `depth` is given, against the depth image (supported / occluded / free-space violation within depth_tol);
+ * DESIGN.md §14 states every test bit for bit.  dets, poses and n_poses are what ppf_match_frame took and returned
+ * (model and edge are ignored); poses and scores are [n_dets][top], score rows with k >= n_poses[i] are zero.
+ * best[i] is the k with the largest score, the lowest k among equal ones, -1 when n_poses[i] == 0.
+ * depth: optional HOST image, float32 metres, packed depth_rows x depth_cols, intr = {fx, fy, ppx, ppy} as ppf_prep_frame
+ * takes them; NULL: no depth test (intr may then be NULL).  A pose's score row does not depend on the other poses and
+ * detections of the call.  Limits: n_dets 0..256, top 1..16, n_poses[i] 0..top.  Argument errors are PPF_ERR_INVALID
+ * before any device work; on any error every score row is zero and every best[i] is -1.  stats may be NULL.  The launch
+ * count does not depend on n_dets; the one read-back is the scores. */
+ppf_status ppf_verify_frame(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top,
+                            const float* depth, int depth_rows, int depth_cols, const double* intr,
+                            const ppf_verify_params* params, ppf_pose_score* scores, int* best, ppf_verify_stats* stats);
 
 #ifdef __cplusplus
 }

@@ -117,6 +117,25 @@ PPF_DEPTH_F32, PPF_DEPTH_U16 = 0, 1
 PPF_DEPTH_FP64 = 1  # DepthParams.flags bit
 
 
+class VerifyParams(C.Structure):
+    _fields_ = [("inlier_dist", C.c_float), ("normal_cos", C.c_float), ("depth_tol", C.c_float), ("model_step", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class PoseScore(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("n_considered", C.c_int32), ("n_inliers", C.c_int32), ("n_visible", C.c_int32),
+                ("n_supported", C.c_int32), ("n_occluded", C.c_int32), ("n_violations", C.c_int32), ("inlier_rmse", C.c_float),
+                ("fitness", C.c_float), ("support", C.c_float), ("score", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class VerifyStats(C.Structure):
+    _fields_ = [("n_dets", C.c_int32), ("n_jobs", C.c_int32), ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32),
+                ("ms_wall", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+PPF_VERIFY_ALL_ROWS, PPF_VERIFY_NORMALS = 1, 2  # VerifyParams.flags bits
+
+
 # every symbol include/ppf_hip.h declares (tests/test_capi_symbols.py checks the header against this)
 _SIGNATURES = {
     "ppf_default_train_params": (None, [C.POINTER(TrainParams)]),
@@ -210,6 +229,10 @@ _SIGNATURES = {
                                        C.POINTER(C.c_void_p)]),
     "ppf_cloud_from_depth_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_double),
                                               C.POINTER(DepthParams), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ppf_default_verify_params": (None, [C.POINTER(VerifyParams)]),
+    "ppf_verify_frame": (C.c_int, [C.POINTER(FrameDetection), C.c_int, C.POINTER(Pose), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int,
+                                   C.c_int, C.POINTER(C.c_double), C.POINTER(VerifyParams), C.POINTER(PoseScore), C.POINTER(C.c_int),
+                                   C.POINTER(VerifyStats)]),
     "ppf_icp_register": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }

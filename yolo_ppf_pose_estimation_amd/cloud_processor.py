@@ -13,7 +13,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _capi
-from ._capi import FrameDetection, FrameParams, FrameStats, IcpParams, MatchFrameStats, Pose, PPFError, check, lib
+from ._capi import (FrameDetection, FrameParams, FrameStats, IcpParams, MatchFrameStats, Pose, PoseScore, PPFError, VerifyParams,
+                    VerifyStats, check, lib)
 from .detector import ICP, PPF3DDetector, Pose3D
 
 
@@ -172,6 +173,66 @@ class DeviceCloud:
         return idx, d2
 
 
+def _intr4(intr):
+    K = np.asarray(intr, dtype=np.float64)
+    return [K[0, 0], K[1, 1], K[0, 2], K[1, 2]] if K.shape == (3, 3) else [float(v) for v in K.reshape(-1)[:4]]
+
+
+def _pose_record(p) -> Pose:
+    if isinstance(p, Pose):
+        return p
+    if isinstance(p, Pose3D):
+        return p.to_record()
+    rec = Pose()
+    rec.pose[:] = np.asarray(p, dtype=np.float64).reshape(16).tolist()
+    return rec
+
+
+def verify_frame(dets, poses, top: Optional[int] = None, depth=None, intr=None, params=None):
+    """One ppf_verify_frame call: score every pose of every detection against its object cloud and, when ``depth`` is given,
+    against the depth image.  dets: per detection a (model cloud, object cloud) pair of DeviceClouds, or
+    None; poses: per detection its poses (Pose3D, Pose records or 4x4 arrays), at most ``top`` of them (default: the
+    longest list).  depth: a 2-D float32 image in metres or None; intr: (fx, fy, ppx, ppy) or the 3x3 camera matrix.
+    params: a VerifyParams, a dict of its fields (the rest default) or None.  Returns (scores, best, stats): the
+    PoseScore rows as a numpy structured array of shape (n_dets, top) (rows past a detection's poses are zero), the best
+    index per detection (-1 without poses) and the call's counters as a dict."""
+    n = len(dets)
+    if len(poses) != n:
+        raise PPFError(_capi.PPF_ERR_INVALID, f"{len(poses)} pose lists for {n} detections")
+    counts = [len(p) if d is not None else 0 for d, p in zip(dets, poses)]
+    top = int(top) if top is not None else max([1] + counts)
+    prm = params
+    if not isinstance(prm, VerifyParams):
+        prm = VerifyParams()
+        lib().ppf_default_verify_params(C.byref(prm))
+        for key, v in (params or {}).items():
+            setattr(prm, key, v)
+    arr = (FrameDetection * max(n, 1))()
+    recs = (Pose * (max(n, 1) * top))()
+    n_poses = (C.c_int * max(n, 1))()
+    for i, (d, plist) in enumerate(zip(dets, poses)):
+        if d is None:
+            continue
+        arr[i].model_cloud, arr[i].scene = d[0]._ptr, d[1]._ptr
+        n_poses[i] = len(plist)
+        for k, p in enumerate(plist[:top]):
+            recs[i * top + k] = _pose_record(p)
+    img, it, rows, cols = None, None, 0, 0
+    if depth is not None:
+        img = np.ascontiguousarray(depth, dtype=np.float32)
+        if img.ndim != 2:
+            raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 image")
+        rows, cols = img.shape
+        it = (C.c_double * 4)(*_intr4(intr))
+    scores = (PoseScore * (max(n, 1) * top))()
+    best = (C.c_int * max(n, 1))()
+    st = VerifyStats()
+    check(lib().ppf_verify_frame(arr, n, recs, n_poses, top, img.ctypes.data if img is not None else None, rows, cols, it, C.byref(prm),
+                                 scores, best, C.byref(st)))
+    out = np.ctypeslib.as_array(scores).copy()[:n * top].reshape(n, top)
+    return out, np.array(best[:n], dtype=np.int32), _capi.stats_dict(st)
+
+
 class CloudProcessor:
     """``ppf::CloudProcessor``: holds the scene cloud, the depth image, the detector's boxes, the per-object clouds
     and the PPF detectors; every method is the reference's, in the order its driver calls them
@@ -200,6 +261,15 @@ class CloudProcessor:
         self.stage_rows: Optional[np.ndarray] = None
         self.frame_stats: Dict[str, object] = {}
         self.match_frame_stats: Dict[str, float] = {}  # ppf_match_frame counters of the last MatchFrame (summed over its calls)
+        self.frame_intr: Optional[tuple] = None  # PrepareFrame's (fx, fy, ppx, ppy)
+        # MatchFrame: per detection its refined top poses in match rank order, and the labels it was called with
+        self.frame_poses: List[List[Pose3D]] = []
+        self.frame_labels: List[Optional[str]] = []
+        # PoseValidation: the score rows (n_dets, top), the best index per detection, the call's counters
+        self.pose_scores: Optional[np.ndarray] = None
+        self.best_index: List[int] = []
+        self.verify_stats: Dict[str, object] = {}
+        self._last_refined: List[Pose3D] = []
 
     # ---- the PCL half -------------------------------------------------------------------------------------
     def Deprojection(self, CameraIntr, fp64: bool = False) -> DeviceCloud:
@@ -252,6 +322,7 @@ class CloudProcessor:
         prm = {"leaf": float(leafsize), "mean_k": int(meanK), "stddev_mul": float(Thresh), "normal_k": int(k),
                "curvature_threshold": float(curvThreshold)}
         pairs, self.stage_rows, self.frame_stats = self.scene.prep_frame(self.boxes, self.depth, intr, prm, return_info=True)
+        self.frame_intr = intr
         self.object_mats = [o for o, _ in pairs]
         self.edge_mats = [e for _, e in pairs]
         return pairs
@@ -265,14 +336,51 @@ class CloudProcessor:
         ``one_pass=False`` refines detections one after another through Matching_S2B.  Same poses either way."""
         if len(labels) != len(self.object_mats):
             raise PPFError(_capi.PPF_ERR_INVALID, f"{len(labels)} labels for {len(self.object_mats)} prepared detections")
+        self.frame_labels = list(labels)
+        self.frame_poses = [[] for _ in labels]
         if one_pass:
             return self._match_frame(labels, relativeSceneSampleStep, relativeSceneDistance)
         out: List[Optional[Pose3D]] = []
-        for name, obj, edge in zip(labels, self.object_mats, self.edge_mats):
+        for i, (name, obj, edge) in enumerate(zip(labels, self.object_mats, self.edge_mats)):
             if name is None or len(obj) == 0:
                 out.append(None)
                 continue
             out.append(self.Matching_S2B(name, obj, edge, relativeSceneSampleStep, relativeSceneDistance))
+            self.frame_poses[i] = self._last_refined
+        return out
+
+    def PoseValidation(self, min_score: float = 0.0, inlier_dist: float = 0.005, depth_tol: float = 0.01, use_depth: bool = True,
+                       all_rows: bool = False, normal_cos: Optional[float] = None) -> List[Optional[Pose3D]]:
+        """The reference's ``// TODO: Pose Validation`` (CloudProcessing.h:477-479, :530-532): one ppf_verify_frame call scores
+        every refined pose the last MatchFrame kept (``frame_poses``) against its detection's object cloud and, with
+        ``use_depth`` and a depth image, against ``self.depth``.  Returns per detection its best-scoring pose, or None
+        where the detection has no pose or its best score is below ``min_score``.  A float ``normal_cos`` also requires the
+        supporting scene row's normal to agree (cos >= normal_cos); ``all_rows`` scores every model row, not only those
+        facing the camera.  Sets ``pose_scores``, ``best_index``, ``verify_stats`` and ``timings["pose_validation"]``."""
+        dets, poses = [], []
+        for name, obj, plist in zip(self.frame_labels, self.object_mats, self.frame_poses):
+            if name is None or not plist:
+                dets.append(None)
+                poses.append([])
+                continue
+            dets.append((self._model_clouds[self.label_to_id[name]], obj))
+            poses.append(plist)
+        prm = {"inlier_dist": float(inlier_dist), "depth_tol": float(depth_tol),
+               "flags": (_capi.PPF_VERIFY_ALL_ROWS if all_rows else 0) | (_capi.PPF_VERIFY_NORMALS if normal_cos is not None else 0)}
+        if normal_cos is not None:
+            prm["normal_cos"] = float(normal_cos)
+        depth = self.depth if use_depth and self.depth is not None else None
+        t0 = time.perf_counter()
+        self.pose_scores, best, self.verify_stats = verify_frame(dets, poses, None, depth, self.frame_intr if depth is not None else None,
+                                                                 prm)
+        self.timings["pose_validation"] = time.perf_counter() - t0
+        self.best_index = [int(b) for b in best]
+        out: List[Optional[Pose3D]] = []
+        for i, b in enumerate(self.best_index):
+            if b < 0 or float(self.pose_scores[i, b]["score"]) < min_score:
+                out.append(None)
+            else:
+                out.append(self.frame_poses[i][b])
         return out
 
     def _match_frame(self, labels, step, dist, top: int = 5) -> List[Optional[Pose3D]]:
@@ -309,6 +417,7 @@ class CloudProcessor:
             for i in members:
                 if n_out[i] > 0:
                     out[i] = Pose3D(poses[i * top])
+                    self.frame_poses[i] = [Pose3D(poses[i * top + k]) for k in range(n_out[i])]
             for f, _ in MatchFrameStats._fields_:
                 if f != "reserved":
                     self.match_frame_stats[f] = self.match_frame_stats.get(f, 0) + getattr(st, f)
@@ -343,6 +452,7 @@ class CloudProcessor:
         return sub[0]
 
     def _match_resident(self, idx, det, scene: DeviceCloud, edge: Optional[DeviceCloud], step, dist) -> Optional[Pose3D]:
+        self._last_refined = []
         mp = det._params(step, dist, False)
         cap = len(scene) + 8
         out = (Pose * cap)()
@@ -361,6 +471,7 @@ class CloudProcessor:
         t0 = time.perf_counter()
         check(lib().ppf_icp_refine_clouds(self._model_clouds[idx]._ptr, scene._ptr, C.byref(prm), out, top, None))
         self.timings["icp"] = time.perf_counter() - t0
+        self._last_refined = [Pose3D(out[k]) for k in range(top)]
         return Pose3D(out[0])
 
     def Matching(self, name: str, scene: np.ndarray, relativeSceneSampleStep: float = 0.0714,

@@ -1,0 +1,191 @@
+/*
+ * ppf_verify_host.h — host side of ppf_verify_frame: score every refined pose of every detection of a frame against its
+ * object cloud and, optionally, the depth image (what the reference leaves as `// TODO: Pose Validation`,
+ * CloudProcessing.h:477-479, :530-532).  Kernels: ppf_verify_kernels.h.  Included by ppf_hip.hip after ppf_frame_host.h
+ * (FrameRun, FRAME_LAUNCH, frame_scan) and ppf_match_frame_host.h (the limits of ppf_match_frame).
+ *
+ * Per call with at least one pose: three uploads (the detection and job tables, the depth image when given), then
+ * k_vfy_grid_count, a five-launch scan, k_vfy_grid_scatter, k_vfy_score, k_vfy_finish -- nine launches whatever the number
+ * of detections -- and one read-back, the score rows.  The slot offsets of every detection's grid follow from the cloud
+ * sizes the host already knows, so building the grids needs no read-back.  Scratch comes from the block cache (FrameRun).
+ */
+namespace {
+
+ppf_status verify_check(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top, const float* depth,
+                        int depth_rows, int depth_cols, const double* intr, const ppf_verify_params* p, ppf_pose_score* scores, int* best) {
+  static const char* who = "ppf_verify_frame";
+  if (n_dets < 0 || n_dets > FRAME_MATCH_MAX_DETS) return fail(PPF_ERR_INVALID, "%s: n_dets must be in [0, %d]", who, FRAME_MATCH_MAX_DETS);
+  if (top < 1 || top > FRAME_MATCH_MAX_TOP) return fail(PPF_ERR_INVALID, "%s: top must be in [1, %d]", who, FRAME_MATCH_MAX_TOP);
+  if (!p) return fail(PPF_ERR_INVALID, "%s: params is NULL", who);
+  if (n_dets > 0 && (!dets || !poses || !n_poses || !scores || !best))
+    return fail(PPF_ERR_INVALID, "%s: dets, poses, n_poses, scores and best must not be NULL", who);
+  for (int i = 0; i < n_dets; i++) {
+    if (n_poses[i] < 0 || n_poses[i] > top) return fail(PPF_ERR_INVALID, "%s: n_poses[%d] = %d is outside [0, top]", who, i, n_poses[i]);
+    if (n_poses[i] > 0 && (!dets[i].model_cloud || !dets[i].scene))
+      return fail(PPF_ERR_INVALID, "%s: detection %d has poses but no model cloud or scene", who, i);
+  }
+  if (!(std::isfinite(p->inlier_dist) && p->inlier_dist > 0.f)) return fail(PPF_ERR_INVALID, "%s: inlier_dist must be finite and > 0", who);
+  if (!(p->normal_cos >= -1.f && p->normal_cos <= 1.f)) return fail(PPF_ERR_INVALID, "%s: normal_cos must be in [-1, 1]", who);
+  if (!(std::isfinite(p->depth_tol) && p->depth_tol > 0.f)) return fail(PPF_ERR_INVALID, "%s: depth_tol must be finite and > 0", who);
+  if (p->model_step < 1) return fail(PPF_ERR_INVALID, "%s: model_step must be >= 1", who);
+  if (p->flags & ~(PPF_VERIFY_ALL_ROWS | PPF_VERIFY_NORMALS)) return fail(PPF_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)p->flags);
+  if (depth) {
+    if (depth_rows <= 0 || depth_cols <= 0) return fail(PPF_ERR_INVALID, "%s: the depth image is %d x %d", who, depth_rows, depth_cols);
+    if ((long long)depth_rows * depth_cols > 0x7fffffffLL)
+      return fail(PPF_ERR_INVALID, "%s: %d x %d pixels exceed INT32_MAX", who, depth_rows, depth_cols);
+    if (!intr) return fail(PPF_ERR_INVALID, "%s: a depth image needs intr", who);
+    if (!std::isfinite(intr[0]) || !std::isfinite(intr[1]) || intr[0] == 0.0 || intr[1] == 0.0)
+      return fail(PPF_ERR_INVALID, "%s: fx and fy must be finite and non-zero", who);
+    if (!std::isfinite(intr[2]) || !std::isfinite(intr[3])) return fail(PPF_ERR_INVALID, "%s: ppx and ppy must be finite", who);
+  }
+  return PPF_OK;
+}
+
+/* grids -> scores -> one read-back; dev[j] = the score row of job j on the host */
+ppf_status verify_run(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top, const float* depth,
+                      int depth_rows, int depth_cols, const double* intr, const ppf_verify_params* p, std::vector<ppf_pose_score>& dev,
+                      FrameRun& fr) {
+  /* live detections (with poses) and their slots; the jobs */
+  std::vector<VfyDet> hd;
+  std::vector<VfyJob> hj;
+  std::vector<int> det_of((size_t)n_dets, -1);
+  size_t slots = 0, rows = 0;
+  int max_scene = 0, max_nb = 1;
+  for (int i = 0; i < n_dets; i++) {
+    if (n_poses[i] == 0) continue;
+    VfyDet d;
+    d.rows = dets[i].scene->rows.p;
+    d.n = dets[i].scene->n;
+    const uint32_t s = next_pow2((uint32_t)std::max(64, 2 * d.n));
+    d.slot_off = (uint32_t)slots;
+    d.slot_mask = s - 1;
+    d.row_off = (uint32_t)rows;
+    slots += s;
+    rows += (size_t)d.n;
+    max_scene = std::max(max_scene, d.n);
+    det_of[i] = (int)hd.size();
+    hd.push_back(d);
+    const int n_model = dets[i].model_cloud->n;
+    const int n_rows = (int)(((long long)n_model + p->model_step - 1) / p->model_step);
+    for (int k = 0; k < n_poses[i]; k++) {
+      VfyJob j;
+      std::memcpy(j.T, poses[(size_t)i * top + k].pose, sizeof(j.T));
+      j.model = dets[i].model_cloud->rows.p;
+      j.scene = d.rows;
+      j.n_rows = n_rows;
+      j.nb = (n_rows + VFY_BLOCK - 1) / VFY_BLOCK;
+      j.det = det_of[i];
+      j.pad = 0;
+      max_nb = std::max(max_nb, j.nb);
+      hj.push_back(j);
+    }
+  }
+  if (slots + 1 > 0xffffffffull || rows > 0xffffffffull) return fail(PPF_ERR_CAPACITY, "ppf_verify_frame: the scene clouds are too large");
+  const int nd = (int)hd.size(), nj = (int)hj.size();
+  VfyDet* d_dets;
+  VfyJob* d_jobs;
+  uint32_t *counts, *start, *rank;
+  float4* pts;
+  VfyPartial* part;
+  ppf_pose_score* d_out;
+  float* d_depth = nullptr;
+  ppf_status s;
+  if ((s = fr.get(nd, &d_dets)) != PPF_OK || (s = fr.get(nj, &d_jobs)) != PPF_OK || (s = fr.get(slots + 1, &counts)) != PPF_OK ||
+      (s = fr.get(slots + 1, &start)) != PPF_OK || (s = fr.get(rows, &rank)) != PPF_OK || (s = fr.get(rows, &pts)) != PPF_OK ||
+      (s = fr.get((size_t)nj * max_nb, &part)) != PPF_OK || (s = fr.get(nj, &d_out)) != PPF_OK)
+    return s;
+  if (depth && (s = fr.get((size_t)depth_rows * depth_cols, &d_depth)) != PPF_OK) return s;
+  HIPCHK(hipMemcpy(d_dets, hd.data(), hd.size() * sizeof(VfyDet), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_jobs, hj.data(), hj.size() * sizeof(VfyJob), hipMemcpyHostToDevice));
+  if (depth) HIPCHK(hipMemcpy(d_depth, depth, (size_t)depth_rows * depth_cols * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(counts, 0, (slots + 1) * sizeof(uint32_t), nullptr));
+  const double inv_h = 1.0 / ((double)p->inlier_dist * VFY_CELL_MARGIN);
+  const dim3 grid_rows(grid_for((size_t)max_scene, 256).x, (unsigned)nd);
+  FRAME_LAUNCH(fr, k_vfy_grid_count, grid_rows, dim3(256), d_dets, inv_h, counts, rank);
+  if ((s = frame_scan(fr, counts, start, slots + 1)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_vfy_grid_scatter, grid_rows, dim3(256), d_dets, inv_h, start, rank, pts);
+  VfyArgs a;
+  a.dets = d_dets;
+  a.jobs = d_jobs;
+  a.slot_start = start;
+  a.pts = pts;
+  a.depth = d_depth;
+  a.rows = depth ? depth_rows : 0;
+  a.cols = depth ? depth_cols : 0;
+  a.fx = depth ? intr[0] : 0.0;
+  a.fy = depth ? intr[1] : 0.0;
+  a.ppx = depth ? intr[2] : 0.0;
+  a.ppy = depth ? intr[3] : 0.0;
+  a.inv_h = inv_h;
+  a.r2 = p->inlier_dist * p->inlier_dist;
+  a.normal_cos = p->normal_cos;
+  a.depth_tol = p->depth_tol;
+  a.step = p->model_step;
+  a.all_rows = (p->flags & PPF_VERIFY_ALL_ROWS) ? 1 : 0;
+  a.normals = (p->flags & PPF_VERIFY_NORMALS) ? 1 : 0;
+  a.max_nb = max_nb;
+  FRAME_LAUNCH(fr, k_vfy_score, dim3((unsigned)max_nb, (unsigned)nj), dim3(VFY_BLOCK), a, part);
+  FRAME_LAUNCH(fr, k_vfy_finish, dim3((unsigned)nj), dim3(64), d_jobs, part, max_nb, depth ? 1 : 0, d_out);
+  HIPCHK(hipGetLastError());
+  dev.resize((size_t)nj);
+  return fr.read(dev.data(), d_out, (size_t)nj * sizeof(ppf_pose_score));
+}
+
+}  // namespace
+
+extern "C" {
+
+void ppf_default_verify_params(ppf_verify_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->inlier_dist = 0.005f;
+  p->normal_cos = 0.5f;
+  p->depth_tol = 0.01f;
+  p->model_step = 1;
+  p->flags = 0;
+}
+
+ppf_status ppf_verify_frame(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top,
+                            const float* depth, int depth_rows, int depth_cols, const double* intr, const ppf_verify_params* params,
+                            ppf_pose_score* scores, int* best, ppf_verify_stats* stats) {
+  static const char* who = "ppf_verify_frame";
+  const auto t0 = std::chrono::steady_clock::now();
+  ppf_verify_stats local;
+  ppf_verify_stats& st = stats ? *stats : local;
+  std::memset(&st, 0, sizeof(st));
+  /* on any error every score row is zero and every best[i] is -1: clear what the valid part of the arguments lets us reach */
+  const bool can_clear = n_dets > 0 && n_dets <= FRAME_MATCH_MAX_DETS && top >= 1 && top <= FRAME_MATCH_MAX_TOP;
+  if (can_clear && scores) std::memset(scores, 0, (size_t)n_dets * top * sizeof(ppf_pose_score));
+  if (can_clear && best)
+    for (int i = 0; i < n_dets; i++) best[i] = -1;
+  ppf_status s = verify_check(dets, n_dets, poses, n_poses, top, depth, depth_rows, depth_cols, intr, params, scores, best);
+  if (s != PPF_OK) return s;
+  st.n_dets = n_dets;
+  if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
+  std::vector<int> job_det;
+  for (int i = 0; i < n_dets; i++) {
+    if (n_poses[i] > 0 && dets[i].model_cloud->n <= 0) return fail(PPF_ERR_INVALID, "%s: detection %d has an empty model cloud", who, i);
+    for (int k = 0; k < n_poses[i]; k++) job_det.push_back(i);
+  }
+  if (!job_det.empty()) {
+    std::vector<ppf_pose_score> dev;
+    {
+      FrameRun fr; /* the scratch goes back to the block cache after the read-back */
+      s = verify_run(dets, n_dets, poses, n_poses, top, depth, depth_rows, depth_cols, intr, params, dev, fr);
+      st.n_launches = fr.launches;
+      st.n_host_syncs = fr.syncs;
+      if (s != PPF_OK) return s;
+    }
+    size_t j = 0;
+    for (int i = 0; i < n_dets; i++)
+      for (int k = 0; k < n_poses[i]; k++) {
+        scores[(size_t)i * top + k] = dev[j++];
+        if (best[i] < 0 || scores[(size_t)i * top + k].score > scores[(size_t)i * top + best[i]].score) best[i] = k;
+      }
+    st.n_jobs = (int)job_det.size();
+  }
+  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PPF_OK;
+}
+
+}  // extern "C"
