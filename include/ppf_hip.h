@@ -211,16 +211,14 @@ typedef struct ppf_icp_params {
   float tolerance;       /* arg 2 (0.005f) */
   float rejection_scale; /* arg 3 (2.5f); <= 0 disables the median+MAD rejection */
   int32_t num_levels;    /* arg 4 (8) */
-  int32_t flags;         /* 0: all poses of a call advance through the same launches, two per iteration, neighbours from a
-                            grid search.  PPF_ICP_LEGACY: the earlier schedule (one stream per pose, seven launches per
-                            iteration, exhaustive neighbour search); with it PPF_ICP_NO_SMALL_LEVELS (coarse levels kernel by
-                            kernel instead of in one workgroup) and PPF_ICP_ONE_STREAM (the poses share the caller's stream).
-                            Same results whichever way (tests/test_gpu_robustness.py). */
+  int32_t flags;         /* all poses of a call advance through the same launches, two per iteration, neighbours from a
+                            grid search.  PPF_ICP_NO_SMALL_LEVELS, PPF_ICP_ONE_STREAM and PPF_ICP_LEGACY are accepted and
+                            ignored: they selected an earlier schedule, since removed, that gave the same results. */
   int32_t reserved[3];
 } ppf_icp_params;
-#define PPF_ICP_NO_SMALL_LEVELS 1
-#define PPF_ICP_ONE_STREAM 2
-#define PPF_ICP_LEGACY 4
+#define PPF_ICP_NO_SMALL_LEVELS 1 /* accepted and ignored */
+#define PPF_ICP_ONE_STREAM 2      /* accepted and ignored */
+#define PPF_ICP_LEGACY 4          /* accepted and ignored */
 #define PPF_ICP_GRID_ALWAYS 8 /* test knob: the grid neighbour search on every level (by default levels of at most 1,024 scene rows scan them all) */
 
 void ppf_default_train_params(ppf_train_params* p);
@@ -501,7 +499,7 @@ typedef struct ppf_match_frame_stats {
  * without a model.  Argument errors are reported before any device work; on any error every n_out[i] is 0.
  * The ICP poses of all detections advance through one launch sequence of up to 256 poses (its launch count does not
  * depend on how many detections share it); a call with more poses runs sequences of 256 one after another.  The match
- * phase reads back per detection.  ip->flags PPF_ICP_LEGACY: detection after detection, same results. */
+ * phase reads back per detection. */
 ppf_status ppf_match_frame(const ppf_frame_detection* dets, int n_dets, const ppf_match_params* mp,
                            const ppf_icp_params* ip, int top, ppf_pose* out, int* n_out, int32_t* icp_iterations,
                            ppf_match_frame_stats* stats);

@@ -31,7 +31,6 @@ if [ "$WHAT" = lines ] || [ "$WHAT" = benchlines ]; then
   # the reference's real call and its ICP: timings and the ICP kernels' trace
   python tools/pipeline_timing.py > "$OUT/pipeline_timing.json" 2> "$OUT/pipeline_timing.err"
   python tools/icp_timing.py --repeat 5 > "$OUT/icp_timing.json" 2> "$OUT/icp_timing.err"
-  python tools/icp_timing.py --repeat 5 --legacy > "$OUT/icp_timing_legacy.json" 2>> "$OUT/icp_timing.err"
   ( cd /tmp && export TMPDIR=/tmp
     rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/trace_icp" -o icp -- python3 "$ROOT/tools/icp_timing.py" --repeat 3 > "$ROOT/$OUT/trace_icp.log" 2>&1 )
   echo "pipeline and ICP done"

@@ -58,7 +58,7 @@ def main():
             s = json.loads(summary)
             print(w, "k_vote fabric GB/s %.0f" % s["hbm_gbs_k_vote"], {k: round(v, 3) for k, v in s["k_vote_issue"].items() if isinstance(v, float) and v < 10})
     # the reference's real call (frame -> pose) and its ICP step
-    for n in ("pipeline_timing", "icp_timing", "icp_timing_legacy"):
+    for n in ("pipeline_timing", "icp_timing"):
         q = os.path.join(src, n + ".json")
         if os.path.exists(q):
             open(os.path.join(ROOT, "profiles", f"{tag}_{n}.json"), "w").write(last_line(q) + "\n")

@@ -21,39 +21,6 @@ bool frame_det_live(const ppf_frame_detection& d) {
   return d.model && d.scene->n > 0 && (!d.edge || d.edge->n > 0);
 }
 
-/* the per-detection route: ppf_match_clouds then ppf_icp_refine_clouds (PPF_ICP_LEGACY) */
-ppf_status frame_match_loop(const ppf_frame_detection* dets, int n_dets, const ppf_match_params* mp, const ppf_icp_params* ip, int top,
-                            ppf_pose* out, int* n_out, int32_t* icp_iterations, ppf_match_frame_stats* st) {
-  std::vector<ppf_pose> buf;
-  std::vector<int> it;
-  for (int i = 0; i < n_dets; i++) {
-    const ppf_frame_detection& d = dets[i];
-    if (!frame_det_live(d)) continue;
-    buf.resize((size_t)d.scene->n + 8);
-    int n = 0;
-    const int sync0 = g_host_syncs;
-    const auto t0 = std::chrono::steady_clock::now();
-    ppf_status s = ppf_match_clouds(d.model, d.scene, d.edge, mp, buf.data(), (int)buf.size(), &n);
-    if (s != PPF_OK) return s;
-    const auto t1 = std::chrono::steady_clock::now();
-    st->n_host_syncs += g_host_syncs - sync0;
-    st->ms_match += std::chrono::duration<float, std::milli>(t1 - t0).count();
-    const int k = std::min(top, n);
-    if (k == 0) continue;
-    it.assign((size_t)k, 0);
-    s = ppf_icp_refine_clouds(d.model_cloud, d.scene, ip, buf.data(), k, it.data());
-    if (s != PPF_OK) return s;
-    st->ms_icp += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
-    memcpy(out + (size_t)i * top, buf.data(), (size_t)k * sizeof(ppf_pose));
-    if (icp_iterations) memcpy(icp_iterations + (size_t)i * top, it.data(), (size_t)k * sizeof(int32_t));
-    n_out[i] = k;
-    st->n_matched++;
-    st->n_icp_jobs += k;
-  }
-  return PPF_OK;
-}
-
-/* the one-pass route */
 ppf_status frame_match_segmented(const ppf_frame_detection* dets, int n_dets, const ppf_match_params* mp, const ppf_icp_params* ip,
                                  int top, ppf_pose* out, int* n_out, int32_t* icp_iterations, ppf_match_frame_stats* st) {
   const int sync0 = g_host_syncs;
@@ -164,10 +131,7 @@ ppf_status ppf_match_frame(const ppf_frame_detection* dets, int n_dets, const pp
   std::memset(out, 0, (size_t)n_dets * top * sizeof(ppf_pose));
   if (icp_iterations) std::memset(icp_iterations, 0, (size_t)n_dets * top * sizeof(int32_t));
   ppf_status s = PPF_OK;
-  if (n_dets > 0) {
-    if (ip->flags & PPF_ICP_LEGACY) s = frame_match_loop(dets, n_dets, mp, ip, top, out, n_out, icp_iterations, &st);
-    else s = frame_match_segmented(dets, n_dets, mp, ip, top, out, n_out, icp_iterations, &st);
-  }
+  if (n_dets > 0) s = frame_match_segmented(dets, n_dets, mp, ip, top, out, n_out, icp_iterations, &st);
   if (s != PPF_OK)
     for (int i = 0; i < n_dets; i++) n_out[i] = 0;
   st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -400,7 +400,7 @@ class ICP:
                  *, flags: int = 0):
         self._prm = IcpParams()
         lib().ppf_default_icp_params(C.byref(self._prm))
-        self._prm.flags = int(flags)  # _capi.PPF_ICP_NO_SMALL_LEVELS | PPF_ICP_ONE_STREAM: other schedules, same results
+        self._prm.flags = int(flags)  # _capi.PPF_ICP_GRID_ALWAYS (a test knob); the other PPF_ICP_* flags are accepted and ignored
         self._prm.iterations, self._prm.tolerance = int(iterations), float(tolerance)
         self._prm.rejection_scale, self._prm.num_levels = float(rejectionScale), int(numLevels)
         self.last_iterations: List[int] = []
