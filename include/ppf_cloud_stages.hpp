@@ -12,6 +12,8 @@
  *   all of the above for every box of a frame  ->  Cloud::prepareFrame(boxes, n, depth, ...)  (one (object, edge) pair per box)
  *   Matching_S2B + ICP for every detection     ->  Cloud::matchFrame(models, modelClouds, dets, ...)  (ICP in one launch sequence)
  *   `// TODO: Pose Validation` (:477-479, :530-532) -> Cloud::verifyFrame(modelClouds, dets, poses, depth, ...)  (scores, best pose)
+ *                                                     Cloud::verifyFrameRendered(...)  (the same with self-occlusion)
+ *   transformPCPose -> writePLY of the result       ->  Cloud::renderFrame(modelClouds, poses, best, ...)  (depth, label images)
  *
  * Every stage returns a new Cloud that stays in HBM; only toMat()/download() copy to the host.  A maintainer replaces
  * the bodies of those CloudProcessor methods by these one-liners; pcl::PointCloud<PointXYZ> goes
@@ -191,6 +193,88 @@ class Cloud {
     for (size_t i = 0; i < nd; i++) out[i].assign(sc.begin() + (std::ptrdiff_t)(i * top), sc.begin() + (std::ptrdiff_t)(i * top + (size_t)n[i]));
     if (best) best->assign(b.begin(), b.begin() + (std::ptrdiff_t)nd);
     return out;
+  }
+  /* verifyFrame with self-occlusion (ppf_verify_frame_rendered): a model row counts only where it is visible in a surfel
+   * z-buffer of its own pose, rows x cols with the intrinsics prepareFrame took.  depth may be 0 (no depth test); the image
+   * size is then still what the render draws into.  rparams == 0: ppf_default_render_params.  PPF_VERIFY_ALL_ROWS is
+   * refused.  Otherwise as verifyFrame. */
+  static std::vector<std::vector<ppf_pose_score> > verifyFrameRendered(const std::vector<const Cloud*>& modelClouds,
+                                                                       const std::vector<std::pair<Cloud, Cloud> >& dets,
+                                                                       const std::vector<std::vector<ppf_match_3d::Pose3D> >& poses,
+                                                                       const float* depth, int rows, int cols, double fx, double fy,
+                                                                       double ppx, double ppy, const ppf_verify_params* params = 0,
+                                                                       const ppf_render_params* rparams = 0, std::vector<int>* best = 0,
+                                                                       ppf_verify_stats* stats = 0) {
+    const size_t nd = dets.size();
+    if (modelClouds.size() != nd || poses.size() != nd)
+      throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::verifyFrameRendered: one model cloud and one pose list per detection");
+    size_t top = 1;
+    for (size_t i = 0; i < nd; i++) top = poses[i].size() > top ? poses[i].size() : top;
+    std::vector<ppf_frame_detection> d(nd + 1);
+    std::vector<ppf_pose> recs(nd * top + 1);
+    std::vector<int> n(nd + 1, 0);
+    for (size_t i = 0; i < nd; i++) {
+      d[i].model = 0;
+      d[i].edge = 0;
+      const bool live = modelClouds[i] && modelClouds[i]->handle() && dets[i].first.handle() && !poses[i].empty();
+      d[i].model_cloud = live ? modelClouds[i]->handle() : 0;
+      d[i].scene = live ? dets[i].first.handle() : 0;
+      n[i] = live ? (int)poses[i].size() : 0;
+      for (int k = 0; k < n[i]; k++) recs[i * top + (size_t)k] = poses[i][(size_t)k].record();
+    }
+    ppf_verify_params p;
+    if (params) p = *params;
+    else ppf_default_verify_params(&p);
+    ppf_render_params rp;
+    if (rparams) rp = *rparams;
+    else ppf_default_render_params(&rp);
+    const double intr[4] = {fx, fy, ppx, ppy};
+    std::vector<ppf_pose_score> sc(nd * top + 1);
+    std::vector<int> b(nd + 1, -1);
+    ppf_match_3d::check(ppf_verify_frame_rendered(&d[0], (int)nd, &recs[0], &n[0], (int)top, depth, rows, cols, intr, &p, &rp, &sc[0],
+                                                  &b[0], stats));
+    std::vector<std::vector<ppf_pose_score> > out(nd);
+    for (size_t i = 0; i < nd; i++) out[i].assign(sc.begin() + (std::ptrdiff_t)(i * top), sc.begin() + (std::ptrdiff_t)(i * top + (size_t)n[i]));
+    if (best) best->assign(b.begin(), b.begin() + (std::ptrdiff_t)nd);
+    return out;
+  }
+  /* Depth and instance-label images of one chosen pose per detection (ppf_render_frame), in place of the reference's
+   * transformPCPose -> writePLY dump: poses[i][which[i]] moves modelClouds[i] (which[i] < 0, or no model cloud: not drawn;
+   * the best of verifyFrame / verifyFrameRendered plugs in), drawn as surfel disks into one rows x cols z-buffer.
+   * depthOut (metres, 0 where empty) and labelOut (the detection index, -1 where empty) are resized to rows x cols; either
+   * may be 0.  rparams == 0: ppf_default_render_params. */
+  static void renderFrame(const std::vector<const Cloud*>& modelClouds, const std::vector<std::vector<ppf_match_3d::Pose3D> >& poses,
+                          const std::vector<int>& which, int rows, int cols, double fx, double fy, double ppx, double ppy,
+                          std::vector<float>* depthOut, std::vector<int32_t>* labelOut, const ppf_render_params* rparams = 0,
+                          ppf_render_stats* stats = 0) {
+    const size_t nd = poses.size();
+    if (modelClouds.size() != nd || which.size() != nd)
+      throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::renderFrame: one model cloud and one pose index per detection");
+    size_t top = 1;
+    for (size_t i = 0; i < nd; i++) top = poses[i].size() > top ? poses[i].size() : top;
+    std::vector<ppf_frame_detection> d(nd + 1);
+    std::vector<ppf_pose> recs(nd * top + 1);
+    std::vector<int> w(nd + 1, -1);
+    for (size_t i = 0; i < nd; i++) {
+      d[i].model = 0;
+      d[i].scene = 0;
+      d[i].edge = 0;
+      const bool live = modelClouds[i] && modelClouds[i]->handle() && which[i] >= 0;
+      d[i].model_cloud = live ? modelClouds[i]->handle() : 0;
+      if (live && (size_t)which[i] >= poses[i].size())
+        throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::renderFrame: which[i] is past the detection's poses");
+      w[i] = live ? which[i] : -1;
+      for (size_t k = 0; k < poses[i].size(); k++) recs[i * top + k] = poses[i][k].record();
+    }
+    ppf_render_params rp;
+    if (rparams) rp = *rparams;
+    else ppf_default_render_params(&rp);
+    const double intr[4] = {fx, fy, ppx, ppy};
+    const size_t npx = rows > 0 && cols > 0 ? (size_t)rows * (size_t)cols : 0;
+    if (depthOut) depthOut->assign(npx, 0.f);
+    if (labelOut) labelOut->assign(npx, -1);
+    ppf_match_3d::check(ppf_render_frame(&d[0], (int)nd, &recs[0], &w[0], (int)top, rows, cols, intr, &rp,
+                                         depthOut && npx ? &(*depthOut)[0] : 0, labelOut && npx ? &(*labelOut)[0] : 0, stats));
   }
   /* the N x 6 CV_32FC1-shaped Mat of PointCloudXYZNormalToMat (normals re-normalised) */
   ppf_match_3d::Mat toMat() const {

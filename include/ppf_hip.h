@@ -41,6 +41,10 @@
  *   ppf_verify_frame                the `// TODO: Pose Validation` after `return *resultsSub[0];` of Matching and
  *                                   Matching_S2B (CloudProcessing.h:477-479, :530-532): scores every refined pose of
  *                                   every detection against its object cloud (and the depth image) and picks the best
+ *   ppf_verify_frame_rendered       the same with self-occlusion: a model row counts only where it is visible in a surfel
+ *                                   z-buffer of its own pose (the reference has no pose validation at all)
+ *   ppf_render_frame                depth and instance-label images of the chosen poses, in place of the reference's
+ *                                   transformPCPose -> writePLY dump of the result (YOLO_cropping_ppf_test.cpp:125-127)
  *
  * Conventions
  *   - A cloud argument is (pointer, rows, stride, normal_offset): float32 rows whose first three floats
@@ -554,6 +558,46 @@ void ppf_default_verify_params(ppf_verify_params* p);
 ppf_status ppf_verify_frame(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top,
                             const float* depth, int depth_rows, int depth_cols, const double* intr,
                             const ppf_verify_params* params, ppf_pose_score* scores, int* best, ppf_verify_stats* stats);
+
+/* ---- surfel z-buffers of posed model clouds: self-occlusion-aware verification, depth and label images ---------- */
+#define PPF_RENDER_MAX_SPLAT 8 /* a rendered row's candidate pixels reach at most this far from its centre pixel */
+
+typedef struct ppf_render_params {
+  float splat_radius; /* metres, finite, > 0: the surfel disk radius */
+  float visible_tol;  /* metres, finite, > 0: a row is visible when z <= zbuf + visible_tol at its centre pixel */
+  int32_t flags;      /* 0; reserved */
+  int32_t reserved[4];
+} ppf_render_params;
+
+typedef struct ppf_render_stats {
+  int32_t n_dets, n_jobs; /* detections given, poses rendered */
+  int32_t n_launches;     /* kernel launches of the call */
+  int32_t n_host_syncs;   /* blocking read-backs + synchronisations of the call (host-to-device uploads not counted) */
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_render_stats;
+
+/* splat_radius 0.003, visible_tol 0.005, flags 0 */
+void ppf_default_render_params(ppf_render_params* p);
+/* ppf_verify_frame with self-occlusion: every row of dets[i].model_cloud moved by a pose is drawn as a
+ * disk of splat_radius into a z-buffer of that pose alone (depth_rows x depth_cols, intr), and a scored row is
+ * considered only when it is finite, faces the camera and is visible there (z <= zbuf + visible_tol at its centre pixel,
+ * or that pixel is empty).  Everything else, the arguments, limits and outputs included, is ppf_verify_frame's, except:
+ * the image size and intr are always required (depth may still be NULL: no depth test), fx and fy must be > 0, and
+ * PPF_VERIFY_ALL_ROWS is PPF_ERR_INVALID.  Two blocking read-backs: the pose windows, then the scores. */
+ppf_status ppf_verify_frame_rendered(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top,
+                                     const float* depth, int depth_rows, int depth_cols, const double* intr,
+                                     const ppf_verify_params* params, const ppf_render_params* rparams, ppf_pose_score* scores,
+                                     int* best, ppf_verify_stats* stats);
+/* One z-buffer of rows x cols pixels (intr = {fx, fy, ppx, ppy}) for pose which[i] of every detection i with
+ * which[i] >= 0 (poses is [n_dets][top] as ppf_match_frame returns it; best of either verify entry plugs in as which),
+ * with the surfel coverage of ppf_verify_frame_rendered; equal depths go to the lowest detection index.  depth_out
+ * (float32 metres, 0 where empty) and label_out (the detection index, -1 where empty) are packed HOST images and may
+ * each be NULL.  Limits: n_dets 0..256, top 1..16, which[i] in [-1, top).  Argument errors are PPF_ERR_INVALID before
+ * any device work; on any error the given images are all 0 and all -1.  stats may be NULL. */
+ppf_status ppf_render_frame(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* which, int top, int rows,
+                            int cols, const double* intr, const ppf_render_params* rparams, float* depth_out, int32_t* label_out,
+                            ppf_render_stats* stats);
 
 #ifdef __cplusplus
 }

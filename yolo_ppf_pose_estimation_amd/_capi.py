@@ -136,6 +136,18 @@ class VerifyStats(C.Structure):
 PPF_VERIFY_ALL_ROWS, PPF_VERIFY_NORMALS = 1, 2  # VerifyParams.flags bits
 
 
+class RenderParams(C.Structure):
+    _fields_ = [("splat_radius", C.c_float), ("visible_tol", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class RenderStats(C.Structure):
+    _fields_ = [("n_dets", C.c_int32), ("n_jobs", C.c_int32), ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32),
+                ("ms_wall", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+PPF_RENDER_MAX_SPLAT = 8  # include/ppf_hip.h
+
+
 # every symbol include/ppf_hip.h declares (tests/test_capi_symbols.py checks the header against this)
 _SIGNATURES = {
     "ppf_default_train_params": (None, [C.POINTER(TrainParams)]),
@@ -233,6 +245,12 @@ _SIGNATURES = {
     "ppf_verify_frame": (C.c_int, [C.POINTER(FrameDetection), C.c_int, C.POINTER(Pose), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int,
                                    C.c_int, C.POINTER(C.c_double), C.POINTER(VerifyParams), C.POINTER(PoseScore), C.POINTER(C.c_int),
                                    C.POINTER(VerifyStats)]),
+    "ppf_default_render_params": (None, [C.POINTER(RenderParams)]),
+    "ppf_verify_frame_rendered": (C.c_int, [C.POINTER(FrameDetection), C.c_int, C.POINTER(Pose), C.POINTER(C.c_int), C.c_int, C.c_void_p,
+                                            C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(VerifyParams), C.POINTER(RenderParams),
+                                            C.POINTER(PoseScore), C.POINTER(C.c_int), C.POINTER(VerifyStats)]),
+    "ppf_render_frame": (C.c_int, [C.POINTER(FrameDetection), C.c_int, C.POINTER(Pose), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
+                                   C.POINTER(C.c_double), C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.POINTER(RenderStats)]),
     "ppf_icp_register": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }

@@ -13,8 +13,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _capi
-from ._capi import (FrameDetection, FrameParams, FrameStats, IcpParams, MatchFrameStats, Pose, PoseScore, PPFError, VerifyParams,
-                    VerifyStats, check, lib)
+from ._capi import (FrameDetection, FrameParams, FrameStats, IcpParams, MatchFrameStats, Pose, PoseScore, PPFError, RenderParams,
+                    RenderStats, VerifyParams, VerifyStats, check, lib)
 from .detector import ICP, PPF3DDetector, Pose3D
 
 
@@ -188,6 +188,48 @@ def _pose_record(p) -> Pose:
     return rec
 
 
+def _verify_params(params) -> VerifyParams:
+    if isinstance(params, VerifyParams):
+        return params
+    prm = VerifyParams()
+    lib().ppf_default_verify_params(C.byref(prm))
+    for key, v in (params or {}).items():
+        setattr(prm, key, v)
+    return prm
+
+
+def _render_params(params) -> RenderParams:
+    if isinstance(params, RenderParams):
+        return params
+    prm = RenderParams()
+    lib().ppf_default_render_params(C.byref(prm))
+    for key, v in (params or {}).items():
+        setattr(prm, key, v)
+    return prm
+
+
+def _frame_tables(dets, poses, top):
+    """the FrameDetection, Pose and count arrays of one call: dets[i] is (model cloud, object cloud) or None"""
+    n = len(dets)
+    if len(poses) != n:
+        raise PPFError(_capi.PPF_ERR_INVALID, f"{len(poses)} pose lists for {n} detections")
+    counts = [len(p) if d is not None else 0 for d, p in zip(dets, poses)]
+    top = int(top) if top is not None else max([1] + counts)
+    arr = (FrameDetection * max(n, 1))()
+    recs = (Pose * (max(n, 1) * top))()
+    n_poses = (C.c_int * max(n, 1))()
+    for i, (d, plist) in enumerate(zip(dets, poses)):
+        if d is None:
+            continue
+        arr[i].model_cloud = d[0]._ptr
+        if d[1] is not None:
+            arr[i].scene = d[1]._ptr
+        n_poses[i] = len(plist)
+        for k, p in enumerate(plist[:top]):
+            recs[i * top + k] = _pose_record(p)
+    return n, top, arr, recs, n_poses
+
+
 def verify_frame(dets, poses, top: Optional[int] = None, depth=None, intr=None, params=None):
     """One ppf_verify_frame call: score every pose of every detection against its object cloud and, when ``depth`` is given,
     against the depth image.  dets: per detection a (model cloud, object cloud) pair of DeviceClouds, or
@@ -196,27 +238,8 @@ def verify_frame(dets, poses, top: Optional[int] = None, depth=None, intr=None, 
     params: a VerifyParams, a dict of its fields (the rest default) or None.  Returns (scores, best, stats): the
     PoseScore rows as a numpy structured array of shape (n_dets, top) (rows past a detection's poses are zero), the best
     index per detection (-1 without poses) and the call's counters as a dict."""
-    n = len(dets)
-    if len(poses) != n:
-        raise PPFError(_capi.PPF_ERR_INVALID, f"{len(poses)} pose lists for {n} detections")
-    counts = [len(p) if d is not None else 0 for d, p in zip(dets, poses)]
-    top = int(top) if top is not None else max([1] + counts)
-    prm = params
-    if not isinstance(prm, VerifyParams):
-        prm = VerifyParams()
-        lib().ppf_default_verify_params(C.byref(prm))
-        for key, v in (params or {}).items():
-            setattr(prm, key, v)
-    arr = (FrameDetection * max(n, 1))()
-    recs = (Pose * (max(n, 1) * top))()
-    n_poses = (C.c_int * max(n, 1))()
-    for i, (d, plist) in enumerate(zip(dets, poses)):
-        if d is None:
-            continue
-        arr[i].model_cloud, arr[i].scene = d[0]._ptr, d[1]._ptr
-        n_poses[i] = len(plist)
-        for k, p in enumerate(plist[:top]):
-            recs[i * top + k] = _pose_record(p)
+    n, top, arr, recs, n_poses = _frame_tables(dets, poses, top)
+    prm = _verify_params(params)
     img, it, rows, cols = None, None, 0, 0
     if depth is not None:
         img = np.ascontiguousarray(depth, dtype=np.float32)
@@ -231,6 +254,57 @@ def verify_frame(dets, poses, top: Optional[int] = None, depth=None, intr=None, 
                                  scores, best, C.byref(st)))
     out = np.ctypeslib.as_array(scores).copy()[:n * top].reshape(n, top)
     return out, np.array(best[:n], dtype=np.int32), _capi.stats_dict(st)
+
+
+def verify_frame_rendered(dets, poses, top: Optional[int] = None, depth=None, intr=None, params=None, render_params=None,
+                          image_size=None):
+    """One ppf_verify_frame_rendered call: verify_frame, with a model row considered only where it is visible in a surfel
+    z-buffer of its own pose.  The render needs the image: ``image_size`` (rows, cols) and ``intr`` are
+    required when ``depth`` is None, and default to the depth image's size otherwise.  render_params: a RenderParams, a
+    dict of its fields (the rest default) or None.  Returns (scores, best, stats) as verify_frame does."""
+    n, top, arr, recs, n_poses = _frame_tables(dets, poses, top)
+    prm, rprm = _verify_params(params), _render_params(render_params)
+    img = None
+    if depth is not None:
+        img = np.ascontiguousarray(depth, dtype=np.float32)
+        if img.ndim != 2:
+            raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 image")
+        if image_size is not None and tuple(image_size) != img.shape:
+            raise PPFError(_capi.PPF_ERR_INVALID, f"image_size {tuple(image_size)} is not the depth image's {img.shape}")
+        rows, cols = img.shape
+    elif image_size is not None:
+        rows, cols = (int(v) for v in image_size)
+    else:
+        raise PPFError(_capi.PPF_ERR_INVALID, "verify_frame_rendered needs a depth image or image_size")
+    it = (C.c_double * 4)(*_intr4(intr)) if intr is not None else None
+    scores = (PoseScore * (max(n, 1) * top))()
+    best = (C.c_int * max(n, 1))()
+    st = VerifyStats()
+    check(lib().ppf_verify_frame_rendered(arr, n, recs, n_poses, top, img.ctypes.data if img is not None else None, rows, cols, it,
+                                          C.byref(prm), C.byref(rprm), scores, best, C.byref(st)))
+    out = np.ctypeslib.as_array(scores).copy()[:n * top].reshape(n, top)
+    return out, np.array(best[:n], dtype=np.int32), _capi.stats_dict(st)
+
+
+def render_frame(dets, poses, which, rows: int, cols: int, intr, render_params=None, top: Optional[int] = None, return_stats: bool = False):
+    """One ppf_render_frame call: pose ``which[i]`` of detection i (skipped where -1 or where dets[i] is None) drawn as
+    surfel disks into one rows x cols z-buffer.  dets: per detection a model cloud (DeviceCloud), a
+    (model cloud, anything) pair, or None; poses: per detection its poses as verify_frame takes them; which: the
+    ``best`` of either verify entry plugs in.  Returns (depth, label): float32 metres with 0 where empty and int32
+    detection indices with -1 where empty; with ``return_stats`` also the call's counters."""
+    pairs = [None if d is None else (d[0] if isinstance(d, tuple) else d, None) for d in dets]
+    n, top, arr, recs, _ = _frame_tables(pairs, poses, top)
+    if len(which) != n:
+        raise PPFError(_capi.PPF_ERR_INVALID, f"{len(which)} entries of which for {n} detections")
+    ws = (C.c_int * max(n, 1))(*[int(w) if pairs[i] is not None else -1 for i, w in enumerate(which)])
+    rprm = _render_params(render_params)
+    it = (C.c_double * 4)(*_intr4(intr)) if intr is not None else None
+    depth = np.zeros((max(int(rows), 0), max(int(cols), 0)), dtype=np.float32)
+    label = np.full(depth.shape, -1, dtype=np.int32)
+    st = RenderStats()
+    check(lib().ppf_render_frame(arr, n, recs, ws, top, int(rows), int(cols), it, C.byref(rprm), depth.ctypes.data, label.ctypes.data,
+                                 C.byref(st)))
+    return (depth, label, _capi.stats_dict(st)) if return_stats else (depth, label)
 
 
 class CloudProcessor:
@@ -269,6 +343,8 @@ class CloudProcessor:
         self.pose_scores: Optional[np.ndarray] = None
         self.best_index: List[int] = []
         self.verify_stats: Dict[str, object] = {}
+        self.kept_index: List[int] = []  # per detection the pose PoseValidation kept, -1 where it kept none
+        self.render_stats: Dict[str, object] = {}  # RenderFrame: the ppf_render_frame counters
         self._last_refined: List[Pose3D] = []
 
     # ---- the PCL half -------------------------------------------------------------------------------------
@@ -350,13 +426,19 @@ class CloudProcessor:
         return out
 
     def PoseValidation(self, min_score: float = 0.0, inlier_dist: float = 0.005, depth_tol: float = 0.01, use_depth: bool = True,
-                       all_rows: bool = False, normal_cos: Optional[float] = None) -> List[Optional[Pose3D]]:
+                       all_rows: bool = False, normal_cos: Optional[float] = None, *, visibility: str = "facing",
+                       render_params=None) -> List[Optional[Pose3D]]:
         """The reference's ``// TODO: Pose Validation`` (CloudProcessing.h:477-479, :530-532): one ppf_verify_frame call scores
         every refined pose the last MatchFrame kept (``frame_poses``) against its detection's object cloud and, with
         ``use_depth`` and a depth image, against ``self.depth``.  Returns per detection its best-scoring pose, or None
         where the detection has no pose or its best score is below ``min_score``.  A float ``normal_cos`` also requires the
         supporting scene row's normal to agree (cos >= normal_cos); ``all_rows`` scores every model row, not only those
-        facing the camera.  Sets ``pose_scores``, ``best_index``, ``verify_stats`` and ``timings["pose_validation"]``."""
+        facing the camera.  ``visibility="rendered"`` calls ppf_verify_frame_rendered instead: a model row also has to be
+        visible in a surfel z-buffer of its own pose at ``self.depth``'s size (self-occlusion, DESIGN.md §15;
+        ``render_params`` as render_frame takes them; not with ``all_rows``).  Sets ``pose_scores``, ``best_index``,
+        ``verify_stats`` and ``timings["pose_validation"]``."""
+        if visibility not in ("facing", "rendered"):
+            raise PPFError(_capi.PPF_ERR_INVALID, f"visibility must be 'facing' or 'rendered', not {visibility!r}")
         dets, poses = [], []
         for name, obj, plist in zip(self.frame_labels, self.object_mats, self.frame_poses):
             if name is None or not plist:
@@ -371,8 +453,14 @@ class CloudProcessor:
             prm["normal_cos"] = float(normal_cos)
         depth = self.depth if use_depth and self.depth is not None else None
         t0 = time.perf_counter()
-        self.pose_scores, best, self.verify_stats = verify_frame(dets, poses, None, depth, self.frame_intr if depth is not None else None,
-                                                                 prm)
+        if visibility == "rendered":
+            if self.depth is None:
+                raise PPFError(_capi.PPF_ERR_INVALID, "PoseValidation(visibility='rendered') renders at the depth image's size")
+            self.pose_scores, best, self.verify_stats = verify_frame_rendered(dets, poses, None, depth, self.frame_intr, prm, render_params,
+                                                                              image_size=self.depth.shape)
+        else:
+            self.pose_scores, best, self.verify_stats = verify_frame(dets, poses, None, depth,
+                                                                     self.frame_intr if depth is not None else None, prm)
         self.timings["pose_validation"] = time.perf_counter() - t0
         self.best_index = [int(b) for b in best]
         out: List[Optional[Pose3D]] = []
@@ -381,7 +469,21 @@ class CloudProcessor:
                 out.append(None)
             else:
                 out.append(self.frame_poses[i][b])
+        self.kept_index = [self.best_index[i] if p is not None else -1 for i, p in enumerate(out)]
         return out
+
+    def RenderFrame(self, render_params=None):
+        """Depth and instance-label images of the poses the last PoseValidation kept (one ppf_render_frame call at
+        ``self.depth``'s size): float32 metres with 0 where no model covers a pixel, and the detection
+        index with -1 there.  Sets ``render_stats`` and ``timings["render_frame"]``; returns (depth, label)."""
+        if self.depth is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "RenderFrame renders at the depth image's size")
+        dets = [None if w < 0 else self._model_clouds[self.label_to_id[self.frame_labels[i]]] for i, w in enumerate(self.kept_index)]
+        t0 = time.perf_counter()
+        depth, label, self.render_stats = render_frame(dets, self.frame_poses, self.kept_index, self.depth.shape[0], self.depth.shape[1],
+                                                       self.frame_intr, render_params, return_stats=True)
+        self.timings["render_frame"] = time.perf_counter() - t0
+        return depth, label
 
     def _match_frame(self, labels, step, dist, top: int = 5) -> List[Optional[Pose3D]]:
         dets = (FrameDetection * max(len(labels), 1))()

@@ -1,0 +1,254 @@
+/*
+ * ppf_render_host.h — host side of ppf_verify_frame_rendered (pose verification with self-occlusion) and ppf_render_frame
+ * (depth and instance-label images of the chosen poses).  Kernels: ppf_render_kernels.h.  Included by ppf_hip.hip after
+ * ppf_verify_host.h (verify_check, verify_tables, verify_args).
+ *
+ * ppf_verify_frame_rendered, per call with at least one pose: the verify tables and grids (seven launches), then
+ * k_rnd_window and the first read-back (each job's window), the window table upload, k_rnd_splat into one scratch of the
+ * summed window sizes, k_rnd_vfy_score, k_vfy_finish and the second read-back (the score rows): eleven launches whatever
+ * the number of detections.
+ * ppf_render_frame, per call with at least one chosen pose: one upload of the job table, k_rnd_splat_frame into a
+ * rows x cols u64 buffer, k_rnd_resolve, one read-back of both images.  Scratch comes from the block cache (FrameRun).
+ */
+namespace {
+
+ppf_status render_params_check(const ppf_render_params* rp, const char* who) {
+  if (!rp) return fail(PPF_ERR_INVALID, "%s: rparams is NULL", who);
+  if (!(std::isfinite(rp->splat_radius) && rp->splat_radius > 0.f)) return fail(PPF_ERR_INVALID, "%s: splat_radius must be finite and > 0", who);
+  if (!(std::isfinite(rp->visible_tol) && rp->visible_tol > 0.f)) return fail(PPF_ERR_INVALID, "%s: visible_tol must be finite and > 0", who);
+  if (rp->flags != 0) return fail(PPF_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)rp->flags);
+  return PPF_OK;
+}
+
+/* the image a render draws into: rows x cols > 0, at most INT32_MAX pixels, fx and fy finite and > 0, ppx and ppy finite */
+ppf_status render_image_check(int rows, int cols, const double* intr, const char* who) {
+  if (rows <= 0 || cols <= 0) return fail(PPF_ERR_INVALID, "%s: the image is %d x %d", who, rows, cols);
+  if ((long long)rows * cols > 0x7fffffffLL) return fail(PPF_ERR_INVALID, "%s: %d x %d pixels exceed INT32_MAX", who, rows, cols);
+  if (!intr) return fail(PPF_ERR_INVALID, "%s: intr is NULL", who);
+  if (!(std::isfinite(intr[0]) && std::isfinite(intr[1]) && intr[0] > 0.0 && intr[1] > 0.0))
+    return fail(PPF_ERR_INVALID, "%s: fx and fy must be finite and > 0", who);
+  if (!std::isfinite(intr[2]) || !std::isfinite(intr[3])) return fail(PPF_ERR_INVALID, "%s: ppx and ppy must be finite", who);
+  return PPF_OK;
+}
+
+RndCam render_cam(int rows, int cols, const double* intr, const ppf_render_params* rp) {
+  RndCam c;
+  c.rows = rows;
+  c.cols = cols;
+  c.fx = intr[0];
+  c.fy = intr[1];
+  c.ppx = intr[2];
+  c.ppy = intr[3];
+  c.r = (double)rp->splat_radius;
+  c.tol = rp->visible_tol;
+  return c;
+}
+
+/* tables and grids -> windows (read-back 1) -> per-job renders -> scores (read-back 2); dev[j] = the score row of job j */
+ppf_status verify_rendered_run(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top,
+                               const float* depth, int rows, int cols, const double* intr, const ppf_verify_params* p,
+                               const ppf_render_params* rp, std::vector<ppf_pose_score>& dev, FrameRun& fr) {
+  static const char* who = "ppf_verify_frame_rendered";
+  VfyTables t;
+  ppf_status s = verify_tables(dets, n_dets, poses, n_poses, top, p, who, t, fr);
+  if (s != PPF_OK) return s;
+  /* the render jobs: the same poses, every model row */
+  std::vector<RndJob> rj((size_t)t.nj);
+  int max_n = 1;
+  {
+    size_t j = 0;
+    for (int i = 0; i < n_dets; i++)
+      for (int k = 0; k < n_poses[i]; k++, j++) {
+        std::memcpy(rj[j].T, poses[(size_t)i * top + k].pose, sizeof(rj[j].T));
+        rj[j].model = dets[i].model_cloud->rows.p;
+        rj[j].n = dets[i].model_cloud->n;
+        rj[j].label = i;
+        max_n = std::max(max_n, rj[j].n);
+      }
+  }
+  RndJob* d_rj;
+  RndWin* d_win;
+  int* d_box;
+  VfyPartial* part;
+  ppf_pose_score* d_out;
+  float* d_depth = nullptr;
+  if ((s = fr.get(t.nj, &d_rj)) != PPF_OK || (s = fr.get(t.nj, &d_win)) != PPF_OK || (s = fr.get((size_t)t.nj * 4, &d_box)) != PPF_OK ||
+      (s = fr.get((size_t)t.nj * t.max_nb, &part)) != PPF_OK || (s = fr.get(t.nj, &d_out)) != PPF_OK)
+    return s;
+  if (depth && (s = fr.get((size_t)rows * cols, &d_depth)) != PPF_OK) return s;
+  HIPCHK(hipMemcpy(d_rj, rj.data(), rj.size() * sizeof(RndJob), hipMemcpyHostToDevice));
+  if (depth) HIPCHK(hipMemcpy(d_depth, depth, (size_t)rows * cols * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(d_box, 0x80, (size_t)t.nj * 4 * sizeof(int), nullptr));
+  const RndCam cam = render_cam(rows, cols, intr, rp);
+  const dim3 grid_jobs(grid_for((size_t)max_n, RND_BLOCK).x, (unsigned)t.nj);
+  FRAME_LAUNCH(fr, k_rnd_window, grid_jobs, dim3(RND_BLOCK), d_rj, cam, d_box);
+  HIPCHK(hipGetLastError());
+  std::vector<int> box((size_t)t.nj * 4);
+  if ((s = fr.read(box.data(), d_box, box.size() * sizeof(int))) != PPF_OK) return s;
+  /* each job's window at its offset in one scratch of the summed sizes */
+  std::vector<RndWin> win((size_t)t.nj);
+  unsigned long long total = 0;
+  for (int j = 0; j < t.nj; j++) {
+    const int* b = &box[(size_t)j * 4];
+    RndWin& w = win[(size_t)j];
+    w.u0 = -b[0];
+    w.v0 = -b[1];
+    const bool empty = b[2] < w.u0 || b[3] < w.v0; /* a job without a rendered row keeps the preset */
+    w.w = empty ? 0 : b[2] - w.u0 + 1;
+    w.h = empty ? 0 : b[3] - w.v0 + 1;
+    if (empty) w.u0 = w.v0 = 0;
+    w.off = total;
+    total += (unsigned long long)w.w * (unsigned long long)w.h;
+  }
+  uint32_t* zbuf;
+  if ((s = fr.get((size_t)total, &zbuf)) != PPF_OK) return s;
+  HIPCHK(hipMemcpy(d_win, win.data(), win.size() * sizeof(RndWin), hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(zbuf, 0xff, (size_t)std::max<unsigned long long>(total, 1) * sizeof(uint32_t), nullptr));
+  FRAME_LAUNCH(fr, k_rnd_splat, grid_jobs, dim3(RND_BLOCK), d_rj, d_win, cam, zbuf);
+  const VfyArgs a = verify_args(t, d_depth, rows, cols, intr, p);
+  RndView rv;
+  rv.wins = d_win;
+  rv.zbuf = zbuf;
+  rv.c = cam;
+  FRAME_LAUNCH(fr, k_rnd_vfy_score, dim3((unsigned)t.max_nb, (unsigned)t.nj), dim3(VFY_BLOCK), a, rv, part);
+  FRAME_LAUNCH(fr, k_vfy_finish, dim3((unsigned)t.nj), dim3(64), t.d_jobs, part, t.max_nb, depth ? 1 : 0, d_out);
+  HIPCHK(hipGetLastError());
+  dev.resize((size_t)t.nj);
+  return fr.read(dev.data(), d_out, (size_t)t.nj * sizeof(ppf_pose_score));
+}
+
+ppf_status render_frame_run(const std::vector<RndJob>& jobs, int rows, int cols, const double* intr, const ppf_render_params* rp,
+                            float* depth_out, int32_t* label_out, FrameRun& fr) {
+  const size_t npx = (size_t)rows * cols;
+  int max_n = 1;
+  for (const RndJob& j : jobs) max_n = std::max(max_n, j.n);
+  RndJob* d_jobs;
+  unsigned long long* zbuf;
+  float* img; /* depth then label, one read-back */
+  ppf_status s;
+  if ((s = fr.get(jobs.size(), &d_jobs)) != PPF_OK || (s = fr.get(npx, &zbuf)) != PPF_OK || (s = fr.get(2 * npx, &img)) != PPF_OK) return s;
+  HIPCHK(hipMemcpy(d_jobs, jobs.data(), jobs.size() * sizeof(RndJob), hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(zbuf, 0xff, npx * sizeof(unsigned long long), nullptr));
+  const RndCam cam = render_cam(rows, cols, intr, rp);
+  FRAME_LAUNCH(fr, k_rnd_splat_frame, dim3(grid_for((size_t)max_n, RND_BLOCK).x, (unsigned)jobs.size()), dim3(RND_BLOCK), d_jobs, cam, zbuf);
+  FRAME_LAUNCH(fr, k_rnd_resolve, grid_for(npx, 256), dim3(256), zbuf, npx, img, (int32_t*)(img + npx));
+  HIPCHK(hipGetLastError());
+  std::vector<float> host(2 * npx);
+  if ((s = fr.read(host.data(), img, 2 * npx * sizeof(float))) != PPF_OK) return s;
+  if (depth_out) std::memcpy(depth_out, host.data(), npx * sizeof(float));
+  if (label_out) std::memcpy(label_out, host.data() + npx, npx * sizeof(int32_t));
+  return PPF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void ppf_default_render_params(ppf_render_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->splat_radius = 0.003f;
+  p->visible_tol = 0.005f;
+  p->flags = 0;
+}
+
+ppf_status ppf_verify_frame_rendered(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top,
+                                     const float* depth, int depth_rows, int depth_cols, const double* intr,
+                                     const ppf_verify_params* params, const ppf_render_params* rparams, ppf_pose_score* scores,
+                                     int* best, ppf_verify_stats* stats) {
+  static const char* who = "ppf_verify_frame_rendered";
+  const auto t0 = std::chrono::steady_clock::now();
+  ppf_verify_stats local;
+  ppf_verify_stats& st = stats ? *stats : local;
+  std::memset(&st, 0, sizeof(st));
+  const bool can_clear = n_dets > 0 && n_dets <= FRAME_MATCH_MAX_DETS && top >= 1 && top <= FRAME_MATCH_MAX_TOP;
+  if (can_clear && scores) std::memset(scores, 0, (size_t)n_dets * top * sizeof(ppf_pose_score));
+  if (can_clear && best)
+    for (int i = 0; i < n_dets; i++) best[i] = -1;
+  ppf_status s = verify_check(dets, n_dets, poses, n_poses, top, depth, depth_rows, depth_cols, intr, params, scores, best, who);
+  if (s != PPF_OK) return s;
+  if (params->flags & PPF_VERIFY_ALL_ROWS)
+    return fail(PPF_ERR_INVALID, "%s: PPF_VERIFY_ALL_ROWS has no meaning against one view's z-buffer", who);
+  if ((s = render_image_check(depth_rows, depth_cols, intr, who)) != PPF_OK || (s = render_params_check(rparams, who)) != PPF_OK) return s;
+  st.n_dets = n_dets;
+  if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
+  int n_jobs = 0;
+  for (int i = 0; i < n_dets; i++) {
+    if (n_poses[i] > 0 && dets[i].model_cloud->n <= 0) return fail(PPF_ERR_INVALID, "%s: detection %d has an empty model cloud", who, i);
+    n_jobs += n_poses[i];
+  }
+  if (n_jobs > 0) {
+    std::vector<ppf_pose_score> dev;
+    {
+      FrameRun fr; /* the scratch goes back to the block cache after the read-back */
+      s = verify_rendered_run(dets, n_dets, poses, n_poses, top, depth, depth_rows, depth_cols, intr, params, rparams, dev, fr);
+      st.n_launches = fr.launches;
+      st.n_host_syncs = fr.syncs;
+      if (s != PPF_OK) return s;
+    }
+    size_t j = 0;
+    for (int i = 0; i < n_dets; i++)
+      for (int k = 0; k < n_poses[i]; k++) {
+        scores[(size_t)i * top + k] = dev[j++];
+        if (best[i] < 0 || scores[(size_t)i * top + k].score > scores[(size_t)i * top + best[i]].score) best[i] = k;
+      }
+    st.n_jobs = n_jobs;
+  }
+  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PPF_OK;
+}
+
+ppf_status ppf_render_frame(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* which, int top, int rows,
+                            int cols, const double* intr, const ppf_render_params* rparams, float* depth_out, int32_t* label_out,
+                            ppf_render_stats* stats) {
+  static const char* who = "ppf_render_frame";
+  const auto t0 = std::chrono::steady_clock::now();
+  ppf_render_stats local;
+  ppf_render_stats& st = stats ? *stats : local;
+  std::memset(&st, 0, sizeof(st));
+  /* on any error the given images are empty: clear what the size arguments let us reach */
+  if (rows > 0 && cols > 0 && (long long)rows * cols <= 0x7fffffffLL) {
+    const size_t npx = (size_t)rows * cols;
+    if (depth_out) std::memset(depth_out, 0, npx * sizeof(float));
+    if (label_out) std::fill(label_out, label_out + npx, -1);
+  }
+  if (n_dets < 0 || n_dets > FRAME_MATCH_MAX_DETS) return fail(PPF_ERR_INVALID, "%s: n_dets must be in [0, %d]", who, FRAME_MATCH_MAX_DETS);
+  if (top < 1 || top > FRAME_MATCH_MAX_TOP) return fail(PPF_ERR_INVALID, "%s: top must be in [1, %d]", who, FRAME_MATCH_MAX_TOP);
+  ppf_status s;
+  if ((s = render_image_check(rows, cols, intr, who)) != PPF_OK || (s = render_params_check(rparams, who)) != PPF_OK) return s;
+  if (n_dets > 0 && (!dets || !poses || !which)) return fail(PPF_ERR_INVALID, "%s: dets, poses and which must not be NULL", who);
+  for (int i = 0; i < n_dets; i++) {
+    if (which[i] < -1 || which[i] >= top) return fail(PPF_ERR_INVALID, "%s: which[%d] = %d is outside [-1, top)", who, i, which[i]);
+    if (which[i] >= 0 && !dets[i].model_cloud) return fail(PPF_ERR_INVALID, "%s: detection %d is chosen but has no model cloud", who, i);
+  }
+  st.n_dets = n_dets;
+  if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
+  std::vector<RndJob> jobs;
+  for (int i = 0; i < n_dets; i++) {
+    if (which[i] < 0) continue;
+    if (dets[i].model_cloud->n <= 0) return fail(PPF_ERR_INVALID, "%s: detection %d has an empty model cloud", who, i);
+    RndJob j;
+    std::memcpy(j.T, poses[(size_t)i * top + which[i]].pose, sizeof(j.T));
+    j.model = dets[i].model_cloud->rows.p;
+    j.n = dets[i].model_cloud->n;
+    j.label = i;
+    jobs.push_back(j);
+  }
+  if (!jobs.empty()) {
+    FrameRun fr;
+    s = render_frame_run(jobs, rows, cols, intr, rparams, depth_out, label_out, fr);
+    st.n_launches = fr.launches;
+    st.n_host_syncs = fr.syncs;
+    if (s != PPF_OK) {
+      const size_t npx = (size_t)rows * cols;
+      if (depth_out) std::memset(depth_out, 0, npx * sizeof(float));
+      if (label_out) std::fill(label_out, label_out + npx, -1);
+      return s;
+    }
+    st.n_jobs = (int)jobs.size();
+  }
+  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PPF_OK;
+}
+
+}  // extern "C"

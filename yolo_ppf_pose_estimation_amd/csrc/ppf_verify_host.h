@@ -12,8 +12,8 @@
 namespace {
 
 ppf_status verify_check(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top, const float* depth,
-                        int depth_rows, int depth_cols, const double* intr, const ppf_verify_params* p, ppf_pose_score* scores, int* best) {
-  static const char* who = "ppf_verify_frame";
+                        int depth_rows, int depth_cols, const double* intr, const ppf_verify_params* p, ppf_pose_score* scores, int* best,
+                        const char* who = "ppf_verify_frame") {
   if (n_dets < 0 || n_dets > FRAME_MATCH_MAX_DETS) return fail(PPF_ERR_INVALID, "%s: n_dets must be in [0, %d]", who, FRAME_MATCH_MAX_DETS);
   if (top < 1 || top > FRAME_MATCH_MAX_TOP) return fail(PPF_ERR_INVALID, "%s: top must be in [1, %d]", who, FRAME_MATCH_MAX_TOP);
   if (!p) return fail(PPF_ERR_INVALID, "%s: params is NULL", who);
@@ -41,13 +41,23 @@ ppf_status verify_check(const ppf_frame_detection* dets, int n_dets, const ppf_p
   return PPF_OK;
 }
 
-/* grids -> scores -> one read-back; dev[j] = the score row of job j on the host */
-ppf_status verify_run(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top, const float* depth,
-                      int depth_rows, int depth_cols, const double* intr, const ppf_verify_params* p, std::vector<ppf_pose_score>& dev,
-                      FrameRun& fr) {
+/* what the scoring needs on the device: the detection and job tables and every live detection's grid */
+struct VfyTables {
+  std::vector<VfyJob> hj;
+  VfyDet* d_dets = nullptr;
+  VfyJob* d_jobs = nullptr;
+  uint32_t* start = nullptr;
+  float4* pts = nullptr;
+  int nd = 0, nj = 0, max_nb = 1;
+  double inv_h = 0.0;
+};
+
+/* the tables (uploaded) and the grids (k_vfy_grid_count, frame_scan, k_vfy_grid_scatter): seven launches, no read-back */
+ppf_status verify_tables(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top,
+                         const ppf_verify_params* p, const char* who, VfyTables& t, FrameRun& fr) {
   /* live detections (with poses) and their slots; the jobs */
   std::vector<VfyDet> hd;
-  std::vector<VfyJob> hj;
+  std::vector<VfyJob>& hj = t.hj;
   std::vector<int> det_of((size_t)n_dets, -1);
   size_t slots = 0, rows = 0;
   int max_scene = 0, max_nb = 1;
@@ -80,55 +90,70 @@ ppf_status verify_run(const ppf_frame_detection* dets, int n_dets, const ppf_pos
       hj.push_back(j);
     }
   }
-  if (slots + 1 > 0xffffffffull || rows > 0xffffffffull) return fail(PPF_ERR_CAPACITY, "ppf_verify_frame: the scene clouds are too large");
-  const int nd = (int)hd.size(), nj = (int)hj.size();
-  VfyDet* d_dets;
-  VfyJob* d_jobs;
-  uint32_t *counts, *start, *rank;
-  float4* pts;
-  VfyPartial* part;
-  ppf_pose_score* d_out;
-  float* d_depth = nullptr;
+  if (slots + 1 > 0xffffffffull || rows > 0xffffffffull) return fail(PPF_ERR_CAPACITY, "%s: the scene clouds are too large", who);
+  t.nd = (int)hd.size();
+  t.nj = (int)hj.size();
+  t.max_nb = max_nb;
+  uint32_t *counts, *rank;
   ppf_status s;
-  if ((s = fr.get(nd, &d_dets)) != PPF_OK || (s = fr.get(nj, &d_jobs)) != PPF_OK || (s = fr.get(slots + 1, &counts)) != PPF_OK ||
-      (s = fr.get(slots + 1, &start)) != PPF_OK || (s = fr.get(rows, &rank)) != PPF_OK || (s = fr.get(rows, &pts)) != PPF_OK ||
-      (s = fr.get((size_t)nj * max_nb, &part)) != PPF_OK || (s = fr.get(nj, &d_out)) != PPF_OK)
+  if ((s = fr.get(t.nd, &t.d_dets)) != PPF_OK || (s = fr.get(t.nj, &t.d_jobs)) != PPF_OK || (s = fr.get(slots + 1, &counts)) != PPF_OK ||
+      (s = fr.get(slots + 1, &t.start)) != PPF_OK || (s = fr.get(rows, &rank)) != PPF_OK || (s = fr.get(rows, &t.pts)) != PPF_OK)
     return s;
-  if (depth && (s = fr.get((size_t)depth_rows * depth_cols, &d_depth)) != PPF_OK) return s;
-  HIPCHK(hipMemcpy(d_dets, hd.data(), hd.size() * sizeof(VfyDet), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_jobs, hj.data(), hj.size() * sizeof(VfyJob), hipMemcpyHostToDevice));
-  if (depth) HIPCHK(hipMemcpy(d_depth, depth, (size_t)depth_rows * depth_cols * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(t.d_dets, hd.data(), hd.size() * sizeof(VfyDet), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(t.d_jobs, hj.data(), hj.size() * sizeof(VfyJob), hipMemcpyHostToDevice));
   HIPCHK(hipMemsetAsync(counts, 0, (slots + 1) * sizeof(uint32_t), nullptr));
-  const double inv_h = 1.0 / ((double)p->inlier_dist * VFY_CELL_MARGIN);
-  const dim3 grid_rows(grid_for((size_t)max_scene, 256).x, (unsigned)nd);
-  FRAME_LAUNCH(fr, k_vfy_grid_count, grid_rows, dim3(256), d_dets, inv_h, counts, rank);
-  if ((s = frame_scan(fr, counts, start, slots + 1)) != PPF_OK) return s;
-  FRAME_LAUNCH(fr, k_vfy_grid_scatter, grid_rows, dim3(256), d_dets, inv_h, start, rank, pts);
+  t.inv_h = 1.0 / ((double)p->inlier_dist * VFY_CELL_MARGIN);
+  const dim3 grid_rows(grid_for((size_t)max_scene, 256).x, (unsigned)t.nd);
+  FRAME_LAUNCH(fr, k_vfy_grid_count, grid_rows, dim3(256), t.d_dets, t.inv_h, counts, rank);
+  if ((s = frame_scan(fr, counts, t.start, slots + 1)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_vfy_grid_scatter, grid_rows, dim3(256), t.d_dets, t.inv_h, t.start, rank, t.pts);
+  return PPF_OK;
+}
+
+/* the scoring arguments of the tables; depth (a device image) may be NULL, intr then too */
+VfyArgs verify_args(const VfyTables& t, const float* d_depth, int depth_rows, int depth_cols, const double* intr, const ppf_verify_params* p) {
   VfyArgs a;
-  a.dets = d_dets;
-  a.jobs = d_jobs;
-  a.slot_start = start;
-  a.pts = pts;
+  a.dets = t.d_dets;
+  a.jobs = t.d_jobs;
+  a.slot_start = t.start;
+  a.pts = t.pts;
   a.depth = d_depth;
-  a.rows = depth ? depth_rows : 0;
-  a.cols = depth ? depth_cols : 0;
-  a.fx = depth ? intr[0] : 0.0;
-  a.fy = depth ? intr[1] : 0.0;
-  a.ppx = depth ? intr[2] : 0.0;
-  a.ppy = depth ? intr[3] : 0.0;
-  a.inv_h = inv_h;
+  a.rows = d_depth ? depth_rows : 0;
+  a.cols = d_depth ? depth_cols : 0;
+  a.fx = d_depth ? intr[0] : 0.0;
+  a.fy = d_depth ? intr[1] : 0.0;
+  a.ppx = d_depth ? intr[2] : 0.0;
+  a.ppy = d_depth ? intr[3] : 0.0;
+  a.inv_h = t.inv_h;
   a.r2 = p->inlier_dist * p->inlier_dist;
   a.normal_cos = p->normal_cos;
   a.depth_tol = p->depth_tol;
   a.step = p->model_step;
   a.all_rows = (p->flags & PPF_VERIFY_ALL_ROWS) ? 1 : 0;
   a.normals = (p->flags & PPF_VERIFY_NORMALS) ? 1 : 0;
-  a.max_nb = max_nb;
-  FRAME_LAUNCH(fr, k_vfy_score, dim3((unsigned)max_nb, (unsigned)nj), dim3(VFY_BLOCK), a, part);
-  FRAME_LAUNCH(fr, k_vfy_finish, dim3((unsigned)nj), dim3(64), d_jobs, part, max_nb, depth ? 1 : 0, d_out);
+  a.max_nb = t.max_nb;
+  return a;
+}
+
+/* grids -> scores -> one read-back; dev[j] = the score row of job j on the host */
+ppf_status verify_run(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top, const float* depth,
+                      int depth_rows, int depth_cols, const double* intr, const ppf_verify_params* p, std::vector<ppf_pose_score>& dev,
+                      FrameRun& fr) {
+  VfyTables t;
+  ppf_status s = verify_tables(dets, n_dets, poses, n_poses, top, p, "ppf_verify_frame", t, fr);
+  if (s != PPF_OK) return s;
+  VfyPartial* part;
+  ppf_pose_score* d_out;
+  float* d_depth = nullptr;
+  if ((s = fr.get((size_t)t.nj * t.max_nb, &part)) != PPF_OK || (s = fr.get(t.nj, &d_out)) != PPF_OK) return s;
+  if (depth && (s = fr.get((size_t)depth_rows * depth_cols, &d_depth)) != PPF_OK) return s;
+  if (depth) HIPCHK(hipMemcpy(d_depth, depth, (size_t)depth_rows * depth_cols * sizeof(float), hipMemcpyHostToDevice));
+  const VfyArgs a = verify_args(t, d_depth, depth_rows, depth_cols, intr, p);
+  FRAME_LAUNCH(fr, k_vfy_score, dim3((unsigned)t.max_nb, (unsigned)t.nj), dim3(VFY_BLOCK), a, part);
+  FRAME_LAUNCH(fr, k_vfy_finish, dim3((unsigned)t.nj), dim3(64), t.d_jobs, part, t.max_nb, depth ? 1 : 0, d_out);
   HIPCHK(hipGetLastError());
-  dev.resize((size_t)nj);
-  return fr.read(dev.data(), d_out, (size_t)nj * sizeof(ppf_pose_score));
+  dev.resize((size_t)t.nj);
+  return fr.read(dev.data(), d_out, (size_t)t.nj * sizeof(ppf_pose_score));
 }
 
 }  // namespace

@@ -129,7 +129,10 @@ __device__ __forceinline__ bool vfy_nearest(const VfyArgs& a, const VfyDet& D, c
   return found;
 }
 
-__global__ __launch_bounds__(VFY_BLOCK) void k_vfy_score(VfyArgs a, VfyPartial* __restrict__ part) {
+/* the body of k_vfy_score; with VIS a considered row must also be visible in its own pose's render (rnd_visible, *rv:
+ * ppf_render_kernels.h, ppf_verify_frame_rendered) -- every other bit is shared */
+template <bool VIS, class View>
+__device__ __forceinline__ void vfy_score_rows(const VfyArgs& a, const View* rv, VfyPartial* __restrict__ part) {
   __shared__ uint32_t wc[VFY_BLOCK / 64][6];
   __shared__ double ws[VFY_BLOCK / 64];
   const VfyJob& J = a.jobs[blockIdx.y];
@@ -148,6 +151,7 @@ __global__ __launch_bounds__(VFY_BLOCK) void k_vfy_score(VfyArgs a, VfyPartial* 
     if (vfy_finite6(o)) {
       const double facing = (double)o[3] * (double)o[0] + (double)o[4] * (double)o[1] + (double)o[5] * (double)o[2];
       cons = a.all_rows || facing < 0.0;
+      if constexpr (VIS) cons = cons && rnd_visible(o, *rv, (int)blockIdx.y);
     }
     if (cons) {
       float m;
@@ -193,6 +197,10 @@ __global__ __launch_bounds__(VFY_BLOCK) void k_vfy_score(VfyArgs a, VfyPartial* 
     P.s = s;
     part[(size_t)blockIdx.y * a.max_nb + blockIdx.x] = P;
   }
+}
+
+__global__ __launch_bounds__(VFY_BLOCK) void k_vfy_score(VfyArgs a, VfyPartial* __restrict__ part) {
+  vfy_score_rows<false>(a, (const int*)nullptr, part);
 }
 
 /* one 64-thread block per job */
