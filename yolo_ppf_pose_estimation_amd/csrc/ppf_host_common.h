@@ -269,6 +269,7 @@ struct ppf_workspace {
   bool cluster_serial = false;           /* force the serial greedy assignment (otherwise only used above 11,520 poses) */
   int device = -1;
   uint32_t* acc_dump = nullptr; /* set by ppf_debug_accumulators for one call */
+  uint32_t odd_epoch = 0;       /* number of the last k_frames launch: MatchArgs::odd_epoch */
   /* pinned: what the host reads of a finished call before anything else -- the 16 totals, the pools' overflow word, the number of
    * clustered poses -- written there by the call's last kernel (k_summary), so that the wait for the stream is the only round
    * trip (four synchronous 4- to 128-byte copies were 40 us of a 0.5 ms match) */
@@ -280,7 +281,7 @@ struct ppf_workspace {
 namespace {
 
 ppf_status enqueue_cluster(ppf_workspace* ws, const ppf_pose* d_in, int n, int num_poses, double pos, double rot,
-                           bool weighted, hipStream_t st, bool rot_relative = false);
+                           bool weighted, hipStream_t st, bool rot_relative = false, bool keys_ready = false);
 
 void resolve_thresholds(const ppf_model* m, const ppf_match_params* p, double* pos, double* rot) {
   *pos = p->position_threshold < 0 ? m->info.position_threshold_default : p->position_threshold;
@@ -288,7 +289,7 @@ void resolve_thresholds(const ppf_model* m, const ppf_match_params* p, double* p
 }
 
 ppf_status enqueue_cluster(ppf_workspace* ws, const ppf_pose* d_in, int n, int num_poses, double pos, double rot,
-                           bool weighted, hipStream_t st, bool rot_relative) {
+                           bool weighted, hipStream_t st, bool rot_relative, bool keys_ready) {
   const size_t nn = (size_t)std::max(n, 1);
   HIPCHK(ws->d_final.reserve(nn));
   HIPCHK(ws->cl_u32.reserve(8 * nn + 4)); /* n_out | order | assign | rin | head | crank | gvotes | sizes | coff[n+1] */
@@ -307,7 +308,8 @@ ppf_status enqueue_cluster(ppf_workspace* ws, const ppf_pose* d_in, int n, int n
   unsigned long long* vkeys = ws->cl_votes.p + nn;
   ca.gq = ws->cl_soa.p; ca.g_heads = ca.gq + 7 * nn;
   ca.out = ws->d_final.p;
-  HIPCHK(hipMemsetAsync(ca.n_out, 0, sizeof(uint32_t), st));
+  ca.small = n <= CL_SMALL_MAX ? 1 : 0;
+  if (n <= 0) HIPCHK(hipMemsetAsync(ca.n_out, 0, sizeof(uint32_t), st)); /* otherwise the assignment kernel writes the count */
   if (n > 0) {
     static std::once_flag once_c;
     static hipError_t attr_c = hipSuccess;
@@ -315,9 +317,8 @@ ppf_status enqueue_cluster(ppf_workspace* ws, const ppf_pose* d_in, int n, int n
       attr_c = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cluster_assign<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 116 * 1024);
     });
     HIPCHK(attr_c);
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    k_vote_keys<<<dim3(nb), dim3(256), 0, st>>>(d_in, n, vkeys);
-    k_rank<<<dim3((unsigned)((n + RANK_KEYS - 1) / RANK_KEYS)), dim3(256), 0, st>>>(vkeys, n, nullptr, order, nullptr);            /* (votes desc, index asc) */
+    const unsigned nb = (unsigned)((n + 255) / 256), nrank = (unsigned)((n + RANK_KEYS - 1) / RANK_KEYS);
+    if (!keys_ready) k_vote_keys<<<dim3(nb), dim3(256), 0, st>>>(d_in, n, vkeys); /* a match: k_finalize wrote them (cl_votes + n) */
     const int np = std::min(num_poses, n);
     const int words = (np + 63) / 64;
     const size_t matrix_words = (size_t)np * words;
@@ -337,20 +338,21 @@ ppf_status enqueue_cluster(ppf_workspace* ws, const ppf_pose* d_in, int n, int n
       uint32_t* prefix = reinterpret_cast<uint32_t*>(heads + words);
       const int pitch = words | 1; /* odd pitch (in 8-byte words): lanes reading the same word of different rows spread over the banks */
       const int rows_per_round = std::max(64, std::min(512, (int)((CLM_LDS_BYTES - (size_t)words * 8) / ((size_t)pitch * 8)) / 64 * 64));
-      k_clm_gather<<<dim3(nb), dim3(256), 0, st>>>(ca);
+      k_rank_gather<<<dim3(nrank), dim3(256), 0, st>>>(ca, vkeys, order); /* (votes desc, index asc), and the poses in that order */
       k_clm_matrix<<<dim3((unsigned)np), dim3(256), 0, st>>>(ca, bits, words);
       k_clm_heads<<<dim3(1), dim3(1024), ((size_t)rows_per_round * pitch + words) * 8, st>>>(ca, bits, words, pitch, rows_per_round, heads, prefix);
-      k_clm_assign<<<dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st>>>(ca, bits, words, heads, prefix);
-    } else if (n <= CLUSTER_LDS_MAX) {
-      k_cluster_assign<true><<<dim3(1), dim3(1024), (size_t)n * 32 + 64, st>>>(ca);
+      k_clm_assign<<<dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st>>>(ca, bits, words, heads, prefix); /* and the clusters' sizes and votes */
     } else {
-      k_cluster_assign<false><<<dim3(1), dim3(1024), 0, st>>>(ca);
+      k_rank<<<dim3(nrank), dim3(256), 0, st>>>(vkeys, n, nullptr, order, nullptr); /* (votes desc, index asc) */
+      if (n <= CLUSTER_LDS_MAX) k_cluster_assign<true><<<dim3(1), dim3(1024), (size_t)n * 32 + 64, st>>>(ca);
+      else k_cluster_assign<false><<<dim3(1), dim3(1024), 0, st>>>(ca);
+      k_cluster_sizes<<<dim3(nb), dim3(256), 0, st>>>(ca);
     }
-    k_cluster_sizes<<<dim3(nb), dim3(256), 0, st>>>(ca);
-    k_cluster_offsets<<<dim3(1), dim3(1024), 0, st>>>(ca);
-    k_cluster_members<<<dim3(nb), dim3(256), 0, st>>>(ca);
-    k_rank<<<dim3((unsigned)((n + RANK_KEYS - 1) / RANK_KEYS)), dim3(256), 0, st>>>(ca.cvotes, 0, ca.n_out, nullptr, ca.crank);    /* (cluster votes desc, creation asc) */
-    k_cluster_finish<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st>>>(ca);
+    /* up to CL_SMALL_MAX poses the members' kernel scans the sizes and the last kernel ranks the clusters, each for itself */
+    if (!ca.small) k_cluster_offsets<<<dim3(1), dim3(1024), 0, st>>>(ca);
+    k_cluster_members<<<dim3((unsigned)((n + MEM_POSES - 1) / MEM_POSES)), dim3(256), 0, st>>>(ca);
+    if (!ca.small) k_rank<<<dim3(nrank), dim3(256), 0, st>>>(ca.cvotes, 0, ca.n_out, nullptr, ca.crank); /* (cluster votes desc, creation asc) */
+    k_cluster_finish<<<dim3((unsigned)((n + 64 / FIN_PARTS - 1) / (64 / FIN_PARTS))), dim3(64), 0, st>>>(ca);
     HIPCHK(hipGetLastError());
   }
   return PPF_OK;

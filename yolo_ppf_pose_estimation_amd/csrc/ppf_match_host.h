@@ -156,7 +156,7 @@ constexpr double HIT_SCRATCH_BYTES = 8.0 + 8.0 + 2.0 + 16.0 / 6.0;
 /* k_pairs<pair feature, surface-to-boundary>: same_cloud == 0 is match_S2B (the paired points come from the edge cloud) */
 static void launch_pairs(const MatchArgs& va, bool darboux, hipStream_t st) {
   const dim3 grid(va.pair_chunks, va.n_ref), block(PAIR_BLOCK);
-  const dim3 ogrid((unsigned)std::min(va.n_ref, 1024)), oblock(256); /* k_pairs_odd: returns at once unless k_frames raised its flag */
+  const dim3 ogrid((unsigned)std::min(va.n_ref, 1024)), oblock(256); /* k_pairs_odd: adds up hit_count, then returns at once unless k_frames raised its flag */
   if (darboux) {
     if (va.same_cloud) k_pairs<true, false><<<grid, block, 0, st>>>(va);
     else k_pairs<true, true><<<grid, block, 0, st>>>(va);
@@ -224,8 +224,7 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
   HIPCHK(ws->votes.reserve(n_ref));
   HIPCHK(ws->raw_poses.reserve(n_ref));
   if (ws->timing) HIPCHK(hipEventRecord(ws->ev[0], st));
-  HIPCHK(hipMemsetAsync(ws->counters.p, 0, n_cnt * sizeof(unsigned long long), st));
-  HIPCHK(hipMemsetAsync(ws->ovf_items.p, 0, (size_t)n_ref * T * sizeof(uint32_t), st));
+  /* counters, ovf_items, the cursors and table_desc are cleared by k_frames (of the first batch / of every batch) */
   if (ws->acc_dump) /* debug dump of the full accumulators: a repeat of the call starts from zeros again (one of its cells is accumulated, not assigned) */
     HIPCHK(hipMemsetAsync(ws->acc_dump, 0, (size_t)n_ref * (size_t)m->info.n_ref * (size_t)m->info.num_angles * sizeof(uint32_t), st));
   if (ws->acc32_policy == 3) {
@@ -272,8 +271,12 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
   va.n_rounds = std::max(1, (int)((m->info.n_buckets + round_cap - 1) / round_cap));
   va.round_buckets = (int)std::min<uint32_t>(std::max<uint32_t>(m->info.n_buckets, 1u), round_cap);
 
+  const bool cursors_new = !ws->cursors.p;
   HIPCHK(ws->cursors.reserve(CUR_WORDS));
   va.cursors = ws->cursors.p;
+  if (cursors_new) HIPCHK(hipMemsetAsync(ws->cursors.p, 0, CUR_WORDS * sizeof(uint32_t), st)); /* k_frames never clears cursors[CUR_ODDVALUES]: a fresh block must not hold a launch's number by chance (see odd_epoch; 0, which the cold pass and the wrap below write, is no launch's number) */
+  va.n_counters = n_cnt;
+  va.n_ovf_items = (unsigned long long)n_ref * T;
   if (!ws->frac_known) {
     /* Cold workspace: nothing is known about this scene's hit density, so the pair kernel first only counts its hits
      * (same arithmetic, nothing stored) and the pools are sized from the exact number.  Costs one extra pair pass and
@@ -375,13 +378,18 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
       HIPCHK(hipEventCreate(&e));
       ws->batch_ev.push_back(e);
     }
-  HIPCHK(hipMemsetAsync(ws->cursors.p, 0, CUR_WORDS * sizeof(uint32_t), st));
   for (int bi = 0; bi < n_batches; bi++) {
     const int base = bi * batch;
     va.ref_base = base;
     va.n_ref = std::min(batch, n_ref - base);
-    if (bi) HIPCHK(hipMemsetAsync(ws->cursors.p, 0, CUR_OVERFLOW * sizeof(uint32_t), st)); /* the overflow word lives on */
-    if (va.agg_min_hits) HIPCHK(hipMemsetAsync(ws->table_desc.p, 0, (size_t)table_cap * sizeof(uint2), st));
+    /* k_frames clears the batch's cursors and table_desc on the side, for the first batch also the call's counters, ovf_items and
+     * the overflow word (which lives on through the later batches); it raises "odd values" by writing this launch's own number */
+    va.first_batch = bi == 0;
+    if (++ws->odd_epoch == 0u) { /* wrapped: a word left by the launch 2^32 before this one must not match */
+      HIPCHK(hipMemsetAsync(ws->cursors.p + CUR_ODDVALUES, 0, sizeof(uint32_t), st));
+      ws->odd_epoch = 1u;
+    }
+    va.odd_epoch = ws->odd_epoch;
 #if PPF_ABL_GROUP != 1 /* attribution builds of k_group store no payload: the later kernels read zeros, never stale values */
     HIPCHK(hipMemsetAsync(ws->s_a64.p, 0, ws->s_a64.bytes(), st));
 #endif
@@ -392,7 +400,6 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
     launch_pairs(va, darboux, st);
     HIPCHK(hipGetLastError());
     if (ws->timing) HIPCHK(hipEventRecord(ws->batch_ev[ws->ev_base + bi * 4 + 1], st));
-    k_ref_hits<<<dim3((va.n_ref + 255) / 256), dim3(256), 0, st>>>(va);
     /* k_group takes the reference points with the most hits first */
     k_rank<<<dim3((va.n_ref + RANK_KEYS - 1) / RANK_KEYS), dim3(256), 0, st>>>(va.hit_count, va.n_ref, nullptr, ws->perm_group.p, nullptr);
     k_group<<<dim3(va.n_ref), dim3(GROUP_BLOCK), group_lds, st>>>(va);
@@ -431,6 +438,11 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
   fa.votes = ws->votes.p; fa.poses = ws->raw_poses.p;
   fa.totals = ws->counters.p + (size_t)n_ref * T + n_ref;
   fa.item_votes = va.item_votes; fa.need_hist = va.item_votes ? ws->need_hist.p : nullptr;
+  fa.vkeys = nullptr;
+  if (!params->skip_clustering) { /* the clustering ranks the poses by their votes: k_finalize leaves the keys where enqueue_cluster looks for them */
+    HIPCHK(ws->cl_votes.reserve(2 * (size_t)n_ref));
+    fa.vkeys = ws->cl_votes.p + n_ref;
+  }
   k_finalize<<<dim3((n_ref + 63) / 64), dim3(64), 0, st>>>(fa);
   HIPCHK(hipGetLastError());
   if (!params->skip_clustering) {
@@ -439,7 +451,7 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
     /* the reference clusters sampled.rows / sceneSamplingStep poses (integer division: the lowest-voted
      * pose is dropped when the stride does not divide the row count); a shard clusters its own share */
     const int num = (params->ref_stride == 1 && params->ref_offset == 0) ? rows / scene_step : n_ref;
-    s = enqueue_cluster(ws, ws->raw_poses.p, n_ref, num, pos, rot, params->use_weighted_avg != 0, st, params->rot_metric_relative != 0);
+    s = enqueue_cluster(ws, ws->raw_poses.p, n_ref, num, pos, rot, params->use_weighted_avg != 0, st, params->rot_metric_relative != 0, true);
     if (s != PPF_OK) return s;
     ws->clustered = true;
   }

@@ -194,7 +194,7 @@ constexpr int LDS_HEADER = 256;       /* bytes: reduction scratch (16 words) + c
 constexpr int CUR_STRIDE = 32;
 constexpr int CUR_SORTED = POOL_STRIPES * CUR_STRIDE;
 constexpr int CUR_RUNS = CUR_SORTED + CUR_STRIDE;
-constexpr int CUR_ODDVALUES = CUR_RUNS + CUR_STRIDE; /* != 0: the batch has a reference frame or a paired point that is not finite (or absurdly large): k_group checks every hit for an alpha_s */
+constexpr int CUR_ODDVALUES = CUR_RUNS + CUR_STRIDE; /* == MatchArgs::odd_epoch: the batch has a reference frame or a paired point that is not finite (or absurdly large): k_group checks every hit for an alpha_s */
 constexpr int CUR_OVFCOUNT = CUR_ODDVALUES + CUR_STRIDE; /* (reference point, tile)s of this batch whose 16-bit cells overflowed: length of ovf_list */
 constexpr int CUR_TABLES = CUR_OVFCOUNT + CUR_STRIDE; /* count tables given out by k_group */
 constexpr int CUR_OVERFLOW = CUR_TABLES + CUR_STRIDE; /* bits 1, 2, 4, 8: raw pool, sorted pool, run table, count-table pool too small */
@@ -372,6 +372,13 @@ struct MatchArgs {
   unsigned long long* pairs;    /* [n_ref_all] pairs hashed */
   unsigned long long* tally;    /* [14] (8 of them: -DPPF_PHASE_CLOCKS only) LDS atomic lane-operations issued by k_vote; hits grouped, runs written by k_group; (reference point, tile)s voted with 32-bit cells; votes the 16-bit launch cast for the ones it flagged; count tables handed out by k_group */
   uint32_t* acc_dump;           /* optional [n_ref_all][n_model*num_angles] full accumulators (debug/tests) */
+  /* what k_frames clears on the side (the batch's cursors and table_desc; for the first batch of a call also the call's
+   * counters and ovf_items): the host enqueues no memset in front of a batch */
+  uint32_t odd_epoch;           /* value of cursors[CUR_ODDVALUES] that means "odd values in THIS batch" (the word is the one k_frames
+                                   cannot clear while it raises it; a new value per launch makes every older one mean "none") */
+  int first_batch;              /* != 0: the overflow word, the counters and ovf_items are cleared too */
+  unsigned long long n_counters; /* words behind cellsum: cellsum | pairs | totals | tally */
+  unsigned long long n_ovf_items; /* words of ovf_items */
 };
 
 __device__ __forceinline__ int ref_row(const MatchArgs& a, int r_local) {
@@ -397,7 +404,17 @@ __global__ __launch_bounds__(64) void k_frames(MatchArgs a) {
 #pragma unroll
     for (int k = 0; k < 3; k++) { f[9 + k] = t[k]; odd |= !(ppf_fabs(t[k]) < 1e30); }
   }
-  if (odd) atomicOr(&a.cursors[CUR_ODDVALUES], 1u);
+  if (odd) atomicExch(&a.cursors[CUR_ODDVALUES], a.odd_epoch);
+  /* the zeroing the host used to enqueue as memsets in front of every batch (each one a launch the device waited for) */
+  const size_t g0 = (size_t)r, gs = (size_t)gridDim.x * blockDim.x;
+  for (size_t k = g0; k < (size_t)(a.first_batch ? CUR_WORDS : CUR_OVERFLOW); k += gs) /* later batches: the overflow word lives on */
+    if (k != (size_t)CUR_ODDVALUES) a.cursors[k] = 0u;
+  if (a.agg_min_hits)
+    for (size_t k = g0; k < (size_t)a.table_cap; k += gs) a.table_desc[k] = make_uint2(0u, 0u);
+  if (a.first_batch) {
+    for (size_t k = g0; k < (size_t)a.n_counters; k += gs) a.cellsum[k] = 0ull;
+    for (size_t k = g0; k < (size_t)a.n_ovf_items; k += gs) a.ovf_items[k] = 0u;
+  }
 }
 
 /* stripe of the raw pool a k_pairs workgroup appends to: a multiplicative hash of its linear index, so that no stripe
@@ -536,7 +553,16 @@ __global__ __launch_bounds__(PAIR_BLOCK) void k_pairs(MatchArgs a) {
  * k_pairs itself the branch cost eight registers and with them a wave per SIMD (0.58 -> 0.64 ms on C2). */
 template <bool DARBOUX, bool S2B>
 __global__ __launch_bounds__(256) void k_pairs_odd(MatchArgs a) {
-  if (a.cursors[CUR_ODDVALUES] == 0u) return;
+  /* first, for every launch: raw hits per reference point = sum of its k_pairs workgroups' counts (k_group's launch order and
+   * its list length; a kernel of its own before) */
+  for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < a.n_ref; r += gridDim.x * 4) { /* a wave per reference point: one round of loads */
+    unsigned long long s = 0;
+    for (int c = threadIdx.x & 63; c < a.pair_chunks; c += 64) s += a.chunk_desc[(size_t)r * a.pair_chunks + c].y;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
+    if ((threadIdx.x & 63) == 0) a.hit_count[r] = s;
+  }
+  if (a.cursors[CUR_ODDVALUES] != a.odd_epoch) return;
   const int lane = threadIdx.x & 63;
   for (int r = blockIdx.x; r < a.n_ref; r += gridDim.x) {
     const int i_ref = ref_row(a, r);
@@ -565,15 +591,6 @@ __global__ __launch_bounds__(256) void k_pairs_odd(MatchArgs a) {
     for (int o = 32; o > 0; o >>= 1) gone += __shfl_down(gone, o);
     if (lane == 0 && gone) atomicAdd(&a.pairs[a.ref_base + r], 0ull - gone);
   }
-}
-
-/* raw hits per reference point = sum of its workgroups' counts */
-__global__ __launch_bounds__(256) void k_ref_hits(MatchArgs a) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= a.n_ref) return;
-  unsigned long long s = 0;
-  for (int c = 0; c < a.pair_chunks; c++) s += a.chunk_desc[(size_t)r * a.pair_chunks + c].y;
-  a.hit_count[r] = s;
 }
 
 /* cell of a hit: y = alpha_s * A/(4 pi) = Y + psi; cell = (Y + 8) * AGG_Q + floor(AGG_Q * psi) */
@@ -640,7 +657,7 @@ __global__ __launch_bounds__(GROUP_BLOCK) void k_group(MatchArgs a) {
   const double R10 = fr[3], R11 = fr[4], R12 = fr[5], R20 = fr[6], R21 = fr[7], R22 = fr[8], ty = fr[10], tz = fr[11];
   const uint32_t agg_min = a.agg_min_hits > 0 ? (uint32_t)a.agg_min_hits : 0xFFFFFFFFu;
   const uint32_t n_list = ok ? n_raw : 0u;
-  const bool check_alpha = a.cursors[CUR_ODDVALUES] != 0u;
+  const bool check_alpha = a.cursors[CUR_ODDVALUES] == a.odd_epoch;
   unsigned long long w = 0;
   uint32_t placed = 0, runs_written = 0, tables_given = 0;
   for (int round = 0; round < a.n_rounds; round++) {

@@ -38,6 +38,7 @@ struct FinalArgs {
   unsigned long long* totals; /* [0] votes, [1] pairs */
   const unsigned long long* item_votes; /* votes per (reference point, tile), or NULL */
   unsigned long long* need_hist;        /* [2][ACC_HIST]: votes of the items that needed 32-bit cells / that did not, by size class of the item */
+  unsigned long long* vkeys;            /* [n_ref] each pose's votes as a ranking key for the clustering that follows, or NULL */
 };
 
 /* size classes of a (reference point, tile) by the votes it casts: four per octave */
@@ -94,6 +95,7 @@ __global__ __launch_bounds__(64) void k_finalize(FinalArgs a) {
   ppf_vote v;
   v.ref_ind_max = refIndMax; v.alpha_ind_max = alphaIndMax; v.max_votes = maxVotes;
   a.votes[r] = v;
+  if (a.vkeys) a.vkeys[r] = maxVotes;
   atomicAdd(&s_tot[0], nv);
   atomicAdd(&s_tot[1], a.pairs[r]);
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -153,22 +155,22 @@ __global__ __launch_bounds__(256) void k_widen_u32(const uint32_t* __restrict__ 
 
 /* Generic ranking: perm[rank] = i and rank_of[i] = rank for keys sorted (key desc, index asc).  n may live on the
  * device (n_dev != nullptr).  O(n^2) spread wide: a workgroup ranks 16 keys, 16 threads per key each counting every
- * 16th key of a 1024-key LDS tile, partial counts added by shuffles. */
+ * 16th key of an LDS tile, partial counts added by shuffles.  The tile holds RANK_TILE keys: up to that many (every
+ * ranking of a 2,500-point match) a workgroup fetches the keys in ONE round of loads; with the 1,024-key tile this
+ * kernel had before, three fetch-wait-count rounds were most of its 15 us. */
 constexpr int RANK_KEYS = 16; /* keys per workgroup of 256 threads */
-__global__ __launch_bounds__(256) void k_rank(const unsigned long long* __restrict__ keys, int n_host,
-                                              const uint32_t* __restrict__ n_dev, uint32_t* __restrict__ perm,
-                                              uint32_t* __restrict__ rank_of) {
-  __shared__ unsigned long long tile[1024];
-  const int n = n_dev ? (int)*n_dev : n_host;
-  if ((int)(blockIdx.x * RANK_KEYS) >= n) return; /* whole workgroup out of range */
-  const int i = blockIdx.x * RANK_KEYS + (threadIdx.x >> 4), part = threadIdx.x & 15;
-  const unsigned long long ki = i < n ? keys[i] : 0ull;
+constexpr int RANK_TILE = 4096;
+/* rank of key i (ki) among keys[0..n), returned to all 16 threads of the key; whole workgroup calls it */
+__device__ __forceinline__ uint32_t rank_among(const unsigned long long* __restrict__ keys, int n, int i, unsigned long long ki,
+                                               unsigned long long* tile) {
+  const int part = threadIdx.x & 15;
   uint32_t rank = 0;
-  for (int j0 = 0; j0 < n; j0 += 1024) {
-    const int cnt = min(1024, n - j0);
+  for (int j0 = 0; j0 < n; j0 += RANK_TILE) {
+    const int cnt = min(RANK_TILE, n - j0);
     __syncthreads();
     for (int t = threadIdx.x; t < cnt; t += 256) tile[t] = keys[j0 + t];
     __syncthreads();
+#pragma unroll 8 /* eight LDS reads in flight: one at a time the loop waited out the LDS latency 157 times for 2,500 keys */
     for (int t = part; t < cnt; t += 16) {
       const unsigned long long kj = tile[t];
       rank += (kj > ki || (kj == ki && j0 + t < i)) ? 1u : 0u; /* keys before position i win ties */
@@ -176,6 +178,17 @@ __global__ __launch_bounds__(256) void k_rank(const unsigned long long* __restri
   }
 #pragma unroll
   for (int o = 1; o < 16; o <<= 1) rank += (uint32_t)__shfl_xor((int)rank, o);
+  return rank;
+}
+__global__ __launch_bounds__(256) void k_rank(const unsigned long long* __restrict__ keys, int n_host,
+                                              const uint32_t* __restrict__ n_dev, uint32_t* __restrict__ perm,
+                                              uint32_t* __restrict__ rank_of) {
+  __shared__ unsigned long long tile[RANK_TILE];
+  const int n = n_dev ? (int)*n_dev : n_host;
+  if ((int)(blockIdx.x * RANK_KEYS) >= n) return; /* whole workgroup out of range */
+  const int i = blockIdx.x * RANK_KEYS + (threadIdx.x >> 4), part = threadIdx.x & 15;
+  const unsigned long long ki = i < n ? keys[i] : 0ull;
+  const uint32_t rank = rank_among(keys, n, i, ki, tile);
   if (i >= n || part != 0) return;
   if (perm) perm[rank] = (uint32_t)i;
   if (rank_of) rank_of[i] = rank;
@@ -201,7 +214,27 @@ struct ClusterArgs {
   double* g_heads;    /* [4n] cluster heads when the LDS variant does not fit */
   ppf_pose* out;      /* [n] */
   uint32_t* n_out;
+  int small;          /* n <= CL_SMALL_MAX: k_cluster_members scans the cluster sizes itself (no k_cluster_offsets) and
+                         k_cluster_finish ranks the clusters itself (no k_rank, crank unused) */
 };
+constexpr int CL_SMALL_MAX = 4096;
+
+/* The pose order of the match-matrix clustering and what used to follow it as k_clm_gather, in one launch: pose i's rank s
+ * among the vote keys (votes desc, index asc) gives order[s] = i; the 16 threads that counted it then write the pose to row s of
+ * the SoA (x, y, z, angle, q0..q3) in g_heads and clear the cluster counters of slot s (every slot has exactly one pose). */
+__global__ __launch_bounds__(256) void k_rank_gather(ClusterArgs a, const unsigned long long* __restrict__ keys, uint32_t* __restrict__ order) {
+  __shared__ unsigned long long tile[RANK_TILE];
+  const int n = a.n;
+  const int i = blockIdx.x * RANK_KEYS + (threadIdx.x >> 4), part = threadIdx.x & 15;
+  const unsigned long long ki = i < n ? keys[i] : 0ull;
+  const uint32_t s = rank_among(keys, n, i, ki, tile);
+  if (i >= n) return;
+  if (part == 8) { order[s] = (uint32_t)i; a.cvotes[s] = 0; a.g_sizes[s] = 0; }
+  if ((int)s >= min(a.num_poses, n) || part >= (a.rot_relative ? 8 : 4)) return;
+  const ppf_pose& p = a.in[i];
+  a.g_heads[(size_t)part * n + s] = part < 3 ? p.t[part] : part == 3 ? p.angle : p.q[part - 4];
+}
+
 
 /*
  * Greedy first-match assignment (step 2 of clusterPoses) without one barrier round per pose: poses are
@@ -340,6 +373,7 @@ __global__ __launch_bounds__(1024) void k_cluster_assign(ClusterArgs a) {
  * k_cluster_assign, 0.72 ms -> tens of microseconds at 2,500 poses. */
 constexpr int CLM_MAX_WORDS = 180;  /* 64 staged rows must fit the LDS window: up to 11,520 poses */
 constexpr int CLM_LDS_BYTES = 96 * 1024;
+constexpr int CLM_PF = CLM_LDS_BYTES / 8 / 1024; /* words of a staged round per thread of k_clm_heads */
 
 /* relative-rotation variant of matchPose() (PCL's posesWithinErrorBounds): the angle of Ra^T Rb is 2 acos(|qa . qb|) */
 __device__ __forceinline__ bool pose_matches_rel(double hx, double hy, double hz, const double* hq, double tx, double ty, double tz,
@@ -353,19 +387,6 @@ __device__ __forceinline__ bool pose_matches_rel(double hx, double hy, double hz
   return ppf_sqrt(d2) < pos_thr;
 }
 
-/* poses in rank order as SoA (x, y, z, angle, q0..q3) in g_heads; cluster counters cleared */
-__global__ __launch_bounds__(256) void k_clm_gather(ClusterArgs a) {
-  const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  const int n = a.n;
-  if (s >= n) return;
-  a.cvotes[s] = 0;
-  a.g_sizes[s] = 0;
-  if (s >= min(a.num_poses, n)) return;
-  const ppf_pose& p = a.in[a.order[s]];
-  a.g_heads[s] = p.t[0]; a.g_heads[(size_t)n + s] = p.t[1]; a.g_heads[2 * (size_t)n + s] = p.t[2]; a.g_heads[3 * (size_t)n + s] = p.angle;
-  if (a.rot_relative)
-    for (int k = 0; k < 4; k++) a.g_heads[(size_t)(4 + k) * n + s] = p.q[k];
-}
 /* bits[i*words + w] bit b = pose 64w+b (< i) matches pose i; one workgroup per pose i, one wave per word */
 __global__ __launch_bounds__(256) void k_clm_matrix(ClusterArgs a, unsigned long long* __restrict__ bits, int words) {
   const int i = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -406,15 +427,39 @@ __global__ __launch_bounds__(1024) void k_clm_heads(ClusterArgs a, const unsigne
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int np = min(a.num_poses, a.n);
   for (int w = tid; w < words; w += 1024) s_heads[w] = 0ull;
+  /* The words of a round come from global memory through registers, and those of the NEXT round are requested as soon as this
+   * round's are in LDS: they arrive while the round is resolved (fetch, wait, resolve in turn made the ten rounds of a 2,500-pose
+   * match ten exposed memory latencies, most of the kernel's 58 us).  The LDS window holds at most CLM_PF * 1024 words. */
+  unsigned long long pf[CLM_PF];
+  int pf_at[CLM_PF]; /* where in s_rows the word goes, -1: none */
+  auto fetch = [&](const int s0) {
+    const int cnt = min(rows_per_round, np - s0);
+    const int wmax = cnt > 0 ? ((s0 + cnt - 1) >> 6) + 1 : 0;
+#pragma unroll
+    for (int k = 0; k < CLM_PF; k++) {
+      const int e = tid + k * 1024;
+      pf[k] = 0ull; pf_at[k] = -1;
+      if (e < cnt * wmax) {
+        const int r = e / wmax, w = e - r * wmax;
+        pf_at[k] = r * pitch + w;
+        if (w <= ((s0 + r) >> 6)) pf[k] = bits[(size_t)(s0 + r) * words + w];
+      }
+    }
+  };
+  fetch(0);
   for (int s0 = 0; s0 < np; s0 += rows_per_round) {
     const int cnt = min(rows_per_round, np - s0);
     const int wmax = ((s0 + cnt - 1) >> 6) + 1; /* words any row of the round can use */
     __syncthreads();
-    for (int e = tid; e < cnt * wmax; e += 1024) {
+#pragma unroll
+    for (int k = 0; k < CLM_PF; k++)
+      if (pf_at[k] >= 0) s_rows[pf_at[k]] = pf[k];
+    for (int e = tid + CLM_PF * 1024; e < cnt * wmax; e += 1024) { /* (a window larger than the registers cover: not with CLM_LDS_BYTES) */
       const int r = e / wmax, w = e - r * wmax;
       s_rows[r * pitch + w] = w <= ((s0 + r) >> 6) ? bits[(size_t)(s0 + r) * words + w] : 0ull;
     }
     __syncthreads();
+    fetch(s0 + rows_per_round);
     /* every row against the heads of the EARLIER ROUNDS (all known): one row per thread, all sixteen waves; the verdict
      * replaces the row's word 0, which nobody reads again.  What is left for the one wave that walks the groups are the
      * head words of this round's own groups. */
@@ -463,7 +508,7 @@ __global__ __launch_bounds__(1024) void k_clm_heads(ClusterArgs a, const unsigne
     *a.n_out = run;
   }
 }
-/* assign[s] = cluster of pose s; head[c] = pose index of the cluster's first member */
+/* assign[s] = cluster of pose s; head[c] = pose index of the cluster's first member; sizes and votes of the clusters */
 __global__ __launch_bounds__(256) void k_clm_assign(ClusterArgs a, const unsigned long long* __restrict__ bits, int words,
                                                     const unsigned long long* __restrict__ heads, const uint32_t* __restrict__ prefix) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -471,21 +516,27 @@ __global__ __launch_bounds__(256) void k_clm_assign(ClusterArgs a, const unsigne
   if (s >= np) return;
   const int ws = s >> 6;
   const unsigned long long hw = heads[ws];
+  const uint32_t pi = a.order[s];
+  uint32_t c = 0xFFFFFFFFu;
   if ((hw >> (s & 63)) & 1ull) {
-    const uint32_t c = prefix[ws] + (uint32_t)__popcll(hw & ((1ull << (s & 63)) - 1ull));
-    a.assign[s] = c;
-    a.head[c] = a.order[s];
-    return;
-  }
-  for (int w = 0; w <= ws; w++) {
-    const unsigned long long h = heads[w];
-    const unsigned long long v = bits[(size_t)s * words + w] & h;
-    if (v) {
-      const int b = __ffsll((long long)v) - 1;
-      a.assign[s] = prefix[w] + (uint32_t)__popcll(h & ((1ull << b) - 1ull));
-      return;
+    c = prefix[ws] + (uint32_t)__popcll(hw & ((1ull << (s & 63)) - 1ull));
+    a.head[c] = pi;
+  } else {
+    for (int w = 0; w <= ws; w++) {
+      const unsigned long long h = heads[w];
+      const unsigned long long v = bits[(size_t)s * words + w] & h;
+      if (v) {
+        const int b = __ffsll((long long)v) - 1;
+        c = prefix[w] + (uint32_t)__popcll(h & ((1ull << b) - 1ull));
+        break;
+      }
     }
   }
+  if (c == 0xFFFFFFFFu) return; /* cannot happen: a pose that opens no cluster matched a head */
+  a.assign[s] = c;
+  /* the cluster's size and votes (integer atomics: order-free), what k_cluster_sizes does after the serial assignment */
+  atomicAdd(&a.g_sizes[c], 1u);
+  atomicAdd(&a.cvotes[c], (unsigned long long)a.in[pi].num_votes);
 }
 
 /* cluster sizes and votes (integer atomics: order-free) */
@@ -528,25 +579,56 @@ __global__ __launch_bounds__(1024) void k_cluster_offsets(ClusterArgs a) {
 }
 
 /* gather the members' q, t, votes into member-slot order = joining order: the joining index of a pose is
- * the number of earlier (rank order) poses of the same cluster */
+ * the number of earlier (rank order) poses of the same cluster.  64 poses per workgroup, four threads per pose each counting
+ * every fourth earlier pose (one thread per pose walking up to n LDS words was 26 us at 2,500 poses).  With a.small every
+ * workgroup first scans the cluster sizes into offsets for itself, in LDS (a few thousand words: cheaper than the launch of
+ * k_cluster_offsets in front of this kernel); workgroup 0 also writes them out for k_cluster_finish. */
+constexpr int MEM_POSES = 64; /* poses per workgroup of 256 threads */
 __global__ __launch_bounds__(256) void k_cluster_members(ClusterArgs a) {
   __shared__ uint32_t tile[1024];
+  __shared__ uint32_t s_coff[CL_SMALL_MAX + 1];
+  __shared__ uint32_t wtot[4];
   const int np = min(a.num_poses, a.n);
-  if ((int)(blockIdx.x * blockDim.x) >= np) return; /* whole workgroup out of range */
-  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if ((int)(blockIdx.x * MEM_POSES) >= np) return; /* whole workgroup out of range */
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (a.small) {
+    const int nc = (int)*a.n_out; /* <= n <= CL_SMALL_MAX */
+    const int per = (nc + 255) / 256, b = tid * per;
+    uint32_t loc = 0;
+    for (int k = 0; k < per; k++) loc += b + k < nc ? a.g_sizes[b + k] : 0u;
+    uint32_t incl = loc;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t y = __shfl_up(incl, o);
+      if (lane >= o) incl += y;
+    }
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    uint32_t run = incl - loc;
+    for (int k = 0; k < wave; k++) run += wtot[k];
+    for (int k = 0; k < per; k++)
+      if (b + k < nc) { s_coff[b + k] = run; run += a.g_sizes[b + k]; }
+    if (tid == 255) s_coff[nc] = run; /* the last thread's chunk ends the list (or lies past it): run is the total */
+    __syncthreads();
+    if (blockIdx.x == 0)
+      for (int c = tid; c <= nc; c += 256) a.coff[c] = s_coff[c];
+  }
+  const int s = blockIdx.x * MEM_POSES + (tid >> 2), part = tid & 3;
   const uint32_t c = s < np ? a.assign[s] : 0xFFFFFFFFu;
   uint32_t rin = 0; /* earlier poses of the same cluster = this pose's position among the members */
-  const int last = min(np, (int)((blockIdx.x + 1) * blockDim.x)); /* no thread of the workgroup looks past its own s */
+  const int last = min(np, (int)((blockIdx.x + 1) * MEM_POSES)); /* no thread of the workgroup looks past its own s */
   for (int j0 = 0; j0 < last; j0 += 1024) {
     const int cnt = min(1024, last - j0);
     __syncthreads();
-    for (int t = threadIdx.x; t < cnt; t += 256) tile[t] = a.assign[j0 + t];
+    for (int t = tid; t < cnt; t += 256) tile[t] = a.assign[j0 + t];
     __syncthreads();
     const int upto = min(max(s - j0, 0), cnt);
-    for (int t = 0; t < upto; t++) rin += tile[t] == c ? 1u : 0u;
+    for (int t = part; t < upto; t += 4) rin += tile[t] == c ? 1u : 0u;
   }
-  if (s >= np) return;
-  const uint32_t slot = a.coff[c] + rin;
+  rin += (uint32_t)__shfl_xor((int)rin, 1);
+  rin += (uint32_t)__shfl_xor((int)rin, 2);
+  if (s >= np || part != 0) return;
+  const uint32_t slot = (a.small ? s_coff[c] : a.coff[c]) + rin;
   const ppf_pose& p = a.in[a.order[s]];
   double* g = a.gq + (size_t)slot * 7;
   g[0] = p.q[0]; g[1] = p.q[1]; g[2] = p.q[2]; g[3] = p.q[3]; g[4] = p.t[0]; g[5] = p.t[1]; g[6] = p.t[2];
@@ -554,36 +636,67 @@ __global__ __launch_bounds__(256) void k_cluster_members(ClusterArgs a) {
 }
 
 /* steps 3 + 4 of clusterPoses: means in joining order (fp64, sequential per cluster: bit-identical to the CPU
- * restatement), pose rebuilt from the mean quaternion, written to the cluster's rank */
+ * restatement), pose rebuilt from the mean quaternion, written to the cluster's rank.  Eight threads per cluster: thread j < 7
+ * sums component j (q0..q3, t0..t2) over the members, each component in the order one thread took it before (a thread
+ * summing all seven waited for seven loads per member: 25 us for the largest cluster of a 2,500-pose match); thread 0 then
+ * collects them and builds the pose.  With a.small the eight threads also rank the cluster among the clusters' votes
+ * (votes desc, creation asc: what k_rank wrote into crank). */
+constexpr int FIN_PARTS = 8;
 __global__ __launch_bounds__(64) void k_cluster_finish(ClusterArgs a) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= (int)*a.n_out) return;
-  double q[4] = {0, 0, 0, 0}, t[3] = {0, 0, 0}, wsum = 0;
-  const uint32_t k0 = a.coff[c], k1 = a.coff[c + 1];
-  for (uint32_t k = k0; k < k1; k++) {
-    const double* g = a.gq + (size_t)k * 7;
-    if (a.weighted) {
-      const double w = (double)a.gvotes[k];
-      for (int j = 0; j < 4; j++) q[j] += w * g[j];
-      for (int j = 0; j < 3; j++) t[j] += w * g[4 + j];
-      wsum += w;
-    } else {
-      for (int j = 0; j < 4; j++) q[j] += g[j];
-      for (int j = 0; j < 3; j++) t[j] += g[4 + j];
+  __shared__ unsigned long long tile[1024];
+  const int nc = (int)*a.n_out;
+  if ((int)(blockIdx.x * (64 / FIN_PARTS)) >= nc) return; /* whole workgroup out of range */
+  const int c = blockIdx.x * (64 / FIN_PARTS) + (threadIdx.x / FIN_PARTS), j = threadIdx.x % FIN_PARTS;
+  const bool valid = c < nc;
+  uint32_t rank = 0;
+  if (a.small) {
+    const unsigned long long kc = valid ? a.cvotes[c] : 0ull;
+    for (int j0 = 0; j0 < nc; j0 += 1024) {
+      const int cnt = min(1024, nc - j0);
+      __syncthreads();
+      for (int t = threadIdx.x; t < cnt; t += 64) tile[t] = a.cvotes[j0 + t];
+      __syncthreads();
+#pragma unroll 8
+      for (int t = j; t < cnt; t += FIN_PARTS) {
+        const unsigned long long kj = tile[t];
+        rank += (kj > kc || (kj == kc && j0 + t < c)) ? 1u : 0u;
+      }
     }
+#pragma unroll
+    for (int o = 1; o < FIN_PARTS; o <<= 1) rank += (uint32_t)__shfl_xor((int)rank, o);
+  } else if (valid) {
+    rank = a.crank[c];
+  }
+  const uint32_t k0 = valid ? a.coff[c] : 0u, k1 = valid ? a.coff[c + 1] : 0u;
+  const int comp = min(j, 6);
+  double acc = 0, wsum = 0;
+  if (a.weighted) {
+#pragma unroll 4
+    for (uint32_t k = k0; k < k1; k++) {
+      const double w = (double)a.gvotes[k];
+      acc += w * a.gq[(size_t)k * 7 + comp];
+      wsum += w;
+    }
+  } else {
+#pragma unroll 4
+    for (uint32_t k = k0; k < k1; k++) acc += a.gq[(size_t)k * 7 + comp];
   }
   const double inv = a.weighted ? 1.0 / wsum : 1.0 / (int)(k1 - k0);
-  for (int j = 0; j < 3; j++) t[j] *= inv;
-  for (int j = 0; j < 4; j++) q[j] *= inv;
+  acc *= inv;
+  double q[4], t[3];
+  const int l0 = (int)(threadIdx.x - j); /* first thread of this cluster */
+  for (int k = 0; k < 4; k++) q[k] = __shfl(acc, l0 + k);
+  for (int k = 0; k < 3; k++) t[k] = __shfl(acc, l0 + 4 + k);
+  if (!valid || j != 0) return;
   ppf_pose P = a.in[a.head[c]];
   double R[9];
   ppf_quat_to_dcm(q, R);
-  for (int j = 0; j < 4; j++) P.q[j] = q[j];
-  for (int j = 0; j < 3; j++) P.t[j] = t[j];
+  for (int k = 0; k < 4; k++) P.q[k] = q[k];
+  for (int k = 0; k < 3; k++) P.t[k] = t[k];
   ppf_rt_to_pose(R, t, P.pose);
   P.angle = ppf_angle_from_trace(R[0] + R[4] + R[8]);
   P.num_votes = (uint32_t)a.cvotes[c];
-  a.out[a.crank[c]] = P;
+  a.out[rank] = P;
 }
 
 __global__ void k_vote_keys(const ppf_pose* __restrict__ in, int n, unsigned long long* __restrict__ keys) {
