@@ -14,6 +14,7 @@
  *   `// TODO: Pose Validation` (:477-479, :530-532) -> Cloud::verifyFrame(modelClouds, dets, poses, depth, ...)  (scores, best pose)
  *                                                     Cloud::verifyFrameRendered(...)  (the same with self-occlusion)
  *   transformPCPose -> writePLY of the result       ->  Cloud::renderFrame(modelClouds, poses, best, ...)  (depth, label images)
+ *   `return *resultsSub[0];` per box (:480, :533)   ->  Cloud::selectFrame(modelClouds, poses, depth, ...)  (one consistent set per frame)
  *
  * Every stage returns a new Cloud that stays in HBM; only toMat()/download() copy to the host.  A maintainer replaces
  * the bodies of those CloudProcessor methods by these one-liners; pcl::PointCloud<PointXYZ> goes
@@ -275,6 +276,67 @@ class Cloud {
     if (labelOut) labelOut->assign(npx, -1);
     ppf_match_3d::check(ppf_render_frame(&d[0], (int)nd, &recs[0], &w[0], (int)top, rows, cols, intr, &rp,
                                          depthOut && npx ? &(*depthOut)[0] : 0, labelOut && npx ? &(*labelOut)[0] : 0, stats));
+  }
+  /* One consistent set among all poses of all detections of a frame (ppf_select_frame): duplicates and the
+   * same object seen through overlapping boxes are suppressed, a second instance inside one box is kept.  Returns the
+   * selected (detection, k) pairs in selection order.  depth is required; top is the longest pose list, and the flat index
+   * of pose k of detection i is i * top + k (suppressed_by in the info rows, the values of labelOut).  scores (what either
+   * verify entry returned) ranks by their score instead of the explained share.  info, when given, gets one row per pose;
+   * depthOut / labelOut are resized to rows x cols, either may be 0.  params == 0 / rparams == 0: the defaults. */
+  static std::vector<std::pair<int, int> > selectFrame(const std::vector<const Cloud*>& modelClouds,
+                                                       const std::vector<std::vector<ppf_match_3d::Pose3D> >& poses, const float* depth,
+                                                       int rows, int cols, double fx, double fy, double ppx, double ppy,
+                                                       const ppf_select_params* params = 0, const ppf_render_params* rparams = 0,
+                                                       const std::vector<std::vector<ppf_pose_score> >* scores = 0,
+                                                       std::vector<std::vector<ppf_select_info> >* info = 0, std::vector<float>* depthOut = 0,
+                                                       std::vector<int32_t>* labelOut = 0, ppf_select_stats* stats = 0) {
+    const size_t nd = poses.size();
+    if (modelClouds.size() != nd || (scores && scores->size() != nd))
+      throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::selectFrame: one model cloud (and one score list) per detection");
+    size_t top = 1;
+    for (size_t i = 0; i < nd; i++) top = poses[i].size() > top ? poses[i].size() : top;
+    std::vector<ppf_frame_detection> d(nd + 1);
+    std::vector<ppf_pose> recs(nd * top + 1);
+    std::vector<ppf_pose_score> sc(nd * top + 1);
+    std::vector<int> n(nd + 1, 0);
+    for (size_t i = 0; i < nd; i++) {
+      d[i].model = 0;
+      d[i].scene = 0;
+      d[i].edge = 0;
+      const bool live = modelClouds[i] && modelClouds[i]->handle() && !poses[i].empty();
+      d[i].model_cloud = live ? modelClouds[i]->handle() : 0;
+      n[i] = live ? (int)poses[i].size() : 0;
+      if (scores && live && (*scores)[i].size() < poses[i].size())
+        throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::selectFrame: fewer scores than poses");
+      for (int k = 0; k < n[i]; k++) {
+        recs[i * top + (size_t)k] = poses[i][(size_t)k].record();
+        if (scores) sc[i * top + (size_t)k] = (*scores)[i][(size_t)k];
+      }
+    }
+    ppf_select_params p;
+    if (params) p = *params;
+    else ppf_default_select_params(&p);
+    ppf_render_params rp;
+    if (rparams) rp = *rparams;
+    else ppf_default_render_params(&rp);
+    const double intr[4] = {fx, fy, ppx, ppy};
+    const size_t npx = rows > 0 && cols > 0 ? (size_t)rows * (size_t)cols : 0;
+    if (depthOut) depthOut->assign(npx, 0.f);
+    if (labelOut) labelOut->assign(npx, -1);
+    std::vector<ppf_select_info> rowsOut(nd * top + 1);
+    std::vector<int> sel(nd * top + 1, -1);
+    int nSel = 0;
+    ppf_match_3d::check(ppf_select_frame(&d[0], (int)nd, &recs[0], &n[0], (int)top, scores ? &sc[0] : 0, depth, rows, cols, intr, &rp, &p,
+                                         &rowsOut[0], &sel[0], &nSel, depthOut && npx ? &(*depthOut)[0] : 0,
+                                         labelOut && npx ? &(*labelOut)[0] : 0, stats));
+    if (info) {
+      info->assign(nd, std::vector<ppf_select_info>());
+      for (size_t i = 0; i < nd; i++)
+        (*info)[i].assign(rowsOut.begin() + (std::ptrdiff_t)(i * top), rowsOut.begin() + (std::ptrdiff_t)(i * top + (size_t)n[i]));
+    }
+    std::vector<std::pair<int, int> > out;
+    for (int r = 0; r < nSel; r++) out.push_back(std::make_pair(sel[(size_t)r] / (int)top, sel[(size_t)r] % (int)top));
+    return out;
   }
   /* the N x 6 CV_32FC1-shaped Mat of PointCloudXYZNormalToMat (normals re-normalised) */
   ppf_match_3d::Mat toMat() const {

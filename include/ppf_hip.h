@@ -45,6 +45,8 @@
  *                                   z-buffer of its own pose (the reference has no pose validation at all)
  *   ppf_render_frame                depth and instance-label images of the chosen poses, in place of the reference's
  *                                   transformPCPose -> writePLY dump of the result (YOLO_cropping_ppf_test.cpp:125-127)
+ *   ppf_select_frame                one consistent set of poses per frame: duplicates and overlapping boxes suppressed,
+ *                                   several instances per box kept (the reference returns `*resultsSub[0]` per box)
  *
  * Conventions
  *   - A cloud argument is (pointer, rows, stride, normal_offset): float32 rows whose first three floats
@@ -598,6 +600,61 @@ ppf_status ppf_verify_frame_rendered(const ppf_frame_detection* dets, int n_dets
 ppf_status ppf_render_frame(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* which, int top, int rows,
                             int cols, const double* intr, const ppf_render_params* rparams, float* depth_out, int32_t* label_out,
                             ppf_render_stats* stats);
+
+/* ---- one consistent set of poses per frame: duplicates, overlapping boxes and several instances per box ---------- */
+#define PPF_SELECT_NONE 0       /* k >= n_poses[i]: the row is all zero */
+#define PPF_SELECT_SELECTED 1
+#define PPF_SELECT_GATED 2      /* key < min_score (or NaN), or n_supported < min_pixels */
+#define PPF_SELECT_SUPPRESSED 3 /* conflicts with a hypothesis selected before it */
+
+typedef struct ppf_select_params {
+  float depth_tol;    /* metres, finite, > 0: a drawn pixel is supported when |depth - z| <= depth_tol */
+  float max_overlap;  /* in [0, 1]: two hypotheses conflict above this share of the smaller supported set */
+  float min_score;    /* finite; gate on the rank key */
+  int32_t min_pixels; /* >= 1; gate on n_supported */
+  int32_t flags;      /* 0; reserved */
+  int32_t reserved[4];
+} ppf_select_params;
+
+typedef struct ppf_select_info {
+  int32_t status, rank;        /* PPF_SELECT_*; rank: position in selection order, -1 unless selected */
+  int32_t suppressed_by;       /* flat index i * top + k of the suppressor, else -1 */
+  int32_t n_drawn, n_supported; /* pixels of the pose's own z-buffer; those the depth image agrees with */
+  int32_t n_overlap;           /* supported pixels shared with the suppressor, else 0 */
+  float explained, key;        /* n_supported / n_drawn; what the order ranks by */
+  int32_t reserved[4];
+} ppf_select_info;
+
+typedef struct ppf_select_stats {
+  int32_t n_dets, n_jobs;         /* detections given, hypotheses rendered */
+  int32_t n_eligible, n_selected; /* hypotheses that passed the gate; those selected */
+  int32_t n_launches;             /* kernel launches of the call */
+  int32_t n_host_syncs;           /* blocking read-backs of the call (host-to-device uploads not counted) */
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_select_stats;
+
+/* depth_tol 0.01, max_overlap 0.25, min_score 0, min_pixels 1, flags 0 */
+void ppf_default_select_params(ppf_select_params* p);
+/* Picks one consistent set among all hypotheses j = i * top + k, k < n_poses[i], of a frame.  Each is drawn
+ * into a z-buffer of its own as ppf_verify_frame_rendered draws it; its supported pixels are the drawn ones whose depth
+ * pixel is finite, > 0 and within depth_tol of the z-buffer.  explained = n_supported / n_drawn; the rank key is
+ * scores[j].score when `scores` is given (what either verify entry returned), else explained.  Hypotheses that pass the
+ * gate (key >= min_score, n_supported >= min_pixels) are taken greedily by key descending, then j ascending; one is
+ * suppressed by the earliest selected hypothesis it shares more than max_overlap * min(n_supported) supported pixels with.
+ * dets, poses, n_poses and top are what ppf_match_frame took and returned (only model_cloud is read).  depth: required
+ * HOST image, float32 metres, packed depth_rows x depth_cols; intr = {fx, fy, ppx, ppy}, fx and fy > 0.
+ * info is [n_dets][top]; selected is [n_dets * top], the selected flat indices in selection order, then -1;
+ * depth_out (0 where empty) and label_out (the flat index j of the nearest selected hypothesis, -1 where empty) are
+ * packed HOST images of the depth image's size and may each be NULL; stats may be NULL.  Limits: n_dets 0..256, top 1..16,
+ * n_poses[i] 0..top.  Argument errors are PPF_ERR_INVALID before any device work; on any error every info row is zero,
+ * selected is all -1, *n_selected is 0 and the given images are all 0 and all -1.  A hypothesis's counts do not depend
+ * on the rest of the call, the launch count does not depend on n_dets, and there are two blocking read-backs: the pose
+ * windows, then the results. */
+ppf_status ppf_select_frame(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top,
+                            const ppf_pose_score* scores, const float* depth, int depth_rows, int depth_cols, const double* intr,
+                            const ppf_render_params* rparams, const ppf_select_params* params, ppf_select_info* info, int* selected,
+                            int* n_selected, float* depth_out, int32_t* label_out, ppf_select_stats* stats);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,81 @@
+"""Time ppf_select_frame against ppf_verify_frame_rendered with the depth image, which draws the same per-pose z-buffers, on
+the frame chain's own inputs.
+
+Cases (default select, verify and render parameters, top 5):
+  c1_k1 / c1_k8  the golden C1 chain's five ICP poses (tests/golden/c1_pipeline_golden.npz) of the bottle model (19,753 rows)
+                 against the C1 object cloud of ppf_prep_frame, one detection or eight copies of it; C1 depth frame 720 x 1280
+  rendered       the rendered two-bottle-and-box frame (tests/test_gpu_frame.py::_render_frame, 360 x 640): the refined top
+                 poses ppf_match_frame returns for its three detections
+Per case: the median and spread of the wall time of each call (perf_counter around the wrapper; `--reps` rounds after a
+warm-up, each round calling ppf_verify_frame_rendered, ppf_select_frame without images and ppf_select_frame with both
+images, alternating), the call's own ms_wall, its launches and host synchronisations, and the ratio of the medians.
+Writes profiles/r12_select_timing.json (or --out).
+The kernel trace is a run of its own:
+  rocprofv3 --kernel-trace --stats -d <dir> -o select -- python tools/select_timing.py --reps 5 --no-write
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from render_timing import stats  # noqa: E402
+from yolo_ppf_pose_estimation_amd.cloud_processor import select_frame, verify_frame_rendered  # noqa: E402
+
+
+def run_case(name, dets, poses, depth, intr, reps):
+    res = {"case": name, "detections": len(dets), "poses": sum(len(p) for p in poses), "depth_shape": list(depth.shape), "reps": reps}
+    mclouds = [d[0] for d in dets]
+    routes = {"rendered_with_depth": lambda: verify_frame_rendered(dets, poses, 5, depth, intr)[2],
+              "select": lambda: select_frame(mclouds, poses, depth, intr, top=5, return_stats=True)[-1],
+              "select_with_images": lambda: select_frame(mclouds, poses, depth, intr, top=5, return_images=True, return_stats=True)[-1]}
+    for fn in routes.values():   # warm-up
+        fn()
+        fn()
+    wall = {k: [] for k in routes}
+    call = {k: [] for k in routes}
+    counters = {}
+    for _ in range(reps):
+        for key, fn in routes.items():
+            t0 = time.perf_counter()
+            st = fn()
+            wall[key].append((time.perf_counter() - t0) * 1e3)
+            call[key].append(st["ms_wall"])
+            counters[key] = {k: st[k] for k in ("n_launches", "n_host_syncs", "n_jobs", "n_eligible", "n_selected") if k in st}
+    for key in wall:
+        res[key] = dict(wall=stats(wall[key]), call_ms_wall=stats(call[key]), **counters[key])
+    for key in ("select", "select_with_images"):
+        res[f"{key}_over_rendered"] = round(res[key]["wall"]["median_ms"] / res["rendered_with_depth"]["wall"]["median_ms"], 3)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12_select_timing.json"))
+    ap.add_argument("--no-write", action="store_true")
+    a = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("select_timing.py needs a GPU")
+    import render_timing as RT
+    RT.run_case = run_case   # the same three cases, timed for the selection
+    bottle = np.load(os.path.join(ROOT, "tests", "golden", "bottle_model_xyzn.npy"))
+    cases = RT.c1_cases(bottle, a.reps) + [RT.rendered_case(bottle, a.reps)]
+    doc = {"tool": "tools/select_timing.py", "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "cases": cases}
+    print(json.dumps(doc, indent=1))
+    if not a.no_write:
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -148,6 +148,25 @@ class RenderStats(C.Structure):
 PPF_RENDER_MAX_SPLAT = 8  # include/ppf_hip.h
 
 
+class SelectParams(C.Structure):
+    _fields_ = [("depth_tol", C.c_float), ("max_overlap", C.c_float), ("min_score", C.c_float), ("min_pixels", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class SelectInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("rank", C.c_int32), ("suppressed_by", C.c_int32), ("n_drawn", C.c_int32),
+                ("n_supported", C.c_int32), ("n_overlap", C.c_int32), ("explained", C.c_float), ("key", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
+class SelectStats(C.Structure):
+    _fields_ = [("n_dets", C.c_int32), ("n_jobs", C.c_int32), ("n_eligible", C.c_int32), ("n_selected", C.c_int32),
+                ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32), ("ms_wall", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+PPF_SELECT_NONE, PPF_SELECT_SELECTED, PPF_SELECT_GATED, PPF_SELECT_SUPPRESSED = 0, 1, 2, 3  # SelectInfo.status
+
+
 # every symbol include/ppf_hip.h declares (tests/test_capi_symbols.py checks the header against this)
 _SIGNATURES = {
     "ppf_default_train_params": (None, [C.POINTER(TrainParams)]),
@@ -251,6 +270,11 @@ _SIGNATURES = {
                                             C.POINTER(PoseScore), C.POINTER(C.c_int), C.POINTER(VerifyStats)]),
     "ppf_render_frame": (C.c_int, [C.POINTER(FrameDetection), C.c_int, C.POINTER(Pose), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
                                    C.POINTER(C.c_double), C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.POINTER(RenderStats)]),
+    "ppf_default_select_params": (None, [C.POINTER(SelectParams)]),
+    "ppf_select_frame": (C.c_int, [C.POINTER(FrameDetection), C.c_int, C.POINTER(Pose), C.POINTER(C.c_int), C.c_int, C.POINTER(PoseScore),
+                                   C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(RenderParams), C.POINTER(SelectParams),
+                                   C.POINTER(SelectInfo), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
+                                   C.POINTER(SelectStats)]),
     "ppf_icp_register": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }

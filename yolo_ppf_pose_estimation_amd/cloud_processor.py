@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import (FrameDetection, FrameParams, FrameStats, IcpParams, MatchFrameStats, Pose, PoseScore, PPFError, RenderParams,
-                    RenderStats, VerifyParams, VerifyStats, check, lib)
+                    RenderStats, SelectInfo, SelectParams, SelectStats, VerifyParams, VerifyStats, check, lib)
 from .detector import ICP, PPF3DDetector, Pose3D
 
 
@@ -307,6 +307,57 @@ def render_frame(dets, poses, which, rows: int, cols: int, intr, render_params=N
     return (depth, label, _capi.stats_dict(st)) if return_stats else (depth, label)
 
 
+def _select_params(params) -> SelectParams:
+    if isinstance(params, SelectParams):
+        return params
+    prm = SelectParams()
+    lib().ppf_default_select_params(C.byref(prm))
+    for key, v in (params or {}).items():
+        setattr(prm, key, v)
+    return prm
+
+
+def select_frame(dets, poses, depth, intr, params=None, render_params=None, scores=None, top: Optional[int] = None,
+                 return_images: bool = False, return_stats: bool = False):
+    """One ppf_select_frame call: one consistent set among all poses of all detections of a frame.  dets:
+    per detection a model cloud (DeviceCloud), a (model cloud, anything) pair, or None; poses: per detection its poses as
+    verify_frame takes them; depth: the 2-D float32 image in metres (required); intr: (fx, fy, ppx, ppy) or the 3x3 camera
+    matrix.  params: a SelectParams, a dict of its fields (the rest default) or None; render_params as render_frame takes
+    them.  scores: the (n_dets, top) PoseScore rows of either verify entry, whose ``score`` then ranks the hypotheses, or
+    None to rank by the explained share.  Returns (info, selected): the SelectInfo rows as a numpy structured array of shape
+    (n_dets, top) and the selected flat indices i * top + k in selection order; with ``return_images`` also the depth
+    (0 where empty) and label (flat index, -1 where empty) images of the selection, with ``return_stats`` the counters."""
+    pairs = [None if d is None else (d[0] if isinstance(d, tuple) else d, None) for d in dets]
+    n, top, arr, recs, n_poses = _frame_tables(pairs, poses, top)
+    prm, rprm = _select_params(params), _render_params(render_params)
+    img = np.ascontiguousarray(depth, dtype=np.float32) if depth is not None else None
+    if img is None or img.ndim != 2:
+        raise PPFError(_capi.PPF_ERR_INVALID, "select_frame needs a 2-D float32 depth image")
+    rows, cols = img.shape
+    it = (C.c_double * 4)(*_intr4(intr)) if intr is not None else None
+    sc = None
+    if scores is not None:
+        given = np.ascontiguousarray(scores)
+        if given.shape != (n, top) or given.dtype.itemsize != C.sizeof(PoseScore):
+            raise PPFError(_capi.PPF_ERR_INVALID, f"scores must be the ({n}, {top}) PoseScore rows of a verify call")
+        sc = (PoseScore * (max(n, 1) * top)).from_buffer_copy(given.tobytes() + bytes(C.sizeof(PoseScore) * (top if n == 0 else 0)))
+    info = (SelectInfo * (max(n, 1) * top))()
+    selected = (C.c_int * (max(n, 1) * top))()
+    n_selected = C.c_int(0)
+    out_d = np.zeros((rows, cols), dtype=np.float32) if return_images else None
+    out_l = np.full((rows, cols), -1, dtype=np.int32) if return_images else None
+    st = SelectStats()
+    check(lib().ppf_select_frame(arr, n, recs, n_poses, top, sc, img.ctypes.data, rows, cols, it, C.byref(rprm), C.byref(prm), info, selected,
+                                 C.byref(n_selected), out_d.ctypes.data if return_images else None,
+                                 out_l.ctypes.data if return_images else None, C.byref(st)))
+    out = [np.ctypeslib.as_array(info).copy()[:n * top].reshape(n, top), np.array(selected[:n_selected.value], dtype=np.int32)]
+    if return_images:
+        out += [out_d, out_l]
+    if return_stats:
+        out.append(_capi.stats_dict(st))
+    return tuple(out)
+
+
 class CloudProcessor:
     """``ppf::CloudProcessor``: holds the scene cloud, the depth image, the detector's boxes, the per-object clouds
     and the PPF detectors; every method is the reference's, in the order its driver calls them
@@ -345,6 +396,10 @@ class CloudProcessor:
         self.verify_stats: Dict[str, object] = {}
         self.kept_index: List[int] = []  # per detection the pose PoseValidation kept, -1 where it kept none
         self.render_stats: Dict[str, object] = {}  # RenderFrame: the ppf_render_frame counters
+        # SelectFrame: the info rows (n_dets, top), the selected (detection, k) pairs in selection order, the counters
+        self.select_info: Optional[np.ndarray] = None
+        self.selected: List[tuple] = []
+        self.select_stats: Dict[str, object] = {}
         self._last_refined: List[Pose3D] = []
 
     # ---- the PCL half -------------------------------------------------------------------------------------
@@ -484,6 +539,33 @@ class CloudProcessor:
                                                        self.frame_intr, render_params, return_stats=True)
         self.timings["render_frame"] = time.perf_counter() - t0
         return depth, label
+
+    def SelectFrame(self, min_score: float = 0.0, max_overlap: float = 0.25, depth_tol: float = 0.01, min_pixels: int = 1,
+                    use_scores: bool = False, render_params=None, return_images: bool = False):
+        """One consistent set among every refined pose the last MatchFrame kept (one ppf_select_frame call at
+        ``self.depth``): duplicates and the same object seen through overlapping boxes are suppressed, a
+        second instance inside one box is kept.  ``use_scores`` ranks by the ``score`` of the last PoseValidation instead of
+        the explained share.  Returns the selected poses as (detection, k, Pose3D) in selection order; with
+        ``return_images`` also the depth and label images (the label is detection * top + k).  Sets ``select_info``,
+        ``selected``, ``select_stats`` and ``timings["select_frame"]``."""
+        if self.depth is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "SelectFrame needs the depth image")
+        if use_scores and self.pose_scores is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "SelectFrame(use_scores=True) needs a PoseValidation first")
+        dets = [None if name is None or not plist else self._model_clouds[self.label_to_id[name]]
+                for name, plist in zip(self.frame_labels, self.frame_poses)]
+        poses = [plist if d is not None else [] for d, plist in zip(dets, self.frame_poses)]
+        top = self.pose_scores.shape[1] if use_scores else None
+        prm = {"min_score": float(min_score), "max_overlap": float(max_overlap), "depth_tol": float(depth_tol), "min_pixels": int(min_pixels)}
+        t0 = time.perf_counter()
+        got = select_frame(dets, poses, self.depth, self.frame_intr, prm, render_params, self.pose_scores if use_scores else None, top,
+                           return_images=return_images, return_stats=True)
+        self.timings["select_frame"] = time.perf_counter() - t0
+        self.select_info, self.select_stats = got[0], got[-1]
+        top = self.select_info.shape[1] if self.select_info.size else 1
+        self.selected = [(int(j) // top, int(j) % top) for j in got[1]]
+        out = [(i, k, self.frame_poses[i][k]) for i, k in self.selected]
+        return (out, got[2], got[3]) if return_images else out
 
     def _match_frame(self, labels, step, dist, top: int = 5) -> List[Optional[Pose3D]]:
         dets = (FrameDetection * max(len(labels), 1))()

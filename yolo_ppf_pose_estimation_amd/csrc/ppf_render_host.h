@@ -44,6 +44,25 @@ RndCam render_cam(int rows, int cols, const double* intr, const ppf_render_param
   return c;
 }
 
+/* each job's window from its box {-u0, -v0, u1, v1}, at its offset in one scratch of the summed sizes; returns that sum */
+unsigned long long render_windows(const std::vector<int>& box, std::vector<RndWin>& win) {
+  win.resize(box.size() / 4);
+  unsigned long long total = 0;
+  for (size_t j = 0; j < win.size(); j++) {
+    const int* b = &box[j * 4];
+    RndWin& w = win[j];
+    w.u0 = -b[0];
+    w.v0 = -b[1];
+    const bool empty = b[2] < w.u0 || b[3] < w.v0; /* a job without a rendered row keeps the preset */
+    w.w = empty ? 0 : b[2] - w.u0 + 1;
+    w.h = empty ? 0 : b[3] - w.v0 + 1;
+    if (empty) w.u0 = w.v0 = 0;
+    w.off = total;
+    total += (unsigned long long)w.w * (unsigned long long)w.h;
+  }
+  return total;
+}
+
 /* tables and grids -> windows (read-back 1) -> per-job renders -> scores (read-back 2); dev[j] = the score row of job j */
 ppf_status verify_rendered_run(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top,
                                const float* depth, int rows, int cols, const double* intr, const ppf_verify_params* p,
@@ -85,21 +104,8 @@ ppf_status verify_rendered_run(const ppf_frame_detection* dets, int n_dets, cons
   HIPCHK(hipGetLastError());
   std::vector<int> box((size_t)t.nj * 4);
   if ((s = fr.read(box.data(), d_box, box.size() * sizeof(int))) != PPF_OK) return s;
-  /* each job's window at its offset in one scratch of the summed sizes */
-  std::vector<RndWin> win((size_t)t.nj);
-  unsigned long long total = 0;
-  for (int j = 0; j < t.nj; j++) {
-    const int* b = &box[(size_t)j * 4];
-    RndWin& w = win[(size_t)j];
-    w.u0 = -b[0];
-    w.v0 = -b[1];
-    const bool empty = b[2] < w.u0 || b[3] < w.v0; /* a job without a rendered row keeps the preset */
-    w.w = empty ? 0 : b[2] - w.u0 + 1;
-    w.h = empty ? 0 : b[3] - w.v0 + 1;
-    if (empty) w.u0 = w.v0 = 0;
-    w.off = total;
-    total += (unsigned long long)w.w * (unsigned long long)w.h;
-  }
+  std::vector<RndWin> win;
+  const unsigned long long total = render_windows(box, win);
   uint32_t* zbuf;
   if ((s = fr.get((size_t)total, &zbuf)) != PPF_OK) return s;
   HIPCHK(hipMemcpy(d_win, win.data(), win.size() * sizeof(RndWin), hipMemcpyHostToDevice));
