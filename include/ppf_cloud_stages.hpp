@@ -168,32 +168,16 @@ class Cloud {
     const size_t nd = dets.size();
     if (modelClouds.size() != nd || poses.size() != nd)
       throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::verifyFrame: one model cloud and one pose list per detection");
-    size_t top = 1;
-    for (size_t i = 0; i < nd; i++) top = poses[i].size() > top ? poses[i].size() : top;
-    std::vector<ppf_frame_detection> d(nd + 1);
-    std::vector<ppf_pose> recs(nd * top + 1);
-    std::vector<int> n(nd + 1, 0);
-    for (size_t i = 0; i < nd; i++) {
-      d[i].model = 0;
-      d[i].edge = 0;
-      const bool live = modelClouds[i] && modelClouds[i]->handle() && dets[i].first.handle() && !poses[i].empty();
-      d[i].model_cloud = live ? modelClouds[i]->handle() : 0;
-      d[i].scene = live ? dets[i].first.handle() : 0;
-      n[i] = live ? (int)poses[i].size() : 0;
-      for (int k = 0; k < n[i]; k++) recs[i * top + (size_t)k] = poses[i][(size_t)k].record();
-    }
-    ppf_verify_params p;
-    if (params) p = *params;
-    else ppf_default_verify_params(&p);
+    const PoseTable t(modelClouds, &dets, poses);
+    const size_t top = t.top;
+    const ppf_verify_params p = orDefaults(params, ppf_default_verify_params);
     const double intr[4] = {fx, fy, ppx, ppy};
     std::vector<ppf_pose_score> sc(nd * top + 1);
     std::vector<int> b(nd + 1, -1);
-    ppf_match_3d::check(ppf_verify_frame(&d[0], (int)nd, &recs[0], &n[0], (int)top, depth, rows, cols, depth ? intr : 0, &p, &sc[0], &b[0],
+    ppf_match_3d::check(ppf_verify_frame(&t.d[0], (int)nd, &t.recs[0], &t.n[0], (int)top, depth, rows, cols, depth ? intr : 0, &p, &sc[0], &b[0],
                                          stats));
-    std::vector<std::vector<ppf_pose_score> > out(nd);
-    for (size_t i = 0; i < nd; i++) out[i].assign(sc.begin() + (std::ptrdiff_t)(i * top), sc.begin() + (std::ptrdiff_t)(i * top + (size_t)n[i]));
     if (best) best->assign(b.begin(), b.begin() + (std::ptrdiff_t)nd);
-    return out;
+    return t.perDetection(sc);
   }
   /* verifyFrame with self-occlusion (ppf_verify_frame_rendered): a model row counts only where it is visible in a surfel
    * z-buffer of its own pose, rows x cols with the intrinsics prepareFrame took.  depth may be 0 (no depth test); the image
@@ -209,35 +193,17 @@ class Cloud {
     const size_t nd = dets.size();
     if (modelClouds.size() != nd || poses.size() != nd)
       throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::verifyFrameRendered: one model cloud and one pose list per detection");
-    size_t top = 1;
-    for (size_t i = 0; i < nd; i++) top = poses[i].size() > top ? poses[i].size() : top;
-    std::vector<ppf_frame_detection> d(nd + 1);
-    std::vector<ppf_pose> recs(nd * top + 1);
-    std::vector<int> n(nd + 1, 0);
-    for (size_t i = 0; i < nd; i++) {
-      d[i].model = 0;
-      d[i].edge = 0;
-      const bool live = modelClouds[i] && modelClouds[i]->handle() && dets[i].first.handle() && !poses[i].empty();
-      d[i].model_cloud = live ? modelClouds[i]->handle() : 0;
-      d[i].scene = live ? dets[i].first.handle() : 0;
-      n[i] = live ? (int)poses[i].size() : 0;
-      for (int k = 0; k < n[i]; k++) recs[i * top + (size_t)k] = poses[i][(size_t)k].record();
-    }
-    ppf_verify_params p;
-    if (params) p = *params;
-    else ppf_default_verify_params(&p);
-    ppf_render_params rp;
-    if (rparams) rp = *rparams;
-    else ppf_default_render_params(&rp);
+    const PoseTable t(modelClouds, &dets, poses);
+    const size_t top = t.top;
+    const ppf_verify_params p = orDefaults(params, ppf_default_verify_params);
+    const ppf_render_params rp = orDefaults(rparams, ppf_default_render_params);
     const double intr[4] = {fx, fy, ppx, ppy};
     std::vector<ppf_pose_score> sc(nd * top + 1);
     std::vector<int> b(nd + 1, -1);
-    ppf_match_3d::check(ppf_verify_frame_rendered(&d[0], (int)nd, &recs[0], &n[0], (int)top, depth, rows, cols, intr, &p, &rp, &sc[0],
+    ppf_match_3d::check(ppf_verify_frame_rendered(&t.d[0], (int)nd, &t.recs[0], &t.n[0], (int)top, depth, rows, cols, intr, &p, &rp, &sc[0],
                                                   &b[0], stats));
-    std::vector<std::vector<ppf_pose_score> > out(nd);
-    for (size_t i = 0; i < nd; i++) out[i].assign(sc.begin() + (std::ptrdiff_t)(i * top), sc.begin() + (std::ptrdiff_t)(i * top + (size_t)n[i]));
     if (best) best->assign(b.begin(), b.begin() + (std::ptrdiff_t)nd);
-    return out;
+    return t.perDetection(sc);
   }
   /* Depth and instance-label images of one chosen pose per detection (ppf_render_frame), in place of the reference's
    * transformPCPose -> writePLY dump: poses[i][which[i]] moves modelClouds[i] (which[i] < 0, or no model cloud: not drawn;
@@ -251,30 +217,20 @@ class Cloud {
     const size_t nd = poses.size();
     if (modelClouds.size() != nd || which.size() != nd)
       throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::renderFrame: one model cloud and one pose index per detection");
-    size_t top = 1;
-    for (size_t i = 0; i < nd; i++) top = poses[i].size() > top ? poses[i].size() : top;
-    std::vector<ppf_frame_detection> d(nd + 1);
-    std::vector<ppf_pose> recs(nd * top + 1);
+    const PoseTable t(modelClouds, 0, poses);
     std::vector<int> w(nd + 1, -1);
     for (size_t i = 0; i < nd; i++) {
-      d[i].model = 0;
-      d[i].scene = 0;
-      d[i].edge = 0;
       const bool live = modelClouds[i] && modelClouds[i]->handle() && which[i] >= 0;
-      d[i].model_cloud = live ? modelClouds[i]->handle() : 0;
       if (live && (size_t)which[i] >= poses[i].size())
         throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::renderFrame: which[i] is past the detection's poses");
       w[i] = live ? which[i] : -1;
-      for (size_t k = 0; k < poses[i].size(); k++) recs[i * top + k] = poses[i][k].record();
     }
-    ppf_render_params rp;
-    if (rparams) rp = *rparams;
-    else ppf_default_render_params(&rp);
+    const ppf_render_params rp = orDefaults(rparams, ppf_default_render_params);
     const double intr[4] = {fx, fy, ppx, ppy};
     const size_t npx = rows > 0 && cols > 0 ? (size_t)rows * (size_t)cols : 0;
     if (depthOut) depthOut->assign(npx, 0.f);
     if (labelOut) labelOut->assign(npx, -1);
-    ppf_match_3d::check(ppf_render_frame(&d[0], (int)nd, &recs[0], &w[0], (int)top, rows, cols, intr, &rp,
+    ppf_match_3d::check(ppf_render_frame(&t.d[0], (int)nd, &t.recs[0], &w[0], (int)t.top, rows, cols, intr, &rp,
                                          depthOut && npx ? &(*depthOut)[0] : 0, labelOut && npx ? &(*labelOut)[0] : 0, stats));
   }
   /* One consistent set among all poses of all detections of a frame (ppf_select_frame): duplicates and the
@@ -293,32 +249,15 @@ class Cloud {
     const size_t nd = poses.size();
     if (modelClouds.size() != nd || (scores && scores->size() != nd))
       throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::selectFrame: one model cloud (and one score list) per detection");
-    size_t top = 1;
-    for (size_t i = 0; i < nd; i++) top = poses[i].size() > top ? poses[i].size() : top;
-    std::vector<ppf_frame_detection> d(nd + 1);
-    std::vector<ppf_pose> recs(nd * top + 1);
+    const PoseTable t(modelClouds, 0, poses);
+    const size_t top = t.top;
     std::vector<ppf_pose_score> sc(nd * top + 1);
-    std::vector<int> n(nd + 1, 0);
-    for (size_t i = 0; i < nd; i++) {
-      d[i].model = 0;
-      d[i].scene = 0;
-      d[i].edge = 0;
-      const bool live = modelClouds[i] && modelClouds[i]->handle() && !poses[i].empty();
-      d[i].model_cloud = live ? modelClouds[i]->handle() : 0;
-      n[i] = live ? (int)poses[i].size() : 0;
-      if (scores && live && (*scores)[i].size() < poses[i].size())
-        throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::selectFrame: fewer scores than poses");
-      for (int k = 0; k < n[i]; k++) {
-        recs[i * top + (size_t)k] = poses[i][(size_t)k].record();
-        if (scores) sc[i * top + (size_t)k] = (*scores)[i][(size_t)k];
-      }
+    for (size_t i = 0; scores && i < nd; i++) {
+      if ((*scores)[i].size() < (size_t)t.n[i]) throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::selectFrame: fewer scores than poses");
+      for (int k = 0; k < t.n[i]; k++) sc[i * top + (size_t)k] = (*scores)[i][(size_t)k];
     }
-    ppf_select_params p;
-    if (params) p = *params;
-    else ppf_default_select_params(&p);
-    ppf_render_params rp;
-    if (rparams) rp = *rparams;
-    else ppf_default_render_params(&rp);
+    const ppf_select_params p = orDefaults(params, ppf_default_select_params);
+    const ppf_render_params rp = orDefaults(rparams, ppf_default_render_params);
     const double intr[4] = {fx, fy, ppx, ppy};
     const size_t npx = rows > 0 && cols > 0 ? (size_t)rows * (size_t)cols : 0;
     if (depthOut) depthOut->assign(npx, 0.f);
@@ -326,14 +265,10 @@ class Cloud {
     std::vector<ppf_select_info> rowsOut(nd * top + 1);
     std::vector<int> sel(nd * top + 1, -1);
     int nSel = 0;
-    ppf_match_3d::check(ppf_select_frame(&d[0], (int)nd, &recs[0], &n[0], (int)top, scores ? &sc[0] : 0, depth, rows, cols, intr, &rp, &p,
+    ppf_match_3d::check(ppf_select_frame(&t.d[0], (int)nd, &t.recs[0], &t.n[0], (int)top, scores ? &sc[0] : 0, depth, rows, cols, intr, &rp, &p,
                                          &rowsOut[0], &sel[0], &nSel, depthOut && npx ? &(*depthOut)[0] : 0,
                                          labelOut && npx ? &(*labelOut)[0] : 0, stats));
-    if (info) {
-      info->assign(nd, std::vector<ppf_select_info>());
-      for (size_t i = 0; i < nd; i++)
-        (*info)[i].assign(rowsOut.begin() + (std::ptrdiff_t)(i * top), rowsOut.begin() + (std::ptrdiff_t)(i * top + (size_t)n[i]));
-    }
+    if (info) *info = t.perDetection(rowsOut);
     std::vector<std::pair<int, int> > out;
     for (int r = 0; r < nSel; r++) out.push_back(std::make_pair(sel[(size_t)r] / (int)top, sel[(size_t)r] % (int)top));
     return out;
@@ -357,6 +292,42 @@ class Cloud {
   }
 
  private:
+  /* the tables every stage after matchFrame takes: one ppf_frame_detection, `top` (the longest list, at least 1) pose records
+   * and one pose count per detection, each padded by one element so that &v[0] is valid without detections.  A detection is
+   * live with a model cloud, poses and, where dets is given, an object cloud; the others get no handles and count 0.
+   * renderFrame draws by which[i], not by n: a live detection it does not draw (which[i] < 0) keeps its handle here, and
+   * ppf_render_frame reads neither handle nor poses of a detection whose which is -1. */
+  struct PoseTable {
+    size_t top;
+    std::vector<ppf_frame_detection> d;
+    std::vector<ppf_pose> recs;
+    std::vector<int> n;
+    PoseTable(const std::vector<const Cloud*>& modelClouds, const std::vector<std::pair<Cloud, Cloud> >* dets,
+              const std::vector<std::vector<ppf_match_3d::Pose3D> >& poses)
+        : top(1), d(poses.size() + 1), n(poses.size() + 1, 0) {
+      for (size_t i = 0; i < poses.size(); i++) top = poses[i].size() > top ? poses[i].size() : top;
+      recs.resize(poses.size() * top + 1);
+      for (size_t i = 0; i < poses.size(); i++) {
+        const bool live = modelClouds[i] && modelClouds[i]->handle() && (!dets || (*dets)[i].first.handle()) && !poses[i].empty();
+        d[i].model = 0;
+        d[i].edge = 0;
+        d[i].model_cloud = live ? modelClouds[i]->handle() : 0;
+        d[i].scene = live && dets ? (*dets)[i].first.handle() : 0;
+        n[i] = live ? (int)poses[i].size() : 0;
+        for (int k = 0; k < n[i]; k++) recs[i * top + (size_t)k] = poses[i][(size_t)k].record();
+      }
+    }
+    /* flat[i * top + k] -> out[i][k], the n[i] rows of each detection */
+    template <class T>
+    std::vector<std::vector<T> > perDetection(const std::vector<T>& flat) const {
+      std::vector<std::vector<T> > out(n.size() - 1);
+      for (size_t i = 0; i < out.size(); i++)
+        out[i].assign(flat.begin() + (std::ptrdiff_t)(i * top), flat.begin() + (std::ptrdiff_t)(i * top + (size_t)n[i]));
+      return out;
+    }
+  };
+  template <class P>
+  static P orDefaults(const P* given, void (*defaults)(P*)) { P p; if (given) p = *given; else defaults(&p); return p; }
   explicit Cloud(ppf_cloud* c) : h_(c, [](ppf_cloud* p) { ppf_cloud_release(p); }) {}
   static Cloud fromDepthImage(const void* depth, int format, double scale, int rows, int cols, double fx, double fy, double ppx,
                               double ppy, float zMin, float zMax, bool fp64, size_t rowPitchBytes) {

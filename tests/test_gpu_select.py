@@ -204,12 +204,11 @@ def test_counts_do_not_depend_on_the_rest_of_the_call(frame):
             assert one[0, 0][f].tobytes() == full[i, k][f].tobytes(), (i, k, f)
         counts.add((st1["n_launches"], st1["n_host_syncs"]))
     counts.add((st24["n_launches"], st24["n_host_syncs"]))
-    assert len(counts) == 1 and counts.pop()[1] <= 2, counts
+    assert counts == {(7, 2)}, counts   # window, splat, mask, key, overlap, greedy, report; the windows and the results
     # with the images: two more launches, the same for 1 and 24 hypotheses
     a = select_frame([mc], [frame["poses"][0][:1]], depth, intr, None, RP, return_images=True, return_stats=True)[-1]
     b = select_frame([mc] * 3, frame["poses"], depth, intr, None, RP, return_images=True, return_stats=True)[-1]
-    assert (a["n_launches"], a["n_host_syncs"]) == (b["n_launches"], b["n_host_syncs"]) and b["n_host_syncs"] <= 2
-    assert b["n_launches"] == st24["n_launches"] + 2
+    assert (a["n_launches"], a["n_host_syncs"]) == (b["n_launches"], b["n_host_syncs"]) == (9, 2)   # + paint and resolve
 
 
 def test_two_concurrent_callers(frame, c1):

@@ -13,20 +13,14 @@ Writes profiles/r12_select_timing.json (or --out).
 The kernel trace is a run of its own:
   rocprofv3 --kernel-trace --stats -d <dir> -o select -- python tools/select_timing.py --reps 5 --no-write
 """
-import argparse
-import json
 import os
 import sys
 import time
 
-import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-from render_timing import stats  # noqa: E402
+import frame_cases  # noqa: E402
+from frame_cases import stats  # noqa: E402
 from yolo_ppf_pose_estimation_amd.cloud_processor import select_frame, verify_frame_rendered  # noqa: E402
 
 
@@ -56,26 +50,5 @@ def run_case(name, dets, poses, depth, intr, reps):
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12_select_timing.json"))
-    ap.add_argument("--no-write", action="store_true")
-    a = ap.parse_args()
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("select_timing.py needs a GPU")
-    import render_timing as RT
-    RT.run_case = run_case   # the same three cases, timed for the selection
-    bottle = np.load(os.path.join(ROOT, "tests", "golden", "bottle_model_xyzn.npy"))
-    cases = RT.c1_cases(bottle, a.reps) + [RT.rendered_case(bottle, a.reps)]
-    doc = {"tool": "tools/select_timing.py", "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "cases": cases}
-    print(json.dumps(doc, indent=1))
-    if not a.no_write:
-        with open(a.out, "w") as f:
-            json.dump(doc, f, indent=1)
-            f.write("\n")
-
-
 if __name__ == "__main__":
-    main()
+    frame_cases.main("select_timing.py", "r12_select_timing.json", run_case)

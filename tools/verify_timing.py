@@ -11,31 +11,15 @@ host-to-device copy of the same image (torch, pageable memory), the part of the 
 profiles/r09_verify_timing.json (or --out).  The kernel trace is a run of its own:
   rocprofv3 --kernel-trace --stats -d <dir> -o verify -- python tools/verify_timing.py --reps 5 --no-write
 """
-import argparse
-import ctypes as C
-import json
 import os
 import sys
 import time
 
-import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import prep_data as D  # noqa: E402
-from yolo_ppf_pose_estimation_amd._capi import FrameDetection, IcpParams, MatchFrameStats, Pose, check, lib  # noqa: E402
-from yolo_ppf_pose_estimation_amd.cloud_processor import DeviceCloud, verify_frame  # noqa: E402
-from yolo_ppf_pose_estimation_amd.detector import PPF3DDetector  # noqa: E402
-
-PREP = dict(leaf=0.003, mean_k=50, stddev_mul=1.0, normal_k=30, curvature_threshold=0.03)
-
-
-def stats(v):
-    v = np.asarray(v)
-    return {"median_ms": round(float(np.median(v)), 4), "p10_ms": round(float(np.percentile(v, 10)), 4),
-            "p90_ms": round(float(np.percentile(v, 90)), 4)}
+import frame_cases  # noqa: E402
+from frame_cases import stats  # noqa: E402
+from yolo_ppf_pose_estimation_amd.cloud_processor import verify_frame  # noqa: E402
 
 
 def upload_ms(depth, reps):
@@ -75,55 +59,5 @@ def run_case(name, dets, poses, depth, intr, reps):
     return res
 
 
-def c1_cases(bottle, reps):
-    xyz, depth, box, intr = D.c1_frame()
-    obj = DeviceCloud.upload(xyz).prep_frame([box], depth, intr, PREP)[0][0]
-    golden = np.load(os.path.join(ROOT, "tests", "golden", "c1_pipeline_golden.npz"))
-    poses = [golden["icp_poses"][k] for k in range(5)]
-    mc = DeviceCloud.upload(bottle)
-    out = [run_case(f"c1_k{K}", [(mc, obj)] * K, [poses] * K, depth, intr, reps) for K in (1, 8)]
-    out[0]["model_rows"], out[0]["object_rows"] = int(bottle.shape[0]), len(obj)
-    return out
-
-
-def rendered_case(bottle, reps):
-    from test_gpu_frame import _render_frame
-    scene, depth, boxes, K, objs, solid = _render_frame(bottle)
-    intr = (K[0, 0], K[1, 1], K[0, 2], K[1, 2])
-    pairs = DeviceCloud.upload(scene).prep_frame(boxes, depth, intr, dict(PREP, leaf=0.004))
-    det_b = PPF3DDetector(0.05, 0.05).trainModel(bottle)
-    det_s = PPF3DDetector(0.05, 0.05).trainModel(solid)
-    mcs = [DeviceCloud.upload(bottle), DeviceCloud.upload(bottle), DeviceCloud.upload(solid)]
-    fd = (FrameDetection * 3)()
-    for i, d in enumerate((det_b, det_b, det_s)):
-        fd[i].model, fd[i].model_cloud, fd[i].scene, fd[i].edge = d._model.ptr, mcs[i]._ptr, pairs[i][0]._ptr, pairs[i][1]._ptr
-    ip = IcpParams()
-    lib().ppf_default_icp_params(C.byref(ip))
-    out, n_out = (Pose * 15)(), (C.c_int * 3)()
-    check(lib().ppf_match_frame(fd, 3, C.byref(det_b._params(0.05, 0.05, False)), C.byref(ip), 5, out, n_out, None,
-                                C.byref(MatchFrameStats())))
-    poses = [[np.array(out[i * 5 + k].pose).reshape(4, 4) for k in range(n_out[i])] for i in range(3)]
-    return run_case("rendered", [(mcs[i], pairs[i][0]) for i in range(3)], poses, depth, intr, reps)
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r09_verify_timing.json"))
-    ap.add_argument("--no-write", action="store_true")
-    a = ap.parse_args()
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("verify_timing.py needs a GPU")
-    bottle = np.load(os.path.join(ROOT, "tests", "golden", "bottle_model_xyzn.npy"))
-    cases = c1_cases(bottle, a.reps) + [rendered_case(bottle, a.reps)]
-    doc = {"tool": "tools/verify_timing.py", "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "cases": cases}
-    print(json.dumps(doc, indent=1))
-    if not a.no_write:
-        with open(a.out, "w") as f:
-            json.dump(doc, f, indent=1)
-            f.write("\n")
-
-
 if __name__ == "__main__":
-    main()
+    frame_cases.main("verify_timing.py", "r09_verify_timing.json", run_case)

@@ -188,24 +188,23 @@ def _pose_record(p) -> Pose:
     return rec
 
 
-def _verify_params(params) -> VerifyParams:
-    if isinstance(params, VerifyParams):
+def _params(cls, defaults: str, params):
+    """``params`` as a ``cls`` record: itself, or the C defaults (``lib().<defaults>``) with a dict's fields set over them"""
+    if isinstance(params, cls):
         return params
-    prm = VerifyParams()
-    lib().ppf_default_verify_params(C.byref(prm))
+    prm = cls()
+    getattr(lib(), defaults)(C.byref(prm))
     for key, v in (params or {}).items():
         setattr(prm, key, v)
     return prm
 
 
-def _render_params(params) -> RenderParams:
-    if isinstance(params, RenderParams):
-        return params
-    prm = RenderParams()
-    lib().ppf_default_render_params(C.byref(prm))
-    for key, v in (params or {}).items():
-        setattr(prm, key, v)
-    return prm
+def _depth_image(depth, error: str):
+    """(the contiguous float32 image, rows, cols) of a 2-D depth image; anything else raises ``error``"""
+    img = np.ascontiguousarray(depth, dtype=np.float32) if depth is not None else None
+    if img is None or img.ndim != 2:
+        raise PPFError(_capi.PPF_ERR_INVALID, error)
+    return (img,) + img.shape
 
 
 def _frame_tables(dets, poses, top):
@@ -230,6 +229,18 @@ def _frame_tables(dets, poses, top):
     return n, top, arr, recs, n_poses
 
 
+def _verify_call(entry, tables, img, rows, cols, it, *prms):
+    """either verify entry on the tables of _frame_tables: (scores (n_dets, top), best (n_dets,), the counters)"""
+    n, top, arr, recs, n_poses = tables
+    scores = (PoseScore * (max(n, 1) * top))()
+    best = (C.c_int * max(n, 1))()
+    st = VerifyStats()
+    check(entry(arr, n, recs, n_poses, top, img.ctypes.data if img is not None else None, rows, cols, it, *[C.byref(p) for p in prms],
+                scores, best, C.byref(st)))
+    out = np.ctypeslib.as_array(scores).copy()[:n * top].reshape(n, top)
+    return out, np.array(best[:n], dtype=np.int32), _capi.stats_dict(st)
+
+
 def verify_frame(dets, poses, top: Optional[int] = None, depth=None, intr=None, params=None):
     """One ppf_verify_frame call: score every pose of every detection against its object cloud and, when ``depth`` is given,
     against the depth image.  dets: per detection a (model cloud, object cloud) pair of DeviceClouds, or
@@ -238,22 +249,13 @@ def verify_frame(dets, poses, top: Optional[int] = None, depth=None, intr=None, 
     params: a VerifyParams, a dict of its fields (the rest default) or None.  Returns (scores, best, stats): the
     PoseScore rows as a numpy structured array of shape (n_dets, top) (rows past a detection's poses are zero), the best
     index per detection (-1 without poses) and the call's counters as a dict."""
-    n, top, arr, recs, n_poses = _frame_tables(dets, poses, top)
-    prm = _verify_params(params)
+    tables = _frame_tables(dets, poses, top)
+    prm = _params(VerifyParams, "ppf_default_verify_params", params)
     img, it, rows, cols = None, None, 0, 0
     if depth is not None:
-        img = np.ascontiguousarray(depth, dtype=np.float32)
-        if img.ndim != 2:
-            raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 image")
-        rows, cols = img.shape
+        img, rows, cols = _depth_image(depth, "depth must be a 2-D float32 image")
         it = (C.c_double * 4)(*_intr4(intr))
-    scores = (PoseScore * (max(n, 1) * top))()
-    best = (C.c_int * max(n, 1))()
-    st = VerifyStats()
-    check(lib().ppf_verify_frame(arr, n, recs, n_poses, top, img.ctypes.data if img is not None else None, rows, cols, it, C.byref(prm),
-                                 scores, best, C.byref(st)))
-    out = np.ctypeslib.as_array(scores).copy()[:n * top].reshape(n, top)
-    return out, np.array(best[:n], dtype=np.int32), _capi.stats_dict(st)
+    return _verify_call(lib().ppf_verify_frame, tables, img, rows, cols, it, prm)
 
 
 def verify_frame_rendered(dets, poses, top: Optional[int] = None, depth=None, intr=None, params=None, render_params=None,
@@ -262,28 +264,20 @@ def verify_frame_rendered(dets, poses, top: Optional[int] = None, depth=None, in
     z-buffer of its own pose.  The render needs the image: ``image_size`` (rows, cols) and ``intr`` are
     required when ``depth`` is None, and default to the depth image's size otherwise.  render_params: a RenderParams, a
     dict of its fields (the rest default) or None.  Returns (scores, best, stats) as verify_frame does."""
-    n, top, arr, recs, n_poses = _frame_tables(dets, poses, top)
-    prm, rprm = _verify_params(params), _render_params(render_params)
+    tables = _frame_tables(dets, poses, top)
+    prm = _params(VerifyParams, "ppf_default_verify_params", params)
+    rprm = _params(RenderParams, "ppf_default_render_params", render_params)
     img = None
     if depth is not None:
-        img = np.ascontiguousarray(depth, dtype=np.float32)
-        if img.ndim != 2:
-            raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 image")
+        img, rows, cols = _depth_image(depth, "depth must be a 2-D float32 image")
         if image_size is not None and tuple(image_size) != img.shape:
             raise PPFError(_capi.PPF_ERR_INVALID, f"image_size {tuple(image_size)} is not the depth image's {img.shape}")
-        rows, cols = img.shape
     elif image_size is not None:
         rows, cols = (int(v) for v in image_size)
     else:
         raise PPFError(_capi.PPF_ERR_INVALID, "verify_frame_rendered needs a depth image or image_size")
     it = (C.c_double * 4)(*_intr4(intr)) if intr is not None else None
-    scores = (PoseScore * (max(n, 1) * top))()
-    best = (C.c_int * max(n, 1))()
-    st = VerifyStats()
-    check(lib().ppf_verify_frame_rendered(arr, n, recs, n_poses, top, img.ctypes.data if img is not None else None, rows, cols, it,
-                                          C.byref(prm), C.byref(rprm), scores, best, C.byref(st)))
-    out = np.ctypeslib.as_array(scores).copy()[:n * top].reshape(n, top)
-    return out, np.array(best[:n], dtype=np.int32), _capi.stats_dict(st)
+    return _verify_call(lib().ppf_verify_frame_rendered, tables, img, rows, cols, it, prm, rprm)
 
 
 def render_frame(dets, poses, which, rows: int, cols: int, intr, render_params=None, top: Optional[int] = None, return_stats: bool = False):
@@ -297,7 +291,7 @@ def render_frame(dets, poses, which, rows: int, cols: int, intr, render_params=N
     if len(which) != n:
         raise PPFError(_capi.PPF_ERR_INVALID, f"{len(which)} entries of which for {n} detections")
     ws = (C.c_int * max(n, 1))(*[int(w) if pairs[i] is not None else -1 for i, w in enumerate(which)])
-    rprm = _render_params(render_params)
+    rprm = _params(RenderParams, "ppf_default_render_params", render_params)
     it = (C.c_double * 4)(*_intr4(intr)) if intr is not None else None
     depth = np.zeros((max(int(rows), 0), max(int(cols), 0)), dtype=np.float32)
     label = np.full(depth.shape, -1, dtype=np.int32)
@@ -305,16 +299,6 @@ def render_frame(dets, poses, which, rows: int, cols: int, intr, render_params=N
     check(lib().ppf_render_frame(arr, n, recs, ws, top, int(rows), int(cols), it, C.byref(rprm), depth.ctypes.data, label.ctypes.data,
                                  C.byref(st)))
     return (depth, label, _capi.stats_dict(st)) if return_stats else (depth, label)
-
-
-def _select_params(params) -> SelectParams:
-    if isinstance(params, SelectParams):
-        return params
-    prm = SelectParams()
-    lib().ppf_default_select_params(C.byref(prm))
-    for key, v in (params or {}).items():
-        setattr(prm, key, v)
-    return prm
 
 
 def select_frame(dets, poses, depth, intr, params=None, render_params=None, scores=None, top: Optional[int] = None,
@@ -329,11 +313,9 @@ def select_frame(dets, poses, depth, intr, params=None, render_params=None, scor
     (0 where empty) and label (flat index, -1 where empty) images of the selection, with ``return_stats`` the counters."""
     pairs = [None if d is None else (d[0] if isinstance(d, tuple) else d, None) for d in dets]
     n, top, arr, recs, n_poses = _frame_tables(pairs, poses, top)
-    prm, rprm = _select_params(params), _render_params(render_params)
-    img = np.ascontiguousarray(depth, dtype=np.float32) if depth is not None else None
-    if img is None or img.ndim != 2:
-        raise PPFError(_capi.PPF_ERR_INVALID, "select_frame needs a 2-D float32 depth image")
-    rows, cols = img.shape
+    prm = _params(SelectParams, "ppf_default_select_params", params)
+    rprm = _params(RenderParams, "ppf_default_render_params", render_params)
+    img, rows, cols = _depth_image(depth, "select_frame needs a 2-D float32 depth image")
     it = (C.c_double * 4)(*_intr4(intr)) if intr is not None else None
     sc = None
     if scores is not None:

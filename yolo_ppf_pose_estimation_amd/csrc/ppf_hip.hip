@@ -26,7 +26,8 @@
  *             ppf_depth_kernels.h  ppf_verify_kernels.h  ppf_render_kernels.h  ppf_select_kernels.h
  *   host      ppf_device_mem.h (errors, block cache)  ppf_host_common.h (scans, sorts, model / workspace structs)
  *             ppf_model_host.h  ppf_match_host.h  ppf_batch_host.h  ppf_icp_host.h  ppf_prep_host.h  ppf_frame_host.h
- *             ppf_match_frame_host.h  ppf_depth_host.h  ppf_verify_host.h  ppf_render_host.h  ppf_select_host.h  (the C-ABI)
+ *             ppf_match_frame_host.h  ppf_depth_host.h  ppf_posetable_host.h  ppf_verify_host.h  ppf_render_host.h
+ *             ppf_select_host.h  (the C-ABI)
  *
  * Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see __graft_entry__.build()).
  * No CPU fallback exists: without a HIP device the compute entry points return PPF_ERR_HIP.
@@ -71,6 +72,7 @@
 #include "ppf_frame_host.h"    /* row N4 for all boxes of a frame: ppf_prep_frame */
 #include "ppf_match_frame_host.h" /* match + ICP for all detections of a frame: ppf_match_frame */
 #include "ppf_depth_host.h"       /* the scene cloud from a depth image: ppf_cloud_from_depth */
+#include "ppf_posetable_host.h"   /* what the stages on a frame's pose table share: checks, render jobs, clears */
 #include "ppf_verify_host.h"      /* pose verification of every detection of a frame: ppf_verify_frame */
 #include "ppf_render_host.h"      /* surfel z-buffers: ppf_verify_frame_rendered, ppf_render_frame */
 #include "ppf_select_host.h"      /* one consistent set of poses per frame: ppf_select_frame */

@@ -1,7 +1,8 @@
 /*
  * ppf_render_host.h — host side of ppf_verify_frame_rendered (pose verification with self-occlusion) and ppf_render_frame
  * (depth and instance-label images of the chosen poses).  Kernels: ppf_render_kernels.h.  Included by ppf_hip.hip after
- * ppf_verify_host.h (verify_check, verify_tables, verify_args).
+ * ppf_posetable_host.h (the checks, job table and clears of a pose table) and ppf_verify_host.h (verify_check, verify_tables,
+ * verify_args).
  *
  * ppf_verify_frame_rendered, per call with at least one pose: the verify tables and grids (seven launches), then
  * k_rnd_window and the first read-back (each job's window), the window table upload, k_rnd_splat into one scratch of the
@@ -17,17 +18,6 @@ ppf_status render_params_check(const ppf_render_params* rp, const char* who) {
   if (!(std::isfinite(rp->splat_radius) && rp->splat_radius > 0.f)) return fail(PPF_ERR_INVALID, "%s: splat_radius must be finite and > 0", who);
   if (!(std::isfinite(rp->visible_tol) && rp->visible_tol > 0.f)) return fail(PPF_ERR_INVALID, "%s: visible_tol must be finite and > 0", who);
   if (rp->flags != 0) return fail(PPF_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)rp->flags);
-  return PPF_OK;
-}
-
-/* the image a render draws into: rows x cols > 0, at most INT32_MAX pixels, fx and fy finite and > 0, ppx and ppy finite */
-ppf_status render_image_check(int rows, int cols, const double* intr, const char* who) {
-  if (rows <= 0 || cols <= 0) return fail(PPF_ERR_INVALID, "%s: the image is %d x %d", who, rows, cols);
-  if ((long long)rows * cols > 0x7fffffffLL) return fail(PPF_ERR_INVALID, "%s: %d x %d pixels exceed INT32_MAX", who, rows, cols);
-  if (!intr) return fail(PPF_ERR_INVALID, "%s: intr is NULL", who);
-  if (!(std::isfinite(intr[0]) && std::isfinite(intr[1]) && intr[0] > 0.0 && intr[1] > 0.0))
-    return fail(PPF_ERR_INVALID, "%s: fx and fy must be finite and > 0", who);
-  if (!std::isfinite(intr[2]) || !std::isfinite(intr[3])) return fail(PPF_ERR_INVALID, "%s: ppx and ppy must be finite", who);
   return PPF_OK;
 }
 
@@ -63,59 +53,61 @@ unsigned long long render_windows(const std::vector<int>& box, std::vector<RndWi
   return total;
 }
 
+/* every job drawn alone: its window of the image, and its z-buffer there at its offset in one scratch */
+struct RndWindows {
+  std::vector<RndWin> win; /* the host's copy of d_win */
+  RndWin* d_win = nullptr;
+  uint32_t* zbuf = nullptr;
+  RndCam cam;
+};
+
+/* job upload, k_rnd_window, one read-back (each job's box), the window table upload, k_rnd_splat; max_n as
+ * table_render_jobs returns it */
+ppf_status render_job_windows(FrameRun& fr, const std::vector<RndJob>& jobs, int max_n, int rows, int cols, const double* intr,
+                              const ppf_render_params* rp, RndWindows& o) {
+  const size_t nj = jobs.size();
+  RndJob* d_jobs;
+  int* d_box;
+  ppf_status s;
+  if ((s = fr.get(nj, &d_jobs)) != PPF_OK || (s = fr.get(nj, &o.d_win)) != PPF_OK || (s = fr.get(nj * 4, &d_box)) != PPF_OK) return s;
+  HIPCHK(hipMemcpy(d_jobs, jobs.data(), nj * sizeof(RndJob), hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(d_box, 0x80, nj * 4 * sizeof(int), nullptr));
+  o.cam = render_cam(rows, cols, intr, rp);
+  const dim3 grid_jobs(grid_for((size_t)max_n, RND_BLOCK).x, (unsigned)nj);
+  FRAME_LAUNCH(fr, k_rnd_window, grid_jobs, dim3(RND_BLOCK), d_jobs, o.cam, d_box);
+  HIPCHK(hipGetLastError());
+  std::vector<int> box(nj * 4);
+  if ((s = fr.read(box.data(), d_box, box.size() * sizeof(int))) != PPF_OK) return s;
+  const unsigned long long total = render_windows(box, o.win);
+  if ((s = fr.get((size_t)total, &o.zbuf)) != PPF_OK) return s;
+  HIPCHK(hipMemcpy(o.d_win, o.win.data(), nj * sizeof(RndWin), hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(o.zbuf, 0xff, (size_t)std::max<unsigned long long>(total, 1) * sizeof(uint32_t), nullptr));
+  FRAME_LAUNCH(fr, k_rnd_splat, grid_jobs, dim3(RND_BLOCK), d_jobs, o.d_win, o.cam, o.zbuf);
+  return PPF_OK;
+}
+
 /* tables and grids -> windows (read-back 1) -> per-job renders -> scores (read-back 2); dev[j] = the score row of job j */
 ppf_status verify_rendered_run(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top,
                                const float* depth, int rows, int cols, const double* intr, const ppf_verify_params* p,
                                const ppf_render_params* rp, std::vector<ppf_pose_score>& dev, FrameRun& fr) {
-  static const char* who = "ppf_verify_frame_rendered";
   VfyTables t;
-  ppf_status s = verify_tables(dets, n_dets, poses, n_poses, top, p, who, t, fr);
+  ppf_status s = verify_tables(dets, n_dets, poses, n_poses, top, p, "ppf_verify_frame_rendered", t, fr);
   if (s != PPF_OK) return s;
   /* the render jobs: the same poses, every model row */
-  std::vector<RndJob> rj((size_t)t.nj);
-  int max_n = 1;
-  {
-    size_t j = 0;
-    for (int i = 0; i < n_dets; i++)
-      for (int k = 0; k < n_poses[i]; k++, j++) {
-        std::memcpy(rj[j].T, poses[(size_t)i * top + k].pose, sizeof(rj[j].T));
-        rj[j].model = dets[i].model_cloud->rows.p;
-        rj[j].n = dets[i].model_cloud->n;
-        rj[j].label = i;
-        max_n = std::max(max_n, rj[j].n);
-      }
-  }
-  RndJob* d_rj;
-  RndWin* d_win;
-  int* d_box;
+  std::vector<RndJob> rj;
+  const int max_n = table_render_jobs(dets, n_dets, poses, n_poses, TABLE_N_POSES, top, LABEL_DET, rj);
   VfyPartial* part;
   ppf_pose_score* d_out;
   float* d_depth = nullptr;
-  if ((s = fr.get(t.nj, &d_rj)) != PPF_OK || (s = fr.get(t.nj, &d_win)) != PPF_OK || (s = fr.get((size_t)t.nj * 4, &d_box)) != PPF_OK ||
-      (s = fr.get((size_t)t.nj * t.max_nb, &part)) != PPF_OK || (s = fr.get(t.nj, &d_out)) != PPF_OK)
-    return s;
-  if (depth && (s = fr.get((size_t)rows * cols, &d_depth)) != PPF_OK) return s;
-  HIPCHK(hipMemcpy(d_rj, rj.data(), rj.size() * sizeof(RndJob), hipMemcpyHostToDevice));
-  if (depth) HIPCHK(hipMemcpy(d_depth, depth, (size_t)rows * cols * sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(hipMemsetAsync(d_box, 0x80, (size_t)t.nj * 4 * sizeof(int), nullptr));
-  const RndCam cam = render_cam(rows, cols, intr, rp);
-  const dim3 grid_jobs(grid_for((size_t)max_n, RND_BLOCK).x, (unsigned)t.nj);
-  FRAME_LAUNCH(fr, k_rnd_window, grid_jobs, dim3(RND_BLOCK), d_rj, cam, d_box);
-  HIPCHK(hipGetLastError());
-  std::vector<int> box((size_t)t.nj * 4);
-  if ((s = fr.read(box.data(), d_box, box.size() * sizeof(int))) != PPF_OK) return s;
-  std::vector<RndWin> win;
-  const unsigned long long total = render_windows(box, win);
-  uint32_t* zbuf;
-  if ((s = fr.get((size_t)total, &zbuf)) != PPF_OK) return s;
-  HIPCHK(hipMemcpy(d_win, win.data(), win.size() * sizeof(RndWin), hipMemcpyHostToDevice));
-  HIPCHK(hipMemsetAsync(zbuf, 0xff, (size_t)std::max<unsigned long long>(total, 1) * sizeof(uint32_t), nullptr));
-  FRAME_LAUNCH(fr, k_rnd_splat, grid_jobs, dim3(RND_BLOCK), d_rj, d_win, cam, zbuf);
+  if ((s = fr.get((size_t)t.nj * t.max_nb, &part)) != PPF_OK || (s = fr.get(t.nj, &d_out)) != PPF_OK) return s;
+  if (depth && (s = frame_upload_depth(fr, depth, rows, cols, &d_depth)) != PPF_OK) return s;
+  RndWindows w;
+  if ((s = render_job_windows(fr, rj, max_n, rows, cols, intr, rp, w)) != PPF_OK) return s;
   const VfyArgs a = verify_args(t, d_depth, rows, cols, intr, p);
   RndView rv;
-  rv.wins = d_win;
-  rv.zbuf = zbuf;
-  rv.c = cam;
+  rv.wins = w.d_win;
+  rv.zbuf = w.zbuf;
+  rv.c = w.cam;
   FRAME_LAUNCH(fr, k_rnd_vfy_score, dim3((unsigned)t.max_nb, (unsigned)t.nj), dim3(VFY_BLOCK), a, rv, part);
   FRAME_LAUNCH(fr, k_vfy_finish, dim3((unsigned)t.nj), dim3(64), t.d_jobs, part, t.max_nb, depth ? 1 : 0, d_out);
   HIPCHK(hipGetLastError());
@@ -123,11 +115,9 @@ ppf_status verify_rendered_run(const ppf_frame_detection* dets, int n_dets, cons
   return fr.read(dev.data(), d_out, (size_t)t.nj * sizeof(ppf_pose_score));
 }
 
-ppf_status render_frame_run(const std::vector<RndJob>& jobs, int rows, int cols, const double* intr, const ppf_render_params* rp,
+ppf_status render_frame_run(const std::vector<RndJob>& jobs, int max_n, int rows, int cols, const double* intr, const ppf_render_params* rp,
                             float* depth_out, int32_t* label_out, FrameRun& fr) {
   const size_t npx = (size_t)rows * cols;
-  int max_n = 1;
-  for (const RndJob& j : jobs) max_n = std::max(max_n, j.n);
   RndJob* d_jobs;
   unsigned long long* zbuf;
   float* img; /* depth then label, one read-back */
@@ -167,22 +157,16 @@ ppf_status ppf_verify_frame_rendered(const ppf_frame_detection* dets, int n_dets
   ppf_verify_stats local;
   ppf_verify_stats& st = stats ? *stats : local;
   std::memset(&st, 0, sizeof(st));
-  const bool can_clear = n_dets > 0 && n_dets <= FRAME_MATCH_MAX_DETS && top >= 1 && top <= FRAME_MATCH_MAX_TOP;
-  if (can_clear && scores) std::memset(scores, 0, (size_t)n_dets * top * sizeof(ppf_pose_score));
-  if (can_clear && best)
-    for (int i = 0; i < n_dets; i++) best[i] = -1;
+  table_clear_scores(n_dets, top, scores, best);
   ppf_status s = verify_check(dets, n_dets, poses, n_poses, top, depth, depth_rows, depth_cols, intr, params, scores, best, who);
   if (s != PPF_OK) return s;
   if (params->flags & PPF_VERIFY_ALL_ROWS)
     return fail(PPF_ERR_INVALID, "%s: PPF_VERIFY_ALL_ROWS has no meaning against one view's z-buffer", who);
-  if ((s = render_image_check(depth_rows, depth_cols, intr, who)) != PPF_OK || (s = render_params_check(rparams, who)) != PPF_OK) return s;
+  if ((s = image_check(depth_rows, depth_cols, intr, true, who)) != PPF_OK || (s = render_params_check(rparams, who)) != PPF_OK) return s;
   st.n_dets = n_dets;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
-  int n_jobs = 0;
-  for (int i = 0; i < n_dets; i++) {
-    if (n_poses[i] > 0 && dets[i].model_cloud->n <= 0) return fail(PPF_ERR_INVALID, "%s: detection %d has an empty model cloud", who, i);
-    n_jobs += n_poses[i];
-  }
+  int n_jobs;
+  if ((s = table_check_models(dets, n_dets, n_poses, TABLE_N_POSES, who, &n_jobs)) != PPF_OK) return s;
   if (n_jobs > 0) {
     std::vector<ppf_pose_score> dev;
     {
@@ -192,12 +176,7 @@ ppf_status ppf_verify_frame_rendered(const ppf_frame_detection* dets, int n_dets
       st.n_host_syncs = fr.syncs;
       if (s != PPF_OK) return s;
     }
-    size_t j = 0;
-    for (int i = 0; i < n_dets; i++)
-      for (int k = 0; k < n_poses[i]; k++) {
-        scores[(size_t)i * top + k] = dev[j++];
-        if (best[i] < 0 || scores[(size_t)i * top + k].score > scores[(size_t)i * top + best[i]].score) best[i] = k;
-      }
+    table_scatter_scores(dev, n_dets, n_poses, top, scores, best);
     st.n_jobs = n_jobs;
   }
   st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -213,15 +192,11 @@ ppf_status ppf_render_frame(const ppf_frame_detection* dets, int n_dets, const p
   ppf_render_stats& st = stats ? *stats : local;
   std::memset(&st, 0, sizeof(st));
   /* on any error the given images are empty: clear what the size arguments let us reach */
-  if (rows > 0 && cols > 0 && (long long)rows * cols <= 0x7fffffffLL) {
-    const size_t npx = (size_t)rows * cols;
-    if (depth_out) std::memset(depth_out, 0, npx * sizeof(float));
-    if (label_out) std::fill(label_out, label_out + npx, -1);
-  }
-  if (n_dets < 0 || n_dets > FRAME_MATCH_MAX_DETS) return fail(PPF_ERR_INVALID, "%s: n_dets must be in [0, %d]", who, FRAME_MATCH_MAX_DETS);
-  if (top < 1 || top > FRAME_MATCH_MAX_TOP) return fail(PPF_ERR_INVALID, "%s: top must be in [1, %d]", who, FRAME_MATCH_MAX_TOP);
+  table_clear_images(rows, cols, depth_out, label_out);
   ppf_status s;
-  if ((s = render_image_check(rows, cols, intr, who)) != PPF_OK || (s = render_params_check(rparams, who)) != PPF_OK) return s;
+  if ((s = table_check_sizes(n_dets, top, who)) != PPF_OK || (s = image_check(rows, cols, intr, true, who)) != PPF_OK ||
+      (s = render_params_check(rparams, who)) != PPF_OK)
+    return s;
   if (n_dets > 0 && (!dets || !poses || !which)) return fail(PPF_ERR_INVALID, "%s: dets, poses and which must not be NULL", who);
   for (int i = 0; i < n_dets; i++) {
     if (which[i] < -1 || which[i] >= top) return fail(PPF_ERR_INVALID, "%s: which[%d] = %d is outside [-1, top)", who, i, which[i]);
@@ -229,29 +204,20 @@ ppf_status ppf_render_frame(const ppf_frame_detection* dets, int n_dets, const p
   }
   st.n_dets = n_dets;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
-  std::vector<RndJob> jobs;
-  for (int i = 0; i < n_dets; i++) {
-    if (which[i] < 0) continue;
-    if (dets[i].model_cloud->n <= 0) return fail(PPF_ERR_INVALID, "%s: detection %d has an empty model cloud", who, i);
-    RndJob j;
-    std::memcpy(j.T, poses[(size_t)i * top + which[i]].pose, sizeof(j.T));
-    j.model = dets[i].model_cloud->rows.p;
-    j.n = dets[i].model_cloud->n;
-    j.label = i;
-    jobs.push_back(j);
-  }
-  if (!jobs.empty()) {
+  int n_jobs;
+  if ((s = table_check_models(dets, n_dets, which, TABLE_WHICH, who, &n_jobs)) != PPF_OK) return s;
+  if (n_jobs > 0) {
+    std::vector<RndJob> jobs;
+    const int max_n = table_render_jobs(dets, n_dets, poses, which, TABLE_WHICH, top, LABEL_DET, jobs);
     FrameRun fr;
-    s = render_frame_run(jobs, rows, cols, intr, rparams, depth_out, label_out, fr);
+    s = render_frame_run(jobs, max_n, rows, cols, intr, rparams, depth_out, label_out, fr);
     st.n_launches = fr.launches;
     st.n_host_syncs = fr.syncs;
     if (s != PPF_OK) {
-      const size_t npx = (size_t)rows * cols;
-      if (depth_out) std::memset(depth_out, 0, npx * sizeof(float));
-      if (label_out) std::fill(label_out, label_out + npx, -1);
+      table_clear_images(rows, cols, depth_out, label_out);
       return s;
     }
-    st.n_jobs = (int)jobs.size();
+    st.n_jobs = n_jobs;
   }
   st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return PPF_OK;

@@ -2,7 +2,7 @@
  * ppf_verify_host.h — host side of ppf_verify_frame: score every refined pose of every detection of a frame against its
  * object cloud and, optionally, the depth image (what the reference leaves as `// TODO: Pose Validation`,
  * CloudProcessing.h:477-479, :530-532).  Kernels: ppf_verify_kernels.h.  Included by ppf_hip.hip after ppf_frame_host.h
- * (FrameRun, FRAME_LAUNCH, frame_scan) and ppf_match_frame_host.h (the limits of ppf_match_frame).
+ * (FrameRun, FRAME_LAUNCH, frame_scan) and ppf_posetable_host.h (the checks, clears and score scatter of a pose table).
  *
  * Per call with at least one pose: three uploads (the detection and job tables, the depth image when given), then
  * k_vfy_grid_count, a five-launch scan, k_vfy_grid_scatter, k_vfy_score, k_vfy_finish -- nine launches whatever the number
@@ -11,34 +11,20 @@
  */
 namespace {
 
+/* the arguments of both verify entries, in the order their errors win */
 ppf_status verify_check(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top, const float* depth,
                         int depth_rows, int depth_cols, const double* intr, const ppf_verify_params* p, ppf_pose_score* scores, int* best,
-                        const char* who = "ppf_verify_frame") {
-  if (n_dets < 0 || n_dets > FRAME_MATCH_MAX_DETS) return fail(PPF_ERR_INVALID, "%s: n_dets must be in [0, %d]", who, FRAME_MATCH_MAX_DETS);
-  if (top < 1 || top > FRAME_MATCH_MAX_TOP) return fail(PPF_ERR_INVALID, "%s: top must be in [1, %d]", who, FRAME_MATCH_MAX_TOP);
+                        const char* who) {
+  ppf_status s = table_check_sizes(n_dets, top, who);
+  if (s != PPF_OK) return s;
   if (!p) return fail(PPF_ERR_INVALID, "%s: params is NULL", who);
-  if (n_dets > 0 && (!dets || !poses || !n_poses || !scores || !best))
-    return fail(PPF_ERR_INVALID, "%s: dets, poses, n_poses, scores and best must not be NULL", who);
-  for (int i = 0; i < n_dets; i++) {
-    if (n_poses[i] < 0 || n_poses[i] > top) return fail(PPF_ERR_INVALID, "%s: n_poses[%d] = %d is outside [0, top]", who, i, n_poses[i]);
-    if (n_poses[i] > 0 && (!dets[i].model_cloud || !dets[i].scene))
-      return fail(PPF_ERR_INVALID, "%s: detection %d has poses but no model cloud or scene", who, i);
-  }
+  if ((s = table_check_rows(dets, n_dets, poses, n_poses, top, scores && best, "scores and best", true, who)) != PPF_OK) return s;
   if (!(std::isfinite(p->inlier_dist) && p->inlier_dist > 0.f)) return fail(PPF_ERR_INVALID, "%s: inlier_dist must be finite and > 0", who);
   if (!(p->normal_cos >= -1.f && p->normal_cos <= 1.f)) return fail(PPF_ERR_INVALID, "%s: normal_cos must be in [-1, 1]", who);
   if (!(std::isfinite(p->depth_tol) && p->depth_tol > 0.f)) return fail(PPF_ERR_INVALID, "%s: depth_tol must be finite and > 0", who);
   if (p->model_step < 1) return fail(PPF_ERR_INVALID, "%s: model_step must be >= 1", who);
   if (p->flags & ~(PPF_VERIFY_ALL_ROWS | PPF_VERIFY_NORMALS)) return fail(PPF_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)p->flags);
-  if (depth) {
-    if (depth_rows <= 0 || depth_cols <= 0) return fail(PPF_ERR_INVALID, "%s: the depth image is %d x %d", who, depth_rows, depth_cols);
-    if ((long long)depth_rows * depth_cols > 0x7fffffffLL)
-      return fail(PPF_ERR_INVALID, "%s: %d x %d pixels exceed INT32_MAX", who, depth_rows, depth_cols);
-    if (!intr) return fail(PPF_ERR_INVALID, "%s: a depth image needs intr", who);
-    if (!std::isfinite(intr[0]) || !std::isfinite(intr[1]) || intr[0] == 0.0 || intr[1] == 0.0)
-      return fail(PPF_ERR_INVALID, "%s: fx and fy must be finite and non-zero", who);
-    if (!std::isfinite(intr[2]) || !std::isfinite(intr[3])) return fail(PPF_ERR_INVALID, "%s: ppx and ppy must be finite", who);
-  }
-  return PPF_OK;
+  return depth ? image_check(depth_rows, depth_cols, intr, false, who) : PPF_OK;
 }
 
 /* what the scoring needs on the device: the detection and job tables and every live detection's grid */
@@ -146,8 +132,7 @@ ppf_status verify_run(const ppf_frame_detection* dets, int n_dets, const ppf_pos
   ppf_pose_score* d_out;
   float* d_depth = nullptr;
   if ((s = fr.get((size_t)t.nj * t.max_nb, &part)) != PPF_OK || (s = fr.get(t.nj, &d_out)) != PPF_OK) return s;
-  if (depth && (s = fr.get((size_t)depth_rows * depth_cols, &d_depth)) != PPF_OK) return s;
-  if (depth) HIPCHK(hipMemcpy(d_depth, depth, (size_t)depth_rows * depth_cols * sizeof(float), hipMemcpyHostToDevice));
+  if (depth && (s = frame_upload_depth(fr, depth, depth_rows, depth_cols, &d_depth)) != PPF_OK) return s;
   const VfyArgs a = verify_args(t, d_depth, depth_rows, depth_cols, intr, p);
   FRAME_LAUNCH(fr, k_vfy_score, dim3((unsigned)t.max_nb, (unsigned)t.nj), dim3(VFY_BLOCK), a, part);
   FRAME_LAUNCH(fr, k_vfy_finish, dim3((unsigned)t.nj), dim3(64), t.d_jobs, part, t.max_nb, depth ? 1 : 0, d_out);
@@ -179,20 +164,14 @@ ppf_status ppf_verify_frame(const ppf_frame_detection* dets, int n_dets, const p
   ppf_verify_stats& st = stats ? *stats : local;
   std::memset(&st, 0, sizeof(st));
   /* on any error every score row is zero and every best[i] is -1: clear what the valid part of the arguments lets us reach */
-  const bool can_clear = n_dets > 0 && n_dets <= FRAME_MATCH_MAX_DETS && top >= 1 && top <= FRAME_MATCH_MAX_TOP;
-  if (can_clear && scores) std::memset(scores, 0, (size_t)n_dets * top * sizeof(ppf_pose_score));
-  if (can_clear && best)
-    for (int i = 0; i < n_dets; i++) best[i] = -1;
-  ppf_status s = verify_check(dets, n_dets, poses, n_poses, top, depth, depth_rows, depth_cols, intr, params, scores, best);
+  table_clear_scores(n_dets, top, scores, best);
+  ppf_status s = verify_check(dets, n_dets, poses, n_poses, top, depth, depth_rows, depth_cols, intr, params, scores, best, who);
   if (s != PPF_OK) return s;
   st.n_dets = n_dets;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
-  std::vector<int> job_det;
-  for (int i = 0; i < n_dets; i++) {
-    if (n_poses[i] > 0 && dets[i].model_cloud->n <= 0) return fail(PPF_ERR_INVALID, "%s: detection %d has an empty model cloud", who, i);
-    for (int k = 0; k < n_poses[i]; k++) job_det.push_back(i);
-  }
-  if (!job_det.empty()) {
+  int n_jobs;
+  if ((s = table_check_models(dets, n_dets, n_poses, TABLE_N_POSES, who, &n_jobs)) != PPF_OK) return s;
+  if (n_jobs > 0) {
     std::vector<ppf_pose_score> dev;
     {
       FrameRun fr; /* the scratch goes back to the block cache after the read-back */
@@ -201,13 +180,8 @@ ppf_status ppf_verify_frame(const ppf_frame_detection* dets, int n_dets, const p
       st.n_host_syncs = fr.syncs;
       if (s != PPF_OK) return s;
     }
-    size_t j = 0;
-    for (int i = 0; i < n_dets; i++)
-      for (int k = 0; k < n_poses[i]; k++) {
-        scores[(size_t)i * top + k] = dev[j++];
-        if (best[i] < 0 || scores[(size_t)i * top + k].score > scores[(size_t)i * top + best[i]].score) best[i] = k;
-      }
-    st.n_jobs = (int)job_det.size();
+    table_scatter_scores(dev, n_dets, n_poses, top, scores, best);
+    st.n_jobs = n_jobs;
   }
   st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return PPF_OK;
