@@ -15,6 +15,7 @@
  *                                                     Cloud::verifyFrameRendered(...)  (the same with self-occlusion)
  *   transformPCPose -> writePLY of the result       ->  Cloud::renderFrame(modelClouds, poses, best, ...)  (depth, label images)
  *   `return *resultsSub[0];` per box (:480, :533)   ->  Cloud::selectFrame(modelClouds, poses, depth, ...)  (one consistent set per frame)
+ *   (nothing: the reference stops at the ICP pose)  ->  Cloud::refineFrame(modelClouds, poses, depth, ...)  (poses fitted to the depth image)
  *
  * Every stage returns a new Cloud that stays in HBM; only toMat()/download() copy to the host.  A maintainer replaces
  * the bodies of those CloudProcessor methods by these one-liners; pcl::PointCloud<PointXYZ> goes
@@ -272,6 +273,34 @@ class Cloud {
     std::vector<std::pair<int, int> > out;
     for (int r = 0; r < nSel; r++) out.push_back(std::make_pair(sel[(size_t)r] / (int)top, sel[(size_t)r] % (int)top));
     return out;
+  }
+  /* Every pose of every detection refined on the depth image itself by projective point-to-plane steps (ppf_refine_frame,
+   * DESIGN.md §17): to polish what selectFrame kept at full depth resolution, or to carry the poses of the last frame into
+   * this frame's image without matching again.  Returns per detection its refined poses (a pose whose refinement was
+   * stopped by a guard comes back as given); info, when given, gets one row per pose.  depth is required.
+   * params == 0: ppf_default_refine_params.  A detection without a model cloud is not refined: its poses come back as given. */
+  static std::vector<std::vector<ppf_match_3d::Pose3D> > refineFrame(const std::vector<const Cloud*>& modelClouds,
+                                                                     const std::vector<std::vector<ppf_match_3d::Pose3D> >& poses,
+                                                                     const float* depth, int rows, int cols, double fx, double fy,
+                                                                     double ppx, double ppy, const ppf_refine_params* params = 0,
+                                                                     std::vector<std::vector<ppf_refine_info> >* info = 0,
+                                                                     ppf_refine_stats* stats = 0) {
+    const size_t nd = poses.size();
+    if (modelClouds.size() != nd) throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::refineFrame: one model cloud per detection");
+    const PoseTable t(modelClouds, 0, poses);
+    const ppf_refine_params p = orDefaults(params, ppf_default_refine_params);
+    const double intr[4] = {fx, fy, ppx, ppy};
+    std::vector<ppf_pose> out(nd * t.top + 1);
+    std::vector<ppf_refine_info> rowsOut(nd * t.top + 1);
+    ppf_match_3d::check(ppf_refine_frame(&t.d[0], (int)nd, &t.recs[0], &t.n[0], (int)t.top, depth, rows, cols, intr, &p, &out[0], &rowsOut[0],
+                                         stats));
+    if (info) *info = t.perDetection(rowsOut);
+    std::vector<std::vector<ppf_match_3d::Pose3D> > refined(nd);
+    for (size_t i = 0; i < nd; i++) {
+      if (t.n[i] == 0) refined[i] = poses[i]; /* not refined: as given */
+      for (int k = 0; k < t.n[i]; k++) refined[i].push_back(ppf_match_3d::Pose3D(out[i * t.top + (size_t)k]));
+    }
+    return refined;
   }
   /* the N x 6 CV_32FC1-shaped Mat of PointCloudXYZNormalToMat (normals re-normalised) */
   ppf_match_3d::Mat toMat() const {

@@ -656,6 +656,64 @@ ppf_status ppf_select_frame(const ppf_frame_detection* dets, int n_dets, const p
                             const ppf_render_params* rparams, const ppf_select_params* params, ppf_select_info* info, int* selected,
                             int* n_selected, float* depth_out, int32_t* label_out, ppf_select_stats* stats);
 
+/* ---- projective point-to-plane refinement of the poses of a frame on the depth image itself ------------------------- */
+#define PPF_REFINE_NONE 0       /* row with k >= n_poses[i] */
+#define PPF_REFINE_CONVERGED 1  /* the last step was below eps_rot and eps_trans */
+#define PPF_REFINE_MAX_ITERS 2
+#define PPF_REFINE_LOST 3       /* too few pairs at an evaluation: the pose of that evaluation is returned */
+#define PPF_REFINE_STEP 4       /* a step over the limits or not finite was refused: likewise */
+
+typedef struct ppf_refine_params {
+  float depth_gate;      /* metres, finite, > 0: a pair needs |d - z| <= depth_gate */
+  float max_step_rot;    /* rad, finite, > 0 */
+  float max_step_trans;  /* metres, finite, > 0 */
+  float eps_rot, eps_trans; /* finite, >= 0 */
+  float min_pair_share;  /* in [0, 1]: pairs needed as a share of the considered rows */
+  int32_t min_pairs;     /* >= 6 */
+  int32_t max_iters;     /* 0..100; 0 evaluates nothing and returns the poses as given, status MAX_ITERS */
+  int32_t model_step;    /* >= 1, as ppf_verify_params */
+  int32_t flags;         /* 0; reserved */
+  int32_t reserved[4];
+} ppf_refine_params;
+
+typedef struct ppf_refine_info {
+  int32_t status, iterations;        /* PPF_REFINE_*; steps applied */
+  int32_t n_rows, n_considered;      /* model rows scored; finite rows facing the camera at the last evaluation */
+  int32_t n_pairs_first, n_pairs_last;
+  float rmse_first, rmse_last;       /* point-to-plane rms of the first / last evaluation, metres */
+  int32_t reserved[4];
+} ppf_refine_info;
+
+typedef struct ppf_refine_stats {
+  int32_t n_dets, n_jobs; /* detections given, poses refined */
+  int32_t n_launches;     /* kernel launches of the call */
+  int32_t n_host_syncs;   /* blocking read-backs of the call (host-to-device uploads not counted) */
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_refine_stats;
+
+/* depth_gate 0.02, max_step_rot 0.35, max_step_trans 0.03, eps_rot 1e-5, eps_trans 1e-5, min_pair_share 0.25, min_pairs 16,
+ * max_iters 20, model_step 1, flags 0 */
+void ppf_default_refine_params(ppf_refine_params* p);
+/* Refines pose k < n_poses[i] of detection i against the depth image alone (DESIGN.md §17 states every step bit for bit):
+ * per iteration the rows 0, s, 2s, ... of dets[i].model_cloud are moved by the pose, a finite row that faces the camera is
+ * paired with the depth pixel under it when that pixel is finite, > 0 and within depth_gate of the row's z, and one damped
+ * point-to-plane step (the model's own moved normal; rotation about the moved centre of the model) is solved and applied,
+ * until a step is below eps_rot and eps_trans (CONVERGED) or max_iters steps were applied (MAX_ITERS).  An evaluation with
+ * fewer than min_pairs pairs or fewer than min_pair_share of the considered rows ends the pose LOST; a step that is not
+ * finite or exceeds max_step_rot / max_step_trans ends it STEP; either way the pose of that evaluation is returned.
+ * dets, poses, n_poses and top are what ppf_verify_frame takes (only model_cloud is read).  depth: required HOST image,
+ * float32 metres, packed depth_rows x depth_cols; intr = {fx, fy, ppx, ppy}, fx and fy finite and non-zero.
+ * out is [n_dets][top] and may be `poses` itself: a pose with iterations > 0 gets the refined matrix and q, t and angle
+ * from it; alpha, model_index and num_votes are copied; residual is rmse_last; with iterations == 0 the rest of the record
+ * is the one given (max_iters == 0 leaves the residual too); rows with k >= n_poses[i] are copied.  info ([n_dets][top]) and
+ * stats may be NULL.  Limits: n_dets 0..256, top 1..16, n_poses[i] 0..top.  Argument errors are PPF_ERR_INVALID before any
+ * device work; on any error out is a copy of poses and every info row is zero.  A pose's result depends neither on the
+ * other poses of the call nor on scheduling; one launch and one read-back whatever n_dets is. */
+ppf_status ppf_refine_frame(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top,
+                            const float* depth, int depth_rows, int depth_cols, const double* intr,
+                            const ppf_refine_params* params, ppf_pose* out, ppf_refine_info* info, ppf_refine_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,27 @@ class SelectStats(C.Structure):
 PPF_SELECT_NONE, PPF_SELECT_SELECTED, PPF_SELECT_GATED, PPF_SELECT_SUPPRESSED = 0, 1, 2, 3  # SelectInfo.status
 
 
+class RefineParams(C.Structure):
+    _fields_ = [("depth_gate", C.c_float), ("max_step_rot", C.c_float), ("max_step_trans", C.c_float), ("eps_rot", C.c_float),
+                ("eps_trans", C.c_float), ("min_pair_share", C.c_float), ("min_pairs", C.c_int32), ("max_iters", C.c_int32),
+                ("model_step", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class RefineInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("n_rows", C.c_int32), ("n_considered", C.c_int32),
+                ("n_pairs_first", C.c_int32), ("n_pairs_last", C.c_int32), ("rmse_first", C.c_float), ("rmse_last", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
+class RefineStats(C.Structure):
+    _fields_ = [("n_dets", C.c_int32), ("n_jobs", C.c_int32), ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32),
+                ("ms_wall", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+# RefineInfo.status
+PPF_REFINE_NONE, PPF_REFINE_CONVERGED, PPF_REFINE_MAX_ITERS, PPF_REFINE_LOST, PPF_REFINE_STEP = 0, 1, 2, 3, 4
+
+
 # every symbol include/ppf_hip.h declares (tests/test_capi_symbols.py checks the header against this)
 _SIGNATURES = {
     "ppf_default_train_params": (None, [C.POINTER(TrainParams)]),
@@ -275,6 +296,10 @@ _SIGNATURES = {
                                    C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(RenderParams), C.POINTER(SelectParams),
                                    C.POINTER(SelectInfo), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
                                    C.POINTER(SelectStats)]),
+    "ppf_default_refine_params": (None, [C.POINTER(RefineParams)]),
+    "ppf_refine_frame": (C.c_int, [C.POINTER(FrameDetection), C.c_int, C.POINTER(Pose), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int,
+                                   C.c_int, C.POINTER(C.c_double), C.POINTER(RefineParams), C.POINTER(Pose), C.POINTER(RefineInfo),
+                                   C.POINTER(RefineStats)]),
     "ppf_icp_register": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }

@@ -13,8 +13,9 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _capi
-from ._capi import (FrameDetection, FrameParams, FrameStats, IcpParams, MatchFrameStats, Pose, PoseScore, PPFError, RenderParams,
-                    RenderStats, SelectInfo, SelectParams, SelectStats, VerifyParams, VerifyStats, check, lib)
+from ._capi import (FrameDetection, FrameParams, FrameStats, IcpParams, MatchFrameStats, Pose, PoseScore, PPFError, RefineInfo,
+                    RefineParams, RefineStats, RenderParams, RenderStats, SelectInfo, SelectParams, SelectStats, VerifyParams, VerifyStats,
+                    check, lib)
 from .detector import ICP, PPF3DDetector, Pose3D
 
 
@@ -340,6 +341,29 @@ def select_frame(dets, poses, depth, intr, params=None, render_params=None, scor
     return tuple(out)
 
 
+def refine_frame(dets, poses, depth, intr, params=None, top: Optional[int] = None, return_stats: bool = False):
+    """One ppf_refine_frame call: every pose of every detection refined on the depth image itself by projective
+    point-to-plane steps -- to polish the poses select_frame kept at full depth resolution, or to carry the
+    poses of the last frame into this frame's depth image without matching again.  dets: per detection a model cloud
+    (DeviceCloud), a (model cloud, anything) pair, or None; poses: per detection its poses as verify_frame takes them;
+    depth: the 2-D float32 image in metres (required); intr: (fx, fy, ppx, ppy) or the 3x3 camera matrix.  params: a
+    RefineParams, a dict of its fields (the rest default) or None.  Returns (refined, info): per detection the list of its
+    refined poses (Pose3D) and the RefineInfo rows as a numpy structured array of shape (n_dets, top); with
+    ``return_stats`` also the call's counters."""
+    pairs = [None if d is None else (d[0] if isinstance(d, tuple) else d, None) for d in dets]
+    n, top, arr, recs, n_poses = _frame_tables(pairs, poses, top)
+    prm = _params(RefineParams, "ppf_default_refine_params", params)
+    img, rows, cols = _depth_image(depth, "refine_frame needs a 2-D float32 depth image")
+    it = (C.c_double * 4)(*_intr4(intr)) if intr is not None else None
+    out = (Pose * (max(n, 1) * top))()
+    info = (RefineInfo * (max(n, 1) * top))()
+    st = RefineStats()
+    check(lib().ppf_refine_frame(arr, n, recs, n_poses, top, img.ctypes.data, rows, cols, it, C.byref(prm), out, info, C.byref(st)))
+    refined = [[Pose3D(out[i * top + k]) for k in range(n_poses[i])] for i in range(n)]
+    rows_info = np.ctypeslib.as_array(info).copy()[:n * top].reshape(n, top)
+    return (refined, rows_info, _capi.stats_dict(st)) if return_stats else (refined, rows_info)
+
+
 class CloudProcessor:
     """``ppf::CloudProcessor``: holds the scene cloud, the depth image, the detector's boxes, the per-object clouds
     and the PPF detectors; every method is the reference's, in the order its driver calls them
@@ -382,6 +406,9 @@ class CloudProcessor:
         self.select_info: Optional[np.ndarray] = None
         self.selected: List[tuple] = []
         self.select_stats: Dict[str, object] = {}
+        # RefineFrame: the info rows (n_dets, top) and the counters
+        self.refine_info: Optional[np.ndarray] = None
+        self.refine_stats: Dict[str, object] = {}
         self._last_refined: List[Pose3D] = []
 
     # ---- the PCL half -------------------------------------------------------------------------------------
@@ -548,6 +575,33 @@ class CloudProcessor:
         self.selected = [(int(j) // top, int(j) % top) for j in got[1]]
         out = [(i, k, self.frame_poses[i][k]) for i, k in self.selected]
         return (out, got[2], got[3]) if return_images else out
+
+    def RefineFrame(self, depth=None, selected_only: bool = False, **params) -> List[List[Pose3D]]:
+        """The poses held after MatchFrame (``frame_poses``) refined on the depth image itself (one ppf_refine_frame call,
+        DESIGN.md §17) and put back into ``frame_poses``, so PoseValidation, SelectFrame and RenderFrame go on with them.
+        ``depth``: another frame's image of the same camera (tracking: the poses of the last frame against this frame's
+        depth; it becomes ``self.depth``), default ``self.depth`` (polish).  ``selected_only`` refines only the poses the last
+        SelectFrame selected and leaves the others as they are.  ``params``: fields of RefineParams.  Sets ``refine_info``,
+        ``refine_stats`` and ``timings["refine_frame"]``; returns ``frame_poses``."""
+        if depth is not None:
+            self.depth = np.ascontiguousarray(depth, dtype=np.float32)
+        if self.depth is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "RefineFrame needs the depth image")
+        keep = set(self.selected) if selected_only else None
+        dets, poses, slots = [], [], []
+        for i, (name, plist) in enumerate(zip(self.frame_labels, self.frame_poses)):
+            ks = [k for k in range(len(plist)) if keep is None or (i, k) in keep] if name is not None else []
+            dets.append(self._model_clouds[self.label_to_id[name]] if ks else None)
+            poses.append([plist[k] for k in ks])
+            slots.append(ks)
+        t0 = time.perf_counter()
+        refined, self.refine_info, self.refine_stats = refine_frame(dets, poses, self.depth, self.frame_intr, params or None,
+                                                                    return_stats=True)
+        self.timings["refine_frame"] = time.perf_counter() - t0
+        for i, ks in enumerate(slots):
+            for k, p in zip(ks, refined[i]):
+                self.frame_poses[i][k] = p
+        return self.frame_poses
 
     def _match_frame(self, labels, step, dist, top: int = 5) -> List[Optional[Pose3D]]:
         dets = (FrameDetection * max(len(labels), 1))()

@@ -369,16 +369,21 @@ ppf_status icp_check(const char* who, const void* src, int n, int sstride, int s
   return PPF_OK;
 }
 
+/* a pose record's matrix replaced by M: q / t / angle from the new matrix */
+void icp_set_pose(ppf_pose* p, const double* M, double residual) {
+  memcpy(p->pose, M, 16 * sizeof(double));
+  const double R[9] = {M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10]};
+  p->t[0] = M[3]; p->t[1] = M[7]; p->t[2] = M[11];
+  ppf_dcm_to_quat(R, p->q);
+  p->angle = ppf_angle_from_trace(R[0] + R[4] + R[8]);
+  p->residual = residual;
+}
+
 /* Pose3D::appendPose: pose = incremental * pose, then q / t / angle from the new matrix */
 void icp_append_pose(ppf_pose* p, const double* inc, double residual) {
   double out[16];
   ppf_mat44_mul(inc, p->pose, out);
-  memcpy(p->pose, out, sizeof(out));
-  const double R[9] = {out[0], out[1], out[2], out[4], out[5], out[6], out[8], out[9], out[10]};
-  p->t[0] = out[3]; p->t[1] = out[7]; p->t[2] = out[11];
-  ppf_dcm_to_quat(R, p->q);
-  p->angle = ppf_angle_from_trace(R[0] + R[4] + R[8]);
-  p->residual = residual;
+  icp_set_pose(p, out, residual);
 }
 
 ppf_status icp_refine_device(const float* d_model, int n, int mstride, int mnoff, const float* d_scene, int nd, int sstride, int snoff,

@@ -327,21 +327,91 @@ __global__ __launch_bounds__(256) void k_icp2_reset(IcpBatch B) {
   for (int b = blockIdx.y * 256 + tid; b < nd_all; b += gridDim.y * 256) owner[b] = ICP_NONE;
 }
 
-/* sums of chunk partials (3 per chunk) in chunk order: thread c < 3 of the block returns the sum of component c.  The partials
- * go through LDS a tile at a time, loaded by the whole block (one thread reading them from memory one after the other is a
- * chain of a thousand load latencies).  Called by every thread of the block. */
+/* sums of chunk partials (NC per chunk, 3 unless said otherwise) in chunk order: thread c < NC of the block returns the sum of
+ * component c.  The partials go through LDS a tile of TILE chunks at a time (lds: TILE * NC doubles), loaded by the whole
+ * block (one thread reading them from memory one after the other is a chain of a thousand load latencies).  Called by every
+ * thread of the block. */
 constexpr int ICP_SUM_TILE = 1024; /* chunks per tile */
+template <int NC = 3, int TILE = ICP_SUM_TILE>
 __device__ __forceinline__ double icp_sum_staged(const double* __restrict__ parts, int chunks, double* lds, int tid, int nthreads) {
   double acc = 0;
-  for (int c0 = 0; c0 < chunks; c0 += ICP_SUM_TILE) {
-    const int cn = min(ICP_SUM_TILE, chunks - c0);
+  for (int c0 = 0; c0 < chunks; c0 += TILE) {
+    const int cn = min(TILE, chunks - c0);
     __syncthreads();
-    for (int k = tid; k < cn * 3; k += nthreads) lds[k] = parts[(size_t)c0 * 3 + k];
+    for (int k = tid; k < cn * NC; k += nthreads) lds[k] = parts[(size_t)c0 * NC + k];
     __syncthreads();
-    if (tid < 3)
-      for (int c = 0; c < cn; c++) acc += lds[c * 3 + tid];
+    if (tid < NC)
+      for (int c = 0; c < cn; c++) acc += lds[c * NC + tid];
   }
   return acc;
+}
+
+/* The damped 6x6 normal equations of a point-to-plane step, solved by one wave: tot = the 21 sums of the upper triangle of
+ * J^T J (row by row), then the 6 of J^T r.  A + 1e-10 * trace * I, Gaussian elimination with partial pivoting (the first
+ * largest pivot), one COLUMN per lane (lanes 0..5: the matrix, lane 6: the right-hand side): the row operations are the
+ * sequential solve's, element for element; the back substitution runs on lane 0, which gets x.  False (in every lane) when
+ * the trace is not positive or a pivot is below 1e-300.  Called by all 64 lanes of the wave. */
+__device__ __forceinline__ bool icp_solve6_wave(const double* tot, int lane, double* x) {
+  double col[6];
+  {
+    int e = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+      for (int j = i; j < 6; j++) { if (lane == j) col[i] = tot[e]; if (lane == i) col[j] = tot[e]; e++; }
+#pragma unroll
+    for (int i = 0; i < 6; i++) if (lane == 6) col[i] = tot[21 + i];
+    if (lane > 6) { for (int i = 0; i < 6; i++) col[i] = 0; }
+  }
+  auto bcast = [&](double v, int src) {
+    const int lo = __shfl(__double2loint(v), src), hi = __shfl(__double2hiint(v), src);
+    return __hiloint2double(hi, lo);
+  };
+  double trace = 0;
+#pragma unroll
+  for (int i = 0; i < 6; i++) trace += bcast(col[i], i); /* M[i][i] in order */
+  bool ok = trace > 0.0;
+  if (ok) {
+    const double lambda = 1e-10 * trace;
+#pragma unroll
+    for (int i = 0; i < 6; i++) if (lane == i) col[i] += lambda;
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+      /* pivot: the first largest |M[r][c]|, r >= c (lane c holds column c) */
+      int piv = c;
+      double pv = ppf_fabs(col[c]);
+#pragma unroll
+      for (int r = c + 1; r < 6; r++) { const double av = ppf_fabs(col[r]); if (av > pv) { pv = av; piv = r; } }
+      piv = __shfl(piv, c);
+      pv = bcast(pv, c);
+      if (pv < 1e-300) { ok = false; break; }
+#pragma unroll
+      for (int r = c + 1; r < 6; r++) if (r == piv) { const double tmp = col[c]; col[c] = col[r]; col[r] = tmp; }
+      const double dcc = bcast(col[c], c);
+#pragma unroll
+      for (int r = c + 1; r < 6; r++) {
+        const double f = bcast(col[r], c) / dcc;
+        if (lane >= c && lane < 7) col[r] -= f * col[c];
+      }
+    }
+  }
+  double M[6][7];
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+#pragma unroll
+    for (int j = 0; j < 7; j++) M[i][j] = bcast(col[i], j);
+  if (lane == 0 && ok) {
+#pragma unroll
+    for (int c = 5; c >= 0; c--) {
+      double sacc = M[c][6];
+#pragma unroll
+      for (int k = c + 1; k < 6; k++) sacc -= M[c][k] * M[k][6];
+      M[c][6] = sacc / M[c][c];
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) x[i] = M[i][6];
+  }
+  return ok;
 }
 
 /* prologue 2: mean_avg = 0.5 * (mean(src0) + mean(dst0)) */
@@ -1259,67 +1329,13 @@ __global__ __launch_bounds__(1024) void k_icp2_tail(IcpBatch B, IcpLive live, in
   if (wave != 0) return;
   int done = s_done;
   if (!done) {
-    /* the damped 6x6 system, one COLUMN per lane (lanes 0..5: the matrix, lane 6: the right-hand side): the row operations
-     * of the elimination are the sequential solve's, element for element; the back substitution runs on lane 0 */
-    double col[6];
-    {
-      int e = 0;
-#pragma unroll
-      for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = i; j < 6; j++) { if (lane == j) col[i] = s_tot[e]; if (lane == i) col[j] = s_tot[e]; e++; }
-#pragma unroll
-      for (int i = 0; i < 6; i++) if (lane == 6) col[i] = s_tot[21 + i];
-      if (lane > 6) { for (int i = 0; i < 6; i++) col[i] = 0; }
-    }
+    /* the damped 6x6 system (icp_solve6_wave: one column per lane, the back substitution on lane 0) */
     const double fsum = s_tot[27];
-    auto bcast = [&](double v, int src) {
-      const int lo = __shfl(__double2loint(v), src), hi = __shfl(__double2hiint(v), src);
-      return __hiloint2double(hi, lo);
-    };
-    double trace = 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++) trace += bcast(col[i], i); /* M[i][i] in order */
-    bool ok = trace > 0.0;
-    if (ok) {
-      const double lambda = 1e-10 * trace;
-#pragma unroll
-      for (int i = 0; i < 6; i++) if (lane == i) col[i] += lambda;
-#pragma unroll
-      for (int c = 0; c < 6; c++) {
-        /* pivot: the first largest |M[r][c]|, r >= c (lane c holds column c) */
-        int piv = c;
-        double pv = ppf_fabs(col[c]);
-#pragma unroll
-        for (int r = c + 1; r < 6; r++) { const double av = ppf_fabs(col[r]); if (av > pv) { pv = av; piv = r; } }
-        piv = __shfl(piv, c);
-        pv = bcast(pv, c);
-        if (pv < 1e-300) { ok = false; break; }
-#pragma unroll
-        for (int r = c + 1; r < 6; r++) if (r == piv) { const double tmp = col[c]; col[c] = col[r]; col[r] = tmp; }
-        const double dcc = bcast(col[c], c);
-#pragma unroll
-        for (int r = c + 1; r < 6; r++) {
-          const double f = bcast(col[r], c) / dcc;
-          if (lane >= c && lane < 7) col[r] -= f * col[c];
-        }
-      }
-    }
-    double M[6][7];
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-      for (int j = 0; j < 7; j++) M[i][j] = bcast(col[i], j);
+    double x[6];
+    bool ok = icp_solve6_wave(s_tot, lane, x);
     if (lane == 0) {
       if (ok) {
-#pragma unroll
-        for (int c = 5; c >= 0; c--) {
-          double sacc = M[c][6];
-#pragma unroll
-          for (int k = c + 1; k < 6; k++) sacc -= M[c][k] * M[k][6];
-          M[c][6] = sacc / M[c][c];
-        }
-        const double rpy[3] = {M[0][6], M[1][6], M[2][6]}, t[3] = {M[3][6], M[4][6], M[5][6]};
+        const double rpy[3] = {x[0], x[1], x[2]}, t[3] = {x[3], x[4], x[5]};
         if (rpy[0] != rpy[0] || rpy[1] != rpy[1] || rpy[2] != rpy[2] || t[0] != t[0] || t[1] != t[1] || t[2] != t[2]) ok = false;
         if (ok) {
           double P[16];
