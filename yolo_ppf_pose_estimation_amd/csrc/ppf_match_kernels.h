@@ -42,8 +42,8 @@
  *                direct      every entry votes once per hit: 1 fma + cvt + fract + address + ds_add_u32
  *                            per vote, entries held in registers while the hits go by;
  *                aggregated  (m >= PPF_AGG_MIN_HITS) the hits of the run were histogrammed by cell (k_tables);
- *                            every entry adds COUNTS: 17 ds_add_u32 per entry and <= 191 hits instead of
- *                            one per hit (see below).
+ *                            every entry adds COUNTS: one ds_add_u32 per non-zero column of the run's table (at most
+ *                            17, see below) per entry and <= 191 hits instead of one per hit.
  *              Work items (run x chunk of entries x group of hits) are claimed by waves from an LDS
  *              counter.
  *
@@ -57,8 +57,11 @@
  * into Q = 64 cells: an entry in cell q = floor(64 phi) and a hit in cell p = floor(64 psi) with p != q
  * are ordered by their cells alone, so for one entry all hits of a run with p < q and the same Y land
  * in bin X - Y, those with p > q in bin X - Y - 1: a table T[q][j] (j = Y + 8 = 0..16, built per run
- * from the hits' cell histogram) holds the COUNT that bin X + 8 - j receives, and the entry casts 17
- * counted atomics whatever m is.  Hits in the entry's own cell (1/64 of them) are voted one by one
+ * from the hits' cell histogram) holds the COUNT that bin X + 8 - j receives, and the entry casts at most 17
+ * counted atomics whatever m is.  Column j is made of the hits with Y + 8 == j or j - 1 only, and the hits of one bucket seen
+ * from one reference point sit on arcs around its normal: most tables have Y values that never occur, so columns that are
+ * zero in every row.  k_tables writes a 17-bit column mask next to the rows and k_vote skips the masked columns on scalar
+ * branches (a skipped add was an add of 0; the headline case casts 12.3 of 17).  Hits in the entry's own cell (1/64 of them) are voted one by one
  * with the direct arithmetic.  Exactness: the table is only used for pairs separated by a cell boundary
  * from which the entry is provably away (fp32 cell index with a guard band, fp64 when inside the band,
  * one-by-one votes when fp64 is still within 1e-7 of a boundary), where the fp64 chain's rounding
@@ -81,7 +84,7 @@
  * out; the votes are then wrong and the 16-bit overflow check is off, only times and counters of such a build mean anything.  The difference to the
  * product build is what the class costs, with the latency it exposes included (profiles/r03_vote_classes.md). */
 #ifndef PPF_ABL_COUNTED
-#define PPF_ABL_COUNTED 1      /* count-table items: the 17 counted atomics per entry and the table-row reads behind them */
+#define PPF_ABL_COUNTED 1      /* count-table items: the counted atomics per entry (<= 17) and the table-row reads behind them */
 #endif
 #ifndef PPF_ABL_OWNCELL
 #define PPF_ABL_OWNCELL 1      /* count-table items: the one-by-one votes of an entry's own cell */
@@ -127,6 +130,12 @@ __device__ __forceinline__ void vote_one(const uint32_t p, const int k, const ui
 #define PPF_PHASE_DECL do { } while (0)
 #define PPF_PHASE(k) do { } while (0)
 #define PPF_PHASE_FLUSH(tally, lane) do { } while (0)
+#endif
+/* Diagnostic build (-DPPF_DIAG_COLUMNS, tools/column_counts.py): ppf_match_stats.phase_clocks[0] = the counted atomic
+ * lane-operations 17 columns per entry would be, [1] = those of the set columns, [2] = those of the tables with all 17 set
+ * (profiles/r14_sparse_tables.md).  The slots are the phase clocks': one build cannot have both. */
+#if defined(PPF_DIAG_COLUMNS) && defined(PPF_PHASE_CLOCKS)
+#error "PPF_DIAG_COLUMNS and PPF_PHASE_CLOCKS share ppf_match_stats.phase_clocks: build one or the other"
 #endif
 #ifndef PPF_COST_TABLE
 #define PPF_COST_TABLE 16   /* k_vote's launch order: what one count table costs a pair record, in direct hits */
@@ -214,6 +223,12 @@ constexpr int AGG_ROW = 20;                                        /* bytes per 
  * ranges as a table of their own behind the rows cost 272 bytes of LDS per wave and two more LDS reads per block, -1.7 %) */
 constexpr int AGG_ROW_CE = 17;
 constexpr int AGG_SCRATCH = ((AGG_Q + 1) * AGG_ROW + 15) / 16 * 16; /* per-wave LDS of k_vote: the rows */
+/* the table's column mask: one word in the padding behind the rows, so the two 16-byte pieces a lane of k_vote copies bring it
+ * along.  Bit j is set when some row's count j can be non-zero, i.e. when a hit of the table has Y + 8 == j or j - 1 (k_tables);
+ * k_vote casts the counted atomics of the set columns only (see agg_pair) */
+constexpr int AGG_OFF_COLS = (AGG_Q + 1) * AGG_ROW;
+constexpr uint32_t AGG_COLS_ALL = (2u << AGG_NY) - 1u; /* all 17 columns */
+static_assert(AGG_OFF_COLS % 4 == 0 && AGG_OFF_COLS + 4 <= AGG_SCRATCH, "the column mask lives in the padding behind the rows");
 constexpr int TBL_OFF_A32 = AGG_SCRATCH;
 constexpr int TBL_A32_BYTES = (AGG_NY * AGG_Q > 768 ? AGG_NY * AGG_Q : 768);
 constexpr int TBL_OFF_IDX = TBL_OFF_A32 + TBL_A32_BYTES;
@@ -767,7 +782,7 @@ __global__ __launch_bounds__(GROUP_BLOCK) void k_group(MatchArgs a) {
               if (okr) a.table_desc[tt] = make_uint2(hit_base + placed + pos + h0, min((uint32_t)AGG_SUB, c - h0));
           }
           /* what this run will cost k_vote (its launch order: longest first), in direct votes: a run that votes through count
-           * tables pays per table what PPF_AGG_MIN_HITS direct hits would, whatever its hits */
+           * tables pays per table, not per hit (PPF_COST_TABLE: swept again with the column masks, profiles/r14_sparse_tables.md) */
           w += (unsigned long long)(many ? ((c + AGG_SUB - 1) / AGG_SUB) * (uint32_t)PPF_COST_TABLE : max(c, (uint32_t)PPF_COST_MIN_HITS)) * a.bucket_total[b0 + k] + (uint32_t)PPF_COST_ITEM;
         }
         pos += c;
@@ -1160,6 +1175,14 @@ __device__ __forceinline__ void table_build(const uint32_t ws, const float S, co
     more[t] = tot - less[t] - c[t];
   }
   const int yy = lane >> 2;
+  { /* the column mask: Y values that occur (one ballot bit per lane quad, squeezed to one bit per Y), each feeding columns Y and Y + 1 */
+    unsigned long long o = __ballot(tot != 0u) & 0x1111111111111111ull;
+    o = (o | (o >> 3)) & 0x0303030303030303ull;
+    o = (o | (o >> 6)) & 0x000F000F000F000Full;
+    o = (o | (o >> 12)) & 0x000000FF000000FFull;
+    o = (o | (o >> 24)) & 0xFFFFull;
+    if (lane == 0) lds_st(ws + AGG_OFF_COLS, ((uint32_t)o | ((uint32_t)o << 1)) & AGG_COLS_ALL);
+  }
 #pragma unroll
   for (int t = 0; t < PER; t++) {
     const uint32_t mprev = __shfl_up(more[t], 4);
@@ -1326,12 +1349,12 @@ __device__ __forceinline__ void agg_own_fetch(const AggConsts& k, const uint4 re
 }
 
 /* The two model entries of one pair record against the count table (rows and cell ranges in the wave's LDS, copied from the
- * table `tbl` the item works with): 17 counted atomics each, then one vote per hit of each entry's own cell (all hits for an
+ * table `tbl` the item works with): one counted atomic each per set column of the table's mask `cols`, then one vote per hit of each entry's own cell (all hits for an
  * entry that votes one by one) with the direct arithmetic.  The offsets of those hits come straight from the table, four
  * per entry, fetched a block ahead (agg_own_fetch): at 64 cells an entry's cell holds three hits on average, so the LDS
  * sees no reads for them and most blocks need no second fetch.  `votes` counts the one-by-one votes. */
 __device__ __forceinline__ void agg_pair(const AggConsts& k, const uint4 rec, const AggOwn& own, const unsigned char* __restrict__ tbl,
-                                         const double* __restrict__ g_a64, uint32_t& votes) {
+                                         const double* __restrict__ g_a64, const uint32_t cols, uint32_t& votes) {
   const float am_a = __uint_as_float(rec.z), am_b = __uint_as_float(rec.w);
   /* X and cell of the two entries: evaluated by the table build (agg_cell_bits), carried in the row codes */
   const int Xa = (int)((rec.x >> ROW_X_SHIFT) & 31u), qa = (int)((rec.x >> ROW_Q_SHIFT) & ROW_Q_MASK);
@@ -1376,10 +1399,26 @@ __device__ __forceinline__ void agg_pair(const AggConsts& k, const uint4 rec, co
     lds_add(vb + (uint32_t)((AGG_NY - j) * 2), __builtin_amdgcn_perm(wb[(j + 1 > AGG_NY ? j : j + 1) >> 2], wb[j >> 2], sb[(j >> 1) & 3]));
   }
 #else
+  /* `cols` is the table's column mask in a scalar register: a table with every column set runs the 17 pairs as one straight block; any other skips the pairs of its all-zero columns, each behind
+   * a scalar bit test and branch (no lane predicate, every atomic still base + immediate offset).  Measured and left
+   * (profiles/r14_sparse_tables.md): the masked block for every table (+0.02 ms), the rows' 8-byte reads skipped with their
+   * columns (+0.02 ms), one test per row word in front of its four (+-0) */
+  uint32_t cm = cols;
+  asm volatile("" : "+s"(cm)); /* the tests stay s_bitcmp1 on this one register: hoisted out of the record loop they would be 17 lane masks in 34 scalar registers */
+  if (cm == AGG_COLS_ALL) {
 #pragma unroll
-  for (int j = 0; j <= AGG_NY; j++) {
-    lds_add(va + (uint32_t)((AGG_NY - j) * 4), __builtin_amdgcn_perm(0u, wa[j >> 2], sa[j & 3]));
-    lds_add(vb + (uint32_t)((AGG_NY - j) * 4), __builtin_amdgcn_perm(0u, wb[j >> 2], sb[j & 3]));
+    for (int j = 0; j <= AGG_NY; j++) {
+      lds_add(va + (uint32_t)((AGG_NY - j) * 4), __builtin_amdgcn_perm(0u, wa[j >> 2], sa[j & 3]));
+      lds_add(vb + (uint32_t)((AGG_NY - j) * 4), __builtin_amdgcn_perm(0u, wb[j >> 2], sb[j & 3]));
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j <= AGG_NY; j++) {
+      if (cm & (1u << j)) {
+        lds_add(va + (uint32_t)((AGG_NY - j) * 4), __builtin_amdgcn_perm(0u, wa[j >> 2], sa[j & 3]));
+        lds_add(vb + (uint32_t)((AGG_NY - j) * 4), __builtin_amdgcn_perm(0u, wb[j >> 2], sb[j & 3]));
+      }
+    }
   }
 #endif
 #endif
@@ -1601,6 +1640,9 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
   const uint32_t agg_min = (!WRAP && a.agg_min_hits > 0 && A <= AGG_MAX_ANGLES) ? (uint32_t)a.agg_min_hits : 0xFFFFFFFFu;
   unsigned long long ops = 0; /* LDS atomic lane-operations issued by this wave (wave-uniform part) */
   uint32_t agg_votes = 0;     /* ... plus this lane's one-by-one votes on the count-table path */
+#ifdef PPF_DIAG_COLUMNS
+  unsigned long long diag_dense = 0, diag_cols = 0, diag_full = 0;
+#endif
   unsigned long long issued = 0; /* votes cast by this wave, wave-uniform: every lane slot of an item casts one vote per hit, into a cell or a guard word */
 
   const int pass = ACC32 ? (vt & 1) : 0;
@@ -1775,6 +1817,10 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
           }
           const unsigned char* __restrict__ tbl = cur.tbl;
           const double* __restrict__ g_a64 = a.s_a64 + cur.g0;
+          /* the table's column mask, out of the lane that copied its word: a scalar for the whole item */
+          constexpr int cols_piece = AGG_OFF_COLS / 16, cols_word = (AGG_OFF_COLS % 16) / 4;
+          const uint4 cols_q = cols_piece < 64 ? tbl0 : tbl1;
+          const uint32_t cols = (uint32_t)__builtin_amdgcn_readlane((int)(cols_word == 0 ? cols_q.x : cols_word == 1 ? cols_q.y : cols_word == 2 ? cols_q.z : cols_q.w), cols_piece & 63) & AGG_COLS_ALL;
           /* two blocks of records in flight: block i+2's records and block i+1's own-cell offsets (which need that block's
            * records and the cell ranges in LDS) are loaded under block i's votes, so a block waits for nothing issued in
            * its own iteration */
@@ -1788,12 +1834,17 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
             agg_own_fetch(ak, rec_n1, tbl, cur.nh, own_n1);
             uint4 rec = rec_cur;
             if (e >= c) { rec.x = tail_bytes | (rec.x & ~ROW_CODE_MASK); rec.y = tail_bytes | (rec.y & ~ROW_CODE_MASK); } /* the clamped record's cells go with its alphas */
-            agg_pair(ak, rec, own_cur, tbl, g_a64, agg_votes);
+            agg_pair(ak, rec, own_cur, tbl, g_a64, cols, agg_votes);
             rec_cur = rec_n1;
             rec_n1 = rec_n2;
             own_cur = own_n1;
           }
-          ops += 2u * (AGG_NY + 1) * 64u * ((c + 63u) / 64u);
+          ops += 2u * (uint32_t)__builtin_popcount(cols) * 64u * ((c + 63u) / 64u); /* what the product issues: the set columns only (the PPF_MOCK_PAIRBINS and PPF_ABL_COUNTED builds cast another number: their n_lds_atomics means nothing) */
+#ifdef PPF_DIAG_COLUMNS
+          diag_dense += 2u * (AGG_NY + 1) * 64u * ((c + 63u) / 64u);
+          diag_cols += 2u * (uint32_t)__builtin_popcount(cols) * 64u * ((c + 63u) / 64u);
+          if (cols == AGG_COLS_ALL) diag_full += 2u * (AGG_NY + 1) * 64u * ((c + 63u) / 64u);
+#endif
           issued += 128ull * ((c + 63u) / 64u) * (uint32_t)cur.nh; /* counted + one-by-one votes of an entry = its hits */
           PPF_PHASE(2);
         } else {
@@ -1990,6 +2041,9 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
   for (int o = 32; o > 0; o >>= 1) wops += __shfl_down(wops, o);
   wops += ops;
   if (lane == 0 && wops) atomicAdd(&a.tally[0], wops);
+#ifdef PPF_DIAG_COLUMNS
+  if (lane == 0 && diag_dense) { atomicAdd(&a.tally[6], diag_dense); atomicAdd(&a.tally[7], diag_cols); atomicAdd(&a.tally[8], diag_full); }
+#endif
   PPF_PHASE(6);
   PPF_PHASE_FLUSH(a.tally, lane);
   if (!ACC32) break;
