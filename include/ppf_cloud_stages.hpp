@@ -16,6 +16,8 @@
  *   transformPCPose -> writePLY of the result       ->  Cloud::renderFrame(modelClouds, poses, best, ...)  (depth, label images)
  *   `return *resultsSub[0];` per box (:480, :533)   ->  Cloud::selectFrame(modelClouds, poses, depth, ...)  (one consistent set per frame)
  *   (nothing: the reference stops at the ICP pose)  ->  Cloud::refineFrame(modelClouds, poses, depth, ...)  (poses fitted to the depth image)
+ *   k4a::transformation::depth_image_to_color_camera (k4a_grabber.h:339, :391) -> DepthMap::registerDepth / registerDepthU16
+ *                                                     (a raw sensor depth frame aligned to the colour camera; Cloud::fromDepth takes it)
  *
  * Every stage returns a new Cloud that stays in HBM; only toMat()/download() copy to the host.  A maintainer replaces
  * the bodies of those CloudProcessor methods by these one-liners; pcl::PointCloud<PointXYZ> goes
@@ -377,6 +379,73 @@ class Cloud {
     return h_.get();
   }
   std::shared_ptr<ppf_cloud> h_;
+};
+
+/* A resident registration map (ppf_depth_map), built once per calibration as k4a::transformation is: registerDepth draws a
+ * raw depth frame of the depth camera into the pixel grid of the colour camera (float32 metres, 0 where nothing was drawn),
+ * which is what Cloud::fromDepth and every frame stage take with fx(), fy(), ppx(), ppy().  R9 (row-major) and t3 (metres)
+ * take a point of the depth camera's frame into the colour camera's.  Copies share the map. */
+class DepthMap {
+ public:
+  DepthMap() : cam_(), rows_(0), cols_(0) {}
+  DepthMap(const ppf_camera& depthCam, int depthRows, int depthCols, const ppf_camera& colorCam, int colorRows, int colorCols,
+           const double R9[9], const double t3[3])
+      : cam_(colorCam), rows_(colorRows), cols_(colorCols) {
+    ppf_depth_map* m = nullptr;
+    ppf_match_3d::check(ppf_depth_map_create(&depthCam, depthRows, depthCols, &colorCam, colorRows, colorCols, R9, t3, &m));
+    h_ = std::shared_ptr<ppf_depth_map>(m, [](ppf_depth_map* p) { ppf_depth_map_release(p); });
+  }
+  static ppf_camera pinhole(double fx, double fy, double cx, double cy) {
+    ppf_camera c;
+    ppf_default_camera(&c, fx, fy, cx, cy);
+    return c;
+  }
+  int rows() const { return rows_; } /* of the aligned image */
+  int cols() const { return cols_; }
+  double fx() const { return cam_.fx; }
+  double fy() const { return cam_.fy; }
+  double ppx() const { return cam_.cx; }
+  double ppy() const { return cam_.cy; }
+  const ppf_depth_map* handle() const { return h_.get(); }
+
+  /* float32 metres in, the aligned rows() x cols() image out; rowPitchBytes 0: packed rows */
+  std::vector<float> registerDepth(const float* depth, float zMin = 0.f, float zMax = 0.f, size_t rowPitchBytes = 0,
+                                   const ppf_register_params* params = 0, ppf_register_stats* stats = 0) const {
+    return run(depth, PPF_DEPTH_F32, 0.001, zMin, zMax, rowPitchBytes, params, stats);
+  }
+  /* a 16-bit sensor image: z = d * scale metres (0.001 for millimetres) */
+  std::vector<float> registerDepthU16(const uint16_t* depth, double scale, float zMin = 0.f, float zMax = 0.f, size_t rowPitchBytes = 0,
+                                      const ppf_register_params* params = 0, ppf_register_stats* stats = 0) const {
+    return run(depth, PPF_DEPTH_U16, scale, zMin, zMax, rowPitchBytes, params, stats);
+  }
+  /* a detector's boxes {x, y, w, h} on the raw colour image (camera `raw`, with its distortion) in this map's colour camera */
+  std::vector<int> mapBoxes(const ppf_camera& raw, const int* boxesXYWH, int n) const {
+    std::vector<int> out((size_t)(n > 0 ? n : 0) * 4 + 1, 0);
+    ppf_match_3d::check(ppf_camera_map_boxes(&raw, &cam_, rows_, cols_, boxesXYWH, n, &out[0]));
+    out.resize((size_t)(n > 0 ? n : 0) * 4);
+    return out;
+  }
+
+ private:
+  std::vector<float> run(const void* depth, int format, double scale, float zMin, float zMax, size_t rowPitchBytes,
+                         const ppf_register_params* params, ppf_register_stats* stats) const {
+    if (!h_) throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::DepthMap: empty handle");
+    ppf_depth_params dp;
+    ppf_default_depth_params(&dp);
+    dp.format = format;
+    dp.depth_scale = scale;
+    dp.z_min = zMin;
+    dp.z_max = zMax;
+    ppf_register_params rp;
+    if (params) rp = *params; else ppf_default_register_params(&rp);
+    std::vector<float> out((size_t)rows_ * (size_t)cols_ + 1);
+    ppf_match_3d::check(ppf_depth_register(h_.get(), depth, rowPitchBytes, &dp, &rp, &out[0], stats));
+    out.resize((size_t)rows_ * (size_t)cols_);
+    return out;
+  }
+  std::shared_ptr<ppf_depth_map> h_;
+  ppf_camera cam_;
+  int rows_, cols_;
 };
 
 }  // namespace prep

@@ -47,6 +47,11 @@
  *                                   transformPCPose -> writePLY dump of the result (YOLO_cropping_ppf_test.cpp:125-127)
  *   ppf_select_frame                one consistent set of poses per frame: duplicates and overlapping boxes suppressed,
  *                                   several instances per box kept (the reference returns `*resultsSub[0]` per box)
+ *   ppf_refine_frame                poses fitted to the depth image itself (the reference stops at the ICP pose)
+ *   ppf_depth_map_create +          k4a::transformation + depth_image_to_color_camera, the vendor SDK call the reference's
+ *   ppf_depth_register (+_device)   grabber makes per capture (k4a_grabber.h:339-340, :391-392): a raw sensor depth image
+ *                                   drawn into the colour camera's pixel grid, lens distortion of both cameras included
+ *   ppf_camera_map_boxes            a detector's boxes on the raw colour image carried into that pixel grid
  *
  * Conventions
  *   - A cloud argument is (pointer, rows, stride, normal_offset): float32 rows whose first three floats
@@ -713,6 +718,88 @@ void ppf_default_refine_params(ppf_refine_params* p);
 ppf_status ppf_refine_frame(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top,
                             const float* depth, int depth_rows, int depth_cols, const double* intr,
                             const ppf_refine_params* params, ppf_pose* out, ppf_refine_info* info, ppf_refine_stats* stats);
+
+/* ---- a raw sensor depth image aligned to the colour camera (what the vendor SDK's depth_image_to_color_camera does) -- */
+#define PPF_CAMERA_NEWTON_ITERS 7   /* Newton steps of an unprojection, always all of them (DESIGN.md §18 measures the count) */
+#define PPF_REGISTER_MAX_QUAD_PX 16 /* a triangle whose clamped bounding box is wider or taller than this is not drawn */
+
+/* A pinhole camera with OpenCV's rational radial + tangential distortion (include/ppf_camera_math.h is the arithmetic,
+ * fp64, bit for bit the same on the host and on the device).  A camera is valid when fx and fy are finite and non-zero,
+ * every other field is finite, max_r >= 0 and reserved is zero. */
+typedef struct ppf_camera {
+  double fx, fy, cx, cy;                 /* fx, fy finite and non-zero; cx, cy finite */
+  double k1, k2, p1, p2, k3, k4, k5, k6; /* OpenCV order: rational radial + tangential; all zero: pinhole */
+  double max_r;                          /* 0: no limit; else a normalised point with x*x + y*y > max_r*max_r is invalid */
+  double reserved[3];                    /* 0 */
+} ppf_camera;
+/* a pinhole camera: every coefficient, max_r and reserved zero */
+void ppf_default_camera(ppf_camera* cam, double fx, double fy, double cx, double cy);
+/* Host only, no device needed.  xy and uv are [n][2] doubles; valid ([n] bytes, 1 or 0) may be NULL.
+ * ppf_camera_project: normalised points (x, y) -> pixels (u, v); ppf_camera_unproject: pixels -> normalised points by
+ * exactly PPF_CAMERA_NEWTON_ITERS Newton steps.  An invalid point (ppf_camera_math.h lists the conditions) gives NaN NaN
+ * and valid 0.  A NULL pointer, n < 0 or an invalid camera is PPF_ERR_INVALID, the outputs all NaN and 0 where they can be
+ * reached. */
+ppf_status ppf_camera_project(const ppf_camera* cam, const double* xy, int n, double* uv, uint8_t* valid);
+ppf_status ppf_camera_unproject(const ppf_camera* cam, const double* uv, int n, double* xy, uint8_t* valid);
+/* Carries n boxes {x, y, width, height} of the image of camera `from` (e.g. a detector's boxes on the raw, distorted colour
+ * image) into the to_rows x to_cols image of camera `to`: the eight points of a box (corners and side midpoints, at x,
+ * x + w / 2.0, x + w and likewise for y) are unprojected with `from` and projected with `to`; the result spans
+ * floor(min) .. ceil(max) of the valid ones, clamped to the image (as doubles, before the conversion to int).  Rounding is
+ * outwards: a point that comes back one ulp past an integer grows the box by a pixel.  A box without a valid point, or
+ * empty after clamping, is {0, 0, 0, 0}.  Host only.  Argument errors are PPF_ERR_INVALID and every output box is zero. */
+ppf_status ppf_camera_map_boxes(const ppf_camera* from, const ppf_camera* to, int to_rows, int to_cols, const int* boxes_xywh, int n,
+                                int* out_xywh);
+
+typedef struct ppf_depth_map ppf_depth_map; /* opaque, device-resident: the ray table of a depth camera + the calibration */
+
+/* Built once per calibration.  R9 (row-major) and t3 (metres) take a point of the depth camera's frame into the colour
+ * camera's: Q[r] = R[r][0]*P0 + R[r][1]*P1 + R[r][2]*P2 + t[r].  R9 is used as given: it is NOT tested for orthonormality.
+ * One kernel (k_reg_rays) unprojects every depth pixel once; the table takes 16 bytes a pixel.  Argument errors (NULL
+ * pointers, sizes <= 0 or above INT32_MAX pixels, an invalid camera, R9 or t3 not finite) are PPF_ERR_INVALID before any
+ * device work; on any error *out is NULL.  A map is immutable: any number of host threads may register with it at once. */
+ppf_status ppf_depth_map_create(const ppf_camera* depth_cam, int depth_rows, int depth_cols, const ppf_camera* color_cam,
+                                int color_rows, int color_cols, const double* R9, const double* t3, ppf_depth_map** out);
+ppf_status ppf_depth_map_release(ppf_depth_map* map);
+/* the ray table, HOST [depth_rows][depth_cols][2] doubles: the normalised (x, y) of every depth pixel, NaN NaN = invalid */
+ppf_status ppf_depth_map_rays(const ppf_depth_map* map, double* rays);
+
+typedef struct ppf_register_params {
+  float quad_dz_abs, quad_dz_rel; /* finite, >= 0: a quad is cut when max(zc) - min(zc) > quad_dz_abs + quad_dz_rel * min(zc) */
+  int32_t flags;                  /* 0 */
+  int32_t reserved[4];
+} ppf_register_params;
+
+typedef struct ppf_register_stats {
+  int32_t n_vertices;       /* depth pixels that are kept, have a valid ray and project validly into the colour camera */
+  int32_t n_quads;          /* quads of four valid vertices */
+  int32_t n_quads_cut;      /* of those, cut at a depth discontinuity */
+  int32_t n_quads_oversize; /* of the uncut ones, with a triangle over PPF_REGISTER_MAX_QUAD_PX */
+  int32_t n_filled;         /* output pixels drawn */
+  int32_t n_launches;       /* kernel launches of the call */
+  int32_t n_host_syncs;     /* blocking waits of the call */
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_register_stats;
+
+/* 0.02, 0.02, 0: a choice, not tuned on real data (2 cm plus 2 % of the depth between the vertices of one quad) */
+void ppf_default_register_params(ppf_register_params* p);
+/* Draws the depth image of the map's depth camera into the pixel grid of its colour camera (DESIGN.md §18 states every
+ * step bit for bit): every kept pixel becomes a vertex in the colour frame, every quad of four valid vertices that is not
+ * cut is drawn as two triangles with linear depth interpolation, and each output pixel takes the nearest depth drawn on it.
+ * out: float32 metres, packed color_rows x color_cols, 0 where nothing was drawn: exactly what ppf_cloud_from_depth and
+ * every frame stage take, with intr = the first four doubles of color_cam.  depth, row_pitch_bytes and dp are
+ * ppf_cloud_from_depth's (format, depth_scale, z_min, z_max; the image is depth_rows x depth_cols of the map), except
+ * that dp->flags must be 0.  The result does not depend on scheduling.  Three launches, one blocking wait and one
+ * read-back whatever the sizes.  Argument errors are PPF_ERR_INVALID before any device work; on any error `out` is all 0
+ * where it can be reached and *stats is zero.  stats may be NULL. */
+ppf_status ppf_depth_register(const ppf_depth_map* map, const void* depth, size_t row_pitch_bytes, const ppf_depth_params* dp,
+                              const ppf_register_params* rp, float* out, ppf_register_stats* stats);
+/* the same between DEVICE buffers: enqueued on `stream` (a hipStream_t, NULL: default stream), returns when the image is
+ * complete.  d_out (color_rows x color_cols floats, packed) serves as the z-buffer while the call runs.  A pointer the
+ * current device cannot read, a buffer that runs past the end of its allocation, or d_out overlapping the depth image is
+ * PPF_ERR_INVALID before anything is launched; d_out is not touched on an error. */
+ppf_status ppf_depth_register_device(const ppf_depth_map* map, const void* d_depth, size_t row_pitch_bytes, const ppf_depth_params* dp,
+                                     const ppf_register_params* rp, float* d_out, void* stream, ppf_register_stats* stats);
 
 #ifdef __cplusplus
 }

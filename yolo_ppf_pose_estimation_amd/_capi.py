@@ -188,6 +188,25 @@ class RefineStats(C.Structure):
 PPF_REFINE_NONE, PPF_REFINE_CONVERGED, PPF_REFINE_MAX_ITERS, PPF_REFINE_LOST, PPF_REFINE_STEP = 0, 1, 2, 3, 4
 
 
+class Camera(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("k1", C.c_double),
+                ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double), ("k3", C.c_double), ("k4", C.c_double),
+                ("k5", C.c_double), ("k6", C.c_double), ("max_r", C.c_double), ("reserved", C.c_double * 3)]
+
+
+class RegisterParams(C.Structure):
+    _fields_ = [("quad_dz_abs", C.c_float), ("quad_dz_rel", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class RegisterStats(C.Structure):
+    _fields_ = [("n_vertices", C.c_int32), ("n_quads", C.c_int32), ("n_quads_cut", C.c_int32), ("n_quads_oversize", C.c_int32),
+                ("n_filled", C.c_int32), ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32), ("ms_wall", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
+PPF_CAMERA_NEWTON_ITERS, PPF_REGISTER_MAX_QUAD_PX = 7, 16  # include/ppf_hip.h
+
+
 # every symbol include/ppf_hip.h declares (tests/test_capi_symbols.py checks the header against this)
 _SIGNATURES = {
     "ppf_default_train_params": (None, [C.POINTER(TrainParams)]),
@@ -300,6 +319,19 @@ _SIGNATURES = {
     "ppf_refine_frame": (C.c_int, [C.POINTER(FrameDetection), C.c_int, C.POINTER(Pose), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int,
                                    C.c_int, C.POINTER(C.c_double), C.POINTER(RefineParams), C.POINTER(Pose), C.POINTER(RefineInfo),
                                    C.POINTER(RefineStats)]),
+    "ppf_default_camera": (None, [C.POINTER(Camera), C.c_double, C.c_double, C.c_double, C.c_double]),
+    "ppf_camera_project": (C.c_int, [C.POINTER(Camera), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "ppf_camera_unproject": (C.c_int, [C.POINTER(Camera), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "ppf_camera_map_boxes": (C.c_int, [C.POINTER(Camera), C.POINTER(Camera), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "ppf_depth_map_create": (C.c_int, [C.POINTER(Camera), C.c_int, C.c_int, C.POINTER(Camera), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_void_p)]),
+    "ppf_depth_map_release": (C.c_int, [C.c_void_p]),
+    "ppf_depth_map_rays": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ppf_default_register_params": (None, [C.POINTER(RegisterParams)]),
+    "ppf_depth_register": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(DepthParams), C.POINTER(RegisterParams), C.c_void_p,
+                                     C.POINTER(RegisterStats)]),
+    "ppf_depth_register_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(DepthParams), C.POINTER(RegisterParams),
+                                            C.c_void_p, C.c_void_p, C.POINTER(RegisterStats)]),
     "ppf_icp_register": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }

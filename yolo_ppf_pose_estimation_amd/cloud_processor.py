@@ -364,6 +364,125 @@ def refine_frame(dets, poses, depth, intr, params=None, top: Optional[int] = Non
     return (refined, rows_info, _capi.stats_dict(st)) if return_stats else (refined, rows_info)
 
 
+def camera(cam) -> _capi.Camera:
+    """A ``ppf_camera`` record from: a Camera; (fx, fy, cx, cy) or a 3x3 camera matrix (pinhole); a dict of its fields; or any
+    object with those attributes (fx, fy, cx, cy and optionally k1..k6, p1, p2, max_r)."""
+    if isinstance(cam, _capi.Camera):
+        return cam
+    names = [f for f, _ in _capi.Camera._fields_ if f != "reserved"]
+    c = _capi.Camera()
+    if isinstance(cam, dict) or hasattr(cam, "fx"):
+        get = cam.get if isinstance(cam, dict) else (lambda k, d=0.0: getattr(cam, k, d))
+        lib().ppf_default_camera(C.byref(c), float(get("fx")), float(get("fy")), float(get("cx")), float(get("cy")))
+        for f in names[4:]:
+            setattr(c, f, float(get(f, 0.0)))
+        return c
+    lib().ppf_default_camera(C.byref(c), *_intr4(cam))
+    return c
+
+
+def camera_points(cam, pts, unproject: bool = False):
+    """ppf_camera_project (normalised points -> pixels) or, with ``unproject``, ppf_camera_unproject (pixels -> normalised
+    points) of an (n, 2) array, on the host: (points (n, 2) float64, NaN where invalid; valid (n,) bool)."""
+    a = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 2)
+    out = np.empty_like(a)
+    valid = np.zeros(a.shape[0], np.uint8)
+    fn = lib().ppf_camera_unproject if unproject else lib().ppf_camera_project
+    check(fn(C.byref(camera(cam)), a.ctypes.data, a.shape[0], out.ctypes.data, valid.ctypes.data))
+    return out, valid.astype(bool)
+
+
+def map_boxes(cam_from, cam_to, to_rows: int, to_cols: int, boxes) -> np.ndarray:
+    """ppf_camera_map_boxes: the boxes (x, y, w, h) of a detector run on the raw colour image (camera ``cam_from``, with its
+    distortion) carried into the pinhole camera ``cam_to`` the aligned depth image lives in; (n, 4) int32, a box that
+    cannot be mapped is all zero."""
+    b = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 4))
+    out = np.zeros_like(b)
+    check(lib().ppf_camera_map_boxes(C.byref(camera(cam_from)), C.byref(camera(cam_to)), int(to_rows), int(to_cols), b.ctypes.data,
+                                     b.shape[0], out.ctypes.data))
+    return out
+
+
+class DepthMap:
+    """A resident registration map (``ppf_depth_map``): built once per calibration from the depth camera, the colour camera
+    and the extrinsics (R, t: depth frame -> colour frame, metres); ``register`` then aligns each raw depth frame to the
+    colour camera's pixel grid on the device."""
+
+    def __init__(self, depth_cam, depth_shape, color_cam, color_shape, R, t):
+        self.depth_shape = (int(depth_shape[0]), int(depth_shape[1]))
+        self.color_shape = (int(color_shape[0]), int(color_shape[1]))
+        self.color_cam = camera(color_cam)
+        R9 = np.ascontiguousarray(R, dtype=np.float64).reshape(-1)
+        t3 = np.ascontiguousarray(t, dtype=np.float64).reshape(-1)
+        if R9.size != 9 or t3.size != 3:
+            raise PPFError(_capi.PPF_ERR_INVALID, "R must have 9 elements and t 3")
+        self._ptr = C.c_void_p()
+        check(lib().ppf_depth_map_create(C.byref(camera(depth_cam)), self.depth_shape[0], self.depth_shape[1], C.byref(self.color_cam),
+                                         self.color_shape[0], self.color_shape[1], R9.ctypes.data, t3.ctypes.data, C.byref(self._ptr)))
+
+    def __del__(self):
+        try:
+            if self._ptr:
+                lib().ppf_depth_map_release(self._ptr)
+                self._ptr = None
+        except Exception:
+            pass
+
+    @property
+    def intr(self):
+        """(fx, fy, ppx, ppy) of the aligned image: what every later stage takes"""
+        c = self.color_cam
+        return (c.fx, c.fy, c.cx, c.cy)
+
+    def rays(self) -> np.ndarray:
+        """the ray table, (rows, cols, 2) float64, NaN NaN where a depth pixel has no ray"""
+        out = np.empty(self.depth_shape + (2,), np.float64)
+        check(lib().ppf_depth_map_rays(self._ptr, out.ctypes.data))
+        return out
+
+    def register(self, depth, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0, params=None, out=None,
+                 return_stats: bool = False):
+        """The depth frame drawn into the colour camera's pixel grid (ppf_depth_register): float32 metres, 0 where nothing
+        was drawn.  depth: a 2-D numpy float32 (metres) or uint16 (units of depth_scale metres) array of the map's depth
+        size, rows read at its stride, which gives a numpy image; or such a torch tensor on the GPU, read in place on
+        ``torch.cuda.current_stream()`` (ppf_depth_register_device), which gives a float32 tensor on the same device (or
+        fills ``out``).  params: a RegisterParams, a dict of its fields or None (the defaults)."""
+        prm = _params(_capi.RegisterParams, "ppf_default_register_params", params)
+        dp = _capi.DepthParams()
+        lib().ppf_default_depth_params(C.byref(dp))
+        dp.depth_scale, dp.z_min, dp.z_max = float(depth_scale), float(z_min), float(z_max)
+        st = _capi.RegisterStats()
+        if type(depth).__module__.startswith("torch") and depth.is_cuda:
+            import torch
+            fmt = {torch.float32: _capi.PPF_DEPTH_F32, torch.uint16: _capi.PPF_DEPTH_U16}.get(depth.dtype)
+            if fmt is None or depth.dim() != 2 or tuple(depth.shape) != self.depth_shape:
+                raise PPFError(_capi.PPF_ERR_INVALID, f"depth must be a float32 or uint16 tensor of shape {self.depth_shape}")
+            if depth.stride(1) != 1 or depth.stride(0) < depth.shape[1]:
+                depth = depth.contiguous()
+            if out is None:
+                out = torch.empty(self.color_shape, dtype=torch.float32, device=depth.device)
+            elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == self.color_shape and out.is_contiguous()):
+                raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous float32 GPU tensor of shape {self.color_shape}")
+            dp.format = fmt
+            with torch.cuda.device(depth.device):
+                stream = torch.cuda.current_stream(depth.device).cuda_stream
+                check(lib().ppf_depth_register_device(self._ptr, C.c_void_p(depth.data_ptr()), depth.stride(0) * depth.element_size(),
+                                                      C.byref(dp), C.byref(prm), C.c_void_p(out.data_ptr()),
+                                                      C.c_void_p(stream) if stream else None, C.byref(st)))
+            return (out, _capi.stats_dict(st)) if return_stats else out
+        a = np.asarray(depth.numpy() if type(depth).__module__.startswith("torch") else depth)
+        fmt = {np.dtype(np.float32): _capi.PPF_DEPTH_F32, np.dtype(np.uint16): _capi.PPF_DEPTH_U16}.get(a.dtype)
+        if fmt is None or a.ndim != 2 or a.shape != self.depth_shape:
+            raise PPFError(_capi.PPF_ERR_INVALID, f"depth must be a float32 or uint16 array of shape {self.depth_shape}")
+        if a.strides[1] != a.itemsize or a.strides[0] < a.shape[1] * a.itemsize or a.strides[0] % a.itemsize:
+            a = np.ascontiguousarray(a)
+        dp.format = fmt
+        img = np.empty(self.color_shape, np.float32)
+        check(lib().ppf_depth_register(self._ptr, C.c_void_p(a.ctypes.data), a.strides[0], C.byref(dp), C.byref(prm), img.ctypes.data,
+                                       C.byref(st)))
+        return (img, _capi.stats_dict(st)) if return_stats else img
+
+
 class CloudProcessor:
     """``ppf::CloudProcessor``: holds the scene cloud, the depth image, the detector's boxes, the per-object clouds
     and the PPF detectors; every method is the reference's, in the order its driver calls them

@@ -50,6 +50,33 @@ ppf_status depth_check(const char* who, const void* depth, int rows, int cols, s
   return PPF_OK;
 }
 
+/* `bytes` from d_ptr on must be memory the current device can read directly, inside one allocation; `what` names the buffer */
+ppf_status depth_device_range(const char* who, const char* what, const void* d_ptr, size_t bytes) {
+  hipPointerAttribute_t attr;
+  std::memset(&attr, 0, sizeof(attr));
+  const hipError_t pe = hipPointerGetAttributes(&attr, d_ptr);
+  if (pe != hipSuccess) {
+    (void)hipGetLastError(); /* the query's error is the answer, not a sticky state */
+    return fail(PPF_ERR_INVALID, "%s: the %s pointer is not device memory (%s)", who, what, hipGetErrorString(pe));
+  }
+  int dev = -1;
+  HIPCHK(hipGetDevice(&dev));
+  if (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)
+    return fail(PPF_ERR_INVALID, "%s: the %s pointer is not device memory (memory type %d)", who, what, (int)attr.type);
+  if (attr.device != dev) return fail(PPF_ERR_INVALID, "%s: the %s lives on device %d, the current device is %d", who, what, attr.device, dev);
+  hipDeviceptr_t base = nullptr;
+  size_t alloc = 0;
+  const hipError_t re = hipMemGetAddressRange(&base, &alloc, const_cast<void*>(d_ptr));
+  if (re != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(PPF_ERR_INVALID, "%s: the %s's allocation is unknown (%s)", who, what, hipGetErrorString(re));
+  }
+  const uintptr_t lo = (uintptr_t)base, at = (uintptr_t)d_ptr;
+  if (at < lo || at - lo > alloc || bytes > alloc - (at - lo))
+    return fail(PPF_ERR_INVALID, "%s: the %s (%zu bytes) runs past the end of its allocation", who, what, bytes);
+  return PPF_OK;
+}
+
 /* count -> scan -> one read-back -> allocate -> scatter, all on `st`; returns once the cloud is complete */
 ppf_status depth_run(const DepthArgs& a, int format, hipStream_t st, ppf_cloud** out) {
   const int n_tiles = (int)(((size_t)a.n + DEPTH_TILE - 1) / DEPTH_TILE);
@@ -124,29 +151,8 @@ ppf_status ppf_cloud_from_depth_device(const void* d_depth, int rows, int cols, 
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
   /* only memory the current device can read directly, and the whole image inside its allocation */
-  hipPointerAttribute_t attr;
-  std::memset(&attr, 0, sizeof(attr));
-  const hipError_t pe = hipPointerGetAttributes(&attr, d_depth);
-  if (pe != hipSuccess) {
-    (void)hipGetLastError(); /* the query's error is the answer, not a sticky state */
-    return fail(PPF_ERR_INVALID, "%s: the image pointer is not device memory (%s)", who, hipGetErrorString(pe));
-  }
-  int dev = -1;
-  HIPCHK(hipGetDevice(&dev));
-  if (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)
-    return fail(PPF_ERR_INVALID, "%s: the image pointer is not device memory (memory type %d)", who, (int)attr.type);
-  if (attr.device != dev) return fail(PPF_ERR_INVALID, "%s: the image lives on device %d, the current device is %d", who, attr.device, dev);
   const size_t bytes = (size_t)(rows - 1) * pitch + (size_t)cols * depth_elem_size(p->format);
-  hipDeviceptr_t base = nullptr;
-  size_t alloc = 0;
-  const hipError_t re = hipMemGetAddressRange(&base, &alloc, const_cast<void*>(d_depth));
-  if (re != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(PPF_ERR_INVALID, "%s: the image's allocation is unknown (%s)", who, hipGetErrorString(re));
-  }
-  const uintptr_t lo = (uintptr_t)base, at = (uintptr_t)d_depth;
-  if (at < lo || at - lo > alloc || bytes > alloc - (at - lo))
-    return fail(PPF_ERR_INVALID, "%s: the image (%zu bytes) runs past the end of its allocation", who, bytes);
+  if ((s = depth_device_range(who, "image", d_depth, bytes)) != PPF_OK) return s;
   a.img = static_cast<const unsigned char*>(d_depth);
   return depth_run(a, p->format, static_cast<hipStream_t>(stream), out);
 }
