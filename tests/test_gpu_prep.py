@@ -2,6 +2,7 @@
 (oracle/ppf_prep_oracle.cpp), bit for bit, on the reference's own depth frame and on synthetic clouds; then the
 reference's whole sequence crop -> subsample -> outlier removal -> normals -> edges -> Matching_S2B (+ICP) through the
 CloudProcessor mirror (/root/reference/src/YOLO_cropping_ppf_test.cpp:84-123)."""
+import gc
 import os
 
 import numpy as np
@@ -10,7 +11,7 @@ import pytest
 import oracle_lib as O
 from conftest import soak_seeds
 import prep_data as D
-from yolo_ppf_pose_estimation_amd import synth
+from yolo_ppf_pose_estimation_amd import _capi, synth
 from yolo_ppf_pose_estimation_amd._capi import PPFError
 from yolo_ppf_pose_estimation_amd.cloud_processor import CloudProcessor, DeviceCloud
 
@@ -238,3 +239,90 @@ def test_stages_random_draw(frame, seed):
     np.testing.assert_array_equal(curv, c)
     thr = float(rng.choice([0.01, 0.03, 0.08]))
     np.testing.assert_array_equal(filt.normals(kn).edges(thr).rows(), rows[c > thr])
+
+
+# ---- the per-cloud entries as the one-segment case of the segmented stages -------------------------------------------
+@pytest.fixture(scope="module")
+def crop_xyz(frame):
+    xyz, depth, box, intr = frame
+    keep, _ = O.prep_crop(xyz, box, depth, intr)
+    return np.ascontiguousarray(xyz[keep])
+
+
+def _neighbour_stages_equal_oracle(cloud, mean_k, mul, k_normals, k_knn=None):
+    dc = DeviceCloud.upload(cloud)
+    keep, _, _ = O.prep_sor(cloud, mean_k, mul)
+    np.testing.assert_array_equal(dc.outlier_removal(mean_k, mul).xyz(), cloud[keep])
+    n, c = O.prep_normals(cloud, k_normals)
+    rows, curv = dc.normals(k_normals).download()
+    np.testing.assert_array_equal(rows[:, :3], cloud)
+    np.testing.assert_array_equal(rows[:, 3:], n)
+    np.testing.assert_array_equal(curv, c)
+    if k_knn:
+        idx, d2 = dc.knn(k_knn)
+        widx, wd2 = O.prep_knn(cloud, k_knn)
+        np.testing.assert_array_equal(idx, widx)
+        np.testing.assert_array_equal(d2, wd2)
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 63, 64, 65, 129])
+def test_segment_and_chunk_boundaries(crop_xyz, n):
+    """sizes around the 64-row SOR chunks, n <= meanK (nothing measured) against n > meanK, and k_eff = n"""
+    _neighbour_stages_equal_oracle(crop_xyz[:n], 8, 1.0, 10, 10)
+
+
+@pytest.mark.parametrize("bad", [np.nan, np.inf])
+def test_non_finite_row_into_the_neighbour_stages(crop_xyz, bad):
+    cloud = np.insert(crop_xyz[:65], 17, [bad, 0.0, 1.0], axis=0).astype(np.float32)
+    dc = DeviceCloud.upload(cloud)
+    for stage in (lambda: dc.outlier_removal(8, 1.0), lambda: dc.normals(10), lambda: dc.knn(10)):
+        with pytest.raises(PPFError) as e:
+            stage()
+        assert e.value.status == _capi.PPF_ERR_INVALID
+    np.testing.assert_array_equal(dc.voxel_grid(0.003).xyz(), O.prep_voxel(cloud, 0.003))
+    assert len(DeviceCloud.upload(np.full((5, 3), np.nan, np.float32)).voxel_grid(0.003)) == 0
+
+
+def test_a_view_into_a_shared_block_as_input(frame):
+    """an output of ppf_prep_frame is a view at an offset of the frame's shared block; every stage takes it like a cloud
+    of its own, also after its siblings are gone"""
+    xyz, depth, (x, y, w, h), intr = frame
+    pairs = DeviceCloud.upload(xyz).prep_frame([(x, y, w, h), (x + 20, y + 20, w, h)], depth, intr)
+    assert len(pairs[0][0]) > 0                                  # so the second box's rows start past the block's first row
+    view = pairs[1][0]
+    rows, curv = view.download()
+    own = DeviceCloud.upload(rows)
+    assert len(view) > 1000
+
+    def same(a, b, curv=True):
+        (ra, ca), (rb, cb) = a.download(), b.download()
+        np.testing.assert_array_equal(ra, rb)
+        if curv:
+            np.testing.assert_array_equal(ca, cb)
+
+    # an upload carries no curvature: where a stage passes the view's own on, only the rows are compared, and the edge
+    # stage is checked against the view's own curvature first
+    box = (x + 30, y + 30, w // 2, h // 2)
+    assert 0 < len(view.crop(box, depth, intr)) < len(view)
+    same(view.crop(box, depth, intr), own.crop(box, depth, intr), curv=False)
+    same(view.voxel_grid(0.006), own.voxel_grid(0.006))
+    same(view.outlier_removal(50, 1.0), own.outlier_removal(50, 1.0), curv=False)
+    same(view.normals(30), own.normals(30))
+    np.testing.assert_array_equal(view.edges(0.03).rows(), rows[curv > 0.03])
+    same(view.normals(30).edges(0.03), own.normals(30).edges(0.03))
+    for got, want in zip(view.knn(10), own.knn(10)):
+        np.testing.assert_array_equal(got, want)
+    del pairs
+    gc.collect()
+    np.testing.assert_array_equal(view.to_mat().rows(), own.to_mat().rows())
+    np.testing.assert_array_equal(view.rows(), rows)
+
+
+def test_one_workgroup_loops_more_than_once():
+    """3,000 rows in one segment: more than one pass of a 256-thread workgroup with 8 rows per thread"""
+    pts, _ = D.plane_cloud(1333, seed=21, noise=0.0005)
+    sp, _ = D.sphere_cloud(1667, seed=22)
+    cloud = np.concatenate([pts, sp]).astype(np.float32)
+    assert cloud.shape[0] == 3000
+    np.testing.assert_array_equal(DeviceCloud.upload(cloud).voxel_grid(0.005).xyz(), O.prep_voxel(cloud, 0.005))
+    _neighbour_stages_equal_oracle(cloud, 50, 1.0, 30)

@@ -26,7 +26,8 @@
  *             ppf_depth_kernels.h  ppf_verify_kernels.h  ppf_render_kernels.h  ppf_select_kernels.h  ppf_refine_kernels.h
  *             ppf_register_kernels.h
  *   host      ppf_device_mem.h (errors, block cache)  ppf_host_common.h (scans, sorts, model / workspace structs)
- *             ppf_model_host.h  ppf_match_host.h  ppf_batch_host.h  ppf_icp_host.h  ppf_prep_host.h  ppf_frame_host.h
+ *             ppf_model_host.h  ppf_match_host.h  ppf_batch_host.h  ppf_icp_host.h  ppf_prep_host.h (the segmented
+ *             preparation stages; ppf_prep_* = one segment)  ppf_frame_host.h (ppf_prep_frame = their chain)
  *             ppf_match_frame_host.h  ppf_depth_host.h  ppf_posetable_host.h  ppf_verify_host.h  ppf_render_host.h
  *             ppf_select_host.h  ppf_refine_host.h  ppf_register_host.h  (the C-ABI)
  *
@@ -71,8 +72,8 @@
 #include "ppf_match_host.h"    /* C-ABI: workspaces, ppf_match_device, ppf_match, ppf_raw_votes, clustering */
 #include "ppf_batch_host.h"    /* C-ABI: crops x models */
 #include "ppf_icp_host.h"      /* row N2: ICP refinement, host side */
-#include "ppf_prep_host.h"     /* row N4: cloud stages, host side */
-#include "ppf_frame_host.h"    /* row N4 for all boxes of a frame: ppf_prep_frame */
+#include "ppf_prep_host.h"     /* row N4: the segmented cloud stages, FrameRun, ppf_prep_* (one segment each) */
+#include "ppf_frame_host.h"    /* row N4 for all boxes of a frame: ppf_prep_frame, the chain of those stages */
 #include "ppf_match_frame_host.h" /* match + ICP for all detections of a frame: ppf_match_frame */
 #include "ppf_depth_host.h"       /* the scene cloud from a depth image: ppf_cloud_from_depth */
 #include "ppf_posetable_host.h"   /* what the stages on a frame's pose table share: checks, render jobs, clears */

@@ -1,8 +1,10 @@
 /*
  * ppf_prep_host.h — host side of the stages that produce the matcher's input (row N4): the device-resident ppf_cloud,
- * ordered compaction, the uniform-grid kNN driver, the C-ABI entry points ppf_cloud_* / ppf_prep_* and the resident
- * ppf_match_clouds / ppf_icp_refine_clouds.  Kernels: ppf_prep_kernels.h.  Included by ppf_hip.hip (one translation
- * unit: shares DevBuf, fail(), HIPCHK, sort_segments and the kernels above).
+ * the segmented stage functions (crop, voxel grid, outlier removal, normals, edges, to-Mat over K segments of one
+ * concatenated cloud; frame_knn, frame_scan and frame_compact beneath them), the C-ABI entry points ppf_cloud_* and
+ * ppf_prep_* (each stage function with one segment) and the resident ppf_match_clouds / ppf_icp_refine_clouds.
+ * ppf_prep_frame chains the same functions for all boxes of a frame (ppf_frame_host.h).  Kernels: ppf_prep_kernels.h.
+ * Included by ppf_hip.hip (one translation unit: shares DevBuf, fail(), HIPCHK and the scan and radix-sort kernels).
  */
 /* ============================================================================================ */
 /* Pre-processing stages (row N4; kernels in ppf_prep_kernels.h)                                  */
@@ -33,32 +35,15 @@ namespace {
 
 inline dim3 grid_for(size_t items, int block) { return dim3((unsigned)std::max<size_t>((items + block - 1) / block, 1)); }
 
-ppf_status cloud_alloc(std::unique_ptr<ppf_cloud>& c, int n) {
-  c.reset(new ppf_cloud());
+ppf_status cloud_reserve(ppf_cloud* c, int n) {
   c->n = n;
   HIPCHK(c->rows.reserve((size_t)std::max(n, 1) * 6));
   HIPCHK(c->curv.reserve((size_t)std::max(n, 1)));
   return PPF_OK;
 }
-
-/* ordered compaction of the rows whose flag is set */
-ppf_status cloud_compact(const ppf_cloud* in, const DevBuf<uint32_t>& flags, ppf_cloud** out) {
-  const int n = in->n;
-  DevBuf<uint32_t> pos;
-  HIPCHK(pos.reserve((size_t)n + 1));
-  ppf_status s = device_exclusive_scan(flags.p, pos.p, (size_t)n + 1, nullptr);
-  if (s != PPF_OK) return s;
-  uint32_t kept = 0;
-  HIPCHK(hipMemcpy(&kept, pos.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost));
-  std::unique_ptr<ppf_cloud> c;
-  if ((s = cloud_alloc(c, (int)kept)) != PPF_OK) return s;
-  if (kept) {
-    k_prep_gather<<<grid_for(n, 256), dim3(256)>>>(in->rows.p, in->curv.p, n, flags.p, pos.p, c->rows.p, c->curv.p);
-    HIPCHK(hipGetLastError());
-  }
-  HIPCHK(hipDeviceSynchronize());
-  *out = c.release();
-  return PPF_OK;
+ppf_status cloud_alloc(std::unique_ptr<ppf_cloud>& c, int n) {
+  c.reset(new ppf_cloud());
+  return cloud_reserve(c.get(), n);
 }
 
 ppf_status prep_check(const char* who, const ppf_cloud* in, ppf_cloud** out) {
@@ -105,61 +90,314 @@ bool crop_planes(const int* box_xywh, const float* depth, int depth_rows, int de
   return true;
 }
 
-/* exact kNN lists of every point of the cloud: idx/d2 are [n][k], k <= min(n, KNN_MAX_K); q4 = xyz by original row */
-ppf_status cloud_knn(const ppf_cloud* in, int k, DevBuf<float4>& q4, DevBuf<int>& idx, DevBuf<float>& d2) {
-  const int n = in->n;
-  HIPCHK(q4.reserve((size_t)n));
-  HIPCHK(idx.reserve((size_t)n * k));
-  HIPCHK(d2.reserve((size_t)n * k));
-  DevBuf<float> scratch;
-  HIPCHK(scratch.reserve((size_t)n * 6));
-  k_icp_sample<<<grid_for(n, 256), dim3(256)>>>(in->rows.p, 6, 3, 1, n, scratch.p, q4.p);
-  /* grid over the bounding box: about sqrt(n)/6 cells along the longest side (a 3x3x3 cube of a surface-like cloud
-   * then holds a few hundred points), at most 128 */
-  DevBuf<uint32_t> mm;
-  HIPCHK(mm.reserve(6));
-  const uint32_t init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
-  HIPCHK(hipMemcpy(mm.p, init, sizeof(init), hipMemcpyHostToDevice));
-  k_prep_minmax<<<dim3(std::max(1u, std::min<unsigned>((unsigned)((n + 2047) / 2048), 256u))), dim3(256)>>>(in->rows.p, n, mm.p);
-  HIPCHK(hipGetLastError());
-  uint32_t h_mm[6];
-  HIPCHK(hipMemcpy(h_mm, mm.p, sizeof(h_mm), hipMemcpyDeviceToHost));
-  KnnGrid g;
-  float ext_max = 0.f;
-  for (int a = 0; a < 3; a++) {
-    const float lo = ordered_to_float(h_mm[a]), hi = ordered_to_float(h_mm[3 + a]);
-    if (!std::isfinite(lo) || !std::isfinite(hi))
-      return fail(PPF_ERR_INVALID, "neighbour search: the cloud holds non-finite points (crop or voxel-grid it first)");
-    g.lo[a] = lo;
-    ext_max = std::max(ext_max, hi - lo);
+/* ---- the segmented stages ---------------------------------------------------------------------------------------- */
+/* scratch of one call, from the block cache; it lives until the call returns (after the last read-back) */
+struct FrameRun {
+  int launches = 0, syncs = 0;
+  struct Holder {
+    virtual ~Holder() {}
+  };
+  template <class T>
+  struct Buf : Holder {
+    DevBuf<T> b;
+  };
+  std::vector<std::unique_ptr<Holder>> keep;
+  template <class T>
+  ppf_status get(size_t n, T** out) {
+    std::unique_ptr<Buf<T>> h(new Buf<T>());
+    HIPCHK(h->b.reserve(std::max<size_t>(n, 1)));
+    *out = h->b.p;
+    keep.push_back(std::move(h));
+    return PPF_OK;
   }
-  const int G = std::max(1, std::min(128, (int)(std::sqrt((double)n) / PPF_KNN_GDIV)));
-  g.h = ext_max > 0.f ? ext_max / (float)G : 1.0f;
-  g.inv_h = 1.0f / g.h;
-  size_t cells = 1;
-  for (int a = 0; a < 3; a++) {
-    const float hi = ordered_to_float(h_mm[3 + a]);
-    g.dim[a] = std::max(1, std::min(G + 1, (int)std::floor((hi - g.lo[a]) * g.inv_h) + 1));
-    cells *= (size_t)g.dim[a];
+  /* a blocking read-back (counted) */
+  ppf_status read(void* dst, const void* src, size_t bytes) {
+    syncs++;
+    HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return PPF_OK;
   }
-  DevBuf<uint32_t> keys, vals, keys2, vals2, starts, cell_count, cell_begin;
-  HIPCHK(keys.reserve(n)); HIPCHK(vals.reserve(n)); HIPCHK(keys2.reserve(n)); HIPCHK(vals2.reserve(n));
-  HIPCHK(cell_count.reserve(cells + 1)); HIPCHK(cell_begin.reserve(cells + 1));
-  HIPCHK(hipMemset(cell_count.p, 0, (cells + 1) * sizeof(uint32_t)));
-  k_prep_knn_keys<<<grid_for(n, 256), dim3(256)>>>(in->rows.p, n, g, keys.p, vals.p, cell_count.p);
+};
+
+#define FRAME_LAUNCH(fr, kern, grid, block, ...) \
+  do {                                           \
+    kern<<<(grid), (block)>>>(__VA_ARGS__);      \
+    (fr).launches++;                             \
+  } while (0)
+
+/* exclusive scan of n u32 in five launches whatever n is (device_exclusive_scan picks its launches by n and waits for
+ * its scratch; here the scratch lives in `fr`) */
+ppf_status frame_scan(FrameRun& fr, const uint32_t* in, uint32_t* out, size_t n) {
+  const size_t nb1 = std::max<size_t>((n + 1023) / 1024, 1), nb2 = (nb1 + 1023) / 1024;
+  uint32_t *s1, *s1x, *s2, *s2x;
+  ppf_status s;
+  if ((s = fr.get(nb1, &s1)) != PPF_OK || (s = fr.get(nb1, &s1x)) != PPF_OK || (s = fr.get(nb2, &s2)) != PPF_OK ||
+      (s = fr.get(nb2, &s2x)) != PPF_OK)
+    return s;
+  FRAME_LAUNCH(fr, k_scan_block, dim3((unsigned)nb1), dim3(256), in, out, s1, n);
+  FRAME_LAUNCH(fr, k_scan_block, dim3((unsigned)nb2), dim3(256), s1, s1x, s2, nb1);
+  FRAME_LAUNCH(fr, k_scan_one, dim3(1), dim3(1024), s2, s2x, nb2);
+  FRAME_LAUNCH(fr, k_scan_add, grid_for(nb1, 256), dim3(256), s1x, s2x, nb1);
+  FRAME_LAUNCH(fr, k_scan_add, grid_for(n, 256), dim3(256), out, s1x, n);
   HIPCHK(hipGetLastError());
-  ppf_status s = device_exclusive_scan(cell_count.p, cell_begin.p, cells + 1, nullptr);
-  if (s != PPF_OK) return s;
-  uint32_t n_runs = 0;
-  uint32_t* order = nullptr;
-  if ((s = sort_segments(keys, vals, keys2, vals2, n, (unsigned long long)cells, starts, &order, &n_runs, nullptr)) != PPF_OK) return s;
-  DevBuf<float4> pts;
-  HIPCHK(pts.reserve((size_t)n));
-  k_prep_knn_pack<<<grid_for(n, 256), dim3(256)>>>(in->rows.p, order, n, pts.p);
-  k_prep_knn<<<grid_for(n, KNN_WAVES), dim3(KNN_WAVES * 64)>>>(pts.p, cell_begin.p, g, n, k, idx.p, d2.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipDeviceSynchronize());
   return PPF_OK;
+}
+
+/* a segmented cloud on the device: K segments, contiguous and in order, in the first rows of `cap` (>= their total);
+ * the table {off, n} lives on the device, nb[s] is what the host knows: an upper bound of segment s's size */
+struct SegCloud {
+  const float* rows = nullptr; /* cap x 6 */
+  const float* curv = nullptr; /* cap */
+  int cap = 0;
+  const FrameSeg* seg = nullptr;
+  int K = 0;
+  std::vector<uint32_t> nb;
+};
+
+/* where a stage writes its n result rows: scratch of the run, or the fresh cloud `own` that the caller hands out */
+ppf_status frame_rows(FrameRun& fr, ppf_cloud* own, int n, float** rows, float** curv) {
+  ppf_status s;
+  if (!own) return (s = fr.get((size_t)n * 6, rows)) != PPF_OK ? s : fr.get(n, curv);
+  if ((s = cloud_reserve(own, n)) != PPF_OK) return s;
+  *rows = own->rows.p;
+  *curv = own->curv.p;
+  return PPF_OK;
+}
+
+/* SceneCropping of n unsegmented rows for K boxes: flags (box, point) -> one scan -> box-major ordered gather.  One
+ * read-back: the cropped total (out->cap) */
+ppf_status frame_crop(FrameRun& fr, const float* rows, const float* curv, int n, const CropPlanes* h_planes, int K, ppf_cloud* own,
+                      SegCloud* out) {
+  CropPlanes* planes;
+  uint32_t *cflags, *cpos;
+  FrameSeg* seg_c;
+  ppf_status s;
+  if ((s = fr.get(K, &planes)) != PPF_OK || (s = fr.get((size_t)K * n + 1, &cflags)) != PPF_OK ||
+      (s = fr.get((size_t)K * n + 1, &cpos)) != PPF_OK || (s = fr.get(K, &seg_c)) != PPF_OK)
+    return s;
+  HIPCHK(hipMemcpy(planes, h_planes, (size_t)K * sizeof(CropPlanes), hipMemcpyHostToDevice));
+  FRAME_LAUNCH(fr, k_frame_crop_flags, dim3(grid_for(n, 256).x, K), dim3(256), rows, n, K, planes, cflags);
+  HIPCHK(hipGetLastError());
+  if ((s = frame_scan(fr, cflags, cpos, (size_t)K * n + 1)) != PPF_OK) return s;
+  uint32_t n_crop = 0;
+  if ((s = fr.read(&n_crop, cpos + (size_t)K * n, sizeof(uint32_t))) != PPF_OK) return s;
+  const int C = (int)n_crop;
+  float *crows = nullptr, *ccurv = nullptr;
+  if ((C > 0 || own) && (s = frame_rows(fr, own, C, &crows, &ccurv)) != PPF_OK) return s;
+  if (C > 0) {
+    FRAME_LAUNCH(fr, k_frame_crop_gather, dim3(grid_for(n, 256).x, K), dim3(256), rows, curv, n, cflags, cpos, crows, ccurv, seg_c);
+    HIPCHK(hipGetLastError());
+  }
+  *out = SegCloud{crows, ccurv, C, seg_c, K, std::vector<uint32_t>((size_t)K, n_crop)};
+  return PPF_OK;
+}
+
+/* Subsampling of a non-empty segmented cloud: per-segment bounds and PCL grid, sort by (segment, cell) in fixed digit
+ * passes, runs, one thread per cell.  Non-finite rows take no part.  One read-back: {cells, finite points, overflow
+ * box, cells per box}.  *overflow = the first box whose cell index would overflow (then nothing is written), ~0 = none */
+ppf_status frame_voxel(FrameRun& fr, const SegCloud& in, double leaf, ppf_cloud* own, SegCloud* out, uint32_t* overflow) {
+  const int C = in.cap, K = in.K;
+  uint32_t *mm, *fin, *err, *k1, *k2, *v1, *v2, *lkey, *skey, *rflags, *runid, *starts, *d_head;
+  VoxelGridDims* dims;
+  FrameSeg* seg_v;
+  ppf_status s;
+  if ((s = fr.get((size_t)K * 6, &mm)) != PPF_OK || (s = fr.get(K, &fin)) != PPF_OK || (s = fr.get(1, &err)) != PPF_OK ||
+      (s = fr.get(K, &dims)) != PPF_OK || (s = fr.get(C, &k1)) != PPF_OK || (s = fr.get(C, &k2)) != PPF_OK ||
+      (s = fr.get(C, &v1)) != PPF_OK || (s = fr.get(C, &v2)) != PPF_OK || (s = fr.get(C, &lkey)) != PPF_OK ||
+      (s = fr.get(C, &skey)) != PPF_OK || (s = fr.get((size_t)C + 1, &rflags)) != PPF_OK || (s = fr.get((size_t)C + 1, &runid)) != PPF_OK ||
+      (s = fr.get(C, &starts)) != PPF_OK || (s = fr.get((size_t)K + 3, &d_head)) != PPF_OK || (s = fr.get(K, &seg_v)) != PPF_OK)
+    return s;
+  FRAME_LAUNCH(fr, k_frame_bounds, dim3(K), dim3(256), in.rows, in.seg, mm, fin);
+  FRAME_LAUNCH(fr, k_frame_voxel_dims, dim3(1), dim3(FRAME_MAX_BOXES), mm, fin, K, 1.0f / (float)leaf, dims, err);
+  FRAME_LAUNCH(fr, k_frame_voxel_keys, grid_for(C, 256), dim3(256), in.rows, C, in.seg, K, dims, k1, lkey, skey, v1);
+  HIPCHK(hipGetLastError());
+  /* stable LSD passes: the local cell index (< 2^31; non-finite points ~0), then the segment */
+  const int nblk = (C + RS_BLOCK - 1) / RS_BLOCK;
+  uint32_t *hist, *offs;
+  if ((s = fr.get((size_t)256 * nblk, &hist)) != PPF_OK || (s = fr.get((size_t)256 * nblk, &offs)) != PPF_OK) return s;
+  uint32_t *ka = k1, *va = v1, *kb = k2, *vb = v2;
+  for (int pass = 0; pass < 5; pass++) {
+    const int shift = pass < 4 ? pass * 8 : 0;
+    if (pass == 4) FRAME_LAUNCH(fr, k_frame_gather_u32, grid_for(C, 256), dim3(256), skey, va, C, ka);
+    FRAME_LAUNCH(fr, k_rs_hist, dim3(nblk), dim3(RS_BLOCK), ka, C, shift, nblk, hist);
+    HIPCHK(hipGetLastError());
+    if ((s = frame_scan(fr, hist, offs, (size_t)256 * nblk)) != PPF_OK) return s;
+    FRAME_LAUNCH(fr, k_rs_scatter, dim3(nblk), dim3(RS_BLOCK), ka, va, C, shift, nblk, offs, kb, vb);
+    HIPCHK(hipGetLastError());
+    std::swap(ka, kb); std::swap(va, vb);
+  }
+  FRAME_LAUNCH(fr, k_frame_voxel_runs, grid_for((size_t)C + 1, 256), dim3(256), va, lkey, skey, C, rflags);
+  HIPCHK(hipGetLastError());
+  if ((s = frame_scan(fr, rflags, runid, (size_t)C + 1)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_seg_starts, grid_for(C, 256), dim3(256), rflags, runid, C, starts);
+  FRAME_LAUNCH(fr, k_frame_voxel_table, dim3(1), dim3(FRAME_MAX_BOXES), fin, K, runid, err, seg_v, d_head);
+  HIPCHK(hipGetLastError());
+  std::vector<uint32_t> head((size_t)K + 3);
+  if ((s = fr.read(head.data(), d_head, head.size() * sizeof(uint32_t))) != PPF_OK) return s;
+  if ((*overflow = head[2]) != 0xFFFFFFFFu) return PPF_OK;
+  const int V = (int)head[0];
+  float *vrows, *vcurv;
+  if ((s = frame_rows(fr, own, V, &vrows, &vcurv)) != PPF_OK) return s;
+  if (V > 0) {
+    FRAME_LAUNCH(fr, k_prep_voxel_sum, grid_for(V, 64), dim3(64), in.rows, va, starts, V, (int)head[1], vrows, vcurv);
+    HIPCHK(hipGetLastError());
+  }
+  *out = SegCloud{vrows, vcurv, V, seg_v, K, std::vector<uint32_t>(head.begin() + 3, head.end())};
+  return PPF_OK;
+}
+
+/* grid cells a segment of up to n points can need (k_frame_knn_grids: at most G + 1 cells per axis) */
+size_t frame_knn_cells_bound(uint32_t n) {
+  const int G = std::max(1, std::min(128, (int)(std::sqrt((double)n) / PPF_KNN_GDIV)));
+  return (size_t)(G + 1) * (G + 1) * (G + 1);
+}
+
+/* exact neighbour lists of every row of a segmented cloud: idx / d2 [cap][kstride], segment-local indices, keff[s]
+ * entries per row (mode 0: SOR, k = meanK; mode 1: normals); q4 = xyz by row; fin[s] = segment s's finite rows.  A
+ * segment that holds a non-finite row is not searched (keff[s] = 0) */
+struct FrameKnn {
+  float4* q4;
+  int *idx, *keff;
+  float* d2;
+  uint32_t *chunk_base, *fin;
+};
+ppf_status frame_knn(FrameRun& fr, const SegCloud& in, int mode, int k, int kstride, FrameKnn* out) {
+  const int cap = in.cap, K = in.K;
+  size_t cells_cap = 0;
+  uint32_t nb_max = 0;
+  for (int s = 0; s < K; s++) {
+    cells_cap += frame_knn_cells_bound(in.nb[s]);
+    nb_max = std::max(nb_max, in.nb[s]);
+  }
+  /* a frame segment is a crop of about 10^4 rows, a single cloud may hold any number: 4,096 rows per workgroup */
+  const unsigned bounds_wgs = std::max(1u, std::min(32u, (nb_max + 4095u) / 4096u));
+  uint32_t *zeroed, *cell_base, *keys, *cell_begin;
+  KnnGrid* grids;
+  float4* pts;
+  ppf_status s;
+  if ((s = fr.get(cells_cap + 1 + (size_t)K * 7, &zeroed)) != PPF_OK || (s = fr.get(K, &grids)) != PPF_OK ||
+      (s = fr.get(K + 1, &cell_base)) != PPF_OK || (s = fr.get(K, &out->keff)) != PPF_OK || (s = fr.get(K + 1, &out->chunk_base)) != PPF_OK ||
+      (s = fr.get(cap, &keys)) != PPF_OK || (s = fr.get(cells_cap + 1, &cell_begin)) != PPF_OK || (s = fr.get(cap, &pts)) != PPF_OK || (s = fr.get(cap, &out->q4)) != PPF_OK ||
+      (s = fr.get((size_t)cap * kstride, &out->idx)) != PPF_OK || (s = fr.get((size_t)cap * kstride, &out->d2)) != PPF_OK)
+    return s;
+  /* one fill zeroes the cell counts and, behind them, the bounds that the workgroups of a segment combine */
+  uint32_t *const cell_count = zeroed, *const mm = zeroed + cells_cap + 1;
+  out->fin = mm + (size_t)K * 6;
+  FRAME_LAUNCH(fr, k_frame_fill_u32, grid_for(cells_cap + 1 + (size_t)K * 7, 256), dim3(256), zeroed, cells_cap + 1 + (size_t)K * 7, 0u);
+  FRAME_LAUNCH(fr, k_frame_bounds, dim3(K, bounds_wgs), dim3(256), in.rows, in.seg, mm, out->fin);
+  FRAME_LAUNCH(fr, k_frame_knn_grids, dim3(1), dim3(FRAME_MAX_BOXES), mm, out->fin, in.seg, K, mode, k, (double)PPF_KNN_GDIV, grids, cell_base,
+               out->keff, out->chunk_base);
+  FRAME_LAUNCH(fr, k_frame_knn_keys, grid_for(cap, 256), dim3(256), in.rows, cap, in.seg, K, grids, cell_base, out->keff, keys, cell_count);
+  HIPCHK(hipGetLastError());
+  if ((s = frame_scan(fr, cell_count, cell_begin, cells_cap + 1)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_frame_knn_scatter, grid_for(cap, 256), dim3(256), in.rows, cap, in.seg, K, keys, cell_begin, cell_count, pts, out->q4);
+  FRAME_LAUNCH(fr, k_frame_knn, grid_for(cap, KNN_WAVES), dim3(KNN_WAVES * 64), pts, cell_begin, grids, cell_base, in.seg, K, out->keff, cap,
+               kstride, out->idx, out->d2);
+  HIPCHK(hipGetLastError());
+  return PPF_OK;
+}
+
+/* segmented ordered compaction of the rows whose flag is set (flags[0..cap]).  Scratch of the run is sized for the
+ * worst case; a cloud of its own takes what is kept, at the price of one read-back */
+ppf_status frame_compact(FrameRun& fr, const SegCloud& in, const uint32_t* flags, ppf_cloud* own, SegCloud* out) {
+  uint32_t* pos;
+  FrameSeg* seg_out;
+  float *orows, *ocurv;
+  ppf_status s;
+  if ((s = fr.get((size_t)in.cap + 1, &pos)) != PPF_OK || (s = fr.get(in.K, &seg_out)) != PPF_OK) return s;
+  if ((s = frame_scan(fr, flags, pos, (size_t)in.cap + 1)) != PPF_OK) return s;
+  uint32_t kept = (uint32_t)in.cap;
+  if (own && (s = fr.read(&kept, pos + in.cap, sizeof(uint32_t))) != PPF_OK) return s;
+  if ((s = frame_rows(fr, own, (int)kept, &orows, &ocurv)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_frame_gather, grid_for(in.cap, 256), dim3(256), in.rows, in.curv, in.cap, flags, pos, in.seg, in.K, orows, ocurv, seg_out);
+  HIPCHK(hipGetLastError());
+  *out = SegCloud{orows, ocurv, (int)kept, seg_out, in.K, in.nb};
+  return PPF_OK;
+}
+
+/* OutlierProcessing: kNN(meanK + 1) per segment, per-segment chunk sums and threshold, compaction.  *fin (optional) =
+ * the finite rows per segment, on the device */
+ppf_status frame_outliers(FrameRun& fr, const SegCloud& in, int mean_k, double stddev_mul, ppf_cloud* own, SegCloud* out,
+                          const uint32_t** fin) {
+  const int V = in.cap, K = in.K, cap_chunks = (V + 63) / 64 + K;
+  FrameKnn nn;
+  float* dist;
+  uint32_t* oflags;
+  double *parts, *thr;
+  ppf_status s;
+  if ((s = frame_knn(fr, in, 0, mean_k, mean_k + 1, &nn)) != PPF_OK) return s;
+  if ((s = fr.get(V, &dist)) != PPF_OK || (s = fr.get((size_t)cap_chunks * 2, &parts)) != PPF_OK || (s = fr.get(K, &thr)) != PPF_OK ||
+      (s = fr.get((size_t)V + 1, &oflags)) != PPF_OK)
+    return s;
+  FRAME_LAUNCH(fr, k_frame_sor_dist, grid_for(V, 256), dim3(256), nn.d2, V, in.seg, K, nn.keff, mean_k, dist);
+  FRAME_LAUNCH(fr, k_frame_sor_chunks, grid_for(cap_chunks, 64), dim3(64), dist, cap_chunks, in.seg, K, nn.chunk_base, parts);
+  FRAME_LAUNCH(fr, k_frame_sor_threshold, dim3(K), dim3(64), parts, in.seg, nn.chunk_base, stddev_mul, thr);
+  FRAME_LAUNCH(fr, k_frame_sor_flags, grid_for((size_t)V + 1, 256), dim3(256), dist, V, in.seg, K, thr, oflags);
+  HIPCHK(hipGetLastError());
+  if (fin) *fin = nn.fin;
+  return frame_compact(fr, in, oflags, own, out);
+}
+
+/* NormalEstimation: kNN(min(k, n_s)) per segment, plane fits; the rows keep their places */
+ppf_status frame_normals(FrameRun& fr, const SegCloud& in, int k, ppf_cloud* own, SegCloud* out, const uint32_t** fin) {
+  FrameKnn nn;
+  float *nrows, *ncurv;
+  ppf_status s;
+  if ((s = frame_knn(fr, in, 1, k, k, &nn)) != PPF_OK) return s;
+  if ((s = frame_rows(fr, own, in.cap, &nrows, &ncurv)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_frame_normals, grid_for(in.cap, 64), dim3(64), in.rows, in.cap, in.seg, in.K, nn.idx, k, nn.keff, nn.q4, nrows, ncurv);
+  HIPCHK(hipGetLastError());
+  if (fin) *fin = nn.fin;
+  *out = in;
+  out->rows = nrows;
+  out->curv = ncurv;
+  return PPF_OK;
+}
+
+/* EdgeExtraction: segmented compaction on curvature */
+ppf_status frame_edges(FrameRun& fr, const SegCloud& in, float curvature_threshold, ppf_cloud* own, SegCloud* out) {
+  uint32_t* eflags;
+  ppf_status s;
+  if ((s = fr.get((size_t)in.cap + 1, &eflags)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_frame_curv_flags, grid_for((size_t)in.cap + 1, 256), dim3(256), in.curv, in.cap, in.seg, in.K, curvature_threshold, eflags);
+  HIPCHK(hipGetLastError());
+  return frame_compact(fr, in, eflags, own, out);
+}
+
+/* PointCloudXYZNormalToMat: rows with the normals re-normalised, the curvature beside them */
+ppf_status frame_to_mat(FrameRun& fr, const SegCloud& in, float* out_rows, float* out_curv) {
+  FRAME_LAUNCH(fr, k_frame_to_mat, grid_for(in.cap, 256), dim3(256), in.rows, in.curv, in.cap, in.seg, in.K, out_rows, out_curv);
+  HIPCHK(hipGetLastError());
+  return PPF_OK;
+}
+
+/* ---- one cloud = one segment ----------------------------------------------------------------------------------- */
+/* the table {0, n} over a handle's rows (a view into a shared block included: only rows.p / curv.p are read) */
+ppf_status one_segment(FrameRun& fr, const ppf_cloud* in, SegCloud* c) {
+  FrameSeg* seg;
+  ppf_status s = fr.get(1, &seg);
+  if (s != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_frame_fill_u32, dim3(1), dim3(256), &seg->off, (size_t)1, 0u); /* two fills cost less than a blocking upload */
+  FRAME_LAUNCH(fr, k_frame_fill_u32, dim3(1), dim3(256), &seg->n, (size_t)1, (uint32_t)in->n);
+  HIPCHK(hipGetLastError());
+  *c = SegCloud{in->rows.p, in->curv.p, in->n, seg, 1, std::vector<uint32_t>(1, (uint32_t)in->n)};
+  return PPF_OK;
+}
+
+/* the segmented search skips a segment that holds non-finite rows; a single cloud reports it.  The read-back is also
+ * the stage's closing wait for the device */
+ppf_status prep_all_finite(FrameRun& fr, const uint32_t* fin, int n) {
+  uint32_t finite = 0;
+  ppf_status s = fr.read(&finite, fin, sizeof(uint32_t));
+  if (s != PPF_OK) return s;
+  if (finite != (uint32_t)n) return fail(PPF_ERR_INVALID, "neighbour search: the cloud holds non-finite points (crop or voxel-grid it first)");
+  return PPF_OK;
+}
+
+ppf_status prep_empty(ppf_cloud** out) {
+  std::unique_ptr<ppf_cloud> c;
+  ppf_status s = cloud_alloc(c, 0);
+  if (s == PPF_OK) *out = c.release();
+  return s;
 }
 
 }  // namespace
@@ -210,6 +448,9 @@ ppf_status ppf_cloud_device_rows(const ppf_cloud* c, const float** d_rows6, int*
   return PPF_OK;
 }
 
+/* Each stage below is the one-segment case of the segmented stage above: the table is {0, n} over the handle's rows,
+ * scratch comes from a FrameRun, and the last kernel writes into the fresh cloud that is returned. */
+
 /* SceneCropping (CloudProcessing.h:263-339) for one bounding box */
 ppf_status ppf_prep_crop(const ppf_cloud* in, const int* box_xywh, const float* depth, int depth_rows, int depth_cols,
                          const double* intr, ppf_cloud** out) {
@@ -218,12 +459,14 @@ ppf_status ppf_prep_crop(const ppf_cloud* in, const int* box_xywh, const float* 
   if (!box_xywh || !depth || !intr || depth_rows <= 0 || depth_cols <= 0) return fail(PPF_ERR_INVALID, "ppf_prep_crop: bad argument");
   CropPlanes pl;
   if (!crop_planes(box_xywh, depth, depth_rows, depth_cols, intr, &pl)) return fail(PPF_ERR_INVALID, "ppf_prep_crop: box outside the depth image");
-  DevBuf<uint32_t> flags;
-  HIPCHK(flags.reserve((size_t)in->n + 1));
-  HIPCHK(hipMemset(flags.p + in->n, 0, sizeof(uint32_t)));
-  if (in->n) k_prep_crop_flags<<<grid_for(in->n, 256), dim3(256)>>>(in->rows.p, in->n, pl, flags.p);
-  HIPCHK(hipGetLastError());
-  return cloud_compact(in, flags, out);
+  if (in->n == 0) return prep_empty(out);
+  std::unique_ptr<ppf_cloud> c(new ppf_cloud());
+  FrameRun fr;
+  SegCloud res;
+  if ((s = frame_crop(fr, in->rows.p, in->curv.p, in->n, &pl, 1, c.get(), &res)) != PPF_OK) return s;
+  HIPCHK(hipDeviceSynchronize());
+  *out = c.release();
+  return PPF_OK;
 }
 
 /* Subsampling (:361-380): pcl::VoxelGrid with a cubic leaf */
@@ -231,49 +474,13 @@ ppf_status ppf_prep_voxel_grid(const ppf_cloud* in, double leaf, ppf_cloud** out
   ppf_status s = prep_check("ppf_prep_voxel_grid", in, out);
   if (s != PPF_OK) return s;
   if (!((float)leaf > 0.f)) return fail(PPF_ERR_INVALID, "ppf_prep_voxel_grid: leaf size must be positive");
-  /* non-finite points do not take part */
-  DevBuf<uint32_t> fin;
-  HIPCHK(fin.reserve((size_t)in->n + 1));
-  HIPCHK(hipMemset(fin.p + in->n, 0, sizeof(uint32_t)));
-  if (in->n) k_prep_finite_flags<<<grid_for(in->n, 256), dim3(256)>>>(in->rows.p, in->n, fin.p);
-  ppf_cloud* dense_raw = nullptr;
-  if ((s = cloud_compact(in, fin, &dense_raw)) != PPF_OK) return s;
-  std::unique_ptr<ppf_cloud> dense(dense_raw);
-  const int n = dense->n;
-  std::unique_ptr<ppf_cloud> c;
-  if (n == 0) {
-    if ((s = cloud_alloc(c, 0)) != PPF_OK) return s;
-    *out = c.release();
-    return PPF_OK;
-  }
-  DevBuf<uint32_t> mm, keys, vals, keys2, vals2, starts;
-  HIPCHK(mm.reserve(6));
-  const uint32_t init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
-  HIPCHK(hipMemcpy(mm.p, init, sizeof(init), hipMemcpyHostToDevice));
-  k_prep_minmax<<<dim3(std::max(1u, std::min<unsigned>((unsigned)((n + 2047) / 2048), 256u))), dim3(256)>>>(dense->rows.p, n, mm.p);
-  HIPCHK(hipGetLastError());
-  uint32_t h_mm[6];
-  HIPCHK(hipMemcpy(h_mm, mm.p, sizeof(h_mm), hipMemcpyDeviceToHost));
-  VoxelGridDims g;
-  g.inv_leaf = 1.0f / (float)leaf;
-  long long cells = 1;
-  for (int k = 0; k < 3; k++) {
-    const float lo = ordered_to_float(h_mm[k]), hi = ordered_to_float(h_mm[3 + k]);
-    g.min_b[k] = (int)std::floor(lo * g.inv_leaf);
-    const int max_b = (int)std::floor(hi * g.inv_leaf);
-    g.div_b[k] = max_b - g.min_b[k] + 1;
-    cells *= g.div_b[k];
-    if (cells > 0x7fffffffLL) return fail(PPF_ERR_INVALID, "ppf_prep_voxel_grid: leaf size is too small for the cloud (index overflow)");
-  }
-  HIPCHK(keys.reserve(n)); HIPCHK(vals.reserve(n)); HIPCHK(keys2.reserve(n)); HIPCHK(vals2.reserve(n));
-  k_prep_voxel_keys<<<grid_for(n, 256), dim3(256)>>>(dense->rows.p, n, g, keys.p, vals.p);
-  HIPCHK(hipGetLastError());
-  uint32_t n_cells = 0;
-  uint32_t* va = nullptr;
-  if ((s = sort_segments(keys, vals, keys2, vals2, n, (unsigned long long)cells, starts, &va, &n_cells, nullptr)) != PPF_OK) return s;
-  if ((s = cloud_alloc(c, (int)n_cells)) != PPF_OK) return s;
-  k_prep_voxel_sum<<<grid_for(n_cells, 64), dim3(64)>>>(dense->rows.p, va, starts.p, (int)n_cells, n, c->rows.p, c->curv.p);
-  HIPCHK(hipGetLastError());
+  if (in->n == 0) return prep_empty(out);
+  std::unique_ptr<ppf_cloud> c(new ppf_cloud());
+  FrameRun fr;
+  SegCloud seg, res;
+  uint32_t overflow;
+  if ((s = one_segment(fr, in, &seg)) != PPF_OK || (s = frame_voxel(fr, seg, leaf, c.get(), &res, &overflow)) != PPF_OK) return s;
+  if (overflow != 0xFFFFFFFFu) return fail(PPF_ERR_INVALID, "ppf_prep_voxel_grid: leaf size is too small for the cloud (index overflow)");
   HIPCHK(hipDeviceSynchronize());
   *out = c.release();
   return PPF_OK;
@@ -285,13 +492,17 @@ ppf_status ppf_prep_knn(const ppf_cloud* in, int k, int* idx, float* d2) {
   if (!have_device()) return fail(PPF_ERR_HIP, "ppf_prep_knn: no HIP device (this engine has no CPU fallback)");
   const int n = in->n, ke = std::min(k, n);
   if (n == 0) return PPF_OK;
-  DevBuf<float4> q4; DevBuf<int> d_idx; DevBuf<float> d_d2;
-  ppf_status s = cloud_knn(in, ke, q4, d_idx, d_d2);
-  if (s != PPF_OK) return s;
+  FrameRun fr;
+  SegCloud seg;
+  FrameKnn nn;
+  ppf_status s;
+  if ((s = one_segment(fr, in, &seg)) != PPF_OK || (s = frame_knn(fr, seg, 1, k, ke, &nn)) != PPF_OK ||
+      (s = prep_all_finite(fr, nn.fin, n)) != PPF_OK)
+    return s;
   std::vector<int> hi((size_t)n * ke);
   std::vector<float> hd((size_t)n * ke);
-  HIPCHK(hipMemcpy(hi.data(), d_idx.p, hi.size() * sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(hd.data(), d_d2.p, hd.size() * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(hi.data(), nn.idx, hi.size() * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(hd.data(), nn.d2, hd.size() * sizeof(float), hipMemcpyDeviceToHost));
   for (int i = 0; i < n; i++)
     for (int m = 0; m < k; m++) {
       idx[(size_t)i * k + m] = m < ke ? hi[(size_t)i * ke + m] : -1;
@@ -305,26 +516,19 @@ ppf_status ppf_prep_outlier_removal(const ppf_cloud* in, int mean_k, double stdd
   ppf_status s = prep_check("ppf_prep_outlier_removal", in, out);
   if (s != PPF_OK) return s;
   if (mean_k < 1 || mean_k + 1 > KNN_MAX_K) return fail(PPF_ERR_INVALID, "ppf_prep_outlier_removal: meanK must be in [1, %d]", KNN_MAX_K - 1);
-  const int n = in->n;
-  DevBuf<uint32_t> flags;
-  HIPCHK(flags.reserve((size_t)n + 1));
-  HIPCHK(hipMemset(flags.p + n, 0, sizeof(uint32_t)));
-  if (n) {
-    DevBuf<float4> q4; DevBuf<int> idx; DevBuf<float> d2, dist;
-    DevBuf<double> parts, thr;
-    const int valid = n > mean_k ? 1 : 0;
-    if (valid && (s = cloud_knn(in, mean_k + 1, q4, idx, d2)) != PPF_OK) return s;
-    HIPCHK(dist.reserve(n));
-    HIPCHK(parts.reserve((size_t)((n + 63) / 64) * 2));
-    HIPCHK(thr.reserve(1));
-    k_prep_sor_dist<<<grid_for(n, 256), dim3(256)>>>(d2.p, n, mean_k, valid, dist.p);
-    k_prep_sor_chunks<<<grid_for((n + 63) / 64, 64), dim3(64)>>>(dist.p, n, parts.p);
-    k_prep_sor_threshold<<<dim3(1), dim3(64)>>>(parts.p, n, stddev_mul, thr.p);
-    k_prep_sor_flags<<<grid_for(n, 256), dim3(256)>>>(dist.p, n, thr.p, flags.p);
-    HIPCHK(hipGetLastError());
+  if (in->n == 0) return prep_empty(out);
+  std::unique_ptr<ppf_cloud> c(new ppf_cloud());
+  FrameRun fr;
+  SegCloud seg, res;
+  const uint32_t* fin;
+  if ((s = one_segment(fr, in, &seg)) != PPF_OK || (s = frame_outliers(fr, seg, mean_k, stddev_mul, c.get(), &res, &fin)) != PPF_OK) return s;
+  if (in->n > mean_k) {
+    if ((s = prep_all_finite(fr, fin, in->n)) != PPF_OK) return s;
+  } else { /* nothing is measured and every row is kept; the search's launches still run, with k_eff = 0 and no cells */
     HIPCHK(hipDeviceSynchronize());
   }
-  return cloud_compact(in, flags, out);
+  *out = c.release();
+  return PPF_OK;
 }
 
 /* NormalEstimation (:381-405): k nearest neighbours, plane fit, normal towards the camera, curvature */
@@ -332,18 +536,14 @@ ppf_status ppf_prep_normals(const ppf_cloud* in, int k, ppf_cloud** out) {
   ppf_status s = prep_check("ppf_prep_normals", in, out);
   if (s != PPF_OK) return s;
   if (k < 1 || k > KNN_MAX_K) return fail(PPF_ERR_INVALID, "ppf_prep_normals: k must be in [1, %d]", KNN_MAX_K);
-  const int n = in->n;
-  std::unique_ptr<ppf_cloud> c;
-  if ((s = cloud_alloc(c, n)) != PPF_OK) return s;
-  if (n) {
-    HIPCHK(hipMemcpy(c->rows.p, in->rows.p, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToDevice));
-    DevBuf<float4> q4; DevBuf<int> idx; DevBuf<float> d2;
-    const int ke = std::min(k, n);
-    if ((s = cloud_knn(in, ke, q4, idx, d2)) != PPF_OK) return s;
-    k_prep_normals<<<grid_for(n, 64), dim3(64)>>>(c->rows.p, c->curv.p, n, idx.p, ke, q4.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-  }
+  if (in->n == 0) return prep_empty(out);
+  std::unique_ptr<ppf_cloud> c(new ppf_cloud());
+  FrameRun fr;
+  SegCloud seg, res;
+  const uint32_t* fin;
+  if ((s = one_segment(fr, in, &seg)) != PPF_OK || (s = frame_normals(fr, seg, k, c.get(), &res, &fin)) != PPF_OK ||
+      (s = prep_all_finite(fr, fin, in->n)) != PPF_OK)
+    return s;
   *out = c.release();
   return PPF_OK;
 }
@@ -352,26 +552,28 @@ ppf_status ppf_prep_normals(const ppf_cloud* in, int k, ppf_cloud** out) {
 ppf_status ppf_prep_edges(const ppf_cloud* in, float curvature_threshold, ppf_cloud** out) {
   ppf_status s = prep_check("ppf_prep_edges", in, out);
   if (s != PPF_OK) return s;
-  DevBuf<uint32_t> flags;
-  HIPCHK(flags.reserve((size_t)in->n + 1));
-  HIPCHK(hipMemset(flags.p + in->n, 0, sizeof(uint32_t)));
-  if (in->n) k_prep_curv_flags<<<grid_for(in->n, 256), dim3(256)>>>(in->curv.p, in->n, curvature_threshold, flags.p);
-  HIPCHK(hipGetLastError());
-  return cloud_compact(in, flags, out);
+  if (in->n == 0) return prep_empty(out);
+  std::unique_ptr<ppf_cloud> c(new ppf_cloud());
+  FrameRun fr;
+  SegCloud seg, res;
+  if ((s = one_segment(fr, in, &seg)) != PPF_OK || (s = frame_edges(fr, seg, curvature_threshold, c.get(), &res)) != PPF_OK) return s;
+  HIPCHK(hipDeviceSynchronize());
+  *out = c.release();
+  return PPF_OK;
 }
 
 /* PointCloudXYZNormalToMat (:163-190): the N x 6 rows the detector consumes, normals re-normalised */
 ppf_status ppf_prep_to_mat(const ppf_cloud* in, ppf_cloud** out) {
   ppf_status s = prep_check("ppf_prep_to_mat", in, out);
   if (s != PPF_OK) return s;
+  if (in->n == 0) return prep_empty(out);
   std::unique_ptr<ppf_cloud> c;
-  if ((s = cloud_alloc(c, in->n)) != PPF_OK) return s;
-  if (in->n) {
-    k_prep_to_mat<<<grid_for(in->n, 256), dim3(256)>>>(in->rows.p, in->n, c->rows.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(c->curv.p, in->curv.p, (size_t)in->n * sizeof(float), hipMemcpyDeviceToDevice));
-    HIPCHK(hipDeviceSynchronize());
-  }
+  FrameRun fr;
+  SegCloud seg;
+  if ((s = cloud_alloc(c, in->n)) != PPF_OK || (s = one_segment(fr, in, &seg)) != PPF_OK ||
+      (s = frame_to_mat(fr, seg, c->rows.p, c->curv.p)) != PPF_OK)
+    return s;
+  HIPCHK(hipDeviceSynchronize());
   *out = c.release();
   return PPF_OK;
 }

@@ -4,11 +4,13 @@
  * NormalEstimation :381-405, EdgeExtraction :406-427, PointCloudXYZNormalToMat :163-190).  Included by ppf_hip.hip.
  *
  * The arithmetic and every order-dependent choice is the one oracle/ppf_prep_oracle.cpp freezes; results are
- * bit-identical to it.  Clouds are device rows `x y z nx ny nz` (pitch 6) plus a curvature array.
+ * bit-identical to it.  Clouds are device rows `x y z nx ny nz` (pitch 6) plus a curvature array.  There is one kernel
+ * family: every stage works on K <= 256 segments of one concatenated cloud (ppf_prep_frame), and a single cloud
+ * (ppf_prep_crop ... ppf_prep_to_mat) is the case K = 1.  The device bodies come first, the kernels after them.
  *   crop / outlier / edge : per-point predicate -> flags -> exclusive scan -> ordered gather (HBM streaming, 28 B/pt)
- *   voxel grid            : finite min/max -> PCL's cell index -> stable LSD radix sort (shared with the sampler) ->
- *                           one thread per cell, float sums in point order
- *   k nearest neighbours  : uniform grid (cells sorted by the same radix sort), ONE WAVE per query, cube of cells
+ *   voxel grid            : finite min/max -> PCL's cell index -> stable LSD radix sort (passes shared with the
+ *                           sampler) -> one thread per cell, float sums in point order
+ *   k nearest neighbours  : uniform grid (counting sort into cell order), ONE WAVE per query, cube of cells
  *                           grown until the k-th distance is provably final; the k <= 64 best (distance bits, index)
  *                           keys live one per lane and 64 candidates at a time are merged in by a register bitonic
  *                           network.  Exact: equals the oracle's exhaustive search bit for bit.
@@ -35,30 +37,6 @@ __device__ __forceinline__ bool prep_crop_inside(const float* p, const CropPlane
   for (int f = 0; f < 4; f++) in = in && (pl.n[f][0] * (double)p[0] + pl.n[f][1] * (double)p[1] + pl.n[f][2] * (double)p[2]) >= 0.0;
   return in;
 }
-__global__ __launch_bounds__(256) void k_prep_crop_flags(const float* __restrict__ rows, int n, CropPlanes pl, uint32_t* __restrict__ flags) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  flags[i] = prep_crop_inside(rows + (size_t)i * 6, pl) ? 1u : 0u;
-}
-__global__ __launch_bounds__(256) void k_prep_finite_flags(const float* __restrict__ rows, int n, uint32_t* __restrict__ flags) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) flags[i] = prep_finite3(rows + (size_t)i * 6) ? 1u : 0u;
-}
-__global__ __launch_bounds__(256) void k_prep_curv_flags(const float* __restrict__ curv, int n, float thr, uint32_t* __restrict__ flags) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) flags[i] = curv[i] > thr ? 1u : 0u;
-}
-/* ordered gather of the flagged rows (pos = exclusive scan of flags) */
-__global__ __launch_bounds__(256) void k_prep_gather(const float* __restrict__ rows, const float* __restrict__ curv, int n,
-                                                     const uint32_t* __restrict__ flags, const uint32_t* __restrict__ pos,
-                                                     float* __restrict__ out_rows, float* __restrict__ out_curv) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || !flags[i]) return;
-  const uint32_t o = pos[i];
-#pragma unroll
-  for (int k = 0; k < 6; k++) out_rows[(size_t)o * 6 + k] = rows[(size_t)i * 6 + k];
-  out_curv[o] = curv[i];
-}
 
 /* rows of `cols` floats at `stride` -> packed rows of 6 (+ zero curvature) */
 __global__ __launch_bounds__(256) void k_prep_pack(const float* __restrict__ src, int n, int stride, int noff, int cols, float* __restrict__ rows,
@@ -74,41 +52,6 @@ __global__ __launch_bounds__(256) void k_prep_pack(const float* __restrict__ src
 }
 
 /* ---- voxel grid ------------------------------------------------------------------------------------------- */
-/* mm[0..2] = min, mm[3..5] = max as order-preserving uints; input must be finite */
-__global__ __launch_bounds__(256) void k_prep_minmax(const float* __restrict__ rows, int n, uint32_t* __restrict__ mm) {
-  uint32_t lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0, 0, 0};
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      const uint32_t o = float_to_ordered(rows[(size_t)i * 6 + k]);
-      lo[k] = min(lo[k], o);
-      hi[k] = max(hi[k], o);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      lo[k] = min(lo[k], (uint32_t)__shfl_down(lo[k], o));
-      hi[k] = max(hi[k], (uint32_t)__shfl_down(hi[k], o));
-    }
-  }
-  /* one set of atomics per workgroup, and few workgroups (the host caps the grid): six addresses serve them one at a time, and
-   * 560 waves' worth were 35 of this kernel's 41 us */
-  __shared__ uint32_t s_mm[4][6];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) { s_mm[wave][k] = lo[k]; s_mm[wave][3 + k] = hi[k]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    const int k = threadIdx.x;
-    uint32_t v = s_mm[0][k];
-    for (int w = 1; w < 4; w++) v = k < 3 ? min(v, s_mm[w][k]) : max(v, s_mm[w][k]);
-    if (k < 3) atomicMin(&mm[k], v); else atomicMax(&mm[k], v);
-  }
-}
 struct VoxelGridDims {
   float inv_leaf;
   int min_b[3], div_b[3];
@@ -119,13 +62,6 @@ __device__ __forceinline__ uint32_t prep_voxel_key(const float* p, const VoxelGr
   const int i1 = ppf_f2i(floorf(p[1] * g.inv_leaf) - (float)g.min_b[1]);
   const int i2 = ppf_f2i(floorf(p[2] * g.inv_leaf) - (float)g.min_b[2]);
   return (uint32_t)(i0 + i1 * g.div_b[0] + i2 * g.div_b[0] * g.div_b[1]);
-}
-__global__ __launch_bounds__(256) void k_prep_voxel_keys(const float* __restrict__ rows, int n, VoxelGridDims g, uint32_t* __restrict__ keys,
-                                                         uint32_t* __restrict__ vals) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  keys[i] = prep_voxel_key(rows + (size_t)i * 6, g);
-  vals[i] = (uint32_t)i;
 }
 /* one thread per occupied cell: float sums in ascending point order, divided by the float count */
 __global__ __launch_bounds__(64) void k_prep_voxel_sum(const float* __restrict__ rows, const uint32_t* __restrict__ vals,
@@ -162,31 +98,12 @@ __device__ __forceinline__ void knn_cell(const KnnGrid& g, float x, float y, flo
   c[1] = min(max(ppf_f2i(floorf((y - g.lo[1]) * g.inv_h)), 0), g.dim[1] - 1);
   c[2] = min(max(ppf_f2i(floorf((z - g.lo[2]) * g.inv_h)), 0), g.dim[2] - 1);
 }
-__global__ __launch_bounds__(256) void k_prep_knn_keys(const float* __restrict__ rows, int n, KnnGrid g, uint32_t* __restrict__ keys,
-                                                       uint32_t* __restrict__ vals, uint32_t* __restrict__ cell_count) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  int c[3];
-  knn_cell(g, rows[(size_t)i * 6], rows[(size_t)i * 6 + 1], rows[(size_t)i * 6 + 2], c);
-  const uint32_t key = (uint32_t)((c[2] * g.dim[1] + c[1]) * g.dim[0] + c[0]);
-  keys[i] = key;
-  vals[i] = (uint32_t)i;
-  atomicAdd(&cell_count[key], 1u);
-}
-/* pts[s] = xyz of the s-th point in cell order, w = its original index */
-__global__ __launch_bounds__(256) void k_prep_knn_pack(const float* __restrict__ rows, const uint32_t* __restrict__ order, int n,
-                                                       float4* __restrict__ pts) {
-  const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= n) return;
-  const uint32_t i = order[s];
-  pts[s] = make_float4(rows[(size_t)i * 6], rows[(size_t)i * 6 + 1], rows[(size_t)i * 6 + 2], __uint_as_float(i));
-}
 /* bitonic compare-exchange across lanes */
 __device__ __forceinline__ unsigned long long knn_cex(unsigned long long key, int stride, bool take_min) {
   const unsigned long long other = __shfl_xor(key, stride);
   return take_min ? (key < other ? key : other) : (key < other ? other : key);
 }
-/* ONE WAVE PER QUERY.  idx/d2: [n][k] at the ORIGINAL row of each point, ascending (d2, index); k <= 64.
+/* ONE WAVE PER QUERY: its k <= 64 nearest points, ascending (d2, index).
  * The wave reads 64 candidates per step (coalesced within a row of cells); its current k best keys live one per
  * lane, ascending by lane (lanes >= k hold the sentinel).  A step whose candidates all fail the k-th key costs one
  * ballot; otherwise the 64 new keys are bitonic-sorted across the lanes (21 exchanges) and merged with the list
@@ -239,19 +156,6 @@ __device__ __forceinline__ unsigned long long prep_knn_search(const float4* __re
   }
   return best; /* lane m holds the m-th best key (m < k), or ~0 */
 }
-__global__ __launch_bounds__(256) void k_prep_knn(const float4* __restrict__ pts, const uint32_t* __restrict__ cell_begin, KnnGrid g,
-                                                  int n, int k, int* __restrict__ idx_out, float* __restrict__ d2_out) {
-  const int lane = threadIdx.x & 63;
-  const int s = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); /* wave-uniform */
-  if (s >= n) return;
-  const float4 p = pts[s];
-  const unsigned long long best = prep_knn_search(pts, cell_begin, g, p, k, lane), none = ~0ull;
-  if (lane < k) {
-    const size_t row = (size_t)__float_as_uint(p.w) * k;
-    idx_out[row + lane] = best == none ? -1 : (int)(uint32_t)best;
-    d2_out[row + lane] = best == none ? 0.f : __uint_as_float((uint32_t)(best >> 32));
-  }
-}
 
 /* ---- statistical outlier removal ---------------------------------------------------------------------------- */
 /* dist[i] = (float)(sum_{m=1..mean_k} sqrtf(d2[i][m]) / mean_k), fp64 sum in neighbour order; 0 when n <= mean_k */
@@ -260,39 +164,17 @@ __device__ __forceinline__ float prep_sor_mean_dist(const float* __restrict__ d2
   for (int m = 1; m <= mean_k; m++) s += (double)sqrtf(d2_row[m]);
   return (float)(s / (double)mean_k);
 }
-__global__ __launch_bounds__(256) void k_prep_sor_dist(const float* __restrict__ d2, int n, int mean_k, int valid, float* __restrict__ dist) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  dist[i] = valid ? prep_sor_mean_dist(d2 + (size_t)i * (mean_k + 1), mean_k) : 0.f;
-}
 /* per-chunk (64 points) sums of d and d*d in fp64 */
 __device__ __forceinline__ void prep_sor_chunk(const float* __restrict__ dist, int b, int e, double* __restrict__ part) {
   double ps = 0, pq = 0;
   for (int i = b; i < e; i++) { const double v = (double)dist[i]; ps += v; pq += v * v; }
   part[0] = ps; part[1] = pq;
 }
-__global__ __launch_bounds__(64) void k_prep_sor_chunks(const float* __restrict__ dist, int n, double* __restrict__ parts) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  const int c0 = c * 64;
-  if (c0 >= n) return;
-  prep_sor_chunk(dist, c0, min(n, c0 + 64), parts + (size_t)c * 2);
-}
 /* out[0] = mean + mul * stddev */
 __device__ __forceinline__ double prep_sor_thr(double sum, double sq, int n, double std_mul) {
   const double mean = sum / (double)n;
   const double variance = (sq - sum * sum / (double)n) / ((double)n - 1);
   return mean + std_mul * ppf_sqrt(variance);
-}
-__global__ __launch_bounds__(64) void k_prep_sor_threshold(const double* __restrict__ parts, int n, double std_mul, double* __restrict__ out) {
-  __shared__ double tot[2];
-  const int n_chunks = (n + 63) / 64;
-  if (threadIdx.x < 2) tot[threadIdx.x] = icp_sum_parts(parts + threadIdx.x, n_chunks, 2);
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = prep_sor_thr(tot[0], tot[1], n, std_mul);
-}
-__global__ __launch_bounds__(256) void k_prep_sor_flags(const float* __restrict__ dist, int n, const double* __restrict__ thr, uint32_t* __restrict__ flags) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) flags[i] = !((double)dist[i] > thr[0]) ? 1u : 0u;
 }
 
 /* ---- normals + curvature ------------------------------------------------------------------------------------ */
@@ -360,14 +242,6 @@ __device__ __forceinline__ void prep_normal_point(float* __restrict__ o, float* 
   const double at = trace < 0 ? -trace : trace;
   *curv_out = trace != 0.0 ? (float)(lam / at) : 0.f;
 }
-/* in place: rows[i][3..5] = normal, curv[i] = curvature; idx = [n][k] neighbour lists (k_eff valid entries) */
-__global__ __launch_bounds__(64) void k_prep_normals(float* __restrict__ rows, float* __restrict__ curv, int n, const int* __restrict__ idx,
-                                                     int k, const float4* __restrict__ q4) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  prep_normal_point(rows + (size_t)i * 6, curv + i, idx + (size_t)i * k, k, q4);
-}
-
 /* PointCloudXYZNormalToMat: n /= (float)sqrtf(n.n) when that length exceeds 1e-5 */
 __device__ __forceinline__ void prep_to_mat_row(const float* __restrict__ row, float* __restrict__ out) {
   float d[6];
@@ -379,20 +253,16 @@ __device__ __forceinline__ void prep_to_mat_row(const float* __restrict__ row, f
 #pragma unroll
   for (int k = 0; k < 6; k++) out[k] = d[k];
 }
-__global__ __launch_bounds__(256) void k_prep_to_mat(const float* __restrict__ rows, int n, float* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  prep_to_mat_row(rows + (size_t)i * 6, out + (size_t)i * 6);
-}
 
 /* ============================================================================================================ */
-/* Segmented stages: every detection of a frame at once (ppf_prep_frame, ppf_frame_host.h)                       */
+/* The stage kernels: K segments at once (host side: ppf_prep_host.h; ppf_prep_frame: ppf_frame_host.h)           */
 /* ============================================================================================================ */
 /* A stage's input is the concatenation of K <= FRAME_MAX_BOXES segments, one per box, described by a device table
  * {off, n} (segments are contiguous and in box order).  Counts never leave the device: grids are sized for a worst
- * case the host knows and threads past the segment table's total exit.  Every floating-point reduction runs in the
- * order the single-cloud kernel above uses on that segment alone (shared bodies), so each segment's result is
- * bit-identical to the per-box chain.  The small per-segment kernels run one workgroup of FRAME_MAX_BOXES threads. */
+ * case the host knows and threads past the segment table's total exit.  Every floating-point reduction runs over a
+ * segment's own rows in their order, counted from the segment's start, so a segment's result depends neither on K
+ * nor on its neighbours: it is what the stage gives for that segment alone (K = 1, the per-cloud entries).  The
+ * small per-segment kernels run one workgroup of FRAME_MAX_BOXES threads. */
 constexpr int FRAME_MAX_BOXES = 256;
 struct FrameSeg {
   uint32_t off, n;
@@ -460,21 +330,23 @@ __global__ __launch_bounds__(256) void k_frame_crop_gather(const float* __restri
   out_curv[o] = curv[i];
 }
 
-/* ---- per-segment bounds of the finite points: mm[s][0..2] = min, [3..5] = max (order-preserving), fin[s] = count;
- * one workgroup per segment ---- */
+/* ---- per-segment bounds of the finite points: mm[s][0..2] = ~min, [3..5] = max (order-preserving words; the minimum
+ * is stored complemented, so that 0 is the identity of all seven words), fin[s] = count.  gridDim.y workgroups share a
+ * segment: one stores its result, several combine theirs with integer atomicMax / atomicAdd on words the host has
+ * zeroed (order-independent, so the result does not depend on gridDim.y) ---- */
 __global__ __launch_bounds__(256) void k_frame_bounds(const float* __restrict__ rows, const FrameSeg* __restrict__ seg,
                                                       uint32_t* __restrict__ mm, uint32_t* __restrict__ fin) {
   const int s = blockIdx.x;
   const FrameSeg sg = seg[s];
-  uint32_t lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0, 0, 0}, cnt = 0;
-  for (uint32_t i = sg.off + threadIdx.x; i < sg.off + sg.n; i += blockDim.x) {
+  uint32_t nlo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, cnt = 0;
+  for (uint32_t i = sg.off + blockIdx.y * blockDim.x + threadIdx.x; i < sg.off + sg.n; i += blockDim.x * gridDim.y) {
     const float* p = rows + (size_t)i * 6;
     if (!prep_finite3(p)) continue;
     cnt++;
 #pragma unroll
     for (int k = 0; k < 3; k++) {
       const uint32_t o = float_to_ordered(p[k]);
-      lo[k] = min(lo[k], o);
+      nlo[k] = max(nlo[k], ~o);
       hi[k] = max(hi[k], o);
     }
   }
@@ -482,7 +354,7 @@ __global__ __launch_bounds__(256) void k_frame_bounds(const float* __restrict__ 
   for (int o = 32; o > 0; o >>= 1) {
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-      lo[k] = min(lo[k], (uint32_t)__shfl_down(lo[k], o));
+      nlo[k] = max(nlo[k], (uint32_t)__shfl_down(nlo[k], o));
       hi[k] = max(hi[k], (uint32_t)__shfl_down(hi[k], o));
     }
     cnt += (uint32_t)__shfl_down(cnt, o);
@@ -491,22 +363,24 @@ __global__ __launch_bounds__(256) void k_frame_bounds(const float* __restrict__ 
   const int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
-    for (int k = 0; k < 3; k++) { s_mm[wave][k] = lo[k]; s_mm[wave][3 + k] = hi[k]; }
+    for (int k = 0; k < 3; k++) { s_mm[wave][k] = nlo[k]; s_mm[wave][3 + k] = hi[k]; }
     s_mm[wave][6] = cnt;
   }
   __syncthreads();
   if (threadIdx.x < 7) {
     const int k = threadIdx.x;
     uint32_t v = s_mm[0][k];
-    for (int w = 1; w < 4; w++) v = k < 3 ? min(v, s_mm[w][k]) : k < 6 ? max(v, s_mm[w][k]) : v + s_mm[w][k];
-    if (k < 6) mm[(size_t)s * 6 + k] = v;
-    else if (fin) fin[s] = v;
+    for (int w = 1; w < 4; w++) v = k < 6 ? max(v, s_mm[w][k]) : v + s_mm[w][k];
+    uint32_t* dst = k < 6 ? &mm[(size_t)s * 6 + k] : &fin[s];
+    if (gridDim.y == 1) *dst = v;
+    else if (k < 6) atomicMax(dst, v);
+    else atomicAdd(dst, v);
   }
 }
 
 /* ---- voxel grid ---- */
-/* per segment: PCL's min_b / div_b exactly as ppf_prep_voxel_grid computes them on the host; *err = the first box
- * whose cell index would overflow (~0 = none) */
+/* per segment: PCL's min_b / div_b from the bounds of its finite points; *err = the first box whose cell index would
+ * overflow (~0 = none) */
 __global__ __launch_bounds__(FRAME_MAX_BOXES) void k_frame_voxel_dims(const uint32_t* __restrict__ mm, const uint32_t* __restrict__ fin, int K,
                                                                       float inv_leaf, VoxelGridDims* __restrict__ dims, uint32_t* __restrict__ err) {
   __shared__ uint32_t e;
@@ -520,7 +394,7 @@ __global__ __launch_bounds__(FRAME_MAX_BOXES) void k_frame_voxel_dims(const uint
     if (fin[s]) {
       long long cells = 1;
       for (int k = 0; k < 3; k++) {
-        const float lo = ordered_to_float(mm[(size_t)s * 6 + k]), hi = ordered_to_float(mm[(size_t)s * 6 + 3 + k]);
+        const float lo = ordered_to_float(~mm[(size_t)s * 6 + k]), hi = ordered_to_float(mm[(size_t)s * 6 + 3 + k]);
         g.min_b[k] = ppf_f2i(floorf(lo * inv_leaf));
         const int max_b = ppf_f2i(floorf(hi * inv_leaf));
         g.div_b[k] = max_b - g.min_b[k] + 1;
@@ -579,21 +453,23 @@ __global__ __launch_bounds__(FRAME_MAX_BOXES) void k_frame_voxel_table(const uin
 }
 
 /* ---- neighbour search: one uniform grid per segment, cells of all grids in one array ---- */
-/* per segment: the grid cloud_knn would build (mode 0: SOR, k_eff = n > k ? k + 1 : 0; mode 1: normals, k_eff = min(k, n)),
- * the base of its cells and of its 64-point SOR chunks */
-__global__ __launch_bounds__(FRAME_MAX_BOXES) void k_frame_knn_grids(const uint32_t* __restrict__ mm, const FrameSeg* __restrict__ seg, int K,
-                                                                     int mode, int k, double gdiv, KnnGrid* __restrict__ grids,
-                                                                     uint32_t* __restrict__ cell_base, int* __restrict__ keff,
-                                                                     uint32_t* __restrict__ chunk_base) {
+/* per segment: its grid, about sqrt(n) / gdiv cells along the longest side of the bounding box (a 3x3x3 cube of a
+ * surface-like cloud then holds a few hundred points), at most 128; k_eff (mode 0: SOR, n > k ? k + 1 : 0; mode 1:
+ * normals, min(k, n); 0 = not searched, also for a segment that holds a non-finite row: fin[s] != n); the base of its
+ * cells and of its 64-point SOR chunks */
+__global__ __launch_bounds__(FRAME_MAX_BOXES) void k_frame_knn_grids(const uint32_t* __restrict__ mm, const uint32_t* __restrict__ fin,
+                                                                     const FrameSeg* __restrict__ seg, int K, int mode, int k, double gdiv,
+                                                                     KnnGrid* __restrict__ grids, uint32_t* __restrict__ cell_base,
+                                                                     int* __restrict__ keff, uint32_t* __restrict__ chunk_base) {
   const int s = threadIdx.x;
   uint32_t cells = 0, chunks = 0;
   if (s < K) {
     const int n = (int)seg[s].n;
-    const int ke = mode == 0 ? (n > k ? k + 1 : 0) : min(k, n);
+    const int ke = fin[s] != (uint32_t)n ? 0 : mode == 0 ? (n > k ? k + 1 : 0) : min(k, n);
     KnnGrid g;
     float ext_max = 0.f;
     for (int a = 0; a < 3; a++) {
-      g.lo[a] = ordered_to_float(mm[(size_t)s * 6 + a]);
+      g.lo[a] = ordered_to_float(~mm[(size_t)s * 6 + a]);
       ext_max = fmaxf(ext_max, ordered_to_float(mm[(size_t)s * 6 + 3 + a]) - g.lo[a]);
     }
     const int G = max(1, min(128, (int)(sqrt((double)n) / gdiv)));
@@ -644,8 +520,8 @@ __global__ __launch_bounds__(256) void k_frame_knn_scatter(const float* __restri
   const uint32_t slot = cell_begin[key] + atomicSub(&cell_count[key], 1u) - 1u;
   pts[slot] = make_float4(x, y, z, __uint_as_float((uint32_t)i));
 }
-/* ONE WAVE PER POINT in cell order, the search of k_prep_knn on the point's own segment grid; idx (segment-local
- * indices) / d2 are [row][kstride] with the segment's k_eff entries */
+/* ONE WAVE PER POINT in cell order, prep_knn_search on the point's own segment grid; idx (segment-local indices) /
+ * d2 are [row][kstride] at the point's row, with the segment's k_eff entries */
 __global__ __launch_bounds__(256) void k_frame_knn(const float4* __restrict__ pts, const uint32_t* __restrict__ cell_begin,
                                                    const KnnGrid* __restrict__ grids, const uint32_t* __restrict__ cell_base,
                                                    const FrameSeg* __restrict__ seg, int K, const int* __restrict__ keff, int cap, int kstride,
@@ -669,11 +545,11 @@ __global__ __launch_bounds__(256) void k_frame_knn(const float4* __restrict__ pt
 /* ---- statistical outlier removal: per-segment mean distance, 64-point chunks from each segment's start, one
  * threshold per segment ---- */
 __global__ __launch_bounds__(256) void k_frame_sor_dist(const float* __restrict__ d2, int cap, const FrameSeg* __restrict__ seg, int K,
-                                                        int mean_k, float* __restrict__ dist) {
+                                                        const int* __restrict__ keff, int mean_k, float* __restrict__ dist) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= cap || (uint32_t)i >= frame_total(seg, K)) return;
   const int s = frame_seg_of(seg, K, (uint32_t)i);
-  dist[i] = (int)seg[s].n > mean_k ? prep_sor_mean_dist(d2 + (size_t)i * (mean_k + 1), mean_k) : 0.f;
+  dist[i] = keff[s] ? prep_sor_mean_dist(d2 + (size_t)i * (mean_k + 1), mean_k) : 0.f; /* a segment that was not searched has no lists */
 }
 __global__ __launch_bounds__(64) void k_frame_sor_chunks(const float* __restrict__ dist, int cap_chunks, const FrameSeg* __restrict__ seg, int K,
                                                          const uint32_t* __restrict__ chunk_base, double* __restrict__ parts) {
