@@ -9,6 +9,7 @@
  *   NormalEstimation   :381-405  ->  Cloud::normals(k)
  *   EdgeExtraction     :406-427  ->  Cloud::edges(curvatureThreshold)
  *   PointCloudXYZNormalToMat :163-190 -> Cloud::toMat()   (an N x 6 ppf_match_3d::Mat for PPF3DDetector / ICP)
+ *   (nothing: pcl::SACSegmentation would be it)    ->  Cloud::removePlanes(params) / Cloud::applyPlanes(planes)  (the table or wall taken out)
  *   all of the above for every box of a frame  ->  Cloud::prepareFrame(boxes, n, depth, ...)  (one (object, edge) pair per box)
  *   Matching_S2B + ICP for every detection     ->  Cloud::matchFrame(models, modelClouds, dets, ...)  (ICP in one launch sequence)
  *   `// TODO: Pose Validation` (:477-479, :530-532) -> Cloud::verifyFrame(modelClouds, dets, poses, depth, ...)  (scores, best pose)
@@ -88,6 +89,62 @@ class Cloud {
   }
   Cloud normals(int k = 30) const { ppf_cloud* o = nullptr; ppf_match_3d::check(ppf_prep_normals(need(), k, &o)); return Cloud(o); }
   Cloud edges(float curvatureThreshold) const { ppf_cloud* o = nullptr; ppf_match_3d::check(ppf_prep_edges(need(), curvatureThreshold, &o)); return Cloud(o); }
+
+  static ppf_plane_params defaultPlaneParams() {
+    ppf_plane_params p;
+    ppf_default_plane_params(&p);
+    return p;
+  }
+  /* The support planes (the table, a wall) of every cloud found and removed in one call (ppf_prep_planes), the step before
+   * crop / prepareFrame: up to params->max_planes rounds of a seeded hypothesis search per cloud, each cloud's result what a
+   * call with it alone gives.  Returns the kept rows per cloud, still in HBM.  info (optional): [clouds][max_planes] rows;
+   * labels (optional): per cloud one byte per input row (0 kept, 1 + p inlier of plane p, 0x80 | (1 + p) behind plane p).
+   * params == 0: defaultPlaneParams(). */
+  static std::vector<Cloud> removePlanes(const std::vector<const Cloud*>& clouds, const ppf_plane_params* params = 0,
+                                         std::vector<ppf_plane_info>* info = 0, std::vector<std::vector<uint8_t> >* labels = 0,
+                                         ppf_plane_stats* stats = 0) {
+    const ppf_plane_params p = orDefaults(params, ppf_default_plane_params);
+    const size_t nc = clouds.size();
+    const size_t planes = p.max_planes >= 1 && p.max_planes <= PPF_PLANE_MAX_PLANES ? (size_t)p.max_planes : 1;
+    std::vector<const ppf_cloud*> in(nc + 1, (const ppf_cloud*)0);
+    std::vector<ppf_cloud*> out(nc + 1, (ppf_cloud*)0);
+    std::vector<ppf_plane_info> rows(nc * planes + 1);
+    std::vector<uint8_t*> lab(nc + 1, (uint8_t*)0);
+    for (size_t i = 0; i < nc; i++) {
+      if (!clouds[i]) throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Cloud::removePlanes: a cloud is missing");
+      in[i] = clouds[i]->need();
+    }
+    if (labels) {
+      labels->assign(nc, std::vector<uint8_t>());
+      for (size_t i = 0; i < nc; i++) {
+        (*labels)[i].assign((size_t)clouds[i]->size() + 1, 0);
+        lab[i] = &(*labels)[i][0];
+      }
+    }
+    ppf_match_3d::check(ppf_prep_planes(&in[0], (int)nc, &p, &out[0], &rows[0], labels ? &lab[0] : 0, stats));
+    std::vector<Cloud> kept;
+    for (size_t i = 0; i < nc; i++) kept.push_back(Cloud(out[i]));
+    if (labels)
+      for (size_t i = 0; i < nc; i++) (*labels)[i].pop_back();
+    if (info) info->assign(rows.begin(), rows.begin() + (std::ptrdiff_t)(nc * planes));
+    return kept;
+  }
+  /* this cloud without its support planes: info receives max_planes rows, labels one byte per row */
+  Cloud removePlanes(const ppf_plane_params* params = 0, std::vector<ppf_plane_info>* info = 0, std::vector<uint8_t>* labels = 0,
+                     ppf_plane_stats* stats = 0) const {
+    std::vector<std::vector<uint8_t> > lab;
+    const std::vector<Cloud> kept = removePlanes(std::vector<const Cloud*>(1, this), params, info, labels ? &lab : 0, stats);
+    if (labels) labels->swap(lab[0]);
+    return kept[0];
+  }
+  /* the rows of a companion cloud (a detection's edge cloud) that the planes removePlanes reported do not remove
+   * (ppf_prep_planes_apply): the same predicate and params */
+  Cloud applyPlanes(const std::vector<ppf_plane_info>& planes, const ppf_plane_params* params = 0) const {
+    const ppf_plane_params p = orDefaults(params, ppf_default_plane_params);
+    ppf_cloud* o = nullptr;
+    ppf_match_3d::check(ppf_prep_planes_apply(need(), planes.empty() ? 0 : &planes[0], (int)planes.size(), &p, &o));
+    return Cloud(o);
+  }
 
   static ppf_frame_params defaultFrameParams() {
     ppf_frame_params p;

@@ -35,6 +35,8 @@
  *                                   (YOLO_cropping_ppf_test.cpp:88-127, CloudProcessing.h:495-523)
  *   ppf_prep_frame                  the same six stages for all of a frame's boxes at once (CloudProcessing.h:263-427
  *                                   return one cloud per detection)
+ *   ppf_prep_planes (+_apply)       pcl::SACSegmentation + ExtractIndices, the step PPF pipelines take before cropping (the
+ *                                   reference has none): the support planes of a frame found and removed
  *   ppf_cloud_from_depth (+_device) CloudProcessor::Deprojection(CameraIntr), an empty stub in the reference
  *                                   (CloudProcessing.h:262): the scene cloud from the depth image, Camera::back_projection
  *                                   (Camera.h:44-46) per valid pixel
@@ -423,6 +425,63 @@ ppf_status ppf_icp_refine_clouds(const ppf_cloud* model, const ppf_cloud* scene,
                                  int n_poses, int* iterations_out);
 /* exact neighbour lists (parity surface): idx, d2 are [n][k], ascending (distance, index) */
 ppf_status ppf_prep_knn(const ppf_cloud* in, int k, int* idx, float* d2);
+
+/* ---- support planes: the table or wall the objects stand on, found and taken out of a cloud --------- */
+#define PPF_PLANE_NONE 0     /* round not run: fewer than 3 rows left, or an earlier round ended the search */
+#define PPF_PLANE_REMOVED 1
+#define PPF_PLANE_REJECTED 2 /* best hypothesis below min_inliers / min_inlier_share: nothing removed, search ends */
+#define PPF_PLANE_NO_REFIT 1      /* flags: remove the best hypothesis as it is */
+#define PPF_PLANE_REMOVE_BEHIND 2 /* flags: also remove rows farther than the threshold on the side away from the origin */
+#define PPF_PLANE_MAX_PLANES 4
+#define PPF_PLANE_MAX_HYPOTHESES 4096
+
+typedef struct ppf_plane_params {
+  float distance_threshold; /* > 0, metres; default 0.005 */
+  int32_t n_hypotheses;     /* 1..4096; default 256 */
+  uint32_t seed;            /* default 1 */
+  int32_t max_planes;       /* 1..4; default 1 */
+  int32_t min_inliers;      /* >= 3; default 100 */
+  float min_inlier_share;   /* 0..1, of the rows left at the round's start; default 0.10 */
+  int32_t flags;
+  int32_t reserved[4];
+} ppf_plane_params;
+
+typedef struct ppf_plane_info {
+  double n[3], d;        /* n.p + d = 0, |n| = 1, d >= 0: the origin (the camera) is on the non-negative side */
+  int32_t status;        /* PPF_PLANE_* */
+  int32_t hypothesis;    /* the index of the best hypothesis */
+  int32_t n_rows;        /* rows left at the round's start */
+  int32_t n_hyp_inliers; /* inliers of the best hypothesis */
+  int32_t n_inliers;     /* inliers of the plane that was removed */
+  int32_t n_behind;      /* rows removed as behind it (PPF_PLANE_REMOVE_BEHIND) */
+  int32_t refit;         /* 1: n, d are the refitted plane, 0: the hypothesis */
+  int32_t reserved;
+} ppf_plane_info;
+
+typedef struct ppf_plane_stats {
+  int32_t n_clouds, n_launches, n_host_syncs;
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_plane_stats;
+
+void ppf_default_plane_params(ppf_plane_params* p);
+/* Up to max_planes rounds per cloud, n_clouds (0..256) clouds in one pass: a round draws n_hypotheses planes through three
+ * of the rows left (a hash of seed, round, hypothesis: the same rows on every machine), counts each one's inliers
+ * (|n.p + d| <= distance_threshold in fp64), refits the best by the fixed-order covariance of its inliers (unless
+ * PPF_PLANE_NO_REFIT; the refit is used iff it counts no fewer inliers) and removes that plane's inliers.  out[i]: the kept
+ * rows of in[i] in their order, normals and curvature carried byte for byte; the outputs share one device block.
+ * info: [n_clouds][max_planes] rows, zero for a round that did not run.  labels: NULL, or n_clouds pointers each NULL or
+ * rows(in[i]) bytes: 0 kept, 1 + p inlier of plane p, 0x80 | (1 + p) removed as behind plane p.  A non-finite row is never
+ * removed.  Each cloud's result is what a call with that cloud alone gives; the launch count depends on max_planes and flags
+ * only; the host blocks in one upload before any device work and waits for the device once, for the results (n_host_syncs 1).  Argument errors are PPF_ERR_INVALID before any device work; on every
+ * error each out[i] is NULL and the info rows are zero. */
+ppf_status ppf_prep_planes(const ppf_cloud* const* in, int n_clouds, const ppf_plane_params* p, ppf_cloud** out,
+                           ppf_plane_info* info, uint8_t* const* labels, ppf_plane_stats* stats /* may be NULL */);
+/* The rows of a companion cloud (a detection's edge cloud) that are neither inliers of one of the n_planes (0..4) planes
+ * whose status is PPF_PLANE_REMOVED nor, with PPF_PLANE_REMOVE_BEHIND, behind one: the same predicate and
+ * distance_threshold.  Applied to in[i] itself it gives out[i]. */
+ppf_status ppf_prep_planes_apply(const ppf_cloud* in, const ppf_plane_info* planes, int n_planes, const ppf_plane_params* p,
+                                 ppf_cloud** out);
 
 /* ---- the organised scene cloud from a depth image, on the device (what CloudProcessor::Deprojection leaves empty) -- */
 #define PPF_DEPTH_F32 0  /* float32 metres: z = value (the reference's EXR frame) */

@@ -207,6 +207,27 @@ class RegisterStats(C.Structure):
 PPF_CAMERA_NEWTON_ITERS, PPF_REGISTER_MAX_QUAD_PX = 7, 16  # include/ppf_hip.h
 
 
+class PlaneParams(C.Structure):
+    _fields_ = [("distance_threshold", C.c_float), ("n_hypotheses", C.c_int32), ("seed", C.c_uint32), ("max_planes", C.c_int32),
+                ("min_inliers", C.c_int32), ("min_inlier_share", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class PlaneInfo(C.Structure):
+    _fields_ = [("n", C.c_double * 3), ("d", C.c_double), ("status", C.c_int32), ("hypothesis", C.c_int32), ("n_rows", C.c_int32),
+                ("n_hyp_inliers", C.c_int32), ("n_inliers", C.c_int32), ("n_behind", C.c_int32), ("refit", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class PlaneStats(C.Structure):
+    _fields_ = [("n_clouds", C.c_int32), ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32), ("ms_wall", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
+PPF_PLANE_NONE, PPF_PLANE_REMOVED, PPF_PLANE_REJECTED = 0, 1, 2  # PlaneInfo.status
+PPF_PLANE_NO_REFIT, PPF_PLANE_REMOVE_BEHIND = 1, 2  # PlaneParams.flags bits
+PPF_PLANE_MAX_PLANES, PPF_PLANE_MAX_HYPOTHESES = 4, 4096
+
+
 # every symbol include/ppf_hip.h declares (tests/test_capi_symbols.py checks the header against this)
 _SIGNATURES = {
     "ppf_default_train_params": (None, [C.POINTER(TrainParams)]),
@@ -332,6 +353,10 @@ _SIGNATURES = {
                                      C.POINTER(RegisterStats)]),
     "ppf_depth_register_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(DepthParams), C.POINTER(RegisterParams),
                                             C.c_void_p, C.c_void_p, C.POINTER(RegisterStats)]),
+    "ppf_default_plane_params": (None, [C.POINTER(PlaneParams)]),
+    "ppf_prep_planes": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(PlaneParams), C.POINTER(C.c_void_p), C.POINTER(PlaneInfo),
+                                  C.POINTER(C.c_void_p), C.POINTER(PlaneStats)]),
+    "ppf_prep_planes_apply": (C.c_int, [C.c_void_p, C.POINTER(PlaneInfo), C.c_int, C.POINTER(PlaneParams), C.POINTER(C.c_void_p)]),
     "ppf_icp_register": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }

@@ -13,7 +13,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _capi
-from ._capi import (FrameDetection, FrameParams, FrameStats, IcpParams, MatchFrameStats, Pose, PoseScore, PPFError, RefineInfo,
+from ._capi import (FrameDetection, FrameParams, FrameStats, IcpParams, MatchFrameStats, PlaneInfo, PlaneParams, PlaneStats, Pose,
+                    PoseScore, PPFError, RefineInfo,
                     RefineParams, RefineStats, RenderParams, RenderStats, SelectInfo, SelectParams, SelectStats, VerifyParams, VerifyStats,
                     check, lib)
 from .detector import ICP, PPF3DDetector, Pose3D
@@ -166,12 +167,59 @@ class DeviceCloud:
             return pairs, rows, _capi.stats_dict(st)
         return pairs
 
+    def remove_planes(self, params=None, return_info: bool = False, return_labels: bool = False):
+        """this cloud without its support planes (ppf_prep_planes with one cloud; see the module-level ``remove_planes``)"""
+        res = remove_planes([self], params, return_info=return_info, return_labels=return_labels)
+        if not (return_info or return_labels):
+            return res[0]
+        out = [part[0] for part in res[:1 + int(return_info) + int(return_labels)]]   # this cloud's kept rows, info rows, labels
+        return tuple(out + [res[-1]] if return_info else out)                        # the stats last
+
+    def apply_planes(self, info, params=None) -> "DeviceCloud":
+        """the rows of this cloud (a detection's edge cloud) that the planes of ``info`` -- the info rows ``remove_planes``
+        returned for one cloud -- do not remove (ppf_prep_planes_apply): same predicate, same ``params``"""
+        prm = _plane_params(params)
+        rec = np.ascontiguousarray(np.asarray(info, dtype=PLANE_INFO).reshape(-1))
+        return self._stage(lib().ppf_prep_planes_apply, rec.ctypes.data_as(C.POINTER(PlaneInfo)), int(rec.shape[0]), C.byref(prm))
+
     def knn(self, k: int):
         n = len(self)
         idx = np.zeros((n, k), dtype=np.int32)
         d2 = np.zeros((n, k), dtype=np.float32)
         check(lib().ppf_prep_knn(self._ptr, int(k), idx.ctypes.data, d2.ctypes.data))
         return idx, d2
+
+
+# ppf_plane_info as a numpy record
+PLANE_INFO = np.dtype([("n", "<f8", 3), ("d", "<f8"), ("status", "<i4"), ("hypothesis", "<i4"), ("n_rows", "<i4"), ("n_hyp_inliers", "<i4"),
+                       ("n_inliers", "<i4"), ("n_behind", "<i4"), ("refit", "<i4"), ("reserved", "<i4")])
+
+
+def remove_planes(clouds, params=None, return_info: bool = False, return_labels: bool = False):
+    """The support planes (the table, a wall) of every cloud found and removed in one segmented call (ppf_prep_planes):
+    up to ``max_planes`` rounds of a seeded hypothesis search per cloud, each cloud's result byte-identical to a call with
+    it alone.  params: a PlaneParams, a dict of its fields (the rest default) or None.  Returns the list of kept clouds; with
+    return_info also the info rows ((n_clouds, max_planes) records of ``PLANE_INFO``) and, last, the call's stats; with
+    return_labels the per-row labels (uint8: 0 kept, 1 + p inlier of plane p, 0x80 | (1 + p) behind plane p) per cloud."""
+    prm = _plane_params(params)
+    K = len(clouds)
+    ins, outs = (C.c_void_p * max(K, 1))(*[c._ptr for c in clouds]), (C.c_void_p * max(K, 1))()
+    info = np.zeros((K, max(1, min(int(prm.max_planes), _capi.PPF_PLANE_MAX_PLANES))), dtype=PLANE_INFO)
+    labels = [np.zeros(len(c), dtype=np.uint8) for c in clouds] if return_labels else None
+    lab = (C.c_void_p * max(K, 1))(*[a.ctypes.data for a in labels]) if return_labels else None
+    st = PlaneStats()
+    check(lib().ppf_prep_planes(ins, K, C.byref(prm), outs, info.ctypes.data_as(C.POINTER(PlaneInfo)), lab, C.byref(st)))
+    kept = [DeviceCloud(C.c_void_p(outs[i])) for i in range(K)]
+    if not (return_info or return_labels):
+        return kept
+    res = [kept]
+    if return_info:
+        res.append(info)
+    if return_labels:
+        res.append(labels)
+    if return_info:
+        res.append(_capi.stats_dict(st))
+    return tuple(res)
 
 
 def _intr4(intr):
@@ -198,6 +246,15 @@ def _params(cls, defaults: str, params):
     for key, v in (params or {}).items():
         setattr(prm, key, v)
     return prm
+
+
+def _plane_params(params) -> PlaneParams:
+    """``_params`` for ppf_plane_params; a key that is no field of the record (a misspelt name) is an error, not ignored"""
+    if isinstance(params, dict):
+        unknown = sorted(set(params) - {f for f, _ in PlaneParams._fields_})
+        if unknown:
+            raise PPFError(_capi.PPF_ERR_INVALID, f"unknown plane parameter(s): {', '.join(unknown)}")
+    return _params(PlaneParams, "ppf_default_plane_params", params)
 
 
 def _depth_image(depth, error: str):
@@ -529,6 +586,9 @@ class CloudProcessor:
         self.refine_info: Optional[np.ndarray] = None
         self.refine_stats: Dict[str, object] = {}
         self._last_refined: List[Pose3D] = []
+        # RemovePlanes: the info rows of the planes taken out of the scene, and the counters
+        self.plane_info: Optional[np.ndarray] = None
+        self.plane_stats: Dict[str, object] = {}
 
     # ---- the PCL half -------------------------------------------------------------------------------------
     def Deprojection(self, CameraIntr, fp64: bool = False) -> DeviceCloud:
@@ -538,6 +598,16 @@ class CloudProcessor:
         if self.depth is None:
             raise PPFError(_capi.PPF_ERR_INVALID, "Deprojection needs a depth image")
         self.scene = DeviceCloud.from_depth(self.depth, np.asarray(CameraIntr, dtype=np.float64), fp64=fp64)
+        return self.scene
+
+    def RemovePlanes(self, **params) -> DeviceCloud:
+        """``self.scene`` without its support planes (ppf_prep_planes), the step before SceneCropping / PrepareFrame: a
+        box's corners lie on the background, so without it every object cloud is mostly table.  params: the fields of
+        ppf_plane_params (distance_threshold, n_hypotheses, seed, max_planes, min_inliers, min_inlier_share, flags).
+        Sets ``plane_info`` (the info rows) and ``plane_stats``; replaces and returns ``self.scene``."""
+        if self.scene is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "RemovePlanes needs a scene cloud")
+        self.scene, self.plane_info, self.plane_stats = self.scene.remove_planes(params, return_info=True)
         return self.scene
 
     def SceneCropping(self, CameraIntr) -> List[DeviceCloud]:

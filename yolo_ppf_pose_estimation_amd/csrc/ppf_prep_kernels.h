@@ -202,6 +202,26 @@ __device__ __forceinline__ void prep_jacobi_rotate(double (&A)[3][3], double (&V
   }
 }
 
+/* 12 cyclic Jacobi sweeps over (0,1), (0,2), (1,2) of the symmetric matrix {xx, xy, xz, yy, yz, zz}: nv = the column of the
+ * smallest diagonal entry (strict <, in the order 0, 1, 2) divided by its length; returns that entry.  Shared by the
+ * normals (prep_normal_point) and the plane refit (ppf_plane_kernels.h) */
+__device__ __forceinline__ double prep_smallest_eigvec(const double (&cov)[6], double (&nv)[3]) {
+  double A[3][3] = {{cov[0], cov[1], cov[2]}, {cov[1], cov[3], cov[4]}, {cov[2], cov[4], cov[5]}};
+  double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+  for (int sweep = 0; sweep < 12; sweep++) {
+    prep_jacobi_rotate(A, V, 0, 1);
+    prep_jacobi_rotate(A, V, 0, 2);
+    prep_jacobi_rotate(A, V, 1, 2);
+  }
+  double lam = A[0][0];
+  nv[0] = V[0][0]; nv[1] = V[1][0]; nv[2] = V[2][0];
+  if (A[1][1] < lam) { lam = A[1][1]; nv[0] = V[0][1]; nv[1] = V[1][1]; nv[2] = V[2][1]; }
+  if (A[2][2] < lam) { lam = A[2][2]; nv[0] = V[0][2]; nv[1] = V[1][2]; nv[2] = V[2][2]; }
+  const double len = ppf_sqrt(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
+  nv[0] /= len; nv[1] /= len; nv[2] /= len;
+  return lam;
+}
+
 /* in place: o[3..5] = normal, *curv = curvature of the point o from its k neighbours nb (indices into q4) */
 __device__ __forceinline__ void prep_normal_point(float* __restrict__ o, float* __restrict__ curv_out, const int* __restrict__ nb, int k,
                                                   const float4* __restrict__ q4) {
@@ -222,19 +242,9 @@ __device__ __forceinline__ void prep_normal_point(float* __restrict__ o, float* 
   }
 #pragma unroll
   for (int a = 0; a < 6; a++) cov[a] /= (double)k;
-  double A[3][3] = {{cov[0], cov[1], cov[2]}, {cov[1], cov[3], cov[4]}, {cov[2], cov[4], cov[5]}};
-  double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
   const double trace = cov[0] + cov[3] + cov[5];
-  for (int sweep = 0; sweep < 12; sweep++) {
-    prep_jacobi_rotate(A, V, 0, 1);
-    prep_jacobi_rotate(A, V, 0, 2);
-    prep_jacobi_rotate(A, V, 1, 2);
-  }
-  double lam = A[0][0], nv[3] = {V[0][0], V[1][0], V[2][0]};
-  if (A[1][1] < lam) { lam = A[1][1]; nv[0] = V[0][1]; nv[1] = V[1][1]; nv[2] = V[2][1]; }
-  if (A[2][2] < lam) { lam = A[2][2]; nv[0] = V[0][2]; nv[1] = V[1][2]; nv[2] = V[2][2]; }
-  const double len = ppf_sqrt(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
-  nv[0] /= len; nv[1] /= len; nv[2] /= len;
+  double nv[3];
+  double lam = prep_smallest_eigvec(cov, nv);
   const double cos_theta = -((double)o[0] * nv[0] + (double)o[1] * nv[1] + (double)o[2] * nv[2]);
   if (cos_theta < 0) { nv[0] = -nv[0]; nv[1] = -nv[1]; nv[2] = -nv[2]; }
   o[3] = (float)nv[0]; o[4] = (float)nv[1]; o[5] = (float)nv[2];
