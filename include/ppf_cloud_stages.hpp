@@ -10,6 +10,7 @@
  *   EdgeExtraction     :406-427  ->  Cloud::edges(curvatureThreshold)
  *   PointCloudXYZNormalToMat :163-190 -> Cloud::toMat()   (an N x 6 ppf_match_3d::Mat for PPF3DDetector / ICP)
  *   (nothing: pcl::SACSegmentation would be it)    ->  Cloud::removePlanes(params) / Cloud::applyPlanes(planes)  (the table or wall taken out)
+ *   (nothing: pcl::EuclideanClusterExtraction would be it) ->  Cloud::clusters(params, info, intr, ...)  (a plane-free cloud split into objects and their boxes)
  *   all of the above for every box of a frame  ->  Cloud::prepareFrame(boxes, n, depth, ...)  (one (object, edge) pair per box)
  *   Matching_S2B + ICP for every detection     ->  Cloud::matchFrame(models, modelClouds, dets, ...)  (ICP in one launch sequence)
  *   `// TODO: Pose Validation` (:477-479, :530-532) -> Cloud::verifyFrame(modelClouds, dets, poses, depth, ...)  (scores, best pose)
@@ -144,6 +145,38 @@ class Cloud {
     ppf_cloud* o = nullptr;
     ppf_match_3d::check(ppf_prep_planes_apply(need(), planes.empty() ? 0 : &planes[0], (int)planes.size(), &p, &o));
     return Cloud(o);
+  }
+
+  static ppf_cluster_params defaultClusterParams() {
+    ppf_cluster_params p;
+    ppf_default_cluster_params(&p);
+    return p;
+  }
+  /* This cloud -- plane-free, so after removePlanes -- split into its object clusters (ppf_prep_clusters): the connected
+   * components of "two rows are no farther apart than params->tolerance" (fp64, <=) with min_size .. max_size rows, the largest
+   * first (equal sizes: the smaller first row first), at most params->max_clusters of them, each a cloud still in HBM with its
+   * rows in ascending row index.  info (optional): one row per returned cluster; with intr = {fx, fy, ppx, ppy} and the image
+   * size its box_xywh is the cluster's image box, what prepareFrame takes as a detection's box.  labels (optional): per row the
+   * rank of its cluster or -1.  counts (optional): {clusters returned, valid components, all components}.
+   * params == 0: defaultClusterParams(). */
+  std::vector<Cloud> clusters(const ppf_cluster_params* params = 0, std::vector<ppf_cluster_info>* info = 0, const double* intr = 0,
+                              int imageRows = 0, int imageCols = 0, std::vector<int32_t>* labels = 0, int32_t* counts = 0,
+                              ppf_cluster_stats* stats = 0) const {
+    const ppf_cluster_params p = orDefaults(params, ppf_default_cluster_params);
+    const size_t slots = p.max_clusters >= 1 && p.max_clusters <= PPF_CLUSTER_MAX_CLUSTERS ? (size_t)p.max_clusters : 1;
+    const ppf_cloud* in[1] = {need()};
+    std::vector<ppf_cloud*> out(slots, (ppf_cloud*)0);
+    std::vector<ppf_cluster_info> rows(slots);
+    std::vector<int32_t> lab((size_t)size() + 1, -1);
+    int32_t* labp[1] = {&lab[0]};
+    int32_t cnt[3] = {0, 0, 0};
+    ppf_match_3d::check(ppf_prep_clusters(in, 1, &p, intr, imageRows, imageCols, &out[0], &rows[0], cnt, labels ? labp : 0, stats));
+    std::vector<Cloud> found;
+    for (int32_t r = 0; r < cnt[0]; r++) found.push_back(Cloud(out[(size_t)r]));
+    if (info) info->assign(rows.begin(), rows.begin() + cnt[0]);
+    if (labels) { lab.pop_back(); labels->swap(lab); }
+    if (counts) { counts[0] = cnt[0]; counts[1] = cnt[1]; counts[2] = cnt[2]; }
+    return found;
   }
 
   static ppf_frame_params defaultFrameParams() {

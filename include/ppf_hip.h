@@ -483,6 +483,53 @@ ppf_status ppf_prep_planes(const ppf_cloud* const* in, int n_clouds, const ppf_p
 ppf_status ppf_prep_planes_apply(const ppf_cloud* in, const ppf_plane_info* planes, int n_planes, const ppf_plane_params* p,
                                  ppf_cloud** out);
 
+/* ---- object clusters: a plane-free cloud split into its connected blobs ------------------------------ */
+#define PPF_CLUSTER_MAX_CLUSTERS 256 /* what ppf_prep_frame takes as boxes */
+
+typedef struct ppf_cluster_params {
+  float tolerance;      /* > 0, metres; default 0.02 */
+  int32_t min_size;     /* >= 1; default 100 */
+  int32_t max_size;     /* 0: no bound; default 0 */
+  int32_t max_clusters; /* 1..256; default 64 */
+  int32_t flags;        /* none defined: 0 */
+  int32_t reserved[4];
+} ppf_cluster_params;
+
+typedef struct ppf_cluster_info {
+  int32_t n_rows;
+  int32_t first_row;   /* the cluster's smallest row index in its cloud */
+  float lo[3], hi[3];  /* the minimum and maximum of its rows */
+  int32_t box_xywh[4]; /* its image box {umin, vmin, umax - umin, vmax - vmin}; zero without intrinsics or without a row of z > 0 */
+  int32_t reserved[4];
+} ppf_cluster_info;
+
+typedef struct ppf_cluster_stats {
+  int32_t n_clouds, n_launches, n_host_syncs;
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_cluster_stats;
+
+void ppf_default_cluster_params(ppf_cluster_params* p);
+/* Euclidean cluster extraction (pcl::EuclideanClusterExtraction) of n_clouds (0..256) clouds in one pass.  A row is finite iff
+ * x, y, z are; finite rows a, b are linked iff ((dx*dx + dy*dy) + dz*dz) <= (double)tolerance * (double)tolerance with
+ * dx = (double)ax - (double)bx ..., all in fp64; a component is a connected component of the links, first_row its smallest
+ * row index; it is valid iff min_size <= n_rows and (max_size == 0 or n_rows <= max_size); the valid components ranked by
+ * n_rows descending, then first_row ascending, the first min(valid, max_clusters) of them are the cloud's clusters.
+ * out: [n_clouds][max_clusters] clouds, a cluster's rows in ascending row index with normals and curvature carried byte for
+ * byte, NULL past the cloud's cluster count; they are views into one device block and are released in any order.
+ * info: [n_clouds][max_clusters], zero past the count.  With intr = {fx, fy, ppx, ppy} the image box of a cluster spans
+ * u = (int)floor((((double)x / (double)z) * fx + ppx) + 0.5), v likewise, clipped to the image, of its rows with z > 0;
+ * intr == NULL: the boxes are zero and image_rows / image_cols are ignored.  counts: [n_clouds][3] = {clusters output, valid
+ * components, all components}.  labels: NULL, or n_clouds pointers each NULL or rows(in[i]) int32: the rank of the row's
+ * cluster, or -1.  Each cloud's result is what a call with that cloud alone gives.  The launch count depends on nothing but
+ * whether any cloud has a row; the host blocks in one upload before any device work and waits for the device once
+ * (n_host_syncs 1).  A cloud whose finite extent needs more than 1,024 grid cells of 0.5773 * tolerance on an axis is
+ * PPF_ERR_INVALID (the message names the smallest tolerance that fits).  Argument errors are PPF_ERR_INVALID before any device
+ * work; on every error each out is NULL and info and counts are zero. */
+ppf_status ppf_prep_clusters(const ppf_cloud* const* in, int n_clouds, const ppf_cluster_params* p, const double* intr /* may be NULL */,
+                             int image_rows, int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts,
+                             int32_t* const* labels, ppf_cluster_stats* stats /* may be NULL */);
+
 /* ---- the organised scene cloud from a depth image, on the device (what CloudProcessor::Deprojection leaves empty) -- */
 #define PPF_DEPTH_F32 0  /* float32 metres: z = value (the reference's EXR frame) */
 #define PPF_DEPTH_U16 1  /* uint16 sensor units: z = (float)((double)d * depth_scale) (Azure Kinect, RealSense) */

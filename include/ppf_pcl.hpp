@@ -290,6 +290,78 @@ class PPFRegistration {
   bool converged_ = false;
 };
 
+/* pcl::PointXYZ's storage for builds without PCL (16 bytes: x y z 1) */
+struct PointXYZ {
+  float x, y, z, pad0;
+  PointXYZ() : x(0), y(0), z(0), pad0(1.f) {}
+  PointXYZ(float x_, float y_, float z_) : x(x_), y(y_), z(z_), pad0(1.f) {}
+};
+
+struct PointIndices {
+  std::vector<int> indices;
+};
+
+/* pcl::EuclideanClusterExtraction over ppf_prep_clusters: the connected components of "two points are no
+ * farther apart than the cluster tolerance" with MinClusterSize .. MaxClusterSize points (PCL's defaults 1 and 25000), the largest
+ * first, as PCL sorts them.  Point types only need members x, y, z.  What differs from PCL, stated: the indices inside a cluster
+ * are ascending (PCL's are in the order its search visited them); clusters of equal size come in the order of their smallest
+ * index; the predicate is (dx*dx + dy*dy) + dz*dz <= tolerance * tolerance in fp64 on the float coordinates (PCL compares a
+ * float squared distance from its k-d tree), so parity with PCL is unpinned, as for every other stage; at most 256 clusters, the
+ * largest, are returned per call; points that are not finite belong to no cluster; a search method is not needed and none is
+ * taken. */
+template <class PointT>
+class EuclideanClusterExtraction {
+ public:
+  void setClusterTolerance(double tolerance) { tolerance_ = tolerance; }
+  double getClusterTolerance() const { return tolerance_; }
+  void setMinClusterSize(int n) { min_ = n; }
+  int getMinClusterSize() const { return min_; }
+  void setMaxClusterSize(int n) { max_ = n; }
+  int getMaxClusterSize() const { return max_; }
+  template <class CloudPtr> void setInputCloud(const CloudPtr& cloud) {
+    read_ = [cloud](std::vector<float>& xyz) {
+      const auto& p = detail::pts(*cloud);
+      xyz.resize(p.size() * 3);
+      for (std::size_t i = 0; i < p.size(); i++) { xyz[i * 3] = p[i].x; xyz[i * 3 + 1] = p[i].y; xyz[i * 3 + 2] = p[i].z; }
+    };
+  }
+  void extract(std::vector<PointIndices>& clusters) {
+    clusters.clear();
+    if (!read_) throw ppf_match_3d::Error(PPF_ERR_INVALID, "EuclideanClusterExtraction: no input cloud");
+    std::vector<float> xyz;
+    read_(xyz); /* the cloud as it is now, as PCL reads through the pointer at extract() */
+    const int n = (int)(xyz.size() / 3);
+    ppf_cluster_params p;
+    ppf_default_cluster_params(&p);
+    p.tolerance = (float)tolerance_;
+    p.min_size = min_;
+    p.max_size = max_;
+    p.max_clusters = PPF_CLUSTER_MAX_CLUSTERS;
+    ppf_cloud* in = nullptr;
+    xyz.push_back(0.f);
+    ppf_match_3d::check(ppf_cloud_upload(&xyz[0], n, 3, PPF_NOFF_MAT, 3, &in));
+    std::shared_ptr<ppf_cloud> hold(in, [](ppf_cloud* c) { ppf_cloud_release(c); });
+    const ppf_cloud* ins[1] = {in};
+    std::vector<ppf_cloud*> out((std::size_t)PPF_CLUSTER_MAX_CLUSTERS, (ppf_cloud*)nullptr);
+    std::vector<ppf_cluster_info> info((std::size_t)PPF_CLUSTER_MAX_CLUSTERS);
+    std::vector<int32_t> labels((std::size_t)n + 1, -1);
+    int32_t* labp[1] = {&labels[0]};
+    int32_t counts[3] = {0, 0, 0};
+    ppf_match_3d::check(ppf_prep_clusters(ins, 1, &p, nullptr, 0, 0, &out[0], &info[0], counts, labp, nullptr));
+    for (std::size_t k = 0; k < out.size(); k++)
+      if (out[k]) ppf_cloud_release(out[k]); /* the labels are what this surface hands out */
+    clusters.resize((std::size_t)counts[0]);
+    for (int r = 0; r < counts[0]; r++) clusters[(std::size_t)r].indices.reserve((std::size_t)info[(std::size_t)r].n_rows);
+    for (int i = 0; i < n; i++)
+      if (labels[(std::size_t)i] >= 0) clusters[(std::size_t)labels[(std::size_t)i]].indices.push_back(i);
+  }
+
+ private:
+  double tolerance_ = 0.0;
+  int min_ = 1, max_ = 25000;
+  std::function<void(std::vector<float>&)> read_;
+};
+
 }  // namespace pcl_shaped
 }  // namespace ppfhip
 

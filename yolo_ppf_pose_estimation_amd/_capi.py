@@ -228,6 +228,24 @@ PPF_PLANE_NO_REFIT, PPF_PLANE_REMOVE_BEHIND = 1, 2  # PlaneParams.flags bits
 PPF_PLANE_MAX_PLANES, PPF_PLANE_MAX_HYPOTHESES = 4, 4096
 
 
+class ClusterParams(C.Structure):
+    _fields_ = [("tolerance", C.c_float), ("min_size", C.c_int32), ("max_size", C.c_int32), ("max_clusters", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class ClusterInfo(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("first_row", C.c_int32), ("lo", C.c_float * 3), ("hi", C.c_float * 3),
+                ("box_xywh", C.c_int32 * 4), ("reserved", C.c_int32 * 4)]
+
+
+class ClusterStats(C.Structure):
+    _fields_ = [("n_clouds", C.c_int32), ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32), ("ms_wall", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
+PPF_CLUSTER_MAX_CLUSTERS = 256
+
+
 # every symbol include/ppf_hip.h declares (tests/test_capi_symbols.py checks the header against this)
 _SIGNATURES = {
     "ppf_default_train_params": (None, [C.POINTER(TrainParams)]),
@@ -357,6 +375,10 @@ _SIGNATURES = {
     "ppf_prep_planes": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(PlaneParams), C.POINTER(C.c_void_p), C.POINTER(PlaneInfo),
                                   C.POINTER(C.c_void_p), C.POINTER(PlaneStats)]),
     "ppf_prep_planes_apply": (C.c_int, [C.c_void_p, C.POINTER(PlaneInfo), C.c_int, C.POINTER(PlaneParams), C.POINTER(C.c_void_p)]),
+    "ppf_default_cluster_params": (None, [C.POINTER(ClusterParams)]),
+    "ppf_prep_clusters": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(ClusterParams), C.POINTER(C.c_double), C.c_int, C.c_int,
+                                    C.POINTER(C.c_void_p), C.POINTER(ClusterInfo), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
+                                    C.POINTER(ClusterStats)]),
     "ppf_icp_register": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }

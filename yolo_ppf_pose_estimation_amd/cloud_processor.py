@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _capi
-from ._capi import (FrameDetection, FrameParams, FrameStats, IcpParams, MatchFrameStats, PlaneInfo, PlaneParams, PlaneStats, Pose,
+from ._capi import (ClusterInfo, ClusterParams, ClusterStats, FrameDetection, FrameParams, FrameStats, IcpParams, MatchFrameStats, PlaneInfo, PlaneParams, PlaneStats, Pose,
                     PoseScore, PPFError, RefineInfo,
                     RefineParams, RefineStats, RenderParams, RenderStats, SelectInfo, SelectParams, SelectStats, VerifyParams, VerifyStats,
                     check, lib)
@@ -182,6 +182,15 @@ class DeviceCloud:
         rec = np.ascontiguousarray(np.asarray(info, dtype=PLANE_INFO).reshape(-1))
         return self._stage(lib().ppf_prep_planes_apply, rec.ctypes.data_as(C.POINTER(PlaneInfo)), int(rec.shape[0]), C.byref(prm))
 
+    def clusters(self, params=None, intr=None, image_size=None, return_info: bool = False, return_labels: bool = False):
+        """this cloud's object clusters (ppf_prep_clusters with one cloud; see the module-level ``cluster_clouds``)"""
+        res = cluster_clouds([self], params, intr, image_size, return_info=return_info, return_labels=return_labels)
+        if not (return_info or return_labels):
+            return res[0]
+        n = 1 + 2 * int(return_info) + int(return_labels)   # this cloud's clusters, info rows, counts, labels
+        out = [part[0] for part in res[:n]]
+        return tuple(out + [res[-1]] if return_info else out)   # the stats last
+
     def knn(self, k: int):
         n = len(self)
         idx = np.zeros((n, k), dtype=np.int32)
@@ -222,6 +231,49 @@ def remove_planes(clouds, params=None, return_info: bool = False, return_labels:
     return tuple(res)
 
 
+# ppf_cluster_info as a numpy record
+CLUSTER_INFO = np.dtype([("n_rows", "<i4"), ("first_row", "<i4"), ("lo", "<f4", 3), ("hi", "<f4", 3), ("box_xywh", "<i4", 4),
+                         ("reserved", "<i4", 4)])
+
+
+def cluster_clouds(clouds, params=None, intr=None, image_size=None, return_info: bool = False, return_labels: bool = False):
+    """Euclidean cluster extraction of every cloud in one segmented call (ppf_prep_clusters): the connected components of
+    "two rows are no farther apart than ``tolerance``" (fp64, ``<=``), those of ``min_size .. max_size`` rows ranked by size
+    (then by their first row), the first ``max_clusters`` of them returned, each cloud's result byte-identical to a call
+    with it alone.  params: a ClusterParams, a dict of its fields (the rest default) or None.  intr: (fx, fy, ppx, ppy) or
+    the 3x3 matrix, with image_size = (rows, cols), gives every cluster its image box; without, the boxes are zero.
+    Returns one list of cluster clouds per cloud; with return_info also the info rows ((n_clouds, max_clusters) records of
+    ``CLUSTER_INFO``, zero past a cloud's count), the counts ((n_clouds, 3): clusters, valid components, all components) and,
+    last, the call's stats; with return_labels the per-row labels (int32: the cluster's rank, or -1) per cloud."""
+    prm = _cluster_params(params)
+    K = len(clouds)
+    mc = max(1, min(int(prm.max_clusters), _capi.PPF_CLUSTER_MAX_CLUSTERS))
+    ins, outs = (C.c_void_p * max(K, 1))(*[c._ptr for c in clouds]), (C.c_void_p * max(K * mc, 1))()
+    info = np.zeros((K, mc), dtype=CLUSTER_INFO)
+    counts = np.zeros((K, 3), dtype=np.int32)
+    labels = [np.full(len(c), -1, dtype=np.int32) for c in clouds] if return_labels else None
+    lab = (C.c_void_p * max(K, 1))(*[a.ctypes.data for a in labels]) if return_labels else None
+    it, rows, cols = None, 0, 0
+    if intr is not None:
+        if image_size is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "cluster_clouds: intr needs image_size = (rows, cols)")
+        it, (rows, cols) = (C.c_double * 4)(*_intr4(intr)), image_size
+    st = ClusterStats()
+    check(lib().ppf_prep_clusters(ins, K, C.byref(prm), it, int(rows), int(cols), outs, info.ctypes.data_as(C.POINTER(ClusterInfo)),
+                                  counts.ctypes.data_as(C.POINTER(C.c_int32)), lab, C.byref(st)))
+    found = [[DeviceCloud(C.c_void_p(outs[i * mc + r])) for r in range(int(counts[i, 0]))] for i in range(K)]
+    if not (return_info or return_labels):
+        return found
+    res = [found]
+    if return_info:
+        res += [info, counts]
+    if return_labels:
+        res.append(labels)
+    if return_info:
+        res.append(_capi.stats_dict(st))
+    return tuple(res)
+
+
 def _intr4(intr):
     K = np.asarray(intr, dtype=np.float64)
     return [K[0, 0], K[1, 1], K[0, 2], K[1, 2]] if K.shape == (3, 3) else [float(v) for v in K.reshape(-1)[:4]]
@@ -255,6 +307,15 @@ def _plane_params(params) -> PlaneParams:
         if unknown:
             raise PPFError(_capi.PPF_ERR_INVALID, f"unknown plane parameter(s): {', '.join(unknown)}")
     return _params(PlaneParams, "ppf_default_plane_params", params)
+
+
+def _cluster_params(params) -> ClusterParams:
+    """``_params`` for ppf_cluster_params; a key that is no field of the record (a misspelt name) is an error, not ignored"""
+    if isinstance(params, dict):
+        unknown = sorted(set(params) - {f for f, _ in ClusterParams._fields_})
+        if unknown:
+            raise PPFError(_capi.PPF_ERR_INVALID, f"unknown cluster parameter(s): {', '.join(unknown)}")
+    return _params(ClusterParams, "ppf_default_cluster_params", params)
 
 
 def _depth_image(depth, error: str):
@@ -589,6 +650,9 @@ class CloudProcessor:
         # RemovePlanes: the info rows of the planes taken out of the scene, and the counters
         self.plane_info: Optional[np.ndarray] = None
         self.plane_stats: Dict[str, object] = {}
+        # ProposeBoxes: the info rows of the scene's clusters, and the counters
+        self.cluster_info: Optional[np.ndarray] = None
+        self.cluster_stats: Dict[str, object] = {}
 
     # ---- the PCL half -------------------------------------------------------------------------------------
     def Deprojection(self, CameraIntr, fp64: bool = False) -> DeviceCloud:
@@ -609,6 +673,20 @@ class CloudProcessor:
             raise PPFError(_capi.PPF_ERR_INVALID, "RemovePlanes needs a scene cloud")
         self.scene, self.plane_info, self.plane_stats = self.scene.remove_planes(params, return_info=True)
         return self.scene
+
+    def ProposeBoxes(self, CameraIntr, params=None) -> List[DeviceCloud]:
+        """Detections without a detector: ``self.scene`` -- plane-free, so after RemovePlanes -- split into its object
+        clusters (ppf_prep_clusters) and ``self.boxes`` set to the clusters' image boxes, largest cluster first, so that
+        PrepareFrame / MatchFrame run on a bare depth frame.  CameraIntr: the 3x3 matrix as SceneCropping takes it; the
+        image is ``self.depth``'s.  params: the fields of ppf_cluster_params (tolerance, min_size, max_size, max_clusters).
+        Sets ``cluster_info`` (one row per cluster) and ``cluster_stats``; returns the cluster clouds."""
+        if self.scene is None or self.depth is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "ProposeBoxes needs a scene cloud and a depth image")
+        found, info, counts, self.cluster_stats = self.scene.clusters(params, np.asarray(CameraIntr, dtype=np.float64), self.depth.shape,
+                                                                      return_info=True)
+        self.cluster_info = info[:int(counts[0])].copy()
+        self.boxes = [tuple(int(v) for v in row["box_xywh"]) for row in self.cluster_info]
+        return found
 
     def SceneCropping(self, CameraIntr) -> List[DeviceCloud]:
         """CameraIntr: 3x3 matrix (fx, fy on the diagonal, ppx, ppy in the last column), as the reference passes it"""

@@ -1,0 +1,259 @@
+/*
+ * ppf_cluster_host.h — host side of ppf_prep_clusters: the connected blobs of up to 256 plane-free clouds in one pass
+ * (DESIGN.md §20).  Kernels: ppf_cluster_kernels.h.  Included by ppf_hip.hip after ppf_prep_host.h (ppf_cloud, FrameRun,
+ * frame_scan).
+ *
+ * Per call: one upload of the segment table before any device work, then k_clu_bounds, k_clu_grid, k_clu_keys, the sort by
+ * (segment, cell) (five digit passes of seven launches and one gather), k_clu_runs, the scan, k_clu_cells, k_clu_link,
+ * k_clu_flatten, k_clu_valid, the ranking's sort (the same five passes), k_clu_rank, k_clu_labels, the gather's sort (three
+ * passes), k_clu_gather and k_clu_reduce: 110 launches whatever the clouds hold, none when no cloud has a row.
+ * Nothing the device counts (cells, components, clusters) comes to the host before the end: grids are sized for the rows and
+ * workgroups past a device-side count leave.  The host waits once, for the cluster heads, the reductions, the counts, the
+ * grids and the labels; the outputs are views into one block sized for the input, so nothing is allocated after that wait.
+ */
+#ifndef PPF_CLUSTER_HOST_H
+#define PPF_CLUSTER_HOST_H
+
+namespace {
+
+ppf_status cluster_params_check(const char* who, const ppf_cluster_params* p) {
+  if (!p) return fail(PPF_ERR_INVALID, "%s: the params are NULL", who);
+  if (!(std::isfinite(p->tolerance) && p->tolerance > 0.f)) return fail(PPF_ERR_INVALID, "%s: tolerance must be finite and > 0", who);
+  if (p->min_size < 1) return fail(PPF_ERR_INVALID, "%s: min_size is %d (>= 1)", who, p->min_size);
+  if (p->max_size < 0) return fail(PPF_ERR_INVALID, "%s: max_size is %d (>= 0; 0: no bound)", who, p->max_size);
+  if (p->max_clusters < 1 || p->max_clusters > PPF_CLUSTER_MAX_CLUSTERS)
+    return fail(PPF_ERR_INVALID, "%s: max_clusters is %d (1..%d)", who, p->max_clusters, PPF_CLUSTER_MAX_CLUSTERS);
+  if (p->flags) return fail(PPF_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)p->flags);
+  return PPF_OK;
+}
+
+/* stable LSD passes over the digits at `shifts` of keys ka (values va); the sorted arrays end in ka / va */
+ppf_status cluster_sort(FrameRun& fr, uint32_t*& ka, uint32_t*& va, uint32_t*& kb, uint32_t*& vb, int n, uint32_t* hist, uint32_t* offs,
+                        const int* shifts, int passes) {
+  const int nblk = (n + RS_BLOCK - 1) / RS_BLOCK;
+  ppf_status s;
+  for (int pass = 0; pass < passes; pass++) {
+    FRAME_LAUNCH(fr, k_rs_hist, dim3(nblk), dim3(RS_BLOCK), ka, n, shifts[pass], nblk, hist);
+    HIPCHK(hipGetLastError());
+    if ((s = frame_scan(fr, hist, offs, (size_t)256 * nblk)) != PPF_OK) return s;
+    FRAME_LAUNCH(fr, k_rs_scatter, dim3(nblk), dim3(RS_BLOCK), ka, va, n, shifts[pass], nblk, offs, kb, vb);
+    HIPCHK(hipGetLastError());
+    std::swap(ka, kb);
+    std::swap(va, vb);
+  }
+  return PPF_OK;
+}
+/* by a 32-bit key, then by segment: a segment's rows end up together, in key order, equal keys in row order */
+ppf_status cluster_sort_segmented(FrameRun& fr, uint32_t*& ka, uint32_t*& va, uint32_t*& kb, uint32_t*& vb, int n, uint32_t* hist,
+                                  uint32_t* offs, const uint32_t* skey) {
+  static const int shifts[5] = {0, 8, 16, 24, 0};
+  ppf_status s;
+  if ((s = cluster_sort(fr, ka, va, kb, vb, n, hist, offs, shifts, 4)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_frame_gather_u32, grid_for(n, 256), dim3(256), skey, va, n, ka);
+  return cluster_sort(fr, ka, va, kb, vb, n, hist, offs, shifts + 4, 1);
+}
+
+/* the smallest float tolerance whose grid holds an extent in CLU_AXIS cells */
+float cluster_smallest_tolerance(double extent) {
+  float t = (float)(extent / ((double)CLU_AXIS * CLU_CELL));
+  auto fits = [&](float v) { return v > 0.f && clu_axis_cells(0.0, extent, (double)v * CLU_CELL) <= (uint32_t)CLU_AXIS; };
+  while (!fits(t)) t = std::nextafter(t, INFINITY);
+  while (fits(std::nextafter(t, 0.f))) t = std::nextafter(t, 0.f);
+  return t;
+}
+
+/* fr and blk belong to the caller: on an error they outlive the wait for what was launched */
+ppf_status clusters_enqueue(FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, const ppf_cloud* const* in, int K, const ppf_cluster_params& p,
+                            const double* intr, int image_rows, int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts,
+                            int32_t* const* labels, ppf_cluster_stats& st) {
+  static const char* who = "ppf_prep_clusters";
+  const int MC = p.max_clusters;
+  std::vector<CluSeg> tab((size_t)K);
+  size_t N = 0;
+  for (int i = 0; i < K; i++) {
+    tab[i] = CluSeg{in[i]->rows.p, in[i]->curv.p, (uint32_t)N, (uint32_t)in[i]->n};
+    N += (size_t)in[i]->n;
+    if (N >= 0x7fffffffull) return fail(PPF_ERR_INVALID, "%s: the clouds hold more than INT32_MAX rows together", who);
+  }
+  if (N == 0) return PPF_OK; /* no cloud has a row: no cluster, no launch */
+  const int n = (int)N, nblk = (n + RS_BLOCK - 1) / RS_BLOCK;
+  const size_t slots = (size_t)K * MC;
+  CluSeg* d_tab;
+  CluGrid* d_grid;
+  float4* pts;
+  unsigned long long* ckey;
+  uint32_t *zero, *lkey, *skey, *k1, *k2, *v1, *v2, *hist, *offs, *parent, *size, *root, *flags, *runid, *cstart;
+  int32_t *rank, *d_labels;
+  /* one zeroed block: the bounds, the counts, the cluster heads, the reductions */
+  const size_t z_mm = 0, z_fin = z_mm + (size_t)K * 6, z_cnt = z_fin + K, z_head = z_cnt + (size_t)K * 2, z_acc = z_head + slots * 2,
+               z_words = (z_acc + slots * CLU_ACC + 3) & ~(size_t)3;
+  ppf_status s;
+  if ((s = fr.get(K, &d_tab)) != PPF_OK || (s = fr.get(K, &d_grid)) != PPF_OK || (s = fr.get(z_words, &zero)) != PPF_OK ||
+      (s = fr.get(N, &pts)) != PPF_OK || (s = fr.get(N + 1, &ckey)) != PPF_OK || (s = fr.get(N, &lkey)) != PPF_OK ||
+      (s = fr.get(N, &skey)) != PPF_OK || (s = fr.get(N, &k1)) != PPF_OK || (s = fr.get(N, &k2)) != PPF_OK || (s = fr.get(N, &v1)) != PPF_OK ||
+      (s = fr.get(N, &v2)) != PPF_OK || (s = fr.get((size_t)256 * nblk, &hist)) != PPF_OK || (s = fr.get((size_t)256 * nblk, &offs)) != PPF_OK ||
+      (s = fr.get(N, &parent)) != PPF_OK || (s = fr.get(N, &size)) != PPF_OK || (s = fr.get(N, &root)) != PPF_OK ||
+      (s = fr.get(N + 1, &flags)) != PPF_OK || (s = fr.get(N + 1, &runid)) != PPF_OK || (s = fr.get(N + 2, &cstart)) != PPF_OK ||
+      (s = fr.get(N, &rank)) != PPF_OK || (s = fr.get(N, &d_labels)) != PPF_OK)
+    return s;
+  blk.reset(new DevBuf<float>());
+  HIPCHK(blk->reserve(N * 7)); /* [rows | curvature] */
+  HIPCHK(hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(CluSeg), hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(zero, 0, z_words * sizeof(uint32_t), nullptr));
+  uint32_t *mm = zero + z_mm, *fin = zero + z_fin, *cnt = zero + z_cnt, *acc = zero + z_acc;
+  int32_t* head = reinterpret_cast<int32_t*>(zero + z_head);
+
+  const dim3 b256(CLU_BLOCK), rows_grid = grid_for(N, CLU_BLOCK), rows1_grid = grid_for(N + 1, CLU_BLOCK);
+  const double tol = (double)p.tolerance, h = tol * CLU_CELL;
+  CluIntr cam = {0.0, 0.0, 0.0, 0.0, image_rows, image_cols, intr ? 1 : 0};
+  if (intr) { cam.fx = intr[0]; cam.fy = intr[1]; cam.ppx = intr[2]; cam.ppy = intr[3]; }
+
+  FRAME_LAUNCH(fr, k_clu_bounds, dim3((unsigned)K, CLU_BOUNDS_WGS), b256, d_tab, mm, fin);
+  FRAME_LAUNCH(fr, k_clu_grid, dim3(1), dim3(FRAME_MAX_BOXES), mm, fin, K, h, d_grid);
+  FRAME_LAUNCH(fr, k_clu_keys, rows_grid, b256, d_tab, K, (uint32_t)N, d_grid, lkey, k1, skey, v1, parent, size);
+  HIPCHK(hipGetLastError());
+  uint32_t *ka = k1, *va = v1, *kb = k2, *vb = v2;
+  if ((s = cluster_sort_segmented(fr, ka, va, kb, vb, n, hist, offs, skey)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_clu_runs, rows1_grid, b256, d_tab, K, (uint32_t)N, va, lkey, skey, pts, flags);
+  HIPCHK(hipGetLastError());
+  if ((s = frame_scan(fr, flags, runid, N + 1)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_clu_cells, rows1_grid, b256, (uint32_t)N, va, lkey, skey, flags, runid, ckey, cstart);
+  FRAME_LAUNCH(fr, k_clu_link, dim3((unsigned)N), dim3(64), pts, ckey, cstart, runid + N, tol * tol, parent);
+  FRAME_LAUNCH(fr, k_clu_flatten, rows_grid, b256, (uint32_t)N, lkey, parent, root, size);
+  FRAME_LAUNCH(fr, k_clu_valid, rows_grid, b256, d_tab, K, (uint32_t)N, root, size, (uint32_t)p.min_size, (uint32_t)p.max_size, ka, va, cnt);
+  HIPCHK(hipGetLastError());
+  if ((s = cluster_sort_segmented(fr, ka, va, kb, vb, n, hist, offs, skey)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_clu_rank, rows_grid, b256, d_tab, K, (uint32_t)N, va, cnt, size, MC, rank, head);
+  FRAME_LAUNCH(fr, k_clu_labels, rows_grid, b256, (uint32_t)N, skey, root, rank, d_labels, ka, va);
+  HIPCHK(hipGetLastError());
+  static const int shifts3[3] = {0, 8, 16};
+  if ((s = cluster_sort(fr, ka, va, kb, vb, n, hist, offs, shifts3, 3)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_clu_gather, rows_grid, b256, d_tab, (uint32_t)N, ka, va, blk->p, blk->p + N * 6);
+  FRAME_LAUNCH(fr, k_clu_reduce, rows_grid, b256, d_tab, (uint32_t)N, ka, va, cam, MC, acc);
+  HIPCHK(hipGetLastError());
+
+  /* the one wait */
+  std::vector<uint32_t> z(z_words);
+  std::vector<CluGrid> grid((size_t)K);
+  std::vector<int32_t> lab;
+  bool want_labels = false;
+  for (int i = 0; labels && i < K; i++) want_labels = want_labels || labels[i];
+  HIPCHK(hipMemcpyAsync(z.data(), zero, z_words * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
+  HIPCHK(hipMemcpyAsync(grid.data(), d_grid, grid.size() * sizeof(CluGrid), hipMemcpyDeviceToHost, nullptr));
+  if (want_labels) {
+    lab.resize(N);
+    HIPCHK(hipMemcpyAsync(lab.data(), d_labels, N * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
+  }
+  fr.syncs++;
+  HIPCHK(hipStreamSynchronize(nullptr));
+  for (int i = 0; i < K; i++) {
+    if (grid[i].ok) continue;
+    const uint32_t* m = &z[z_mm + (size_t)i * 6];
+    double ext = 0.0;
+    for (int k = 0; k < 3; k++) ext = std::max(ext, (double)ordered_to_float(m[3 + k]) - (double)ordered_to_float(~m[k]));
+    return fail(PPF_ERR_INVALID, "%s: in[%d] spans %g m, %u cells of its grid on an axis (at most %d); the smallest tolerance that fits is %.9g",
+                who, i, ext, std::max(grid[i].cells[0], std::max(grid[i].cells[1], grid[i].cells[2])), CLU_AXIS,
+                (double)cluster_smallest_tolerance(ext));
+  }
+  std::vector<std::unique_ptr<ppf_cloud>> res(slots);
+  size_t at = 0; /* the clusters lie in the block one after the other, in (cloud, rank) order */
+  for (int i = 0; i < K; i++) {
+    const uint32_t valid = z[z_cnt + (size_t)i * 2], all = z[z_cnt + (size_t)i * 2 + 1], shown = std::min(valid, (uint32_t)MC);
+    counts[i * 3] = (int32_t)shown;
+    counts[i * 3 + 1] = (int32_t)valid;
+    counts[i * 3 + 2] = (int32_t)all;
+    for (uint32_t r = 0; r < shown; r++) {
+      const size_t slot = (size_t)i * MC + r;
+      ppf_cluster_info& ci = info[slot];
+      const uint32_t* a = &z[z_acc + slot * CLU_ACC];
+      ci.n_rows = (int32_t)z[z_head + slot * 2];
+      ci.first_row = (int32_t)z[z_head + slot * 2 + 1];
+      for (int k = 0; k < 3; k++) {
+        ci.lo[k] = ordered_to_float(~a[k]);
+        ci.hi[k] = ordered_to_float(a[3 + k]);
+      }
+      if (a[7]) { /* a row with z > 0 gave a pixel */
+        const int32_t u0 = (int32_t)~a[6], u1 = (int32_t)a[7] - 1, v0 = (int32_t)~a[8], v1p = (int32_t)a[9] - 1;
+        ci.box_xywh[0] = u0; ci.box_xywh[1] = v0; ci.box_xywh[2] = u1 - u0; ci.box_xywh[3] = v1p - v0;
+      }
+      res[slot].reset(new ppf_cloud());
+      res[slot]->n = ci.n_rows;
+      res[slot]->shared = blk;
+      res[slot]->rows.p = blk->p + at * 6;
+      res[slot]->curv.p = blk->p + N * 6 + at;
+      at += (size_t)ci.n_rows;
+    }
+    if (want_labels && labels[i] && tab[i].n) std::memcpy(labels[i], lab.data() + tab[i].off, (size_t)tab[i].n * sizeof(int32_t));
+  }
+  for (size_t k = 0; k < slots; k++) out[k] = res[k].release();
+  st.n_launches = fr.launches;
+  st.n_host_syncs = fr.syncs;
+  return PPF_OK;
+}
+
+ppf_status clusters_run(const ppf_cloud* const* in, int K, const ppf_cluster_params& p, const double* intr, int image_rows, int image_cols,
+                        ppf_cloud** out, ppf_cluster_info* info, int32_t* counts, int32_t* const* labels, ppf_cluster_stats& st) {
+  FrameRun fr;
+  std::shared_ptr<DevBuf<float>> blk;
+  const ppf_status s = clusters_enqueue(fr, blk, in, K, p, intr, image_rows, image_cols, out, info, counts, labels, st);
+  /* kernels of a failed call may still run: wait before its scratch and the output block go back to the block cache,
+   * where another host thread could be handed them */
+  if (s != PPF_OK) (void)hipDeviceSynchronize();
+  return s;
+}
+
+}  // namespace
+
+extern "C" {
+
+void ppf_default_cluster_params(ppf_cluster_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->tolerance = 0.02f;
+  p->min_size = 100;
+  p->max_size = 0;
+  p->max_clusters = 64;
+}
+
+ppf_status ppf_prep_clusters(const ppf_cloud* const* in, int n_clouds, const ppf_cluster_params* p, const double* intr, int image_rows,
+                             int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts, int32_t* const* labels,
+                             ppf_cluster_stats* stats) {
+  static const char* who = "ppf_prep_clusters";
+  const auto t0 = std::chrono::steady_clock::now();
+  ppf_cluster_stats local;
+  ppf_cluster_stats& st = stats ? *stats : local;
+  std::memset(&st, 0, sizeof(st));
+  const bool count_ok = n_clouds >= 0 && n_clouds <= FRAME_MAX_BOXES;
+  const size_t slots = count_ok ? (size_t)n_clouds * (size_t)(p ? std::min(std::max(p->max_clusters, 1), PPF_CLUSTER_MAX_CLUSTERS) : 1) : 0;
+  auto clear = [&]() {
+    for (size_t k = 0; out && k < slots; k++) out[k] = nullptr;
+    if (info && slots) std::memset(info, 0, slots * sizeof(ppf_cluster_info));
+    if (counts && count_ok && n_clouds) std::memset(counts, 0, (size_t)n_clouds * 3 * sizeof(int32_t));
+  };
+  clear();
+  if (!count_ok) return fail(PPF_ERR_INVALID, "%s: n_clouds is %d (0..%d)", who, n_clouds, FRAME_MAX_BOXES);
+  if (!in || !out || !info || !counts) return fail(PPF_ERR_INVALID, "%s: in, out, info and counts must not be NULL", who);
+  ppf_status s = cluster_params_check(who, p);
+  if (s != PPF_OK) return s;
+  if (intr) {
+    for (int k = 0; k < 4; k++)
+      if (!std::isfinite(intr[k])) return fail(PPF_ERR_INVALID, "%s: the intrinsics are not finite", who);
+    if (image_rows < 1 || image_cols < 1) return fail(PPF_ERR_INVALID, "%s: the image is %d x %d", who, image_rows, image_cols);
+  }
+  for (int i = 0; i < n_clouds; i++)
+    if (!in[i]) return fail(PPF_ERR_INVALID, "%s: in[%d] is NULL", who, i);
+  if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
+  st.n_clouds = n_clouds;
+  if (n_clouds > 0) s = clusters_run(in, n_clouds, *p, intr, image_rows, image_cols, out, info, counts, labels, st);
+  if (s != PPF_OK) {
+    clear();
+    std::memset(&st, 0, sizeof(st));
+    return s;
+  }
+  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PPF_OK;
+}
+
+}  // extern "C"
+
+#endif /* PPF_CLUSTER_HOST_H */
