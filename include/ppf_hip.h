@@ -345,10 +345,21 @@ ppf_status ppf_workspace_results(ppf_workspace* ws, ppf_vote* votes, ppf_pose* r
 /* exact per-reference-point counters of the last call: accumulator increments and pairs hashed */
 ppf_status ppf_workspace_ref_counters(ppf_workspace* ws, uint64_t* votes_per_ref, uint64_t* pairs_per_ref, int cap);
 /* Full accumulators (n_ref x n_model*num_angles u32, the reference's `accumulator` array before its
- * argmax scan) of the voted reference points; presampled clouds only.  Debug / parity surface. */
+ * argmax scan) of the voted reference points; presampled clouds only.  Debug / parity surface: the tests compare
+ * every cell with the CPU oracle's accumulator, on every voting path (direct items and count tables, 16- and 32-bit
+ * cells, the re-vote after a 16-bit overflow, several tiles, staging segments, group rounds and batches, repeated
+ * calls), on scenes with planted pairs whose alpha bin is num_angles: the vote that spills into the next model
+ * row's bin 0, at a tile's half boundary, at a tile boundary, and behind the last row, where it is dropped.
+ * ppf_debug_accumulators runs the call on a fresh workspace (cold, default options). */
 ppf_status ppf_debug_accumulators(const ppf_model* m, const float* scene, int ns, int sstride, int snoff, const float* edge, int ne,
                                   int estride, int enoff, const ppf_match_params* params, uint32_t* acc, size_t cap_words,
                                   int* n_ref);
+/* The same on the caller's workspace (the host buffers go through the default stream): the call runs with the workspace's
+ * options, its learned pool estimates and its 16/32-bit decision, is repeated when a pool runs out (the dump starts from
+ * zeros again), and leaves its results readable through ppf_workspace_results and ppf_workspace_ref_counters. */
+ppf_status ppf_debug_accumulators_ws(const ppf_model* m, ppf_workspace* ws, const float* scene, int ns, int sstride, int snoff,
+                                     const float* edge, int ne, int estride, int enoff, const ppf_match_params* params, uint32_t* acc,
+                                     size_t cap_words, int* n_ref);
 /* Size of the cached device block a request of `bytes` is served from (host only, no device needed): classes of 1/8
  * octave, so at most 12.5 % more than asked for.  Test surface of the block cache's keying. */
 size_t ppf_debug_block_size(size_t bytes);

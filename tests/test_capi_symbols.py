@@ -86,6 +86,14 @@ def test_argument_validation_precedes_any_device_work(bottle):
     lib().ppf_default_train_params(C.byref(tp))
     assert lib().ppf_model_train(None, 10, 6, 3, C.byref(tp), C.byref(out)) == _capi.PPF_ERR_INVALID
     assert "bad argument" in _capi.last_error()
+    mp, acc = MatchParams(), np.zeros(8, dtype=np.uint32)
+    lib().ppf_default_match_params(C.byref(mp))
+    mp.presampled = 1
+    pts = np.ascontiguousarray(bottle[:10], dtype=np.float32)
+    fake_model = C.c_void_p(16)  # never dereferenced: the NULL workspace is refused first
+    assert lib().ppf_debug_accumulators_ws(fake_model, None, pts.ctypes.data, 10, 6, 3, None, 0, 6, 3, C.byref(mp), acc.ctypes.data,
+                                           acc.size, None) == _capi.PPF_ERR_INVALID
+    assert "bad argument" in _capi.last_error()
 
 
 def _write_model_file(path, n_ref=2, junk=b""):

@@ -138,12 +138,13 @@ def columns(ys):
 
 
 def check_scene(rings, det, scene, refs=(0,)):
-    """Device accumulators of the reference points `refs` (auto and direct voting, 16- and 32-bit cells through the
-    triples) against the oracle's, cell by cell; returns the statistics of an automatic run over those reference points."""
+    """Device accumulators of the reference points `refs` (auto and direct voting, 16- and 32-bit cells) against the
+    oracle's, cell by cell, and the triples of every reference point; returns the statistics of an automatic run over those reference points."""
     n = scene.shape[0]
     want_all = rings.ora.match(scene, relative_scene_sample_step=1.0, presampled=True, cluster=False)
+    want_acc = {}
     for r in refs:
-        want = rings.ora.accumulator(scene, r)
+        want = want_acc[r] = rings.ora.accumulator(scene, r)
         a0 = det.accumulators(scene, 1.0, ref_offset=r, ref_stride=n, vote_mode=0)
         a1 = det.accumulators(scene, 1.0, ref_offset=r, ref_stride=n, vote_mode=1)
         assert a0.shape[0] == 1
@@ -161,6 +162,10 @@ def check_scene(rings, det, scene, refs=(0,)):
         res = ws.results(n)
         np.testing.assert_array_equal(res["triples"], want_all["triples"])
         assert res["stats"]["n_votes"] == int(want_all["votes_per_ref"].sum())
+        for r in refs:  # and cell by cell, on the same workspace
+            a32 = ws.accumulators(det, scene, 1.0, ref_offset=r, ref_stride=n, vote_mode=mode)
+            assert a32.shape[0] == 1 and ws.stats()["n_acc32_items"] == det.info()["n_tiles"]
+            np.testing.assert_array_equal(a32[0], want_acc[r])
     one = det.raw_votes(scene, 1.0, 0.05, presampled=True, ref_offset=refs[0], ref_stride=n, vote_mode=0)
     assert one["n_ref"] == 1
     np.testing.assert_array_equal(one["triples"][0], want_all["triples"][refs[0]])

@@ -619,34 +619,54 @@ ppf_status ppf_workspace_ref_counters(ppf_workspace* ws, uint64_t* votes_per_ref
   return PPF_OK;
 }
 
-ppf_status ppf_debug_accumulators(const ppf_model* m, const float* scene, int ns, int sstride, int snoff, const float* edge, int ne,
-                                  int estride, int enoff, const ppf_match_params* params, uint32_t* acc, size_t cap_words,
-                                  int* n_ref) {
-  if (!m || !acc || !params) return fail(PPF_ERR_INVALID, "ppf_debug_accumulators: bad argument");
+/* the dump runs on the caller's workspace: its options (32-bit cells, staging segments, group rounds, batches, pool fractions),
+ * its learned pool estimates and its 16/32-bit decision all apply, and the call's results stay readable through
+ * ppf_workspace_results / ppf_workspace_ref_counters.  ws->acc_dump is set for this one call and cleared on every way out. */
+ppf_status ppf_debug_accumulators_ws(const ppf_model* m, ppf_workspace* ws, const float* scene, int ns, int sstride, int snoff,
+                                     const float* edge, int ne, int estride, int enoff, const ppf_match_params* params, uint32_t* acc,
+                                     size_t cap_words, int* n_ref) {
+  if (!m || !ws || !acc || !params) return fail(PPF_ERR_INVALID, "ppf_debug_accumulators: bad argument");
   ppf_match_params p = *params;
   const size_t per_ref = (size_t)m->info.n_ref * m->info.num_angles;
+  if (!(p.relative_scene_sample_step <= 1 && p.relative_scene_sample_step > 0) || p.ref_stride < 1 || p.ref_offset < 0 || ns <= 0)
+    return fail(PPF_ERR_INVALID, "ppf_debug_accumulators: bad argument");
   const int scene_step = (int)(1.0 / p.relative_scene_sample_step);
   if (!p.presampled) return fail(PPF_ERR_INVALID, "ppf_debug_accumulators: presampled clouds only");
   const int n_ref_total = (ns + scene_step - 1) / scene_step;
   const int nr = n_ref_total > p.ref_offset ? (n_ref_total - p.ref_offset + p.ref_stride - 1) / p.ref_stride : 0;
   if (cap_words < per_ref * nr) return fail(PPF_ERR_CAPACITY, "ppf_debug_accumulators: need %zu words", per_ref * nr);
   DevBuf<uint32_t> dump;
+  struct Reset { /* also after an error: a later call of the workspace must not write into a block that went back to the cache */
+    ppf_workspace* w;
+    ~Reset() { w->acc_dump = nullptr; }
+  } reset{ws};
   HIPCHK(dump.reserve(std::max<size_t>(per_ref * nr, 1)));
   HIPCHK(hipMemset(dump.p, 0, per_ref * nr * sizeof(uint32_t)));
-  ppf_workspace ws;
-  ws.acc_dump = dump.p;
+  ws->acc_dump = dump.p;
   p.skip_clustering = 1;
-  ppf_status s = run_host(m, scene, ns, sstride, snoff, edge, ne, estride, enoff, &p, &ws);
-  if (s != PPF_OK) return s;
-  /* a cold workspace sizes its pools from estimates: when one ran out, runs were left out of the vote and the dump is incomplete.
+  ppf_status s = run_host(m, scene, ns, sstride, snoff, edge, ne, estride, enoff, &p, ws);
+  /* a workspace sizes its pools from estimates: when one ran out, runs were left out of the vote and the dump is incomplete.
    * workspace_finish reads the flag and repeats the call with bigger pools (match_prepared clears the dump first) -- without it
    * this entry returned a partial accumulator whenever the table pool's first guess was too small, depending on which
    * reference points reached the pool first */
-  if ((s = workspace_finish(&ws)) != PPF_OK) return s;
+  if (s == PPF_OK) s = workspace_finish(ws);
+  if (s != PPF_OK) {
+    if (have_device()) (void)hipDeviceSynchronize(); /* nothing may still write the dump when it goes back to the block cache */
+    return s;
+  }
   HIPCHK(hipStreamSynchronize(nullptr));
   HIPCHK(hipMemcpy(acc, dump.p, per_ref * nr * sizeof(uint32_t), hipMemcpyDeviceToHost));
   if (n_ref) *n_ref = nr;
   return PPF_OK;
+}
+
+/* the same on a fresh workspace: cold, default options */
+ppf_status ppf_debug_accumulators(const ppf_model* m, const float* scene, int ns, int sstride, int snoff, const float* edge, int ne,
+                                  int estride, int enoff, const ppf_match_params* params, uint32_t* acc, size_t cap_words,
+                                  int* n_ref) {
+  if (!m || !acc || !params) return fail(PPF_ERR_INVALID, "ppf_debug_accumulators: bad argument");
+  ppf_workspace ws;
+  return ppf_debug_accumulators_ws(m, &ws, scene, ns, sstride, snoff, edge, ne, estride, enoff, params, acc, cap_words, n_ref);
 }
 
 /* the block cache's size class for a request (host only): what DevBuf is granted for `bytes` */

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import BatchStats, MatchStats, Pose, Vote, check, lib
-from .detector import Pose3D, PPF3DDetector
+from .detector import Pose3D, PPF3DDetector, _cloud
 
 POSE_WORDS = C.sizeof(Pose) // 8  # a ppf_pose record as float64 words (27)
 
@@ -85,6 +85,27 @@ class Workspace:
         p = np.zeros(cap, dtype=np.uint64)
         check(lib().ppf_workspace_ref_counters(self.ptr, v.ctypes.data, p.ctypes.data, cap))
         return v, p
+
+    def accumulators(self, det: PPF3DDetector, scene: np.ndarray, step: float, *, edge: Optional[np.ndarray] = None,
+                     ref_offset: int = 0, ref_stride: int = 1, vote_mode: int = 0) -> np.ndarray:
+        """Full Hough accumulators (n_ref, N_m, numAngles) of presampled host clouds, voted on this workspace: its options,
+        its learned pool sizes, its 16/32-bit decision (ppf_debug_accumulators_ws).  results() / ref_counters() then return
+        the same call's triples and counters."""
+        det._require_trained()
+        sc = _cloud(scene, "scene")
+        ed = _cloud(edge, "edge") if edge is not None else None
+        mp = det._params(step, 0.05, True, ref_offset, ref_stride, True, vote_mode)
+        mi = det.info()
+        stride = int(1.0 / step)
+        n_tot = (sc.shape[0] + stride - 1) // stride
+        nr = max((n_tot - ref_offset + ref_stride - 1) // ref_stride, 0)
+        acc = np.zeros((max(nr, 1), mi["n_ref"], mi["num_angles"]), dtype=np.uint32)
+        n = C.c_int(0)
+        check(lib().ppf_debug_accumulators_ws(det._model.ptr, self.ptr, sc.ctypes.data, sc.shape[0], sc.shape[1], 3,
+                                              ed.ctypes.data if ed is not None else None,
+                                              ed.shape[0] if ed is not None else 0, ed.shape[1] if ed is not None else 6, 3,
+                                              C.byref(mp), acc.ctypes.data, acc.size, C.byref(n)))
+        return acc[: n.value]
 
     def device_poses(self):
         ptr = C.c_void_p()
