@@ -3,6 +3,7 @@
  * ppf_hip.h): the PCL half of the reference's ppf::CloudProcessor (/root/reference/include/CloudProcessing.h)
  *
  *   Deprojection       :262      ->  Cloud::fromDepth(depth, rows, cols, fx, fy, ppx, ppy) / fromDepthU16(..., scale, ...)
+ *   (nothing: pcl::IntegralImageNormalEstimation would be it) ->  Cloud::fromDepth(depth, rows, cols, normalParams, fx, ...)  (with normals and curvature)
  *   SceneCropping      :263-339  ->  Cloud::crop(box, depth, rows, cols, fx, fy, ppx, ppy)
  *   Subsampling        :361-380  ->  Cloud::voxelGrid(leaf)
  *   OutlierProcessing  :341-360  ->  Cloud::outlierRemoval(meanK, stddevMul)
@@ -64,6 +65,23 @@ class Cloud {
   static Cloud fromDepthU16(const uint16_t* depth, int rows, int cols, double scale, double fx, double fy, double ppx, double ppy,
                             float zMin = 0.f, float zMax = 0.f, bool fp64 = false, size_t rowPitchBytes = 0) {
     return fromDepthImage(depth, PPF_DEPTH_U16, scale, rows, cols, fx, fy, ppx, ppy, zMin, zMax, fp64, rowPitchBytes);
+  }
+  static ppf_depth_normal_params defaultDepthNormalParams() {
+    ppf_depth_normal_params p;
+    ppf_default_depth_normal_params(&p);
+    return p;
+  }
+  /* the same clouds with the normal and curvature of a plane fit over each pixel's (2 radius + 1)^2 image window
+   * (ppf_cloud_from_depth_normals): what crop, removePlanes, clusters, edges and toMat carry.  A pixel with fewer than
+   * min_neighbours neighbours gets NaNs, or with PPF_DEPTH_NORMALS_DROP no row. */
+  static Cloud fromDepth(const float* depth, int rows, int cols, const ppf_depth_normal_params& normals, double fx, double fy,
+                         double ppx, double ppy, float zMin = 0.f, float zMax = 0.f, bool fp64 = false, size_t rowPitchBytes = 0) {
+    return fromDepthImage(depth, PPF_DEPTH_F32, 0.001, rows, cols, fx, fy, ppx, ppy, zMin, zMax, fp64, rowPitchBytes, &normals);
+  }
+  static Cloud fromDepthU16(const uint16_t* depth, int rows, int cols, double scale, const ppf_depth_normal_params& normals, double fx,
+                            double fy, double ppx, double ppy, float zMin = 0.f, float zMax = 0.f, bool fp64 = false,
+                            size_t rowPitchBytes = 0) {
+    return fromDepthImage(depth, PPF_DEPTH_U16, scale, rows, cols, fx, fy, ppx, ppy, zMin, zMax, fp64, rowPitchBytes, &normals);
   }
 
   bool empty() const { return size() == 0; }
@@ -451,7 +469,8 @@ class Cloud {
   static P orDefaults(const P* given, void (*defaults)(P*)) { P p; if (given) p = *given; else defaults(&p); return p; }
   explicit Cloud(ppf_cloud* c) : h_(c, [](ppf_cloud* p) { ppf_cloud_release(p); }) {}
   static Cloud fromDepthImage(const void* depth, int format, double scale, int rows, int cols, double fx, double fy, double ppx,
-                              double ppy, float zMin, float zMax, bool fp64, size_t rowPitchBytes) {
+                              double ppy, float zMin, float zMax, bool fp64, size_t rowPitchBytes,
+                              const ppf_depth_normal_params* normals = 0) {
     ppf_depth_params p;
     ppf_default_depth_params(&p);
     p.format = format;
@@ -461,7 +480,8 @@ class Cloud {
     p.z_max = zMax;
     const double intr[4] = {fx, fy, ppx, ppy};
     ppf_cloud* c = nullptr;
-    ppf_match_3d::check(ppf_cloud_from_depth(depth, rows, cols, rowPitchBytes, intr, &p, &c));
+    ppf_match_3d::check(normals ? ppf_cloud_from_depth_normals(depth, rows, cols, rowPitchBytes, intr, &p, normals, &c)
+                                : ppf_cloud_from_depth(depth, rows, cols, rowPitchBytes, intr, &p, &c));
     return Cloud(c);
   }
   const ppf_cloud* need() const {

@@ -570,6 +570,37 @@ ppf_status ppf_cloud_from_depth(const void* depth, int rows, int cols, size_t ro
 ppf_status ppf_cloud_from_depth_device(const void* d_depth, int rows, int cols, size_t row_pitch_bytes, const double* intr,
                                        const ppf_depth_params* p, void* stream, ppf_cloud** out);
 
+/* ---- the same cloud with normals and curvature from the image's own neighbourhoods ----------------- */
+#define PPF_DEPTH_NORMALS_DROP 1 /* flags: rows without a normal are left out of the cloud */
+#define PPF_DEPTH_NORMALS_MAX_RADIUS 8
+typedef struct ppf_depth_normal_params {
+  int32_t radius;         /* 1..8: the window is (2r+1) x (2r+1) pixels; default 3 */
+  float max_depth_change; /* finite, > 0, relative to the pixel's own z; default 0.02 */
+  int32_t min_neighbours; /* 3..(2r+1)^2, the pixel itself counts; default 3 */
+  int32_t flags;          /* 0 | PPF_DEPTH_NORMALS_DROP */
+  int32_t reserved[4];
+} ppf_depth_normal_params;
+/* radius 3, max_depth_change 0.02, min_neighbours 3, flags 0 */
+void ppf_default_depth_normal_params(ppf_depth_normal_params* p);
+/* ppf_cloud_from_depth with a plane fit per kept pixel p = (u, v) over its image window.  q = (u + du, v + dv) is a
+ * neighbour of p iff |du|, |dv| <= radius, q lies inside the image, q is kept by the same rule as p (p's formats, scale,
+ * z_min, z_max) and fabs((double)zq - (double)zp) <= (double)max_depth_change * (double)zp; p is its own neighbour, k counts
+ * them, and they are visited with dv ascending and du ascending inside a row.  The fit is ppf_prep_normals' over that list,
+ * on the float x y z the cloud's rows hold: fp64 centroid (sequential sums, / k), in a second pass the six covariance
+ * sums of q - c (/ k), the eigenvector of the smallest eigenvalue by the same 12 Jacobi sweeps, turned towards the origin
+ * (flipped when -(p . n) < 0) and cast to float; curvature = (float)(|lambda| / |trace|), 0 when the trace is 0.  A pixel
+ * with k < min_neighbours gets normal NaN NaN NaN and curvature NaN, or with PPF_DEPTH_NORMALS_DROP no row (the flag never
+ * changes who is a neighbour).  Without the flag the rows, their order and their xyz bytes are ppf_cloud_from_depth's of
+ * the same arguments.  Everything ppf_cloud_from_depth says about depth, the pitch, intr, p, errors and *out holds; np
+ * NULL, a radius outside 1..PPF_DEPTH_NORMALS_MAX_RADIUS, a max_depth_change that is not finite or <= 0, min_neighbours
+ * outside 3..(2r+1)^2 or an unknown flag are PPF_ERR_INVALID before any device work too. */
+ppf_status ppf_cloud_from_depth_normals(const void* depth, int rows, int cols, size_t row_pitch_bytes, const double* intr,
+                                        const ppf_depth_params* p, const ppf_depth_normal_params* np, ppf_cloud** out);
+/* the same from DEVICE memory on `stream`, as ppf_cloud_from_depth_device */
+ppf_status ppf_cloud_from_depth_normals_device(const void* d_depth, int rows, int cols, size_t row_pitch_bytes, const double* intr,
+                                               const ppf_depth_params* p, const ppf_depth_normal_params* np, void* stream,
+                                               ppf_cloud** out);
+
 /* ---- every detection of a frame in one segmented device pass ------------------------------------------------ */
 typedef struct ppf_frame_params {
   double leaf;                /* Subsampling(leafsize), cubic voxel leaf */

@@ -117,6 +117,15 @@ PPF_DEPTH_F32, PPF_DEPTH_U16 = 0, 1
 PPF_DEPTH_FP64 = 1  # DepthParams.flags bit
 
 
+class DepthNormalParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("max_depth_change", C.c_float), ("min_neighbours", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+PPF_DEPTH_NORMALS_DROP = 1  # DepthNormalParams.flags bit
+PPF_DEPTH_NORMALS_MAX_RADIUS = 8
+
+
 class VerifyParams(C.Structure):
     _fields_ = [("inlier_dist", C.c_float), ("normal_cos", C.c_float), ("depth_tol", C.c_float), ("model_step", C.c_int32),
                 ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
@@ -341,6 +350,12 @@ _SIGNATURES = {
                                        C.POINTER(C.c_void_p)]),
     "ppf_cloud_from_depth_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_double),
                                               C.POINTER(DepthParams), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ppf_default_depth_normal_params": (None, [C.POINTER(DepthNormalParams)]),
+    "ppf_cloud_from_depth_normals": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_double), C.POINTER(DepthParams),
+                                               C.POINTER(DepthNormalParams), C.POINTER(C.c_void_p)]),
+    "ppf_cloud_from_depth_normals_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_double),
+                                                      C.POINTER(DepthParams), C.POINTER(DepthNormalParams), C.c_void_p,
+                                                      C.POINTER(C.c_void_p)]),
     "ppf_default_verify_params": (None, [C.POINTER(VerifyParams)]),
     "ppf_verify_frame": (C.c_int, [C.POINTER(FrameDetection), C.c_int, C.POINTER(Pose), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int,
                                    C.c_int, C.POINTER(C.c_double), C.POINTER(VerifyParams), C.POINTER(PoseScore), C.POINTER(C.c_int),

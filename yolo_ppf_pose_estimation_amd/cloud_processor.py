@@ -38,19 +38,33 @@ class DeviceCloud:
 
     @classmethod
     def from_depth(cls, depth, intr, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0,
-                   fp64: bool = False) -> "DeviceCloud":
+                   fp64: bool = False, normals: Optional[dict] = None) -> "DeviceCloud":
         """The organised scene cloud of a depth image, back-projected on the device (ppf_cloud_from_depth): rows
         ``x y z 0 0 0`` of every pixel with a finite z > 0 inside [z_min, z_max] (z_max 0: no upper bound), in row-major
         pixel order.  depth: a 2-D numpy float32 (metres) or uint16 (units of depth_scale metres) array, rows read at its
         stride; or a float32 / uint16 torch tensor on the GPU, read in place on ``torch.cuda.current_stream()``.
         intr: (fx, fy, ppx, ppy) or the 3x3 camera matrix.  fp64=True: the fp64 formula instead of
-        Camera::back_projection's rounding (DESIGN.md §13)."""
+        Camera::back_projection's rounding (DESIGN.md §13).  normals: None, or a dict with any of radius,
+        max_depth_change, min_neighbours, drop (ppf_cloud_from_depth_normals): the same rows with the normal
+        and curvature of a plane fit over each pixel's (2 radius + 1)^2 image window; a pixel with fewer than
+        min_neighbours neighbours gets NaNs, or with drop=True no row."""
         K = np.asarray(intr, dtype=np.float64)
         it = (C.c_double * 4)(*([K[0, 0], K[1, 1], K[0, 2], K[1, 2]] if K.shape == (3, 3) else [float(v) for v in K.reshape(-1)[:4]]))
         prm = _capi.DepthParams()
         lib().ppf_default_depth_params(C.byref(prm))
         prm.depth_scale, prm.z_min, prm.z_max = float(depth_scale), float(z_min), float(z_max)
         prm.flags = _capi.PPF_DEPTH_FP64 if fp64 else 0
+        nprm = None
+        if normals is not None:
+            unknown = set(normals) - {"radius", "max_depth_change", "min_neighbours", "drop"}
+            if unknown:
+                raise PPFError(_capi.PPF_ERR_INVALID, f"normals: unknown keys {sorted(unknown)}")
+            nprm = _capi.DepthNormalParams()
+            lib().ppf_default_depth_normal_params(C.byref(nprm))
+            nprm.radius = int(normals.get("radius", nprm.radius))
+            nprm.max_depth_change = float(normals.get("max_depth_change", nprm.max_depth_change))
+            nprm.min_neighbours = int(normals.get("min_neighbours", nprm.min_neighbours))
+            nprm.flags = _capi.PPF_DEPTH_NORMALS_DROP if normals.get("drop", False) else 0
         out = C.c_void_p()
         if type(depth).__module__.startswith("torch"):
             import torch
@@ -65,9 +79,13 @@ class DeviceCloud:
                 prm.format = fmt
                 with torch.cuda.device(depth.device):
                     stream = torch.cuda.current_stream(depth.device).cuda_stream
-                    check(lib().ppf_cloud_from_depth_device(C.c_void_p(depth.data_ptr()), depth.shape[0], depth.shape[1],
-                                                            depth.stride(0) * depth.element_size(), it, C.byref(prm),
-                                                            C.c_void_p(stream) if stream else None, C.byref(out)))
+                    args = (C.c_void_p(depth.data_ptr()), depth.shape[0], depth.shape[1], depth.stride(0) * depth.element_size(), it,
+                            C.byref(prm))
+                    st = C.c_void_p(stream) if stream else None
+                    if nprm is None:
+                        check(lib().ppf_cloud_from_depth_device(*args, st, C.byref(out)))
+                    else:
+                        check(lib().ppf_cloud_from_depth_normals_device(*args, C.byref(nprm), st, C.byref(out)))
                 return cls(out)
         a = np.asarray(depth)
         fmt = {np.dtype(np.float32): _capi.PPF_DEPTH_F32, np.dtype(np.uint16): _capi.PPF_DEPTH_U16}.get(a.dtype)
@@ -76,8 +94,11 @@ class DeviceCloud:
         if a.strides[1] != a.itemsize or a.strides[0] < a.shape[1] * a.itemsize or a.strides[0] % a.itemsize:
             a = np.ascontiguousarray(a)
         prm.format = fmt
-        check(lib().ppf_cloud_from_depth(C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1], a.strides[0], it, C.byref(prm),
-                                         C.byref(out)))
+        args = (C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1], a.strides[0], it, C.byref(prm))
+        if nprm is None:
+            check(lib().ppf_cloud_from_depth(*args, C.byref(out)))
+        else:
+            check(lib().ppf_cloud_from_depth_normals(*args, C.byref(nprm), C.byref(out)))
         return cls(out)
 
     def __del__(self):
@@ -655,13 +676,13 @@ class CloudProcessor:
         self.cluster_stats: Dict[str, object] = {}
 
     # ---- the PCL half -------------------------------------------------------------------------------------
-    def Deprojection(self, CameraIntr, fp64: bool = False) -> DeviceCloud:
+    def Deprojection(self, CameraIntr, fp64: bool = False, normals: Optional[dict] = None) -> DeviceCloud:
         """The scene cloud from ``self.depth`` (float32 metres), back-projected on the device -- the reference's
         ``Deprojection(Mat CameraIntr)`` is an empty stub (CloudProcessing.h:262).  CameraIntr: the 3x3 matrix as
-        SceneCropping takes it.  Sets and returns ``self.scene``; fp64 as in ``DeviceCloud.from_depth``."""
+        SceneCropping takes it.  Sets and returns ``self.scene``; fp64 and normals as in ``DeviceCloud.from_depth``."""
         if self.depth is None:
             raise PPFError(_capi.PPF_ERR_INVALID, "Deprojection needs a depth image")
-        self.scene = DeviceCloud.from_depth(self.depth, np.asarray(CameraIntr, dtype=np.float64), fp64=fp64)
+        self.scene = DeviceCloud.from_depth(self.depth, np.asarray(CameraIntr, dtype=np.float64), fp64=fp64, normals=normals)
         return self.scene
 
     def RemovePlanes(self, **params) -> DeviceCloud:

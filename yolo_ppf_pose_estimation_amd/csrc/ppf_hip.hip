@@ -23,7 +23,7 @@
  * This file is the one translation unit of libppf_hip.so; the code lives in the headers included at the bottom:
  *   kernels   ppf_train_kernels.h (table build)  ppf_sample_kernels.h (A2)  ppf_match_kernels.h (k_frames / k_pairs /
  *             k_group / k_vote)  ppf_pose_kernels.h (k_finalize, k_rank, clustering)  ppf_icp_kernels.h  ppf_prep_kernels.h
- *             ppf_depth_kernels.h  ppf_verify_kernels.h  ppf_render_kernels.h  ppf_select_kernels.h  ppf_refine_kernels.h
+ *             ppf_depth_kernels.h  ppf_depth_normals_kernels.h  ppf_verify_kernels.h  ppf_render_kernels.h  ppf_select_kernels.h  ppf_refine_kernels.h
  *             ppf_register_kernels.h  ppf_plane_kernels.h  ppf_cluster_kernels.h
  *   host      ppf_device_mem.h (errors, block cache)  ppf_host_common.h (scans, sorts, model / workspace structs)
  *             ppf_model_host.h  ppf_match_host.h  ppf_batch_host.h  ppf_icp_host.h  ppf_prep_host.h (the segmented
@@ -62,6 +62,7 @@
 #include "ppf_icp_kernels.h"
 #include "ppf_prep_kernels.h"
 #include "ppf_depth_kernels.h" /* k_depth_count, k_depth_scatter */
+#include "ppf_depth_normals_kernels.h" /* k_depth_normals, k_depthn_count, k_depthn_scatter */
 #include "ppf_verify_kernels.h" /* k_vfy_grid_count / _grid_scatter, k_vfy_score, k_vfy_finish */
 #include "ppf_render_kernels.h" /* k_rnd_window, k_rnd_splat, k_rnd_vfy_score, k_rnd_splat_frame, k_rnd_resolve */
 #include "ppf_select_kernels.h" /* k_sel_mask, k_sel_key, k_sel_overlap, k_sel_greedy, k_sel_report, k_sel_paint */
