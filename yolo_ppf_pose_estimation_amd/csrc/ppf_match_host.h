@@ -349,7 +349,7 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
   va.tables = ws->tables.p; va.table_desc = ws->table_desc.p; va.table_cap = table_cap;
   va.work = ws->work.p; va.perm = ws->perm.p; va.perm_group = ws->perm_group.p;
 
-  /* the run staging gets the LDS this model's accumulator tile leaves (its least size is what the tile was sized against) */
+  /* the item staging gets the LDS this model's accumulator tile leaves (its least size is what the tile was sized against) */
   const size_t acc_words = (size_t)vote_lds_words(m->info.tile_refs, m->info.num_angles);
   va.run_seg = vote_run_seg(acc_words, (size_t)LDS_BYTES);
   if (ws->run_seg_cap > 0) va.run_seg = std::max(64, std::min(va.run_seg, ws->run_seg_cap / 64 * 64)); /* test knob: PPF_OPT_RUN_STAGING */

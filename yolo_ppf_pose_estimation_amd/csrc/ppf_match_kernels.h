@@ -185,11 +185,13 @@ constexpr int AGG_MAX_ANGLES = 31;    /* Y = floor(alpha_s*A/(4pi)) must stay in
 #ifndef PPF_RUN_SEG
 #define PPF_RUN_SEG 704
 #endif
-constexpr int RUN_SEG = PPF_RUN_SEG;  /* runs staged in LDS per segment, AT LEAST (every segment costs the workgroup two dependent reads and three barriers: 256 -> 512
-                                         was worth 3 % on C2, whose reference points have about 600 runs): the tile size of a model is chosen with this much staging ... */
-constexpr int RUN_SEG_MAX = 1024;     /* ... and a call gives the staging whatever LDS the model's accumulator tile then leaves, in steps of 64 runs (MatchArgs::run_seg;
-                                         C2's 2,000-row tile: 896, and 704 -> 896 is another 1 % -- a third of its reference points have more than 704 runs) */
-static_assert(RUN_SEG % 64 == 0 && RUN_SEG <= RUN_SEG_MAX && RUN_SEG_MAX == 1024, "the staging loop gives one thread to a run and scans whole waves");
+constexpr int RUN_SEG = PPF_RUN_SEG;  /* size of k_vote's staging area in LDS, AT LEAST, reckoned in runs of 24 bytes as it was when the area held runs: it holds one 16-byte
+                                         record per WORK ITEM now, 3/2 as many (vote_item_seg: 704 -> 1,058).  Every segment costs the workgroup two dependent reads and
+                                         three barriers (256 -> 512 runs was worth 3 % on C2, whose reference points have about 600 runs and as many items): the tile size
+                                         of a model is chosen with this much staging ... */
+constexpr int RUN_SEG_MAX = 1024;     /* ... and a call gives the staging whatever LDS the model's accumulator tile then leaves, in steps of 64 runs = 96 items (MatchArgs::run_seg;
+                                         C2's 2,000-row tile: 896 = 1,346 items) */
+static_assert(RUN_SEG % 64 == 0 && RUN_SEG <= RUN_SEG_MAX && RUN_SEG_MAX == 1024, "the staging area is sized in steps of 64 runs");
 constexpr int GROUP_BLOCK = 512;       /* two k_group workgroups per CU when the bucket counters fit half the LDS (0.705 -> 0.665 ms on C2) */
 #ifndef PPF_GROUP_MLP
 #define PPF_GROUP_MLP 4
@@ -371,7 +373,7 @@ struct MatchArgs {
   int agg_min_hits;             /* 0: every run votes directly */
   int key_exact;                /* PPF_KEY_EXACT table: keys outside the key table (but for NaN angle bins, key_index_nan) match nothing */
   double pair_radius;           /* > 0: pairs farther apart than this are skipped (not counted) */
-  int run_seg;                  /* runs k_vote stages per segment: RUN_SEG .. RUN_SEG_MAX, a multiple of 64 (vote_run_seg) */
+  int run_seg;                  /* size of k_vote's staging area in runs of 24 bytes: RUN_SEG .. RUN_SEG_MAX, a multiple of 64 (vote_run_seg); it holds vote_item_seg(run_seg) work items */
   int acc32;                    /* k_vote<.., true> (32-bit cells, one workgroup per half of a tile's rows): 1 = every (reference point, tile),
                                    2 = only those the 16-bit launch flagged in ovf_items */
   uint32_t* ovf_items;          /* [n_ref_all * n_tiles] != 0: voted with 32-bit cells -- 1: a 16-bit cell of this (reference point, tile) overflowed;
@@ -1463,11 +1465,22 @@ __device__ __forceinline__ void agg_pair(const AggConsts& k, const uint4 rec, co
 #endif
 }
 
-/* a staged run of k_vote's run table in LDS: its work items' exclusive prefix, this tile's record range of its bucket, its
- * hits, its first count table.  One record per run (not an array per field): a look-up reads the six words behind ONE address,
- * and the size of the staging area (MatchArgs::run_seg) moves no other array */
-constexpr int SEG_WORDS = 6, SEG_PREFIX = 0, SEG_OFF = 1, SEG_CNT = 2, SEG_HIT = 3, SEG_M = 4, SEG_TBL = 5;
-__host__ __device__ constexpr size_t vote_seg_bytes(int run_seg) { return ((size_t)(run_seg + 1) * SEG_WORDS * 4 + 15) / 16 * 16; } /* + the sentinel; what follows stays 16-byte aligned */
+/* k_vote's staging area in LDS holds one finished 16-byte record per WORK ITEM of the segment (not one per run): everything an
+ * item's look-up used to derive from its run -- which run, which chunk of the bucket, which range of hits, which count table --
+ * is a function of the staged runs alone, so the workgroup's 1,024 threads work it out once while staging, and a wave that
+ * claims item i reads record i with one wave-uniform ds_read_b128:
+ *   x  first pair record of the item (off + chunk * chunk size, an index into MatchArgs::records)
+ *   y  first sorted hit g0
+ *   z  count table of the item (the run's first + sub), count-table items only
+ *   w  records c (<= 1,024; a build with PPF_AGG_CHUNK=4096: that) | hits nh << 13 (<= 191) | count-table flag << 21
+ * Items keep the order run, sub (range of hits), chunk (range of records).  The area's size is still reckoned in runs of 24
+ * bytes (MatchArgs::run_seg, PPF_OPT_RUN_STAGING), rounded as it was with its sentinel, so that no model's tile size and no
+ * other array moves: it holds 3/2 as many items + 2. */
+constexpr int ITEM_C_BITS = 13, ITEM_NH_BITS = 8;
+static_assert(VOTE_CHUNK < (1 << ITEM_C_BITS) && AGG_CHUNK < (1 << ITEM_C_BITS) && VOTE_MAX_HITS < (1 << ITEM_NH_BITS) && AGG_SUB < (1 << ITEM_NH_BITS),
+              "an item's records and hits share one word of its staged record");
+__host__ __device__ constexpr size_t vote_seg_bytes(int run_seg) { return ((size_t)(run_seg + 1) * 24 + 15) / 16 * 16; } /* what follows stays 16-byte aligned */
+__host__ __device__ constexpr int vote_item_seg(int run_seg) { return (int)(vote_seg_bytes(run_seg) / 16); } /* item records the area holds: 64 runs -> 98, 704 -> 1,058, 896 -> 1,346 */
 /* one work item of k_vote, located and with its first loads issued (wave-uniform fields live in scalar registers) */
 struct VoteItem {
   const uint4* src; /* first record of the item */
@@ -1502,34 +1515,35 @@ __device__ __forceinline__ void vote_item_settle(VoteItem& it) {
   it.a64 = __hiloint2double((int)hi, (int)lo);
 }
 
-__device__ __forceinline__ void vote_locate(VoteItem& it, const uint32_t item, int& h, const uint32_t* seg, const int lane, const MatchArgs& a,
+/* this tile's share of a run, as the staging threads hold it while a segment is staged (registers of the staging phase only) */
+struct VoteRun {
+  uint32_t off, cnt; /* this tile's record range of the run's bucket */
+  uint32_t hit0, m;  /* first sorted hit, hits */
+  uint32_t tbl0;     /* first count table */
+  uint32_t nchunk;   /* items per range of hits: ceil(cnt / chunk size) */
+  uint32_t agg;      /* 1: votes through count tables */
+};
+/* the staged record of item (sub, chunk) of a run */
+__device__ __forceinline__ uint4 vote_item_record(const VoteRun& r, const uint32_t sub, const uint32_t chunk) {
+  const uint32_t chunk_sz = r.agg ? (uint32_t)AGG_CHUNK : (uint32_t)VOTE_CHUNK;
+  const uint32_t group_sz = r.agg ? (uint32_t)AGG_SUB : (uint32_t)VOTE_MAX_HITS;
+  const uint32_t c = min(chunk_sz, r.cnt - chunk * chunk_sz), nh = min(group_sz, r.m - sub * group_sz);
+  return make_uint4(r.off + chunk * chunk_sz, r.hit0 + sub * group_sz, r.tbl0 + sub, c | (nh << ITEM_C_BITS) | (r.agg << (ITEM_C_BITS + ITEM_NH_BITS)));
+}
+
+__device__ __forceinline__ void vote_locate(VoteItem& it, const uint32_t item, const uint4* seg, const int lane, const MatchArgs& a,
                                             const uint4* __restrict__ records) {
-  while (true) { /* advance h to the last position with prefix <= item (position run_seg: the sentinel) */
-    const uint32_t pv = seg[min(h + 1 + lane, a.run_seg) * SEG_WORDS + SEG_PREFIX];
-    const unsigned long long le = __ballot(pv <= item);
-    const int adv = __popcll(le);
-    h += adv;
-    if (adv < 64) break;
-  }
-  /* the staged values are the same in every lane: move them to scalar registers so the item
+  /* the staged record is the same in every lane (one wave-uniform 16-byte read): its words go to scalar registers so the item
    * runs on scalar control flow and scalar base addresses */
-  const uint32_t* run = seg + h * SEG_WORDS; /* the staged run: six consecutive words behind one wave-uniform address */
-  const uint32_t local = item - (uint32_t)__builtin_amdgcn_readfirstlane((int)run[SEG_PREFIX]);
-  const uint32_t c_all = (uint32_t)__builtin_amdgcn_readfirstlane((int)run[SEG_CNT]);
-  const uint32_t mm = (uint32_t)__builtin_amdgcn_readfirstlane((int)run[SEG_M]);
-  const uint32_t m_all = mm & 0x7FFFFFFFu;
-  const uint32_t hit0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)run[SEG_HIT]);
-  const uint32_t off0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)run[SEG_OFF]);
-  it.agg = (mm & 0x80000000u) != 0;
-  const uint32_t chunk_sz = it.agg ? (uint32_t)AGG_CHUNK : (uint32_t)VOTE_CHUNK;
-  const uint32_t group_sz = it.agg ? (uint32_t)AGG_SUB : (uint32_t)VOTE_MAX_HITS;
-  const uint32_t nchunk = (c_all + chunk_sz - 1) / chunk_sz;
-  const uint32_t sub = local / nchunk, chunk = local - sub * nchunk;
-  it.c = min(chunk_sz, c_all - chunk * chunk_sz);
-  it.src = records + off0 + chunk * chunk_sz;
-  it.g0 = hit0 + sub * group_sz;
-  it.nh = (int)min(group_sz, m_all - sub * group_sz);
-  it.tbl = it.agg ? a.tables + (size_t)((uint32_t)__builtin_amdgcn_readfirstlane((int)run[SEG_TBL]) + sub) * TBL_BYTES : nullptr;
+  const uint4 rec = seg[item];
+  const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec.x);
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec.w);
+  it.g0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec.y);
+  it.agg = (w >> (ITEM_C_BITS + ITEM_NH_BITS)) != 0;
+  it.c = w & ((1u << ITEM_C_BITS) - 1u);
+  it.nh = (int)((w >> ITEM_C_BITS) & ((1u << ITEM_NH_BITS) - 1u));
+  it.src = records + first;
+  it.tbl = it.agg ? a.tables + (size_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)rec.z) * TBL_BYTES : nullptr;
 #if PPF_PREFETCH >= 1
   vote_fetch_hits(it, lane, a);
 #endif
@@ -1543,9 +1557,9 @@ template <bool WRAP, bool ACC32>
 __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
   uint32_t* red = reinterpret_cast<uint32_t*>(smem);                               /* LDS_HEADER */
-  const int RS = a.run_seg;                                                        /* runs staged per segment (RUN_SEG .. RUN_SEG_MAX) */
-  uint32_t* seg = reinterpret_cast<uint32_t*>(smem + LDS_HEADER);                  /* RS staged runs of SEG_WORDS words + the sentinel's prefix */
-  unsigned char* wave_scratch = smem + LDS_HEADER + vote_seg_bytes(RS);            /* VOTE_WAVES x AGG_SCRATCH */
+  const uint32_t IS = (uint32_t)vote_item_seg(a.run_seg);                          /* work items staged per segment */
+  uint4* seg = reinterpret_cast<uint4*>(smem + LDS_HEADER);                        /* IS staged item records */
+  unsigned char* wave_scratch = smem + LDS_HEADER + vote_seg_bytes(a.run_seg);     /* VOTE_WAVES x AGG_SCRATCH */
   const int A = a.num_angles;
   const int P = vote_pitch(A);
   const int GW = vote_guard(A);
@@ -1649,7 +1663,9 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
   PPF_PHASE_DECL;
   { /* clear guard + cells with 16-byte LDS stores (the region starts 16-byte aligned) */
     uint4* z = reinterpret_cast<uint4*>(lds_acc);
-    for (int c = tid; c < words / 4; c += VOTE_BLOCK) z[c] = make_uint4(0u, 0u, 0u, 0u);
+    uint32_t zero = 0u;
+    asm volatile("" : "+v"(zero)); /* made here, for every unit of work: as a constant, four registers of zeros are kept through the whole unit (32-bit cells: spilled) to save this v_mov */
+    for (int c = tid; c < words / 4; c += VOTE_BLOCK) z[c] = make_uint4(zero, zero, zero, zero);
     for (int c = (words & ~3) + tid; c < words; c += VOTE_BLOCK) lds_acc[c] = 0u;
   }
   VoteInc vi;
@@ -1662,40 +1678,46 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
 
   for (int blk = 0; blk < a.n_rounds; blk++) {
     const uint2 rb = a.run_blocks[(size_t)r * a.n_rounds + blk];
-    for (uint32_t seg0 = 0; seg0 < rb.y; seg0 += (uint32_t)RS) {
-      /* Stage a segment of the run table: this tile's record range of every run and its work items, exclusive scan */
+    /* A segment is cut by ITEMS: it takes the round's runs from (run_first, item_first) on -- item_first: items of that run
+     * which earlier segments have had -- until the staging area is full, and may start and end inside a run (one run can
+     * have more items than the area holds: a bucket of tens of thousands of records times several count tables, or
+     * thousands of hits that vote directly).  Both cursors are the same in every thread. */
+    uint32_t run_first = 0, item_first = 0;
+    while (run_first < rb.y) {
+      /* Stage a segment: this tile's record range of every run, its work items, exclusive scan, one record per item */
       __syncthreads(); /* previous segment fully consumed (and the accumulator clear, first time) */
-      PPF_PHASE(seg0 ? 5 : 0);
-      const uint32_t n_seg = min((uint32_t)RS, rb.y - seg0);
-      uint32_t items = 0;
+      PPF_PHASE((run_first | item_first) ? 5 : 0);
+      /* one thread per run; a run with records here has at least one item, so more runs than the area has records are never needed */
+      const uint32_t n_read = min(min(IS, (uint32_t)VOTE_BLOCK), rb.y - run_first);
+      uint32_t items = 0, local0 = 0; /* the run's items that this and later segments stage, and the first of them */
+      VoteRun vr;
+      vr.off = vr.cnt = vr.hit0 = vr.m = vr.tbl0 = vr.agg = 0u; vr.nchunk = 1u;
       bool heavy_run = false; /* a run k_group filed under "many hits": those come first in every round's run list */
-      if (tid < RS) {
-        uint32_t off = 0, cnt = 0, hs = 0, mm = 0, tb0 = 0;
-        if ((uint32_t)tid < n_seg) {
-          const uint4 run = a.runs[rb.x + seg0 + tid];
-          off = boff[run.x];
-          cnt = boff[run.x + 1] - off;
-          if (acc32) { /* this pass counts one half of the tile's rows: only the records that can hold them */
-            const uint32_t n0 = a.bucket_mid[(size_t)tile * a.n_buckets + run.x], blk = 32u * (n0 >> 6), d = n0 & 63u;
-            if (pass == 0) cnt = min(cnt, blk + min(d, 32u));
-            else { const uint32_t skip = min(cnt, blk + (d > 32u ? d - 32u : 0u)); off += skip; cnt -= skip; }
-          }
-          hs = run.y;
-          mm = run.z;
-          tb0 = run.w;
-          heavy_run = run.z >= agg_min;
-          (void)heavy_run; /* only the two-queue variant (PPF_TWO_QUEUES) counts them */
-          if (cnt) {
-            if (run.z >= agg_min && cnt >= PPF_AGG_MIN_RECORDS) {
-              items = ((run.z + AGG_SUB - 1) / AGG_SUB) * ((cnt + AGG_CHUNK - 1) / AGG_CHUNK);
-              mm |= 0x80000000u;
-            } else {
-              items = ((run.z + VOTE_MAX_HITS - 1) / VOTE_MAX_HITS) * ((cnt + VOTE_CHUNK - 1) / VOTE_CHUNK);
-            }
+      if ((uint32_t)tid < n_read) {
+        const uint4 run = a.runs[rb.x + run_first + tid];
+        vr.off = boff[run.x];
+        vr.cnt = boff[run.x + 1] - vr.off;
+        if (acc32) { /* this pass counts one half of the tile's rows: only the records that can hold them */
+          const uint32_t n0 = a.bucket_mid[(size_t)tile * a.n_buckets + run.x], blk = 32u * (n0 >> 6), d = n0 & 63u;
+          if (pass == 0) vr.cnt = min(vr.cnt, blk + min(d, 32u));
+          else { const uint32_t skip = min(vr.cnt, blk + (d > 32u ? d - 32u : 0u)); vr.off += skip; vr.cnt -= skip; }
+        }
+        vr.hit0 = run.y;
+        vr.m = run.z;
+        vr.tbl0 = run.w;
+        heavy_run = run.z >= agg_min;
+        (void)heavy_run; /* only the two-queue variant (PPF_TWO_QUEUES) counts them */
+        if (vr.cnt) {
+          if (run.z >= agg_min && vr.cnt >= PPF_AGG_MIN_RECORDS) {
+            vr.nchunk = (vr.cnt + AGG_CHUNK - 1) / AGG_CHUNK;
+            items = ((run.z + AGG_SUB - 1) / AGG_SUB) * vr.nchunk;
+            vr.agg = 1u;
+          } else {
+            vr.nchunk = (vr.cnt + VOTE_CHUNK - 1) / VOTE_CHUNK;
+            items = ((run.z + VOTE_MAX_HITS - 1) / VOTE_MAX_HITS) * vr.nchunk;
           }
         }
-        uint32_t* run_out = seg + tid * SEG_WORDS;
-        run_out[SEG_OFF] = off; run_out[SEG_CNT] = cnt; run_out[SEG_HIT] = hs; run_out[SEG_M] = mm; run_out[SEG_TBL] = tb0;
+        if (tid == 0) { local0 = item_first; items -= item_first; } /* item_first < the run's items: a segment that ends with a run moves on to the next */
       }
       uint32_t incl = items;
 #pragma unroll
@@ -1710,22 +1732,54 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
       __syncthreads();
       uint32_t woff = 0, total = 0;
 #pragma unroll
-      for (int kk = 0; kk < RUN_SEG_MAX / 64; kk++) { /* waves that staged nothing wrote a zero */
+      for (int kk = 0; kk < VOTE_WAVES; kk++) { /* waves that read no run wrote a zero */
         const uint32_t w = red[kk];
         if (kk < wave) woff += w;
         total += w;
       }
-      if (tid < RS) seg[tid * SEG_WORDS + SEG_PREFIX] = woff + incl - items; /* exclusive */
-      if (tid == 0) seg[RS * SEG_WORDS + SEG_PREFIX] = total;                 /* the sentinel the 64-wide look-ahead is clamped to */
+      const uint32_t first = woff + incl - items;  /* exclusive: the run's first slot, if the area reaches that far */
+      const uint32_t n_items = min(total, IS);     /* items of this segment */
+      const uint32_t n_mine = first < IS ? min(items, IS - first) : 0u;
+      /* A run's own thread writes its first STAGE_OWN items (nearly every run has one or two), the run's wave the rest, 64 at a
+       * time, so that a run of hundreds of items does not hold up the staging on one thread.  One division per thread: its items
+       * follow each other chunk-minor. */
+      constexpr uint32_t STAGE_OWN = 4;
+      if (n_mine) {
+        uint32_t sub = local0 / vr.nchunk, chunk = local0 - sub * vr.nchunk;
+        for (uint32_t j = 0; j < min(n_mine, STAGE_OWN); j++) {
+          seg[first + j] = vote_item_record(vr, sub, chunk);
+          if (++chunk == vr.nchunk) { chunk = 0u; sub++; }
+        }
+      }
+      for (unsigned long long many = __ballot(n_mine > STAGE_OWN); many; many &= many - 1ull) {
+        const int src = __builtin_ctzll(many);
+        VoteRun wr;
+        wr.off = (uint32_t)__builtin_amdgcn_readlane((int)vr.off, src); wr.cnt = (uint32_t)__builtin_amdgcn_readlane((int)vr.cnt, src);
+        wr.hit0 = (uint32_t)__builtin_amdgcn_readlane((int)vr.hit0, src); wr.m = (uint32_t)__builtin_amdgcn_readlane((int)vr.m, src);
+        wr.tbl0 = (uint32_t)__builtin_amdgcn_readlane((int)vr.tbl0, src); wr.nchunk = (uint32_t)__builtin_amdgcn_readlane((int)vr.nchunk, src);
+        wr.agg = (uint32_t)__builtin_amdgcn_readlane((int)vr.agg, src);
+        const uint32_t w_first = (uint32_t)__builtin_amdgcn_readlane((int)first, src), w_n = (uint32_t)__builtin_amdgcn_readlane((int)n_mine, src);
+        const uint32_t w_local0 = (uint32_t)__builtin_amdgcn_readlane((int)local0, src);
+        for (uint32_t j = STAGE_OWN + (uint32_t)lane; j < w_n; j += 64u) {
+          const uint32_t local = w_local0 + j, sub = local / wr.nchunk;
+          seg[w_first + j] = vote_item_record(wr, sub, local - sub * wr.nchunk);
+        }
+      }
+      /* where the next segment starts: the run whose items the area's end cuts off (or falls in front of) tells.  One unsigned
+       * comparison: for the runs behind the end IS - first wraps to more items than any run has.  What it rests on, as the scan
+       * above does and the run staging before it did: the items of the at most 1,024 runs read here add up to less than 2^32.  A
+       * run of m hits on c records has at most (m / 24 + 1) * (c / 1024 + 1) items and the m of a reference point add up to at most
+       * the paired points of the call: 10^6 points on buckets of 10^6 records in a tile are 4 * 10^7 items + 1,000 per run */
+      if (items > IS - first) { red[54] = run_first + (uint32_t)tid; red[55] = local0 + (IS - first); }
 #if PPF_TWO_QUEUES
       /* Two queues: the items of the many-hit runs (count tables: LDS-bound) and those of the few-hit runs behind them
        * (direct votes over whole buckets: bound by the latency of the record loads).  `split` = first item of the second. */
       {
         uint32_t n_heavy = 0;
 #pragma unroll
-        for (int kk = 0; kk < RUN_SEG_MAX / 64; kk++) n_heavy += red[16 + kk];
-        if (tid == (int)n_heavy && n_heavy < (uint32_t)RS) red[56] = woff + incl - items;
-        if (tid == 0) { if (n_heavy >= (uint32_t)RS) red[56] = total; red[48] = 0u; }
+        for (int kk = 0; kk < VOTE_WAVES; kk++) n_heavy += red[16 + kk];
+        if (tid == (int)n_heavy && n_heavy < (uint32_t)VOTE_BLOCK) red[56] = min(first, IS);
+        if (tid == 0) { if (n_heavy >= (uint32_t)VOTE_BLOCK) red[56] = n_items; red[48] = 0u; }
       }
       __syncthreads();
       if (tid == 0) red[49] = red[56];
@@ -1733,11 +1787,17 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
       if (tid == 0) red[48] = VOTE_WAVES; /* next unclaimed work item (each wave starts with item == its id) */
 #endif
       __syncthreads();
+      if (total > IS) {
+        run_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)red[54]);
+        item_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)red[55]);
+      } else {
+        run_first += n_read;
+        item_first = 0u;
+      }
       PPF_PHASE(0);
 
       /* Work items are claimed from an LDS counter as waves become free (items differ by orders of magnitude in
-       * size); a wave's items still come in increasing order, so the owning run is found with a 64-wide look-ahead
-       * from the previous one (runs with no records in this tile have 0 items and are skipped).  A wave always holds
+       * size); item i is record i of the staging area, whichever wave claims it and in whichever order.  A wave always holds
        * TWO items: while it votes one, the first loads of the next (its hits' alpha_s, its first records) are in
        * flight -- most items are small (a bucket's share of one tile: median 14 records) and would otherwise spend
        * their time waiting for those loads. */
@@ -1745,16 +1805,14 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
 #if PPF_TWO_QUEUES
       /* Half of the waves (two per SIMD) take from the first queue while it lasts, the other half from the second, so a CU
        * runs its LDS-bound and its load-bound work side by side instead of one after the other; a wave whose queue is
-       * empty helps with the other one.  Inside a queue the order is k_group's: heaviest first.  A wave's items of ONE
-       * queue still come in increasing order: one look-ahead cursor per queue. */
+       * empty helps with the other one.  Inside a queue the order is k_group's: heaviest first. */
       const uint32_t split = red[56];
-      int hq[2] = {0, 0};
       const int pref = (wave >> 2) & 1; /* waves w, w + 4, w + 8, w + 12 share a SIMD: every SIMD gets two of each kind */
       auto claim = [&](uint32_t& it_out, int& q_out) -> bool {
         int q = pref;
 #pragma unroll
         for (int attempt = 0; attempt < 2; attempt++, q ^= 1) {
-          const uint32_t lim = q == 0 ? split : total;
+          const uint32_t lim = q == 0 ? split : n_items;
           /* an empty queue is left alone once its counter has passed the end (the counter may overshoot by one per wave) */
           const uint32_t it = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lane == 0 ? atomicAdd(&red[48 + q], 1u) : 0u));
           if (it < lim) { it_out = it; q_out = q; return true; }
@@ -1764,7 +1822,7 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
       uint32_t item = 0;
       int q_item = 0;
       bool have = claim(item, q_item);
-      if (have) vote_locate(cur, item, hq[q_item], seg, lane, a, records);
+      if (have) vote_locate(cur, item, seg, lane, a, records);
       vote_item_settle(cur);
       while (have) {
         uint4 tbl0 = make_uint4(0u, 0u, 0u, 0u), tbl1 = tbl0;
@@ -1774,12 +1832,11 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
           tbl1 = rec_at(t, (uint32_t)min(lane + 64, AGG_SCRATCH / 16 - 1));
         }
         const bool have_next = claim(item, q_item);
-        if (have_next) vote_locate(nxt, item, hq[q_item], seg, lane, a, records);
+        if (have_next) vote_locate(nxt, item, seg, lane, a, records);
 #else
-      int h = 0;
       uint32_t item = (uint32_t)wave;
-      bool have = item < total;
-      if (have) vote_locate(cur, item, h, seg, lane, a, records);
+      bool have = item < n_items;
+      if (have) vote_locate(cur, item, seg, lane, a, records);
       vote_item_settle(cur);
       while (have) {
         /* a count-table item: its table's rows and cell ranges (two 16-byte pieces per lane) set out first, ahead of the next
@@ -1791,8 +1848,8 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
           tbl1 = rec_at(t, (uint32_t)min(lane + 64, AGG_SCRATCH / 16 - 1));
         }
         item = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lane == 0 ? atomicAdd(&red[48], 1u) : 0u));
-        const bool have_next = item < total;
-        if (have_next) vote_locate(nxt, item, h, seg, lane, a, records);
+        const bool have_next = item < n_items;
+        if (have_next) vote_locate(nxt, item, seg, lane, a, records);
 #endif
 #if PPF_PREFETCH < 1
         vote_fetch_hits(cur, lane, a);
@@ -1992,8 +2049,8 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
     found += __shfl_down(found, o);
     if (v2 > bv || (v2 == bv && i2 < bi)) { bv = v2; bi = i2; }
   }
-  uint32_t* red_v = seg; /* the staging area is free now */
-  uint32_t* red_i = seg + VOTE_WAVES;
+  uint32_t* red_v = reinterpret_cast<uint32_t*>(seg); /* the staging area is free now */
+  uint32_t* red_i = red_v + VOTE_WAVES;
   __syncthreads();
   if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; }
   if (lane == 0) {
@@ -2052,14 +2109,14 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
   } while (wid < n_work);
 }
 
-/* fixed LDS of k_vote: header + run staging + per-wave count tables (the guard and the cells are sized per model) */
+/* fixed LDS of k_vote: header + item staging + per-wave count tables (the guard and the cells are sized per model) */
 constexpr size_t vote_lds_fixed(int run_seg) { return LDS_HEADER + vote_seg_bytes(run_seg) + (size_t)VOTE_WAVES * AGG_SCRATCH; }
 constexpr size_t VOTE_LDS_FIXED = vote_lds_fixed(RUN_SEG); /* with the least staging: what a model's tile size is chosen against */
-/* runs a call stages per segment: what the LDS holds next to the accumulator of `acc_words` words, RUN_SEG at least */
+/* size of a call's staging area, in runs of 24 bytes: what the LDS holds next to the accumulator of `acc_words` words, RUN_SEG at least */
 inline int vote_run_seg(size_t acc_words, size_t lds_bytes) {
   const size_t least = VOTE_LDS_FIXED + acc_words * 4;
   if (least >= lds_bytes) return RUN_SEG;
-  const size_t more = (lds_bytes - least) / (64 * SEG_WORDS * 4); /* 64 more staged runs */
+  const size_t more = (lds_bytes - least) / (64 * 24); /* 64 more runs = 96 more staged items */
   return (int)std::min<size_t>((size_t)RUN_SEG_MAX, (size_t)RUN_SEG + 64 * more);
 }
 
