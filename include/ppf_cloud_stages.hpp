@@ -12,6 +12,7 @@
  *   PointCloudXYZNormalToMat :163-190 -> Cloud::toMat()   (an N x 6 ppf_match_3d::Mat for PPF3DDetector / ICP)
  *   (nothing: pcl::SACSegmentation would be it)    ->  Cloud::removePlanes(params) / Cloud::applyPlanes(planes)  (the table or wall taken out)
  *   (nothing: pcl::EuclideanClusterExtraction would be it) ->  Cloud::clusters(params, info, intr, ...)  (a plane-free cloud split into objects and their boxes)
+ *   (nothing: pcl::RegionGrowing would be it)              ->  Cloud::regions(params, info, intr, ...)   (a cloud with normals split into smooth surface regions)
  *   all of the above for every box of a frame  ->  Cloud::prepareFrame(boxes, n, depth, ...)  (one (object, edge) pair per box)
  *   Matching_S2B + ICP for every detection     ->  Cloud::matchFrame(models, modelClouds, dets, ...)  (ICP in one launch sequence)
  *   `// TODO: Pose Validation` (:477-479, :530-532) -> Cloud::verifyFrame(modelClouds, dets, poses, depth, ...)  (scores, best pose)
@@ -48,6 +49,12 @@ class Cloud {
     return Cloud(c);
   }
   static Cloud fromXYZ(const float* xyz, int n, int strideFloats = 3) { return fromRows(xyz, n, strideFloats, 3); }
+  /* the same with the curvature an upload leaves zero: n floats (ppf_cloud_set_curvature) */
+  static Cloud fromRows(const float* rows, int n, int strideFloats, int cols, const float* curvature) {
+    const Cloud c = fromRows(rows, n, strideFloats, cols);
+    ppf_match_3d::check(ppf_cloud_set_curvature(c.h_.get(), curvature, n));
+    return c;
+  }
   /* an N x 3 or N x 6 float32 Mat (cv::Mat when OpenCV is present: rows read through step1()) */
   static Cloud fromMat(const ppf_match_3d::Mat& m) {
     return fromRows(m.ptr<float>(0), m.rows, ppf_match_3d::detail::stride_of(m), m.cols >= 6 ? 6 : 3);
@@ -194,6 +201,39 @@ class Cloud {
     if (info) info->assign(rows.begin(), rows.begin() + cnt[0]);
     if (labels) { lab.pop_back(); labels->swap(lab); }
     if (counts) { counts[0] = cnt[0]; counts[1] = cnt[1]; counts[2] = cnt[2]; }
+    return found;
+  }
+
+  static ppf_region_params defaultRegionParams() {
+    ppf_region_params p;
+    ppf_default_region_params(&p);
+    return p;
+  }
+  /* This cloud, with the normals and curvature it carries (fromDepth with ppf_depth_normal_params, or normals()), split into
+   * its smooth surface regions (ppf_prep_regions): what cuts objects that touch, where clusters() leaves
+   * one blob.  Rows of curvature <= params->curvature_threshold are smooth; two smooth rows are linked iff they are no farther
+   * apart than params->tolerance and the dot product of their normals is >= params->normal_cos (fp64; with
+   * PPF_REGION_UNORIENTED its absolute value); a region is a connected component of the links plus the other (border) rows
+   * whose nearest linkable smooth row is in it.  Sizes, order, info, labels and the boxes are clusters()', except that
+   * info.first_row is the region's smallest smooth row.  counts (optional): {regions returned, valid components, all
+   * components, border rows attached}.  params == 0: defaultRegionParams(). */
+  std::vector<Cloud> regions(const ppf_region_params* params = 0, std::vector<ppf_cluster_info>* info = 0, const double* intr = 0,
+                             int imageRows = 0, int imageCols = 0, std::vector<int32_t>* labels = 0, int32_t* counts = 0,
+                             ppf_cluster_stats* stats = 0) const {
+    const ppf_region_params p = orDefaults(params, ppf_default_region_params);
+    const size_t slots = p.max_regions >= 1 && p.max_regions <= PPF_CLUSTER_MAX_CLUSTERS ? (size_t)p.max_regions : 1;
+    const ppf_cloud* in[1] = {need()};
+    std::vector<ppf_cloud*> out(slots, (ppf_cloud*)0);
+    std::vector<ppf_cluster_info> rows(slots);
+    std::vector<int32_t> lab((size_t)size() + 1, -1);
+    int32_t* labp[1] = {&lab[0]};
+    int32_t cnt[4] = {0, 0, 0, 0};
+    ppf_match_3d::check(ppf_prep_regions(in, 1, &p, intr, imageRows, imageCols, &out[0], &rows[0], cnt, labels ? labp : 0, stats));
+    std::vector<Cloud> found;
+    for (int32_t r = 0; r < cnt[0]; r++) found.push_back(Cloud(out[(size_t)r]));
+    if (info) info->assign(rows.begin(), rows.begin() + cnt[0]);
+    if (labels) { lab.pop_back(); labels->swap(lab); }
+    if (counts) { counts[0] = cnt[0]; counts[1] = cnt[1]; counts[2] = cnt[2]; counts[3] = cnt[3]; }
     return found;
   }
 

@@ -408,6 +408,9 @@ ppf_status ppf_icp_register(const float* src, int n_src, int sstride, int snoff,
 /* ---- the producers of the N x 6 input (CloudProcessing.h:263-427), device-resident between stages ---------- */
 /* cols = 3 (xyz; normals zero; normal_offset ignored) or 6 (xyz + the normal at normal_offset), `stride` floats between rows */
 ppf_status ppf_cloud_upload(const float* rows, int n, int stride, int normal_offset, int cols, ppf_cloud** out);
+/* the curvature ppf_cloud_upload leaves zero: n = the cloud's rows floats, copied before the call returns (what a
+ * pcl::PointCloud<pcl::Normal> carries beside its normals, and what ppf_prep_regions and ppf_prep_edges read) */
+ppf_status ppf_cloud_set_curvature(ppf_cloud* c, const float* curvature, int n);
 ppf_status ppf_cloud_release(ppf_cloud* c);
 ppf_status ppf_cloud_size(const ppf_cloud* c, int* n);
 /* rows6: n x 6 floats, curvature: n floats; either may be NULL */
@@ -541,6 +544,40 @@ void ppf_default_cluster_params(ppf_cluster_params* p);
 ppf_status ppf_prep_clusters(const ppf_cloud* const* in, int n_clouds, const ppf_cluster_params* p, const double* intr /* may be NULL */,
                              int image_rows, int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts,
                              int32_t* const* labels, ppf_cluster_stats* stats /* may be NULL */);
+
+/* ---- smooth surface regions: what cuts objects that touch, where distance alone cannot -------------- */
+#define PPF_REGION_UNORIENTED 1 /* flags: normals agree on |dot| (pcl::RegionGrowing's rule, for normals of no common orientation) */
+
+typedef struct ppf_region_params {
+  float tolerance;           /* > 0, metres; default 0.01 */
+  float normal_cos;          /* finite, -1..1; default 0.9659258f (15 degrees) */
+  float curvature_threshold; /* >= 0, +inf allowed (every eligible row smooth), not NaN; default 0.03, the project's edge cut */
+  int32_t min_size;          /* >= 1; default 100 */
+  int32_t max_size;          /* 0: no bound */
+  int32_t max_regions;       /* 1..256; default 64 */
+  int32_t flags;             /* 0 | PPF_REGION_UNORIENTED */
+  int32_t reserved[4];
+} ppf_region_params;
+
+void ppf_default_region_params(ppf_region_params* p);
+/* Region growing on normals, as a closed specification, of n_clouds (0..256) clouds in one pass.  Normals are taken as they
+ * are.  A row is eligible iff x, y, z, nx, ny, nz are finite (every other row belongs to no region), smooth iff it is eligible
+ * and curvature <= curvature_threshold (a float comparison: a NaN curvature is not smooth), a border row iff eligible and
+ * not smooth.  near(a, b) iff ((dx*dx + dy*dy) + dz*dz) <= (double)tolerance * (double)tolerance as in ppf_prep_clusters;
+ * agree(a, b) iff dot >= (double)normal_cos with dot = ((double)anx*(double)bnx + (double)any*(double)bny) +
+ * (double)anz*(double)bnz (fabs(dot) with PPF_REGION_UNORIENTED), all in fp64.  Two smooth rows are linked iff near and agree;
+ * a component is a connected component of the links over a cloud's smooth rows.  A border row joins the component of the
+ * smooth row with the smallest squared distance (ties: the smaller row index) among those it is near to and agrees with, or
+ * no region; border rows link nothing.  n_rows counts a component's smooth and attached border rows; from there on validity,
+ * ranking, out, info, labels, the image boxes and the grid limit (over the eligible rows) are ppf_prep_clusters', with
+ * max_regions for max_clusters -- except that a region's info.first_row is its smallest SMOOTH row.  counts: [n_clouds][4] =
+ * {regions output, valid components, all components, border rows attached}.  Each cloud's result is what a call with that
+ * cloud alone gives; the launch count depends on nothing but whether any cloud has a row; one upload before any device work
+ * and one wait (n_host_syncs 1).  Argument errors are PPF_ERR_INVALID before any device work; on every error each out is
+ * NULL and info and counts are zero. */
+ppf_status ppf_prep_regions(const ppf_cloud* const* in, int n_clouds, const ppf_region_params* p, const double* intr /* may be NULL */,
+                            int image_rows, int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts,
+                            int32_t* const* labels, ppf_cluster_stats* stats /* may be NULL */);
 
 /* ---- the organised scene cloud from a depth image, on the device (what CloudProcessor::Deprojection leaves empty) -- */
 #define PPF_DEPTH_F32 0  /* float32 metres: z = value (the reference's EXR frame) */

@@ -41,6 +41,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "ppf_detmath.h" /* ppf_cos: RegionGrowing's smoothness threshold as a cosine, the same bits on every machine */
 #include "ppf_match_3d.hpp"
 
 namespace ppfhip {
@@ -360,6 +361,108 @@ class EuclideanClusterExtraction {
   double tolerance_ = 0.0;
   int min_ = 1, max_ = 25000;
   std::function<void(std::vector<float>&)> read_;
+};
+
+/* pcl::Normal's storage for builds without PCL (32 bytes: normal_x normal_y normal_z 0 | curvature pad pad pad) */
+struct Normal {
+  float normal_x, normal_y, normal_z, pad0;
+  float curvature, pad1[3];
+  Normal() : normal_x(0), normal_y(0), normal_z(0), pad0(0), curvature(0), pad1{0, 0, 0} {}
+  Normal(float nx, float ny, float nz, float c = 0.f) : normal_x(nx), normal_y(ny), normal_z(nz), pad0(0), curvature(c), pad1{0, 0, 0} {}
+};
+
+/* pcl::RegionGrowing over ppf_prep_regions.  Points need members x, y, z; normals normal_x, normal_y,
+ * normal_z and curvature (pcl::Normal qualifies).  setSmoothnessThreshold takes radians, as PCL does, and becomes normal_cos by
+ * ppf_detmath's cosine; setCurvatureThreshold, setMinClusterSize and setMaxClusterSize are PCL's (a maximum
+ * of 0, the default here, means no bound).  What differs from PCL, stated:
+ *   - the neighbourhood is a radius, setDistanceThreshold (metres; default 0.01), not the k nearest (setNumberOfNeighbours does
+ *     not exist here, and no search method is taken);
+ *   - the normals are compared by the signed cosine, dot >= cos(threshold), unless setUnorientedFlag(true) makes it |dot| as
+ *     PCL's always is;
+ *   - component semantics instead of seed order: two smooth points (curvature <= the threshold) are linked iff they are
+ *     within the distance and their normals agree, a region is a connected component of the links, and a point above the
+ *     curvature threshold joins the region of the nearest smooth point it is within the distance of and agrees with, carrying
+ *     no link itself.  PCL grows from seeds in curvature order and lets such a point join without becoming a seed, so where
+ *     two regions touch PCL's answer depends on which seed came first; this one does not.  PCL's residual test is not there;
+ *   - the indices inside a region are ascending, regions come largest first (equal sizes: by their smallest smooth index), at
+ *     most 256 per call; points or normals that are not finite belong to no region. */
+template <class PointT, class NormalT>
+class RegionGrowing {
+ public:
+  void setDistanceThreshold(double metres) { tolerance_ = metres; }
+  double getDistanceThreshold() const { return tolerance_; }
+  void setSmoothnessThreshold(float radians) { theta_ = radians; }
+  float getSmoothnessThreshold() const { return theta_; }
+  void setCurvatureThreshold(float c) { curvature_ = c; }
+  float getCurvatureThreshold() const { return curvature_; }
+  void setMinClusterSize(int n) { min_ = n; }
+  int getMinClusterSize() const { return min_; }
+  void setMaxClusterSize(int n) { max_ = n; }
+  int getMaxClusterSize() const { return max_; }
+  void setUnorientedFlag(bool on) { unoriented_ = on; }
+  template <class CloudPtr> void setInputCloud(const CloudPtr& cloud) {
+    points_ = [cloud](std::vector<float>& rows) {
+      const auto& p = detail::pts(*cloud);
+      rows.assign(p.size() * 6, 0.f);
+      for (std::size_t i = 0; i < p.size(); i++) { rows[i * 6] = p[i].x; rows[i * 6 + 1] = p[i].y; rows[i * 6 + 2] = p[i].z; }
+    };
+  }
+  template <class NormalsPtr> void setInputNormals(const NormalsPtr& normals) {
+    normals_ = [normals](std::vector<float>& rows, std::vector<float>& curv) {
+      const auto& q = detail::pts(*normals);
+      if (q.size() * 6 != rows.size()) throw ppf_match_3d::Error(PPF_ERR_INVALID, "RegionGrowing: the normals are not as many as the points");
+      curv.resize(q.size());
+      for (std::size_t i = 0; i < q.size(); i++) {
+        rows[i * 6 + 3] = q[i].normal_x; rows[i * 6 + 4] = q[i].normal_y; rows[i * 6 + 5] = q[i].normal_z;
+        curv[i] = q[i].curvature;
+      }
+    };
+  }
+  void extract(std::vector<PointIndices>& clusters) {
+    clusters.clear();
+    if (!points_ || !normals_) throw ppf_match_3d::Error(PPF_ERR_INVALID, "RegionGrowing: no input cloud or no input normals");
+    std::vector<float> rows, curv;
+    points_(rows); /* the clouds as they are now, as PCL reads through the pointers at extract() */
+    normals_(rows, curv);
+    const int n = (int)curv.size();
+    ppf_region_params p;
+    ppf_default_region_params(&p);
+    p.tolerance = (float)tolerance_;
+    p.normal_cos = (float)ppf_cos((double)theta_);
+    p.curvature_threshold = curvature_;
+    p.min_size = min_;
+    p.max_size = max_;
+    p.max_regions = PPF_CLUSTER_MAX_CLUSTERS;
+    p.flags = unoriented_ ? PPF_REGION_UNORIENTED : 0;
+    ppf_cloud* in = nullptr;
+    rows.push_back(0.f);
+    curv.push_back(0.f);
+    ppf_match_3d::check(ppf_cloud_upload(&rows[0], n, 6, PPF_NOFF_MAT, 6, &in));
+    std::shared_ptr<ppf_cloud> hold(in, [](ppf_cloud* c) { ppf_cloud_release(c); });
+    ppf_match_3d::check(ppf_cloud_set_curvature(in, &curv[0], n));
+    const ppf_cloud* ins[1] = {in};
+    std::vector<ppf_cloud*> out((std::size_t)PPF_CLUSTER_MAX_CLUSTERS, (ppf_cloud*)nullptr);
+    std::vector<ppf_cluster_info> info((std::size_t)PPF_CLUSTER_MAX_CLUSTERS);
+    std::vector<int32_t> labels((std::size_t)n + 1, -1);
+    int32_t* labp[1] = {&labels[0]};
+    int32_t counts[4] = {0, 0, 0, 0};
+    ppf_match_3d::check(ppf_prep_regions(ins, 1, &p, nullptr, 0, 0, &out[0], &info[0], counts, labp, nullptr));
+    for (std::size_t k = 0; k < out.size(); k++)
+      if (out[k]) ppf_cloud_release(out[k]); /* the labels are what this surface hands out */
+    clusters.resize((std::size_t)counts[0]);
+    for (int r = 0; r < counts[0]; r++) clusters[(std::size_t)r].indices.reserve((std::size_t)info[(std::size_t)r].n_rows);
+    for (int i = 0; i < n; i++)
+      if (labels[(std::size_t)i] >= 0) clusters[(std::size_t)labels[(std::size_t)i]].indices.push_back(i);
+  }
+
+ private:
+  double tolerance_ = 0.01;
+  float theta_ = 30.0f / 180.0f * 3.14159265f; /* PCL's default */
+  float curvature_ = 0.05f;                    /* PCL's default */
+  int min_ = 1, max_ = 0;
+  bool unoriented_ = false;
+  std::function<void(std::vector<float>&)> points_;
+  std::function<void(std::vector<float>&, std::vector<float>&)> normals_;
 };
 
 }  // namespace pcl_shaped

@@ -255,6 +255,14 @@ class ClusterStats(C.Structure):
 PPF_CLUSTER_MAX_CLUSTERS = 256
 
 
+class RegionParams(C.Structure):
+    _fields_ = [("tolerance", C.c_float), ("normal_cos", C.c_float), ("curvature_threshold", C.c_float), ("min_size", C.c_int32),
+                ("max_size", C.c_int32), ("max_regions", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+PPF_REGION_UNORIENTED = 1  # RegionParams.flags bit
+
+
 # every symbol include/ppf_hip.h declares (tests/test_capi_symbols.py checks the header against this)
 _SIGNATURES = {
     "ppf_default_train_params": (None, [C.POINTER(TrainParams)]),
@@ -323,6 +331,7 @@ _SIGNATURES = {
     "ppf_icp_refine_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams),
                                         C.POINTER(Pose), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
     "ppf_cloud_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "ppf_cloud_set_curvature": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "ppf_cloud_release": (C.c_int, [C.c_void_p]),
     "ppf_cloud_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "ppf_cloud_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
@@ -396,6 +405,10 @@ _SIGNATURES = {
     "ppf_prep_clusters": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(ClusterParams), C.POINTER(C.c_double), C.c_int, C.c_int,
                                     C.POINTER(C.c_void_p), C.POINTER(ClusterInfo), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
                                     C.POINTER(ClusterStats)]),
+    "ppf_default_region_params": (None, [C.POINTER(RegionParams)]),
+    "ppf_prep_regions": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(RegionParams), C.POINTER(C.c_double), C.c_int, C.c_int,
+                                   C.POINTER(C.c_void_p), C.POINTER(ClusterInfo), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
+                                   C.POINTER(ClusterStats)]),
     "ppf_icp_register": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }

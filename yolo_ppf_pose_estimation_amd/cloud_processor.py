@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _capi
-from ._capi import (ClusterInfo, ClusterParams, ClusterStats, FrameDetection, FrameParams, FrameStats, IcpParams, MatchFrameStats, PlaneInfo, PlaneParams, PlaneStats, Pose,
+from ._capi import (ClusterInfo, ClusterParams, ClusterStats, RegionParams, FrameDetection, FrameParams, FrameStats, IcpParams, MatchFrameStats, PlaneInfo, PlaneParams, PlaneStats, Pose,
                     PoseScore, PPFError, RefineInfo,
                     RefineParams, RefineStats, RenderParams, RenderStats, SelectInfo, SelectParams, SelectStats, VerifyParams, VerifyStats,
                     check, lib)
@@ -27,14 +27,19 @@ class DeviceCloud:
         self._ptr = ptr
 
     @classmethod
-    def upload(cls, rows: np.ndarray, normal_offset: int = 3) -> "DeviceCloud":
+    def upload(cls, rows: np.ndarray, normal_offset: int = 3, curvature=None) -> "DeviceCloud":
+        """rows: N x 3 (xyz) or N x 6 (xyz + normal); curvature: None (zero) or N float32 (ppf_cloud_set_curvature)"""
         a = np.ascontiguousarray(rows, dtype=np.float32)
         if a.ndim != 2 or a.shape[1] < 3:
             raise PPFError(_capi.PPF_ERR_INVALID, "cloud must be N x 3 (xyz) or N x 6 (xyz + normal) float32")
         cols = 6 if a.shape[1] >= 6 else 3
         out = C.c_void_p()
         check(lib().ppf_cloud_upload(a.ctypes.data, a.shape[0], a.shape[1], normal_offset, cols, C.byref(out)))
-        return cls(out)
+        cloud = cls(out)
+        if curvature is not None:
+            c = np.ascontiguousarray(curvature, dtype=np.float32).reshape(-1)
+            check(lib().ppf_cloud_set_curvature(cloud._ptr, c.ctypes.data, c.shape[0]))
+        return cloud
 
     @classmethod
     def from_depth(cls, depth, intr, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0,
@@ -212,6 +217,15 @@ class DeviceCloud:
         out = [part[0] for part in res[:n]]
         return tuple(out + [res[-1]] if return_info else out)   # the stats last
 
+    def regions(self, params=None, intr=None, image_size=None, return_info: bool = False, return_labels: bool = False):
+        """this cloud's smooth surface regions (ppf_prep_regions with one cloud; see the module-level ``region_clouds``)"""
+        res = region_clouds([self], params, intr, image_size, return_info=return_info, return_labels=return_labels)
+        if not (return_info or return_labels):
+            return res[0]
+        n = 1 + 2 * int(return_info) + int(return_labels)   # this cloud's regions, info rows, counts, labels
+        out = [part[0] for part in res[:n]]
+        return tuple(out + [res[-1]] if return_info else out)   # the stats last
+
     def knn(self, k: int):
         n = len(self)
         idx = np.zeros((n, k), dtype=np.int32)
@@ -295,6 +309,45 @@ def cluster_clouds(clouds, params=None, intr=None, image_size=None, return_info:
     return tuple(res)
 
 
+def region_clouds(clouds, params=None, intr=None, image_size=None, return_info: bool = False, return_labels: bool = False):
+    """The smooth surface regions of every cloud in one segmented call (ppf_prep_regions): region growing on the normals the
+    clouds carry, as a closed specification.  Rows of finite x, y, z and normal take part; those of curvature <=
+    ``curvature_threshold`` are smooth, the others border rows.  Two smooth rows are linked iff they are no farther apart than
+    ``tolerance`` and the dot product of their normals is >= ``normal_cos`` (both fp64; ``flags = PPF_REGION_UNORIENTED``: its
+    absolute value); a region is a connected component of the links plus the border rows whose nearest linkable smooth row
+    is in it.  Validity, ranking and the return values are ``cluster_clouds``', with ``max_regions`` for ``max_clusters``:
+    one list of region clouds per cloud; with return_info also the info rows (``CLUSTER_INFO``; ``first_row`` is the region's
+    smallest smooth row), the counts ((n_clouds, 4): regions, valid components, all components, border rows attached) and,
+    last, the call's stats; with return_labels the per-row labels (int32: the region's rank, or -1) per cloud."""
+    prm = _region_params(params)
+    K = len(clouds)
+    mc = max(1, min(int(prm.max_regions), _capi.PPF_CLUSTER_MAX_CLUSTERS))
+    ins, outs = (C.c_void_p * max(K, 1))(*[c._ptr for c in clouds]), (C.c_void_p * max(K * mc, 1))()
+    info = np.zeros((K, mc), dtype=CLUSTER_INFO)
+    counts = np.zeros((K, 4), dtype=np.int32)
+    labels = [np.full(len(c), -1, dtype=np.int32) for c in clouds] if return_labels else None
+    lab = (C.c_void_p * max(K, 1))(*[a.ctypes.data for a in labels]) if return_labels else None
+    it, rows, cols = None, 0, 0
+    if intr is not None:
+        if image_size is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "region_clouds: intr needs image_size = (rows, cols)")
+        it, (rows, cols) = (C.c_double * 4)(*_intr4(intr)), image_size
+    st = ClusterStats()
+    check(lib().ppf_prep_regions(ins, K, C.byref(prm), it, int(rows), int(cols), outs, info.ctypes.data_as(C.POINTER(ClusterInfo)),
+                                 counts.ctypes.data_as(C.POINTER(C.c_int32)), lab, C.byref(st)))
+    found = [[DeviceCloud(C.c_void_p(outs[i * mc + r])) for r in range(int(counts[i, 0]))] for i in range(K)]
+    if not (return_info or return_labels):
+        return found
+    res = [found]
+    if return_info:
+        res += [info, counts]
+    if return_labels:
+        res.append(labels)
+    if return_info:
+        res.append(_capi.stats_dict(st))
+    return tuple(res)
+
+
 def _intr4(intr):
     K = np.asarray(intr, dtype=np.float64)
     return [K[0, 0], K[1, 1], K[0, 2], K[1, 2]] if K.shape == (3, 3) else [float(v) for v in K.reshape(-1)[:4]]
@@ -337,6 +390,15 @@ def _cluster_params(params) -> ClusterParams:
         if unknown:
             raise PPFError(_capi.PPF_ERR_INVALID, f"unknown cluster parameter(s): {', '.join(unknown)}")
     return _params(ClusterParams, "ppf_default_cluster_params", params)
+
+
+def _region_params(params) -> RegionParams:
+    """``_params`` for ppf_region_params; a key that is no field of the record (a misspelt name) is an error, not ignored"""
+    if isinstance(params, dict):
+        unknown = sorted(set(params) - {f for f, _ in RegionParams._fields_})
+        if unknown:
+            raise PPFError(_capi.PPF_ERR_INVALID, f"unknown region parameter(s): {', '.join(unknown)}")
+    return _params(RegionParams, "ppf_default_region_params", params)
 
 
 def _depth_image(depth, error: str):
@@ -705,6 +767,20 @@ class CloudProcessor:
             raise PPFError(_capi.PPF_ERR_INVALID, "ProposeBoxes needs a scene cloud and a depth image")
         found, info, counts, self.cluster_stats = self.scene.clusters(params, np.asarray(CameraIntr, dtype=np.float64), self.depth.shape,
                                                                       return_info=True)
+        self.cluster_info = info[:int(counts[0])].copy()
+        self.boxes = [tuple(int(v) for v in row["box_xywh"]) for row in self.cluster_info]
+        return found
+
+    def ProposeRegions(self, CameraIntr, params=None) -> List[DeviceCloud]:
+        """ProposeBoxes for objects that touch: ``self.scene`` -- with normals and curvature, as ``Deprojection(normals=...)``
+        leaves it -- split into its smooth surface regions (ppf_prep_regions) and ``self.boxes`` set to the regions' image
+        boxes, largest region first.  params: the fields of ppf_region_params (tolerance, normal_cos, curvature_threshold,
+        min_size, max_size, max_regions, flags).  Sets ``cluster_info`` (one row per region) and ``cluster_stats``; returns
+        the region clouds."""
+        if self.scene is None or self.depth is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "ProposeRegions needs a scene cloud and a depth image")
+        found, info, counts, self.cluster_stats = self.scene.regions(params, np.asarray(CameraIntr, dtype=np.float64), self.depth.shape,
+                                                                     return_info=True)
         self.cluster_info = info[:int(counts[0])].copy()
         self.boxes = [tuple(int(v) for v in row["box_xywh"]) for row in self.cluster_info]
         return found

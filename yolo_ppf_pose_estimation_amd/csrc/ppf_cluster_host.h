@@ -7,6 +7,8 @@
  * (segment, cell) (five digit passes of seven launches and one gather), k_clu_runs, the scan, k_clu_cells, k_clu_link,
  * k_clu_flatten, k_clu_valid, the ranking's sort (the same five passes), k_clu_rank, k_clu_labels, the gather's sort (three
  * passes), k_clu_gather and k_clu_reduce: 110 launches whatever the clouds hold, none when no cloud has a row.
+ * The sequence is cut in three shared pieces (clu_begin, clu_cells, clu_finish) that ppf_prep_regions runs too, around kernels
+ * of its own (ppf_region_host.h).
  * Nothing the device counts (cells, components, clusters) comes to the host before the end: grids are sized for the rows and
  * workgroups past a device-side count leave.  The host waits once, for the cluster heads, the reductions, the counts, the
  * grids and the labels; the outputs are views into one block sized for the input, so nothing is allocated after that wait.
@@ -62,65 +64,106 @@ float cluster_smallest_tolerance(double extent) {
   return t;
 }
 
-/* fr and blk belong to the caller: on an error they outlive the wait for what was launched */
-ppf_status clusters_enqueue(FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, const ppf_cloud* const* in, int K, const ppf_cluster_params& p,
-                            const double* intr, int image_rows, int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts,
-                            int32_t* const* labels, ppf_cluster_stats& st) {
-  static const char* who = "ppf_prep_clusters";
-  const int MC = p.max_clusters;
-  std::vector<CluSeg> tab((size_t)K);
-  size_t N = 0;
-  for (int i = 0; i < K; i++) {
-    tab[i] = CluSeg{in[i]->rows.p, in[i]->curv.p, (uint32_t)N, (uint32_t)in[i]->n};
-    N += (size_t)in[i]->n;
-    if (N >= 0x7fffffffull) return fail(PPF_ERR_INVALID, "%s: the clouds hold more than INT32_MAX rows together", who);
-  }
-  if (N == 0) return PPF_OK; /* no cloud has a row: no cluster, no launch */
-  const int n = (int)N, nblk = (n + RS_BLOCK - 1) / RS_BLOCK;
-  const size_t slots = (size_t)K * MC;
+/* What ppf_prep_clusters and ppf_prep_regions (ppf_region_host.h) share: the segment table, the scratch, one zeroed block
+ * (the bounds, the counts, the cluster heads, the reductions and `extra` words of the entry's own) and the output block.
+ * clu_begin runs up to the sort by (segment, cell), the entry its k_*_runs, clu_cells the scan and the table of cells, the
+ * entry its link and flatten passes (root[], size[] final), clu_finish the ranking, the gather, the one wait and the results. */
+struct CluWork {
+  const char* who;
+  int K, MC, n;
+  size_t N;
+  std::vector<CluSeg> tab;
   CluSeg* d_tab;
   CluGrid* d_grid;
   float4* pts;
   unsigned long long* ckey;
-  uint32_t *zero, *lkey, *skey, *k1, *k2, *v1, *v2, *hist, *offs, *parent, *size, *root, *flags, *runid, *cstart;
+  uint32_t *zero, *lkey, *skey, *ka, *va, *kb, *vb, *hist, *offs, *parent, *size, *root, *flags, *runid, *cstart;
   int32_t *rank, *d_labels;
-  /* one zeroed block: the bounds, the counts, the cluster heads, the reductions */
-  const size_t z_mm = 0, z_fin = z_mm + (size_t)K * 6, z_cnt = z_fin + K, z_head = z_cnt + (size_t)K * 2, z_acc = z_head + slots * 2,
-               z_words = (z_acc + slots * CLU_ACC + 3) & ~(size_t)3;
+  size_t z_mm, z_fin, z_cnt, z_head, z_acc, z_extra, z_words;
+  dim3 rows_grid, rows1_grid;
+  double tol;
+};
+
+/* fr and blk belong to the caller: on an error they outlive the wait for what was launched.  w.N == 0 on PPF_OK: no cloud has
+ * a row, nothing was launched and nothing is to be done */
+template <bool NORMALS>
+ppf_status clu_begin(FrameRun& fr, CluWork& w, std::shared_ptr<DevBuf<float>>& blk, const char* who, const ppf_cloud* const* in, int K, int MC,
+                     float tolerance, size_t extra) {
+  w.who = who;
+  w.K = K;
+  w.MC = MC;
+  w.tab.resize((size_t)K);
+  size_t N = 0;
+  for (int i = 0; i < K; i++) {
+    w.tab[i] = CluSeg{in[i]->rows.p, in[i]->curv.p, (uint32_t)N, (uint32_t)in[i]->n};
+    N += (size_t)in[i]->n;
+    if (N >= 0x7fffffffull) return fail(PPF_ERR_INVALID, "%s: the clouds hold more than INT32_MAX rows together", who);
+  }
+  w.N = N;
+  if (N == 0) return PPF_OK; /* no cloud has a row: no cluster, no launch */
+  const int n = w.n = (int)N, nblk = (n + RS_BLOCK - 1) / RS_BLOCK;
+  const size_t slots = (size_t)K * MC;
+  uint32_t *k1, *k2, *v1, *v2;
+  w.z_mm = 0; w.z_fin = w.z_mm + (size_t)K * 6; w.z_cnt = w.z_fin + K; w.z_head = w.z_cnt + (size_t)K * 2; w.z_acc = w.z_head + slots * 2;
+  w.z_extra = w.z_acc + slots * CLU_ACC;
+  w.z_words = (w.z_extra + extra + 3) & ~(size_t)3;
   ppf_status s;
-  if ((s = fr.get(K, &d_tab)) != PPF_OK || (s = fr.get(K, &d_grid)) != PPF_OK || (s = fr.get(z_words, &zero)) != PPF_OK ||
-      (s = fr.get(N, &pts)) != PPF_OK || (s = fr.get(N + 1, &ckey)) != PPF_OK || (s = fr.get(N, &lkey)) != PPF_OK ||
-      (s = fr.get(N, &skey)) != PPF_OK || (s = fr.get(N, &k1)) != PPF_OK || (s = fr.get(N, &k2)) != PPF_OK || (s = fr.get(N, &v1)) != PPF_OK ||
-      (s = fr.get(N, &v2)) != PPF_OK || (s = fr.get((size_t)256 * nblk, &hist)) != PPF_OK || (s = fr.get((size_t)256 * nblk, &offs)) != PPF_OK ||
-      (s = fr.get(N, &parent)) != PPF_OK || (s = fr.get(N, &size)) != PPF_OK || (s = fr.get(N, &root)) != PPF_OK ||
-      (s = fr.get(N + 1, &flags)) != PPF_OK || (s = fr.get(N + 1, &runid)) != PPF_OK || (s = fr.get(N + 2, &cstart)) != PPF_OK ||
-      (s = fr.get(N, &rank)) != PPF_OK || (s = fr.get(N, &d_labels)) != PPF_OK)
+  if ((s = fr.get(K, &w.d_tab)) != PPF_OK || (s = fr.get(K, &w.d_grid)) != PPF_OK || (s = fr.get(w.z_words, &w.zero)) != PPF_OK ||
+      (s = fr.get(N, &w.pts)) != PPF_OK || (s = fr.get(N + 1, &w.ckey)) != PPF_OK || (s = fr.get(N, &w.lkey)) != PPF_OK ||
+      (s = fr.get(N, &w.skey)) != PPF_OK || (s = fr.get(N, &k1)) != PPF_OK || (s = fr.get(N, &k2)) != PPF_OK || (s = fr.get(N, &v1)) != PPF_OK ||
+      (s = fr.get(N, &v2)) != PPF_OK || (s = fr.get((size_t)256 * nblk, &w.hist)) != PPF_OK || (s = fr.get((size_t)256 * nblk, &w.offs)) != PPF_OK ||
+      (s = fr.get(N, &w.parent)) != PPF_OK || (s = fr.get(N, &w.size)) != PPF_OK || (s = fr.get(N, &w.root)) != PPF_OK ||
+      (s = fr.get(N + 1, &w.flags)) != PPF_OK || (s = fr.get(N + 1, &w.runid)) != PPF_OK || (s = fr.get(N + 2, &w.cstart)) != PPF_OK ||
+      (s = fr.get(N, &w.rank)) != PPF_OK || (s = fr.get(N, &w.d_labels)) != PPF_OK)
     return s;
   blk.reset(new DevBuf<float>());
   HIPCHK(blk->reserve(N * 7)); /* [rows | curvature] */
-  HIPCHK(hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(CluSeg), hipMemcpyHostToDevice));
-  HIPCHK(hipMemsetAsync(zero, 0, z_words * sizeof(uint32_t), nullptr));
-  uint32_t *mm = zero + z_mm, *fin = zero + z_fin, *cnt = zero + z_cnt, *acc = zero + z_acc;
-  int32_t* head = reinterpret_cast<int32_t*>(zero + z_head);
+  HIPCHK(hipMemcpy(w.d_tab, w.tab.data(), w.tab.size() * sizeof(CluSeg), hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(w.zero, 0, w.z_words * sizeof(uint32_t), nullptr));
+  uint32_t *mm = w.zero + w.z_mm, *fin = w.zero + w.z_fin;
 
-  const dim3 b256(CLU_BLOCK), rows_grid = grid_for(N, CLU_BLOCK), rows1_grid = grid_for(N + 1, CLU_BLOCK);
-  const double tol = (double)p.tolerance, h = tol * CLU_CELL;
+  const dim3 b256(CLU_BLOCK);
+  w.rows_grid = grid_for(N, CLU_BLOCK);
+  w.rows1_grid = grid_for(N + 1, CLU_BLOCK);
+  w.tol = (double)tolerance;
+  const double h = w.tol * CLU_CELL;
+  FRAME_LAUNCH(fr, k_clu_bounds<NORMALS>, dim3((unsigned)K, CLU_BOUNDS_WGS), b256, w.d_tab, mm, fin);
+  FRAME_LAUNCH(fr, k_clu_grid, dim3(1), dim3(FRAME_MAX_BOXES), mm, fin, K, h, w.d_grid);
+  FRAME_LAUNCH(fr, k_clu_keys<NORMALS>, w.rows_grid, b256, w.d_tab, K, (uint32_t)N, w.d_grid, w.lkey, k1, w.skey, v1, w.parent, w.size);
+  HIPCHK(hipGetLastError());
+  w.ka = k1; w.va = v1; w.kb = k2; w.vb = v2;
+  return cluster_sort_segmented(fr, w.ka, w.va, w.kb, w.vb, n, w.hist, w.offs, w.skey);
+}
+
+/* after the entry's k_*_runs (w.va: the sorted order; flags): the scan of the run starts and the table of occupied cells */
+ppf_status clu_cells(FrameRun& fr, CluWork& w) {
+  ppf_status s;
+  if ((s = frame_scan(fr, w.flags, w.runid, w.N + 1)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_clu_cells, w.rows1_grid, dim3(CLU_BLOCK), (uint32_t)w.N, w.va, w.lkey, w.skey, w.flags, w.runid, w.ckey, w.cstart);
+  return PPF_OK;
+}
+
+/* counts: [K][stride] = {output, valid, all, then the entry's `extra` words per cloud} */
+ppf_status clu_finish(FrameRun& fr, CluWork& w, std::shared_ptr<DevBuf<float>>& blk, int min_size, int max_size, const double* intr,
+                      int image_rows, int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts, int stride,
+                      int32_t* const* labels, ppf_cluster_stats& st) {
+  const char* who = w.who;
+  const int K = w.K, MC = w.MC, n = w.n;
+  const size_t N = w.N, slots = (size_t)K * MC, z_mm = w.z_mm, z_cnt = w.z_cnt, z_head = w.z_head, z_acc = w.z_acc, z_words = w.z_words;
+  const std::vector<CluSeg>& tab = w.tab;
+  CluSeg* d_tab = w.d_tab;
+  CluGrid* d_grid = w.d_grid;
+  uint32_t *zero = w.zero, *skey = w.skey, *hist = w.hist, *offs = w.offs, *size = w.size, *root = w.root;
+  uint32_t *&ka = w.ka, *&va = w.va, *&kb = w.kb, *&vb = w.vb;
+  int32_t *rank = w.rank, *d_labels = w.d_labels;
+  uint32_t *cnt = zero + z_cnt, *acc = zero + z_acc;
+  int32_t* head = reinterpret_cast<int32_t*>(zero + w.z_head);
+  const dim3 b256(CLU_BLOCK), rows_grid = w.rows_grid;
   CluIntr cam = {0.0, 0.0, 0.0, 0.0, image_rows, image_cols, intr ? 1 : 0};
   if (intr) { cam.fx = intr[0]; cam.fy = intr[1]; cam.ppx = intr[2]; cam.ppy = intr[3]; }
+  ppf_status s;
 
-  FRAME_LAUNCH(fr, k_clu_bounds, dim3((unsigned)K, CLU_BOUNDS_WGS), b256, d_tab, mm, fin);
-  FRAME_LAUNCH(fr, k_clu_grid, dim3(1), dim3(FRAME_MAX_BOXES), mm, fin, K, h, d_grid);
-  FRAME_LAUNCH(fr, k_clu_keys, rows_grid, b256, d_tab, K, (uint32_t)N, d_grid, lkey, k1, skey, v1, parent, size);
-  HIPCHK(hipGetLastError());
-  uint32_t *ka = k1, *va = v1, *kb = k2, *vb = v2;
-  if ((s = cluster_sort_segmented(fr, ka, va, kb, vb, n, hist, offs, skey)) != PPF_OK) return s;
-  FRAME_LAUNCH(fr, k_clu_runs, rows1_grid, b256, d_tab, K, (uint32_t)N, va, lkey, skey, pts, flags);
-  HIPCHK(hipGetLastError());
-  if ((s = frame_scan(fr, flags, runid, N + 1)) != PPF_OK) return s;
-  FRAME_LAUNCH(fr, k_clu_cells, rows1_grid, b256, (uint32_t)N, va, lkey, skey, flags, runid, ckey, cstart);
-  FRAME_LAUNCH(fr, k_clu_link, dim3((unsigned)N), dim3(64), pts, ckey, cstart, runid + N, tol * tol, parent);
-  FRAME_LAUNCH(fr, k_clu_flatten, rows_grid, b256, (uint32_t)N, lkey, parent, root, size);
-  FRAME_LAUNCH(fr, k_clu_valid, rows_grid, b256, d_tab, K, (uint32_t)N, root, size, (uint32_t)p.min_size, (uint32_t)p.max_size, ka, va, cnt);
+  FRAME_LAUNCH(fr, k_clu_valid, rows_grid, b256, d_tab, K, (uint32_t)N, root, size, (uint32_t)min_size, (uint32_t)max_size, ka, va, cnt);
   HIPCHK(hipGetLastError());
   if ((s = cluster_sort_segmented(fr, ka, va, kb, vb, n, hist, offs, skey)) != PPF_OK) return s;
   FRAME_LAUNCH(fr, k_clu_rank, rows_grid, b256, d_tab, K, (uint32_t)N, va, cnt, size, MC, rank, head);
@@ -159,9 +202,10 @@ ppf_status clusters_enqueue(FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, c
   size_t at = 0; /* the clusters lie in the block one after the other, in (cloud, rank) order */
   for (int i = 0; i < K; i++) {
     const uint32_t valid = z[z_cnt + (size_t)i * 2], all = z[z_cnt + (size_t)i * 2 + 1], shown = std::min(valid, (uint32_t)MC);
-    counts[i * 3] = (int32_t)shown;
-    counts[i * 3 + 1] = (int32_t)valid;
-    counts[i * 3 + 2] = (int32_t)all;
+    counts[i * stride] = (int32_t)shown;
+    counts[i * stride + 1] = (int32_t)valid;
+    counts[i * stride + 2] = (int32_t)all;
+    for (int k = 3; k < stride; k++) counts[i * stride + k] = (int32_t)z[w.z_extra + (size_t)i * (stride - 3) + (k - 3)];
     for (uint32_t r = 0; r < shown; r++) {
       const size_t slot = (size_t)i * MC + r;
       ppf_cluster_info& ci = info[slot];
@@ -189,6 +233,21 @@ ppf_status clusters_enqueue(FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, c
   st.n_launches = fr.launches;
   st.n_host_syncs = fr.syncs;
   return PPF_OK;
+}
+
+ppf_status clusters_enqueue(FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, const ppf_cloud* const* in, int K, const ppf_cluster_params& p,
+                            const double* intr, int image_rows, int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts,
+                            int32_t* const* labels, ppf_cluster_stats& st) {
+  CluWork w;
+  ppf_status s = clu_begin<false>(fr, w, blk, "ppf_prep_clusters", in, K, p.max_clusters, p.tolerance, 0);
+  if (s != PPF_OK || w.N == 0) return s;
+  const dim3 b256(CLU_BLOCK);
+  FRAME_LAUNCH(fr, k_clu_runs, w.rows1_grid, b256, w.d_tab, K, (uint32_t)w.N, w.va, w.lkey, w.skey, w.pts, w.flags);
+  HIPCHK(hipGetLastError());
+  if ((s = clu_cells(fr, w)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_clu_link, dim3((unsigned)w.N), dim3(64), w.pts, w.ckey, w.cstart, w.runid + w.N, w.tol * w.tol, w.parent);
+  FRAME_LAUNCH(fr, k_clu_flatten, w.rows_grid, b256, (uint32_t)w.N, w.lkey, w.parent, w.root, w.size);
+  return clu_finish(fr, w, blk, p.min_size, p.max_size, intr, image_rows, image_cols, out, info, counts, 3, labels, st);
 }
 
 ppf_status clusters_run(const ppf_cloud* const* in, int K, const ppf_cluster_params& p, const double* intr, int image_rows, int image_cols,

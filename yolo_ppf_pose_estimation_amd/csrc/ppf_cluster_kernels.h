@@ -50,16 +50,20 @@ struct CluGrid {
 
 __device__ __forceinline__ int clu_seg_of(const CluSeg* __restrict__ tab, int K, uint32_t g) { return frame_find(&tab[0].off, 6, K, g); }
 __device__ __forceinline__ const float* clu_row(const CluSeg& sg, uint32_t g) { return sg.rows + (size_t)(g - sg.off) * 6; }
+/* the rows that take part: those of finite x, y, z; NORMALS (ppf_prep_regions): of finite normals too */
+template <bool NORMALS>
+__device__ __forceinline__ bool clu_takes(const float* p) { return prep_finite3(p) && (!NORMALS || prep_finite3(p + 3)); }
 
 /* per-segment bounds of the finite rows, as k_frame_bounds keeps them: mm[s][0..2] = ~min, [3..5] = max (ordered words,
  * identity 0), fin[s] = their number; integer atomicMax / atomicAdd on zeroed words.  grid: (K, CLU_BOUNDS_WGS) */
+template <bool NORMALS = false>
 __global__ __launch_bounds__(CLU_BLOCK) void k_clu_bounds(const CluSeg* __restrict__ tab, uint32_t* __restrict__ mm, uint32_t* __restrict__ fin) {
   const int s = blockIdx.x;
   const CluSeg sg = tab[s];
   uint32_t v[7] = {0, 0, 0, 0, 0, 0, 0};
   for (uint32_t i = blockIdx.y * CLU_BLOCK + threadIdx.x; i < sg.n; i += CLU_BLOCK * gridDim.y) {
     const float* p = sg.rows + (size_t)i * 6;
-    if (!prep_finite3(p)) continue;
+    if (!clu_takes<NORMALS>(p)) continue;
     v[6]++;
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -109,6 +113,7 @@ __global__ __launch_bounds__(FRAME_MAX_BOXES) void k_clu_grid(const uint32_t* __
 
 /* per row g: its cell key (10 bits per axis; CLU_NO_KEY: not finite, or its segment's grid does not fit), its segment,
  * and the union-find's start: every row its own parent, every size 0.  grid: rows */
+template <bool NORMALS = false>
 __global__ __launch_bounds__(CLU_BLOCK) void k_clu_keys(const CluSeg* __restrict__ tab, int K, uint32_t N, const CluGrid* __restrict__ grid,
                                                         uint32_t* __restrict__ lkey, uint32_t* __restrict__ sort_key, uint32_t* __restrict__ skey,
                                                         uint32_t* __restrict__ vals, uint32_t* __restrict__ parent, uint32_t* __restrict__ size) {
@@ -118,7 +123,7 @@ __global__ __launch_bounds__(CLU_BLOCK) void k_clu_keys(const CluSeg* __restrict
   const CluSeg sg = tab[s];
   const float* p = clu_row(sg, g);
   uint32_t key = CLU_NO_KEY;
-  if (prep_finite3(p) && grid[s].ok) {
+  if (clu_takes<NORMALS>(p) && grid[s].ok) {
     key = 0u;
 #pragma unroll
     for (int k = 0; k < 3; k++) {

@@ -24,12 +24,12 @@
  *   kernels   ppf_train_kernels.h (table build)  ppf_sample_kernels.h (A2)  ppf_match_kernels.h (k_frames / k_pairs /
  *             k_group / k_vote)  ppf_pose_kernels.h (k_finalize, k_rank, clustering)  ppf_icp_kernels.h  ppf_prep_kernels.h
  *             ppf_depth_kernels.h  ppf_depth_normals_kernels.h  ppf_verify_kernels.h  ppf_render_kernels.h  ppf_select_kernels.h  ppf_refine_kernels.h
- *             ppf_register_kernels.h  ppf_plane_kernels.h  ppf_cluster_kernels.h
+ *             ppf_register_kernels.h  ppf_plane_kernels.h  ppf_cluster_kernels.h  ppf_region_kernels.h
  *   host      ppf_device_mem.h (errors, block cache)  ppf_host_common.h (scans, sorts, model / workspace structs)
  *             ppf_model_host.h  ppf_match_host.h  ppf_batch_host.h  ppf_icp_host.h  ppf_prep_host.h (the segmented
  *             preparation stages; ppf_prep_* = one segment)  ppf_frame_host.h (ppf_prep_frame = their chain)
  *             ppf_match_frame_host.h  ppf_depth_host.h  ppf_posetable_host.h  ppf_verify_host.h  ppf_render_host.h
- *             ppf_select_host.h  ppf_refine_host.h  ppf_register_host.h  ppf_plane_host.h  ppf_cluster_host.h
+ *             ppf_select_host.h  ppf_refine_host.h  ppf_register_host.h  ppf_plane_host.h  ppf_cluster_host.h  ppf_region_host.h
  *             (the C-ABI)
  *
  * Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see __graft_entry__.build()).
@@ -70,6 +70,7 @@
 #include "ppf_register_kernels.h" /* k_reg_rays, k_reg_clear, k_reg_draw, k_reg_resolve */
 #include "ppf_plane_kernels.h" /* k_pln_hyp, k_pln_count, k_pln_best, k_pln_sum / _finish, k_pln_flags, k_pln_compact, k_pln_gather */
 #include "ppf_cluster_kernels.h" /* k_clu_bounds, k_clu_grid, k_clu_keys, k_clu_runs, k_clu_cells, k_clu_link, k_clu_flatten ... k_clu_reduce */
+#include "ppf_region_kernels.h" /* k_reg_runs, k_reg_link, k_reg_flatten, k_reg_attach */
 #include "ppf_pose_kernels.h"  /* k_finalize, k_rank, clustering, result blocks */
 #include "ppf_host_common.h"   /* scans, sorts, sampling, ppf_model / ppf_workspace, enqueue_cluster */
 #include "ppf_model_host.h"    /* C-ABI: defaults, training, handles, model file */
@@ -88,3 +89,4 @@
 #include "ppf_register_host.h"    /* a sensor depth image aligned to the colour camera: ppf_camera_*, ppf_depth_map, ppf_depth_register */
 #include "ppf_plane_host.h"       /* a frame's support planes found and removed: ppf_prep_planes, ppf_prep_planes_apply */
 #include "ppf_cluster_host.h"     /* a plane-free cloud split into object clusters: ppf_prep_clusters */
+#include "ppf_region_host.h"      /* a cloud split into smooth surface regions: ppf_prep_regions */

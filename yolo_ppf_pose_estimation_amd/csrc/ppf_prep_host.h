@@ -424,6 +424,11 @@ ppf_status ppf_cloud_upload(const float* rows, int n, int stride, int noff, int 
   *out = c.release();
   return PPF_OK;
 }
+ppf_status ppf_cloud_set_curvature(ppf_cloud* c, const float* curvature, int n) {
+  if (!c || !curvature || n != c->n) return fail(PPF_ERR_INVALID, "ppf_cloud_set_curvature: NULL, or n is not the cloud's row count");
+  if (n) HIPCHK(hipMemcpy(c->curv.p, curvature, (size_t)n * sizeof(float), hipMemcpyHostToDevice)); /* after every kernel queued so far */
+  return PPF_OK;
+}
 ppf_status ppf_cloud_release(ppf_cloud* c) {
   if (c) (void)hipDeviceSynchronize(); /* its rows return to the block cache: no kernel may still be reading them */
   delete c;

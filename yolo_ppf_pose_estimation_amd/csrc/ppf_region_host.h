@@ -1,0 +1,112 @@
+/*
+ * ppf_region_host.h — host side of ppf_prep_regions: the smooth surface regions of up to 256 clouds in one pass (DESIGN.md
+ * §22).  Kernels: ppf_region_kernels.h.  Included by ppf_hip.hip after ppf_cluster_host.h, whose clu_begin, clu_cells and
+ * clu_finish it runs around its own four kernels.
+ *
+ * Per call: clu_begin<true> (k_clu_bounds, k_clu_grid and k_clu_keys over the eligible rows, the sort by (segment, cell)),
+ * k_reg_runs, clu_cells, k_reg_link, k_reg_flatten, k_reg_attach, clu_finish: 111 launches whatever the clouds hold -- one more
+ * than ppf_prep_clusters, the attach pass -- and none when no cloud has a row.  One upload before any device work, one wait.
+ */
+#ifndef PPF_REGION_HOST_H
+#define PPF_REGION_HOST_H
+
+namespace {
+
+ppf_status region_params_check(const char* who, const ppf_region_params* p) {
+  if (!p) return fail(PPF_ERR_INVALID, "%s: the params are NULL", who);
+  if (!(std::isfinite(p->tolerance) && p->tolerance > 0.f)) return fail(PPF_ERR_INVALID, "%s: tolerance must be finite and > 0", who);
+  if (!(p->normal_cos >= -1.f && p->normal_cos <= 1.f)) return fail(PPF_ERR_INVALID, "%s: normal_cos must lie in -1..1", who);
+  if (!(p->curvature_threshold >= 0.f)) return fail(PPF_ERR_INVALID, "%s: curvature_threshold must be >= 0 (+inf: every eligible row is smooth)", who);
+  if (p->min_size < 1) return fail(PPF_ERR_INVALID, "%s: min_size is %d (>= 1)", who, p->min_size);
+  if (p->max_size < 0) return fail(PPF_ERR_INVALID, "%s: max_size is %d (>= 0; 0: no bound)", who, p->max_size);
+  if (p->max_regions < 1 || p->max_regions > PPF_CLUSTER_MAX_CLUSTERS)
+    return fail(PPF_ERR_INVALID, "%s: max_regions is %d (1..%d)", who, p->max_regions, PPF_CLUSTER_MAX_CLUSTERS);
+  if (p->flags & ~PPF_REGION_UNORIENTED) return fail(PPF_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)p->flags);
+  return PPF_OK;
+}
+
+/* fr and blk belong to the caller, as in clusters_enqueue */
+ppf_status regions_enqueue(FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, const ppf_cloud* const* in, int K, const ppf_region_params& p,
+                           const double* intr, int image_rows, int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts,
+                           int32_t* const* labels, ppf_cluster_stats& st) {
+  CluWork w;
+  ppf_status s = clu_begin<true>(fr, w, blk, "ppf_prep_regions", in, K, p.max_regions, p.tolerance, (size_t)K /* attached border rows */);
+  if (s != PPF_OK || w.N == 0) return s;
+  float4* nrm;
+  if ((s = fr.get(w.N, &nrm)) != PPF_OK) return s;
+  const dim3 b256(CLU_BLOCK);
+  const double tol2 = w.tol * w.tol, cosv = (double)p.normal_cos;
+  const int unoriented = (p.flags & PPF_REGION_UNORIENTED) ? 1 : 0;
+  FRAME_LAUNCH(fr, k_reg_runs, w.rows1_grid, b256, w.d_tab, (uint32_t)w.N, w.va, w.lkey, w.skey, p.curvature_threshold, w.pts, nrm, w.flags);
+  HIPCHK(hipGetLastError());
+  if ((s = clu_cells(fr, w)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_reg_link, dim3((unsigned)w.N), dim3(64), w.pts, nrm, w.ckey, w.cstart, w.runid + w.N, tol2, cosv, unoriented, w.parent);
+  FRAME_LAUNCH(fr, k_reg_flatten, w.rows_grid, b256, (uint32_t)w.N, w.pts, nrm, w.parent, w.root, w.size);
+  FRAME_LAUNCH(fr, k_reg_attach, w.rows_grid, b256, (uint32_t)w.N, w.pts, nrm, w.lkey, w.skey, w.ckey, w.cstart, w.runid + w.N, tol2, cosv,
+               unoriented, w.root, w.size, w.zero + w.z_extra);
+  return clu_finish(fr, w, blk, p.min_size, p.max_size, intr, image_rows, image_cols, out, info, counts, 4, labels, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+void ppf_default_region_params(ppf_region_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->tolerance = 0.01f;
+  p->normal_cos = 0.9659258f;
+  p->curvature_threshold = 0.03f;
+  p->min_size = 100;
+  p->max_size = 0;
+  p->max_regions = 64;
+}
+
+ppf_status ppf_prep_regions(const ppf_cloud* const* in, int n_clouds, const ppf_region_params* p, const double* intr, int image_rows,
+                            int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts, int32_t* const* labels,
+                            ppf_cluster_stats* stats) {
+  static const char* who = "ppf_prep_regions";
+  const auto t0 = std::chrono::steady_clock::now();
+  ppf_cluster_stats local;
+  ppf_cluster_stats& st = stats ? *stats : local;
+  std::memset(&st, 0, sizeof(st));
+  const bool count_ok = n_clouds >= 0 && n_clouds <= FRAME_MAX_BOXES;
+  const size_t slots = count_ok ? (size_t)n_clouds * (size_t)(p ? std::min(std::max(p->max_regions, 1), PPF_CLUSTER_MAX_CLUSTERS) : 1) : 0;
+  auto clear = [&]() {
+    for (size_t k = 0; out && k < slots; k++) out[k] = nullptr;
+    if (info && slots) std::memset(info, 0, slots * sizeof(ppf_cluster_info));
+    if (counts && count_ok && n_clouds) std::memset(counts, 0, (size_t)n_clouds * 4 * sizeof(int32_t));
+  };
+  clear();
+  if (!count_ok) return fail(PPF_ERR_INVALID, "%s: n_clouds is %d (0..%d)", who, n_clouds, FRAME_MAX_BOXES);
+  if (!in || !out || !info || !counts) return fail(PPF_ERR_INVALID, "%s: in, out, info and counts must not be NULL", who);
+  ppf_status s = region_params_check(who, p);
+  if (s != PPF_OK) return s;
+  if (intr) {
+    for (int k = 0; k < 4; k++)
+      if (!std::isfinite(intr[k])) return fail(PPF_ERR_INVALID, "%s: the intrinsics are not finite", who);
+    if (image_rows < 1 || image_cols < 1) return fail(PPF_ERR_INVALID, "%s: the image is %d x %d", who, image_rows, image_cols);
+  }
+  for (int i = 0; i < n_clouds; i++)
+    if (!in[i]) return fail(PPF_ERR_INVALID, "%s: in[%d] is NULL", who, i);
+  if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
+  st.n_clouds = n_clouds;
+  if (n_clouds > 0) {
+    FrameRun fr;
+    std::shared_ptr<DevBuf<float>> blk;
+    s = regions_enqueue(fr, blk, in, n_clouds, *p, intr, image_rows, image_cols, out, info, counts, labels, st);
+    /* kernels of a failed call may still run: wait before its scratch and the output block go back to the block cache */
+    if (s != PPF_OK) (void)hipDeviceSynchronize();
+  }
+  if (s != PPF_OK) {
+    clear();
+    std::memset(&st, 0, sizeof(st));
+    return s;
+  }
+  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PPF_OK;
+}
+
+}  // extern "C"
+
+#endif /* PPF_REGION_HOST_H */
