@@ -1,7 +1,9 @@
 """ppf_refine_frame on the device against the numpy restatement of DESIGN.md §17 (tests/refine_oracle.py): the refined
 matrices and every info field byte for byte over models of 50, 128 and 3,001 rows, both model steps and every status; a job's
 bytes do not depend on the rest of the call; the in-place call; max_iters 0; constant launch and read-back counts; and the
-chain prep -> match -> select -> refine on the two-bottle frame, then the same poses tracked into a second frame."""
+chain prep -> match -> select -> refine on the two-bottle frame, then the same poses tracked into a second frame; the edge
+cases of tests/refine_cases.py (image borders, depth holes, non-finite rows and poses, the guards at equality, tied pivots, the
+sizes at the tiles of the sums), more jobs than compute units, and seeded random draws."""
 import ctypes as C
 import os
 import subprocess
@@ -9,8 +11,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import refine_cases as RC
 import refine_oracle as R
 import render_oracle as RO
+from conftest import soak_seeds
 from test_gpu_frame import LAYOUT, _render_frame
 from yolo_ppf_pose_estimation_amd import _capi
 from yolo_ppf_pose_estimation_amd._capi import FrameDetection, Pose, RefineInfo, RefineParams, RefineStats, check, lib
@@ -292,3 +296,78 @@ def test_cpp_facade_refine_frame(tmp_path, bottle, compiler):
             assert lines[at] == f"jobs {len(sel)} launches 1 read-backs 1"
             at += 1
         held = [[refined[rnk][0]] for rnk in range(len(sel))]
+
+
+# ---- 4. the edges: tests/refine_cases.py on the device --------------------------------------------------------------------------
+def assert_run(r, what):
+    """one call for the run r of refine_cases.py: every pose's matrix, info row and residual are the oracle's bytes, a pose no
+    step was applied to keeps its record, the hand counts hold on the device's info, rows without a pose stay NONE.  Returns
+    the statuses seen."""
+    clouds = [DeviceCloud.upload(m) for m in r["models"]]
+    top = max(len(plist) for plist in r["poses"])
+    mats, info, st, out = call(clouds, r["poses"], r["depth"], r["intr"], r["prm"], top=top)
+    assert (st["n_jobs"], st["n_launches"], st["n_host_syncs"]) == (sum(len(plist) for plist in r["poses"]), 1, 1), (what, st)
+    seen = set()
+    for i, plist in enumerate(r["poses"]):
+        for k, T0 in enumerate(plist):
+            T, want = R.refine(r["models"][i], T0, r["depth"], r["intr"], r["prm"])
+            assert_job(mats[i, k], info[i, k], T, want, (what, i, k))
+            for f, v in r["hand"].get((i, k), {}).items():
+                assert int(info[i, k][f]) == v, (what, i, k, f, info[i, k])
+            rec = out[i * top + k]
+            assert np.float64(rec.residual).tobytes() == np.float64(want["rmse_last"]).tobytes(), (what, i, k)
+            if want["iterations"] == 0:   # the record as given, apart from the residual
+                given = Pose()
+                given.pose[:] = np.asarray(T0, dtype=np.float64).reshape(16).tolist()
+                given.num_votes, given.alpha, given.residual = 10 * i + k, 0.25 * k, rec.residual
+                assert bytes(rec) == bytes(given), (what, i, k)
+            seen.add(int(info[i, k]["status"]))
+        for k in range(len(plist), top):
+            assert info[i, k].tobytes() == bytes(C.sizeof(RefineInfo)) and bytes(out[i * top + k]) == bytes(Pose()), (what, i, k)
+            seen.add(int(info[i, k]["status"]))
+    return seen
+
+
+_SEEN = {}
+
+
+@pytest.mark.parametrize("name", RC.NAMES)
+def test_byte_parity_on_the_edge_cases(name):
+    c = RC.case(name)
+    _SEEN[name] = set()
+    for r in c["runs"]:
+        _SEEN[name] |= assert_run(r, (name, r["what"]))
+    if name == RC.NAMES[-1] and len(_SEEN) == len(RC.NAMES):   # the whole set ran: every status without the old fixture
+        assert set().union(*_SEEN.values()) == {R.NONE, R.CONVERGED, R.MAX_ITERS, R.LOST, R.STEP}, _SEEN
+
+
+def test_more_jobs_than_compute_units(case):
+    """24 detections x 16 poses, 384 workgroups on 256 CUs: each job's bytes are those of the same (model, pose) alone"""
+    aside = np.eye(4)
+    aside[:3, 3] = [0.2, 0.1, -0.1]   # the plane on the background at 0.9, beside the object
+    plane = RC.plane64()
+    models = [case["models"][0], case["models"][1], plane]
+    clouds = [case["clouds"][0], case["clouds"][1], DeviceCloud.upload(plane)]
+    starts = [case["poses"][0], case["poses"][1],
+              [aside, R.offset_pose(aside, np.array([0.2, 0.1, 0.9]), [0.0, 0.0, 0.002], [0.0, 0.0, 0.0]),
+               R.offset_pose(aside, np.array([0.2, 0.1, 0.9]), [0.001, 0.001, 0.002], [0.01, -0.005, 0.02])]]
+    alone = {}
+    for m in range(3):
+        for s, T0 in enumerate(starts[m]):
+            m1, i1, st, _ = call([clouds[m]], [[T0]], case["depth"], INTR, top=1)
+            alone[m, s] = (m1[0, 0].tobytes(), i1[0, 0].tobytes())
+            T, want = R.refine(models[m], T0, case["depth"], INTR)
+            assert_job(m1[0, 0], i1[0, 0], T, want, ("alone", m, s))
+    which = [[(d % 3, (d // 3 + k) % len(starts[d % 3])) for k in range(16)] for d in range(24)]
+    mats, info, st, _ = call([clouds[m] for m, _ in (w[0] for w in which)], [[starts[m][s] for m, s in w] for w in which], case["depth"], INTR, top=16)
+    assert (st["n_jobs"], st["n_launches"], st["n_host_syncs"]) == (384, 1, 1), st
+    assert {int(v) for v in info["status"].ravel()} >= {R.CONVERGED, R.LOST}
+    for d, w in enumerate(which):
+        for k, (m, s) in enumerate(w):
+            assert (mats[d, k].tobytes(), info[d, k].tobytes()) == alone[m, s], (d, k, m, s)
+
+
+@pytest.mark.parametrize("seed", soak_seeds(6, "PPF_SOAK_REFINE"))
+def test_refine_random_draw(seed):
+    cfg, r = RC.random_draw(seed)
+    assert_run(r, cfg)

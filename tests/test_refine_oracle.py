@@ -108,23 +108,6 @@ def test_summation_order(case, n):
     c0 = R.centre(model, 1)
     tot, n_cons, n_pairs, ck = R.evaluate(model, T0, c0, depth, INTR, 0.02)
     assert n_pairs > 0 and n_cons >= n_pairs
-    o = R.transform_rows(model, T0).astype(np.float64)
-    prods = np.zeros((n, R.ENTRIES))
-    for j in range(n):
-        x, y, z, nx, ny, nz = (float(v) for v in o[j])
-        if not (nx * x + ny * y) + nz * z < 0 or not z > 0:
-            continue
-        ui, vi = np.floor((x * INTR[0] / z + INTR[2]) + 0.5), np.floor((y * INTR[1] / z + INTR[3]) + 0.5)
-        if not (0 <= ui < COLS and 0 <= vi < ROWS):
-            continue
-        d = depth[int(vi), int(ui)]
-        if not (np.isfinite(d) and d > 0 and abs(np.float32(d - np.float32(o[j, 2]))) <= np.float32(0.02)):
-            continue
-        d = float(d)
-        q = ((ui - INTR[2]) * d / INTR[0], (vi - INTR[3]) * d / INTR[1], d)
-        a = (x - ck[0], y - ck[1], z - ck[2])
-        r = (nx * (q[0] - x) + ny * (q[1] - y)) + nz * (q[2] - z)
-        J = (a[1] * nz - a[2] * ny, a[2] * nx - a[0] * nz, a[0] * ny - a[1] * nx, nx, ny, nz)
-        prods[j] = [J[i] * J[k] for i in range(6) for k in range(i, 6)] + [J[i] * r for i in range(6)] + [r * r]
+    loop_tot, prods = R.evaluate_loop(model, T0, c0, depth, INTR, 0.02)   # the loop, shared with tests/test_refine_cases.py
     assert int((prods[:, 27] != 0).sum()) <= n_pairs
-    assert tot.tobytes() == R.chunk_sums_loop(prods).tobytes()
+    assert tot.tobytes() == loop_tot.tobytes()
