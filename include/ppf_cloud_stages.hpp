@@ -22,6 +22,7 @@
  *   (nothing: the reference stops at the ICP pose)  ->  Cloud::refineFrame(modelClouds, poses, depth, ...)  (poses fitted to the depth image)
  *   k4a::transformation::depth_image_to_color_camera (k4a_grabber.h:339, :391) -> DepthMap::registerDepth / registerDepthU16
  *                                                     (a raw sensor depth frame aligned to the colour camera; Cloud::fromDepth takes it)
+ *   (nothing: a sensor pipeline's depth clean-up)     ->  filterDepth / filterDepthU16 / DepthMap::registerFiltered
  *
  * Every stage returns a new Cloud that stays in HBM; only toMat()/download() copy to the host.  A maintainer replaces
  * the bodies of those CloudProcessor methods by these one-liners; pcl::PointCloud<PointXYZ> goes
@@ -531,6 +532,38 @@ class Cloud {
   std::shared_ptr<ppf_cloud> h_;
 };
 
+/* ppf_depth_filter: the depth image without its unsupported ("flying") pixels and smoothed inside each
+ * surface, float32 metres, packed rows x cols, 0 where nothing is written: what Cloud::fromDepth and every frame stage take. */
+inline ppf_depth_filter_params defaultDepthFilterParams() {
+  ppf_depth_filter_params p;
+  ppf_default_depth_filter_params(&p);
+  return p;
+}
+inline std::vector<float> filterDepthImage(const void* depth, int format, double scale, int rows, int cols, const ppf_depth_filter_params* params,
+                                           float zMin, float zMax, size_t rowPitchBytes, ppf_depth_filter_stats* stats) {
+  ppf_depth_params dp;
+  ppf_default_depth_params(&dp);
+  dp.format = format;
+  dp.depth_scale = scale;
+  dp.z_min = zMin;
+  dp.z_max = zMax;
+  const ppf_depth_filter_params fp = params ? *params : defaultDepthFilterParams();
+  std::vector<float> out((rows > 0 && cols > 0 ? (size_t)rows * (size_t)cols : 0) + 1);
+  ppf_match_3d::check(ppf_depth_filter(depth, rows, cols, rowPitchBytes, &dp, &fp, &out[0], stats));
+  out.resize(out.size() - 1);
+  return out;
+}
+/* float32 metres in; rowPitchBytes 0: packed rows; params 0: the defaults */
+inline std::vector<float> filterDepth(const float* depth, int rows, int cols, const ppf_depth_filter_params* params = 0, float zMin = 0.f,
+                                      float zMax = 0.f, size_t rowPitchBytes = 0, ppf_depth_filter_stats* stats = 0) {
+  return filterDepthImage(depth, PPF_DEPTH_F32, 0.001, rows, cols, params, zMin, zMax, rowPitchBytes, stats);
+}
+/* a 16-bit sensor image: z = d * scale metres (0.001 for millimetres) */
+inline std::vector<float> filterDepthU16(const uint16_t* depth, int rows, int cols, double scale, const ppf_depth_filter_params* params = 0,
+                                         float zMin = 0.f, float zMax = 0.f, size_t rowPitchBytes = 0, ppf_depth_filter_stats* stats = 0) {
+  return filterDepthImage(depth, PPF_DEPTH_U16, scale, rows, cols, params, zMin, zMax, rowPitchBytes, stats);
+}
+
 /* A resident registration map (ppf_depth_map), built once per calibration as k4a::transformation is: registerDepth draws a
  * raw depth frame of the depth camera into the pixel grid of the colour camera (float32 metres, 0 where nothing was drawn),
  * which is what Cloud::fromDepth and every frame stage take with fx(), fy(), ppx(), ppy().  R9 (row-major) and t3 (metres)
@@ -567,6 +600,10 @@ class DepthMap {
   std::vector<float> registerDepthU16(const uint16_t* depth, double scale, float zMin = 0.f, float zMax = 0.f, size_t rowPitchBytes = 0,
                                       const ppf_register_params* params = 0, ppf_register_stats* stats = 0) const {
     return run(depth, PPF_DEPTH_U16, scale, zMin, zMax, rowPitchBytes, params, stats);
+  }
+  /* registerDepth, then filterDepth on the aligned image */
+  std::vector<float> registerFiltered(const float* depth, const ppf_depth_filter_params* filter = 0, float zMin = 0.f, float zMax = 0.f) const {
+    return filterDepth(&registerDepth(depth, zMin, zMax)[0], rows_, cols_, filter, zMin, zMax);
   }
   /* a detector's boxes {x, y, w, h} on the raw colour image (camera `raw`, with its distortion) in this map's colour camera */
   std::vector<int> mapBoxes(const ppf_camera& raw, const int* boxesXYWH, int n) const {

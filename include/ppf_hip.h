@@ -54,6 +54,8 @@
  *   ppf_depth_register (+_device)   grabber makes per capture (k4a_grabber.h:339-340, :391-392): a raw sensor depth image
  *                                   drawn into the colour camera's pixel grid, lens distortion of both cameras included
  *   ppf_camera_map_boxes            a detector's boxes on the raw colour image carried into that pixel grid
+ *   ppf_depth_filter (+_device)     the depth clean-up a sensor pipeline runs before anything else (the reference has none):
+ *                                   unsupported "flying" pixels removed, the others smoothed without crossing a depth step
  *
  * Conventions
  *   - A cloud argument is (pointer, rows, stride, normal_offset): float32 rows whose first three floats
@@ -638,6 +640,53 @@ ppf_status ppf_cloud_from_depth_normals(const void* depth, int rows, int cols, s
 ppf_status ppf_cloud_from_depth_normals_device(const void* d_depth, int rows, int cols, size_t row_pitch_bytes, const double* intr,
                                                const ppf_depth_params* p, const ppf_depth_normal_params* np, void* stream,
                                                ppf_cloud** out);
+
+/* ---- edge-preserving smoothing of the depth image itself, in front of the calls above --------------- */
+#define PPF_DEPTH_FILTER_MAX_RADIUS 8
+typedef struct ppf_depth_filter_params {
+  int32_t radius;       /* 0..8: the window is (2r+1)^2; 0: the support test only; default 3 */
+  float range_abs;      /* finite, > 0, metres; default 0.01 */
+  float range_quad;     /* finite, >= 0, 1/metres: the range grows by range_quad * z^2; default 0 */
+  float support_abs;    /* finite, >= 0; default 0.01 */
+  float support_quad;   /* finite, >= 0; default 0 */
+  int32_t min_support;  /* 0..8; 0: every kept pixel is supported; default 6 */
+  int32_t flags;        /* none defined: 0 */
+  int32_t reserved[4];
+} ppf_depth_filter_params;
+typedef struct ppf_depth_filter_stats {
+  int32_t n_kept, n_unsupported, n_written; /* n_kept = n_unsupported + n_written */
+  int32_t n_launches;   /* kernel launches of the call: 1 */
+  int32_t n_host_syncs; /* blocking waits of the call: 1 */
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_depth_filter_stats;
+/* radius 3, range_abs 0.01, range_quad 0, support_abs 0.01, support_quad 0, min_support 6, flags 0 */
+void ppf_default_depth_filter_params(ppf_depth_filter_params* p);
+/* Removes the unsupported ("flying") pixels of a depth image and smooths the others without crossing a depth step.  Every
+ * operation is fp64 as written, nothing fused; z(p) and "kept" are ppf_cloud_from_depth's, Z = (double)z.
+ *  1. Support.  S(p) = (double)support_abs + (double)support_quad * (Zp * Zp).  Of the 8 neighbours q of a kept p, one outside
+ *     the image supports p (the border is no depth edge) and one inside supports p iff it is kept and
+ *     fabs(Zq - Zp) <= S(p).  p is supported iff it is kept and (min_support == 0 or the count is >= min_support).  A kept
+ *     pixel that is not supported counts in n_unsupported, is written as 0 and takes no part in step 2 for any pixel.
+ *  2. Smoothing of a supported p.  R = (double)range_abs + (double)range_quad * (Zp * Zp), D = (double)((radius + 1) *
+ *     (radius + 1)), num = den = 0.  For dv = -r..r ascending and du = -r..r ascending inside each row, q = (u + du, v + dv):
+ *     skip q unless it is inside the image and supported; s = 1.0 - (double)(du*du + dv*dv) / D, skip unless s > 0;
+ *     t = (Zq - Zp) / R, k = 1.0 - t * t, skip unless k > 0; w = (s * s) * (k * k); num = num + w * Zq; den = den + w.
+ *     out(p) = (float)(num / den).  The centre weighs 1, so den >= 1; with radius 0 the result is z(p) exactly.
+ * Both weights are Tukey biweights: a neighbour at or beyond R in depth weighs exactly 0, so a depth step stays byte for
+ * byte.  out: float32 metres, packed rows x cols, 0.0f at every pixel that is not written: what ppf_cloud_from_depth*,
+ * ppf_depth_register and the frame stages take as PPF_DEPTH_F32.  depth, rows, cols, row_pitch_bytes and dp (format,
+ * depth_scale, z_min, z_max) are ppf_cloud_from_depth's with their errors; dp->flags is ignored.  fp NULL, a field outside
+ * the range stated beside it, a non-zero flag or out NULL are PPF_ERR_INVALID before any device work too; without a device
+ * the call is PPF_ERR_HIP.  One launch and one blocking wait whatever the image holds.  On any error *stats is zero and
+ * out is not touched.  stats may be NULL. */
+ppf_status ppf_depth_filter(const void* depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
+                            const ppf_depth_filter_params* fp, float* out, ppf_depth_filter_stats* stats /* may be NULL */);
+/* the same between DEVICE buffers, as ppf_depth_register_device: enqueued on `stream` (a hipStream_t, NULL: default stream),
+ * returns when the image is complete.  A pointer the current device cannot read, a buffer that runs past the end of its
+ * allocation, or d_out overlapping the depth image is PPF_ERR_INVALID before anything is launched. */
+ppf_status ppf_depth_filter_device(const void* d_depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
+                                   const ppf_depth_filter_params* fp, float* d_out, void* stream, ppf_depth_filter_stats* stats);
 
 /* ---- every detection of a frame in one segmented device pass ------------------------------------------------ */
 typedef struct ppf_frame_params {

@@ -126,6 +126,19 @@ PPF_DEPTH_NORMALS_DROP = 1  # DepthNormalParams.flags bit
 PPF_DEPTH_NORMALS_MAX_RADIUS = 8
 
 
+class DepthFilterParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("range_abs", C.c_float), ("range_quad", C.c_float), ("support_abs", C.c_float),
+                ("support_quad", C.c_float), ("min_support", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class DepthFilterStats(C.Structure):
+    _fields_ = [("n_kept", C.c_int32), ("n_unsupported", C.c_int32), ("n_written", C.c_int32), ("n_launches", C.c_int32),
+                ("n_host_syncs", C.c_int32), ("ms_wall", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+PPF_DEPTH_FILTER_MAX_RADIUS = 8
+
+
 class VerifyParams(C.Structure):
     _fields_ = [("inlier_dist", C.c_float), ("normal_cos", C.c_float), ("depth_tol", C.c_float), ("model_step", C.c_int32),
                 ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
@@ -365,6 +378,11 @@ _SIGNATURES = {
     "ppf_cloud_from_depth_normals_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_double),
                                                       C.POINTER(DepthParams), C.POINTER(DepthNormalParams), C.c_void_p,
                                                       C.POINTER(C.c_void_p)]),
+    "ppf_default_depth_filter_params": (None, [C.POINTER(DepthFilterParams)]),
+    "ppf_depth_filter": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(DepthParams), C.POINTER(DepthFilterParams),
+                                   C.c_void_p, C.POINTER(DepthFilterStats)]),
+    "ppf_depth_filter_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(DepthParams),
+                                          C.POINTER(DepthFilterParams), C.c_void_p, C.c_void_p, C.POINTER(DepthFilterStats)]),
     "ppf_default_verify_params": (None, [C.POINTER(VerifyParams)]),
     "ppf_verify_frame": (C.c_int, [C.POINTER(FrameDetection), C.c_int, C.POINTER(Pose), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int,
                                    C.c_int, C.POINTER(C.c_double), C.POINTER(VerifyParams), C.POINTER(PoseScore), C.POINTER(C.c_int),

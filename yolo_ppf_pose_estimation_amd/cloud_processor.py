@@ -43,7 +43,7 @@ class DeviceCloud:
 
     @classmethod
     def from_depth(cls, depth, intr, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0,
-                   fp64: bool = False, normals: Optional[dict] = None) -> "DeviceCloud":
+                   fp64: bool = False, normals: Optional[dict] = None, filter: Optional[dict] = None) -> "DeviceCloud":
         """The organised scene cloud of a depth image, back-projected on the device (ppf_cloud_from_depth): rows
         ``x y z 0 0 0`` of every pixel with a finite z > 0 inside [z_min, z_max] (z_max 0: no upper bound), in row-major
         pixel order.  depth: a 2-D numpy float32 (metres) or uint16 (units of depth_scale metres) array, rows read at its
@@ -52,7 +52,12 @@ class DeviceCloud:
         Camera::back_projection's rounding (DESIGN.md §13).  normals: None, or a dict with any of radius,
         max_depth_change, min_neighbours, drop (ppf_cloud_from_depth_normals): the same rows with the normal
         and curvature of a plane fit over each pixel's (2 radius + 1)^2 image window; a pixel with fewer than
-        min_neighbours neighbours gets NaNs, or with drop=True no row."""
+        min_neighbours neighbours gets NaNs, or with drop=True no row.  filter: None, or a dict of ppf_depth_filter_params
+        fields ({}: the defaults): the image goes through ``filter_depth`` first -- on the device and the
+        current stream for a GPU tensor -- and the cloud is built from the filtered float32 image with the same z_min and
+        z_max."""
+        if filter is not None:
+            depth = filter_depth(depth, depth_scale=depth_scale, z_min=z_min, z_max=z_max, params=filter)
         K = np.asarray(intr, dtype=np.float64)
         it = (C.c_double * 4)(*([K[0, 0], K[1, 1], K[0, 2], K[1, 2]] if K.shape == (3, 3) else [float(v) for v in K.reshape(-1)[:4]]))
         prm = _capi.DepthParams()
@@ -684,6 +689,65 @@ class DepthMap:
         return (img, _capi.stats_dict(st)) if return_stats else img
 
 
+def _depth_filter_params(params) -> _capi.DepthFilterParams:
+    """``_params`` for ppf_depth_filter_params; a key that is no field of the record (a misspelt name) is an error, not ignored"""
+    if isinstance(params, dict):
+        unknown = sorted(set(params) - {f for f, _ in _capi.DepthFilterParams._fields_})
+        if unknown:
+            raise PPFError(_capi.PPF_ERR_INVALID, f"unknown depth filter parameter(s): {', '.join(unknown)}")
+    return _params(_capi.DepthFilterParams, "ppf_default_depth_filter_params", params)
+
+
+def filter_depth(depth, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0, params=None, out=None,
+                 return_stats: bool = False):
+    """The depth image without its unsupported ("flying") pixels and smoothed inside each surface (ppf_depth_filter,
+    DESIGN.md §23): float32 metres of the same shape, 0 where nothing is written -- what ``DeviceCloud.from_depth``,
+    ``DepthMap.register`` and the frame stages take.  depth: a 2-D numpy float32 (metres) or uint16 (units of depth_scale
+    metres) array, rows read at its stride, which gives a numpy image; or such a torch tensor on the GPU, read in place on
+    ``torch.cuda.current_stream()`` (ppf_depth_filter_device), which gives a float32 tensor on the same device (or fills
+    ``out``, which must not overlap the input).  params: a DepthFilterParams, a dict of its fields or None (the defaults)."""
+    prm = _depth_filter_params(params)
+    dp = _capi.DepthParams()
+    lib().ppf_default_depth_params(C.byref(dp))
+    dp.depth_scale, dp.z_min, dp.z_max = float(depth_scale), float(z_min), float(z_max)
+    st = _capi.DepthFilterStats()
+    if type(depth).__module__.startswith("torch") and depth.is_cuda:
+        import torch
+        fmt = {torch.float32: _capi.PPF_DEPTH_F32, torch.uint16: _capi.PPF_DEPTH_U16}.get(depth.dtype)
+        if fmt is None or depth.dim() != 2:
+            raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 or uint16 tensor")
+        if depth.stride(1) != 1 or depth.stride(0) < depth.shape[1]:
+            depth = depth.contiguous()
+        shape = tuple(depth.shape)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=depth.device)
+        elif not (out.is_cuda and out.device == depth.device and out.dtype == torch.float32 and tuple(out.shape) == shape
+                  and out.is_contiguous()):
+            raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous float32 tensor of shape {shape} on the depth image's device")
+        dp.format = fmt
+        with torch.cuda.device(depth.device):
+            stream = torch.cuda.current_stream(depth.device).cuda_stream
+            check(lib().ppf_depth_filter_device(C.c_void_p(depth.data_ptr()), shape[0], shape[1], depth.stride(0) * depth.element_size(),
+                                                C.byref(dp), C.byref(prm), C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(stream) if stream else None, C.byref(st)))
+        return (out, _capi.stats_dict(st)) if return_stats else out
+    a = np.asarray(depth.numpy() if type(depth).__module__.startswith("torch") else depth)
+    fmt = {np.dtype(np.float32): _capi.PPF_DEPTH_F32, np.dtype(np.uint16): _capi.PPF_DEPTH_U16}.get(a.dtype)
+    if fmt is None or a.ndim != 2:
+        raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 or uint16 array")
+    if a.strides[1] != a.itemsize or a.strides[0] < a.shape[1] * a.itemsize or a.strides[0] % a.itemsize:
+        a = np.ascontiguousarray(a)
+    dp.format = fmt
+    if out is None:
+        out = np.empty(a.shape, np.float32)
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == a.shape and out.flags.c_contiguous
+              and out.flags.writeable):
+        raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous float32 array of shape {a.shape}")
+    check(lib().ppf_depth_filter(C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1], a.strides[0], C.byref(dp), C.byref(prm),
+                                 out.ctypes.data, C.byref(st)))
+    return (out, _capi.stats_dict(st)) if return_stats else out
+
+
 class CloudProcessor:
     """``ppf::CloudProcessor``: holds the scene cloud, the depth image, the detector's boxes, the per-object clouds
     and the PPF detectors; every method is the reference's, in the order its driver calls them
@@ -736,6 +800,7 @@ class CloudProcessor:
         # ProposeBoxes: the info rows of the scene's clusters, and the counters
         self.cluster_info: Optional[np.ndarray] = None
         self.cluster_stats: Dict[str, object] = {}
+        self.depth_filter_stats: Dict[str, object] = {}  # FilterDepth: the ppf_depth_filter counters
 
     # ---- the PCL half -------------------------------------------------------------------------------------
     def Deprojection(self, CameraIntr, fp64: bool = False, normals: Optional[dict] = None) -> DeviceCloud:
@@ -746,6 +811,15 @@ class CloudProcessor:
             raise PPFError(_capi.PPF_ERR_INVALID, "Deprojection needs a depth image")
         self.scene = DeviceCloud.from_depth(self.depth, np.asarray(CameraIntr, dtype=np.float64), fp64=fp64, normals=normals)
         return self.scene
+
+    def FilterDepth(self, params=None) -> np.ndarray:
+        """``self.depth`` without its unsupported pixels and smoothed inside each surface (``filter_depth``), the step in
+        front of Deprojection.  params: the fields of ppf_depth_filter_params (radius, range_abs, range_quad, support_abs,
+        support_quad, min_support).  Sets ``depth_filter_stats``; replaces and returns ``self.depth``."""
+        if self.depth is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "FilterDepth needs a depth image")
+        self.depth, self.depth_filter_stats = filter_depth(self.depth, params=params, return_stats=True)
+        return self.depth
 
     def RemovePlanes(self, **params) -> DeviceCloud:
         """``self.scene`` without its support planes (ppf_prep_planes), the step before SceneCropping / PrepareFrame: a
