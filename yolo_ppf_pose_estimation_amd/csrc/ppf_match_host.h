@@ -253,6 +253,8 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
   va.acc_dump = ws->acc_dump;
   va.bucket_total = m->bucket_total.p;
   va.bucket_mid = m->bucket_mid.p;
+  va.grp_records = m->n_grp_records ? m->grp_records.p : nullptr;
+  va.grp_hdr = m->n_grp_records ? m->grp_hdr.p : nullptr;
   va.key_exact = m->params.key_equality == PPF_KEY_EXACT;
   /* 16-bit cells first, 32-bit cells for the (reference point, tile)s whose cells overflow -- until a call casts more than
    * PPF_ACC32_SWITCH of its votes twice that way: from then on 32-bit cells for everything (what they cost extra is less than

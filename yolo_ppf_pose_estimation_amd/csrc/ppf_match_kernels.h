@@ -62,7 +62,10 @@
  * from one reference point sit on arcs around its normal: most tables have Y values that never occur, so columns that are
  * zero in every row.  k_tables writes a 17-bit column mask next to the rows and k_vote skips the masked columns on scalar
  * branches (a skipped add was an add of 0; the headline case casts 12.3 of 17).  Hits in the entry's own cell (1/64 of them) are voted one by one
- * with the direct arithmetic.  Exactness: the table is only used for pairs separated by a cell boundary
+ * with the direct arithmetic.  Entries of a bucket that share row and X cast their counted adds at the same words: where the
+ * table's counts add up four to a byte (k_tables says so next to the mask) the 16-bit launch casts them from the bucket's
+ * group records, one set of adds per up to four entries (see AGG_GROUP_CELLS), and walks the entries for their own cells only.
+ * Exactness: the table is only used for pairs separated by a cell boundary
  * from which the entry is provably away (fp32 cell index with a guard band, fp64 when inside the band,
  * one-by-one votes when fp64 is still within 1e-7 of a boundary), where the fp64 chain's rounding
  * (1.5e-14 bins) cannot change floor().  alpha_m < -pi (only (float)-pi) could make x - y negative, where
@@ -178,6 +181,7 @@ constexpr int VOTE_MAX_HITS = PPF_AGG_MIN_HITS; /* hits of one run voted per dir
 #ifndef PPF_AGG_CHUNK
 #define PPF_AGG_CHUNK 1024
 #endif
+static_assert(PPF_AGG_CHUNK >= 32 && PPF_AGG_CHUNK % 32 == 0, "chunks of pair records start in different blocks of 32 (MatchArgs::grp_hdr)");
 constexpr int AGG_CHUNK = PPF_AGG_CHUNK; /* pair records per aggregated work item (each item copies its count table into LDS; 512 / 2048: +1 %) */
 constexpr int AGG_NY = 16;            /* integer parts Y + 8 of a hit */
 constexpr int AGG_SUB = 191;          /* hits per count table (counts are bytes; 3 hits per lane) */
@@ -230,6 +234,15 @@ constexpr int AGG_SCRATCH = ((AGG_Q + 1) * AGG_ROW + 15) / 16 * 16; /* per-wave 
  * k_vote casts the counted atomics of the set columns only (see agg_pair) */
 constexpr int AGG_OFF_COLS = (AGG_Q + 1) * AGG_ROW;
 constexpr uint32_t AGG_COLS_ALL = (2u << AGG_NY) - 1u; /* all 17 columns */
+/* Group records (build_row_groups): the entries of a (tile, bucket) that share accumulator row and count-table shift X cast
+ * their counted adds at the same words, so a lane adds up the table rows of up to AGG_GROUP_CELLS of them as packed bytes and
+ * casts one set of adds.  A table whose largest count is at most AGG_NARROW_MAX (bit AGG_COLS_NARROW of its mask word) can be
+ * summed that way without a carry between bytes; any other table votes entry by entry (agg_pair<true>). */
+constexpr int AGG_GROUP_CELLS = 4;
+constexpr uint32_t AGG_NARROW_MAX = 255u / AGG_GROUP_CELLS;
+constexpr uint32_t AGG_COLS_NARROW = 1u << 31;
+constexpr uint32_t AGG_CELLS_FREE = (uint32_t)AGG_Q * 0x01010101u; /* four free slots: the all-zero row */
+constexpr uint32_t AGG_GROUP_X = 8u; /* X of a padding group record: its (all-zero) adds fall on its own word and the 16 behind it */
 static_assert(AGG_OFF_COLS % 4 == 0 && AGG_OFF_COLS + 4 <= AGG_SCRATCH, "the column mask lives in the padding behind the rows");
 constexpr int TBL_OFF_A32 = AGG_SCRATCH;
 constexpr int TBL_A32_BYTES = (AGG_NY * AGG_Q > 768 ? AGG_NY * AGG_Q : 768);
@@ -367,6 +380,8 @@ struct MatchArgs {
   int n_rounds, round_buckets; /* k_group sorts round_buckets bucket ids per pass over the reference point's hits */
   const uint32_t* bucket_total; /* [n_buckets] entries of a bucket over all tiles */
   const uint32_t* bucket_mid;   /* [n_tiles][n_buckets] entries of low-half rows = the first dealing positions of the bucket (k_bucket_mid) */
+  const uint4* grp_records;     /* group records {row_a, row_b, cells_a, cells_b}: the (row, X)-sorted view of the (tile, bucket)s that can vote through count tables (build_row_groups); NULL: none */
+  const uint2* grp_hdr;         /* [records / 32] {first group record, group records} of the chunk of pair records that starts in this block of 32 */
   unsigned long long* work;     /* [n_ref] votes the reference point will cast (sum of its hits' bucket sizes) */
   uint32_t* perm;               /* [n_ref] reference points ordered by work, heaviest first (k_rank) */
   const uint32_t* perm_group;   /* [n_ref] reference points ordered by hit count, for k_group */
@@ -1177,14 +1192,16 @@ __device__ __forceinline__ void table_build(const uint32_t ws, const float S, co
     more[t] = tot - less[t] - c[t];
   }
   const int yy = lane >> 2;
+  uint32_t colw;
   { /* the column mask: Y values that occur (one ballot bit per lane quad, squeezed to one bit per Y), each feeding columns Y and Y + 1 */
     unsigned long long o = __ballot(tot != 0u) & 0x1111111111111111ull;
     o = (o | (o >> 3)) & 0x0303030303030303ull;
     o = (o | (o >> 6)) & 0x000F000F000F000Full;
     o = (o | (o >> 12)) & 0x000000FF000000FFull;
     o = (o | (o >> 24)) & 0xFFFFull;
-    if (lane == 0) lds_st(ws + AGG_OFF_COLS, ((uint32_t)o | ((uint32_t)o << 1)) & AGG_COLS_ALL);
+    colw = ((uint32_t)o | ((uint32_t)o << 1)) & AGG_COLS_ALL;
   }
+  uint32_t cmax = 0; /* the largest count of the table */
 #pragma unroll
   for (int t = 0; t < PER; t++) {
     const uint32_t mprev = __shfl_up(more[t], 4);
@@ -1192,7 +1209,12 @@ __device__ __forceinline__ void table_build(const uint32_t ws, const float S, co
     const uint32_t p = (uint32_t)(quarter * PER + t);
     lds_st8(ws + p * AGG_ROW + yy, v);
     if (yy == AGG_NY - 1) lds_st8(ws + p * AGG_ROW + AGG_NY, more[t]);
+    cmax = max(cmax, yy == AGG_NY - 1 ? max(v, more[t]) : v);
   }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cmax = max(cmax, (uint32_t)__shfl_xor((int)cmax, o));
+  /* behind the column mask, in the same word: whether the counts of AGG_GROUP_CELLS rows add up inside a byte (k_vote's merged counted adds) */
+  if (lane == 0) lds_st(ws + AGG_OFF_COLS, colw | (cmax <= AGG_NARROW_MAX ? AGG_COLS_NARROW : 0u));
   wave_lds_fence();
   /* cell ends: inclusive scan of the per-p counts (one cell per lane); the scatter below counts them down to the cell starts */
   uint32_t h = lane < AGG_Q ? lds_ld(ws + AGG_OFF_CE + lane * 4) : 0u;
@@ -1350,29 +1372,10 @@ __device__ __forceinline__ void agg_own_fetch(const AggConsts& k, const uint4 re
 #endif
 }
 
-/* The two model entries of one pair record against the count table (rows and cell ranges in the wave's LDS, copied from the
- * table `tbl` the item works with): one counted atomic each per set column of the table's mask `cols`, then one vote per hit of each entry's own cell (all hits for an
- * entry that votes one by one) with the direct arithmetic.  The offsets of those hits come straight from the table, four
- * per entry, fetched a block ahead (agg_own_fetch): at 64 cells an entry's cell holds three hits on average, so the LDS
- * sees no reads for them and most blocks need no second fetch.  `votes` counts the one-by-one votes. */
-__device__ __forceinline__ void agg_pair(const AggConsts& k, const uint4 rec, const AggOwn& own, const unsigned char* __restrict__ tbl,
-                                         const double* __restrict__ g_a64, const uint32_t cols, uint32_t& votes) {
-  const float am_a = __uint_as_float(rec.z), am_b = __uint_as_float(rec.w);
-  /* X and cell of the two entries: evaluated by the table build (agg_cell_bits), carried in the row codes */
-  const int Xa = (int)((rec.x >> ROW_X_SHIFT) & 31u), qa = (int)((rec.x >> ROW_Q_SHIFT) & ROW_Q_MASK);
-  const int Xb = (int)((rec.y >> ROW_X_SHIFT) & 31u), qb = (int)((rec.y >> ROW_Q_SHIFT) & ROW_Q_MASK);
-  const uint32_t ta = k.ws + (uint32_t)qa * AGG_ROW, tb = k.ws + (uint32_t)qb * AGG_ROW;
-  const uint2 a01 = lds_ld2(ta), a23 = lds_ld2(ta + 8);
-  const uint2 b01 = lds_ld2(tb), b23 = lds_ld2(tb + 8);
-  const uint32_t a4 = own.wa, b4 = own.wb; /* read a block ahead, with the cell's range in bytes 1 and 2 */
-  const uint2 ca = make_uint2(__builtin_amdgcn_ubfe(a4, 8u, 8u), __builtin_amdgcn_ubfe(a4, 16u, 8u));
-  const uint2 cb = make_uint2(__builtin_amdgcn_ubfe(b4, 8u, 8u), __builtin_amdgcn_ubfe(b4, 16u, 8u));
-  const uint32_t pa = k.acc_base + (rec.x & ROW_OFFSET_MASK), pb = k.acc_base + (rec.y & ROW_OFFSET_MASK);
-  const bool ha = (rec.x & 1u) != 0, hb = (rec.y & 1u) != 0;
-  const uint32_t inc_a = vote_inc(k.vi, rec.x), inc_b = vote_inc(k.vi, rec.y);
-  uint32_t va = pa + (uint32_t)((Xa - 8) * 4), vb = pb + (uint32_t)((Xb - 8) * 4); /* bin X + 8 - j lives at v + (16 - j)*4 */
-  asm volatile("" : "+v"(va), "+v"(vb)); /* keep these as the bases: every atomic below is base + immediate offset */
-  const uint32_t wa[5] = {a01.x, a01.y, a23.x, a23.y, a4}, wb[5] = {b01.x, b01.y, b23.x, b23.y, b4};
+/* the counted adds of two lanes' worth of summed table words: one (v_perm_b32, ds_add_u32) per set column of the mask `cols`,
+ * every add base + immediate offset (bin X + 8 - j lives at v + (16 - j)*4) */
+__device__ __forceinline__ void agg_cast(const AggConsts& k, const uint32_t va, const uint32_t vb, const bool ha, const bool hb,
+                                         const uint32_t (&wa)[5], const uint32_t (&wb)[5], const uint32_t cols) {
   uint32_t sa[4], sb[4]; /* one v_perm_b32 per count: byte jj of the table word -> the half this entry's row owns */
   {
     const uint32_t sa0 = ha ? k.sel_hi : k.sel_lo, sta = ha ? k.step_hi : k.step_lo;
@@ -1380,9 +1383,9 @@ __device__ __forceinline__ void agg_pair(const AggConsts& k, const uint4 rec, co
 #pragma unroll
     for (int jj = 0; jj < 4; jj++) { sa[jj] = sa0 + (uint32_t)jj * sta; sb[jj] = sb0 + (uint32_t)jj * stb; }
   }
-#if PPF_ABL_COUNTED
 #if PPF_MOCK_PAIRBINS == 3 /* nine 64-bit atomics (two adjacent words each), one v_perm per count as now: timing of the ds_add_u64 form */
   {
+    (void)cols;
     const uint32_t va8 = va & ~7u, vb8 = vb & ~7u;
 #pragma unroll
     for (int j = 0; j <= AGG_NY; j += 2) {
@@ -1395,6 +1398,7 @@ __device__ __forceinline__ void agg_pair(const AggConsts& k, const uint4 rec, co
     }
   }
 #elif PPF_MOCK_PAIRBINS
+  (void)cols;
 #pragma unroll
   for (int j = 0; j <= AGG_NY; j += 2) { /* 9 atomics, one two-source v_perm each */
     lds_add(va + (uint32_t)((AGG_NY - j) * 2), __builtin_amdgcn_perm(wa[(j + 1 > AGG_NY ? j : j + 1) >> 2], wa[j >> 2], sa[(j >> 1) & 3]));
@@ -1423,8 +1427,76 @@ __device__ __forceinline__ void agg_pair(const AggConsts& k, const uint4 rec, co
     }
   }
 #endif
+}
+
+/* one table row added to a lane's packed sums: 17 byte counts in five words (count 16 is byte 0 of the last word, the cell's
+ * range sits behind it) */
+__device__ __forceinline__ void agg_row_add(const uint32_t t, uint32_t (&w)[5]) {
+  const uint2 r01 = lds_ld2(t), r23 = lds_ld2(t + 8);
+  const uint32_t r4 = lds_ld(t + 16);
+  w[0] += r01.x; w[1] += r01.y; w[2] += r23.x; w[3] += r23.y; w[4] += r4 & 0xFFu;
+}
+
+/* The counted adds of two group records {row_a, row_b, cells_a, cells_b} against a narrow count table: the rows of the up
+ * to AGG_GROUP_CELLS cells of each are summed as packed bytes (a free slot names the all-zero row, as a guard-band entry's
+ * does), then one set of adds is cast.  Records are ordered by used slots, so the reads of slots 2 and 3 are skipped for the
+ * whole wave where no lane uses them. */
+__device__ __forceinline__ void agg_group_pair(const AggConsts& k, const uint4 g, const uint32_t cols) {
+  static_assert(AGG_GROUP_CELLS == 4, "a group record holds four cell bytes");
+  const int Xa = (int)((g.x >> ROW_X_SHIFT) & 31u), Xb = (int)((g.y >> ROW_X_SHIFT) & 31u);
+  const uint32_t pa = k.acc_base + (g.x & ROW_OFFSET_MASK), pb = k.acc_base + (g.y & ROW_OFFSET_MASK);
+  const bool ha = (g.x & 1u) != 0, hb = (g.y & 1u) != 0;
+  uint32_t va = pa + (uint32_t)((Xa - 8) * 4), vb = pb + (uint32_t)((Xb - 8) * 4);
+  asm volatile("" : "+v"(va), "+v"(vb)); /* the bases of the adds */
+  uint32_t wa[5] = {0u, 0u, 0u, 0u, 0u}, wb[5] = {0u, 0u, 0u, 0u, 0u};
+  agg_row_add(k.ws + (g.z & 0xFFu) * AGG_ROW, wa);
+  agg_row_add(k.ws + (g.w & 0xFFu) * AGG_ROW, wb);
+  agg_row_add(k.ws + __builtin_amdgcn_ubfe(g.z, 8u, 8u) * AGG_ROW, wa);
+  agg_row_add(k.ws + __builtin_amdgcn_ubfe(g.w, 8u, 8u) * AGG_ROW, wb);
+  if (__any(((g.z >> 16) != (AGG_CELLS_FREE >> 16)) | ((g.w >> 16) != (AGG_CELLS_FREE >> 16)))) { /* some lane uses slot 2 or 3 of one of its records */
+    agg_row_add(k.ws + __builtin_amdgcn_ubfe(g.z, 16u, 8u) * AGG_ROW, wa);
+    agg_row_add(k.ws + __builtin_amdgcn_ubfe(g.w, 16u, 8u) * AGG_ROW, wb);
+    if (__any(((g.z >> 24) != (AGG_CELLS_FREE >> 24)) | ((g.w >> 24) != (AGG_CELLS_FREE >> 24)))) {
+      agg_row_add(k.ws + (g.z >> 24) * AGG_ROW, wa);
+      agg_row_add(k.ws + (g.w >> 24) * AGG_ROW, wb);
+    }
+  }
+  agg_cast(k, va, vb, ha, hb, wa, wb, cols);
+}
+
+/* The two model entries of one pair record against the count table (rows and cell ranges in the wave's LDS, copied from the
+ * table `tbl` the item works with): one counted atomic each per set column of the table's mask `cols`, then one vote per hit of each entry's own cell (all hits for an
+ * entry that votes one by one) with the direct arithmetic.  The offsets of those hits come straight from the table, four
+ * per entry, fetched a block ahead (agg_own_fetch): at 64 cells an entry's cell holds three hits on average, so the LDS
+ * sees no reads for them and most blocks need no second fetch.  `votes` counts the one-by-one votes.
+ * COUNTED = false: the own-cell votes only (the counted adds of these entries are cast from their group records); `live` = false: a lane past the end of the item, which then casts nothing */
+template <bool COUNTED>
+__device__ __forceinline__ void agg_pair(const AggConsts& k, const uint4 rec, const AggOwn& own, const unsigned char* __restrict__ tbl,
+                                         const double* __restrict__ g_a64, const uint32_t cols, uint32_t& votes, const bool live = true) {
+  const float am_a = __uint_as_float(rec.z), am_b = __uint_as_float(rec.w);
+  const uint32_t a4 = own.wa, b4 = own.wb; /* read a block ahead, with the cell's range in bytes 1 and 2 */
+  const uint2 ca = make_uint2(__builtin_amdgcn_ubfe(a4, 8u, 8u), __builtin_amdgcn_ubfe(a4, 16u, 8u));
+  const uint2 cb = make_uint2(__builtin_amdgcn_ubfe(b4, 8u, 8u), __builtin_amdgcn_ubfe(b4, 16u, 8u));
+  const uint32_t pa = k.acc_base + (rec.x & ROW_OFFSET_MASK), pb = k.acc_base + (rec.y & ROW_OFFSET_MASK);
+  const uint32_t inc_a = vote_inc(k.vi, rec.x), inc_b = vote_inc(k.vi, rec.y);
+#if !PPF_ABL_COUNTED
+  (void)cols;
+#else
+  if constexpr (COUNTED) {
+    /* X and cell of the two entries: evaluated by the table build (agg_cell_bits), carried in the row codes */
+    const int Xa = (int)((rec.x >> ROW_X_SHIFT) & 31u), qa = (int)((rec.x >> ROW_Q_SHIFT) & ROW_Q_MASK);
+    const int Xb = (int)((rec.y >> ROW_X_SHIFT) & 31u), qb = (int)((rec.y >> ROW_Q_SHIFT) & ROW_Q_MASK);
+    const uint32_t ta = k.ws + (uint32_t)qa * AGG_ROW, tb = k.ws + (uint32_t)qb * AGG_ROW;
+    const uint2 a01 = lds_ld2(ta), a23 = lds_ld2(ta + 8);
+    const uint2 b01 = lds_ld2(tb), b23 = lds_ld2(tb + 8);
+    const bool ha = (rec.x & 1u) != 0, hb = (rec.y & 1u) != 0;
+    uint32_t va = pa + (uint32_t)((Xa - 8) * 4), vb = pb + (uint32_t)((Xb - 8) * 4); /* bin X + 8 - j lives at v + (16 - j)*4 */
+    asm volatile("" : "+v"(va), "+v"(vb)); /* keep these as the bases: every atomic below is base + immediate offset */
+    const uint32_t wa[5] = {a01.x, a01.y, a23.x, a23.y, a4}, wb[5] = {b01.x, b01.y, b23.x, b23.y, b4};
+    agg_cast(k, va, vb, ha, hb, wa, wb, cols);
+  }
 #endif
-  const uint32_t na = ca.y - ca.x, nb = cb.y - cb.x;
+  const uint32_t na = live ? ca.y - ca.x : 0u, nb = live ? cb.y - cb.x : 0u;
   votes += na + nb;
 #if PPF_ABL_OWNCELL
   if (__any((na > 0u) | (nb > 0u))) {
@@ -1720,10 +1792,22 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
         if (tid == 0) { local0 = item_first; items -= item_first; } /* item_first < the run's items: a segment that ends with a run moves on to the next */
       }
       uint32_t incl = items;
+      if constexpr (ACC32) { /* the 32-bit launches have no merged pass: their scan, and with it their code, stays what it was */
 #pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(incl, o);
-        if (lane >= o) incl += y;
+        for (int o = 1; o < 64; o <<= 1) {
+          const uint32_t y = __shfl_up(incl, o);
+          if (lane >= o) incl += y;
+        }
+      } else {
+        /* the scan's source lanes are worked out here, from a copy of the lane id made per segment: as values of the whole
+         * kernel (__shfl_up's own) they took six registers through every item loop, which the count-table items need */
+        int lane_s = lane;
+        asm volatile("" : "+v"(lane_s));
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((lane_s - o) << 2, (int)incl);
+          if (lane_s >= o) incl += y;
+        }
       }
       if (lane == 63) red[wave] = incl;
 #if PPF_TWO_QUEUES
@@ -1826,10 +1910,14 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
       vote_item_settle(cur);
       while (have) {
         uint4 tbl0 = make_uint4(0u, 0u, 0u, 0u), tbl1 = tbl0;
+        uint2 grp = make_uint2(0u, 0u);
         if (cur.agg) {
           const uint4* __restrict__ t = reinterpret_cast<const uint4*>(cur.tbl);
           tbl0 = rec_at(t, (uint32_t)min(lane, AGG_SCRATCH / 16 - 1));
           tbl1 = rec_at(t, (uint32_t)min(lane + 64, AGG_SCRATCH / 16 - 1));
+          /* with them the chunk's slice of its bucket's group records, {first, number}: chunks of at least 32 records start in
+           * different blocks of 32 records, a smaller one (a bucket's last) has no slice */
+          if (!ACC32 && cur.c >= 32u && a.grp_hdr) grp = a.grp_hdr[(uint32_t)(cur.src - records) >> 5];
         }
         const bool have_next = claim(item, q_item);
         if (have_next) vote_locate(nxt, item, seg, lane, a, records);
@@ -1842,10 +1930,14 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
         /* a count-table item: its table's rows and cell ranges (two 16-byte pieces per lane) set out first, ahead of the next
          * item's prefetch, so that the wait for them is not also a wait for that */
         uint4 tbl0 = make_uint4(0u, 0u, 0u, 0u), tbl1 = tbl0;
+        uint2 grp = make_uint2(0u, 0u);
         if (cur.agg) {
           const uint4* __restrict__ t = reinterpret_cast<const uint4*>(cur.tbl);
           tbl0 = rec_at(t, (uint32_t)min(lane, AGG_SCRATCH / 16 - 1));
           tbl1 = rec_at(t, (uint32_t)min(lane + 64, AGG_SCRATCH / 16 - 1));
+          /* with them the chunk's slice of its bucket's group records, {first, number}: chunks of at least 32 records start in
+           * different blocks of 32 records, a smaller one (a bucket's last) has no slice */
+          if (!ACC32 && cur.c >= 32u && a.grp_hdr) grp = a.grp_hdr[(uint32_t)(cur.src - records) >> 5];
         }
         item = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lane == 0 ? atomicAdd(&red[48], 1u) : 0u));
         const bool have_next = item < n_items;
@@ -1877,7 +1969,50 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
           /* the table's column mask, out of the lane that copied its word: a scalar for the whole item */
           constexpr int cols_piece = AGG_OFF_COLS / 16, cols_word = (AGG_OFF_COLS % 16) / 4;
           const uint4 cols_q = cols_piece < 64 ? tbl0 : tbl1;
-          const uint32_t cols = (uint32_t)__builtin_amdgcn_readlane((int)(cols_word == 0 ? cols_q.x : cols_word == 1 ? cols_q.y : cols_word == 2 ? cols_q.z : cols_q.w), cols_piece & 63) & AGG_COLS_ALL;
+          const uint32_t cols_w = (uint32_t)__builtin_amdgcn_readlane((int)(cols_word == 0 ? cols_q.x : cols_word == 1 ? cols_q.y : cols_word == 2 ? cols_q.z : cols_q.w), cols_piece & 63);
+          const uint32_t cols = cols_w & AGG_COLS_ALL;
+          /* A narrow table (its counts add up four to a byte) of a model with group records: the counted adds are cast from this
+           * chunk's slice of the bucket's group records, merged per (row, X), the own-cell votes from the chunk's entries.  Summed
+           * over the chunks of the bucket that is every entry's counted adds once: any partition of the group records will do. */
+          const bool merged = !ACC32 && a.grp_hdr != nullptr && (cols_w & AGG_COLS_NARROW) != 0u;
+          if (merged) {
+            const uint32_t gn = (uint32_t)__builtin_amdgcn_readfirstlane((int)grp.y);
+            if (PPF_ABL_COUNTED && gn) {
+              const uint4* __restrict__ gsrc = a.grp_records + (uint32_t)__builtin_amdgcn_readfirstlane((int)grp.x);
+              /* lanes past the slice: a padding record on the lane's guard word, every slot free */
+              uint32_t g_code = tail_bytes | (AGG_GROUP_X << ROW_X_SHIFT), g_free = AGG_CELLS_FREE;
+              asm volatile("" : "+v"(g_code), "+v"(g_free)); /* made here, per item: as loop constants they are kept in registers through the whole unit */
+              uint4 g_cur = rec_at(gsrc, min((uint32_t)lane, gn - 1));
+              for (uint32_t e0 = 0; e0 < gn; e0 += 64) {
+                const uint32_t e = e0 + (uint32_t)lane;
+                const uint4 g_n1 = rec_at(gsrc, min(e + 64, gn - 1));
+                uint4 g = g_cur;
+                if (e >= gn) g = make_uint4(g_code, g_code, g_free, g_free);
+                agg_group_pair(ak, g, cols);
+                g_cur = g_n1;
+              }
+            }
+            AggOwn own_cur;
+            agg_own_fetch(ak, rec_cur, tbl, cur.nh, own_cur);
+            uint4 rec_n1 = rec_at(src, min((uint32_t)lane + 64u, c - 1));
+            for (uint32_t e0 = 0; e0 < c; e0 += 64) {
+              const uint32_t e = e0 + (uint32_t)lane;
+              const uint4 rec_n2 = rec_at(src, min(e + 128, c - 1));
+              AggOwn own_n1;
+              agg_own_fetch(ak, rec_n1, tbl, cur.nh, own_n1);
+              agg_pair<false>(ak, rec_cur, own_cur, tbl, g_a64, cols, agg_votes, e < c);
+              rec_cur = rec_n1;
+              rec_n1 = rec_n2;
+              own_cur = own_n1;
+            }
+            ops += 2u * (uint32_t)__builtin_popcount(cols) * 64u * ((gn + 63u) / 64u);
+#ifdef PPF_DIAG_COLUMNS
+            diag_dense += 2u * (AGG_NY + 1) * 64u * ((gn + 63u) / 64u);
+            diag_cols += 2u * (uint32_t)__builtin_popcount(cols) * 64u * ((gn + 63u) / 64u);
+            if (cols == AGG_COLS_ALL) diag_full += 2u * (AGG_NY + 1) * 64u * ((gn + 63u) / 64u);
+#endif
+            issued += 2ull * c * (uint32_t)cur.nh; /* the lanes past the end cast nothing here; the bucket's padding slots are entries of its group records too */
+          } else {
           /* two blocks of records in flight: block i+2's records and block i+1's own-cell offsets (which need that block's
            * records and the cell ranges in LDS) are loaded under block i's votes, so a block waits for nothing issued in
            * its own iteration */
@@ -1891,7 +2026,7 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
             agg_own_fetch(ak, rec_n1, tbl, cur.nh, own_n1);
             uint4 rec = rec_cur;
             if (e >= c) { rec.x = tail_bytes | (rec.x & ~ROW_CODE_MASK); rec.y = tail_bytes | (rec.y & ~ROW_CODE_MASK); } /* the clamped record's cells go with its alphas */
-            agg_pair(ak, rec, own_cur, tbl, g_a64, cols, agg_votes);
+            agg_pair<true>(ak, rec, own_cur, tbl, g_a64, cols, agg_votes);
             rec_cur = rec_n1;
             rec_n1 = rec_n2;
             own_cur = own_n1;
@@ -1903,6 +2038,7 @@ __global__ __launch_bounds__(VOTE_BLOCK) void k_vote(MatchArgs a) {
           if (cols == AGG_COLS_ALL) diag_full += 2u * (AGG_NY + 1) * 64u * ((c + 63u) / 64u);
 #endif
           issued += 128ull * ((c + 63u) / 64u) * (uint32_t)cur.nh; /* counted + one-by-one votes of an entry = its hits */
+          }
           PPF_PHASE(2);
         } else {
           /* ---- direct item: <= VOTE_MAX_HITS hits x <= VOTE_CHUNK records ---- */

@@ -82,6 +82,131 @@ static ppf_status build_key_lut(ppf_model* m, hipStream_t st) {
   return PPF_OK;
 }
 
+/* Group records: a second, (row, X)-sorted view of every (tile, bucket) that can vote through count tables (at least
+ * PPF_AGG_MIN_RECORDS pair records).  The entries of a bucket that share accumulator row, half and count-table shift X cast
+ * their counted adds at the same words and differ only in the table row T[q] they take the counts from, so k_vote adds up
+ * the rows of up to AGG_GROUP_CELLS of them and casts one set of adds (agg_group_pair).  A group record is
+ * {row code without its cell, cell bytes}: two of them make one 16-byte record {row_a, row_b, cells_a, cells_b}, laid out by
+ * dealing position like the pair records (position j = record 32*(j/64) + j%32, slot (j%64)/32); a group of g entries
+ * becomes ceil(g / AGG_GROUP_CELLS) records, a free slot names the all-zero row AGG_Q.  Every slot of the bucket's pair
+ * records is an entry here, its padding included: the votes cast stay hits x slots.  Order inside a bucket: records with
+ * more used slots first (a wave then reads the same number of rows in every lane), and inside such a class dealt over the
+ * LDS banks like the entries (bank = (row word + X) mod DEAL_BANKS, every bank's records spread evenly over the class).
+ * The records of a bucket are shared out over its chunks of AGG_CHUNK pair records in whole blocks of 32, in proportion to
+ * the chunks' sizes; grp_hdr[first pair record of the chunk / 32] = {first group record, group records}.  Chunks of at least
+ * 32 records start in different blocks of 32, and a smaller one (a bucket's last) gets no slice.
+ * Derived from the pair records alone (like bucket_mid), on the host, once per model: not part of the model file. */
+static ppf_status build_row_groups(ppf_model* m) {
+  const size_t nb = m->info.n_buckets, T = (size_t)m->info.n_tiles, nr = m->n_records;
+  if (m->info.num_angles > AGG_MAX_ANGLES || !nr || !nb) return PPF_OK; /* no count tables */
+  std::vector<uint32_t> boff(T * (nb + 1));
+  std::vector<uint4> rec(nr);
+  HIPCHK(hipMemcpy(boff.data(), m->bucket_off.p, boff.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(rec.data(), m->records.p, nr * sizeof(uint4), hipMemcpyDeviceToHost));
+  struct Slice { uint32_t hdr, first, count; };
+  struct Part { std::vector<uint4> out; std::vector<Slice> slices; bool failed = false; };
+  const unsigned W = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
+  std::vector<Part> parts(W);
+  auto work = [&](unsigned w) {
+    Part& P = parts[w];
+    try {
+      struct G { uint32_t code, cells, used; };
+      std::vector<uint64_t> ent;
+      std::vector<G> grp;
+      std::vector<std::pair<uint32_t, uint32_t>> order; /* {spread key, index} */
+      for (size_t t = 0; t < T; t++)
+        for (size_t b = 0; b < nb; b++) {
+          const uint32_t off = boff[t * (nb + 1) + b], cnt = boff[t * (nb + 1) + b + 1] - off;
+          if (cnt < (uint32_t)PPF_AGG_MIN_RECORDS || (unsigned)(((uint64_t)off * W) / nr) != w) continue;
+          ent.clear();
+          for (uint32_t r = 0; r < cnt; r++) {
+            const uint32_t codes[2] = {rec[off + r].x, rec[off + r].y};
+            for (int sl = 0; sl < 2; sl++)
+              ent.push_back(((uint64_t)(codes[sl] & ((1u << ROW_Q_SHIFT) - 1u)) << 8) | ((codes[sl] >> ROW_Q_SHIFT) & ROW_Q_MASK));
+          }
+          std::sort(ent.begin(), ent.end());
+          grp.clear();
+          for (size_t i = 0; i < ent.size();) {
+            size_t e = i;
+            while (e < ent.size() && (ent[e] >> 8) == (ent[i] >> 8)) e++;
+            for (size_t f = i; f < e; f += AGG_GROUP_CELLS) {
+              G g{(uint32_t)(ent[f] >> 8), AGG_CELLS_FREE, (uint32_t)std::min<size_t>(AGG_GROUP_CELLS, e - f)};
+              for (uint32_t k = 0; k < g.used; k++) g.cells = (g.cells & ~(0xFFu << (8 * k))) | ((uint32_t)(ent[f + k] & 0xFFu) << (8 * k));
+              grp.push_back(g);
+            }
+            i = e;
+          }
+          const uint32_t n_grp = (uint32_t)grp.size(), n_rec = records_for(n_grp);
+          const uint32_t base = (uint32_t)P.out.size();
+          P.out.resize((size_t)base + n_rec);
+          for (uint32_t r = 0; r < n_rec; r++) {
+            const uint32_t pad = ((base + r) & 63u) * 4u | (AGG_GROUP_X << ROW_X_SHIFT);
+            P.out[base + r] = make_uint4(pad, pad, AGG_CELLS_FREE, AGG_CELLS_FREE);
+          }
+          uint32_t pos = 0;
+          for (uint32_t used = AGG_GROUP_CELLS; used >= 1; used--) {
+            uint32_t bank_n[DEAL_BANKS] = {0}, bank_k[DEAL_BANKS] = {0};
+            auto bank = [](const G& g) { return ((g.code & ROW_OFFSET_MASK) / 4u + ((g.code >> ROW_X_SHIFT) & 31u)) & (DEAL_BANKS - 1u); };
+            for (const G& g : grp) if (g.used == used) bank_n[bank(g)]++;
+            order.clear();
+            for (uint32_t i = 0; i < n_grp; i++)
+              if (grp[i].used == used) {
+                const uint32_t c = bank(grp[i]);
+                order.emplace_back((uint32_t)((((uint64_t)(2u * bank_k[c] + 1u)) << 31) / bank_n[c]), i);
+                bank_k[c]++;
+              }
+            std::stable_sort(order.begin(), order.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+            for (const auto& o : order) {
+              uint32_t* dst = reinterpret_cast<uint32_t*>(&P.out[base + 32u * (pos / 64u) + (pos % 32u)]);
+              const uint32_t slot = (pos % 64u) / 32u;
+              dst[slot] = grp[o.second].code;
+              dst[2 + slot] = grp[o.second].cells;
+              pos++;
+            }
+          }
+          /* the chunks that take a slice, and their shares in blocks of 32 records */
+          const uint32_t n_chunk = (cnt + AGG_CHUNK - 1) / AGG_CHUNK, blocks = (n_rec + 31u) / 32u;
+          uint64_t elig = 0, cum = 0;
+          for (uint32_t k = 0; k < n_chunk; k++) { const uint32_t c = std::min<uint32_t>(AGG_CHUNK, cnt - k * AGG_CHUNK); if (c >= 32u) elig += c; }
+          for (uint32_t k = 0; k < n_chunk; k++) {
+            const uint32_t c = std::min<uint32_t>(AGG_CHUNK, cnt - k * AGG_CHUNK);
+            if (c < 32u) continue;
+            const uint32_t b0 = (uint32_t)((uint64_t)blocks * cum / elig), b1 = (uint32_t)((uint64_t)blocks * (cum + c) / elig);
+            cum += c;
+            const uint32_t first = std::min(b0 * 32u, n_rec), end = std::min(b1 * 32u, n_rec);
+            P.slices.push_back(Slice{(off + k * (uint32_t)AGG_CHUNK) >> 5, base + first, end - first});
+          }
+        }
+    } catch (...) {
+      P.failed = true;
+    }
+  };
+  {
+    std::vector<std::thread> th;
+    for (unsigned w = 1; w < W; w++) th.emplace_back(work, w);
+    work(0);
+    for (auto& x : th) x.join();
+  }
+  size_t total = 0;
+  for (const Part& P : parts) {
+    if (P.failed) return fail(PPF_ERR_NOMEM, "ppf_model: out of host memory building the group records");
+    total += P.out.size();
+  }
+  if (total >= 0xFFFFFFFFull) return fail(PPF_ERR_INVALID, "ppf_model: %zu group records are more than 32 bits index", total);
+  std::vector<uint2> hdr((nr >> 5) + 1, make_uint2(0u, 0u));
+  HIPCHK(m->grp_records.reserve(std::max<size_t>(total, 1)));
+  HIPCHK(m->grp_hdr.reserve(hdr.size()));
+  size_t base = 0;
+  for (const Part& P : parts) {
+    for (const auto& sl : P.slices) hdr[sl.hdr] = make_uint2((uint32_t)(base + sl.first), sl.count);
+    if (!P.out.empty()) HIPCHK(hipMemcpy(m->grp_records.p + base, P.out.data(), P.out.size() * sizeof(uint4), hipMemcpyHostToDevice));
+    base += P.out.size();
+  }
+  HIPCHK(hipMemcpy(m->grp_hdr.p, hdr.data(), hdr.size() * sizeof(uint2), hipMemcpyHostToDevice));
+  m->n_grp_records = total;
+  return PPF_OK;
+}
+
 static ppf_status build_table(ppf_model* m, hipStream_t st) {
   const int N = m->info.n_ref;
   const size_t NN = (size_t)N * N;
@@ -232,8 +357,10 @@ static ppf_status build_table(ppf_model* m, hipStream_t st) {
   HIPCHK(hipStreamSynchronize(st));
   ppf_status sl = build_key_lut(m, st);
   if (sl != PPF_OK) return sl;
+  sl = build_row_groups(m);
+  if (sl != PPF_OK) return sl;
   m->info.device_bytes = m->cloud.buf.bytes() + m->slotmap.bytes() + m->bucket_off.bytes() + m->bucket_slot.bytes() +
-                         m->records.bytes() + m->key_lut.bytes();
+                         m->records.bytes() + m->key_lut.bytes() + m->grp_records.bytes() + m->grp_hdr.bytes();
   return PPF_OK;
 }
 
@@ -633,9 +760,10 @@ static ppf_status model_load_stream(FILE* f, const char* path, ppf_model** out, 
     }
   }
   if (s == PPF_OK) s = build_key_lut(m, nullptr); /* not stored in the file: rebuilt from the slot map */
+  if (s == PPF_OK) s = build_row_groups(m);       /* nor are the group records: rebuilt from the pair records */
   if (s != PPF_OK) return s;
   m->info.device_bytes = m->cloud.buf.bytes() + m->slotmap.bytes() + m->bucket_off.bytes() + m->bucket_slot.bytes() +
-                         m->records.bytes() + m->key_lut.bytes();
+                         m->records.bytes() + m->key_lut.bytes() + m->grp_records.bytes() + m->grp_hdr.bytes();
   *out = owner.release();
   return PPF_OK;
 }
