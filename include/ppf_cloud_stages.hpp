@@ -23,6 +23,7 @@
  *   k4a::transformation::depth_image_to_color_camera (k4a_grabber.h:339, :391) -> DepthMap::registerDepth / registerDepthU16
  *                                                     (a raw sensor depth frame aligned to the colour camera; Cloud::fromDepth takes it)
  *   (nothing: a sensor pipeline's depth clean-up)     ->  filterDepth / filterDepthU16 / DepthMap::registerFiltered
+ *   (nothing: the boxes come from YOLO)               ->  segmentDepth / segmentDepthU16  (the depth image's surfaces as labels and boxes)
  *
  * Every stage returns a new Cloud that stays in HBM; only toMat()/download() copy to the host.  A maintainer replaces
  * the bodies of those CloudProcessor methods by these one-liners; pcl::PointCloud<PointXYZ> goes
@@ -562,6 +563,48 @@ inline std::vector<float> filterDepth(const float* depth, int rows, int cols, co
 inline std::vector<float> filterDepthU16(const uint16_t* depth, int rows, int cols, double scale, const ppf_depth_filter_params* params = 0,
                                          float zMin = 0.f, float zMax = 0.f, size_t rowPitchBytes = 0, ppf_depth_filter_stats* stats = 0) {
   return filterDepthImage(depth, PPF_DEPTH_U16, scale, rows, cols, params, zMin, zMax, rowPitchBytes, stats);
+}
+
+/* ppf_depth_segments: the depth image's connected surfaces labelled in image space.  Returns the label image
+ * (packed rows x cols: a pixel's segment rank, largest segment 0, or -1) and fills `info` with one record per segment, whose
+ * box_xywh is what Cloud::prepareFrame takes as a box.  normals: 0 (depth alone decides), or the cloud Cloud::fromDepth gives
+ * for this image with ppf_depth_normal_params (no PPF_DEPTH_NORMALS_DROP) and the same zMin / zMax. */
+inline ppf_segment_params defaultSegmentParams() {
+  ppf_segment_params p;
+  ppf_default_segment_params(&p);
+  return p;
+}
+inline std::vector<int32_t> segmentDepthImage(const void* depth, int format, double scale, int rows, int cols, const Cloud* normals,
+                                              const ppf_segment_params* params, std::vector<ppf_segment_info>& info, float zMin, float zMax,
+                                              size_t rowPitchBytes, int32_t* counts, ppf_segment_stats* stats) {
+  ppf_depth_params dp;
+  ppf_default_depth_params(&dp);
+  dp.format = format;
+  dp.depth_scale = scale;
+  dp.z_min = zMin;
+  dp.z_max = zMax;
+  const ppf_segment_params sp = params ? *params : defaultSegmentParams();
+  const int slots = sp.max_segments >= 1 && sp.max_segments <= PPF_CLUSTER_MAX_CLUSTERS ? sp.max_segments : 1;
+  std::vector<int32_t> labels((rows > 0 && cols > 0 ? (size_t)rows * (size_t)cols : 0) + 1);
+  int32_t local[3] = {0, 0, 0};
+  info.assign((size_t)slots, ppf_segment_info());
+  ppf_match_3d::check(ppf_depth_segments(depth, rows, cols, rowPitchBytes, &dp, normals ? normals->handle() : 0, &sp, &labels[0], &info[0],
+                                         counts ? counts : local, stats));
+  info.resize((size_t)(counts ? counts : local)[0]);
+  labels.resize(labels.size() - 1);
+  return labels;
+}
+/* float32 metres in; rowPitchBytes 0: packed rows; params 0: the defaults; counts: 0 or {segments, valid, all components} */
+inline std::vector<int32_t> segmentDepth(const float* depth, int rows, int cols, std::vector<ppf_segment_info>& info, const Cloud* normals = 0,
+                                         const ppf_segment_params* params = 0, float zMin = 0.f, float zMax = 0.f, size_t rowPitchBytes = 0,
+                                         int32_t* counts = 0, ppf_segment_stats* stats = 0) {
+  return segmentDepthImage(depth, PPF_DEPTH_F32, 0.001, rows, cols, normals, params, info, zMin, zMax, rowPitchBytes, counts, stats);
+}
+/* a 16-bit sensor image: z = d * scale metres (0.001 for millimetres) */
+inline std::vector<int32_t> segmentDepthU16(const uint16_t* depth, int rows, int cols, double scale, std::vector<ppf_segment_info>& info,
+                                            const Cloud* normals = 0, const ppf_segment_params* params = 0, float zMin = 0.f, float zMax = 0.f,
+                                            size_t rowPitchBytes = 0, int32_t* counts = 0, ppf_segment_stats* stats = 0) {
+  return segmentDepthImage(depth, PPF_DEPTH_U16, scale, rows, cols, normals, params, info, zMin, zMax, rowPitchBytes, counts, stats);
 }
 
 /* A resident registration map (ppf_depth_map), built once per calibration as k4a::transformation is: registerDepth draws a

@@ -56,6 +56,8 @@
  *   ppf_camera_map_boxes            a detector's boxes on the raw colour image carried into that pixel grid
  *   ppf_depth_filter (+_device)     the depth clean-up a sensor pipeline runs before anything else (the reference has none):
  *                                   unsupported "flying" pixels removed, the others smoothed without crossing a depth step
+ *   ppf_depth_segments (+_device)   detections without a detector, straight from the organised depth image (the reference takes
+ *                                   its boxes from YOLO): the image's connected smooth surfaces as a label image and boxes
  *
  * Conventions
  *   - A cloud argument is (pointer, rows, stride, normal_offset): float32 rows whose first three floats
@@ -687,6 +689,71 @@ ppf_status ppf_depth_filter(const void* depth, int rows, int cols, size_t row_pi
  * allocation, or d_out overlapping the depth image is PPF_ERR_INVALID before anything is launched. */
 ppf_status ppf_depth_filter_device(const void* d_depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
                                    const ppf_depth_filter_params* fp, float* d_out, void* stream, ppf_depth_filter_stats* stats);
+
+/* ---- a depth image's surfaces labelled in image space: proposals without leaving the image ----------- */
+#define PPF_SEGMENT_EIGHT 1      /* flags: 8-connectivity instead of 4 */
+#define PPF_SEGMENT_UNORIENTED 2 /* flags: normals agree on |dot|, as PPF_REGION_UNORIENTED */
+typedef struct ppf_segment_params {
+  float depth_abs;           /* finite, >= 0, metres; default 0.005 */
+  float depth_quad;          /* finite, >= 0, 1/metres; default 0 */
+  float normal_cos;          /* finite, -1..1; default 0.9659258f; ignored without normals */
+  float curvature_threshold; /* >= 0, +inf allowed, not NaN; default 0.03; ignored without normals */
+  int32_t min_size;          /* >= 1 pixels; default 100 */
+  int32_t max_size;          /* 0: no bound */
+  int32_t max_segments;      /* 1..PPF_CLUSTER_MAX_CLUSTERS; default 64 */
+  int32_t flags;             /* 0 | PPF_SEGMENT_EIGHT | PPF_SEGMENT_UNORIENTED */
+  int32_t reserved[4];
+} ppf_segment_params;
+typedef struct ppf_segment_info {
+  int32_t n_pixels, n_border; /* all its pixels; the attached border pixels among them */
+  int32_t first_pixel;        /* v * cols + u of its smallest SMOOTH pixel */
+  int32_t box_xywh[4];        /* {umin, vmin, umax - umin, vmax - vmin} over all its pixels: ppf_cluster_info's convention */
+  float z_lo, z_hi;           /* the float minimum and maximum of its pixels' z */
+  int32_t reserved[3];
+} ppf_segment_info;
+typedef struct ppf_segment_stats {
+  int32_t n_kept, n_eligible, n_smooth, n_attached; /* pixels: kept, eligible, smooth, border pixels that joined a component */
+  int32_t n_launches;   /* kernel launches of the call */
+  int32_t n_host_syncs; /* blocking waits of the call: 1 */
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_segment_stats;
+/* depth_abs 0.005, depth_quad 0, normal_cos 0.9659258, curvature_threshold 0.03, min_size 100, max_size 0, max_segments 64,
+ * flags 0 */
+void ppf_default_segment_params(ppf_segment_params* p);
+/* Connected components of the depth image's own pixel grid, as a closed specification.  Every operation is fp64 as written,
+ * nothing fused; z(p) and "kept" are ppf_cloud_from_depth's, Z = (double)z, a pixel's index is v * cols + u; dp->flags is
+ * ignored.  Adjacent means the 4 neighbours (+-1 in u or in v), or all 8 with PPF_SEGMENT_EIGHT.
+ *   normals == NULL: every kept pixel is eligible and smooth, and agree(p, q) is always true.
+ *   normals != NULL: the cloud must be what ppf_cloud_from_depth_normals gives for this image and this dp without
+ *     PPF_DEPTH_NORMALS_DROP: row k belongs to the k-th kept pixel in row-major order; only nx ny nz and the curvature are
+ *     read.  A pixel is eligible iff it is kept and nx, ny, nz are finite, smooth iff eligible and curvature <=
+ *     curvature_threshold (a float comparison: a NaN curvature is not smooth), a border pixel iff eligible and not smooth.
+ *     agree(p, q) iff dot >= (double)normal_cos with dot = ((double)pnx*(double)qnx + (double)pny*(double)qny) +
+ *     (double)pnz*(double)qnz (fabs(dot) with PPF_SEGMENT_UNORIENTED): ppf_prep_regions' rule.
+ *   step(p, q) iff fabs(Zq - Zp) <= (double)depth_abs + (double)depth_quad * (Zp * Zq); it is symmetric.
+ * Two adjacent smooth pixels are linked iff step and agree; a component is a connected component of the links.  A border pixel
+ * joins the component of the adjacent smooth pixel with the smallest fabs(Zq - Zb) (ties: the smaller pixel index) among those
+ * it steps to and agrees with, or no segment; border pixels link nothing.  n_pixels counts a component's smooth and attached
+ * border pixels.  A component is valid iff min_size <= n_pixels and (max_size == 0 or n_pixels <= max_size); the valid
+ * components ranked by n_pixels descending, then first_pixel ascending, the first min(valid, max_segments) are the segments.
+ * labels: packed rows x cols int32, the rank of the pixel's segment or -1.  info: [max_segments], zero past the count.
+ * counts: [3] = {segments output, valid components, all components}.  Everything ppf_depth_filter says about depth, the pitch,
+ * dp and their errors holds; sp NULL, a field outside the range stated beside it, an unknown flag or labels / info / counts
+ * NULL are PPF_ERR_INVALID before any device work too; a normals cloud whose row count is not n_kept is PPF_ERR_INVALID,
+ * found at the call's one wait; without a device the call is PPF_ERR_HIP.  The launch count depends on nothing but
+ * normals != NULL; one blocking wait (n_host_syncs 1).  On every error info, counts and
+ * *stats are zero and labels is not touched.  stats may be NULL. */
+ppf_status ppf_depth_segments(const void* depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
+                              const ppf_cloud* normals /* may be NULL */, const ppf_segment_params* sp, int32_t* labels,
+                              ppf_segment_info* info, int32_t* counts, ppf_segment_stats* stats /* may be NULL */);
+/* the same between DEVICE buffers, as ppf_depth_filter_device: enqueued on `stream` (a hipStream_t, NULL: default stream),
+ * returns when the label image is complete; info, counts and stats stay HOST memory.  A pointer the current device cannot
+ * read, a buffer that runs past the end of its allocation, or d_labels overlapping the depth image is PPF_ERR_INVALID before
+ * anything is launched; after any other error the content of d_labels is unspecified. */
+ppf_status ppf_depth_segments_device(const void* d_depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
+                                     const ppf_cloud* normals /* may be NULL */, const ppf_segment_params* sp, int32_t* d_labels,
+                                     void* stream, ppf_segment_info* info, int32_t* counts, ppf_segment_stats* stats /* may be NULL */);
 
 /* ---- every detection of a frame in one segmented device pass ------------------------------------------------ */
 typedef struct ppf_frame_params {

@@ -139,6 +139,25 @@ class DepthFilterStats(C.Structure):
 PPF_DEPTH_FILTER_MAX_RADIUS = 8
 
 
+class SegmentParams(C.Structure):
+    _fields_ = [("depth_abs", C.c_float), ("depth_quad", C.c_float), ("normal_cos", C.c_float), ("curvature_threshold", C.c_float),
+                ("min_size", C.c_int32), ("max_size", C.c_int32), ("max_segments", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class SegmentInfo(C.Structure):
+    _fields_ = [("n_pixels", C.c_int32), ("n_border", C.c_int32), ("first_pixel", C.c_int32), ("box_xywh", C.c_int32 * 4),
+                ("z_lo", C.c_float), ("z_hi", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class SegmentStats(C.Structure):
+    _fields_ = [("n_kept", C.c_int32), ("n_eligible", C.c_int32), ("n_smooth", C.c_int32), ("n_attached", C.c_int32),
+                ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32), ("ms_wall", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+PPF_SEGMENT_EIGHT, PPF_SEGMENT_UNORIENTED = 1, 2  # SegmentParams.flags bits
+
+
 class VerifyParams(C.Structure):
     _fields_ = [("inlier_dist", C.c_float), ("normal_cos", C.c_float), ("depth_tol", C.c_float), ("model_step", C.c_int32),
                 ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
@@ -383,6 +402,13 @@ _SIGNATURES = {
                                    C.c_void_p, C.POINTER(DepthFilterStats)]),
     "ppf_depth_filter_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(DepthParams),
                                           C.POINTER(DepthFilterParams), C.c_void_p, C.c_void_p, C.POINTER(DepthFilterStats)]),
+    "ppf_default_segment_params": (None, [C.POINTER(SegmentParams)]),
+    "ppf_depth_segments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(DepthParams), C.c_void_p,
+                                     C.POINTER(SegmentParams), C.c_void_p, C.POINTER(SegmentInfo), C.POINTER(C.c_int32),
+                                     C.POINTER(SegmentStats)]),
+    "ppf_depth_segments_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(DepthParams), C.c_void_p,
+                                            C.POINTER(SegmentParams), C.c_void_p, C.c_void_p, C.POINTER(SegmentInfo),
+                                            C.POINTER(C.c_int32), C.POINTER(SegmentStats)]),
     "ppf_default_verify_params": (None, [C.POINTER(VerifyParams)]),
     "ppf_verify_frame": (C.c_int, [C.POINTER(FrameDetection), C.c_int, C.POINTER(Pose), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int,
                                    C.c_int, C.POINTER(C.c_double), C.POINTER(VerifyParams), C.POINTER(PoseScore), C.POINTER(C.c_int),

@@ -748,6 +748,91 @@ def filter_depth(depth, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max
     return (out, _capi.stats_dict(st)) if return_stats else out
 
 
+# ppf_segment_info as a numpy record
+SEGMENT_INFO = np.dtype([("n_pixels", "<i4"), ("n_border", "<i4"), ("first_pixel", "<i4"), ("box_xywh", "<i4", 4), ("z_lo", "<f4"),
+                         ("z_hi", "<f4"), ("reserved", "<i4", 3)])
+
+
+def _segment_params(params) -> _capi.SegmentParams:
+    """``_params`` for ppf_segment_params; a key that is no field of the record (a misspelt name) is an error, not ignored"""
+    if isinstance(params, dict):
+        unknown = sorted(set(params) - {f for f, _ in _capi.SegmentParams._fields_})
+        if unknown:
+            raise PPFError(_capi.PPF_ERR_INVALID, f"unknown segment parameter(s): {', '.join(unknown)}")
+    return _params(_capi.SegmentParams, "ppf_default_segment_params", params)
+
+
+def segment_depth(depth, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0, normals=None, params=None,
+                  out=None, return_info: bool = False, return_stats: bool = False):
+    """The depth image's connected surfaces, labelled in image space (ppf_depth_segments): an int32 image of
+    the same shape holding each pixel's segment rank (largest segment 0) or -1.  Two adjacent kept pixels are linked iff
+    their depths differ by at most ``depth_abs + depth_quad * Zp * Zq`` and -- with ``normals``, the DeviceCloud that
+    ``DeviceCloud.from_depth(depth, ..., normals={...})`` gives for this image (no ``drop``) -- both are smooth (curvature
+    <= ``curvature_threshold``) and their normals agree (``normal_cos``); the other pixels with a normal join the nearest
+    smooth neighbour in depth.  depth: a 2-D numpy float32 (metres) or uint16 (units of depth_scale metres) array, rows read
+    at its stride, which gives a numpy image; or such a torch tensor on the GPU, read in place on
+    ``torch.cuda.current_stream()`` (ppf_depth_segments_device), which gives an int32 tensor on the same device (or fills
+    ``out``, which must not overlap the input).  params: a SegmentParams, a dict of its fields or None (the defaults).
+    return_info adds the segments' ``SEGMENT_INFO`` records (one per segment) and the counts (segments, valid components,
+    all components); return_stats adds the call's stats last."""
+    prm = _segment_params(params)
+    dp = _capi.DepthParams()
+    lib().ppf_default_depth_params(C.byref(dp))
+    dp.depth_scale, dp.z_min, dp.z_max = float(depth_scale), float(z_min), float(z_max)
+    if normals is not None and not isinstance(normals, DeviceCloud):
+        raise PPFError(_capi.PPF_ERR_INVALID, "normals must be a DeviceCloud or None")
+    nrm = normals._ptr if normals is not None else None
+    mc = max(1, min(int(prm.max_segments), _capi.PPF_CLUSTER_MAX_CLUSTERS))
+    info = np.zeros(mc, dtype=SEGMENT_INFO)
+    counts = np.zeros(3, dtype=np.int32)
+    st = _capi.SegmentStats()
+    tail = (info.ctypes.data_as(C.POINTER(_capi.SegmentInfo)), counts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st))
+
+    def result(labels):
+        res = [labels]
+        if return_info:
+            res += [info[:int(counts[0])].copy(), counts]
+        if return_stats:
+            res.append(_capi.stats_dict(st))
+        return labels if len(res) == 1 else tuple(res)
+
+    if type(depth).__module__.startswith("torch") and depth.is_cuda:
+        import torch
+        fmt = {torch.float32: _capi.PPF_DEPTH_F32, torch.uint16: _capi.PPF_DEPTH_U16}.get(depth.dtype)
+        if fmt is None or depth.dim() != 2:
+            raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 or uint16 tensor")
+        if depth.stride(1) != 1 or depth.stride(0) < depth.shape[1]:
+            depth = depth.contiguous()
+        shape = tuple(depth.shape)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=depth.device)
+        elif not (out.is_cuda and out.device == depth.device and out.dtype == torch.int32 and tuple(out.shape) == shape
+                  and out.is_contiguous()):
+            raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous int32 tensor of shape {shape} on the depth image's device")
+        dp.format = fmt
+        with torch.cuda.device(depth.device):
+            stream = torch.cuda.current_stream(depth.device).cuda_stream
+            check(lib().ppf_depth_segments_device(C.c_void_p(depth.data_ptr()), shape[0], shape[1], depth.stride(0) * depth.element_size(),
+                                                  C.byref(dp), nrm, C.byref(prm), C.c_void_p(out.data_ptr()),
+                                                  C.c_void_p(stream) if stream else None, *tail))
+        return result(out)
+    a = np.asarray(depth.numpy() if type(depth).__module__.startswith("torch") else depth)
+    fmt = {np.dtype(np.float32): _capi.PPF_DEPTH_F32, np.dtype(np.uint16): _capi.PPF_DEPTH_U16}.get(a.dtype)
+    if fmt is None or a.ndim != 2:
+        raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 or uint16 array")
+    if a.strides[1] != a.itemsize or a.strides[0] < a.shape[1] * a.itemsize or a.strides[0] % a.itemsize:
+        a = np.ascontiguousarray(a)
+    dp.format = fmt
+    if out is None:
+        out = np.empty(a.shape, np.int32)
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.int32 and out.shape == a.shape and out.flags.c_contiguous
+              and out.flags.writeable):
+        raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous int32 array of shape {a.shape}")
+    check(lib().ppf_depth_segments(C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1], a.strides[0], C.byref(dp), nrm, C.byref(prm),
+                                   out.ctypes.data, *tail))
+    return result(out)
+
+
 class CloudProcessor:
     """``ppf::CloudProcessor``: holds the scene cloud, the depth image, the detector's boxes, the per-object clouds
     and the PPF detectors; every method is the reference's, in the order its driver calls them
@@ -801,6 +886,11 @@ class CloudProcessor:
         self.cluster_info: Optional[np.ndarray] = None
         self.cluster_stats: Dict[str, object] = {}
         self.depth_filter_stats: Dict[str, object] = {}  # FilterDepth: the ppf_depth_filter counters
+        # ProposeSegments: the info rows of the image's segments, its label image and the counters
+        self.segment_info: Optional[np.ndarray] = None
+        self.segment_labels: Optional[np.ndarray] = None
+        self.segment_stats: Dict[str, object] = {}
+        self._depth_normals_of: tuple = (None, None)  # the (scene, depth) pair Deprojection(normals=...) last made
 
     # ---- the PCL half -------------------------------------------------------------------------------------
     def Deprojection(self, CameraIntr, fp64: bool = False, normals: Optional[dict] = None) -> DeviceCloud:
@@ -810,6 +900,7 @@ class CloudProcessor:
         if self.depth is None:
             raise PPFError(_capi.PPF_ERR_INVALID, "Deprojection needs a depth image")
         self.scene = DeviceCloud.from_depth(self.depth, np.asarray(CameraIntr, dtype=np.float64), fp64=fp64, normals=normals)
+        self._depth_normals_of = (self.scene, self.depth) if normals is not None and not normals.get("drop", False) else (None, None)
         return self.scene
 
     def FilterDepth(self, params=None) -> np.ndarray:
@@ -858,6 +949,22 @@ class CloudProcessor:
         self.cluster_info = info[:int(counts[0])].copy()
         self.boxes = [tuple(int(v) for v in row["box_xywh"]) for row in self.cluster_info]
         return found
+
+    def ProposeSegments(self, params=None) -> np.ndarray:
+        """ProposeBoxes without leaving the image: ``self.depth`` split into its connected surfaces in image space
+        (``segment_depth``, ppf_depth_segments) and ``self.boxes`` set to the segments' boxes, largest segment first.  When
+        ``self.scene`` is what ``Deprojection(normals=...)`` gave for this depth image it serves as the normals cloud;
+        otherwise depth alone decides.  params: the fields of ppf_segment_params (depth_abs, depth_quad, normal_cos,
+        curvature_threshold, min_size, max_size, max_segments, flags).  Sets ``segment_info`` (one row per segment),
+        ``segment_labels`` and ``segment_stats``; returns the label image."""
+        if self.depth is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "ProposeSegments needs a depth image")
+        made = self.scene is not None and self.scene is self._depth_normals_of[0] and self.depth is self._depth_normals_of[1]
+        normals = self.scene if made else None
+        self.segment_labels, self.segment_info, _, self.segment_stats = segment_depth(self.depth, normals=normals, params=params,
+                                                                                      return_info=True, return_stats=True)
+        self.boxes = [tuple(int(v) for v in row["box_xywh"]) for row in self.segment_info]
+        return self.segment_labels
 
     def SceneCropping(self, CameraIntr) -> List[DeviceCloud]:
         """CameraIntr: 3x3 matrix (fx, fy on the diagonal, ppx, ppy in the last column), as the reference passes it"""
