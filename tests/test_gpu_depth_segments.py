@@ -326,6 +326,8 @@ def test_launches_and_waits_do_not_depend_on_the_content():
     with_n = [segment_depth(img, normals=cloud_of(seeded_normals(rng, img)), params=dict(min_size=1), return_stats=True)[1] for img in imgs]
     assert len({(st["n_launches"], st["n_host_syncs"]) for st in with_n}) == 1 and with_n[0]["n_host_syncs"] == 1
     assert with_n[0]["n_launches"] > plain[0]["n_launches"]
+    # 5 stage kernels + 4 digit passes of 7 launches + 2; a normals cloud adds k_depth_count and a five-launch scan
+    assert (plain[0]["n_launches"], with_n[0]["n_launches"]) == (35, 41)
     other = segment_depth(seeded(rng, (2 * TH + 1, 2 * TW + 1)), return_stats=True)[1]          # nor on the image's size
     assert other["n_launches"] == plain[0]["n_launches"]
 

@@ -151,7 +151,10 @@ def test_without_a_device_the_entry_is_loud():
 
 
 def test_python_wrapper_rejects_a_misspelt_parameter():
-    from yolo_ppf_pose_estimation_amd.cloud_processor import _region_params, region_clouds
+    from yolo_ppf_pose_estimation_amd.cloud_processor import _params, region_clouds
+
+    def _region_params(params):
+        return _params(RegionParams, "ppf_default_region_params", params, "region")
     assert _region_params(dict(max_regions=7, flags=1)).max_regions == 7 and _region_params(None).max_regions == 64
     for call in (lambda: _region_params(dict(max_clusters=7)), lambda: region_clouds([], dict(normal_cosine=0.5))):
         with pytest.raises(_capi.PPFError) as e:

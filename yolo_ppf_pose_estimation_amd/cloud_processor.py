@@ -209,27 +209,26 @@ class DeviceCloud:
     def apply_planes(self, info, params=None) -> "DeviceCloud":
         """the rows of this cloud (a detection's edge cloud) that the planes of ``info`` -- the info rows ``remove_planes``
         returned for one cloud -- do not remove (ppf_prep_planes_apply): same predicate, same ``params``"""
-        prm = _plane_params(params)
+        prm = _params(PlaneParams, "ppf_default_plane_params", params, "plane")
         rec = np.ascontiguousarray(np.asarray(info, dtype=PLANE_INFO).reshape(-1))
         return self._stage(lib().ppf_prep_planes_apply, rec.ctypes.data_as(C.POINTER(PlaneInfo)), int(rec.shape[0]), C.byref(prm))
 
-    def clusters(self, params=None, intr=None, image_size=None, return_info: bool = False, return_labels: bool = False):
-        """this cloud's object clusters (ppf_prep_clusters with one cloud; see the module-level ``cluster_clouds``)"""
-        res = cluster_clouds([self], params, intr, image_size, return_info=return_info, return_labels=return_labels)
+    def _labelled(self, fn, params, intr, image_size, return_info, return_labels):
+        """``fn`` (cluster_clouds or region_clouds) on this cloud alone: its parts of the results, the stats last"""
+        res = fn([self], params, intr, image_size, return_info=return_info, return_labels=return_labels)
         if not (return_info or return_labels):
             return res[0]
-        n = 1 + 2 * int(return_info) + int(return_labels)   # this cloud's clusters, info rows, counts, labels
+        n = 1 + 2 * int(return_info) + int(return_labels)   # this cloud's components, info rows, counts, labels
         out = [part[0] for part in res[:n]]
-        return tuple(out + [res[-1]] if return_info else out)   # the stats last
+        return tuple(out + [res[-1]] if return_info else out)
+
+    def clusters(self, params=None, intr=None, image_size=None, return_info: bool = False, return_labels: bool = False):
+        """this cloud's object clusters (ppf_prep_clusters with one cloud; see the module-level ``cluster_clouds``)"""
+        return self._labelled(cluster_clouds, params, intr, image_size, return_info, return_labels)
 
     def regions(self, params=None, intr=None, image_size=None, return_info: bool = False, return_labels: bool = False):
         """this cloud's smooth surface regions (ppf_prep_regions with one cloud; see the module-level ``region_clouds``)"""
-        res = region_clouds([self], params, intr, image_size, return_info=return_info, return_labels=return_labels)
-        if not (return_info or return_labels):
-            return res[0]
-        n = 1 + 2 * int(return_info) + int(return_labels)   # this cloud's regions, info rows, counts, labels
-        out = [part[0] for part in res[:n]]
-        return tuple(out + [res[-1]] if return_info else out)   # the stats last
+        return self._labelled(region_clouds, params, intr, image_size, return_info, return_labels)
 
     def knn(self, k: int):
         n = len(self)
@@ -250,7 +249,7 @@ def remove_planes(clouds, params=None, return_info: bool = False, return_labels:
     it alone.  params: a PlaneParams, a dict of its fields (the rest default) or None.  Returns the list of kept clouds; with
     return_info also the info rows ((n_clouds, max_planes) records of ``PLANE_INFO``) and, last, the call's stats; with
     return_labels the per-row labels (uint8: 0 kept, 1 + p inlier of plane p, 0x80 | (1 + p) behind plane p) per cloud."""
-    prm = _plane_params(params)
+    prm = _params(PlaneParams, "ppf_default_plane_params", params, "plane")
     K = len(clouds)
     ins, outs = (C.c_void_p * max(K, 1))(*[c._ptr for c in clouds]), (C.c_void_p * max(K, 1))()
     info = np.zeros((K, max(1, min(int(prm.max_planes), _capi.PPF_PLANE_MAX_PLANES))), dtype=PLANE_INFO)
@@ -285,33 +284,8 @@ def cluster_clouds(clouds, params=None, intr=None, image_size=None, return_info:
     Returns one list of cluster clouds per cloud; with return_info also the info rows ((n_clouds, max_clusters) records of
     ``CLUSTER_INFO``, zero past a cloud's count), the counts ((n_clouds, 3): clusters, valid components, all components) and,
     last, the call's stats; with return_labels the per-row labels (int32: the cluster's rank, or -1) per cloud."""
-    prm = _cluster_params(params)
-    K = len(clouds)
-    mc = max(1, min(int(prm.max_clusters), _capi.PPF_CLUSTER_MAX_CLUSTERS))
-    ins, outs = (C.c_void_p * max(K, 1))(*[c._ptr for c in clouds]), (C.c_void_p * max(K * mc, 1))()
-    info = np.zeros((K, mc), dtype=CLUSTER_INFO)
-    counts = np.zeros((K, 3), dtype=np.int32)
-    labels = [np.full(len(c), -1, dtype=np.int32) for c in clouds] if return_labels else None
-    lab = (C.c_void_p * max(K, 1))(*[a.ctypes.data for a in labels]) if return_labels else None
-    it, rows, cols = None, 0, 0
-    if intr is not None:
-        if image_size is None:
-            raise PPFError(_capi.PPF_ERR_INVALID, "cluster_clouds: intr needs image_size = (rows, cols)")
-        it, (rows, cols) = (C.c_double * 4)(*_intr4(intr)), image_size
-    st = ClusterStats()
-    check(lib().ppf_prep_clusters(ins, K, C.byref(prm), it, int(rows), int(cols), outs, info.ctypes.data_as(C.POINTER(ClusterInfo)),
-                                  counts.ctypes.data_as(C.POINTER(C.c_int32)), lab, C.byref(st)))
-    found = [[DeviceCloud(C.c_void_p(outs[i * mc + r])) for r in range(int(counts[i, 0]))] for i in range(K)]
-    if not (return_info or return_labels):
-        return found
-    res = [found]
-    if return_info:
-        res += [info, counts]
-    if return_labels:
-        res.append(labels)
-    if return_info:
-        res.append(_capi.stats_dict(st))
-    return tuple(res)
+    return _label_clouds("cluster_clouds", lib().ppf_prep_clusters, _params(ClusterParams, "ppf_default_cluster_params", params, "cluster"),
+                         "max_clusters", 3, clouds, intr, image_size, return_info, return_labels)
 
 
 def region_clouds(clouds, params=None, intr=None, image_size=None, return_info: bool = False, return_labels: bool = False):
@@ -324,22 +298,28 @@ def region_clouds(clouds, params=None, intr=None, image_size=None, return_info: 
     one list of region clouds per cloud; with return_info also the info rows (``CLUSTER_INFO``; ``first_row`` is the region's
     smallest smooth row), the counts ((n_clouds, 4): regions, valid components, all components, border rows attached) and,
     last, the call's stats; with return_labels the per-row labels (int32: the region's rank, or -1) per cloud."""
-    prm = _region_params(params)
+    return _label_clouds("region_clouds", lib().ppf_prep_regions, _params(RegionParams, "ppf_default_region_params", params, "region"),
+                         "max_regions", 4, clouds, intr, image_size, return_info, return_labels)
+
+
+def _label_clouds(who, entry, prm, max_field, n_counts, clouds, intr, image_size, return_info, return_labels):
+    """what ``cluster_clouds`` and ``region_clouds`` share: one call of ``entry`` (ppf_prep_clusters' signature) with the params
+    record ``prm``, whose ``max_field`` bounds a cloud's components; ``n_counts`` words of counts per cloud"""
     K = len(clouds)
-    mc = max(1, min(int(prm.max_regions), _capi.PPF_CLUSTER_MAX_CLUSTERS))
+    mc = max(1, min(int(getattr(prm, max_field)), _capi.PPF_CLUSTER_MAX_CLUSTERS))
     ins, outs = (C.c_void_p * max(K, 1))(*[c._ptr for c in clouds]), (C.c_void_p * max(K * mc, 1))()
     info = np.zeros((K, mc), dtype=CLUSTER_INFO)
-    counts = np.zeros((K, 4), dtype=np.int32)
+    counts = np.zeros((K, n_counts), dtype=np.int32)
     labels = [np.full(len(c), -1, dtype=np.int32) for c in clouds] if return_labels else None
     lab = (C.c_void_p * max(K, 1))(*[a.ctypes.data for a in labels]) if return_labels else None
     it, rows, cols = None, 0, 0
     if intr is not None:
         if image_size is None:
-            raise PPFError(_capi.PPF_ERR_INVALID, "region_clouds: intr needs image_size = (rows, cols)")
+            raise PPFError(_capi.PPF_ERR_INVALID, f"{who}: intr needs image_size = (rows, cols)")
         it, (rows, cols) = (C.c_double * 4)(*_intr4(intr)), image_size
     st = ClusterStats()
-    check(lib().ppf_prep_regions(ins, K, C.byref(prm), it, int(rows), int(cols), outs, info.ctypes.data_as(C.POINTER(ClusterInfo)),
-                                 counts.ctypes.data_as(C.POINTER(C.c_int32)), lab, C.byref(st)))
+    check(entry(ins, K, C.byref(prm), it, int(rows), int(cols), outs, info.ctypes.data_as(C.POINTER(ClusterInfo)),
+                counts.ctypes.data_as(C.POINTER(C.c_int32)), lab, C.byref(st)))
     found = [[DeviceCloud(C.c_void_p(outs[i * mc + r])) for r in range(int(counts[i, 0]))] for i in range(K)]
     if not (return_info or return_labels):
         return found
@@ -368,42 +348,20 @@ def _pose_record(p) -> Pose:
     return rec
 
 
-def _params(cls, defaults: str, params):
-    """``params`` as a ``cls`` record: itself, or the C defaults (``lib().<defaults>``) with a dict's fields set over them"""
+def _params(cls, defaults: str, params, what: Optional[str] = None):
+    """``params`` as a ``cls`` record: itself, or the C defaults (``lib().<defaults>``) with a dict's fields set over them.
+    With ``what`` (the record's name in words) a key that is no field of the record (a misspelt name) is an error, not ignored"""
     if isinstance(params, cls):
         return params
+    if what is not None and isinstance(params, dict):
+        unknown = sorted(set(params) - {f for f, _ in cls._fields_})
+        if unknown:
+            raise PPFError(_capi.PPF_ERR_INVALID, f"unknown {what} parameter(s): {', '.join(unknown)}")
     prm = cls()
     getattr(lib(), defaults)(C.byref(prm))
     for key, v in (params or {}).items():
         setattr(prm, key, v)
     return prm
-
-
-def _plane_params(params) -> PlaneParams:
-    """``_params`` for ppf_plane_params; a key that is no field of the record (a misspelt name) is an error, not ignored"""
-    if isinstance(params, dict):
-        unknown = sorted(set(params) - {f for f, _ in PlaneParams._fields_})
-        if unknown:
-            raise PPFError(_capi.PPF_ERR_INVALID, f"unknown plane parameter(s): {', '.join(unknown)}")
-    return _params(PlaneParams, "ppf_default_plane_params", params)
-
-
-def _cluster_params(params) -> ClusterParams:
-    """``_params`` for ppf_cluster_params; a key that is no field of the record (a misspelt name) is an error, not ignored"""
-    if isinstance(params, dict):
-        unknown = sorted(set(params) - {f for f, _ in ClusterParams._fields_})
-        if unknown:
-            raise PPFError(_capi.PPF_ERR_INVALID, f"unknown cluster parameter(s): {', '.join(unknown)}")
-    return _params(ClusterParams, "ppf_default_cluster_params", params)
-
-
-def _region_params(params) -> RegionParams:
-    """``_params`` for ppf_region_params; a key that is no field of the record (a misspelt name) is an error, not ignored"""
-    if isinstance(params, dict):
-        unknown = sorted(set(params) - {f for f, _ in RegionParams._fields_})
-        if unknown:
-            raise PPFError(_capi.PPF_ERR_INVALID, f"unknown region parameter(s): {', '.join(unknown)}")
-    return _params(RegionParams, "ppf_default_region_params", params)
 
 
 def _depth_image(depth, error: str):
@@ -689,15 +647,6 @@ class DepthMap:
         return (img, _capi.stats_dict(st)) if return_stats else img
 
 
-def _depth_filter_params(params) -> _capi.DepthFilterParams:
-    """``_params`` for ppf_depth_filter_params; a key that is no field of the record (a misspelt name) is an error, not ignored"""
-    if isinstance(params, dict):
-        unknown = sorted(set(params) - {f for f, _ in _capi.DepthFilterParams._fields_})
-        if unknown:
-            raise PPFError(_capi.PPF_ERR_INVALID, f"unknown depth filter parameter(s): {', '.join(unknown)}")
-    return _params(_capi.DepthFilterParams, "ppf_default_depth_filter_params", params)
-
-
 def filter_depth(depth, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0, params=None, out=None,
                  return_stats: bool = False):
     """The depth image without its unsupported ("flying") pixels and smoothed inside each surface (ppf_depth_filter,
@@ -706,7 +655,7 @@ def filter_depth(depth, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max
     metres) array, rows read at its stride, which gives a numpy image; or such a torch tensor on the GPU, read in place on
     ``torch.cuda.current_stream()`` (ppf_depth_filter_device), which gives a float32 tensor on the same device (or fills
     ``out``, which must not overlap the input).  params: a DepthFilterParams, a dict of its fields or None (the defaults)."""
-    prm = _depth_filter_params(params)
+    prm = _params(_capi.DepthFilterParams, "ppf_default_depth_filter_params", params, "depth filter")
     dp = _capi.DepthParams()
     lib().ppf_default_depth_params(C.byref(dp))
     dp.depth_scale, dp.z_min, dp.z_max = float(depth_scale), float(z_min), float(z_max)
@@ -753,15 +702,6 @@ SEGMENT_INFO = np.dtype([("n_pixels", "<i4"), ("n_border", "<i4"), ("first_pixel
                          ("z_hi", "<f4"), ("reserved", "<i4", 3)])
 
 
-def _segment_params(params) -> _capi.SegmentParams:
-    """``_params`` for ppf_segment_params; a key that is no field of the record (a misspelt name) is an error, not ignored"""
-    if isinstance(params, dict):
-        unknown = sorted(set(params) - {f for f, _ in _capi.SegmentParams._fields_})
-        if unknown:
-            raise PPFError(_capi.PPF_ERR_INVALID, f"unknown segment parameter(s): {', '.join(unknown)}")
-    return _params(_capi.SegmentParams, "ppf_default_segment_params", params)
-
-
 def segment_depth(depth, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0, normals=None, params=None,
                   out=None, return_info: bool = False, return_stats: bool = False):
     """The depth image's connected surfaces, labelled in image space (ppf_depth_segments): an int32 image of
@@ -775,7 +715,7 @@ def segment_depth(depth, *, depth_scale: float = 0.001, z_min: float = 0.0, z_ma
     ``out``, which must not overlap the input).  params: a SegmentParams, a dict of its fields or None (the defaults).
     return_info adds the segments' ``SEGMENT_INFO`` records (one per segment) and the counts (segments, valid components,
     all components); return_stats adds the call's stats last."""
-    prm = _segment_params(params)
+    prm = _params(_capi.SegmentParams, "ppf_default_segment_params", params, "segment")
     dp = _capi.DepthParams()
     lib().ppf_default_depth_params(C.byref(dp))
     dp.depth_scale, dp.z_min, dp.z_max = float(depth_scale), float(z_min), float(z_max)

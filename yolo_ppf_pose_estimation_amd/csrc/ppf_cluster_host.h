@@ -1,14 +1,14 @@
 /*
  * ppf_cluster_host.h — host side of ppf_prep_clusters: the connected blobs of up to 256 plane-free clouds in one pass
  * (DESIGN.md §20).  Kernels: ppf_cluster_kernels.h.  Included by ppf_hip.hip after ppf_prep_host.h (ppf_cloud, FrameRun,
- * frame_scan).
+ * frame_scan, frame_sort, frame_sort_segmented).
  *
  * Per call: one upload of the segment table before any device work, then k_clu_bounds, k_clu_grid, k_clu_keys, the sort by
  * (segment, cell) (five digit passes of seven launches and one gather), k_clu_runs, the scan, k_clu_cells, k_clu_link,
  * k_clu_flatten, k_clu_valid, the ranking's sort (the same five passes), k_clu_rank, k_clu_labels, the gather's sort (three
  * passes), k_clu_gather and k_clu_reduce: 110 launches whatever the clouds hold, none when no cloud has a row.
  * The sequence is cut in three shared pieces (clu_begin, clu_cells, clu_finish) that ppf_prep_regions runs too, around kernels
- * of its own (ppf_region_host.h).
+ * of its own (ppf_region_host.h), inside the same entry body (clu_entry).
  * Nothing the device counts (cells, components, clusters) comes to the host before the end: grids are sized for the rows and
  * workgroups past a device-side count leave.  The host waits once, for the cluster heads, the reductions, the counts, the
  * grids and the labels; the outputs are views into one block sized for the input, so nothing is allocated after that wait.
@@ -27,32 +27,6 @@ ppf_status cluster_params_check(const char* who, const ppf_cluster_params* p) {
     return fail(PPF_ERR_INVALID, "%s: max_clusters is %d (1..%d)", who, p->max_clusters, PPF_CLUSTER_MAX_CLUSTERS);
   if (p->flags) return fail(PPF_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)p->flags);
   return PPF_OK;
-}
-
-/* stable LSD passes over the digits at `shifts` of keys ka (values va); the sorted arrays end in ka / va */
-ppf_status cluster_sort(FrameRun& fr, uint32_t*& ka, uint32_t*& va, uint32_t*& kb, uint32_t*& vb, int n, uint32_t* hist, uint32_t* offs,
-                        const int* shifts, int passes) {
-  const int nblk = (n + RS_BLOCK - 1) / RS_BLOCK;
-  ppf_status s;
-  for (int pass = 0; pass < passes; pass++) {
-    FRAME_LAUNCH(fr, k_rs_hist, dim3(nblk), dim3(RS_BLOCK), ka, n, shifts[pass], nblk, hist);
-    HIPCHK(hipGetLastError());
-    if ((s = frame_scan(fr, hist, offs, (size_t)256 * nblk)) != PPF_OK) return s;
-    FRAME_LAUNCH(fr, k_rs_scatter, dim3(nblk), dim3(RS_BLOCK), ka, va, n, shifts[pass], nblk, offs, kb, vb);
-    HIPCHK(hipGetLastError());
-    std::swap(ka, kb);
-    std::swap(va, vb);
-  }
-  return PPF_OK;
-}
-/* by a 32-bit key, then by segment: a segment's rows end up together, in key order, equal keys in row order */
-ppf_status cluster_sort_segmented(FrameRun& fr, uint32_t*& ka, uint32_t*& va, uint32_t*& kb, uint32_t*& vb, int n, uint32_t* hist,
-                                  uint32_t* offs, const uint32_t* skey) {
-  static const int shifts[5] = {0, 8, 16, 24, 0};
-  ppf_status s;
-  if ((s = cluster_sort(fr, ka, va, kb, vb, n, hist, offs, shifts, 4)) != PPF_OK) return s;
-  FRAME_LAUNCH(fr, k_frame_gather_u32, grid_for(n, 256), dim3(256), skey, va, n, ka);
-  return cluster_sort(fr, ka, va, kb, vb, n, hist, offs, shifts + 4, 1);
 }
 
 /* the smallest float tolerance whose grid holds an extent in CLU_AXIS cells */
@@ -132,7 +106,7 @@ ppf_status clu_begin(FrameRun& fr, CluWork& w, std::shared_ptr<DevBuf<float>>& b
   FRAME_LAUNCH(fr, k_clu_keys<NORMALS>, w.rows_grid, b256, w.d_tab, K, (uint32_t)N, w.d_grid, w.lkey, k1, w.skey, v1, w.parent, w.size);
   HIPCHK(hipGetLastError());
   w.ka = k1; w.va = v1; w.kb = k2; w.vb = v2;
-  return cluster_sort_segmented(fr, w.ka, w.va, w.kb, w.vb, n, w.hist, w.offs, w.skey);
+  return frame_sort_segmented(fr, w.ka, w.va, w.kb, w.vb, n, w.hist, w.offs, w.skey);
 }
 
 /* after the entry's k_*_runs (w.va: the sorted order; flags): the scan of the run starts and the table of occupied cells */
@@ -165,12 +139,12 @@ ppf_status clu_finish(FrameRun& fr, CluWork& w, std::shared_ptr<DevBuf<float>>& 
 
   FRAME_LAUNCH(fr, k_clu_valid, rows_grid, b256, d_tab, K, (uint32_t)N, root, size, (uint32_t)min_size, (uint32_t)max_size, ka, va, cnt);
   HIPCHK(hipGetLastError());
-  if ((s = cluster_sort_segmented(fr, ka, va, kb, vb, n, hist, offs, skey)) != PPF_OK) return s;
+  if ((s = frame_sort_segmented(fr, ka, va, kb, vb, n, hist, offs, skey)) != PPF_OK) return s;
   FRAME_LAUNCH(fr, k_clu_rank, rows_grid, b256, d_tab, K, (uint32_t)N, va, cnt, size, MC, rank, head);
   FRAME_LAUNCH(fr, k_clu_labels, rows_grid, b256, (uint32_t)N, skey, root, rank, d_labels, ka, va);
   HIPCHK(hipGetLastError());
   static const int shifts3[3] = {0, 8, 16};
-  if ((s = cluster_sort(fr, ka, va, kb, vb, n, hist, offs, shifts3, 3)) != PPF_OK) return s;
+  if ((s = frame_sort(fr, ka, va, kb, vb, n, hist, offs, shifts3, 3)) != PPF_OK) return s;
   FRAME_LAUNCH(fr, k_clu_gather, rows_grid, b256, d_tab, (uint32_t)N, ka, va, blk->p, blk->p + N * 6);
   FRAME_LAUNCH(fr, k_clu_reduce, rows_grid, b256, d_tab, (uint32_t)N, ka, va, cam, MC, acc);
   HIPCHK(hipGetLastError());
@@ -250,16 +224,57 @@ ppf_status clusters_enqueue(FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, c
   return clu_finish(fr, w, blk, p.min_size, p.max_size, intr, image_rows, image_cols, out, info, counts, 3, labels, st);
 }
 
-ppf_status clusters_run(const ppf_cloud* const* in, int K, const ppf_cluster_params& p, const double* intr, int image_rows, int image_cols,
-                        ppf_cloud** out, ppf_cluster_info* info, int32_t* counts, int32_t* const* labels, ppf_cluster_stats& st) {
-  FrameRun fr;
-  std::shared_ptr<DevBuf<float>> blk;
-  const ppf_status s = clusters_enqueue(fr, blk, in, K, p, intr, image_rows, image_cols, out, info, counts, labels, st);
-  /* kernels of a failed call may still run: wait before its scratch and the output block go back to the block cache,
-   * where another host thread could be handed them */
-  if (s != PPF_OK) (void)hipDeviceSynchronize();
-  return s;
+/* The body of the C entries ppf_prep_clusters and ppf_prep_regions: the outputs cleared, the argument checks in the order the
+ * entries document, one FrameRun and one output block around `enqueue`, the outputs cleared again on an error.
+ * max_shown: the entry's max_clusters / max_regions clamped to 1 .. PPF_CLUSTER_MAX_CLUSTERS (1: no params), the length of a
+ * cloud's part of out and info; stride: the words a cloud has in counts.  check_params() -> ppf_status;
+ * enqueue(fr, blk, st) -> ppf_status runs the call up to its results */
+template <class Check, class Enqueue>
+ppf_status clu_entry(const char* who, const ppf_cloud* const* in, int n_clouds, int max_shown, int stride, const double* intr, int image_rows,
+                     int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts, ppf_cluster_stats* stats, Check check_params,
+                     Enqueue enqueue) {
+  const auto t0 = std::chrono::steady_clock::now();
+  ppf_cluster_stats local;
+  ppf_cluster_stats& st = stats ? *stats : local;
+  std::memset(&st, 0, sizeof(st));
+  const bool count_ok = n_clouds >= 0 && n_clouds <= FRAME_MAX_BOXES;
+  const size_t slots = count_ok ? (size_t)n_clouds * (size_t)max_shown : 0;
+  auto clear = [&]() {
+    for (size_t k = 0; out && k < slots; k++) out[k] = nullptr;
+    if (info && slots) std::memset(info, 0, slots * sizeof(ppf_cluster_info));
+    if (counts && count_ok && n_clouds) std::memset(counts, 0, (size_t)n_clouds * stride * sizeof(int32_t));
+  };
+  clear();
+  if (!count_ok) return fail(PPF_ERR_INVALID, "%s: n_clouds is %d (0..%d)", who, n_clouds, FRAME_MAX_BOXES);
+  if (!in || !out || !info || !counts) return fail(PPF_ERR_INVALID, "%s: in, out, info and counts must not be NULL", who);
+  ppf_status s = check_params();
+  if (s != PPF_OK) return s;
+  if (intr) {
+    for (int k = 0; k < 4; k++)
+      if (!std::isfinite(intr[k])) return fail(PPF_ERR_INVALID, "%s: the intrinsics are not finite", who);
+    if (image_rows < 1 || image_cols < 1) return fail(PPF_ERR_INVALID, "%s: the image is %d x %d", who, image_rows, image_cols);
+  }
+  for (int i = 0; i < n_clouds; i++)
+    if (!in[i]) return fail(PPF_ERR_INVALID, "%s: in[%d] is NULL", who, i);
+  if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
+  st.n_clouds = n_clouds;
+  if (n_clouds > 0) {
+    FrameRun fr;
+    std::shared_ptr<DevBuf<float>> blk;
+    s = enqueue(fr, blk, st);
+    /* kernels of a failed call may still run: wait before its scratch and the output block go back to the block cache,
+     * where another host thread could be handed them */
+    if (s != PPF_OK) (void)hipDeviceSynchronize();
+  }
+  if (s != PPF_OK) {
+    clear();
+    std::memset(&st, 0, sizeof(st));
+    return s;
+  }
+  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PPF_OK;
 }
+inline int clu_max_shown(int max_components) { return std::min(std::max(max_components, 1), PPF_CLUSTER_MAX_CLUSTERS); }
 
 }  // namespace
 
@@ -278,39 +293,12 @@ ppf_status ppf_prep_clusters(const ppf_cloud* const* in, int n_clouds, const ppf
                              int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts, int32_t* const* labels,
                              ppf_cluster_stats* stats) {
   static const char* who = "ppf_prep_clusters";
-  const auto t0 = std::chrono::steady_clock::now();
-  ppf_cluster_stats local;
-  ppf_cluster_stats& st = stats ? *stats : local;
-  std::memset(&st, 0, sizeof(st));
-  const bool count_ok = n_clouds >= 0 && n_clouds <= FRAME_MAX_BOXES;
-  const size_t slots = count_ok ? (size_t)n_clouds * (size_t)(p ? std::min(std::max(p->max_clusters, 1), PPF_CLUSTER_MAX_CLUSTERS) : 1) : 0;
-  auto clear = [&]() {
-    for (size_t k = 0; out && k < slots; k++) out[k] = nullptr;
-    if (info && slots) std::memset(info, 0, slots * sizeof(ppf_cluster_info));
-    if (counts && count_ok && n_clouds) std::memset(counts, 0, (size_t)n_clouds * 3 * sizeof(int32_t));
-  };
-  clear();
-  if (!count_ok) return fail(PPF_ERR_INVALID, "%s: n_clouds is %d (0..%d)", who, n_clouds, FRAME_MAX_BOXES);
-  if (!in || !out || !info || !counts) return fail(PPF_ERR_INVALID, "%s: in, out, info and counts must not be NULL", who);
-  ppf_status s = cluster_params_check(who, p);
-  if (s != PPF_OK) return s;
-  if (intr) {
-    for (int k = 0; k < 4; k++)
-      if (!std::isfinite(intr[k])) return fail(PPF_ERR_INVALID, "%s: the intrinsics are not finite", who);
-    if (image_rows < 1 || image_cols < 1) return fail(PPF_ERR_INVALID, "%s: the image is %d x %d", who, image_rows, image_cols);
-  }
-  for (int i = 0; i < n_clouds; i++)
-    if (!in[i]) return fail(PPF_ERR_INVALID, "%s: in[%d] is NULL", who, i);
-  if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
-  st.n_clouds = n_clouds;
-  if (n_clouds > 0) s = clusters_run(in, n_clouds, *p, intr, image_rows, image_cols, out, info, counts, labels, st);
-  if (s != PPF_OK) {
-    clear();
-    std::memset(&st, 0, sizeof(st));
-    return s;
-  }
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PPF_OK;
+  return clu_entry(
+      who, in, n_clouds, p ? clu_max_shown(p->max_clusters) : 1, 3, intr, image_rows, image_cols, out, info, counts, stats,
+      [&]() { return cluster_params_check(who, p); },
+      [&](FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, ppf_cluster_stats& st) {
+        return clusters_enqueue(fr, blk, in, n_clouds, *p, intr, image_rows, image_cols, out, info, counts, labels, st);
+      });
 }
 
 }  // extern "C"

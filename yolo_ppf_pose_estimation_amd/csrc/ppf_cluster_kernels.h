@@ -1,8 +1,9 @@
 /*
  * ppf_cluster_kernels.h — the kernels of ppf_prep_clusters: Euclidean cluster extraction, the connected components of
  * "two rows are no farther apart than the tolerance", of K <= 256 clouds at once (host side:
- * ppf_cluster_host.h).  Included by ppf_hip.hip after ppf_prep_kernels.h (frame_find, prep_finite3) and
- * ppf_sample_kernels.h (float_to_ordered, the radix-sort passes).
+ * ppf_cluster_host.h).  Included by ppf_hip.hip after ppf_prep_kernels.h (frame_find, prep_finite3),
+ * ppf_sample_kernels.h (float_to_ordered, the radix-sort passes) and ppf_label_kernels.h (the union-find uf_find / uf_unite,
+ * uf_root, cells_lower_bound, wave_max_by_key).
  *
  * The specification is closed -- the link predicate is fp64, evaluated as written, a component is a set, its rank is by
  * integers -- so every output byte equals tests/cluster_oracle.py whatever the order the unions happen in.  The clouds are
@@ -11,16 +12,13 @@
  *   grid          cells of edge h = CLU_CELL * tolerance, CLU_CELL a little below 1 / sqrt(3): two rows of one cell are
  *                 always linked, two linked rows are at most two cells apart on an axis (DESIGN.md §20 has the margins).
  *                 Rows are sorted by (segment, cell), stable, so a cell is a run whose first row has its smallest index.
- *   k_clu_link    the hot pass, one wave per occupied cell.  A lock-free union-find over row indices: a parent is always
- *                 a smaller index, so a root is its component's smallest row.  The cell's rows are united with its first
- *                 row; then, for each of the 62 neighbour cells with a larger key (found by binary search in the table of
- *                 occupied cells), lanes own rows of the neighbour and test them against the cell's rows, staged in LDS as
- *                 fp64 and read by broadcast.  A cell pair stops at its first hit: both cells are one set each, so one
- *                 union per pair of cells suffices.
- *                 Inside that launch every read of parent[] is an agent-scope relaxed atomic load (L1 is per CU: a plain
- *                 load may return a stale line for ever), every write a compare-and-swap on a root, or the atomic store of
- *                 a grandparent (path halving).  No workgroup waits for another: the only retry loop is a failed
- *                 compare-and-swap, which means another thread's succeeded.
+ *   k_clu_link    the hot pass, one wave per occupied cell.  The union-find runs over row indices, so a root is its
+ *                 component's smallest row.  The cell's rows are united with its first row; then, for each of the 62
+ *                 neighbour cells with a larger key (clu_neighbour: found by binary search in the table of occupied cells),
+ *                 lanes own rows of the neighbour and test them against the cell's rows, staged in LDS as fp64 and read by
+ *                 broadcast.  A cell pair stops at its first hit: both cells are one set each, so one union per pair of
+ *                 cells suffices.  Inside that launch parent[] is read and written by uf_find / uf_unite only
+ *                 (ppf_label_kernels.h has the memory rules and why no loop waits).
  */
 #ifndef PPF_CLUSTER_KERNELS_H
 #define PPF_CLUSTER_KERNELS_H
@@ -139,6 +137,14 @@ __global__ __launch_bounds__(CLU_BLOCK) void k_clu_keys(const CluSeg* __restrict
   size[g] = 0u;
 }
 
+/* does sorted row i (row g = order[i]) start a run of equal (segment, cell)? */
+__device__ __forceinline__ uint32_t clu_starts_run(const uint32_t* __restrict__ order, const uint32_t* __restrict__ lkey,
+                                                   const uint32_t* __restrict__ skey, uint32_t i, uint32_t g) {
+  if (i == 0) return 1u;
+  const uint32_t q = order[i - 1];
+  return (lkey[q] != lkey[g] || skey[q] != skey[g]) ? 1u : 0u;
+}
+
 /* after the sort by (segment, cell): pts[i] = {x, y, z, bits of g} of the i-th row, flags[i] = it starts a run;
  * flags[N] = 0 closes the scan.  grid: rows + 1 */
 __global__ __launch_bounds__(CLU_BLOCK) void k_clu_runs(const CluSeg* __restrict__ tab, int K, uint32_t N, const uint32_t* __restrict__ order,
@@ -150,12 +156,7 @@ __global__ __launch_bounds__(CLU_BLOCK) void k_clu_runs(const CluSeg* __restrict
   const uint32_t g = order[i];
   const float* p = clu_row(tab[skey[g]], g);
   pts[i] = make_float4(p[0], p[1], p[2], __uint_as_float(g));
-  uint32_t f = 1u;
-  if (i > 0) {
-    const uint32_t q = order[i - 1];
-    f = (lkey[q] != lkey[g] || skey[q] != skey[g]) ? 1u : 0u;
-  }
-  flags[i] = f;
+  flags[i] = clu_starts_run(order, lkey, skey, i, g);
 }
 
 /* the table of occupied cells, ascending: ckey[c] = segment << 32 | cell key, cstart[c] = its first sorted row;
@@ -173,36 +174,26 @@ __global__ __launch_bounds__(CLU_BLOCK) void k_clu_cells(uint32_t N, const uint3
   cstart[c] = i;
 }
 
-/* ---- the union-find.  Inside k_clu_link parent[] is read and written by these three only ---- */
-__device__ __forceinline__ uint32_t clu_ld(uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void clu_st(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-/* the root of x as far as this thread can see; every step goes to a smaller index, so it ends.  A row that is not a root
- * never becomes one again and its parent only ever moves to another row of its set: storing a grandparent is safe
- * whatever other threads do */
-__device__ __forceinline__ uint32_t clu_find(uint32_t* parent, uint32_t x) {
-  for (;;) {
-    const uint32_t p = clu_ld(parent + x);
-    if (p == x) return x;
-    const uint32_t gp = clu_ld(parent + p);
-    if (gp == p) return p;
-    clu_st(parent + x, gp);
-    x = gp;
-  }
-}
-/* the larger root is hung under the smaller.  A failed compare-and-swap: another thread hung that root first */
-__device__ __forceinline__ void clu_unite(uint32_t* parent, uint32_t a, uint32_t b) {
-  for (;;) {
-    a = clu_find(parent, a);
-    b = clu_find(parent, b);
-    if (a == b) return;
-    if (a < b) { const uint32_t t = a; a = b; b = t; }
-    if (atomicCAS(parent + a, a, b) == a) return;
-  }
-}
-
 __device__ __forceinline__ bool clu_linked(double ax, double ay, double az, double bx, double by, double bz, double tol2) {
   const double dx = ax - bx, dy = ay - by, dz = az - bz;
   return ((dx * dx + dy * dy) + dz * dz) <= tol2;
+}
+
+/* Of the 62 cells within two cells per axis of cell c (key `self`) whose key is larger, lane t < 62 looks for the t-th: its
+ * sorted rows are *nbs .. *nbe, none (0, 0) where the table of cells does not hold it */
+__device__ __forceinline__ void clu_neighbour(const unsigned long long* __restrict__ ckey, const uint32_t* __restrict__ cstart, uint32_t c,
+                                              uint32_t nc, unsigned long long self, int lane, uint32_t* nbs, uint32_t* nbe) {
+  *nbs = 0;
+  *nbe = 0;
+  if (lane < 62) {
+    const int o = 63 + lane; /* 62 is the cell itself */
+    const int cx = (int)((self >> 20) & 1023u) + o / 25 - 2, cy = (int)((self >> 10) & 1023u) + (o / 5) % 5 - 2, cz = (int)(self & 1023u) + o % 5 - 2;
+    if (cx >= 0 && cx < CLU_AXIS && cy >= 0 && cy < CLU_AXIS && cz >= 0 && cz < CLU_AXIS) {
+      const unsigned long long want = (self & 0xFFFFFFFF00000000ull) | (unsigned long long)(((uint32_t)cx << 20) | ((uint32_t)cy << 10) | (uint32_t)cz);
+      const uint32_t lo = cells_lower_bound(ckey, c + 1, nc, want); /* a larger key lies past c */
+      if (lo < nc && ckey[lo] == want) { *nbs = cstart[lo]; *nbe = cstart[lo + 1]; }
+    }
+  }
 }
 
 /* one wave per occupied cell.  grid: rows (an upper bound of the cells; workgroups past n_cells[0] leave) */
@@ -217,26 +208,13 @@ __global__ __launch_bounds__(64) void k_clu_link(const float4* __restrict__ pts,
   const int lane = threadIdx.x;
   const uint32_t a0 = cstart[c], a1 = cstart[c + 1];
 
-  /* the 62 cells within two cells per axis whose key is larger: lane t looks for the t-th */
-  uint32_t nbs = 0, nbe = 0;
-  if (lane < 62) {
-    const int o = 63 + lane; /* 62 is the cell itself */
-    const int cx = (int)((self >> 20) & 1023u) + o / 25 - 2, cy = (int)((self >> 10) & 1023u) + (o / 5) % 5 - 2, cz = (int)(self & 1023u) + o % 5 - 2;
-    if (cx >= 0 && cx < CLU_AXIS && cy >= 0 && cy < CLU_AXIS && cz >= 0 && cz < CLU_AXIS) {
-      const unsigned long long want = (self & 0xFFFFFFFF00000000ull) | (unsigned long long)(((uint32_t)cx << 20) | ((uint32_t)cy << 10) | (uint32_t)cz);
-      uint32_t lo = c + 1, hi = nc; /* the first cell in (c, nc) whose key is >= want */
-      while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (ckey[mid] < want) lo = mid + 1; else hi = mid;
-      }
-      if (lo < nc && ckey[lo] == want) { nbs = cstart[lo]; nbe = cstart[lo + 1]; }
-    }
-  }
+  uint32_t nbs, nbe;
+  clu_neighbour(ckey, cstart, c, nc, self, lane, &nbs, &nbe);
   unsigned long long todo = __ballot(nbe > nbs);
 
   /* the cell is one set: its first row has its smallest index */
   const uint32_t first = __float_as_uint(pts[a0].w);
-  for (uint32_t i = a0 + 1 + (uint32_t)lane; i < a1; i += 64) clu_unite(parent, first, __float_as_uint(pts[i].w));
+  for (uint32_t i = a0 + 1 + (uint32_t)lane; i < a1; i += 64) uf_unite(parent, first, __float_as_uint(pts[i].w));
 
   for (uint32_t ta = a0; ta < a1 && todo; ta += CLU_TILE) { /* todo is the same in every lane */
     const int nt = (int)min((uint32_t)CLU_TILE, a1 - ta);
@@ -265,7 +243,7 @@ __global__ __launch_bounds__(64) void k_clu_link(const float4* __restrict__ pts,
       }
       if (found) {
         todo &= ~(1ull << t);
-        if (lane == 0) clu_unite(parent, first, __float_as_uint(pts[bs].w));
+        if (lane == 0) uf_unite(parent, first, __float_as_uint(pts[bs].w));
       }
     }
   }
@@ -279,8 +257,7 @@ __global__ __launch_bounds__(CLU_BLOCK) void k_clu_flatten(uint32_t N, const uin
   if (g >= N) return;
   uint32_t r = CLU_NO_KEY;
   if (lkey[g] != CLU_NO_KEY) {
-    r = g;
-    for (uint32_t p = parent[r]; p != r; p = parent[r]) r = p;
+    r = uf_root(parent, g);
     atomicAdd(&size[r], 1u);
   }
   root[g] = r;
@@ -356,7 +333,7 @@ __global__ __launch_bounds__(CLU_BLOCK) void k_clu_gather(const CluSeg* __restri
 
 /* acc[segment][rank] = the maxima of {~lo, hi, ~umin, umax + 1, ~vmin, vmax + 1} over a cluster's rows, zero the identity of
  * all ten: ordered words and integers only.  The image words come from the rows with z > 0 (intr == NULL: none).  A wave
- * that lies in one cluster, as most do, combines by shuffles and adds once.  grid: rows */
+ * that lies in one cluster, as most do, combines by shuffles and adds once (wave_max_by_key).  grid: rows */
 struct CluIntr {
   double fx, fy, ppx, ppy;
   int rows, cols, on;
@@ -388,20 +365,8 @@ __global__ __launch_bounds__(CLU_BLOCK) void k_clu_reduce(const CluSeg* __restri
       v[6] = ~pu; v[7] = pu + 1u; v[8] = ~pv; v[9] = pv + 1u;
     }
   }
-  const unsigned long long live = __ballot(in);
-  if (!live) return;
-  const uint32_t key0 = (uint32_t)__shfl((int)key, __ffsll((long long)live) - 1);
-  if (__all(!in || key == key0)) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-      for (int k = 0; k < CLU_ACC; k++) v[k] = max(v[k], (uint32_t)__shfl_down((int)v[k], o));
-    }
-    if ((threadIdx.x & 63) != 0) return;
-  } else if (!in) {
-    return;
-  }
-  const uint32_t k1 = (threadIdx.x & 63) == 0 ? key0 : key; /* lane 0 of a one-cluster wave may itself be in none */
+  uint32_t k1 = key;
+  if (!wave_max_by_key(in, k1, v)) return;
   uint32_t* dst = acc + ((size_t)(k1 >> 8) * max_clusters + (k1 & 255u)) * CLU_ACC;
 #pragma unroll
   for (int k = 0; k < CLU_ACC; k++)

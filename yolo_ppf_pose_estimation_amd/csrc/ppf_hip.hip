@@ -24,7 +24,7 @@
  *   kernels   ppf_train_kernels.h (table build)  ppf_sample_kernels.h (A2)  ppf_match_kernels.h (k_frames / k_pairs /
  *             k_group / k_vote)  ppf_pose_kernels.h (k_finalize, k_rank, clustering)  ppf_icp_kernels.h  ppf_prep_kernels.h
  *             ppf_depth_kernels.h  ppf_depth_normals_kernels.h  ppf_verify_kernels.h  ppf_render_kernels.h  ppf_select_kernels.h  ppf_refine_kernels.h
- *             ppf_register_kernels.h  ppf_plane_kernels.h  ppf_cluster_kernels.h  ppf_region_kernels.h  ppf_filter_kernels.h
+ *             ppf_register_kernels.h  ppf_plane_kernels.h  ppf_label_kernels.h  ppf_cluster_kernels.h  ppf_region_kernels.h  ppf_filter_kernels.h
  *             ppf_segment_kernels.h
  *   host      ppf_device_mem.h (errors, block cache)  ppf_host_common.h (scans, sorts, model / workspace structs)
  *             ppf_model_host.h  ppf_match_host.h  ppf_batch_host.h  ppf_icp_host.h  ppf_prep_host.h (the segmented
@@ -73,6 +73,7 @@
 #include "ppf_refine_kernels.h" /* k_rfn_refine */
 #include "ppf_register_kernels.h" /* k_reg_rays, k_reg_clear, k_reg_draw, k_reg_resolve */
 #include "ppf_plane_kernels.h" /* k_pln_hyp, k_pln_count, k_pln_best, k_pln_sum / _finish, k_pln_flags, k_pln_compact, k_pln_gather */
+#include "ppf_label_kernels.h" /* uf_find, uf_unite, uf_root, cells_lower_bound, wave_max_by_key: no kernel */
 #include "ppf_cluster_kernels.h" /* k_clu_bounds, k_clu_grid, k_clu_keys, k_clu_runs, k_clu_cells, k_clu_link, k_clu_flatten ... k_clu_reduce */
 #include "ppf_segment_kernels.h" /* k_seg_classify, k_seg_tile, k_seg_merge, k_seg_flatten, k_seg_valid, k_seg_rank, k_seg_labels */
 #include "ppf_region_kernels.h" /* k_reg_runs, k_reg_link, k_reg_flatten, k_reg_attach */

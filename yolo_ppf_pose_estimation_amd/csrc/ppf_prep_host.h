@@ -1,7 +1,7 @@
 /*
  * ppf_prep_host.h — host side of the stages that produce the matcher's input (row N4): the device-resident ppf_cloud,
  * the segmented stage functions (crop, voxel grid, outlier removal, normals, edges, to-Mat over K segments of one
- * concatenated cloud; frame_knn, frame_scan and frame_compact beneath them), the C-ABI entry points ppf_cloud_* and
+ * concatenated cloud; frame_knn, frame_scan, frame_sort and frame_compact beneath them), the C-ABI entry points ppf_cloud_* and
  * ppf_prep_* (each stage function with one segment) and the resident ppf_match_clouds / ppf_icp_refine_clouds.
  * ppf_prep_frame chains the same functions for all boxes of a frame (ppf_frame_host.h).  Kernels: ppf_prep_kernels.h.
  * Included by ppf_hip.hip (one translation unit: shares DevBuf, fail(), HIPCHK and the scan and radix-sort kernels).
@@ -91,8 +91,10 @@ bool crop_planes(const int* box_xywh, const float* depth, int depth_rows, int de
 }
 
 /* ---- the segmented stages ---------------------------------------------------------------------------------------- */
-/* scratch of one call, from the block cache; it lives until the call returns (after the last read-back) */
+/* one call's launches, counted, on one stream (the null stream unless the entry has a stream argument), and its scratch,
+ * from the block cache; it lives until the call returns (after the last read-back) */
 struct FrameRun {
+  hipStream_t st = nullptr;
   int launches = 0, syncs = 0;
   struct Holder {
     virtual ~Holder() {}
@@ -110,7 +112,7 @@ struct FrameRun {
     keep.push_back(std::move(h));
     return PPF_OK;
   }
-  /* a blocking read-back (counted) */
+  /* a blocking read-back (counted), on the null stream: the stages that run on a caller's stream never call it */
   ppf_status read(void* dst, const void* src, size_t bytes) {
     syncs++;
     HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
@@ -118,10 +120,10 @@ struct FrameRun {
   }
 };
 
-#define FRAME_LAUNCH(fr, kern, grid, block, ...) \
-  do {                                           \
-    kern<<<(grid), (block)>>>(__VA_ARGS__);      \
-    (fr).launches++;                             \
+#define FRAME_LAUNCH(fr, kern, grid, block, ...)        \
+  do {                                                  \
+    kern<<<(grid), (block), 0, (fr).st>>>(__VA_ARGS__); \
+    (fr).launches++;                                    \
   } while (0)
 
 /* exclusive scan of n u32 in five launches whatever n is (device_exclusive_scan picks its launches by n and waits for
@@ -140,6 +142,34 @@ ppf_status frame_scan(FrameRun& fr, const uint32_t* in, uint32_t* out, size_t n)
   FRAME_LAUNCH(fr, k_scan_add, grid_for(n, 256), dim3(256), out, s1x, n);
   HIPCHK(hipGetLastError());
   return PPF_OK;
+}
+
+/* the frame-level radix sort: stable LSD passes over the digits at `shifts` of keys ka (values va), seven launches a pass
+ * whatever n is (hist and offs: 256 words per RS_BLOCK rows each); the sorted arrays end in ka / va */
+ppf_status frame_sort(FrameRun& fr, uint32_t*& ka, uint32_t*& va, uint32_t*& kb, uint32_t*& vb, int n, uint32_t* hist, uint32_t* offs,
+                      const int* shifts, int passes) {
+  const int nblk = (n + RS_BLOCK - 1) / RS_BLOCK;
+  ppf_status s;
+  for (int pass = 0; pass < passes; pass++) {
+    FRAME_LAUNCH(fr, k_rs_hist, dim3(nblk), dim3(RS_BLOCK), ka, n, shifts[pass], nblk, hist);
+    HIPCHK(hipGetLastError());
+    if ((s = frame_scan(fr, hist, offs, (size_t)256 * nblk)) != PPF_OK) return s;
+    FRAME_LAUNCH(fr, k_rs_scatter, dim3(nblk), dim3(RS_BLOCK), ka, va, n, shifts[pass], nblk, offs, kb, vb);
+    HIPCHK(hipGetLastError());
+    std::swap(ka, kb);
+    std::swap(va, vb);
+  }
+  return PPF_OK;
+}
+/* by a 32-bit key, then by segment (skey[row], below 256): a segment's rows end up together, in key order, equal keys in row
+ * order.  Five passes and one gather */
+ppf_status frame_sort_segmented(FrameRun& fr, uint32_t*& ka, uint32_t*& va, uint32_t*& kb, uint32_t*& vb, int n, uint32_t* hist,
+                                uint32_t* offs, const uint32_t* skey) {
+  static const int shifts[5] = {0, 8, 16, 24, 0};
+  ppf_status s;
+  if ((s = frame_sort(fr, ka, va, kb, vb, n, hist, offs, shifts, 4)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_frame_gather_u32, grid_for(n, 256), dim3(256), skey, va, n, ka);
+  return frame_sort(fr, ka, va, kb, vb, n, hist, offs, shifts + 4, 1);
 }
 
 /* a segmented cloud on the device: K segments, contiguous and in order, in the first rows of `cap` (>= their total);
@@ -210,21 +240,12 @@ ppf_status frame_voxel(FrameRun& fr, const SegCloud& in, double leaf, ppf_cloud*
   FRAME_LAUNCH(fr, k_frame_voxel_dims, dim3(1), dim3(FRAME_MAX_BOXES), mm, fin, K, 1.0f / (float)leaf, dims, err);
   FRAME_LAUNCH(fr, k_frame_voxel_keys, grid_for(C, 256), dim3(256), in.rows, C, in.seg, K, dims, k1, lkey, skey, v1);
   HIPCHK(hipGetLastError());
-  /* stable LSD passes: the local cell index (< 2^31; non-finite points ~0), then the segment */
+  /* by the local cell index (< 2^31; non-finite points ~0), then by the segment */
   const int nblk = (C + RS_BLOCK - 1) / RS_BLOCK;
   uint32_t *hist, *offs;
   if ((s = fr.get((size_t)256 * nblk, &hist)) != PPF_OK || (s = fr.get((size_t)256 * nblk, &offs)) != PPF_OK) return s;
   uint32_t *ka = k1, *va = v1, *kb = k2, *vb = v2;
-  for (int pass = 0; pass < 5; pass++) {
-    const int shift = pass < 4 ? pass * 8 : 0;
-    if (pass == 4) FRAME_LAUNCH(fr, k_frame_gather_u32, grid_for(C, 256), dim3(256), skey, va, C, ka);
-    FRAME_LAUNCH(fr, k_rs_hist, dim3(nblk), dim3(RS_BLOCK), ka, C, shift, nblk, hist);
-    HIPCHK(hipGetLastError());
-    if ((s = frame_scan(fr, hist, offs, (size_t)256 * nblk)) != PPF_OK) return s;
-    FRAME_LAUNCH(fr, k_rs_scatter, dim3(nblk), dim3(RS_BLOCK), ka, va, C, shift, nblk, offs, kb, vb);
-    HIPCHK(hipGetLastError());
-    std::swap(ka, kb); std::swap(va, vb);
-  }
+  if ((s = frame_sort_segmented(fr, ka, va, kb, vb, C, hist, offs, skey)) != PPF_OK) return s;
   FRAME_LAUNCH(fr, k_frame_voxel_runs, grid_for((size_t)C + 1, 256), dim3(256), va, lkey, skey, C, rflags);
   HIPCHK(hipGetLastError());
   if ((s = frame_scan(fr, rflags, runid, (size_t)C + 1)) != PPF_OK) return s;

@@ -1,7 +1,7 @@
 /*
  * ppf_region_host.h — host side of ppf_prep_regions: the smooth surface regions of up to 256 clouds in one pass (DESIGN.md
  * §22).  Kernels: ppf_region_kernels.h.  Included by ppf_hip.hip after ppf_cluster_host.h, whose clu_begin, clu_cells and
- * clu_finish it runs around its own four kernels.
+ * clu_finish it runs around its own four kernels, inside that file's entry body (clu_entry).
  *
  * Per call: clu_begin<true> (k_clu_bounds, k_clu_grid and k_clu_keys over the eligible rows, the sort by (segment, cell)),
  * k_reg_runs, clu_cells, k_reg_link, k_reg_flatten, k_reg_attach, clu_finish: 111 launches whatever the clouds hold -- one more
@@ -66,45 +66,12 @@ ppf_status ppf_prep_regions(const ppf_cloud* const* in, int n_clouds, const ppf_
                             int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts, int32_t* const* labels,
                             ppf_cluster_stats* stats) {
   static const char* who = "ppf_prep_regions";
-  const auto t0 = std::chrono::steady_clock::now();
-  ppf_cluster_stats local;
-  ppf_cluster_stats& st = stats ? *stats : local;
-  std::memset(&st, 0, sizeof(st));
-  const bool count_ok = n_clouds >= 0 && n_clouds <= FRAME_MAX_BOXES;
-  const size_t slots = count_ok ? (size_t)n_clouds * (size_t)(p ? std::min(std::max(p->max_regions, 1), PPF_CLUSTER_MAX_CLUSTERS) : 1) : 0;
-  auto clear = [&]() {
-    for (size_t k = 0; out && k < slots; k++) out[k] = nullptr;
-    if (info && slots) std::memset(info, 0, slots * sizeof(ppf_cluster_info));
-    if (counts && count_ok && n_clouds) std::memset(counts, 0, (size_t)n_clouds * 4 * sizeof(int32_t));
-  };
-  clear();
-  if (!count_ok) return fail(PPF_ERR_INVALID, "%s: n_clouds is %d (0..%d)", who, n_clouds, FRAME_MAX_BOXES);
-  if (!in || !out || !info || !counts) return fail(PPF_ERR_INVALID, "%s: in, out, info and counts must not be NULL", who);
-  ppf_status s = region_params_check(who, p);
-  if (s != PPF_OK) return s;
-  if (intr) {
-    for (int k = 0; k < 4; k++)
-      if (!std::isfinite(intr[k])) return fail(PPF_ERR_INVALID, "%s: the intrinsics are not finite", who);
-    if (image_rows < 1 || image_cols < 1) return fail(PPF_ERR_INVALID, "%s: the image is %d x %d", who, image_rows, image_cols);
-  }
-  for (int i = 0; i < n_clouds; i++)
-    if (!in[i]) return fail(PPF_ERR_INVALID, "%s: in[%d] is NULL", who, i);
-  if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
-  st.n_clouds = n_clouds;
-  if (n_clouds > 0) {
-    FrameRun fr;
-    std::shared_ptr<DevBuf<float>> blk;
-    s = regions_enqueue(fr, blk, in, n_clouds, *p, intr, image_rows, image_cols, out, info, counts, labels, st);
-    /* kernels of a failed call may still run: wait before its scratch and the output block go back to the block cache */
-    if (s != PPF_OK) (void)hipDeviceSynchronize();
-  }
-  if (s != PPF_OK) {
-    clear();
-    std::memset(&st, 0, sizeof(st));
-    return s;
-  }
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PPF_OK;
+  return clu_entry(
+      who, in, n_clouds, p ? clu_max_shown(p->max_regions) : 1, 4, intr, image_rows, image_cols, out, info, counts, stats,
+      [&]() { return region_params_check(who, p); },
+      [&](FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, ppf_cluster_stats& st) {
+        return regions_enqueue(fr, blk, in, n_clouds, *p, intr, image_rows, image_cols, out, info, counts, labels, st);
+      });
 }
 
 }  // extern "C"

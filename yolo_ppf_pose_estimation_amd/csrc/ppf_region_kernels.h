@@ -2,7 +2,8 @@
  * ppf_region_kernels.h — the kernels ppf_prep_regions adds to ppf_prep_clusters': smooth surface regions, the connected
  * components of "two smooth rows are near and their normals agree", with the border rows attached afterwards (DESIGN.md §22;
  * host side: ppf_region_host.h).  Included by ppf_hip.hip after ppf_cluster_kernels.h: the grid, the sorts, the table of cells,
- * the union-find (clu_ld / clu_st / clu_find / clu_unite) and the whole tail from k_clu_valid on are that file's.
+ * the neighbour-cell lookup (clu_neighbour) and the whole tail from k_clu_valid on are that file's; the union-find (uf_find /
+ * uf_unite, uf_root) and cells_lower_bound are ppf_label_kernels.h's.
  *
  *   k_reg_runs     the sorted rows as two float4: {x, y, z, index} and {nx, ny, nz, kind}
  *   k_reg_link     the hot pass, one wave per occupied cell.  §20's guarantee (2) holds (linked rows are at most two cells
@@ -12,7 +13,7 @@
  *   k_reg_flatten  after the launch boundary, plain loads: every smooth row its root, the sizes counted
  *   k_reg_attach   every border row to the nearest smooth row it can attach to
  * (ppf_register_kernels.h has k_reg_ kernels and REG_ constants of its own, the depth registration's; the helpers here are
- * rgn_ / RGN_.)  The memory rules inside k_reg_link are k_clu_link's: parent[] is read and written by clu_ld / clu_st / clu_unite only.
+ * rgn_ / RGN_.)  The memory rules inside k_reg_link are k_clu_link's: parent[] is read and written by uf_find / uf_unite only.
  */
 #ifndef PPF_REGION_KERNELS_H
 #define PPF_REGION_KERNELS_H
@@ -40,17 +41,12 @@ __global__ __launch_bounds__(CLU_BLOCK) void k_reg_runs(const CluSeg* __restrict
   if (lkey[g] != CLU_NO_KEY) kind = sg.curv[g - sg.off] <= curv_thr ? RGN_SMOOTH : RGN_BORDER;
   pts[i] = make_float4(p[0], p[1], p[2], __uint_as_float(g));
   nrm[i] = make_float4(p[3], p[4], p[5], __uint_as_float(kind));
-  uint32_t f = 1u;
-  if (i > 0) {
-    const uint32_t q = order[i - 1];
-    f = (lkey[q] != lkey[g] || skey[q] != skey[g]) ? 1u : 0u;
-  }
-  flags[i] = f;
+  flags[i] = clu_starts_run(order, lkey, skey, i, g);
 }
 
 /* The staged tile of the wave's cell: xyz as fp64 (what near() takes), the normal (widened where agree() is reached, for the
  * few pairs that are near), g[] the row's index (CLU_NO_KEY: not smooth, no partner of a link), r[] a row that was in the
- * staged row's set when it was read (clu_find's answer).  Sets only ever merge, so two staged rows of equal r[] are in one set
+ * staged row's set when it was read (uf_find's answer).  Sets only ever merge, so two staged rows of equal r[] are in one set
  * for good. */
 struct RgnTile {
   double p[CLU_TILE * 3];
@@ -82,7 +78,7 @@ __device__ __forceinline__ void rgn_pass(const RgnTile& t, int nt, const float4*
       if (!rgn_agree((double)t.n[i * 3], (double)t.n[i * 3 + 1], (double)t.n[i * 3 + 2], mx, my, mz, cosv, unoriented)) continue;
       const uint32_t ri = t.r[i];
       if (ri == known) continue;
-      clu_unite(parent, gi, gj);
+      uf_unite(parent, gi, gj);
       known = ri;
     }
   }
@@ -103,21 +99,8 @@ __global__ __launch_bounds__(64) void k_reg_link(const float4* __restrict__ pts,
   const int lane = threadIdx.x;
   const uint32_t a0 = cstart[c], a1 = cstart[c + 1];
 
-  /* the 62 cells within two cells per axis whose key is larger: lane l looks for the l-th (as k_clu_link does) */
-  uint32_t nbs = 0, nbe = 0;
-  if (lane < 62) {
-    const int o = 63 + lane; /* 62 is the cell itself */
-    const int cx = (int)((self >> 20) & 1023u) + o / 25 - 2, cy = (int)((self >> 10) & 1023u) + (o / 5) % 5 - 2, cz = (int)(self & 1023u) + o % 5 - 2;
-    if (cx >= 0 && cx < CLU_AXIS && cy >= 0 && cy < CLU_AXIS && cz >= 0 && cz < CLU_AXIS) {
-      const unsigned long long want = (self & 0xFFFFFFFF00000000ull) | (unsigned long long)(((uint32_t)cx << 20) | ((uint32_t)cy << 10) | (uint32_t)cz);
-      uint32_t lo = c + 1, hi = nc; /* the first cell in (c, nc) whose key is >= want */
-      while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (ckey[mid] < want) lo = mid + 1; else hi = mid;
-      }
-      if (lo < nc && ckey[lo] == want) { nbs = cstart[lo]; nbe = cstart[lo + 1]; }
-    }
-  }
+  uint32_t nbs, nbe;
+  clu_neighbour(ckey, cstart, c, nc, self, lane, &nbs, &nbe);
   const unsigned long long todo = __ballot(nbe > nbs);
 
   for (uint32_t ta = a0; ta < a1; ta += CLU_TILE) {
@@ -131,7 +114,7 @@ __global__ __launch_bounds__(64) void k_reg_link(const float4* __restrict__ pts,
       t.p[i * 3] = (double)q.x; t.p[i * 3 + 1] = (double)q.y; t.p[i * 3 + 2] = (double)q.z;
       t.n[i * 3] = m.x; t.n[i * 3 + 1] = m.y; t.n[i * 3 + 2] = m.z;
       t.g[i] = smooth ? g : CLU_NO_KEY;
-      t.r[i] = smooth ? clu_find(parent, g) : CLU_NO_KEY;
+      t.r[i] = smooth ? uf_find(parent, g) : CLU_NO_KEY;
       any |= smooth;
     }
     __syncthreads();
@@ -139,7 +122,7 @@ __global__ __launch_bounds__(64) void k_reg_link(const float4* __restrict__ pts,
     rgn_pass<true>(t, nt, pts, nrm, ta, ta + (uint32_t)nt, tol2, cosv, unoriented != 0, parent, lane);
     __syncthreads();
     for (int i = lane; i < nt; i += 64)
-      if (t.g[i] != CLU_NO_KEY) t.r[i] = clu_find(parent, t.g[i]);
+      if (t.g[i] != CLU_NO_KEY) t.r[i] = uf_find(parent, t.g[i]);
     __syncthreads();
     rgn_pass<false>(t, nt, pts, nrm, ta + (uint32_t)nt, a1, tol2, cosv, unoriented != 0, parent, lane);
     unsigned long long m = todo;
@@ -162,8 +145,7 @@ __global__ __launch_bounds__(CLU_BLOCK) void k_reg_flatten(uint32_t N, const flo
   const uint32_t g = __float_as_uint(pts[i].w);
   uint32_t r = CLU_NO_KEY;
   if (__float_as_uint(nrm[i].w) == RGN_SMOOTH) {
-    r = g;
-    for (uint32_t p = parent[r]; p != r; p = parent[r]) r = p;
+    r = uf_root(parent, g);
     atomicAdd(&size[r], 1u);
   }
   root[g] = r;
@@ -195,11 +177,7 @@ __global__ __launch_bounds__(CLU_BLOCK) void k_reg_attach(uint32_t N, const floa
     const int x = cx + o / 5 - 2, y = cy + o % 5 - 2;
     if (x < 0 || x >= CLU_AXIS || y < 0 || y >= CLU_AXIS) continue;
     const unsigned long long base = ((unsigned long long)seg << 32) | (unsigned long long)(((uint32_t)x << 20) | ((uint32_t)y << 10));
-    uint32_t lo = 0, hi = nc; /* the first cell whose key is >= base | z0 */
-    while (lo < hi) {
-      const uint32_t mid = lo + ((hi - lo) >> 1);
-      if (ckey[mid] < (base | z0)) lo = mid + 1; else hi = mid;
-    }
+    const uint32_t lo = cells_lower_bound(ckey, 0, nc, base | z0);
     uint32_t ce = lo; /* at most five cells on */
     while (ce < nc && ckey[ce] <= (base | z1)) ce++;
     if (ce == lo) continue;

@@ -1,9 +1,10 @@
 /*
  * ppf_segment_host.h — host side of ppf_depth_segments / ppf_depth_segments_device: a depth image's surfaces labelled in image
  * space.  Kernels: ppf_segment_kernels.h.  Included by ppf_hip.hip after ppf_filter_host.h (and so after
- * ppf_depth_host.h: depth_check, depth_elem_size, depth_device_range, depth_upload; and ppf_prep_host.h: FrameRun's scratch).
+ * ppf_depth_host.h: depth_check, depth_elem_size, depth_device_range, depth_upload; and ppf_prep_host.h: FrameRun, frame_scan,
+ * frame_sort).
  *
- * Per call, all on the caller's stream: with a normals cloud k_depth_count and a five-launch scan; then k_seg_classify,
+ * Per call, all on the caller's stream (FrameRun::st): with a normals cloud k_depth_count and a five-launch scan; then k_seg_classify,
  * k_seg_tile, k_seg_merge, k_seg_flatten, k_seg_valid, the ranking's sort (four digit passes of seven launches), k_seg_rank
  * and k_seg_labels: 35 launches, 41 with a normals cloud, whatever the image's size or content.  Nothing the device counts
  * comes to the host before the end: the host waits once, for the counters, the segment heads and the reductions (and, in the
@@ -13,35 +14,6 @@
 #define PPF_SEGMENT_HOST_H
 
 namespace {
-
-/* launches on a stream, counted; the scratch lives in `mem` until the call returns */
-struct SegRun {
-  hipStream_t st = nullptr;
-  int launches = 0;
-  FrameRun mem;
-};
-#define SEG_LAUNCH(sr, kern, grid, block, ...)            \
-  do {                                                    \
-    kern<<<(grid), (block), 0, (sr).st>>>(__VA_ARGS__);   \
-    (sr).launches++;                                      \
-  } while (0)
-
-/* frame_scan on the run's stream: five launches whatever n is */
-ppf_status seg_scan(SegRun& sr, const uint32_t* in, uint32_t* out, size_t n) {
-  const size_t nb1 = std::max<size_t>((n + 1023) / 1024, 1), nb2 = (nb1 + 1023) / 1024;
-  uint32_t *s1, *s1x, *s2, *s2x;
-  ppf_status s;
-  if ((s = sr.mem.get(nb1, &s1)) != PPF_OK || (s = sr.mem.get(nb1, &s1x)) != PPF_OK || (s = sr.mem.get(nb2, &s2)) != PPF_OK ||
-      (s = sr.mem.get(nb2, &s2x)) != PPF_OK)
-    return s;
-  SEG_LAUNCH(sr, k_scan_block, dim3((unsigned)nb1), dim3(256), in, out, s1, n);
-  SEG_LAUNCH(sr, k_scan_block, dim3((unsigned)nb2), dim3(256), s1, s1x, s2, nb1);
-  SEG_LAUNCH(sr, k_scan_one, dim3(1), dim3(1024), s2, s2x, nb2);
-  SEG_LAUNCH(sr, k_scan_add, grid_for(nb1, 256), dim3(256), s1x, s2x, nb1);
-  SEG_LAUNCH(sr, k_scan_add, grid_for(n, 256), dim3(256), out, s1x, n);
-  HIPCHK(hipGetLastError());
-  return PPF_OK;
-}
 
 /* every argument check of both entries, before any device work; fills the kernel arguments (img and pitch excepted) */
 ppf_status segment_check(const char* who, const void* depth, int rows, int cols, size_t* pitch, const ppf_depth_params* dp,
@@ -90,8 +62,8 @@ struct SegWork {
   size_t z_head = 0, z_acc = 0, z_words = 0;
 };
 
-/* everything up to the label image, enqueued on sr.st; a.img and a.pitch are set by the caller */
-ppf_status segment_enqueue(SegRun& sr, SegWork& w, const DepthArgs& a, const SegArgs& sa, int format, const ppf_segment_params& sp,
+/* everything up to the label image, enqueued on fr.st; a.img and a.pitch are set by the caller */
+ppf_status segment_enqueue(FrameRun& fr, SegWork& w, const DepthArgs& a, const SegArgs& sa, int format, const ppf_segment_params& sp,
                            int32_t* d_labels) {
   const size_t N = (size_t)a.n;
   const int n = a.n, MC = sp.max_segments;
@@ -106,51 +78,44 @@ ppf_status segment_enqueue(SegRun& sr, SegWork& w, const DepthArgs& a, const Seg
   w.z_acc = w.z_head + (size_t)MC * SEG_HEAD;
   w.z_words = w.z_acc + (size_t)MC * SEG_ACC;
   ppf_status s;
-  if ((s = sr.mem.get(w.z_words, &w.zero)) != PPF_OK || (s = sr.mem.get(N, &rec)) != PPF_OK || (s = sr.mem.get(N, &cls)) != PPF_OK ||
-      (s = sr.mem.get(N, &parent)) != PPF_OK || (s = sr.mem.get(N, &size)) != PPF_OK || (s = sr.mem.get(N, &nbord)) != PPF_OK ||
-      (s = sr.mem.get(N, &root)) != PPF_OK || (s = sr.mem.get(N, &rank)) != PPF_OK || (s = sr.mem.get(N, &ka)) != PPF_OK ||
-      (s = sr.mem.get(N, &va)) != PPF_OK || (s = sr.mem.get(N, &kb)) != PPF_OK || (s = sr.mem.get(N, &vb)) != PPF_OK ||
-      (s = sr.mem.get((size_t)256 * nblk, &hist)) != PPF_OK || (s = sr.mem.get((size_t)256 * nblk, &offs)) != PPF_OK)
+  if ((s = fr.get(w.z_words, &w.zero)) != PPF_OK || (s = fr.get(N, &rec)) != PPF_OK || (s = fr.get(N, &cls)) != PPF_OK ||
+      (s = fr.get(N, &parent)) != PPF_OK || (s = fr.get(N, &size)) != PPF_OK || (s = fr.get(N, &nbord)) != PPF_OK ||
+      (s = fr.get(N, &root)) != PPF_OK || (s = fr.get(N, &rank)) != PPF_OK || (s = fr.get(N, &ka)) != PPF_OK ||
+      (s = fr.get(N, &va)) != PPF_OK || (s = fr.get(N, &kb)) != PPF_OK || (s = fr.get(N, &vb)) != PPF_OK ||
+      (s = fr.get((size_t)256 * nblk, &hist)) != PPF_OK || (s = fr.get((size_t)256 * nblk, &offs)) != PPF_OK)
     return s;
-  if (sa.nrm_rows && ((s = sr.mem.get((size_t)n_dt + 1, &tcnt)) != PPF_OK || (s = sr.mem.get((size_t)n_dt + 1, &toff)) != PPF_OK)) return s;
-  HIPCHK(hipMemsetAsync(w.zero, 0, w.z_words * sizeof(uint32_t), sr.st));
+  if (sa.nrm_rows && ((s = fr.get((size_t)n_dt + 1, &tcnt)) != PPF_OK || (s = fr.get((size_t)n_dt + 1, &toff)) != PPF_OK)) return s;
+  HIPCHK(hipMemsetAsync(w.zero, 0, w.z_words * sizeof(uint32_t), fr.st));
   const dim3 bd(DEPTH_BLOCK), bs(SEG_BLOCK), g_dt((unsigned)n_dt), g_tiles((unsigned)n_tiles), g_px = grid_for(N, SEG_BLOCK);
   if (sa.nrm_rows) {
     if (format == PPF_DEPTH_U16)
-      SEG_LAUNCH(sr, k_depth_count<uint16_t>, g_dt, bd, a, n_dt, tcnt);
+      FRAME_LAUNCH(fr, k_depth_count<uint16_t>, g_dt, bd, a, n_dt, tcnt);
     else
-      SEG_LAUNCH(sr, k_depth_count<float>, g_dt, bd, a, n_dt, tcnt);
+      FRAME_LAUNCH(fr, k_depth_count<float>, g_dt, bd, a, n_dt, tcnt);
     HIPCHK(hipGetLastError());
-    if ((s = seg_scan(sr, tcnt, toff, (size_t)n_dt + 1)) != PPF_OK) return s;
+    if ((s = frame_scan(fr, tcnt, toff, (size_t)n_dt + 1)) != PPF_OK) return s;
   }
   if (format == PPF_DEPTH_U16)
-    SEG_LAUNCH(sr, k_seg_classify<uint16_t>, g_dt, bd, a, sa, toff, rec, cls, size, nbord, rank);
+    FRAME_LAUNCH(fr, k_seg_classify<uint16_t>, g_dt, bd, a, sa, toff, rec, cls, size, nbord, rank);
   else
-    SEG_LAUNCH(sr, k_seg_classify<float>, g_dt, bd, a, sa, toff, rec, cls, size, nbord, rank);
-  SEG_LAUNCH(sr, k_seg_tile, g_tiles, bs, sa, rec, cls, parent);
-  SEG_LAUNCH(sr, k_seg_merge, g_px, bs, sa, rec, cls, parent);
-  SEG_LAUNCH(sr, k_seg_flatten, g_tiles, bs, sa, rec, cls, parent, root, size, nbord, w.zero);
-  SEG_LAUNCH(sr, k_seg_valid, g_px, bs, (uint32_t)N, root, size, (uint32_t)sp.min_size, (uint32_t)sp.max_size, ka, va, w.zero);
+    FRAME_LAUNCH(fr, k_seg_classify<float>, g_dt, bd, a, sa, toff, rec, cls, size, nbord, rank);
+  FRAME_LAUNCH(fr, k_seg_tile, g_tiles, bs, sa, rec, cls, parent);
+  FRAME_LAUNCH(fr, k_seg_merge, g_px, bs, sa, rec, cls, parent);
+  FRAME_LAUNCH(fr, k_seg_flatten, g_tiles, bs, sa, rec, cls, parent, root, size, nbord, w.zero);
+  FRAME_LAUNCH(fr, k_seg_valid, g_px, bs, (uint32_t)N, root, size, (uint32_t)sp.min_size, (uint32_t)sp.max_size, ka, va, w.zero);
   HIPCHK(hipGetLastError());
-  /* stable LSD passes over all four digits of the key, so the launch count does not depend on the image's size */
-  for (int shift = 0; shift < 32; shift += 8) {
-    SEG_LAUNCH(sr, k_rs_hist, dim3(nblk), dim3(RS_BLOCK), ka, n, shift, nblk, hist);
-    HIPCHK(hipGetLastError());
-    if ((s = seg_scan(sr, hist, offs, (size_t)256 * nblk)) != PPF_OK) return s;
-    SEG_LAUNCH(sr, k_rs_scatter, dim3(nblk), dim3(RS_BLOCK), ka, va, n, shift, nblk, offs, kb, vb);
-    HIPCHK(hipGetLastError());
-    std::swap(ka, kb);
-    std::swap(va, vb);
-  }
-  SEG_LAUNCH(sr, k_seg_rank, dim3(1), dim3(PPF_CLUSTER_MAX_CLUSTERS), (uint32_t)N, va, w.zero, size, nbord, MC, rank,
+  /* all four digits of the key, so the launch count does not depend on the image's size */
+  static const int shifts[4] = {0, 8, 16, 24};
+  if ((s = frame_sort(fr, ka, va, kb, vb, n, hist, offs, shifts, 4)) != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_seg_rank, dim3(1), dim3(PPF_CLUSTER_MAX_CLUSTERS), (uint32_t)N, va, w.zero, size, nbord, MC, rank,
              reinterpret_cast<int32_t*>(w.zero + w.z_head));
-  SEG_LAUNCH(sr, k_seg_labels, grid_for(N, SEG_TILE), bs, (uint32_t)N, a.cols, root, rank, rec, d_labels, w.zero + w.z_acc);
+  FRAME_LAUNCH(fr, k_seg_labels, grid_for(N, SEG_TILE), bs, (uint32_t)N, a.cols, root, rank, rec, d_labels, w.zero + w.z_acc);
   HIPCHK(hipGetLastError());
   return PPF_OK;
 }
 
 /* after the one wait: z is the zeroed block as the device left it */
-ppf_status segment_results(const char* who, const std::vector<uint32_t>& z, const SegWork& w, const SegRun& sr, const ppf_cloud* normals,
+ppf_status segment_results(const char* who, const std::vector<uint32_t>& z, const SegWork& w, const FrameRun& fr, const ppf_cloud* normals,
                            const ppf_segment_params& sp, ppf_segment_info* info, int32_t* counts, ppf_segment_stats& st) {
   if (normals && (uint32_t)normals->n != z[SEG_C_KEPT])
     return fail(PPF_ERR_INVALID, "%s: the normals cloud has %d rows, the image keeps %u pixels", who, normals->n, z[SEG_C_KEPT]);
@@ -174,7 +139,7 @@ ppf_status segment_results(const char* who, const std::vector<uint32_t>& z, cons
   st.n_eligible = (int32_t)z[SEG_C_ELIGIBLE];
   st.n_smooth = (int32_t)z[SEG_C_SMOOTH];
   st.n_attached = (int32_t)z[SEG_C_ATTACHED];
-  st.n_launches = sr.launches;
+  st.n_launches = fr.launches;
   st.n_host_syncs = 1;
   return PPF_OK;
 }
@@ -189,19 +154,19 @@ ppf_status segment_host(const char* who, const void* depth, int rows, int cols, 
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
   const size_t n = (size_t)rows * (size_t)cols;
-  SegRun sr;
+  FrameRun fr;
   SegWork w;
   DevBuf<unsigned char> img;
   int32_t* d_labels;
   if ((s = depth_upload(depth, rows, cols, pitch, dp->format, img, &a)) != PPF_OK) return s;
-  if ((s = sr.mem.get(n, &d_labels)) != PPF_OK) return s;
+  if ((s = fr.get(n, &d_labels)) != PPF_OK) return s;
   std::vector<int32_t> lab(n); /* labels stay untouched when the wait brings an error */
   std::vector<uint32_t> z;
-  if ((s = segment_enqueue(sr, w, a, sa, dp->format, *sp, d_labels)) == PPF_OK) {
+  if ((s = segment_enqueue(fr, w, a, sa, dp->format, *sp, d_labels)) == PPF_OK) {
     z.resize(w.z_words);
-    hipError_t e = hipMemcpyAsync(lab.data(), d_labels, n * sizeof(int32_t), hipMemcpyDeviceToHost, sr.st);
-    if (e == hipSuccess) e = hipMemcpyAsync(z.data(), w.zero, w.z_words * sizeof(uint32_t), hipMemcpyDeviceToHost, sr.st);
-    if (e == hipSuccess) e = host_stream_sync(sr.st);
+    hipError_t e = hipMemcpyAsync(lab.data(), d_labels, n * sizeof(int32_t), hipMemcpyDeviceToHost, fr.st);
+    if (e == hipSuccess) e = hipMemcpyAsync(z.data(), w.zero, w.z_words * sizeof(uint32_t), hipMemcpyDeviceToHost, fr.st);
+    if (e == hipSuccess) e = host_stream_sync(fr.st);
     if (e != hipSuccess) s = fail(PPF_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
   }
   /* kernels of a failed call may still run: wait before its scratch goes back to the block cache */
@@ -209,7 +174,7 @@ ppf_status segment_host(const char* who, const void* depth, int rows, int cols, 
     (void)hipDeviceSynchronize();
     return s;
   }
-  if ((s = segment_results(who, z, w, sr, normals, *sp, info, counts, st)) != PPF_OK) return s;
+  if ((s = segment_results(who, z, w, fr, normals, *sp, info, counts, st)) != PPF_OK) return s;
   std::memcpy(labels, lab.data(), n * sizeof(int32_t));
   return PPF_OK;
 }
@@ -230,22 +195,22 @@ ppf_status segment_device(const char* who, const void* d_depth, int rows, int co
   if ((s = depth_device_range(who, "label buffer", d_labels, out_bytes)) != PPF_OK) return s;
   const uintptr_t i0 = (uintptr_t)d_depth, o0 = (uintptr_t)d_labels;
   if (i0 < o0 + out_bytes && o0 < i0 + in_bytes) return fail(PPF_ERR_INVALID, "%s: the label buffer overlaps the image", who);
-  SegRun sr;
+  FrameRun fr;
   SegWork w;
-  sr.st = stream;
+  fr.st = stream;
   a.img = static_cast<const unsigned char*>(d_depth);
   std::vector<uint32_t> z;
-  if ((s = segment_enqueue(sr, w, a, sa, dp->format, *sp, d_labels)) == PPF_OK) {
+  if ((s = segment_enqueue(fr, w, a, sa, dp->format, *sp, d_labels)) == PPF_OK) {
     z.resize(w.z_words);
-    hipError_t e = hipMemcpyAsync(z.data(), w.zero, w.z_words * sizeof(uint32_t), hipMemcpyDeviceToHost, sr.st);
-    if (e == hipSuccess) e = host_stream_sync(sr.st);
+    hipError_t e = hipMemcpyAsync(z.data(), w.zero, w.z_words * sizeof(uint32_t), hipMemcpyDeviceToHost, fr.st);
+    if (e == hipSuccess) e = host_stream_sync(fr.st);
     if (e != hipSuccess) s = fail(PPF_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
   }
   if (s != PPF_OK) {
     (void)hipDeviceSynchronize();
     return s;
   }
-  return segment_results(who, z, w, sr, normals, *sp, info, counts, st);
+  return segment_results(who, z, w, fr, normals, *sp, info, counts, st);
 }
 
 /* the outputs of a failed call are zero; info is only cleared when the params say how long it is */

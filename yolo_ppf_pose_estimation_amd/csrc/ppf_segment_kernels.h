@@ -1,7 +1,8 @@
 /*
  * ppf_segment_kernels.h — the kernels of ppf_depth_segments: the connected surfaces of a depth image, labelled in image space
  * (host side: ppf_segment_host.h).  Included by ppf_hip.hip after ppf_depth_kernels.h (DepthArgs, depth_pixel),
- * ppf_sample_kernels.h (float_to_ordered, the radix-sort passes) and ppf_cluster_kernels.h (clu_ld, clu_find, clu_unite).
+ * ppf_sample_kernels.h (float_to_ordered, the radix-sort passes) and ppf_label_kernels.h (uf_find, uf_unite, uf_root, agent_ld,
+ * wave_max_by_key).
  *
  * The specification is closed -- step and agree are fp64 expressions evaluated as written, a component is a set, its rank is by
  * integers -- so every output byte equals tests/depth_segments_oracle.py whatever the order the unions happen in.  A pixel is
@@ -14,12 +15,12 @@
  *                   cloud's row count reads nothing (the pixel gets SEG_KEPT; the host refuses the call after its one wait).
  *                   Also the start of everything per pixel: size, border count 0, rank -1.
  *   k_seg_tile      one 256-thread workgroup per tile, four pixels a thread.  Records and classes are staged in LDS; a
- *                   union-find over the tile's 1,024 pixels runs entirely in LDS with clu_find / clu_unite on a shared array
+ *                   union-find over the tile's 1,024 pixels runs entirely in LDS with uf_find / uf_unite on a shared array
  *                   (each smooth pixel unites with its right, lower and, for 8-connectivity, two lower diagonal neighbours
  *                   inside the tile).  After a barrier every pixel walks to its local root and writes the global
  *                   parent[p] = that root's pixel index; a pixel that is not smooth is its own parent.
  *   k_seg_merge     the links that cross a tile edge: one thread per pixel, only those of a tile's last column, last row or
- *                   (diagonals) first column do anything; clu_unite on the global parent[].
+ *                   (diagonals) first column do anything; uf_unite on the global parent[].
  *   k_seg_flatten   one workgroup per tile.  A smooth pixel walks to its root; a border pixel picks its smooth neighbour by
  *                   the border rule from the global records and takes that pixel's root.  The tile then counts its pixels per
  *                   root in an LDS hash table (a wave that lies in one set inserts once with its popcount) and issues one
@@ -33,11 +34,10 @@
  *                   lies in one segment combines by shuffles and adds once) and issues a global atomicMax only for a word
  *                   that still raises the total: one add per wave on the words of the frame's largest segment cost 1.05 ms.
  *
- * Why every loop ends.  clu_find steps to a strictly smaller index.  clu_unite retries only after a failed compare-and-swap,
- * which means another thread's succeeded, and the number of roots only falls.  The plain root walks of k_seg_tile (after its
- * barrier) and k_seg_flatten (after a launch boundary) step to a strictly smaller index.  The hash insert of k_seg_flatten
- * probes a table of 2 * SEG_TILE slots that receives at most SEG_TILE distinct keys, so a free or equal slot is always met.
- * No workgroup waits for another.  Inside k_seg_merge parent[] is touched by clu_ld / clu_st / atomicCAS only.
+ * Why every loop ends.  The union-find's loops end by ppf_label_kernels.h's argument; uf_root is used by k_seg_tile after its
+ * barrier and by k_seg_flatten after a launch boundary.  The hash insert of k_seg_flatten probes a table of 2 * SEG_TILE slots
+ * that receives at most SEG_TILE distinct keys, so a free or equal slot is always met.  No workgroup waits for another.
+ * Inside k_seg_merge parent[] is touched by uf_unite only.
  */
 #ifndef PPF_SEGMENT_KERNELS_H
 #define PPF_SEGMENT_KERNELS_H
@@ -162,13 +162,13 @@ __global__ __launch_bounds__(SEG_BLOCK) void k_seg_tile(SegArgs sa, const float4
     const int i = (int)threadIdx.x + k * SEG_BLOCK, lx = i & (SEG_TW - 1), ly = i >> 6;
     if (s_cls[i] != SEG_SMOOTH) continue;
     const float4 me = s_rec[i];
-    if (lx + 1 < SEG_TW && s_cls[i + 1] == SEG_SMOOTH && seg_link(me, s_rec[i + 1], sa)) clu_unite(s_par, (uint32_t)i, (uint32_t)(i + 1));
+    if (lx + 1 < SEG_TW && s_cls[i + 1] == SEG_SMOOTH && seg_link(me, s_rec[i + 1], sa)) uf_unite(s_par, (uint32_t)i, (uint32_t)(i + 1));
     if (ly + 1 < SEG_TH) {
       const int d = i + SEG_TW;
-      if (s_cls[d] == SEG_SMOOTH && seg_link(me, s_rec[d], sa)) clu_unite(s_par, (uint32_t)i, (uint32_t)d);
+      if (s_cls[d] == SEG_SMOOTH && seg_link(me, s_rec[d], sa)) uf_unite(s_par, (uint32_t)i, (uint32_t)d);
       if (sa.eight) {
-        if (lx > 0 && s_cls[d - 1] == SEG_SMOOTH && seg_link(me, s_rec[d - 1], sa)) clu_unite(s_par, (uint32_t)i, (uint32_t)(d - 1));
-        if (lx + 1 < SEG_TW && s_cls[d + 1] == SEG_SMOOTH && seg_link(me, s_rec[d + 1], sa)) clu_unite(s_par, (uint32_t)i, (uint32_t)(d + 1));
+        if (lx > 0 && s_cls[d - 1] == SEG_SMOOTH && seg_link(me, s_rec[d - 1], sa)) uf_unite(s_par, (uint32_t)i, (uint32_t)(d - 1));
+        if (lx + 1 < SEG_TW && s_cls[d + 1] == SEG_SMOOTH && seg_link(me, s_rec[d + 1], sa)) uf_unite(s_par, (uint32_t)i, (uint32_t)(d + 1));
       }
     }
   }
@@ -178,8 +178,7 @@ __global__ __launch_bounds__(SEG_BLOCK) void k_seg_tile(SegArgs sa, const float4
     const int i = (int)threadIdx.x + k * SEG_BLOCK, lx = i & (SEG_TW - 1), ly = i >> 6;
     const int u = u0 + lx, v = v0 + ly;
     if (u >= sa.cols || v >= sa.rows) continue;
-    uint32_t r = (uint32_t)i;
-    for (uint32_t q = s_par[r]; q != r; q = s_par[r]) r = q; /* nobody writes s_par after the barrier */
+    const uint32_t r = uf_root(s_par, (uint32_t)i); /* nobody writes s_par after the barrier */
     const int rx = (int)r & (SEG_TW - 1), ry = (int)r >> 6;
     parent[(size_t)v * (size_t)sa.cols + (size_t)u] = (uint32_t)(v0 + ry) * (uint32_t)sa.cols + (uint32_t)(u0 + rx);
   }
@@ -199,21 +198,16 @@ __global__ __launch_bounds__(SEG_BLOCK) void k_seg_merge(SegArgs sa, const float
   const bool right = u + 1 < sa.cols, down = v + 1 < sa.rows;
   if (last_x && right) {
     const uint32_t q = p + 1u;
-    if (cls[q] == SEG_SMOOTH && seg_link(me, rec[q], sa)) clu_unite(parent, p, q);
+    if (cls[q] == SEG_SMOOTH && seg_link(me, rec[q], sa)) uf_unite(parent, p, q);
   }
   if (down) {
     const uint32_t d = p + (uint32_t)sa.cols;
-    if (last_y && cls[d] == SEG_SMOOTH && seg_link(me, rec[d], sa)) clu_unite(parent, p, d);
+    if (last_y && cls[d] == SEG_SMOOTH && seg_link(me, rec[d], sa)) uf_unite(parent, p, d);
     if (sa.eight) {
-      if (u > 0 && (last_y || first_x) && cls[d - 1u] == SEG_SMOOTH && seg_link(me, rec[d - 1u], sa)) clu_unite(parent, p, d - 1u);
-      if (right && (last_y || last_x) && cls[d + 1u] == SEG_SMOOTH && seg_link(me, rec[d + 1u], sa)) clu_unite(parent, p, d + 1u);
+      if (u > 0 && (last_y || first_x) && cls[d - 1u] == SEG_SMOOTH && seg_link(me, rec[d - 1u], sa)) uf_unite(parent, p, d - 1u);
+      if (right && (last_y || last_x) && cls[d + 1u] == SEG_SMOOTH && seg_link(me, rec[d + 1u], sa)) uf_unite(parent, p, d + 1u);
     }
   }
-}
-
-__device__ __forceinline__ uint32_t seg_root(const uint32_t* __restrict__ parent, uint32_t r) {
-  for (uint32_t q = parent[r]; q != r; q = parent[r]) r = q;
-  return r;
 }
 
 /* grid: tiles_x * tiles_y.  counters: SEG_C_KEPT .. SEG_C_ATTACHED */
@@ -242,7 +236,7 @@ __global__ __launch_bounds__(SEG_BLOCK) void k_seg_flatten(SegArgs sa, const flo
     const uint8_t c = inside ? cls[p] : SEG_OUT;
     uint32_t r = SEG_NONE;
     if (c == SEG_SMOOTH) {
-      r = seg_root(parent, p);
+      r = uf_root(parent, p);
     } else if (c == SEG_BORDER) {
       const float4 me = rec[p];
       double best = 0.0;
@@ -263,7 +257,7 @@ __global__ __launch_bounds__(SEG_BLOCK) void k_seg_flatten(SegArgs sa, const flo
             bq = q;
           }
         }
-      if (bq != SEG_NONE) r = seg_root(parent, bq);
+      if (bq != SEG_NONE) r = uf_root(parent, bq);
     }
     if (inside) root[p] = r;
     const bool in = r != SEG_NONE, bor = in && c == SEG_BORDER;
@@ -348,8 +342,8 @@ __global__ __launch_bounds__(PPF_CLUSTER_MAX_CLUSTERS) void k_seg_rank(uint32_t 
 }
 
 /* grid: spans of SEG_TILE consecutive pixels.  The span's maxima per segment are gathered in LDS first (a wave that lies in
- * one segment combines by shuffles and adds once), then one global atomicMax per word that still raises the total: a stale
- * read of the total is never above it, so a skipped add is one that could not have changed it */
+ * one segment combines by shuffles and adds once: wave_max_by_key), then one global atomicMax per word that still raises the
+ * total: a stale read of the total (agent_ld) is never above it, so a skipped add is one that could not have changed it */
 __global__ __launch_bounds__(SEG_BLOCK) void k_seg_labels(uint32_t N, int cols, const uint32_t* __restrict__ root, const int32_t* __restrict__ rank,
                                                           const float4* __restrict__ rec, int32_t* __restrict__ labels, uint32_t* acc) {
   __shared__ uint32_t s_acc[PPF_CLUSTER_MAX_CLUSTERS * SEG_ACC];
@@ -371,22 +365,8 @@ __global__ __launch_bounds__(SEG_BLOCK) void k_seg_labels(uint32_t N, int cols, 
         v[0] = ~pu; v[1] = pu + 1u; v[2] = ~pv; v[3] = pv + 1u; v[4] = ~o; v[5] = o;
       }
     }
-    const bool in = l >= 0;
-    const unsigned long long live = __ballot(in);
-    if (!live) continue;
-    const int32_t l0 = __shfl(l, __ffsll((long long)live) - 1);
-    bool add = in;
-    int32_t l1 = l;
-    if (__all(!in || l == l0)) {
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int j = 0; j < SEG_ACC; j++) v[j] = max(v[j], (uint32_t)__shfl_down((int)v[j], o));
-      }
-      add = (threadIdx.x & 63) == 0; /* lane 0 of a one-segment wave may itself be in none */
-      l1 = l0;
-    }
-    if (add) {
+    uint32_t l1 = (uint32_t)l;
+    if (wave_max_by_key(l >= 0, l1, v)) {
 #pragma unroll
       for (int j = 0; j < SEG_ACC; j++)
         if (v[j]) atomicMax(&s_acc[l1 * SEG_ACC + j], v[j]);
@@ -395,7 +375,7 @@ __global__ __launch_bounds__(SEG_BLOCK) void k_seg_labels(uint32_t N, int cols, 
   __syncthreads();
   for (int i = threadIdx.x; i < PPF_CLUSTER_MAX_CLUSTERS * SEG_ACC; i += SEG_BLOCK) {
     const uint32_t m = s_acc[i];
-    if (m && clu_ld(acc + i) < m) atomicMax(acc + i, m);
+    if (m && agent_ld(acc + i) < m) atomicMax(acc + i, m);
   }
 }
 
