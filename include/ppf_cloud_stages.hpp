@@ -24,6 +24,7 @@
  *                                                     (a raw sensor depth frame aligned to the colour camera; Cloud::fromDepth takes it)
  *   (nothing: a sensor pipeline's depth clean-up)     ->  filterDepth / filterDepthU16 / DepthMap::registerFiltered
  *   (nothing: the boxes come from YOLO)               ->  segmentDepth / segmentDepthU16  (the depth image's surfaces as labels and boxes)
+ *   (nothing: the labels come from YOLO)              ->  Recognizer::recognize  (per proposal cloud the trained models it can be a view of)
  *
  * Every stage returns a new Cloud that stays in HBM; only toMat()/download() copy to the host.  A maintainer replaces
  * the bodies of those CloudProcessor methods by these one-liners; pcl::PointCloud<PointXYZ> goes
@@ -606,6 +607,67 @@ inline std::vector<int32_t> segmentDepthU16(const uint16_t* depth, int rows, int
                                             size_t rowPitchBytes = 0, int32_t* counts = 0, ppf_segment_stats* stats = 0) {
   return segmentDepthImage(depth, PPF_DEPTH_U16, scale, rows, cols, normals, params, info, zMin, zMax, rowPitchBytes, counts, stats);
 }
+
+/* ppf_recognizer / ppf_recognize_frame: which trained models a proposal cloud can be a view of, from the models'
+ * quantised pair-feature keys.  Built once from trained detectors (ppf_match_3d::PPF3DDetector::handle(), PPF_FEATURE_PPF models
+ * only), which it keeps alive; copies share the recogniser.  recognize() returns per cloud its candidates, best first, at most
+ * params.top of them; a null pointer in `clouds` or an empty Cloud has none. */
+class Recognizer {
+ public:
+  Recognizer() : n_models_(0) {}
+  explicit Recognizer(const std::vector<const ppf_model*>& models) : n_models_((int)models.size()) {
+    ppf_recognizer* r = nullptr;
+    ppf_match_3d::check(ppf_recognizer_create(models.empty() ? 0 : &models[0], (int)models.size(), &r));
+    h_ = std::shared_ptr<ppf_recognizer>(r, [](ppf_recognizer* p) { ppf_recognizer_release(p); });
+  }
+  static ppf_recognize_params defaultParams() {
+    ppf_recognize_params p;
+    ppf_default_recognize_params(&p);
+    return p;
+  }
+  int models() const { return n_models_; }
+  const ppf_recognizer* handle() const { return h_.get(); }
+  ppf_recognizer_info modelInfo(int i) const {
+    ppf_recognizer_info info;
+    ppf_match_3d::check(ppf_recognizer_model_info(need(), i, &info));
+    return info;
+  }
+  /* model i's key set: 4 int32 a key, in lexicographic order */
+  std::vector<int32_t> keys(int i) const {
+    int n = 0;
+    (void)ppf_recognizer_keys(need(), i, 0, 0, &n); /* PPF_ERR_CAPACITY: n is the size */
+    std::vector<int32_t> out((size_t)n * 4 + 4);
+    ppf_match_3d::check(ppf_recognizer_keys(need(), i, &out[0], n + 1, &n));
+    out.resize((size_t)n * 4);
+    return out;
+  }
+  /* nUsed: 0 or the used rows per cloud; counts: 0 or per cloud and model {n_known, n_keys_hit} */
+  std::vector<std::vector<ppf_recognize_score> > recognize(const std::vector<const Cloud*>& clouds, const ppf_recognize_params* params = 0,
+                                                           std::vector<int32_t>* nUsed = 0, std::vector<uint64_t>* counts = 0,
+                                                           ppf_recognize_stats* stats = 0) const {
+    const ppf_recognize_params p = params ? *params : defaultParams();
+    const size_t n = clouds.size(), top = p.top >= 1 && p.top <= PPF_RECOGNIZE_MAX_TOP ? (size_t)p.top : 1;
+    std::vector<const ppf_cloud*> handles(n + 1, (const ppf_cloud*)0);
+    for (size_t i = 0; i < n; i++) handles[i] = clouds[i] ? clouds[i]->handle() : 0;
+    std::vector<ppf_recognize_score> ranked(n * top + 1);
+    std::vector<int32_t> nRanked(n + 1, 0), used(n + 1, 0);
+    std::vector<uint64_t> cnt(n * (size_t)n_models_ * 2 + 1, 0);
+    ppf_match_3d::check(ppf_recognize_frame(need(), &handles[0], (int)n, &p, &used[0], &cnt[0], &ranked[0], &nRanked[0], stats));
+    std::vector<std::vector<ppf_recognize_score> > out(n);
+    for (size_t i = 0; i < n; i++) out[i].assign(ranked.begin() + i * top, ranked.begin() + i * top + nRanked[i]);
+    if (nUsed) nUsed->assign(used.begin(), used.begin() + n);
+    if (counts) counts->assign(cnt.begin(), cnt.begin() + n * (size_t)n_models_ * 2);
+    return out;
+  }
+
+ private:
+  const ppf_recognizer* need() const {
+    if (!h_) throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::Recognizer: empty handle");
+    return h_.get();
+  }
+  std::shared_ptr<ppf_recognizer> h_;
+  int n_models_;
+};
 
 /* A resident registration map (ppf_depth_map), built once per calibration as k4a::transformation is: registerDepth draws a
  * raw depth frame of the depth camera into the pixel grid of the colour camera (float32 metres, 0 where nothing was drawn),

@@ -58,6 +58,9 @@
  *                                   unsupported "flying" pixels removed, the others smoothed without crossing a depth step
  *   ppf_depth_segments (+_device)   detections without a detector, straight from the organised depth image (the reference takes
  *                                   its boxes from YOLO): the image's connected smooth surfaces as a label image and boxes
+ *   ppf_recognize_frame             labels without a detector (the reference takes each crop's class from YOLO,
+ *   (+ppf_recognizer_*)             YOLO_cropping_ppf_test.cpp:88-127): per proposal cloud a shortlist of the trained models
+ *                                   it can be a view of, from the quantised pair features the models were trained on
  *
  * Conventions
  *   - A cloud argument is (pointer, rows, stride, normal_offset): float32 rows whose first three floats
@@ -754,6 +757,82 @@ ppf_status ppf_depth_segments(const void* depth, int rows, int cols, size_t row_
 ppf_status ppf_depth_segments_device(const void* d_depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
                                      const ppf_cloud* normals /* may be NULL */, const ppf_segment_params* sp, int32_t* d_labels,
                                      void* stream, ppf_segment_info* info, int32_t* counts, ppf_segment_stats* stats /* may be NULL */);
+
+/* ---- which trained models a proposal can be a view of: labels for detections nobody named ------------ */
+#define PPF_RECOGNIZE_MAX_MODELS 64
+#define PPF_RECOGNIZE_MAX_CLOUDS 256
+#define PPF_RECOGNIZE_MAX_ROWS 2048
+#define PPF_RECOGNIZE_MAX_TOP 16
+typedef struct ppf_recognizer ppf_recognizer; /* opaque, immutable, reference counted; retains its models */
+typedef struct ppf_recognizer_info {
+  int32_t n_rows;    /* the model's sampled rows (ppf_model_info.n_ref) */
+  int32_t n_bins[4]; /* n_a, n_a, n_a, n_d: the bins of the key set's four dimensions */
+  int32_t in_lds;    /* 1: the scoring kernel stages the set in LDS; 0: it reads it from global memory */
+  uint64_t n_keys;   /* the size of the key set */
+  uint64_t bytes;    /* what the set takes on the device */
+  int32_t reserved[4];
+} ppf_recognizer_info;
+typedef struct ppf_recognize_params {
+  int32_t max_rows;     /* 2..2048; default 512 */
+  int32_t top;          /* 1..16; default 2 */
+  double min_score;     /* finite, >= 0; default 0 */
+  double min_precision; /* finite, >= 0; default 0 */
+  int32_t flags;        /* none defined: 0 */
+  int32_t reserved[4];
+} ppf_recognize_params;
+typedef struct ppf_recognize_score {
+  int32_t model; /* index into the recogniser's models */
+  int32_t reserved;
+  uint64_t n_known, n_keys_hit;
+  double precision, recall, score;
+} ppf_recognize_score;
+typedef struct ppf_recognize_stats {
+  int32_t n_clouds, n_models;
+  int32_t n_launches;   /* kernel launches of the call */
+  int32_t n_host_syncs; /* blocking waits of the call: 1 */
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_recognize_stats;
+/* Builds every model's key set on the device, once.  models: n_models (1..64) trained models of feature PPF_FEATURE_PPF, under
+ * either key_equality, all on the current device; the same model may appear more than once.  A NULL pointer, a count outside
+ * its range, a model with fewer than two sampled rows or a PPF_FEATURE_DARBOUX model is PPF_ERR_INVALID before any device work;
+ * on every error *out is NULL.  The recogniser retains its models until its last reference is dropped. */
+ppf_status ppf_recognizer_create(const ppf_model* const* models, int n_models, ppf_recognizer** out);
+ppf_status ppf_recognizer_retain(ppf_recognizer* rec);
+ppf_status ppf_recognizer_release(ppf_recognizer* rec); /* NULL is PPF_OK */
+ppf_status ppf_recognizer_model_info(const ppf_recognizer* rec, int i, ppf_recognizer_info* info);
+/* the key set of model i as tuples, keys4[4q .. 4q + 3], in lexicographic order of the four int32 (INT32_MIN, the bin of a NaN
+ * angle, first); *n = its size.  cap (tuples) too small, or keys4 NULL: PPF_ERR_CAPACITY with *n set.  Host only. */
+ppf_status ppf_recognizer_keys(const ppf_recognizer* rec, int i, int32_t* keys4, int cap, int* n);
+/* max_rows 512, top 2, min_score 0, min_precision 0, flags 0 */
+void ppf_default_recognize_params(ppf_recognize_params* p);
+/* Scores every proposal cloud against every model of the recogniser and shortlists, per proposal, the models it can be a view
+ * of, as a closed specification.  All arithmetic is fp64 as written, nothing fused, with ppf_pair_feature (the table build's
+ * pair feature: three deterministic acos of include/ppf_detmath.h and the distance) and ppf_d2i.
+ *   Key of an ordered pair of rows i != j (by index: coincident points are pairs like any other) under a model's angle_step and
+ *     distance_step (ppf_model_info): with f = {0, 0, 0, 0} and ppf_pair_feature(p_i, n_i, p_j, n_j, f), the tuple
+ *     (ppf_d2i(f[0] / angle_step), ppf_d2i(f[1] / angle_step), ppf_d2i(f[2] / angle_step), ppf_d2i(f[3] / distance_step)).
+ *     Coordinates and normals are the float rows converted to double, read as they are, with no re-normalisation.  A NaN angle
+ *     gives the bin INT32_MIN, a value like any other.  Tuples are compared, not hashes.
+ *   Key set of a model: the keys of all ordered pairs of the rows ppf_model_get_sampled returns; n_keys is its size.
+ *   Rows of a proposal of n rows: s = ceil(n / max_rows); the candidates are rows 0, s, 2s, ...; the used rows are the
+ *     candidates whose six values are all finite, n_used their count, n_pairs = n_used * (n_used - 1).
+ *   Per (proposal, model): n_known = the ordered pairs of used rows whose key is in the model's key set; n_keys_hit = the
+ *     distinct keys among those pairs; precision = (double)n_known / (double)n_pairs, recall = (double)n_keys_hit /
+ *     (double)n_keys, score = precision * recall; all three 0 when n_pairs == 0.  They are computed on the host.
+ *   Ranking: the models with score >= min_score and precision >= min_precision, by score descending, then model index
+ *     ascending; the first min(top, count) are the proposal's candidates.  A proposal nothing passes has none: clutter.
+ * clouds: n_clouds (0..256) pointers; a NULL cloud or one without rows has n_used 0 and no candidates.  n_used: [n_clouds] or
+ * NULL.  counts: [n_clouds][n_models][2] = {n_known, n_keys_hit} or NULL.  ranked: [n_clouds][top], zero past a proposal's
+ * n_ranked; n_ranked: [n_clouds].  Argument errors (NULL where it is not allowed, a field outside the range stated beside it,
+ * an unknown flag, a count outside its range) are PPF_ERR_INVALID before any device work; without a device the call is
+ * PPF_ERR_HIP.  On every error n_ranked, ranked, counts, n_used and *stats are zero.  One upload before any device work and one
+ * blocking wait (n_host_syncs 1); two launches, whatever n_clouds and the row counts are.  All proposals and models of a call go
+ * through one work list built on the host from the row counts.  Each proposal's result is what a call with that cloud alone
+ * gives, and it does not depend on scheduling.  stats may be NULL. */
+ppf_status ppf_recognize_frame(const ppf_recognizer* rec, const ppf_cloud* const* clouds, int n_clouds, const ppf_recognize_params* p,
+                               int32_t* n_used /* may be NULL */, uint64_t* counts /* may be NULL */, ppf_recognize_score* ranked,
+                               int32_t* n_ranked, ppf_recognize_stats* stats /* may be NULL */);
 
 /* ---- every detection of a frame in one segmented device pass ------------------------------------------------ */
 typedef struct ppf_frame_params {

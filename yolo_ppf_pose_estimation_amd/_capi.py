@@ -158,6 +158,29 @@ class SegmentStats(C.Structure):
 PPF_SEGMENT_EIGHT, PPF_SEGMENT_UNORIENTED = 1, 2  # SegmentParams.flags bits
 
 
+class RecognizerInfo(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("n_bins", C.c_int32 * 4), ("in_lds", C.c_int32), ("n_keys", C.c_uint64),
+                ("bytes", C.c_uint64), ("reserved", C.c_int32 * 4)]
+
+
+class RecognizeParams(C.Structure):
+    _fields_ = [("max_rows", C.c_int32), ("top", C.c_int32), ("min_score", C.c_double), ("min_precision", C.c_double),
+                ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class RecognizeScore(C.Structure):
+    _fields_ = [("model", C.c_int32), ("reserved", C.c_int32), ("n_known", C.c_uint64), ("n_keys_hit", C.c_uint64),
+                ("precision", C.c_double), ("recall", C.c_double), ("score", C.c_double)]
+
+
+class RecognizeStats(C.Structure):
+    _fields_ = [("n_clouds", C.c_int32), ("n_models", C.c_int32), ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32),
+                ("ms_wall", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+PPF_RECOGNIZE_MAX_MODELS, PPF_RECOGNIZE_MAX_CLOUDS, PPF_RECOGNIZE_MAX_ROWS, PPF_RECOGNIZE_MAX_TOP = 64, 256, 2048, 16
+
+
 class VerifyParams(C.Structure):
     _fields_ = [("inlier_dist", C.c_float), ("normal_cos", C.c_float), ("depth_tol", C.c_float), ("model_step", C.c_int32),
                 ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
@@ -409,6 +432,14 @@ _SIGNATURES = {
     "ppf_depth_segments_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(DepthParams), C.c_void_p,
                                             C.POINTER(SegmentParams), C.c_void_p, C.c_void_p, C.POINTER(SegmentInfo),
                                             C.POINTER(C.c_int32), C.POINTER(SegmentStats)]),
+    "ppf_recognizer_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]),
+    "ppf_recognizer_retain": (C.c_int, [C.c_void_p]),
+    "ppf_recognizer_release": (C.c_int, [C.c_void_p]),
+    "ppf_recognizer_model_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RecognizerInfo)]),
+    "ppf_recognizer_keys": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "ppf_default_recognize_params": (None, [C.POINTER(RecognizeParams)]),
+    "ppf_recognize_frame": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(RecognizeParams), C.c_void_p, C.c_void_p,
+                                      C.POINTER(RecognizeScore), C.POINTER(C.c_int32), C.POINTER(RecognizeStats)]),
     "ppf_default_verify_params": (None, [C.POINTER(VerifyParams)]),
     "ppf_verify_frame": (C.c_int, [C.POINTER(FrameDetection), C.c_int, C.POINTER(Pose), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int,
                                    C.c_int, C.POINTER(C.c_double), C.POINTER(VerifyParams), C.POINTER(PoseScore), C.POINTER(C.c_int),

@@ -773,6 +773,81 @@ def segment_depth(depth, *, depth_scale: float = 0.001, z_min: float = 0.0, z_ma
     return result(out)
 
 
+# ppf_recognize_score as a numpy record
+RECOGNIZE_SCORE = np.dtype([("model", "<i4"), ("reserved", "<i4"), ("n_known", "<u8"), ("n_keys_hit", "<u8"), ("precision", "<f8"),
+                            ("recall", "<f8"), ("score", "<f8")])
+
+
+class Recognizer:
+    """Which trained models a proposal cloud can be a view of (ppf_recognizer_*, ppf_recognize_frame): every
+    model's set of quantised pair-feature keys, built once on the device.  models: trained ``PPF3DDetector``s (feature 0,
+    either key_equality); the recogniser keeps their tables alive."""
+
+    def __init__(self, models: Sequence[PPF3DDetector]):
+        models = list(models)
+        for d in models:
+            if not isinstance(d, PPF3DDetector) or not d.trained:
+                raise PPFError(_capi.PPF_ERR_NOT_TRAINED, "Recognizer takes trained PPF3DDetector objects")
+        self._ptr = None
+        self.n_models = len(models)
+        ptrs = (C.c_void_p * max(len(models), 1))(*[d._model.ptr for d in models])
+        out = C.c_void_p()
+        check(lib().ppf_recognizer_create(ptrs, len(models), C.byref(out)))
+        self._ptr = out
+
+    def __del__(self):
+        try:
+            if self._ptr:
+                lib().ppf_recognizer_release(self._ptr)
+                self._ptr = None
+        except Exception:
+            pass
+
+    def model_info(self, i: int) -> dict:
+        """n_rows, n_bins (n_a, n_a, n_a, n_d), in_lds, n_keys and bytes of model i's key set"""
+        ri = _capi.RecognizerInfo()
+        check(lib().ppf_recognizer_model_info(self._ptr, int(i), C.byref(ri)))
+        d = _capi.stats_dict(ri)
+        d.pop("reserved")
+        return d
+
+    def keys(self, i: int) -> np.ndarray:
+        """model i's key set: (n_keys, 4) int32 tuples in lexicographic order"""
+        n = C.c_int(0)
+        lib().ppf_recognizer_keys(self._ptr, int(i), None, 0, C.byref(n))  # PPF_ERR_CAPACITY: n is the size
+        out = np.zeros((max(n.value, 1), 4), dtype=np.int32)
+        check(lib().ppf_recognizer_keys(self._ptr, int(i), out.ctypes.data, out.shape[0], C.byref(n)))
+        return out[:n.value]
+
+    def recognize(self, clouds, params=None, return_counts: bool = False, return_stats: bool = False):
+        """Per cloud (a ``DeviceCloud`` or None) its candidates, best first: a ``RECOGNIZE_SCORE`` array of at most ``top``
+        rows.  params: a RecognizeParams, a dict of its fields (max_rows, top, min_score, min_precision) or None (the
+        defaults).  return_counts adds ``n_used`` (n_clouds) and ``counts`` (n_clouds, n_models, 2: n_known, n_keys_hit);
+        return_stats adds the call's stats last."""
+        prm = _params(_capi.RecognizeParams, "ppf_default_recognize_params", params, "recognize")
+        clouds = list(clouds)
+        for c in clouds:
+            if c is not None and not isinstance(c, DeviceCloud):
+                raise PPFError(_capi.PPF_ERR_INVALID, "clouds must be DeviceCloud objects or None")
+        n = len(clouds)
+        ptrs = (C.c_void_p * max(n, 1))(*[c._ptr if c is not None else None for c in clouds])
+        top = max(1, min(int(prm.top), _capi.PPF_RECOGNIZE_MAX_TOP))
+        ranked = np.zeros((max(n, 1), top), dtype=RECOGNIZE_SCORE)
+        n_ranked = np.zeros(max(n, 1), dtype=np.int32)
+        n_used = np.zeros(max(n, 1), dtype=np.int32)
+        counts = np.zeros((max(n, 1), self.n_models, 2), dtype=np.uint64)
+        st = _capi.RecognizeStats()
+        check(lib().ppf_recognize_frame(self._ptr, ptrs, n, C.byref(prm), n_used.ctypes.data, counts.ctypes.data,
+                                        ranked.ctypes.data_as(C.POINTER(_capi.RecognizeScore)),
+                                        n_ranked.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st)))
+        res = [[ranked[i, :int(n_ranked[i])].copy() for i in range(n)]]
+        if return_counts:
+            res += [n_used[:n], counts[:n]]
+        if return_stats:
+            res.append(_capi.stats_dict(st))
+        return res[0] if len(res) == 1 else tuple(res)
+
+
 class CloudProcessor:
     """``ppf::CloudProcessor``: holds the scene cloud, the depth image, the detector's boxes, the per-object clouds
     and the PPF detectors; every method is the reference's, in the order its driver calls them
@@ -831,6 +906,10 @@ class CloudProcessor:
         self.segment_labels: Optional[np.ndarray] = None
         self.segment_stats: Dict[str, object] = {}
         self._depth_normals_of: tuple = (None, None)  # the (scene, depth) pair Deprojection(normals=...) last made
+        # RecognizeFrame: per detection its (label, score, precision, recall) candidates, best first, and the counters
+        self.frame_candidates: List[List[tuple]] = []
+        self.recognize_stats: Dict[str, object] = {}
+        self._recognizer: Optional[tuple] = None  # (the detectors' model handles, their Recognizer)
 
     # ---- the PCL half -------------------------------------------------------------------------------------
     def Deprojection(self, CameraIntr, fp64: bool = False, normals: Optional[dict] = None) -> DeviceCloud:
@@ -951,6 +1030,23 @@ class CloudProcessor:
         self.object_mats = [o for o, _ in pairs]
         self.edge_mats = [e for _, e in pairs]
         return pairs
+
+    def RecognizeFrame(self, top: int = 2, min_score: float = 0.0, min_precision: float = 0.0, max_rows: int = 512) -> List[Optional[str]]:
+        """Labels without a detector: the object clouds of the last PrepareFrame scored against every detector of
+        TrainDetector by their pair-feature keys (``Recognizer``, ppf_recognize_frame).  Sets ``frame_candidates`` -- per
+        detection its ``(label, score, precision, recall)`` list, best first, at most ``top`` -- and ``recognize_stats``;
+        returns the best label per detection, None where nothing passed ``min_score`` / ``min_precision``: exactly what
+        ``MatchFrame(labels)`` takes."""
+        if not self.detectors or not all(self.if_trained):
+            raise PPFError(_capi.PPF_ERR_NOT_TRAINED, "RecognizeFrame needs the detectors of TrainDetector")
+        handles = tuple(d._model for d in self.detectors)
+        if self._recognizer is None or self._recognizer[0] != handles:
+            self._recognizer = (handles, Recognizer(self.detectors))
+        prm = {"top": int(top), "min_score": float(min_score), "min_precision": float(min_precision), "max_rows": int(max_rows)}
+        ranked, self.recognize_stats = self._recognizer[1].recognize(self.object_mats, prm, return_stats=True)
+        self.frame_candidates = [[(self.id_to_label[int(r["model"])], float(r["score"]), float(r["precision"]), float(r["recall"]))
+                                  for r in rows] for rows in ranked]
+        return [c[0][0] if c else None for c in self.frame_candidates]
 
     def MatchFrame(self, labels: Sequence[Optional[str]], relativeSceneSampleStep: float = 0.05,
                    relativeSceneDistance: float = 0.05, one_pass: bool = True) -> List[Optional[Pose3D]]:

@@ -25,13 +25,13 @@
  *             k_group / k_vote)  ppf_pose_kernels.h (k_finalize, k_rank, clustering)  ppf_icp_kernels.h  ppf_prep_kernels.h
  *             ppf_depth_kernels.h  ppf_depth_normals_kernels.h  ppf_verify_kernels.h  ppf_render_kernels.h  ppf_select_kernels.h  ppf_refine_kernels.h
  *             ppf_register_kernels.h  ppf_plane_kernels.h  ppf_label_kernels.h  ppf_cluster_kernels.h  ppf_region_kernels.h  ppf_filter_kernels.h
- *             ppf_segment_kernels.h
+ *             ppf_segment_kernels.h  ppf_recognize_kernels.h
  *   host      ppf_device_mem.h (errors, block cache)  ppf_host_common.h (scans, sorts, model / workspace structs)
  *             ppf_model_host.h  ppf_match_host.h  ppf_batch_host.h  ppf_icp_host.h  ppf_prep_host.h (the segmented
  *             preparation stages; ppf_prep_* = one segment)  ppf_frame_host.h (ppf_prep_frame = their chain)
  *             ppf_match_frame_host.h  ppf_depth_host.h  ppf_posetable_host.h  ppf_verify_host.h  ppf_render_host.h
  *             ppf_select_host.h  ppf_refine_host.h  ppf_register_host.h  ppf_plane_host.h  ppf_cluster_host.h  ppf_region_host.h
- *             ppf_filter_host.h  ppf_segment_host.h
+ *             ppf_filter_host.h  ppf_segment_host.h  ppf_recognize_host.h
  *             (the C-ABI)
  *
  * Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see __graft_entry__.build()).
@@ -76,6 +76,7 @@
 #include "ppf_label_kernels.h" /* uf_find, uf_unite, uf_root, cells_lower_bound, wave_max_by_key: no kernel */
 #include "ppf_cluster_kernels.h" /* k_clu_bounds, k_clu_grid, k_clu_keys, k_clu_runs, k_clu_cells, k_clu_link, k_clu_flatten ... k_clu_reduce */
 #include "ppf_segment_kernels.h" /* k_seg_classify, k_seg_tile, k_seg_merge, k_seg_flatten, k_seg_valid, k_seg_rank, k_seg_labels */
+#include "ppf_recognize_kernels.h" /* k_rec_dmax, k_rec_build, k_rec_popcount, k_rec_score, k_rec_finish */
 #include "ppf_region_kernels.h" /* k_reg_runs, k_reg_link, k_reg_flatten, k_reg_attach */
 #include "ppf_pose_kernels.h"  /* k_finalize, k_rank, clustering, result blocks */
 #include "ppf_host_common.h"   /* scans, sorts, sampling, ppf_model / ppf_workspace, enqueue_cluster */
@@ -98,3 +99,4 @@
 #include "ppf_region_host.h"      /* a cloud split into smooth surface regions: ppf_prep_regions */
 #include "ppf_filter_host.h"      /* a depth image without flying pixels, smoothed inside each surface: ppf_depth_filter */
 #include "ppf_segment_host.h"     /* a depth image's surfaces labelled in image space: ppf_depth_segments */
+#include "ppf_recognize_host.h"   /* which trained models a proposal can be a view of: ppf_recognizer_*, ppf_recognize_frame */
