@@ -23,6 +23,7 @@
  *   k4a::transformation::depth_image_to_color_camera (k4a_grabber.h:339, :391) -> DepthMap::registerDepth / registerDepthU16
  *                                                     (a raw sensor depth frame aligned to the colour camera; Cloud::fromDepth takes it)
  *   (nothing: a sensor pipeline's depth clean-up)     ->  filterDepth / filterDepthU16 / DepthMap::registerFiltered
+ *   (nothing: the frames of a fixed camera fused)     ->  DepthHistory::push / pushU16
  *   (nothing: the boxes come from YOLO)               ->  segmentDepth / segmentDepthU16  (the depth image's surfaces as labels and boxes)
  *   (nothing: the labels come from YOLO)              ->  Recognizer::recognize  (per proposal cloud the trained models it can be a view of)
  *
@@ -565,6 +566,74 @@ inline std::vector<float> filterDepthU16(const uint16_t* depth, int rows, int co
                                          float zMin = 0.f, float zMax = 0.f, size_t rowPitchBytes = 0, ppf_depth_filter_stats* stats = 0) {
   return filterDepthImage(depth, PPF_DEPTH_U16, scale, rows, cols, params, zMin, zMax, rowPitchBytes, stats);
 }
+
+/* ppf_depth_history: the last `window` depth images of a fixed camera, resident on the device; push takes the
+ * next frame and returns the fused image (float32 metres, packed rows x cols, 0 where nothing is written), which filterDepth,
+ * Cloud::fromDepth and every frame stage take.  format: PPF_DEPTH_F32 (push) or PPF_DEPTH_U16 (pushU16, z = d * scale metres).
+ * Copies share the history. */
+class DepthHistory {
+ public:
+  static ppf_depth_history_params defaultParams() {
+    ppf_depth_history_params p;
+    ppf_default_depth_history_params(&p);
+    return p;
+  }
+  DepthHistory() : rows_(0), cols_(0) {}
+  DepthHistory(int rows, int cols, const ppf_depth_history_params* params = 0, int format = PPF_DEPTH_F32, double scale = 0.001,
+               float zMin = 0.f, float zMax = 0.f)
+      : rows_(rows), cols_(cols) {
+    ppf_depth_params dp;
+    ppf_default_depth_params(&dp);
+    dp.format = format;
+    dp.depth_scale = scale;
+    dp.z_min = zMin;
+    dp.z_max = zMax;
+    const ppf_depth_history_params hp = params ? *params : defaultParams();
+    ppf_depth_history* h = nullptr;
+    ppf_match_3d::check(ppf_depth_history_create(rows, cols, &dp, &hp, &h));
+    h_ = std::shared_ptr<ppf_depth_history>(h, [](ppf_depth_history* p) { ppf_depth_history_release(p); });
+  }
+  int rows() const { return rows_; }
+  int cols() const { return cols_; }
+  ppf_depth_history* handle() const { return h_.get(); }
+
+  /* float32 metres in; rowPitchBytes 0: packed rows; state: 0, or it receives the packed rows x cols state image */
+  std::vector<float> push(const float* depth, std::vector<uint8_t>* state = 0, ppf_depth_history_stats* stats = 0, size_t rowPitchBytes = 0) {
+    return run(depth, state, stats, rowPitchBytes);
+  }
+  /* a 16-bit sensor image, for a history made with PPF_DEPTH_U16 */
+  std::vector<float> pushU16(const uint16_t* depth, std::vector<uint8_t>* state = 0, ppf_depth_history_stats* stats = 0,
+                             size_t rowPitchBytes = 0) {
+    return run(depth, state, stats, rowPitchBytes);
+  }
+  /* forget every frame */
+  void reset() { ppf_match_3d::check(ppf_depth_history_reset(need())); }
+  ppf_depth_history_desc info() const {
+    ppf_depth_history_desc d;
+    ppf_match_3d::check(ppf_depth_history_info(need(), &d));
+    return d;
+  }
+
+ private:
+  ppf_depth_history* need() const {
+    if (!h_) throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::DepthHistory: empty handle");
+    return h_.get();
+  }
+  std::vector<float> run(const void* depth, std::vector<uint8_t>* state, ppf_depth_history_stats* stats, size_t rowPitchBytes) {
+    const size_t n = (size_t)rows_ * (size_t)cols_;
+    std::vector<float> out(n + 1);
+    std::vector<uint8_t> st(state ? n + 1 : 1);
+    ppf_match_3d::check(ppf_depth_history_push(need(), depth, rowPitchBytes, &out[0], state ? &st[0] : 0, stats));
+    out.resize(n);
+    if (state) {
+      st.resize(n);
+      state->swap(st);
+    }
+    return out;
+  }
+  std::shared_ptr<ppf_depth_history> h_;
+  int rows_, cols_;
+};
 
 /* ppf_depth_segments: the depth image's connected surfaces labelled in image space.  Returns the label image
  * (packed rows x cols: a pixel's segment rank, largest segment 0, or -1) and fills `info` with one record per segment, whose

@@ -693,6 +693,88 @@ ppf_status ppf_depth_filter(const void* depth, int rows, int cols, size_t row_pi
 ppf_status ppf_depth_filter_device(const void* d_depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
                                    const ppf_depth_filter_params* fp, float* d_out, void* stream, ppf_depth_filter_stats* stats);
 
+/* ---- the last frames of a fixed camera fused into one depth image: noise, holes and flicker ---------- */
+#define PPF_HISTORY_MEAN 1        /* flags: the mean of the consensus instead of its lower median */
+#define PPF_HISTORY_MAX_WINDOW 16
+#define PPF_HISTORY_MAX_AGE 15
+#define PPF_HISTORY_MEASURED 1    /* state values: the newest frame has the pixel */
+#define PPF_HISTORY_FILLED 2      /*   an older frame fills the hole */
+#define PPF_HISTORY_UNSUPPORTED 3 /*   fewer than min_support frames agree with the anchor */
+#define PPF_HISTORY_CHANGED 16    /* state bit, on top of PPF_HISTORY_MEASURED: the newest sample agrees with nothing remembered */
+typedef struct ppf_depth_history_params {
+  int32_t window;      /* K, 1..16: the frames remembered, the pushed one included; default 8 */
+  float range_abs;     /* finite, > 0, metres; default 0.01 */
+  float range_quad;    /* finite, >= 0, 1/metres: the range grows by range_quad * z^2; default 0 */
+  int32_t min_support; /* 1..window; default 1 */
+  int32_t max_age;     /* 0..15: how old a sample may be and still fill a hole; 0: no hole filling; default 7 */
+  int32_t flags;       /* 0 | PPF_HISTORY_MEAN */
+  int32_t reserved[4];
+} ppf_depth_history_params;
+typedef struct ppf_depth_history_stats {
+  int32_t n_kept;                                       /* kept pixels of the pushed frame */
+  int32_t n_measured, n_filled, n_unsupported, n_empty; /* pixels per state: they add up to rows * cols */
+  int32_t n_changed;                                    /* measured pixels with PPF_HISTORY_CHANGED */
+  int64_t frame;                                        /* t of this push: pushes before it since creation or the last reset */
+  int32_t n_launches;                                   /* kernel launches of the call: 1 */
+  int32_t n_host_syncs;                                 /* blocking waits of the call: 1 */
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_depth_history_stats;
+typedef struct ppf_depth_history_desc {
+  int32_t rows, cols, window;
+  int32_t reserved0;
+  int64_t frames;        /* pushes since creation or the last reset */
+  uint64_t device_bytes; /* device memory the handle holds: the ring and its counters */
+  int32_t reserved[4];
+} ppf_depth_history_desc;
+typedef struct ppf_depth_history ppf_depth_history;
+/* window 8, range_abs 0.01, range_quad 0, min_support 1, max_age 7, flags 0 */
+void ppf_default_depth_history_params(ppf_depth_history_params* p);
+/* A ppf_depth_history keeps the last K = window depth images of one camera on the device and turns every pushed frame into
+ * one fused image.  It is made for one image size, one ppf_depth_params (format, depth_scale, z_min, z_max; flags is ignored)
+ * and one ppf_depth_history_params.  Every operation is fp64 as written, nothing fused; z(p) and "kept" are
+ * ppf_cloud_from_depth's.  Let t be the number of pushes since creation or the last reset -- the pushed frame is frame t --
+ * and n_hist = min(t + 1, K).  Per pixel, s_a for the age a = 0 .. n_hist - 1 is the float z of frame t - a where that frame
+ * kept the pixel, and "none" elsewhere.
+ *  1. Anchor.  a* is the smallest a in 0 .. min(max_age, n_hist - 1) with s_a kept.  None: out = 0, state = 0 (empty).
+ *  2. Consensus.  Za = (double)s_a*, R = (double)range_abs + (double)range_quad * (Za * Za),
+ *     C = {a in 0 .. n_hist - 1 : s_a kept and fabs((double)s_a - Za) <= R}, n = |C| >= 1.
+ *  3. Support.  n < min_support: out = 0, state = PPF_HISTORY_UNSUPPORTED.
+ *  4. Value.  Without PPF_HISTORY_MEAN the element of rank (n - 1) / 2 (integer division: the lower median) of C's values in
+ *     ascending order -- a kept value is finite and > 0, so equal values have equal bytes and no tie rule is needed; no
+ *     arithmetic touches the value.  With it: sum = 0.0; for a = n_hist - 1 down to 0 (oldest first), a in C:
+ *     sum = sum + (double)s_a; out = (float)(sum / (double)n).
+ *  5. State.  PPF_HISTORY_MEASURED when a* = 0, PPF_HISTORY_FILLED when a* > 0.  When a* = 0, n = 1 and some older s_a is
+ *     kept, PPF_HISTORY_CHANGED is OR-ed in: the newest sample disagrees with everything remembered.
+ * With a* = 0 the consensus is taken around the newest sample: a surface that moved is followed in the frame it moves and
+ * nothing ghosts.  With window 1 the output is the kept pixels of the input, byte for byte.
+ * rows, cols and dp are ppf_cloud_from_depth's with their errors; dp or hp NULL, a field outside the range stated beside it,
+ * an unknown flag or out NULL are PPF_ERR_INVALID before any device work; without a device the call is PPF_ERR_HIP; a ring
+ * (window x rows x cols floats, rows padded to four pixels) that cannot be allocated is PPF_ERR_NOMEM.  On any error *out is
+ * NULL. */
+ppf_status ppf_depth_history_create(int rows, int cols, const ppf_depth_params* dp, const ppf_depth_history_params* hp,
+                                    ppf_depth_history** out);
+/* Push one frame: a HOST image of the history's size and format whose rows are row_pitch_bytes apart (0: packed), with the
+ * pointer, pitch and alignment rules of ppf_cloud_from_depth.  out: float32 metres, packed rows x cols, 0.0f where nothing is
+ * written: what ppf_depth_filter, ppf_cloud_from_depth*, ppf_depth_register and the frame stages take as PPF_DEPTH_F32.
+ * state: packed rows x cols uint8, or NULL.  One launch and one blocking wait whatever the image and the history hold.  A
+ * NULL handle, image or out, or a bad pitch, is PPF_ERR_INVALID before any device work.  On any error *stats is zero, out and
+ * state are not touched and t does not advance.  Pushes on one history are serialised inside the library; different
+ * histories may be pushed from different threads. */
+ppf_status ppf_depth_history_push(ppf_depth_history* h, const void* depth, size_t row_pitch_bytes, float* out,
+                                  uint8_t* state /* may be NULL */, ppf_depth_history_stats* stats /* may be NULL */);
+/* the same between DEVICE buffers, as ppf_depth_filter_device: enqueued on `stream` (a hipStream_t, NULL: default stream),
+ * returns when the image is complete.  A pointer the current device cannot read, a buffer that runs past the end of its
+ * allocation, or an output overlapping the depth image or the other output is PPF_ERR_INVALID before anything is launched. */
+ppf_status ppf_depth_history_push_device(ppf_depth_history* h, const void* d_depth, size_t row_pitch_bytes, float* d_out,
+                                         uint8_t* d_state /* may be NULL */, void* stream,
+                                         ppf_depth_history_stats* stats /* may be NULL */);
+/* t back to 0: the next push sees no older frame.  The ring is not cleared, n_hist bounds what is read. */
+ppf_status ppf_depth_history_reset(ppf_depth_history* h);
+/* the size, the window, the pushes since the last reset and the device memory held */
+ppf_status ppf_depth_history_info(const ppf_depth_history* h, ppf_depth_history_desc* info);
+ppf_status ppf_depth_history_release(ppf_depth_history* h);
+
 /* ---- a depth image's surfaces labelled in image space: proposals without leaving the image ----------- */
 #define PPF_SEGMENT_EIGHT 1      /* flags: 8-connectivity instead of 4 */
 #define PPF_SEGMENT_UNORIENTED 2 /* flags: normals agree on |dot|, as PPF_REGION_UNORIENTED */

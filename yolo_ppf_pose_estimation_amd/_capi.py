@@ -139,6 +139,28 @@ class DepthFilterStats(C.Structure):
 PPF_DEPTH_FILTER_MAX_RADIUS = 8
 
 
+class DepthHistoryParams(C.Structure):
+    _fields_ = [("window", C.c_int32), ("range_abs", C.c_float), ("range_quad", C.c_float), ("min_support", C.c_int32),
+                ("max_age", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class DepthHistoryStats(C.Structure):
+    _fields_ = [("n_kept", C.c_int32), ("n_measured", C.c_int32), ("n_filled", C.c_int32), ("n_unsupported", C.c_int32),
+                ("n_empty", C.c_int32), ("n_changed", C.c_int32), ("frame", C.c_int64), ("n_launches", C.c_int32),
+                ("n_host_syncs", C.c_int32), ("ms_wall", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+class DepthHistoryDesc(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("window", C.c_int32), ("reserved0", C.c_int32), ("frames", C.c_int64),
+                ("device_bytes", C.c_uint64), ("reserved", C.c_int32 * 4)]
+
+
+PPF_HISTORY_MEAN = 1  # DepthHistoryParams.flags bit
+PPF_HISTORY_MAX_WINDOW = 16
+PPF_HISTORY_MAX_AGE = 15
+PPF_HISTORY_MEASURED, PPF_HISTORY_FILLED, PPF_HISTORY_UNSUPPORTED, PPF_HISTORY_CHANGED = 1, 2, 3, 16  # the state image
+
+
 class SegmentParams(C.Structure):
     _fields_ = [("depth_abs", C.c_float), ("depth_quad", C.c_float), ("normal_cos", C.c_float), ("curvature_threshold", C.c_float),
                 ("min_size", C.c_int32), ("max_size", C.c_int32), ("max_segments", C.c_int32), ("flags", C.c_int32),
@@ -425,6 +447,14 @@ _SIGNATURES = {
                                    C.c_void_p, C.POINTER(DepthFilterStats)]),
     "ppf_depth_filter_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(DepthParams),
                                           C.POINTER(DepthFilterParams), C.c_void_p, C.c_void_p, C.POINTER(DepthFilterStats)]),
+    "ppf_default_depth_history_params": (None, [C.POINTER(DepthHistoryParams)]),
+    "ppf_depth_history_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(DepthParams), C.POINTER(DepthHistoryParams), C.POINTER(C.c_void_p)]),
+    "ppf_depth_history_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(DepthHistoryStats)]),
+    "ppf_depth_history_push_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(DepthHistoryStats)]),
+    "ppf_depth_history_reset": (C.c_int, [C.c_void_p]),
+    "ppf_depth_history_info": (C.c_int, [C.c_void_p, C.POINTER(DepthHistoryDesc)]),
+    "ppf_depth_history_release": (C.c_int, [C.c_void_p]),
     "ppf_default_segment_params": (None, [C.POINTER(SegmentParams)]),
     "ppf_depth_segments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(DepthParams), C.c_void_p,
                                      C.POINTER(SegmentParams), C.c_void_p, C.POINTER(SegmentInfo), C.POINTER(C.c_int32),

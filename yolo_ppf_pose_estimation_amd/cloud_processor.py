@@ -697,6 +697,91 @@ def filter_depth(depth, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max
     return (out, _capi.stats_dict(st)) if return_stats else out
 
 
+class DepthHistory:
+    """The last ``window`` depth images of a fixed camera, resident on the device, and the image they fuse into
+    (ppf_depth_history): ``push`` takes a frame and gives the fused float32 image -- less noise, the holes of
+    this frame filled from the frames before it, flickering pixels gone -- that ``filter_depth``, ``DeviceCloud.from_depth``
+    and the frame stages take.  shape: (rows, cols) of every frame; dtype: numpy float32 (metres) or uint16 (units of
+    depth_scale metres), fixed like the shape; params: a DepthHistoryParams, a dict of its fields (window, range_abs,
+    range_quad, min_support, max_age, flags) or None (the defaults)."""
+
+    def __init__(self, shape, *, dtype=np.float32, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0, params=None):
+        self._ptr = None
+        self.params = _params(_capi.DepthHistoryParams, "ppf_default_depth_history_params", params, "depth history")
+        fmt = {np.dtype(np.float32): _capi.PPF_DEPTH_F32, np.dtype(np.uint16): _capi.PPF_DEPTH_U16}.get(np.dtype(dtype))
+        if fmt is None or len(tuple(shape)) != 2:
+            raise PPFError(_capi.PPF_ERR_INVALID, "a depth history takes a (rows, cols) shape and float32 or uint16 frames")
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.dtype = np.dtype(dtype)
+        dp = _capi.DepthParams()
+        lib().ppf_default_depth_params(C.byref(dp))
+        dp.format, dp.depth_scale, dp.z_min, dp.z_max = fmt, float(depth_scale), float(z_min), float(z_max)
+        ptr = C.c_void_p()
+        check(lib().ppf_depth_history_create(self.shape[0], self.shape[1], C.byref(dp), C.byref(self.params), C.byref(ptr)))
+        self._ptr = ptr
+
+    def __del__(self):
+        try:
+            if self._ptr is not None:
+                lib().ppf_depth_history_release(self._ptr)
+                self._ptr = None
+        except Exception:
+            pass
+
+    def reset(self) -> None:
+        """forget every frame: the next push sees no older one"""
+        check(lib().ppf_depth_history_reset(self._ptr))
+
+    def info(self) -> dict:
+        """rows, cols, window, frames (pushes since the last reset) and device_bytes"""
+        d = _capi.DepthHistoryDesc()
+        check(lib().ppf_depth_history_info(self._ptr, C.byref(d)))
+        return {k: v for k, v in _capi.stats_dict(d).items() if not k.startswith("reserved")}
+
+    def push(self, depth, out=None, return_state: bool = False, return_stats: bool = False):
+        """Push one frame and get the fused image (float32 metres, 0 where nothing is written).  depth: a 2-D numpy array of
+        the history's shape and dtype, rows read at its stride, which gives a numpy image; or such a torch tensor on the GPU,
+        read in place on ``torch.cuda.current_stream()`` (ppf_depth_history_push_device), which gives a float32 tensor on the
+        same device (or fills ``out``, which must not overlap the input).  return_state adds the uint8 state image (0 empty,
+        1 measured, 2 filled, 3 unsupported, +16 changed), return_stats the counters: (image[, state][, stats])."""
+        st = _capi.DepthHistoryStats()
+        shape = self.shape
+        if type(depth).__module__.startswith("torch") and depth.is_cuda:
+            import torch
+            want = {np.dtype(np.float32): torch.float32, np.dtype(np.uint16): torch.uint16}[self.dtype]
+            if depth.dtype != want or depth.dim() != 2 or tuple(depth.shape) != shape:
+                raise PPFError(_capi.PPF_ERR_INVALID, f"depth must be a {self.dtype} tensor of shape {shape}")
+            if depth.stride(1) != 1 or depth.stride(0) < depth.shape[1]:
+                depth = depth.contiguous()
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float32, device=depth.device)
+            elif not (out.is_cuda and out.device == depth.device and out.dtype == torch.float32 and tuple(out.shape) == shape
+                      and out.is_contiguous()):
+                raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous float32 tensor of shape {shape} on the depth image's device")
+            state = torch.empty(shape, dtype=torch.uint8, device=depth.device) if return_state else None
+            with torch.cuda.device(depth.device):
+                stream = torch.cuda.current_stream(depth.device).cuda_stream
+                check(lib().ppf_depth_history_push_device(self._ptr, C.c_void_p(depth.data_ptr()), depth.stride(0) * depth.element_size(),
+                                                          C.c_void_p(out.data_ptr()), C.c_void_p(state.data_ptr()) if return_state else None,
+                                                          C.c_void_p(stream) if stream else None, C.byref(st)))
+        else:
+            a = np.asarray(depth.numpy() if type(depth).__module__.startswith("torch") else depth)
+            if a.dtype != self.dtype or a.ndim != 2 or a.shape != shape:
+                raise PPFError(_capi.PPF_ERR_INVALID, f"depth must be a {self.dtype} array of shape {shape}")
+            if a.strides[1] != a.itemsize or a.strides[0] < a.shape[1] * a.itemsize or a.strides[0] % a.itemsize:
+                a = np.ascontiguousarray(a)
+            if out is None:
+                out = np.empty(shape, np.float32)
+            elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == shape and out.flags.c_contiguous
+                      and out.flags.writeable):
+                raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous float32 array of shape {shape}")
+            state = np.empty(shape, np.uint8) if return_state else None
+            check(lib().ppf_depth_history_push(self._ptr, C.c_void_p(a.ctypes.data), a.strides[0], out.ctypes.data,
+                                               state.ctypes.data if return_state else None, C.byref(st)))
+        res = (out,) + ((state,) if return_state else ()) + ((_capi.stats_dict(st),) if return_stats else ())
+        return res if len(res) > 1 else out
+
+
 # ppf_segment_info as a numpy record
 SEGMENT_INFO = np.dtype([("n_pixels", "<i4"), ("n_border", "<i4"), ("first_pixel", "<i4"), ("box_xywh", "<i4", 4), ("z_lo", "<f4"),
                          ("z_hi", "<f4"), ("reserved", "<i4", 3)])
@@ -901,6 +986,10 @@ class CloudProcessor:
         self.cluster_info: Optional[np.ndarray] = None
         self.cluster_stats: Dict[str, object] = {}
         self.depth_filter_stats: Dict[str, object] = {}  # FilterDepth: the ppf_depth_filter counters
+        # FuseDepth: the ppf_depth_history counters and state image of the last frame, and the history with what it was made for
+        self.depth_history_stats: Dict[str, object] = {}
+        self.depth_state = None
+        self._depth_history: Optional[tuple] = None
         # ProposeSegments: the info rows of the image's segments, its label image and the counters
         self.segment_info: Optional[np.ndarray] = None
         self.segment_labels: Optional[np.ndarray] = None
@@ -929,6 +1018,23 @@ class CloudProcessor:
         if self.depth is None:
             raise PPFError(_capi.PPF_ERR_INVALID, "FilterDepth needs a depth image")
         self.depth, self.depth_filter_stats = filter_depth(self.depth, params=params, return_stats=True)
+        return self.depth
+
+    def FuseDepth(self, depth, params=None):
+        """The next frame of a fixed camera fused with the frames before it (``DepthHistory.push``): less noise, this frame's
+        holes filled, flicker gone.  depth: the new frame, as ``DepthHistory.push`` takes it; params: the fields of
+        ppf_depth_history_params (window, range_abs, range_quad, min_support, max_age, flags).  The processor keeps one
+        history; it starts afresh when the frame's shape, dtype or the parameters change.  Sets ``self.depth`` to the fused
+        image, ``depth_history_stats`` and ``depth_state`` (the uint8 state image); returns the fused image, so FilterDepth /
+        Deprojection follow as on a single frame."""
+        if depth is None or not hasattr(depth, "shape") or len(depth.shape) != 2:
+            raise PPFError(_capi.PPF_ERR_INVALID, "FuseDepth needs a 2-D depth image")
+        prm = _params(_capi.DepthHistoryParams, "ppf_default_depth_history_params", params, "depth history")
+        dtype = np.dtype(str(depth.dtype).replace("torch.", ""))
+        key = (tuple(depth.shape), dtype, bytes(prm))
+        if self._depth_history is None or self._depth_history[0] != key:
+            self._depth_history = (key, DepthHistory(tuple(depth.shape), dtype=dtype, params=prm))
+        self.depth, self.depth_state, self.depth_history_stats = self._depth_history[1].push(depth, return_state=True, return_stats=True)
         return self.depth
 
     def RemovePlanes(self, **params) -> DeviceCloud:
