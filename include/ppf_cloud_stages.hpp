@@ -43,6 +43,18 @@
 namespace ppfhip {
 namespace prep {
 
+/* ppf_depth_params of an image of `format` (PPF_DEPTH_F32: metres; PPF_DEPTH_U16: units of `scale` metres) kept inside zMin..zMax */
+inline ppf_depth_params depthParams(int format, double scale, float zMin, float zMax, int flags = 0) {
+  ppf_depth_params p;
+  ppf_default_depth_params(&p);
+  p.format = format;
+  p.flags = flags;
+  p.depth_scale = scale;
+  p.z_min = zMin;
+  p.z_max = zMax;
+  return p;
+}
+
 class Cloud {
  public:
   Cloud() {}
@@ -515,13 +527,7 @@ class Cloud {
   static Cloud fromDepthImage(const void* depth, int format, double scale, int rows, int cols, double fx, double fy, double ppx,
                               double ppy, float zMin, float zMax, bool fp64, size_t rowPitchBytes,
                               const ppf_depth_normal_params* normals = 0) {
-    ppf_depth_params p;
-    ppf_default_depth_params(&p);
-    p.format = format;
-    p.flags = fp64 ? PPF_DEPTH_FP64 : 0;
-    p.depth_scale = scale;
-    p.z_min = zMin;
-    p.z_max = zMax;
+    const ppf_depth_params p = depthParams(format, scale, zMin, zMax, fp64 ? PPF_DEPTH_FP64 : 0);
     const double intr[4] = {fx, fy, ppx, ppy};
     ppf_cloud* c = nullptr;
     ppf_match_3d::check(normals ? ppf_cloud_from_depth_normals(depth, rows, cols, rowPitchBytes, intr, &p, normals, &c)
@@ -544,12 +550,7 @@ inline ppf_depth_filter_params defaultDepthFilterParams() {
 }
 inline std::vector<float> filterDepthImage(const void* depth, int format, double scale, int rows, int cols, const ppf_depth_filter_params* params,
                                            float zMin, float zMax, size_t rowPitchBytes, ppf_depth_filter_stats* stats) {
-  ppf_depth_params dp;
-  ppf_default_depth_params(&dp);
-  dp.format = format;
-  dp.depth_scale = scale;
-  dp.z_min = zMin;
-  dp.z_max = zMax;
+  const ppf_depth_params dp = depthParams(format, scale, zMin, zMax);
   const ppf_depth_filter_params fp = params ? *params : defaultDepthFilterParams();
   std::vector<float> out((rows > 0 && cols > 0 ? (size_t)rows * (size_t)cols : 0) + 1);
   ppf_match_3d::check(ppf_depth_filter(depth, rows, cols, rowPitchBytes, &dp, &fp, &out[0], stats));
@@ -582,12 +583,7 @@ class DepthHistory {
   DepthHistory(int rows, int cols, const ppf_depth_history_params* params = 0, int format = PPF_DEPTH_F32, double scale = 0.001,
                float zMin = 0.f, float zMax = 0.f)
       : rows_(rows), cols_(cols) {
-    ppf_depth_params dp;
-    ppf_default_depth_params(&dp);
-    dp.format = format;
-    dp.depth_scale = scale;
-    dp.z_min = zMin;
-    dp.z_max = zMax;
+    const ppf_depth_params dp = depthParams(format, scale, zMin, zMax);
     const ppf_depth_history_params hp = params ? *params : defaultParams();
     ppf_depth_history* h = nullptr;
     ppf_match_3d::check(ppf_depth_history_create(rows, cols, &dp, &hp, &h));
@@ -647,12 +643,7 @@ inline ppf_segment_params defaultSegmentParams() {
 inline std::vector<int32_t> segmentDepthImage(const void* depth, int format, double scale, int rows, int cols, const Cloud* normals,
                                               const ppf_segment_params* params, std::vector<ppf_segment_info>& info, float zMin, float zMax,
                                               size_t rowPitchBytes, int32_t* counts, ppf_segment_stats* stats) {
-  ppf_depth_params dp;
-  ppf_default_depth_params(&dp);
-  dp.format = format;
-  dp.depth_scale = scale;
-  dp.z_min = zMin;
-  dp.z_max = zMax;
+  const ppf_depth_params dp = depthParams(format, scale, zMin, zMax);
   const ppf_segment_params sp = params ? *params : defaultSegmentParams();
   const int slots = sp.max_segments >= 1 && sp.max_segments <= PPF_CLUSTER_MAX_CLUSTERS ? sp.max_segments : 1;
   std::vector<int32_t> labels((rows > 0 && cols > 0 ? (size_t)rows * (size_t)cols : 0) + 1);
@@ -791,12 +782,7 @@ class DepthMap {
   std::vector<float> run(const void* depth, int format, double scale, float zMin, float zMax, size_t rowPitchBytes,
                          const ppf_register_params* params, ppf_register_stats* stats) const {
     if (!h_) throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::DepthMap: empty handle");
-    ppf_depth_params dp;
-    ppf_default_depth_params(&dp);
-    dp.format = format;
-    dp.depth_scale = scale;
-    dp.z_min = zMin;
-    dp.z_max = zMax;
+    const ppf_depth_params dp = depthParams(format, scale, zMin, zMax);
     ppf_register_params rp;
     if (params) rp = *params; else ppf_default_register_params(&rp);
     std::vector<float> out((size_t)rows_ * (size_t)cols_ + 1);

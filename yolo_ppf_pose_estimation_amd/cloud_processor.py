@@ -6,7 +6,9 @@ device between stages (``DeviceCloud`` wraps a ``ppf_cloud*``).  Method names, a
 reference's; the YOLO detector that supplies ``boxes`` is out of scope."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import functools
 import time
 from typing import Dict, List, Optional, Sequence
 
@@ -60,10 +62,7 @@ class DeviceCloud:
             depth = filter_depth(depth, depth_scale=depth_scale, z_min=z_min, z_max=z_max, params=filter)
         K = np.asarray(intr, dtype=np.float64)
         it = (C.c_double * 4)(*([K[0, 0], K[1, 1], K[0, 2], K[1, 2]] if K.shape == (3, 3) else [float(v) for v in K.reshape(-1)[:4]]))
-        prm = _capi.DepthParams()
-        lib().ppf_default_depth_params(C.byref(prm))
-        prm.depth_scale, prm.z_min, prm.z_max = float(depth_scale), float(z_min), float(z_max)
-        prm.flags = _capi.PPF_DEPTH_FP64 if fp64 else 0
+        prm = _depth_params(depth_scale, z_min, z_max, _capi.PPF_DEPTH_FP64 if fp64 else 0)
         nprm = None
         if normals is not None:
             unknown = set(normals) - {"radius", "max_depth_change", "min_neighbours", "drop"}
@@ -75,40 +74,13 @@ class DeviceCloud:
             nprm.max_depth_change = float(normals.get("max_depth_change", nprm.max_depth_change))
             nprm.min_neighbours = int(normals.get("min_neighbours", nprm.min_neighbours))
             nprm.flags = _capi.PPF_DEPTH_NORMALS_DROP if normals.get("drop", False) else 0
+        inp = _DepthInput(depth, "depth must be a 2-D float32 or uint16 {kind}")
+        prm.format = inp.format
         out = C.c_void_p()
-        if type(depth).__module__.startswith("torch"):
-            import torch
-            if not depth.is_cuda:
-                depth = depth.numpy()
-            else:
-                fmt = {torch.float32: _capi.PPF_DEPTH_F32, torch.uint16: _capi.PPF_DEPTH_U16}.get(depth.dtype)
-                if fmt is None or depth.dim() != 2:
-                    raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 or uint16 tensor")
-                if depth.stride(1) != 1 or depth.stride(0) < depth.shape[1]:
-                    depth = depth.contiguous()
-                prm.format = fmt
-                with torch.cuda.device(depth.device):
-                    stream = torch.cuda.current_stream(depth.device).cuda_stream
-                    args = (C.c_void_p(depth.data_ptr()), depth.shape[0], depth.shape[1], depth.stride(0) * depth.element_size(), it,
-                            C.byref(prm))
-                    st = C.c_void_p(stream) if stream else None
-                    if nprm is None:
-                        check(lib().ppf_cloud_from_depth_device(*args, st, C.byref(out)))
-                    else:
-                        check(lib().ppf_cloud_from_depth_normals_device(*args, C.byref(nprm), st, C.byref(out)))
-                return cls(out)
-        a = np.asarray(depth)
-        fmt = {np.dtype(np.float32): _capi.PPF_DEPTH_F32, np.dtype(np.uint16): _capi.PPF_DEPTH_U16}.get(a.dtype)
-        if fmt is None or a.ndim != 2:
-            raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 or uint16 array")
-        if a.strides[1] != a.itemsize or a.strides[0] < a.shape[1] * a.itemsize or a.strides[0] % a.itemsize:
-            a = np.ascontiguousarray(a)
-        prm.format = fmt
-        args = (C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1], a.strides[0], it, C.byref(prm))
-        if nprm is None:
-            check(lib().ppf_cloud_from_depth(*args, C.byref(out)))
-        else:
-            check(lib().ppf_cloud_from_depth_normals(*args, C.byref(nprm), C.byref(out)))
+        name = "ppf_cloud_from_depth" + ("_normals" if nprm is not None else "") + ("_device" if inp.is_device else "")
+        with inp.device():
+            tail = (() if nprm is None else (C.byref(nprm),)) + ((inp.stream(),) if inp.is_device else ())
+            check(getattr(lib(), name)(inp.ptr, inp.rows, inp.cols, inp.pitch, it, C.byref(prm), *tail, C.byref(out)))
         return cls(out)
 
     def __del__(self):
@@ -372,6 +344,91 @@ def _depth_image(depth, error: str):
     return (img,) + img.shape
 
 
+_DEPTH_FORMATS = {np.dtype(np.float32): _capi.PPF_DEPTH_F32, np.dtype(np.uint16): _capi.PPF_DEPTH_U16}   # by numpy dtype
+_NO_DEVICE = contextlib.nullcontext()
+
+
+@functools.lru_cache(maxsize=None)
+def _torch_formats():
+    """(torch, PPF_DEPTH_* by torch dtype): torch is only imported once a tensor has come in"""
+    import torch
+    return torch, {torch.float32: _capi.PPF_DEPTH_F32, torch.uint16: _capi.PPF_DEPTH_U16}
+
+
+def _depth_params(depth_scale, z_min, z_max, flags: int = 0) -> _capi.DepthParams:
+    dp = _capi.DepthParams()
+    lib().ppf_default_depth_params(C.byref(dp))
+    dp.depth_scale, dp.z_min, dp.z_max, dp.flags = float(depth_scale), float(z_min), float(z_max), flags
+    return dp
+
+
+class _DepthInput:
+    """A depth image as the entries take it: ``ptr``, ``rows``, ``cols``, ``pitch`` (bytes) and ``format`` of ``keep``, the
+    array or tensor they point into.  ``is_device``: a GPU tensor, for the ``*_device`` entry, called inside ``device()`` with
+    ``stream()``; otherwise a numpy array (a CPU tensor goes the numpy way) for the host entry."""
+
+    __slots__ = ("keep", "ptr", "rows", "cols", "shape", "pitch", "format", "is_device", "torch")
+
+    def __init__(self, depth, error: str, shape=None, dtype=None):
+        """shape and dtype (a numpy dtype): what the image must have, None for any 2-D float32 or uint16 image; error: the text
+        for a wrong dtype, rank or shape, formatted only when raised, with ``{kind}`` ("tensor" or "array"), ``{shape}`` and
+        ``{dtype}``.  Rows are read at their stride; an image whose strides are not row strides is copied."""
+        is_torch = type(depth).__module__.startswith("torch")
+        self.is_device = is_torch and depth.is_cuda
+        if self.is_device:
+            self.torch, formats = _torch_formats()
+        else:
+            depth, formats = np.asarray(depth.numpy() if is_torch else depth), _DEPTH_FORMATS
+        self.format = formats.get(depth.dtype)
+        self.shape = tuple(depth.shape)
+        if (self.format is None or len(self.shape) != 2 or (shape is not None and self.shape != tuple(shape))
+                or (dtype is not None and self.format != _DEPTH_FORMATS[dtype])):
+            raise PPFError(_capi.PPF_ERR_INVALID, error.format(kind="tensor" if self.is_device else "array", shape=shape, dtype=dtype))
+        self.rows, self.cols = self.shape
+        if self.is_device:
+            if depth.stride(1) != 1 or depth.stride(0) < self.cols:
+                depth = depth.contiguous()
+            self.ptr, self.pitch = C.c_void_p(depth.data_ptr()), depth.stride(0) * depth.element_size()
+        else:
+            size, (pitch, step) = depth.itemsize, depth.strides
+            if step != size or pitch < self.cols * size or pitch % size:
+                depth = np.ascontiguousarray(depth)
+                pitch = depth.strides[0]
+            self.ptr, self.pitch = C.c_void_p(depth.ctypes.data), pitch
+        self.keep = depth
+
+    def device(self):
+        """the context the entry is called in: the tensor's device made current, nothing for a host image"""
+        return self.torch.cuda.device(self.keep.device) if self.is_device else _NO_DEVICE
+
+    def stream(self):
+        """the ``stream`` argument of the device entry: the tensor's device's current stream, None for stream 0"""
+        stream = self.torch.cuda.current_stream(self.keep.device).cuda_stream
+        return C.c_void_p(stream) if stream else None
+
+    def output(self, out, dtype, shape=None, tensor_error: Optional[str] = None):
+        """(out, its pointer): ``out`` checked, or made when None -- a contiguous image of ``dtype`` (a numpy scalar type) and
+        ``shape`` (None: the input's) where the entry writes: a tensor on the input's device for a GPU input, a writeable
+        numpy array otherwise.  tensor_error: another text for a refused tensor, ``{shape}`` filled in when raised"""
+        shape = self.shape if shape is None else tuple(shape)
+        if self.is_device:
+            torch = self.torch
+            want = getattr(torch, dtype.__name__)
+            if out is None:
+                out = torch.empty(shape, dtype=want, device=self.keep.device)
+            elif not (getattr(out, "is_cuda", False) and out.device == self.keep.device and out.dtype == want
+                      and tuple(out.shape) == shape and out.is_contiguous()):
+                raise PPFError(_capi.PPF_ERR_INVALID, (tensor_error or "out must be a contiguous {dtype} tensor of shape {shape} on the "
+                                                       "depth image's device").format(dtype=dtype.__name__, shape=shape))
+            return out, C.c_void_p(out.data_ptr())
+        if out is None:
+            out = np.empty(shape, dtype)
+        elif not (isinstance(out, np.ndarray) and out.dtype == dtype and out.shape == shape and out.flags.c_contiguous
+                  and out.flags.writeable):
+            raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous {dtype.__name__} array of shape {shape}")
+        return out, C.c_void_p(out.ctypes.data)
+
+
 def _frame_tables(dets, poses, top):
     """the FrameDetection, Pose and count arrays of one call: dets[i] is (model cloud, object cloud) or None"""
     n = len(dets)
@@ -612,39 +669,19 @@ class DepthMap:
         ``torch.cuda.current_stream()`` (ppf_depth_register_device), which gives a float32 tensor on the same device (or
         fills ``out``).  params: a RegisterParams, a dict of its fields or None (the defaults)."""
         prm = _params(_capi.RegisterParams, "ppf_default_register_params", params)
-        dp = _capi.DepthParams()
-        lib().ppf_default_depth_params(C.byref(dp))
-        dp.depth_scale, dp.z_min, dp.z_max = float(depth_scale), float(z_min), float(z_max)
+        dp = _depth_params(depth_scale, z_min, z_max)
         st = _capi.RegisterStats()
-        if type(depth).__module__.startswith("torch") and depth.is_cuda:
-            import torch
-            fmt = {torch.float32: _capi.PPF_DEPTH_F32, torch.uint16: _capi.PPF_DEPTH_U16}.get(depth.dtype)
-            if fmt is None or depth.dim() != 2 or tuple(depth.shape) != self.depth_shape:
-                raise PPFError(_capi.PPF_ERR_INVALID, f"depth must be a float32 or uint16 tensor of shape {self.depth_shape}")
-            if depth.stride(1) != 1 or depth.stride(0) < depth.shape[1]:
-                depth = depth.contiguous()
-            if out is None:
-                out = torch.empty(self.color_shape, dtype=torch.float32, device=depth.device)
-            elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == self.color_shape and out.is_contiguous()):
-                raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous float32 GPU tensor of shape {self.color_shape}")
-            dp.format = fmt
-            with torch.cuda.device(depth.device):
-                stream = torch.cuda.current_stream(depth.device).cuda_stream
-                check(lib().ppf_depth_register_device(self._ptr, C.c_void_p(depth.data_ptr()), depth.stride(0) * depth.element_size(),
-                                                      C.byref(dp), C.byref(prm), C.c_void_p(out.data_ptr()),
-                                                      C.c_void_p(stream) if stream else None, C.byref(st)))
-            return (out, _capi.stats_dict(st)) if return_stats else out
-        a = np.asarray(depth.numpy() if type(depth).__module__.startswith("torch") else depth)
-        fmt = {np.dtype(np.float32): _capi.PPF_DEPTH_F32, np.dtype(np.uint16): _capi.PPF_DEPTH_U16}.get(a.dtype)
-        if fmt is None or a.ndim != 2 or a.shape != self.depth_shape:
-            raise PPFError(_capi.PPF_ERR_INVALID, f"depth must be a float32 or uint16 array of shape {self.depth_shape}")
-        if a.strides[1] != a.itemsize or a.strides[0] < a.shape[1] * a.itemsize or a.strides[0] % a.itemsize:
-            a = np.ascontiguousarray(a)
-        dp.format = fmt
-        img = np.empty(self.color_shape, np.float32)
-        check(lib().ppf_depth_register(self._ptr, C.c_void_p(a.ctypes.data), a.strides[0], C.byref(dp), C.byref(prm), img.ctypes.data,
-                                       C.byref(st)))
-        return (img, _capi.stats_dict(st)) if return_stats else img
+        inp = _DepthInput(depth, "depth must be a float32 or uint16 {kind} of shape {shape}", shape=self.depth_shape)
+        dp.format = inp.format
+        # a host image always gets a fresh numpy image
+        out, optr = inp.output(out if inp.is_device else None, np.float32, self.color_shape,
+                               "out must be a contiguous float32 GPU tensor of shape {shape}")
+        with inp.device():
+            if inp.is_device:
+                check(lib().ppf_depth_register_device(self._ptr, inp.ptr, inp.pitch, C.byref(dp), C.byref(prm), optr, inp.stream(), C.byref(st)))
+            else:
+                check(lib().ppf_depth_register(self._ptr, inp.ptr, inp.pitch, C.byref(dp), C.byref(prm), optr, C.byref(st)))
+        return (out, _capi.stats_dict(st)) if return_stats else out
 
 
 def filter_depth(depth, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0, params=None, out=None,
@@ -656,44 +693,16 @@ def filter_depth(depth, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max
     ``torch.cuda.current_stream()`` (ppf_depth_filter_device), which gives a float32 tensor on the same device (or fills
     ``out``, which must not overlap the input).  params: a DepthFilterParams, a dict of its fields or None (the defaults)."""
     prm = _params(_capi.DepthFilterParams, "ppf_default_depth_filter_params", params, "depth filter")
-    dp = _capi.DepthParams()
-    lib().ppf_default_depth_params(C.byref(dp))
-    dp.depth_scale, dp.z_min, dp.z_max = float(depth_scale), float(z_min), float(z_max)
+    dp = _depth_params(depth_scale, z_min, z_max)
     st = _capi.DepthFilterStats()
-    if type(depth).__module__.startswith("torch") and depth.is_cuda:
-        import torch
-        fmt = {torch.float32: _capi.PPF_DEPTH_F32, torch.uint16: _capi.PPF_DEPTH_U16}.get(depth.dtype)
-        if fmt is None or depth.dim() != 2:
-            raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 or uint16 tensor")
-        if depth.stride(1) != 1 or depth.stride(0) < depth.shape[1]:
-            depth = depth.contiguous()
-        shape = tuple(depth.shape)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=depth.device)
-        elif not (out.is_cuda and out.device == depth.device and out.dtype == torch.float32 and tuple(out.shape) == shape
-                  and out.is_contiguous()):
-            raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous float32 tensor of shape {shape} on the depth image's device")
-        dp.format = fmt
-        with torch.cuda.device(depth.device):
-            stream = torch.cuda.current_stream(depth.device).cuda_stream
-            check(lib().ppf_depth_filter_device(C.c_void_p(depth.data_ptr()), shape[0], shape[1], depth.stride(0) * depth.element_size(),
-                                                C.byref(dp), C.byref(prm), C.c_void_p(out.data_ptr()),
-                                                C.c_void_p(stream) if stream else None, C.byref(st)))
-        return (out, _capi.stats_dict(st)) if return_stats else out
-    a = np.asarray(depth.numpy() if type(depth).__module__.startswith("torch") else depth)
-    fmt = {np.dtype(np.float32): _capi.PPF_DEPTH_F32, np.dtype(np.uint16): _capi.PPF_DEPTH_U16}.get(a.dtype)
-    if fmt is None or a.ndim != 2:
-        raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 or uint16 array")
-    if a.strides[1] != a.itemsize or a.strides[0] < a.shape[1] * a.itemsize or a.strides[0] % a.itemsize:
-        a = np.ascontiguousarray(a)
-    dp.format = fmt
-    if out is None:
-        out = np.empty(a.shape, np.float32)
-    elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == a.shape and out.flags.c_contiguous
-              and out.flags.writeable):
-        raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous float32 array of shape {a.shape}")
-    check(lib().ppf_depth_filter(C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1], a.strides[0], C.byref(dp), C.byref(prm),
-                                 out.ctypes.data, C.byref(st)))
+    inp = _DepthInput(depth, "depth must be a 2-D float32 or uint16 {kind}")
+    dp.format = inp.format
+    out, optr = inp.output(out, np.float32)
+    with inp.device():
+        if inp.is_device:
+            check(lib().ppf_depth_filter_device(inp.ptr, inp.rows, inp.cols, inp.pitch, C.byref(dp), C.byref(prm), optr, inp.stream(), C.byref(st)))
+        else:
+            check(lib().ppf_depth_filter(inp.ptr, inp.rows, inp.cols, inp.pitch, C.byref(dp), C.byref(prm), optr, C.byref(st)))
     return (out, _capi.stats_dict(st)) if return_stats else out
 
 
@@ -708,14 +717,13 @@ class DepthHistory:
     def __init__(self, shape, *, dtype=np.float32, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0, params=None):
         self._ptr = None
         self.params = _params(_capi.DepthHistoryParams, "ppf_default_depth_history_params", params, "depth history")
-        fmt = {np.dtype(np.float32): _capi.PPF_DEPTH_F32, np.dtype(np.uint16): _capi.PPF_DEPTH_U16}.get(np.dtype(dtype))
+        fmt = _DEPTH_FORMATS.get(np.dtype(dtype))
         if fmt is None or len(tuple(shape)) != 2:
             raise PPFError(_capi.PPF_ERR_INVALID, "a depth history takes a (rows, cols) shape and float32 or uint16 frames")
         self.shape = (int(shape[0]), int(shape[1]))
         self.dtype = np.dtype(dtype)
-        dp = _capi.DepthParams()
-        lib().ppf_default_depth_params(C.byref(dp))
-        dp.format, dp.depth_scale, dp.z_min, dp.z_max = fmt, float(depth_scale), float(z_min), float(z_max)
+        dp = _depth_params(depth_scale, z_min, z_max)
+        dp.format = fmt
         ptr = C.c_void_p()
         check(lib().ppf_depth_history_create(self.shape[0], self.shape[1], C.byref(dp), C.byref(self.params), C.byref(ptr)))
         self._ptr = ptr
@@ -745,39 +753,14 @@ class DepthHistory:
         same device (or fills ``out``, which must not overlap the input).  return_state adds the uint8 state image (0 empty,
         1 measured, 2 filled, 3 unsupported, +16 changed), return_stats the counters: (image[, state][, stats])."""
         st = _capi.DepthHistoryStats()
-        shape = self.shape
-        if type(depth).__module__.startswith("torch") and depth.is_cuda:
-            import torch
-            want = {np.dtype(np.float32): torch.float32, np.dtype(np.uint16): torch.uint16}[self.dtype]
-            if depth.dtype != want or depth.dim() != 2 or tuple(depth.shape) != shape:
-                raise PPFError(_capi.PPF_ERR_INVALID, f"depth must be a {self.dtype} tensor of shape {shape}")
-            if depth.stride(1) != 1 or depth.stride(0) < depth.shape[1]:
-                depth = depth.contiguous()
-            if out is None:
-                out = torch.empty(shape, dtype=torch.float32, device=depth.device)
-            elif not (out.is_cuda and out.device == depth.device and out.dtype == torch.float32 and tuple(out.shape) == shape
-                      and out.is_contiguous()):
-                raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous float32 tensor of shape {shape} on the depth image's device")
-            state = torch.empty(shape, dtype=torch.uint8, device=depth.device) if return_state else None
-            with torch.cuda.device(depth.device):
-                stream = torch.cuda.current_stream(depth.device).cuda_stream
-                check(lib().ppf_depth_history_push_device(self._ptr, C.c_void_p(depth.data_ptr()), depth.stride(0) * depth.element_size(),
-                                                          C.c_void_p(out.data_ptr()), C.c_void_p(state.data_ptr()) if return_state else None,
-                                                          C.c_void_p(stream) if stream else None, C.byref(st)))
-        else:
-            a = np.asarray(depth.numpy() if type(depth).__module__.startswith("torch") else depth)
-            if a.dtype != self.dtype or a.ndim != 2 or a.shape != shape:
-                raise PPFError(_capi.PPF_ERR_INVALID, f"depth must be a {self.dtype} array of shape {shape}")
-            if a.strides[1] != a.itemsize or a.strides[0] < a.shape[1] * a.itemsize or a.strides[0] % a.itemsize:
-                a = np.ascontiguousarray(a)
-            if out is None:
-                out = np.empty(shape, np.float32)
-            elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == shape and out.flags.c_contiguous
-                      and out.flags.writeable):
-                raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous float32 array of shape {shape}")
-            state = np.empty(shape, np.uint8) if return_state else None
-            check(lib().ppf_depth_history_push(self._ptr, C.c_void_p(a.ctypes.data), a.strides[0], out.ctypes.data,
-                                               state.ctypes.data if return_state else None, C.byref(st)))
+        inp = _DepthInput(depth, "depth must be a {dtype} {kind} of shape {shape}", shape=self.shape, dtype=self.dtype)
+        out, optr = inp.output(out, np.float32)
+        state, sptr = inp.output(None, np.uint8) if return_state else (None, None)
+        with inp.device():
+            if inp.is_device:
+                check(lib().ppf_depth_history_push_device(self._ptr, inp.ptr, inp.pitch, optr, sptr, inp.stream(), C.byref(st)))
+            else:
+                check(lib().ppf_depth_history_push(self._ptr, inp.ptr, inp.pitch, optr, sptr, C.byref(st)))
         res = (out,) + ((state,) if return_state else ()) + ((_capi.stats_dict(st),) if return_stats else ())
         return res if len(res) > 1 else out
 
@@ -801,9 +784,7 @@ def segment_depth(depth, *, depth_scale: float = 0.001, z_min: float = 0.0, z_ma
     return_info adds the segments' ``SEGMENT_INFO`` records (one per segment) and the counts (segments, valid components,
     all components); return_stats adds the call's stats last."""
     prm = _params(_capi.SegmentParams, "ppf_default_segment_params", params, "segment")
-    dp = _capi.DepthParams()
-    lib().ppf_default_depth_params(C.byref(dp))
-    dp.depth_scale, dp.z_min, dp.z_max = float(depth_scale), float(z_min), float(z_max)
+    dp = _depth_params(depth_scale, z_min, z_max)
     if normals is not None and not isinstance(normals, DeviceCloud):
         raise PPFError(_capi.PPF_ERR_INVALID, "normals must be a DeviceCloud or None")
     nrm = normals._ptr if normals is not None else None
@@ -821,40 +802,14 @@ def segment_depth(depth, *, depth_scale: float = 0.001, z_min: float = 0.0, z_ma
             res.append(_capi.stats_dict(st))
         return labels if len(res) == 1 else tuple(res)
 
-    if type(depth).__module__.startswith("torch") and depth.is_cuda:
-        import torch
-        fmt = {torch.float32: _capi.PPF_DEPTH_F32, torch.uint16: _capi.PPF_DEPTH_U16}.get(depth.dtype)
-        if fmt is None or depth.dim() != 2:
-            raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 or uint16 tensor")
-        if depth.stride(1) != 1 or depth.stride(0) < depth.shape[1]:
-            depth = depth.contiguous()
-        shape = tuple(depth.shape)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.int32, device=depth.device)
-        elif not (out.is_cuda and out.device == depth.device and out.dtype == torch.int32 and tuple(out.shape) == shape
-                  and out.is_contiguous()):
-            raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous int32 tensor of shape {shape} on the depth image's device")
-        dp.format = fmt
-        with torch.cuda.device(depth.device):
-            stream = torch.cuda.current_stream(depth.device).cuda_stream
-            check(lib().ppf_depth_segments_device(C.c_void_p(depth.data_ptr()), shape[0], shape[1], depth.stride(0) * depth.element_size(),
-                                                  C.byref(dp), nrm, C.byref(prm), C.c_void_p(out.data_ptr()),
-                                                  C.c_void_p(stream) if stream else None, *tail))
-        return result(out)
-    a = np.asarray(depth.numpy() if type(depth).__module__.startswith("torch") else depth)
-    fmt = {np.dtype(np.float32): _capi.PPF_DEPTH_F32, np.dtype(np.uint16): _capi.PPF_DEPTH_U16}.get(a.dtype)
-    if fmt is None or a.ndim != 2:
-        raise PPFError(_capi.PPF_ERR_INVALID, "depth must be a 2-D float32 or uint16 array")
-    if a.strides[1] != a.itemsize or a.strides[0] < a.shape[1] * a.itemsize or a.strides[0] % a.itemsize:
-        a = np.ascontiguousarray(a)
-    dp.format = fmt
-    if out is None:
-        out = np.empty(a.shape, np.int32)
-    elif not (isinstance(out, np.ndarray) and out.dtype == np.int32 and out.shape == a.shape and out.flags.c_contiguous
-              and out.flags.writeable):
-        raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous int32 array of shape {a.shape}")
-    check(lib().ppf_depth_segments(C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1], a.strides[0], C.byref(dp), nrm, C.byref(prm),
-                                   out.ctypes.data, *tail))
+    inp = _DepthInput(depth, "depth must be a 2-D float32 or uint16 {kind}")
+    dp.format = inp.format
+    out, optr = inp.output(out, np.int32)
+    with inp.device():
+        if inp.is_device:
+            check(lib().ppf_depth_segments_device(inp.ptr, inp.rows, inp.cols, inp.pitch, C.byref(dp), nrm, C.byref(prm), optr, inp.stream(), *tail))
+        else:
+            check(lib().ppf_depth_segments(inp.ptr, inp.rows, inp.cols, inp.pitch, C.byref(dp), nrm, C.byref(prm), optr, *tail))
     return result(out)
 
 

@@ -1,7 +1,8 @@
 /*
  * ppf_depth_host.h — host side of ppf_cloud_from_depth / ppf_cloud_from_depth_device: the scene cloud from a depth image,
  * resident in HBM (what the reference's CloudProcessor::Deprojection, CloudProcessing.h:262, leaves empty).  Kernels:
- * ppf_depth_kernels.h.  Included by ppf_hip.hip after ppf_prep_host.h (ppf_cloud, cloud_alloc, grid_for).
+ * ppf_depth_kernels.h.  Included by ppf_hip.hip after ppf_prep_host.h (ppf_cloud, cloud_alloc, grid_for) and
+ * ppf_depthimage_host.h (the image checks, depth_bind_host / _device, depth_typed).
  *
  * Per call: k_depth_count, one scan launch (up to SCAN_ONE_MAX tiles, about 40 M pixels), k_depth_scatter -- three
  * launches -- one blocking 4-byte read-back of the total and a final wait for the stream.  The host entry adds one
@@ -15,69 +16,15 @@
 
 namespace {
 
-size_t depth_elem_size(int format) { return format == PPF_DEPTH_U16 ? sizeof(uint16_t) : sizeof(float); }
-
-/* every argument check of both entries, before any device work; fills the kernel arguments (img and pitch excepted) */
-ppf_status depth_check(const char* who, const void* depth, int rows, int cols, size_t* pitch, const double* intr,
-                       const ppf_depth_params* p, ppf_cloud** out, DepthArgs* a) {
+/* every argument check of the cloud entries, before any device work; fills the kernel arguments (img excepted) */
+ppf_status cloud_depth_check(const char* who, const void* depth, int rows, int cols, size_t pitch, const double* intr,
+                             const ppf_depth_params* p, ppf_cloud** out, DepthArgs* a) {
   if (!out) return fail(PPF_ERR_INVALID, "%s: out is NULL", who);
   *out = nullptr;
-  if (!depth || !intr || !p) return fail(PPF_ERR_INVALID, "%s: depth, intr and params must not be NULL", who);
-  if (rows <= 0 || cols <= 0) return fail(PPF_ERR_INVALID, "%s: the image is %d x %d", who, rows, cols);
-  if ((long long)rows * cols > 0x7fffffffLL) return fail(PPF_ERR_INVALID, "%s: %d x %d pixels exceed INT32_MAX", who, rows, cols);
-  if (p->format != PPF_DEPTH_F32 && p->format != PPF_DEPTH_U16) return fail(PPF_ERR_INVALID, "%s: unknown depth format %d", who, p->format);
-  if (p->flags & ~PPF_DEPTH_FP64) return fail(PPF_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)p->flags);
-  const size_t es = depth_elem_size(p->format), width = (size_t)cols * es;
-  if (*pitch == 0) *pitch = width;
-  if (*pitch < width || *pitch % es != 0)
-    return fail(PPF_ERR_INVALID, "%s: row pitch %zu bytes is below %zu or not a multiple of %zu", who, *pitch, width, es);
-  if (*pitch > (SIZE_MAX - width) / (size_t)rows) return fail(PPF_ERR_INVALID, "%s: row pitch %zu bytes is too large", who, *pitch);
-  if ((uintptr_t)depth % es != 0) return fail(PPF_ERR_INVALID, "%s: the image is not aligned to its %zu-byte elements", who, es);
-  if (p->format == PPF_DEPTH_U16 && !(p->depth_scale > 0.0 && std::isfinite(p->depth_scale)))
-    return fail(PPF_ERR_INVALID, "%s: depth_scale must be positive and finite for PPF_DEPTH_U16", who);
-  const double fx = intr[0], fy = intr[1], ppx = intr[2], ppy = intr[3];
-  if (!std::isfinite(fx) || !std::isfinite(fy) || fx == 0.0 || fy == 0.0)
-    return fail(PPF_ERR_INVALID, "%s: fx and fy must be finite and non-zero", who);
-  if (!std::isfinite(ppx) || !std::isfinite(ppy)) return fail(PPF_ERR_INVALID, "%s: ppx and ppy must be finite", who);
-  if (!std::isfinite(p->z_min) || !std::isfinite(p->z_max) || p->z_max < 0.f)
-    return fail(PPF_ERR_INVALID, "%s: z_min and z_max must be finite and z_max >= 0", who);
-  a->img = nullptr;
-  a->pitch = *pitch;
-  a->cols = cols;
-  a->n = rows * cols;
-  a->fx = fx; a->fy = fy; a->ppx = ppx; a->ppy = ppy;
-  a->scale = p->depth_scale;
-  a->z_min = p->z_min;
-  a->z_max = p->z_max;
-  a->fp64 = (p->flags & PPF_DEPTH_FP64) ? 1 : 0;
-  return PPF_OK;
-}
-
-/* `bytes` from d_ptr on must be memory the current device can read directly, inside one allocation; `what` names the buffer */
-ppf_status depth_device_range(const char* who, const char* what, const void* d_ptr, size_t bytes) {
-  hipPointerAttribute_t attr;
-  std::memset(&attr, 0, sizeof(attr));
-  const hipError_t pe = hipPointerGetAttributes(&attr, d_ptr);
-  if (pe != hipSuccess) {
-    (void)hipGetLastError(); /* the query's error is the answer, not a sticky state */
-    return fail(PPF_ERR_INVALID, "%s: the %s pointer is not device memory (%s)", who, what, hipGetErrorString(pe));
-  }
-  int dev = -1;
-  HIPCHK(hipGetDevice(&dev));
-  if (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)
-    return fail(PPF_ERR_INVALID, "%s: the %s pointer is not device memory (memory type %d)", who, what, (int)attr.type);
-  if (attr.device != dev) return fail(PPF_ERR_INVALID, "%s: the %s lives on device %d, the current device is %d", who, what, attr.device, dev);
-  hipDeviceptr_t base = nullptr;
-  size_t alloc = 0;
-  const hipError_t re = hipMemGetAddressRange(&base, &alloc, const_cast<void*>(d_ptr));
-  if (re != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(PPF_ERR_INVALID, "%s: the %s's allocation is unknown (%s)", who, what, hipGetErrorString(re));
-  }
-  const uintptr_t lo = (uintptr_t)base, at = (uintptr_t)d_ptr;
-  if (at < lo || at - lo > alloc || bytes > alloc - (at - lo))
-    return fail(PPF_ERR_INVALID, "%s: the %s (%zu bytes) runs past the end of its allocation", who, what, bytes);
-  return PPF_OK;
+  if (!intr) return fail(PPF_ERR_INVALID, "%s: depth, intr and params must not be NULL", who);
+  ppf_status s = depth_pixels_check(who, depth, rows, cols, pitch, p, DEPTH_FLAGS_FP64, a);
+  if (s != PPF_OK || (s = depth_intr_check(who, intr, a)) != PPF_OK) return s;
+  return depth_z_check(who, p);
 }
 
 /* count -> scan -> one read-back -> allocate -> scatter, all on `st`; returns once the cloud is complete */
@@ -86,10 +33,7 @@ ppf_status depth_run(const DepthArgs& a, int format, hipStream_t st, ppf_cloud**
   DevBuf<uint32_t> counts, offs;
   HIPCHK(counts.reserve((size_t)n_tiles + 1));
   HIPCHK(offs.reserve((size_t)n_tiles + 1));
-  if (format == PPF_DEPTH_U16)
-    k_depth_count<uint16_t><<<dim3((unsigned)n_tiles), dim3(DEPTH_BLOCK), 0, st>>>(a, n_tiles, counts.p);
-  else
-    k_depth_count<float><<<dim3((unsigned)n_tiles), dim3(DEPTH_BLOCK), 0, st>>>(a, n_tiles, counts.p);
+  depth_typed(format, [&](auto px) { k_depth_count<decltype(px)><<<dim3((unsigned)n_tiles), dim3(DEPTH_BLOCK), 0, st>>>(a, n_tiles, counts.p); });
   HIPCHK(hipGetLastError());
   ppf_status s = device_exclusive_scan(counts.p, offs.p, (size_t)n_tiles + 1, st);
   if (s != PPF_OK) return s;
@@ -99,10 +43,9 @@ ppf_status depth_run(const DepthArgs& a, int format, hipStream_t st, ppf_cloud**
   std::unique_ptr<ppf_cloud> c;
   if ((s = cloud_alloc(c, (int)total)) != PPF_OK) return s;
   if (total) {
-    if (format == PPF_DEPTH_U16)
-      k_depth_scatter<uint16_t><<<dim3((unsigned)n_tiles), dim3(DEPTH_BLOCK), 0, st>>>(a, offs.p, c->rows.p, c->curv.p);
-    else
-      k_depth_scatter<float><<<dim3((unsigned)n_tiles), dim3(DEPTH_BLOCK), 0, st>>>(a, offs.p, c->rows.p, c->curv.p);
+    depth_typed(format, [&](auto px) {
+      k_depth_scatter<decltype(px)><<<dim3((unsigned)n_tiles), dim3(DEPTH_BLOCK), 0, st>>>(a, offs.p, c->rows.p, c->curv.p);
+    });
     HIPCHK(hipGetLastError());
     HIPCHK(host_stream_sync(st)); /* the scratch goes back to the block cache at scope exit */
   }
@@ -142,10 +85,7 @@ ppf_status depth_normals_run(const DepthArgs& a, const DepthNormalArgs& na, int 
   HIPCHK(flag.reserve((size_t)a.n));
   HIPCHK(counts.reserve((size_t)n_tiles + 1));
   HIPCHK(offs.reserve((size_t)n_tiles + 1));
-  if (format == PPF_DEPTH_U16)
-    k_depth_normals<uint16_t><<<dim3((unsigned)n_win), dim3(DN_BLOCK), 0, st>>>(a, na, nrm.p, flag.p);
-  else
-    k_depth_normals<float><<<dim3((unsigned)n_win), dim3(DN_BLOCK), 0, st>>>(a, na, nrm.p, flag.p);
+  depth_typed(format, [&](auto px) { k_depth_normals<decltype(px)><<<dim3((unsigned)n_win), dim3(DN_BLOCK), 0, st>>>(a, na, nrm.p, flag.p); });
   HIPCHK(hipGetLastError());
   k_depthn_count<<<dim3((unsigned)n_tiles), dim3(DEPTH_BLOCK), 0, st>>>(flag.p, a.n, na.drop, n_tiles, counts.p);
   HIPCHK(hipGetLastError());
@@ -157,27 +97,13 @@ ppf_status depth_normals_run(const DepthArgs& a, const DepthNormalArgs& na, int 
   std::unique_ptr<ppf_cloud> c;
   if ((s = cloud_alloc(c, (int)total)) != PPF_OK) return s;
   if (total) {
-    if (format == PPF_DEPTH_U16)
-      k_depthn_scatter<uint16_t><<<dim3((unsigned)n_tiles), dim3(DEPTH_BLOCK), 0, st>>>(a, flag.p, na.drop, nrm.p, offs.p, c->rows.p, c->curv.p);
-    else
-      k_depthn_scatter<float><<<dim3((unsigned)n_tiles), dim3(DEPTH_BLOCK), 0, st>>>(a, flag.p, na.drop, nrm.p, offs.p, c->rows.p, c->curv.p);
+    depth_typed(format, [&](auto px) {
+      k_depthn_scatter<decltype(px)><<<dim3((unsigned)n_tiles), dim3(DEPTH_BLOCK), 0, st>>>(a, flag.p, na.drop, nrm.p, offs.p, c->rows.p, c->curv.p);
+    });
     HIPCHK(hipGetLastError());
     HIPCHK(host_stream_sync(st)); /* the scratch goes back to the block cache at scope exit */
   }
   *out = c.release();
-  return PPF_OK;
-}
-
-/* the image of a host entry goes over packed: rows of cols elements */
-ppf_status depth_upload(const void* depth, int rows, int cols, size_t pitch, int format, DevBuf<unsigned char>& img, DepthArgs* a) {
-  const size_t width = (size_t)cols * depth_elem_size(format);
-  HIPCHK(img.reserve(width * (size_t)rows));
-  if (pitch == width)
-    HIPCHK(hipMemcpy(img.p, depth, width * (size_t)rows, hipMemcpyHostToDevice));
-  else
-    HIPCHK(hipMemcpy2D(img.p, width, depth, pitch, width, (size_t)rows, hipMemcpyHostToDevice));
-  a->img = img.p;
-  a->pitch = width;
   return PPF_OK;
 }
 
@@ -199,12 +125,11 @@ ppf_status ppf_cloud_from_depth(const void* depth, int rows, int cols, size_t ro
                                 const ppf_depth_params* p, ppf_cloud** out) {
   static const char* who = "ppf_cloud_from_depth";
   DepthArgs a;
-  size_t pitch = row_pitch_bytes;
-  ppf_status s = depth_check(who, depth, rows, cols, &pitch, intr, p, out, &a);
+  ppf_status s = cloud_depth_check(who, depth, rows, cols, row_pitch_bytes, intr, p, out, &a);
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
   DevBuf<unsigned char> img;
-  if ((s = depth_upload(depth, rows, cols, pitch, p->format, img, &a)) != PPF_OK) return s;
+  if ((s = depth_bind_host(depth, p->format, img, &a)) != PPF_OK) return s;
   return depth_run(a, p->format, nullptr, out);
 }
 
@@ -212,14 +137,11 @@ ppf_status ppf_cloud_from_depth_device(const void* d_depth, int rows, int cols, 
                                        const ppf_depth_params* p, void* stream, ppf_cloud** out) {
   static const char* who = "ppf_cloud_from_depth_device";
   DepthArgs a;
-  size_t pitch = row_pitch_bytes;
-  ppf_status s = depth_check(who, d_depth, rows, cols, &pitch, intr, p, out, &a);
+  DepthBuf image;
+  ppf_status s = cloud_depth_check(who, d_depth, rows, cols, row_pitch_bytes, intr, p, out, &a);
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
-  /* only memory the current device can read directly, and the whole image inside its allocation */
-  const size_t bytes = (size_t)(rows - 1) * pitch + (size_t)cols * depth_elem_size(p->format);
-  if ((s = depth_device_range(who, "image", d_depth, bytes)) != PPF_OK) return s;
-  a.img = static_cast<const unsigned char*>(d_depth);
+  if ((s = depth_bind_device(who, d_depth, p->format, &a, &image)) != PPF_OK) return s;
   return depth_run(a, p->format, static_cast<hipStream_t>(stream), out);
 }
 
@@ -237,12 +159,11 @@ ppf_status ppf_cloud_from_depth_normals(const void* depth, int rows, int cols, s
   static const char* who = "ppf_cloud_from_depth_normals";
   DepthArgs a;
   DepthNormalArgs na;
-  size_t pitch = row_pitch_bytes;
-  ppf_status s = depth_check(who, depth, rows, cols, &pitch, intr, p, out, &a);
+  ppf_status s = cloud_depth_check(who, depth, rows, cols, row_pitch_bytes, intr, p, out, &a);
   if (s != PPF_OK || (s = depth_normal_check(who, np, rows, cols, &na)) != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
   DevBuf<unsigned char> img;
-  if ((s = depth_upload(depth, rows, cols, pitch, p->format, img, &a)) != PPF_OK) return s;
+  if ((s = depth_bind_host(depth, p->format, img, &a)) != PPF_OK) return s;
   return depth_normals_run(a, na, p->format, nullptr, out);
 }
 
@@ -252,13 +173,11 @@ ppf_status ppf_cloud_from_depth_normals_device(const void* d_depth, int rows, in
   static const char* who = "ppf_cloud_from_depth_normals_device";
   DepthArgs a;
   DepthNormalArgs na;
-  size_t pitch = row_pitch_bytes;
-  ppf_status s = depth_check(who, d_depth, rows, cols, &pitch, intr, p, out, &a);
+  DepthBuf image;
+  ppf_status s = cloud_depth_check(who, d_depth, rows, cols, row_pitch_bytes, intr, p, out, &a);
   if (s != PPF_OK || (s = depth_normal_check(who, np, rows, cols, &na)) != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
-  const size_t bytes = (size_t)(rows - 1) * pitch + (size_t)cols * depth_elem_size(p->format);
-  if ((s = depth_device_range(who, "image", d_depth, bytes)) != PPF_OK) return s;
-  a.img = static_cast<const unsigned char*>(d_depth);
+  if ((s = depth_bind_device(who, d_depth, p->format, &a, &image)) != PPF_OK) return s;
   return depth_normals_run(a, na, p->format, static_cast<hipStream_t>(stream), out);
 }
 

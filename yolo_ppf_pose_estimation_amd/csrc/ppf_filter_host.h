@@ -1,7 +1,7 @@
 /*
  * ppf_filter_host.h — host side of ppf_depth_filter / ppf_depth_filter_device: a depth image without its unsupported pixels,
  * smoothed inside each surface.  Kernel: ppf_filter_kernels.h.  Included by ppf_hip.hip after
- * ppf_depth_host.h (depth_check, depth_elem_size, depth_device_range, depth_upload).
+ * ppf_depthimage_host.h (the image check, the bindings, depth_outputs_check, depth_finish, depth_entry, depth_typed).
  *
  * Per call: an 8-byte clear of the counters, k_depth_filter -- one launch -- and one blocking wait, whatever the image
  * holds.  The host entry adds one upload of the image and reads the image and the counters back behind that one wait.
@@ -13,19 +13,11 @@
 namespace {
 
 /* every argument check of both entries, before any device work; fills the kernel arguments (img, pitch and counters excepted) */
-ppf_status filter_check(const char* who, const void* depth, int rows, int cols, size_t* pitch, const ppf_depth_params* dp,
+ppf_status filter_check(const char* who, const void* depth, int rows, int cols, size_t pitch, const ppf_depth_params* dp,
                         const ppf_depth_filter_params* fp, const float* out, DepthArgs* a, DepthFilterArgs* fa) {
   if (!out) return fail(PPF_ERR_INVALID, "%s: out is NULL", who);
   if (!fp) return fail(PPF_ERR_INVALID, "%s: the filter params are NULL", who);
-  /* the image: ppf_cloud_from_depth's checks (the intrinsics of those checks are not used here, nor are dp's flags) */
-  static const double unit_intr[4] = {1.0, 1.0, 0.0, 0.0};
-  ppf_depth_params plain;
-  if (dp) {
-    plain = *dp;
-    plain.flags = 0;
-  }
-  ppf_cloud* none = nullptr;
-  ppf_status s = depth_check(who, depth, rows, cols, pitch, unit_intr, dp ? &plain : nullptr, &none, a);
+  ppf_status s = depth_image_check(who, depth, rows, cols, pitch, dp, DEPTH_FLAGS_IGNORED, a);
   if (s != PPF_OK) return s;
   if (fp->radius < 0 || fp->radius > PPF_DEPTH_FILTER_MAX_RADIUS)
     return fail(PPF_ERR_INVALID, "%s: radius %d is outside 0..%d", who, fp->radius, PPF_DEPTH_FILTER_MAX_RADIUS);
@@ -52,10 +44,7 @@ ppf_status filter_enqueue(const DepthArgs& a, const DepthFilterArgs& fa, int for
   /* at most n / 256 + rows / 4 + cols / 64 + 1 workgroups: below 2^31 for every n <= INT32_MAX */
   const long long n_win = (long long)fa.tiles_x * (((long long)fa.rows + DF_TILE_H - 1) / DF_TILE_H);
   HIPCHK(hipMemsetAsync(fa.counters, 0, DF_N_COUNTERS * sizeof(int32_t), st));
-  if (format == PPF_DEPTH_U16)
-    k_depth_filter<uint16_t><<<dim3((unsigned)n_win), dim3(DF_BLOCK), 0, st>>>(a, fa, d_out);
-  else
-    k_depth_filter<float><<<dim3((unsigned)n_win), dim3(DF_BLOCK), 0, st>>>(a, fa, d_out);
+  depth_typed(format, [&](auto px) { k_depth_filter<decltype(px)><<<dim3((unsigned)n_win), dim3(DF_BLOCK), 0, st>>>(a, fa, d_out); });
   HIPCHK(hipGetLastError());
   return PPF_OK;
 }
@@ -72,49 +61,40 @@ ppf_status filter_host(const char* who, const void* depth, int rows, int cols, s
                        const ppf_depth_filter_params* fp, float* out, ppf_depth_filter_stats& st) {
   DepthArgs a;
   DepthFilterArgs fa;
-  size_t pitch = row_pitch_bytes;
-  ppf_status s = filter_check(who, depth, rows, cols, &pitch, dp, fp, out, &a, &fa);
+  ppf_status s = filter_check(who, depth, rows, cols, row_pitch_bytes, dp, fp, out, &a, &fa);
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
   const size_t n = (size_t)rows * (size_t)cols;
   DevBuf<unsigned char> img;
   DevBuf<float> buf; /* the output, then the counters */
-  if ((s = depth_upload(depth, rows, cols, pitch, dp->format, img, &a)) != PPF_OK) return s;
+  if ((s = depth_bind_host(depth, dp->format, img, &a)) != PPF_OK) return s;
   HIPCHK(buf.reserve(n + DF_N_COUNTERS));
   fa.counters = reinterpret_cast<int32_t*>(buf.p + n);
-  if ((s = filter_enqueue(a, fa, dp->format, buf.p, nullptr)) != PPF_OK) return s;
   int32_t c[DF_N_COUNTERS];
-  HIPCHK(hipMemcpyAsync(out, buf.p, n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-  HIPCHK(hipMemcpyAsync(c, fa.counters, sizeof(c), hipMemcpyDeviceToHost, nullptr));
-  HIPCHK(host_stream_sync(nullptr)); /* the scratch goes back to the block cache at scope exit */
-  filter_fill_stats(st, c);
-  return PPF_OK;
+  s = depth_finish(who, filter_enqueue(a, fa, dp->format, buf.p, nullptr), nullptr,
+                   {{"output", buf.p, n * sizeof(float), out}, {"counters", fa.counters, sizeof(c), c}});
+  if (s == PPF_OK) filter_fill_stats(st, c);
+  return s;
 }
 
 ppf_status filter_device(const char* who, const void* d_depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
                          const ppf_depth_filter_params* fp, float* d_out, hipStream_t stream, ppf_depth_filter_stats& st) {
   DepthArgs a;
   DepthFilterArgs fa;
-  size_t pitch = row_pitch_bytes;
-  ppf_status s = filter_check(who, d_depth, rows, cols, &pitch, dp, fp, d_out, &a, &fa);
+  DepthBuf image;
+  ppf_status s = filter_check(who, d_depth, rows, cols, row_pitch_bytes, dp, fp, d_out, &a, &fa);
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
-  const size_t in_bytes = (size_t)(rows - 1) * pitch + (size_t)cols * depth_elem_size(dp->format);
-  const size_t out_bytes = (size_t)rows * (size_t)cols * sizeof(float);
-  if ((s = depth_device_range(who, "image", d_depth, in_bytes)) != PPF_OK) return s;
-  if ((s = depth_device_range(who, "output", d_out, out_bytes)) != PPF_OK) return s;
-  const uintptr_t i0 = (uintptr_t)d_depth, o0 = (uintptr_t)d_out;
-  if (i0 < o0 + out_bytes && o0 < i0 + in_bytes) return fail(PPF_ERR_INVALID, "%s: the output overlaps the image", who);
+  if ((s = depth_bind_device(who, d_depth, dp->format, &a, &image)) != PPF_OK ||
+      (s = depth_outputs_check(who, image, {{"output", d_out, (size_t)rows * (size_t)cols * sizeof(float), nullptr}})) != PPF_OK)
+    return s;
   DevBuf<int32_t> counters;
   HIPCHK(counters.reserve(DF_N_COUNTERS));
-  a.img = static_cast<const unsigned char*>(d_depth);
   fa.counters = counters.p;
-  if ((s = filter_enqueue(a, fa, dp->format, d_out, stream)) != PPF_OK) return s;
   int32_t c[DF_N_COUNTERS];
-  HIPCHK(hipMemcpyAsync(c, counters.p, sizeof(c), hipMemcpyDeviceToHost, stream));
-  HIPCHK(host_stream_sync(stream));
-  filter_fill_stats(st, c);
-  return PPF_OK;
+  s = depth_finish(who, filter_enqueue(a, fa, dp->format, d_out, stream), stream, {{"counters", counters.p, sizeof(c), c}});
+  if (s == PPF_OK) filter_fill_stats(st, c);
+  return s;
 }
 
 }  // namespace
@@ -135,33 +115,16 @@ void ppf_default_depth_filter_params(ppf_depth_filter_params* p) {
 
 ppf_status ppf_depth_filter(const void* depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
                             const ppf_depth_filter_params* fp, float* out, ppf_depth_filter_stats* stats) {
-  const auto t0 = std::chrono::steady_clock::now();
-  ppf_depth_filter_stats local;
-  ppf_depth_filter_stats& st = stats ? *stats : local;
-  std::memset(&st, 0, sizeof(st));
-  const ppf_status s = filter_host("ppf_depth_filter", depth, rows, cols, row_pitch_bytes, dp, fp, out, st);
-  if (s != PPF_OK) {
-    std::memset(&st, 0, sizeof(st));
-    return s;
-  }
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PPF_OK;
+  return depth_entry(stats, depth_clear_stats<ppf_depth_filter_stats>, [&](ppf_depth_filter_stats& st) {
+    return filter_host("ppf_depth_filter", depth, rows, cols, row_pitch_bytes, dp, fp, out, st);
+  });
 }
 
 ppf_status ppf_depth_filter_device(const void* d_depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
                                    const ppf_depth_filter_params* fp, float* d_out, void* stream, ppf_depth_filter_stats* stats) {
-  const auto t0 = std::chrono::steady_clock::now();
-  ppf_depth_filter_stats local;
-  ppf_depth_filter_stats& st = stats ? *stats : local;
-  std::memset(&st, 0, sizeof(st));
-  const ppf_status s = filter_device("ppf_depth_filter_device", d_depth, rows, cols, row_pitch_bytes, dp, fp, d_out,
-                                     static_cast<hipStream_t>(stream), st);
-  if (s != PPF_OK) {
-    std::memset(&st, 0, sizeof(st));
-    return s;
-  }
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PPF_OK;
+  return depth_entry(stats, depth_clear_stats<ppf_depth_filter_stats>, [&](ppf_depth_filter_stats& st) {
+    return filter_device("ppf_depth_filter_device", d_depth, rows, cols, row_pitch_bytes, dp, fp, d_out, static_cast<hipStream_t>(stream), st);
+  });
 }
 
 }  // extern "C"

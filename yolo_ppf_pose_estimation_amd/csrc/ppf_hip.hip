@@ -47,6 +47,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -88,6 +89,7 @@
 #include "ppf_prep_host.h"     /* row N4: the segmented cloud stages, FrameRun, ppf_prep_* (one segment each) */
 #include "ppf_frame_host.h"    /* row N4 for all boxes of a frame: ppf_prep_frame, the chain of those stages */
 #include "ppf_match_frame_host.h" /* match + ICP for all detections of a frame: ppf_match_frame */
+#include "ppf_depthimage_host.h"  /* what the stages on a depth image share: checks, bindings, the one wait, the entry body */
 #include "ppf_depth_host.h"       /* the scene cloud from a depth image: ppf_cloud_from_depth */
 #include "ppf_posetable_host.h"   /* what the stages on a frame's pose table share: checks, render jobs, clears */
 #include "ppf_verify_host.h"      /* pose verification of every detection of a frame: ppf_verify_frame */

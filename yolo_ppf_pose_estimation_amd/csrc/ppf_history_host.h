@@ -1,7 +1,7 @@
 /*
  * ppf_history_host.h — host side of ppf_depth_history: a device-resident ring of a camera's last `window` depth images and
  * the fused image every pushed frame gives.  Kernel: ppf_history_kernels.h.  Included by ppf_hip.hip after
- * ppf_depth_host.h (depth_check, depth_elem_size, depth_device_range, depth_upload).
+ * ppf_depthimage_host.h (the image check, the bindings, depth_outputs_check, depth_finish, depth_entry, depth_typed).
  *
  * Per push: a 20-byte clear of the counters, k_history_push -- one launch -- and one blocking wait, whatever the image and
  * the history hold.  The host entry adds one upload of the image and reads the images and the counters back behind that one
@@ -36,13 +36,6 @@ void history_launch(int window, unsigned grid, hipStream_t st, const DepthArgs& 
   }
 }
 
-/* the image checks of ppf_cloud_from_depth for this history's size and params; fills a (img excepted) */
-ppf_status history_image_check(const char* who, const ppf_depth_history* h, const void* depth, size_t* pitch, DepthArgs* a) {
-  static const double unit_intr[4] = {1.0, 1.0, 0.0, 0.0};
-  ppf_cloud* none = nullptr;
-  return depth_check(who, depth, h->rows, h->cols, pitch, unit_intr, &h->dp, &none, a);
-}
-
 /* the kernel arguments of the push of frame h->t; ring, counters and the three alignment decisions included */
 HistoryArgs history_args(const ppf_depth_history* h, const DepthArgs& a, float* d_out, uint8_t* d_state) {
   HistoryArgs ha;
@@ -75,10 +68,7 @@ ppf_status history_enqueue(const ppf_depth_history* h, const DepthArgs& a, const
   const long long lanes = (long long)ha.rows * ha.groups;
   const unsigned grid = (unsigned)((lanes + DH_BLOCK - 1) / DH_BLOCK);
   HIPCHK(hipMemsetAsync(ha.counters, 0, DH_N_COUNTERS * sizeof(int32_t), st));
-  if (h->dp.format == PPF_DEPTH_U16)
-    history_launch<uint16_t>(h->hp.window, grid, st, a, ha);
-  else
-    history_launch<float>(h->hp.window, grid, st, a, ha);
+  depth_typed(h->dp.format, [&](auto px) { history_launch<decltype(px)>(h->hp.window, grid, st, a, ha); });
   HIPCHK(hipGetLastError());
   return PPF_OK;
 }
@@ -100,8 +90,7 @@ ppf_status history_push_host(const char* who, ppf_depth_history* h, const void* 
   if (!h) return fail(PPF_ERR_INVALID, "%s: the history is NULL", who);
   if (!out) return fail(PPF_ERR_INVALID, "%s: out is NULL", who);
   DepthArgs a;
-  size_t pitch = row_pitch_bytes;
-  ppf_status s = history_image_check(who, h, depth, &pitch, &a);
+  ppf_status s = depth_image_check(who, depth, h->rows, h->cols, row_pitch_bytes, &h->dp, DEPTH_FLAGS_IGNORED, &a);
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
   std::lock_guard<std::mutex> lock(h->mu);
@@ -109,19 +98,19 @@ ppf_status history_push_host(const char* who, ppf_depth_history* h, const void* 
   DevBuf<unsigned char> img;
   DevBuf<float> buf;       /* the output */
   DevBuf<uint8_t> sbuf;    /* the state */
-  if ((s = depth_upload(depth, h->rows, h->cols, pitch, h->dp.format, img, &a)) != PPF_OK) return s;
+  if ((s = depth_bind_host(depth, h->dp.format, img, &a)) != PPF_OK) return s;
   HIPCHK(buf.reserve(n));
   if (state) HIPCHK(sbuf.reserve(n));
   const HistoryArgs ha = history_args(h, a, buf.p, state ? sbuf.p : nullptr);
-  if ((s = history_enqueue(h, a, ha, nullptr)) != PPF_OK) return s;
   /* into staging first: out and state are only written once everything has succeeded */
   std::vector<float> o(n);
   std::vector<uint8_t> sv(state ? n : 0);
   int32_t c[DH_N_COUNTERS];
-  HIPCHK(hipMemcpyAsync(o.data(), buf.p, n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-  if (state) HIPCHK(hipMemcpyAsync(sv.data(), sbuf.p, n, hipMemcpyDeviceToHost, nullptr));
-  HIPCHK(hipMemcpyAsync(c, ha.counters, sizeof(c), hipMemcpyDeviceToHost, nullptr));
-  HIPCHK(host_stream_sync(nullptr)); /* the scratch goes back to the block cache at scope exit */
+  s = depth_finish(who, history_enqueue(h, a, ha, nullptr), nullptr,
+                   {{"output", buf.p, n * sizeof(float), o.data()},
+                    {"state image", sbuf.p, n, state ? sv.data() : nullptr},
+                    {"counters", ha.counters, sizeof(c), c}});
+  if (s != PPF_OK) return s;
   std::memcpy(out, o.data(), n * sizeof(float));
   if (state) std::memcpy(state, sv.data(), n);
   history_fill_stats(st, c, h);
@@ -129,36 +118,24 @@ ppf_status history_push_host(const char* who, ppf_depth_history* h, const void* 
   return PPF_OK;
 }
 
-bool history_overlap(const void* p, size_t pb, const void* q, size_t qb) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + qb && b < a + pb;
-}
-
 ppf_status history_push_device(const char* who, ppf_depth_history* h, const void* d_depth, size_t row_pitch_bytes, float* d_out,
                                uint8_t* d_state, hipStream_t stream, ppf_depth_history_stats& st) {
   if (!h) return fail(PPF_ERR_INVALID, "%s: the history is NULL", who);
   if (!d_out) return fail(PPF_ERR_INVALID, "%s: out is NULL", who);
   DepthArgs a;
-  size_t pitch = row_pitch_bytes;
-  ppf_status s = history_image_check(who, h, d_depth, &pitch, &a);
+  DepthBuf image;
+  ppf_status s = depth_image_check(who, d_depth, h->rows, h->cols, row_pitch_bytes, &h->dp, DEPTH_FLAGS_IGNORED, &a);
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
   const size_t n = (size_t)h->rows * (size_t)h->cols;
-  const size_t in_bytes = (size_t)(h->rows - 1) * pitch + (size_t)h->cols * depth_elem_size(h->dp.format);
-  const size_t out_bytes = n * sizeof(float);
-  if ((s = depth_device_range(who, "image", d_depth, in_bytes)) != PPF_OK) return s;
-  if ((s = depth_device_range(who, "output", d_out, out_bytes)) != PPF_OK) return s;
-  if (d_state && (s = depth_device_range(who, "state image", d_state, n)) != PPF_OK) return s;
-  if (history_overlap(d_depth, in_bytes, d_out, out_bytes)) return fail(PPF_ERR_INVALID, "%s: the output overlaps the image", who);
-  if (d_state && history_overlap(d_depth, in_bytes, d_state, n)) return fail(PPF_ERR_INVALID, "%s: the state image overlaps the image", who);
-  if (d_state && history_overlap(d_out, out_bytes, d_state, n)) return fail(PPF_ERR_INVALID, "%s: the state image overlaps the output", who);
+  if ((s = depth_bind_device(who, d_depth, h->dp.format, &a, &image)) != PPF_OK ||
+      (s = depth_outputs_check(who, image, {{"output", d_out, n * sizeof(float), nullptr}, {"state image", d_state, n, nullptr}})) != PPF_OK)
+    return s;
   std::lock_guard<std::mutex> lock(h->mu);
-  a.img = static_cast<const unsigned char*>(d_depth);
   const HistoryArgs ha = history_args(h, a, d_out, d_state);
-  if ((s = history_enqueue(h, a, ha, stream)) != PPF_OK) return s;
   int32_t c[DH_N_COUNTERS];
-  HIPCHK(hipMemcpyAsync(c, ha.counters, sizeof(c), hipMemcpyDeviceToHost, stream));
-  HIPCHK(host_stream_sync(stream));
+  s = depth_finish(who, history_enqueue(h, a, ha, stream), stream, {{"counters", ha.counters, sizeof(c), c}});
+  if (s != PPF_OK) return s;
   history_fill_stats(st, c, h);
   h->t++;
   return PPF_OK;
@@ -185,19 +162,12 @@ ppf_status ppf_depth_history_create(int rows, int cols, const ppf_depth_params* 
   if (!out) return fail(PPF_ERR_INVALID, "%s: out is NULL", who);
   *out = nullptr;
   if (!hp) return fail(PPF_ERR_INVALID, "%s: the history params are NULL", who);
-  /* rows, cols and dp: ppf_cloud_from_depth's checks on a packed image that is never read (dp's flags are not used here) */
-  static const double unit_intr[4] = {1.0, 1.0, 0.0, 0.0};
-  alignas(16) static const unsigned char never_read[16] = {0};
-  ppf_depth_params plain;
-  if (dp) {
-    plain = *dp;
-    plain.flags = 0;
-  }
-  ppf_cloud* none = nullptr;
-  DepthArgs a;
-  size_t pitch = 0;
-  ppf_status s = depth_check(who, never_read, rows, cols, &pitch, unit_intr, dp ? &plain : nullptr, &none, &a);
-  if (s != PPF_OK) return s;
+  /* rows, cols and dp as every push will have them checked, without an image */
+  if (!dp) return fail(PPF_ERR_INVALID, "%s: depth, intr and params must not be NULL", who);
+  ppf_status s;
+  if ((s = depth_size_check(who, rows, cols, dp)) != PPF_OK || (s = depth_scale_check(who, dp)) != PPF_OK ||
+      (s = depth_z_check(who, dp)) != PPF_OK)
+    return s;
   if (hp->window < 1 || hp->window > PPF_HISTORY_MAX_WINDOW)
     return fail(PPF_ERR_INVALID, "%s: window %d is outside 1..%d", who, hp->window, PPF_HISTORY_MAX_WINDOW);
   if (!std::isfinite(hp->range_abs) || !(hp->range_abs > 0.f)) return fail(PPF_ERR_INVALID, "%s: range_abs must be finite and > 0", who);
@@ -212,7 +182,7 @@ ppf_status ppf_depth_history_create(int rows, int cols, const ppf_depth_params* 
   if (!h) return fail(PPF_ERR_NOMEM, "%s: out of host memory", who);
   h->rows = rows;
   h->cols = cols;
-  h->dp = plain;
+  h->dp = *dp;
   h->hp = *hp;
   h->plane = (size_t)rows * (size_t)((cols + DH_PX - 1) / DH_PX) * DH_PX;
   const hipError_t e = h->ring.reserve(h->plane * (size_t)hp->window);
@@ -228,33 +198,16 @@ ppf_status ppf_depth_history_create(int rows, int cols, const ppf_depth_params* 
 
 ppf_status ppf_depth_history_push(ppf_depth_history* h, const void* depth, size_t row_pitch_bytes, float* out, uint8_t* state,
                                   ppf_depth_history_stats* stats) {
-  const auto t0 = std::chrono::steady_clock::now();
-  ppf_depth_history_stats local;
-  ppf_depth_history_stats& st = stats ? *stats : local;
-  std::memset(&st, 0, sizeof(st));
-  const ppf_status s = history_push_host("ppf_depth_history_push", h, depth, row_pitch_bytes, out, state, st);
-  if (s != PPF_OK) {
-    std::memset(&st, 0, sizeof(st));
-    return s;
-  }
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PPF_OK;
+  return depth_entry(stats, depth_clear_stats<ppf_depth_history_stats>, [&](ppf_depth_history_stats& st) {
+    return history_push_host("ppf_depth_history_push", h, depth, row_pitch_bytes, out, state, st);
+  });
 }
 
 ppf_status ppf_depth_history_push_device(ppf_depth_history* h, const void* d_depth, size_t row_pitch_bytes, float* d_out, uint8_t* d_state,
                                          void* stream, ppf_depth_history_stats* stats) {
-  const auto t0 = std::chrono::steady_clock::now();
-  ppf_depth_history_stats local;
-  ppf_depth_history_stats& st = stats ? *stats : local;
-  std::memset(&st, 0, sizeof(st));
-  const ppf_status s = history_push_device("ppf_depth_history_push_device", h, d_depth, row_pitch_bytes, d_out, d_state,
-                                           static_cast<hipStream_t>(stream), st);
-  if (s != PPF_OK) {
-    std::memset(&st, 0, sizeof(st));
-    return s;
-  }
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PPF_OK;
+  return depth_entry(stats, depth_clear_stats<ppf_depth_history_stats>, [&](ppf_depth_history_stats& st) {
+    return history_push_device("ppf_depth_history_push_device", h, d_depth, row_pitch_bytes, d_out, d_state, static_cast<hipStream_t>(stream), st);
+  });
 }
 
 ppf_status ppf_depth_history_reset(ppf_depth_history* h) {

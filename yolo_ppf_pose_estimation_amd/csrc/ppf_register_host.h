@@ -2,7 +2,8 @@
  * ppf_register_host.h — host side of the camera entries (ppf_camera_project / _unproject / _map_boxes, host only), of
  * ppf_depth_map and of ppf_depth_register / ppf_depth_register_device: a raw sensor depth image aligned to the colour
  * camera.  Kernels: ppf_register_kernels.h; arithmetic: include/ppf_camera_math.h.  Included by
- * ppf_hip.hip after ppf_depth_host.h (depth_check, depth_elem_size, depth_device_range).
+ * ppf_hip.hip after ppf_depthimage_host.h (the image check, the bindings, depth_outputs_check, depth_finish, depth_entry,
+ * depth_typed).
  *
  * Per call: k_reg_clear, k_reg_draw, k_reg_resolve -- three launches -- and one blocking wait, whatever the sizes.  The
  * host entry adds one upload of the image and reads the image and the counters back behind that one wait.  Scratch (the
@@ -52,16 +53,13 @@ ppf_status camera_points(const ppf_camera* cam, const double* in, int n, double*
   return PPF_OK;
 }
 
-ppf_status register_check(const char* who, const ppf_depth_map* map, const void* depth, size_t* pitch, const ppf_depth_params* dp,
+ppf_status register_check(const char* who, const ppf_depth_map* map, const void* depth, size_t pitch, const ppf_depth_params* dp,
                           const ppf_register_params* rp, const float* out, DepthArgs* a) {
   if (!map) return fail(PPF_ERR_INVALID, "%s: map is NULL", who);
   if (!out) return fail(PPF_ERR_INVALID, "%s: out is NULL", who);
   if (!rp) return fail(PPF_ERR_INVALID, "%s: the register params are NULL", who);
-  if (dp && dp->flags != 0) return fail(PPF_ERR_INVALID, "%s: the depth params' flags must be 0 here (0x%x)", who, (unsigned)dp->flags);
-  /* the image: ppf_cloud_from_depth's checks, with the map's size (the intrinsics of those checks are not used here) */
-  static const double unit_intr[4] = {1.0, 1.0, 0.0, 0.0};
-  ppf_cloud* none = nullptr;
-  ppf_status s = depth_check(who, depth, map->d_rows, map->d_cols, pitch, unit_intr, dp, &none, a);
+  /* the image has the map's size */
+  ppf_status s = depth_image_check(who, depth, map->d_rows, map->d_cols, pitch, dp, DEPTH_FLAGS_ZERO, a);
   if (s != PPF_OK) return s;
   if (!(std::isfinite(rp->quad_dz_abs) && rp->quad_dz_abs >= 0.f) || !(std::isfinite(rp->quad_dz_rel) && rp->quad_dz_rel >= 0.f))
     return fail(PPF_ERR_INVALID, "%s: quad_dz_abs and quad_dz_rel must be finite and >= 0", who);
@@ -95,10 +93,7 @@ ppf_status register_enqueue(const ppf_depth_map* map, RegArgs& a, int format, co
   const unsigned out_blocks = (unsigned)((n_out + REG_BLOCK - 1) / REG_BLOCK);
   const unsigned tiles = (unsigned)a.tiles_x * (unsigned)((map->d_rows + REG_TILE - 1) / REG_TILE);
   k_reg_clear<<<dim3(out_blocks), dim3(REG_BLOCK), 0, st>>>(zbuf, n_out, counters);
-  if (format == PPF_DEPTH_U16)
-    k_reg_draw<uint16_t><<<dim3(tiles), dim3(REG_BLOCK), 0, st>>>(a);
-  else
-    k_reg_draw<float><<<dim3(tiles), dim3(REG_BLOCK), 0, st>>>(a);
+  depth_typed(format, [&](auto px) { k_reg_draw<decltype(px)><<<dim3(tiles), dim3(REG_BLOCK), 0, st>>>(a); });
   k_reg_resolve<<<dim3(out_blocks), dim3(REG_BLOCK), 0, st>>>(zbuf, d_out, n_out, counters);
   HIPCHK(hipGetLastError());
   return PPF_OK;
@@ -117,57 +112,41 @@ void register_fill_stats(ppf_register_stats& st, const int32_t* c) {
 ppf_status register_host(const char* who, const ppf_depth_map* map, const void* depth, size_t row_pitch_bytes, const ppf_depth_params* dp,
                          const ppf_register_params* rp, float* out, ppf_register_stats& st) {
   RegArgs a;
-  size_t pitch = row_pitch_bytes;
-  ppf_status s = register_check(who, map, depth, &pitch, dp, rp, out, &a.d);
+  ppf_status s = register_check(who, map, depth, row_pitch_bytes, dp, rp, out, &a.d);
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
   if ((s = register_device_of(who, map)) != PPF_OK) return s;
-  /* the image goes over packed, as in ppf_cloud_from_depth */
-  const size_t width = (size_t)map->d_cols * depth_elem_size(dp->format), n_out = (size_t)map->c_rows * map->c_cols;
+  const size_t n_out = (size_t)map->c_rows * map->c_cols;
   DevBuf<unsigned char> img;
   DevBuf<uint32_t> buf; /* the z-buffer, resolved in place, then the counters */
-  HIPCHK(img.reserve(width * (size_t)map->d_rows));
+  if ((s = depth_bind_host(depth, dp->format, img, &a.d)) != PPF_OK) return s;
   HIPCHK(buf.reserve(n_out + REG_N_COUNTERS));
-  if (pitch == width)
-    HIPCHK(hipMemcpy(img.p, depth, width * (size_t)map->d_rows, hipMemcpyHostToDevice));
-  else
-    HIPCHK(hipMemcpy2D(img.p, width, depth, pitch, width, (size_t)map->d_rows, hipMemcpyHostToDevice));
-  a.d.img = img.p;
-  a.d.pitch = width;
   int32_t* counters = reinterpret_cast<int32_t*>(buf.p + n_out);
-  if ((s = register_enqueue(map, a, dp->format, rp, buf.p, reinterpret_cast<float*>(buf.p), counters, nullptr)) != PPF_OK) return s;
   int32_t c[REG_N_COUNTERS];
-  HIPCHK(hipMemcpyAsync(out, buf.p, n_out * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-  HIPCHK(hipMemcpyAsync(c, counters, sizeof(c), hipMemcpyDeviceToHost, nullptr));
-  HIPCHK(host_stream_sync(nullptr)); /* the scratch goes back to the block cache at scope exit */
-  register_fill_stats(st, c);
-  return PPF_OK;
+  s = depth_finish(who, register_enqueue(map, a, dp->format, rp, buf.p, reinterpret_cast<float*>(buf.p), counters, nullptr), nullptr,
+                   {{"output", buf.p, n_out * sizeof(float), out}, {"counters", counters, sizeof(c), c}});
+  if (s == PPF_OK) register_fill_stats(st, c);
+  return s;
 }
 
 ppf_status register_device(const char* who, const ppf_depth_map* map, const void* d_depth, size_t row_pitch_bytes,
                            const ppf_depth_params* dp, const ppf_register_params* rp, float* d_out, hipStream_t stream,
                            ppf_register_stats& st) {
   RegArgs a;
-  size_t pitch = row_pitch_bytes;
-  ppf_status s = register_check(who, map, d_depth, &pitch, dp, rp, d_out, &a.d);
+  DepthBuf image;
+  ppf_status s = register_check(who, map, d_depth, row_pitch_bytes, dp, rp, d_out, &a.d);
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
-  if ((s = register_device_of(who, map)) != PPF_OK) return s;
-  const size_t in_bytes = (size_t)(map->d_rows - 1) * pitch + (size_t)map->d_cols * depth_elem_size(dp->format);
-  const size_t out_bytes = (size_t)map->c_rows * map->c_cols * sizeof(float);
-  if ((s = depth_device_range(who, "image", d_depth, in_bytes)) != PPF_OK) return s;
-  if ((s = depth_device_range(who, "output", d_out, out_bytes)) != PPF_OK) return s;
-  const uintptr_t i0 = (uintptr_t)d_depth, o0 = (uintptr_t)d_out;
-  if (i0 < o0 + out_bytes && o0 < i0 + in_bytes) return fail(PPF_ERR_INVALID, "%s: the output overlaps the image", who);
+  if ((s = register_device_of(who, map)) != PPF_OK || (s = depth_bind_device(who, d_depth, dp->format, &a.d, &image)) != PPF_OK ||
+      (s = depth_outputs_check(who, image, {{"output", d_out, (size_t)map->c_rows * map->c_cols * sizeof(float), nullptr}})) != PPF_OK)
+    return s;
   DevBuf<int32_t> counters;
   HIPCHK(counters.reserve(REG_N_COUNTERS));
-  a.d.img = static_cast<const unsigned char*>(d_depth);
-  if ((s = register_enqueue(map, a, dp->format, rp, reinterpret_cast<uint32_t*>(d_out), d_out, counters.p, stream)) != PPF_OK) return s;
   int32_t c[REG_N_COUNTERS];
-  HIPCHK(hipMemcpyAsync(c, counters.p, sizeof(c), hipMemcpyDeviceToHost, stream));
-  HIPCHK(host_stream_sync(stream));
-  register_fill_stats(st, c);
-  return PPF_OK;
+  s = depth_finish(who, register_enqueue(map, a, dp->format, rp, reinterpret_cast<uint32_t*>(d_out), d_out, counters.p, stream), stream,
+                   {{"counters", counters.p, sizeof(c), c}});
+  if (s == PPF_OK) register_fill_stats(st, c);
+  return s;
 }
 
 }  // namespace
@@ -290,34 +269,21 @@ void ppf_default_register_params(ppf_register_params* p) {
 
 ppf_status ppf_depth_register(const ppf_depth_map* map, const void* depth, size_t row_pitch_bytes, const ppf_depth_params* dp,
                               const ppf_register_params* rp, float* out, ppf_register_stats* stats) {
-  const auto t0 = std::chrono::steady_clock::now();
-  ppf_register_stats local;
-  ppf_register_stats& st = stats ? *stats : local;
-  std::memset(&st, 0, sizeof(st));
-  const ppf_status s = register_host("ppf_depth_register", map, depth, row_pitch_bytes, dp, rp, out, st);
-  if (s != PPF_OK) {
+  /* the host entry alone also leaves a failed call's out zero, when the map says how large it is */
+  const auto clear = [&](ppf_register_stats& st, bool failed) {
     std::memset(&st, 0, sizeof(st));
-    if (map && out) std::memset(out, 0, (size_t)map->c_rows * map->c_cols * sizeof(float));
-    return s;
-  }
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PPF_OK;
+    if (failed && map && out) std::memset(out, 0, (size_t)map->c_rows * map->c_cols * sizeof(float));
+  };
+  return depth_entry(stats, clear, [&](ppf_register_stats& st) {
+    return register_host("ppf_depth_register", map, depth, row_pitch_bytes, dp, rp, out, st);
+  });
 }
 
 ppf_status ppf_depth_register_device(const ppf_depth_map* map, const void* d_depth, size_t row_pitch_bytes, const ppf_depth_params* dp,
                                      const ppf_register_params* rp, float* d_out, void* stream, ppf_register_stats* stats) {
-  const auto t0 = std::chrono::steady_clock::now();
-  ppf_register_stats local;
-  ppf_register_stats& st = stats ? *stats : local;
-  std::memset(&st, 0, sizeof(st));
-  const ppf_status s = register_device("ppf_depth_register_device", map, d_depth, row_pitch_bytes, dp, rp, d_out,
-                                       static_cast<hipStream_t>(stream), st);
-  if (s != PPF_OK) {
-    std::memset(&st, 0, sizeof(st));
-    return s;
-  }
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PPF_OK;
+  return depth_entry(stats, depth_clear_stats<ppf_register_stats>, [&](ppf_register_stats& st) {
+    return register_device("ppf_depth_register_device", map, d_depth, row_pitch_bytes, dp, rp, d_out, static_cast<hipStream_t>(stream), st);
+  });
 }
 
 }  // extern "C"

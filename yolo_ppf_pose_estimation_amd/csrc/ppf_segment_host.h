@@ -1,7 +1,7 @@
 /*
  * ppf_segment_host.h — host side of ppf_depth_segments / ppf_depth_segments_device: a depth image's surfaces labelled in image
- * space.  Kernels: ppf_segment_kernels.h.  Included by ppf_hip.hip after ppf_filter_host.h (and so after
- * ppf_depth_host.h: depth_check, depth_elem_size, depth_device_range, depth_upload; and ppf_prep_host.h: FrameRun, frame_scan,
+ * space.  Kernels: ppf_segment_kernels.h.  Included by ppf_hip.hip after ppf_depthimage_host.h (the image
+ * check, the bindings, depth_outputs_check, depth_finish, depth_entry, depth_typed) and ppf_prep_host.h (FrameRun, frame_scan,
  * frame_sort).
  *
  * Per call, all on the caller's stream (FrameRun::st): with a normals cloud k_depth_count and a five-launch scan; then k_seg_classify,
@@ -16,19 +16,12 @@
 namespace {
 
 /* every argument check of both entries, before any device work; fills the kernel arguments (img and pitch excepted) */
-ppf_status segment_check(const char* who, const void* depth, int rows, int cols, size_t* pitch, const ppf_depth_params* dp,
+ppf_status segment_check(const char* who, const void* depth, int rows, int cols, size_t pitch, const ppf_depth_params* dp,
                          const ppf_cloud* normals, const ppf_segment_params* sp, const int32_t* labels, const ppf_segment_info* info,
                          const int32_t* counts, DepthArgs* a, SegArgs* sa) {
   if (!labels || !info || !counts) return fail(PPF_ERR_INVALID, "%s: labels, info and counts must not be NULL", who);
   if (!sp) return fail(PPF_ERR_INVALID, "%s: the segment params are NULL", who);
-  static const double unit_intr[4] = {1.0, 1.0, 0.0, 0.0};
-  ppf_depth_params plain;
-  if (dp) {
-    plain = *dp;
-    plain.flags = 0;
-  }
-  ppf_cloud* none = nullptr;
-  ppf_status s = depth_check(who, depth, rows, cols, pitch, unit_intr, dp ? &plain : nullptr, &none, a);
+  ppf_status s = depth_image_check(who, depth, rows, cols, pitch, dp, DEPTH_FLAGS_IGNORED, a);
   if (s != PPF_OK) return s;
   if (!(std::isfinite(sp->depth_abs) && sp->depth_abs >= 0.f) || !(std::isfinite(sp->depth_quad) && sp->depth_quad >= 0.f))
     return fail(PPF_ERR_INVALID, "%s: depth_abs and depth_quad must be finite and >= 0", who);
@@ -88,17 +81,11 @@ ppf_status segment_enqueue(FrameRun& fr, SegWork& w, const DepthArgs& a, const S
   HIPCHK(hipMemsetAsync(w.zero, 0, w.z_words * sizeof(uint32_t), fr.st));
   const dim3 bd(DEPTH_BLOCK), bs(SEG_BLOCK), g_dt((unsigned)n_dt), g_tiles((unsigned)n_tiles), g_px = grid_for(N, SEG_BLOCK);
   if (sa.nrm_rows) {
-    if (format == PPF_DEPTH_U16)
-      FRAME_LAUNCH(fr, k_depth_count<uint16_t>, g_dt, bd, a, n_dt, tcnt);
-    else
-      FRAME_LAUNCH(fr, k_depth_count<float>, g_dt, bd, a, n_dt, tcnt);
+    depth_typed(format, [&](auto px) { FRAME_LAUNCH(fr, k_depth_count<decltype(px)>, g_dt, bd, a, n_dt, tcnt); });
     HIPCHK(hipGetLastError());
     if ((s = frame_scan(fr, tcnt, toff, (size_t)n_dt + 1)) != PPF_OK) return s;
   }
-  if (format == PPF_DEPTH_U16)
-    FRAME_LAUNCH(fr, k_seg_classify<uint16_t>, g_dt, bd, a, sa, toff, rec, cls, size, nbord, rank);
-  else
-    FRAME_LAUNCH(fr, k_seg_classify<float>, g_dt, bd, a, sa, toff, rec, cls, size, nbord, rank);
+  depth_typed(format, [&](auto px) { FRAME_LAUNCH(fr, k_seg_classify<decltype(px)>, g_dt, bd, a, sa, toff, rec, cls, size, nbord, rank); });
   FRAME_LAUNCH(fr, k_seg_tile, g_tiles, bs, sa, rec, cls, parent);
   FRAME_LAUNCH(fr, k_seg_merge, g_px, bs, sa, rec, cls, parent);
   FRAME_LAUNCH(fr, k_seg_flatten, g_tiles, bs, sa, rec, cls, parent, root, size, nbord, w.zero);
@@ -149,8 +136,7 @@ ppf_status segment_host(const char* who, const void* depth, int rows, int cols, 
                         ppf_segment_stats& st) {
   DepthArgs a;
   SegArgs sa;
-  size_t pitch = row_pitch_bytes;
-  ppf_status s = segment_check(who, depth, rows, cols, &pitch, dp, normals, sp, labels, info, counts, &a, &sa);
+  ppf_status s = segment_check(who, depth, rows, cols, row_pitch_bytes, dp, normals, sp, labels, info, counts, &a, &sa);
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
   const size_t n = (size_t)rows * (size_t)cols;
@@ -158,23 +144,14 @@ ppf_status segment_host(const char* who, const void* depth, int rows, int cols, 
   SegWork w;
   DevBuf<unsigned char> img;
   int32_t* d_labels;
-  if ((s = depth_upload(depth, rows, cols, pitch, dp->format, img, &a)) != PPF_OK) return s;
+  if ((s = depth_bind_host(depth, dp->format, img, &a)) != PPF_OK) return s;
   if ((s = fr.get(n, &d_labels)) != PPF_OK) return s;
   std::vector<int32_t> lab(n); /* labels stay untouched when the wait brings an error */
   std::vector<uint32_t> z;
-  if ((s = segment_enqueue(fr, w, a, sa, dp->format, *sp, d_labels)) == PPF_OK) {
-    z.resize(w.z_words);
-    hipError_t e = hipMemcpyAsync(lab.data(), d_labels, n * sizeof(int32_t), hipMemcpyDeviceToHost, fr.st);
-    if (e == hipSuccess) e = hipMemcpyAsync(z.data(), w.zero, w.z_words * sizeof(uint32_t), hipMemcpyDeviceToHost, fr.st);
-    if (e == hipSuccess) e = host_stream_sync(fr.st);
-    if (e != hipSuccess) s = fail(PPF_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-  }
-  /* kernels of a failed call may still run: wait before its scratch goes back to the block cache */
-  if (s != PPF_OK) {
-    (void)hipDeviceSynchronize();
-    return s;
-  }
-  if ((s = segment_results(who, z, w, fr, normals, *sp, info, counts, st)) != PPF_OK) return s;
+  if ((s = segment_enqueue(fr, w, a, sa, dp->format, *sp, d_labels)) == PPF_OK) z.resize(w.z_words);
+  s = depth_finish(who, s, fr.st, {{"label buffer", d_labels, n * sizeof(int32_t), lab.data()},
+                                   {"counters", w.zero, w.z_words * sizeof(uint32_t), z.data()}});
+  if (s != PPF_OK || (s = segment_results(who, z, w, fr, normals, *sp, info, counts, st)) != PPF_OK) return s;
   std::memcpy(labels, lab.data(), n * sizeof(int32_t));
   return PPF_OK;
 }
@@ -184,33 +161,21 @@ ppf_status segment_device(const char* who, const void* d_depth, int rows, int co
                           int32_t* counts, ppf_segment_stats& st) {
   DepthArgs a;
   SegArgs sa;
-  size_t pitch = row_pitch_bytes;
-  ppf_status s = segment_check(who, d_depth, rows, cols, &pitch, dp, normals, sp, d_labels, info, counts, &a, &sa);
+  DepthBuf image;
+  ppf_status s = segment_check(who, d_depth, rows, cols, row_pitch_bytes, dp, normals, sp, d_labels, info, counts, &a, &sa);
   if (s != PPF_OK) return s;
   if ((uintptr_t)d_labels % sizeof(int32_t) != 0) return fail(PPF_ERR_INVALID, "%s: the label buffer is not aligned to 4 bytes", who);
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
-  const size_t in_bytes = (size_t)(rows - 1) * pitch + (size_t)cols * depth_elem_size(dp->format);
-  const size_t out_bytes = (size_t)rows * (size_t)cols * sizeof(int32_t);
-  if ((s = depth_device_range(who, "image", d_depth, in_bytes)) != PPF_OK) return s;
-  if ((s = depth_device_range(who, "label buffer", d_labels, out_bytes)) != PPF_OK) return s;
-  const uintptr_t i0 = (uintptr_t)d_depth, o0 = (uintptr_t)d_labels;
-  if (i0 < o0 + out_bytes && o0 < i0 + in_bytes) return fail(PPF_ERR_INVALID, "%s: the label buffer overlaps the image", who);
+  if ((s = depth_bind_device(who, d_depth, dp->format, &a, &image)) != PPF_OK ||
+      (s = depth_outputs_check(who, image, {{"label buffer", d_labels, (size_t)rows * (size_t)cols * sizeof(int32_t), nullptr}})) != PPF_OK)
+    return s;
   FrameRun fr;
   SegWork w;
   fr.st = stream;
-  a.img = static_cast<const unsigned char*>(d_depth);
   std::vector<uint32_t> z;
-  if ((s = segment_enqueue(fr, w, a, sa, dp->format, *sp, d_labels)) == PPF_OK) {
-    z.resize(w.z_words);
-    hipError_t e = hipMemcpyAsync(z.data(), w.zero, w.z_words * sizeof(uint32_t), hipMemcpyDeviceToHost, fr.st);
-    if (e == hipSuccess) e = host_stream_sync(fr.st);
-    if (e != hipSuccess) s = fail(PPF_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-  }
-  if (s != PPF_OK) {
-    (void)hipDeviceSynchronize();
-    return s;
-  }
-  return segment_results(who, z, w, fr, normals, *sp, info, counts, st);
+  if ((s = segment_enqueue(fr, w, a, sa, dp->format, *sp, d_labels)) == PPF_OK) z.resize(w.z_words);
+  s = depth_finish(who, s, fr.st, {{"counters", w.zero, w.z_words * sizeof(uint32_t), z.data()}});
+  return s != PPF_OK ? s : segment_results(who, z, w, fr, normals, *sp, info, counts, st);
 }
 
 /* the outputs of a failed call are zero; info is only cleared when the params say how long it is */
@@ -241,34 +206,18 @@ void ppf_default_segment_params(ppf_segment_params* p) {
 ppf_status ppf_depth_segments(const void* depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
                               const ppf_cloud* normals, const ppf_segment_params* sp, int32_t* labels, ppf_segment_info* info,
                               int32_t* counts, ppf_segment_stats* stats) {
-  const auto t0 = std::chrono::steady_clock::now();
-  ppf_segment_stats local;
-  ppf_segment_stats& st = stats ? *stats : local;
-  segment_clear(sp, info, counts, st);
-  const ppf_status s = segment_host("ppf_depth_segments", depth, rows, cols, row_pitch_bytes, dp, normals, sp, labels, info, counts, st);
-  if (s != PPF_OK) {
-    segment_clear(sp, info, counts, st);
-    return s;
-  }
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PPF_OK;
+  return depth_entry(stats, [&](ppf_segment_stats& st, bool) { segment_clear(sp, info, counts, st); }, [&](ppf_segment_stats& st) {
+    return segment_host("ppf_depth_segments", depth, rows, cols, row_pitch_bytes, dp, normals, sp, labels, info, counts, st);
+  });
 }
 
 ppf_status ppf_depth_segments_device(const void* d_depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
                                      const ppf_cloud* normals, const ppf_segment_params* sp, int32_t* d_labels, void* stream,
                                      ppf_segment_info* info, int32_t* counts, ppf_segment_stats* stats) {
-  const auto t0 = std::chrono::steady_clock::now();
-  ppf_segment_stats local;
-  ppf_segment_stats& st = stats ? *stats : local;
-  segment_clear(sp, info, counts, st);
-  const ppf_status s = segment_device("ppf_depth_segments_device", d_depth, rows, cols, row_pitch_bytes, dp, normals, sp, d_labels,
-                                      static_cast<hipStream_t>(stream), info, counts, st);
-  if (s != PPF_OK) {
-    segment_clear(sp, info, counts, st);
-    return s;
-  }
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PPF_OK;
+  return depth_entry(stats, [&](ppf_segment_stats& st, bool) { segment_clear(sp, info, counts, st); }, [&](ppf_segment_stats& st) {
+    return segment_device("ppf_depth_segments_device", d_depth, rows, cols, row_pitch_bytes, dp, normals, sp, d_labels,
+                          static_cast<hipStream_t>(stream), info, counts, st);
+  });
 }
 
 }  // extern "C"
