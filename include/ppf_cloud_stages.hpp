@@ -24,6 +24,7 @@
  *                                                     (a raw sensor depth frame aligned to the colour camera; Cloud::fromDepth takes it)
  *   (nothing: a sensor pipeline's depth clean-up)     ->  filterDepth / filterDepthU16 / DepthMap::registerFiltered
  *   (nothing: the frames of a fixed camera fused)     ->  DepthHistory::push / pushU16
+ *   (nothing: the camera stands still there)          ->  depthMotion / depthMotionU16 / DepthOdometry::push  (the camera's motion between two depth frames)
  *   (nothing: the boxes come from YOLO)               ->  segmentDepth / segmentDepthU16  (the depth image's surfaces as labels and boxes)
  *   (nothing: the labels come from YOLO)              ->  Recognizer::recognize  (per proposal cloud the trained models it can be a view of)
  *
@@ -629,6 +630,100 @@ class DepthHistory {
   }
   std::shared_ptr<ppf_depth_history> h_;
   int rows_, cols_;
+};
+
+/* ppf_depth_motion: the camera's rigid motion between two depth images of one size and format.  T (16 doubles,
+ * row-major) takes a static point's coordinates in the previous camera frame to the current one: a pose of the previous frame
+ * is T * pose in the current one.  status is the status of the last level reached; PPF_MOTION_LOST or PPF_MOTION_STEP: not
+ * found, T is the start. */
+struct DepthMotion {
+  double T[16];
+  int status;
+  ppf_depth_motion_level levels[PPF_MOTION_MAX_LEVELS];
+  ppf_depth_motion_stats stats;
+  bool found() const { return status != PPF_MOTION_LOST && status != PPF_MOTION_STEP; }
+};
+inline ppf_depth_motion_params defaultDepthMotionParams() {
+  ppf_depth_motion_params p;
+  ppf_default_depth_motion_params(&p);
+  return p;
+}
+inline DepthMotion depthMotionImage(const void* prev, const void* cur, int format, double scale, int rows, int cols, const double* intr,
+                                    const ppf_depth_motion_params* params, const double* init16, float zMin, float zMax,
+                                    size_t prevPitchBytes, size_t curPitchBytes) {
+  const ppf_depth_params dp = depthParams(format, scale, zMin, zMax);
+  const ppf_depth_motion_params mp = params ? *params : defaultDepthMotionParams();
+  DepthMotion m;
+  ppf_match_3d::check(ppf_depth_motion(prev, prevPitchBytes, cur, curPitchBytes, rows, cols, intr, &dp, &mp, init16, m.T, m.levels, &m.stats));
+  m.status = m.stats.status;
+  return m;
+}
+/* float32 metres in; intr = {fx, fy, ppx, ppy}; params 0: the defaults; init16 0: the identity; a pitch of 0: packed rows */
+inline DepthMotion depthMotion(const float* prev, const float* cur, int rows, int cols, const double* intr,
+                               const ppf_depth_motion_params* params = 0, const double* init16 = 0, float zMin = 0.f, float zMax = 0.f,
+                               size_t prevPitchBytes = 0, size_t curPitchBytes = 0) {
+  return depthMotionImage(prev, cur, PPF_DEPTH_F32, 0.001, rows, cols, intr, params, init16, zMin, zMax, prevPitchBytes, curPitchBytes);
+}
+/* two 16-bit sensor images: z = d * scale metres (0.001 for millimetres) */
+inline DepthMotion depthMotionU16(const uint16_t* prev, const uint16_t* cur, int rows, int cols, double scale, const double* intr,
+                                  const ppf_depth_motion_params* params = 0, const double* init16 = 0, float zMin = 0.f, float zMax = 0.f,
+                                  size_t prevPitchBytes = 0, size_t curPitchBytes = 0) {
+  return depthMotionImage(prev, cur, PPF_DEPTH_U16, scale, rows, cols, intr, params, init16, zMin, zMax, prevPitchBytes, curPitchBytes);
+}
+
+/* Frame-to-frame camera tracking on float32 depth images: push keeps a copy of the frame, runs depthMotion from the frame kept
+ * before it and accumulates pose(), which takes the first frame's camera coordinates to the current frame's (T * pose, summed as
+ * ppf_mat44_mul sums it).  When the motion is not found pose() stays where it was, and the new frame becomes the next previous
+ * frame only with keepOnFailure. */
+class DepthOdometry {
+ public:
+  DepthOdometry(int rows, int cols, const double* intr, const ppf_depth_motion_params* params = 0, float zMin = 0.f, float zMax = 0.f)
+      : rows_(rows), cols_(cols), mp_(params ? *params : defaultDepthMotionParams()), zMin_(zMin), zMax_(zMax), frames_(0) {
+    for (int i = 0; i < 4; i++) intr_[i] = intr[i];
+    reset();
+  }
+  void reset() {
+    prev_.clear();
+    frames_ = 0;
+    for (int i = 0; i < 16; i++) pose_[i] = (i % 5 == 0) ? 1.0 : 0.0;
+  }
+  const double* pose() const { return pose_; }
+  int frames() const { return frames_; }
+  /* the first push only keeps the frame: the identity, status PPF_MOTION_NONE */
+  DepthMotion push(const float* depth, bool keepOnFailure = false) {
+    const size_t n = (size_t)rows_ * (size_t)cols_;
+    DepthMotion m;
+    if (prev_.empty()) {
+      m = DepthMotion();
+      for (int i = 0; i < 16; i++) m.T[i] = (i % 5 == 0) ? 1.0 : 0.0;
+      m.status = PPF_MOTION_NONE;
+      prev_.assign(depth, depth + n);
+      frames_ = 1;
+      return m;
+    }
+    m = depthMotion(&prev_[0], depth, rows_, cols_, intr_, &mp_, 0, zMin_, zMax_);
+    if (m.found()) {
+      double next[16];
+      for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+          double s = 0;
+          for (int k = 0; k < 4; k++) s += m.T[i * 4 + k] * pose_[k * 4 + j];
+          next[i * 4 + j] = s;
+        }
+      for (int i = 0; i < 16; i++) pose_[i] = next[i];
+    }
+    if (m.found() || keepOnFailure) prev_.assign(depth, depth + n);
+    frames_++;
+    return m;
+  }
+
+ private:
+  int rows_, cols_;
+  ppf_depth_motion_params mp_;
+  float zMin_, zMax_;
+  int frames_;
+  double intr_[4], pose_[16];
+  std::vector<float> prev_;
 };
 
 /* ppf_depth_segments: the depth image's connected surfaces labelled in image space.  Returns the label image

@@ -56,6 +56,8 @@
  *   ppf_camera_map_boxes            a detector's boxes on the raw colour image carried into that pixel grid
  *   ppf_depth_filter (+_device)     the depth clean-up a sensor pipeline runs before anything else (the reference has none):
  *                                   unsupported "flying" pixels removed, the others smoothed without crossing a depth step
+ *   ppf_depth_motion (+_device)     the camera's rigid motion between two depth images (the reference's camera stands still):
+ *                                   last frame's poses times it are this frame's start poses for ppf_refine_frame
  *   ppf_depth_segments (+_device)   detections without a detector, straight from the organised depth image (the reference takes
  *                                   its boxes from YOLO): the image's connected smooth surfaces as a label image and boxes
  *   ppf_recognize_frame             labels without a detector (the reference takes each crop's class from YOLO,
@@ -774,6 +776,106 @@ ppf_status ppf_depth_history_reset(ppf_depth_history* h);
 /* the size, the window, the pushes since the last reset and the device memory held */
 ppf_status ppf_depth_history_info(const ppf_depth_history* h, ppf_depth_history_desc* info);
 ppf_status ppf_depth_history_release(ppf_depth_history* h);
+
+/* ---- the camera's motion between two depth images: whole-image projective point-to-plane ICP --------- */
+#define PPF_MOTION_MAX_LEVELS 4
+#define PPF_MOTION_MAX_ITERS 64
+#define PPF_MOTION_NONE 0       /* level not reached: an earlier level ended the call, or l >= levels; the row is zero */
+#define PPF_MOTION_CONVERGED 1  /* the last step was below eps_rot and eps_trans */
+#define PPF_MOTION_MAX_ITERS_REACHED 2 /* iters[l] steps were applied */
+#define PPF_MOTION_LOST 3       /* too few pairs at an evaluation: the call ends with the pose of that evaluation */
+#define PPF_MOTION_STEP 4       /* a step over the limits, not finite or not solvable was refused: likewise */
+#define PPF_MOTION_SKIPPED 5    /* iters[l] == 0 or n_source < min_pairs: the pose passes through to the next finer level */
+typedef struct ppf_depth_motion_params {
+  int32_t levels;         /* 1..4: the image must have at least one row and column at level levels - 1; default 3 */
+  int32_t iters[4];       /* per level, level 0 (full size) first, each 0..64; default 10, 5, 4, 4 */
+  float pyr_gate;         /* finite, > 0, metres; default 0.03 */
+  float normal_gate;      /* finite, > 0, metres at level 0, doubled per level; default 0.01 */
+  float dist_gate;        /* finite, > 0, metres; default 0.05 */
+  float normal_cos;       /* finite, -1..1; default 0.8 */
+  float max_step_rot;     /* rad, finite, > 0; default 0.3 */
+  float max_step_trans;   /* metres, finite, > 0; default 0.15 */
+  float eps_rot, eps_trans; /* finite, >= 0; default 1e-5 */
+  float min_pair_share;   /* 0..1: pairs needed as a share of n_source; default 0.25 */
+  int32_t min_pairs;      /* >= 6; default 16 */
+  int32_t flags;          /* 0 */
+  int32_t reserved[4];
+} ppf_depth_motion_params;
+typedef struct ppf_depth_motion_level {
+  int32_t status, iterations;        /* PPF_MOTION_*; steps applied at this level */
+  int32_t rows, cols;                /* the level's size */
+  int32_t n_source;                  /* pixels of `prev` with a normal at this level */
+  int32_t n_pairs_first, n_pairs_last;
+  float rmse_first, rmse_last;       /* point-to-plane rms of the level's first / last evaluation, metres */
+  int32_t reserved[3];
+} ppf_depth_motion_level;
+typedef struct ppf_depth_motion_stats {
+  int32_t status;         /* the status of the last level reached */
+  int32_t n_evaluations;  /* evaluations that ran, over all levels */
+  int32_t n_enqueued;     /* evaluations enqueued: the sum of iters[0 .. levels - 1]; the rest returned at the state word */
+  int32_t n_launches;     /* kernel launches of the call: a function of levels, iters and the image size alone */
+  int32_t n_host_syncs;   /* blocking waits of the call: 1 */
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_depth_motion_stats;
+/* levels 3, iters 10 5 4 4, pyr_gate 0.03, normal_gate 0.01, dist_gate 0.05, normal_cos 0.8, max_step_rot 0.3,
+ * max_step_trans 0.15, eps_rot 1e-5, eps_trans 1e-5, min_pair_share 0.25, min_pairs 16, flags 0 */
+void ppf_default_depth_motion_params(ppf_depth_motion_params* p);
+/* The rigid motion T between two depth images of one camera: p_cur = T p_prev for a static point, so a pose (model -> camera)
+ * of the previous frame is T * pose in the current one.  A projective point-to-plane ICP over a small pyramid.  Everything
+ * is fp64 unless stated, evaluated as written, left to right, nothing fused; z(p) and "kept" are ppf_cloud_from_depth's.
+ *  1. Level 0 of each image: the float z of a kept pixel, 0 elsewhere.
+ *  2. Level l + 1 is rows_l / 2 by cols_l / 2 (integer division: an odd last row or column is dropped).  Pixel (u, v) reads the
+ *     level-l pixels (2u, 2v), (2u+1, 2v), (2u, 2v+1), (2u+1, 2v+1); a value is kept when it is > 0; m is the smallest kept
+ *     one; the result is the fp64 sum, in that order, of the kept values s with (double)s - (double)m <= (double)pyr_gate,
+ *     divided by their count and cast to float; 0 when none is kept.  fx_{l+1} = fx_l / 2, fy likewise,
+ *     ppx_{l+1} = (ppx_l - 0.5) / 2, ppy likewise.
+ *  3. Maps, per level and image.  V(u, v) = (((double)u - ppx) * Z / fx, ((double)v - ppy) * Z / fy, Z), Z = (double)z.  A pixel
+ *     has a normal when it and its four 4-neighbours are inside the image and kept, each neighbour's Z differs from its own by
+ *     at most (double)normal_gate * 2^l, and with dx = V(u+1, v) - V(u-1, v), dy = V(u, v+1) - V(u, v-1), c = dy x dx
+ *     (c0 = dy1 dx2 - dy2 dx1, c1 = dy2 dx0 - dy0 dx2, c2 = dy0 dx1 - dy1 dx0), len = sqrt((c0 c0 + c1 c1) + c2 c2) > 0,
+ *     n = (float)(c_i / len) is not all zero and faces the camera: ((double)n0 V0 + (double)n1 V1) + (double)n2 V2 < 0.
+ *     Nothing is flipped.
+ *  4. Levels run from levels - 1 down to 0 on one T, which starts as init16 (NULL: the identity).  The source pixels of a level
+ *     are the pixels of `prev` with a normal, n_source of them; the targets are those of `cur`.  A level with iters[l] == 0 or
+ *     n_source < min_pairs is SKIPPED.
+ *  5. Evaluation k = 0, 1, ... of a level, per source pixel (u, v) with vertex V and normal n: p_r = ((T[r][0] V0 + T[r][1] V1) +
+ *     T[r][2] V2) + T[r][3], n'_r = (T[r][0] n0 + T[r][1] n1) + T[r][2] n2; p2 > 0; ui = floor((p0 * fx / p2 + ppx) + 0.5), vi
+ *     likewise with fy, ppy; both inside the level's image; the pixel (ui, vi) of `cur` has a normal nt and the vertex q;
+ *     dq = q - p; it is a pair when (dq0 dq0 + dq1 dq1) + dq2 dq2 <= (double)dist_gate * (double)dist_gate and
+ *     (n'0 nt0 + n'1 nt1) + n'2 nt2 >= (double)normal_cos.  r = (nt0 dq0 + nt1 dq1) + nt2 dq2,
+ *     J = (p1 nt2 - p2 nt1, p2 nt0 - p0 nt2, p0 nt1 - p1 nt0, nt0, nt1, nt2): the rotation is about the camera origin.
+ *  6. The 28 sums of ppf_refine_frame (J_i J_j for i <= j row by row, J_i r, r r), each product rounded, then summed by a
+ *     fixed tree: source pixel j = v * cols_l + u is lane j % 64 of chunk j / 64, a lane that is no pair or past the last
+ *     pixel holds +0.0, a chunk is summed by lane l adding lane l + 32, then + 16, 8, 4, 2, 1; the chunk sums are reduced by
+ *     the same tree, chunk c being lane c % 64 of group c / 64, and so on until one value is left.  n_pairs is an integer;
+ *     rmse = (float)sqrt(sum r r / (double)n_pairs), 0 without pairs.
+ *  7. LOST when n_pairs < min_pairs or (double)n_pairs < (double)min_pair_share * (double)n_source.  Otherwise the damped solve
+ *     of ppf_refine_frame (A + 1e-10 trace I, first largest pivot) gives x; STEP when it fails, a component is not finite,
+ *     (x0 x0 + x1 x1) + x2 x2 > max_step_rot^2 or (x3 x3 + x4 x4) + x5 x5 > max_step_trans^2 (the limits as (double) of the
+ *     float, squared).  Else R = Rz(x2) Ry(x1) Rx(x0), M = [R | x3 x4 x5], T <- M T (each element the sum 0 + a0 b0 + a1 b1 +
+ *     a2 b2 + a3 b3), iterations = k + 1; CONVERGED when both squares are <= eps^2, else MAX_ITERS_REACHED at
+ *     k + 1 == iters[l]; both go on to the next finer level.  LOST and STEP end the call with the pose of the evaluation that
+ *     raised them; the finer levels stay NONE, their rows zero.
+ * prev and cur: HOST images of the same rows, cols and format, each with its own pitch (0: packed), with the pointer, pitch
+ * and alignment rules of ppf_cloud_from_depth; dp is its format, depth_scale, z_min, z_max (flags is ignored); intr = {fx,
+ * fy, ppx, ppy}.  init16: row-major 4 x 4 doubles, all finite, or NULL.  pose16 (16 doubles) is required; level_rows (4 rows,
+ * one per level 0..3) and stats may be NULL.  Checked in this order, all PPF_ERR_INVALID before any device work: pose16, mp, dp
+ * or intr NULL; prev; cur; the intrinsics; init16; the fields of mp against the ranges stated beside them; the image against
+ * `levels`.  Without a device the call is PPF_ERR_HIP.  On any error pose16 is init16 (or the identity), the rows and *stats
+ * are zero.  The launch count depends on levels, iters and the image size only (evaluations are enqueued ahead; those behind
+ * the end of their level or of the call return at a device-side state word); one blocking wait.  No float atomics: the result
+ * does not depend on scheduling. */
+ppf_status ppf_depth_motion(const void* prev, size_t prev_pitch_bytes, const void* cur, size_t cur_pitch_bytes, int rows, int cols,
+                            const double* intr, const ppf_depth_params* dp, const ppf_depth_motion_params* mp, const double* init16,
+                            double* pose16, ppf_depth_motion_level* level_rows, ppf_depth_motion_stats* stats);
+/* the same from DEVICE images: enqueued on `stream` (a hipStream_t, NULL: default stream), returns when the pose is complete.
+ * pose16, level_rows and stats are host memory as above.  An image pointer the current device cannot read, an image that
+ * runs past the end of its allocation, or two images that overlap are PPF_ERR_INVALID before anything is launched. */
+ppf_status ppf_depth_motion_device(const void* d_prev, size_t prev_pitch_bytes, const void* d_cur, size_t cur_pitch_bytes, int rows,
+                                   int cols, const double* intr, const ppf_depth_params* dp, const ppf_depth_motion_params* mp,
+                                   const double* init16, void* stream, double* pose16, ppf_depth_motion_level* level_rows,
+                                   ppf_depth_motion_stats* stats);
 
 /* ---- a depth image's surfaces labelled in image space: proposals without leaving the image ----------- */
 #define PPF_SEGMENT_EIGHT 1      /* flags: 8-connectivity instead of 4 */

@@ -161,6 +161,29 @@ PPF_HISTORY_MAX_AGE = 15
 PPF_HISTORY_MEASURED, PPF_HISTORY_FILLED, PPF_HISTORY_UNSUPPORTED, PPF_HISTORY_CHANGED = 1, 2, 3, 16  # the state image
 
 
+class DepthMotionParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("iters", C.c_int32 * 4), ("pyr_gate", C.c_float), ("normal_gate", C.c_float),
+                ("dist_gate", C.c_float), ("normal_cos", C.c_float), ("max_step_rot", C.c_float), ("max_step_trans", C.c_float),
+                ("eps_rot", C.c_float), ("eps_trans", C.c_float), ("min_pair_share", C.c_float), ("min_pairs", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class DepthMotionLevel(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("n_source", C.c_int32),
+                ("n_pairs_first", C.c_int32), ("n_pairs_last", C.c_int32), ("rmse_first", C.c_float), ("rmse_last", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
+class DepthMotionStats(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_evaluations", C.c_int32), ("n_enqueued", C.c_int32), ("n_launches", C.c_int32),
+                ("n_host_syncs", C.c_int32), ("ms_wall", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+PPF_MOTION_MAX_LEVELS, PPF_MOTION_MAX_ITERS = 4, 64
+(PPF_MOTION_NONE, PPF_MOTION_CONVERGED, PPF_MOTION_MAX_ITERS_REACHED, PPF_MOTION_LOST, PPF_MOTION_STEP,
+ PPF_MOTION_SKIPPED) = range(6)  # DepthMotionLevel.status
+
+
 class SegmentParams(C.Structure):
     _fields_ = [("depth_abs", C.c_float), ("depth_quad", C.c_float), ("normal_cos", C.c_float), ("curvature_threshold", C.c_float),
                 ("min_size", C.c_int32), ("max_size", C.c_int32), ("max_segments", C.c_int32), ("flags", C.c_int32),
@@ -455,6 +478,13 @@ _SIGNATURES = {
     "ppf_depth_history_reset": (C.c_int, [C.c_void_p]),
     "ppf_depth_history_info": (C.c_int, [C.c_void_p, C.POINTER(DepthHistoryDesc)]),
     "ppf_depth_history_release": (C.c_int, [C.c_void_p]),
+    "ppf_default_depth_motion_params": (None, [C.POINTER(DepthMotionParams)]),
+    "ppf_depth_motion": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                   C.POINTER(DepthParams), C.POINTER(DepthMotionParams), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                   C.POINTER(DepthMotionLevel), C.POINTER(DepthMotionStats)]),
+    "ppf_depth_motion_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                          C.POINTER(DepthParams), C.POINTER(DepthMotionParams), C.POINTER(C.c_double), C.c_void_p,
+                                          C.POINTER(C.c_double), C.POINTER(DepthMotionLevel), C.POINTER(DepthMotionStats)]),
     "ppf_default_segment_params": (None, [C.POINTER(SegmentParams)]),
     "ppf_depth_segments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(DepthParams), C.c_void_p,
                                      C.POINTER(SegmentParams), C.c_void_p, C.POINTER(SegmentInfo), C.POINTER(C.c_int32),

@@ -765,8 +765,136 @@ class DepthHistory:
         return res if len(res) > 1 else out
 
 
+# ppf_depth_motion_level as a numpy record
+MOTION_LEVEL = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("rows", "<i4"), ("cols", "<i4"), ("n_source", "<i4"),
+                         ("n_pairs_first", "<i4"), ("n_pairs_last", "<i4"), ("rmse_first", "<f4"), ("rmse_last", "<f4"),
+                         ("reserved", "<i4", 3)])
+
+
+def depth_motion(prev, cur, intr, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0, params=None, init=None,
+                 return_info: bool = False, return_stats: bool = False):
+    """The camera's rigid motion between two depth images (ppf_depth_motion): the 4 x 4 float64 ``T`` with
+    ``p_cur = T p_prev`` for a static point, so a pose (model -> camera) of the previous frame is ``T @ pose`` in the current
+    one.  prev, cur: two 2-D images of one shape and dtype, numpy float32 (metres) or uint16 (units of depth_scale metres),
+    rows read at their strides; or two such torch tensors on one GPU, read in place on ``torch.cuda.current_stream()``
+    (ppf_depth_motion_device).  intr: (fx, fy, ppx, ppy) or the 3x3 camera matrix.  params: a DepthMotionParams, a dict of its
+    fields (``iters`` a sequence of up to four counts, level 0 first) or None (the defaults); init: a 4 x 4 start, default the
+    identity.  return_info adds the four level rows (MOTION_LEVEL records, level 0 first), return_stats the call's counters;
+    ``stats["status"]`` LOST or STEP means the motion was not found and ``T`` is the start."""
+    if isinstance(params, dict) and "iters" in params:
+        params = dict(params)
+        iters = [int(v) for v in params.pop("iters")]
+        if len(iters) > _capi.PPF_MOTION_MAX_LEVELS:
+            raise PPFError(_capi.PPF_ERR_INVALID, f"iters holds more than {_capi.PPF_MOTION_MAX_LEVELS} levels")
+        prm = _params(_capi.DepthMotionParams, "ppf_default_depth_motion_params", params, "depth motion")
+        for l, v in enumerate(iters):
+            prm.iters[l] = v
+    else:
+        prm = _params(_capi.DepthMotionParams, "ppf_default_depth_motion_params", params, "depth motion")
+    a = _DepthInput(prev, "prev must be a 2-D float32 or uint16 {kind}")
+    b = _DepthInput(cur, "cur must be a {dtype} {kind} of shape {shape}, as prev is", shape=a.shape,
+                    dtype=next(d for d, f in _DEPTH_FORMATS.items() if f == a.format))
+    if a.is_device != b.is_device or (a.is_device and a.keep.device != b.keep.device):
+        raise PPFError(_capi.PPF_ERR_INVALID, "prev and cur must both be numpy arrays or both be tensors on one GPU")
+    dp = _depth_params(depth_scale, z_min, z_max)
+    dp.format = a.format
+    it = (C.c_double * 4)(*_intr4(intr))
+    start = None
+    if init is not None:
+        m = np.ascontiguousarray(init, dtype=np.float64)
+        if m.size != 16:
+            raise PPFError(_capi.PPF_ERR_INVALID, "init must be a 4 x 4 matrix")
+        start = (C.c_double * 16)(*m.reshape(-1).tolist())
+    pose = (C.c_double * 16)()
+    rows = (_capi.DepthMotionLevel * _capi.PPF_MOTION_MAX_LEVELS)()
+    st = _capi.DepthMotionStats()
+    with a.device():
+        if a.is_device:
+            check(lib().ppf_depth_motion_device(a.ptr, a.pitch, b.ptr, b.pitch, a.rows, a.cols, it, C.byref(dp), C.byref(prm), start, a.stream(),
+                                                pose, rows, C.byref(st)))
+        else:
+            check(lib().ppf_depth_motion(a.ptr, a.pitch, b.ptr, b.pitch, a.rows, a.cols, it, C.byref(dp), C.byref(prm), start, pose, rows,
+                                         C.byref(st)))
+    T = np.array(pose, dtype=np.float64).reshape(4, 4)
+    res = (T,) + ((np.frombuffer(bytes(rows), dtype=MOTION_LEVEL).copy(),) if return_info else ()) + \
+        ((_capi.stats_dict(st),) if return_stats else ())
+    return res if len(res) > 1 else T
+
+
+def _mat44_mul(A, B) -> np.ndarray:
+    """A B as ppf_mat44_mul adds it up (0 + a0 b0 + a1 b1 + a2 b2 + a3 b3, nothing fused): the same bytes on every machine"""
+    A, B = np.asarray(A, dtype=np.float64).reshape(4, 4).tolist(), np.asarray(B, dtype=np.float64).reshape(4, 4).tolist()
+    out = np.empty((4, 4), np.float64)
+    for i in range(4):
+        for j in range(4):
+            acc = 0.0
+            for k in range(4):
+                acc = acc + A[i][k] * B[k][j]
+            out[i, j] = acc
+    return out
+
+
+def _pose_premultiply(p: Pose3D, T) -> None:
+    """p.pose <- T p.pose, with t, q and angle of the new matrix"""
+    M = _mat44_mul(T, p.pose)
+    R = M[:3, :3]
+    p.pose, p.t = M, M[:3, 3].copy()
+    p.angle = float(np.arccos(np.clip((np.trace(R) - 1.0) / 2.0, -1.0, 1.0)))
+    w = np.sqrt(max(0.0, 1.0 + np.trace(R))) / 2.0
+    if w > 1e-6:
+        q = np.array([w, (R[2, 1] - R[1, 2]) / (4 * w), (R[0, 2] - R[2, 0]) / (4 * w), (R[1, 0] - R[0, 1]) / (4 * w)])
+    else:  # a half turn: the axis from the diagonal
+        ax = np.sqrt(np.maximum(0.0, (np.diag(R) + 1.0) / 2.0))
+        q = np.array([0.0, ax[0], np.copysign(ax[1], R[0, 1]), np.copysign(ax[2], R[0, 2])])
+    p.q = q / np.linalg.norm(q)
+
+
+class DepthOdometry:
+    """Frame-to-frame camera tracking on depth images alone: ``push`` takes the next frame, runs ``depth_motion`` from the
+    frame kept before it and accumulates ``pose``, which takes the first frame's camera coordinates to the current frame's.
+    rows, cols, intr: fixed for the stream; depth_scale, z_min, z_max, params: as ``depth_motion`` takes them.  A numpy frame
+    is copied, a GPU tensor is cloned on its device, so the caller may reuse its buffer."""
+
+    def __init__(self, rows: int, cols: int, intr, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0, params=None):
+        self.shape = (int(rows), int(cols))
+        self.intr = _intr4(intr)
+        self._kw = dict(depth_scale=depth_scale, z_min=z_min, z_max=z_max, params=params)
+        self.reset()
+
+    def reset(self) -> None:
+        """forget the previous frame; ``pose`` is the identity again and the next push only keeps its frame"""
+        self._prev = None
+        self.pose = np.eye(4)
+        self.frames = 0
+        self.last_info = None
+        self.last_stats: Dict[str, object] = {}
+
+    def push(self, depth, keep_on_failure: bool = False):
+        """(T, status): the motion from the frame kept before to this one and PPF_MOTION_* of the call; the first push gives
+        the identity and PPF_MOTION_NONE.  On LOST or STEP ``pose`` stays where it was, T is the identity, and the new frame
+        becomes the next previous frame only with ``keep_on_failure`` (else the next push is measured against the old one)."""
+        if tuple(depth.shape) != self.shape:
+            raise PPFError(_capi.PPF_ERR_INVALID, f"depth must have the shape {self.shape}")
+        own = depth.clone() if type(depth).__module__.startswith("torch") else np.array(depth)
+        if self._prev is None:
+            self._prev = own
+            self.frames = 1
+            return np.eye(4), _capi.PPF_MOTION_NONE
+        T, self.last_info, self.last_stats = depth_motion(self._prev, own, self.intr, return_info=True, return_stats=True, **self._kw)
+        status = int(self.last_stats["status"])
+        failed = status in (_capi.PPF_MOTION_LOST, _capi.PPF_MOTION_STEP)
+        if failed:
+            T = np.eye(4)
+        else:
+            self.pose = _mat44_mul(T, self.pose)
+        if not failed or keep_on_failure:
+            self._prev = own
+        self.frames += 1
+        return T, status
+
+
 # ppf_segment_info as a numpy record
-SEGMENT_INFO = np.dtype([("n_pixels", "<i4"), ("n_border", "<i4"), ("first_pixel", "<i4"), ("box_xywh", "<i4", 4), ("z_lo", "<f4"),
+SEGMENT_INFO =np.dtype([("n_pixels", "<i4"), ("n_border", "<i4"), ("first_pixel", "<i4"), ("box_xywh", "<i4", 4), ("z_lo", "<f4"),
                          ("z_hi", "<f4"), ("reserved", "<i4", 3)])
 
 
@@ -945,6 +1073,10 @@ class CloudProcessor:
         self.depth_history_stats: Dict[str, object] = {}
         self.depth_state = None
         self._depth_history: Optional[tuple] = None
+        # TrackCamera: the last motion, its level rows and the ppf_depth_motion counters
+        self.camera_motion: Optional[np.ndarray] = None
+        self.motion_info = None
+        self.motion_stats: Dict[str, object] = {}
         # ProposeSegments: the info rows of the image's segments, its label image and the counters
         self.segment_info: Optional[np.ndarray] = None
         self.segment_labels: Optional[np.ndarray] = None
@@ -1244,6 +1376,31 @@ class CloudProcessor:
             for k, p in zip(ks, refined[i]):
                 self.frame_poses[i][k] = p
         return self.frame_poses
+
+    def TrackCamera(self, depth, CameraIntr=None, params=None, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0):
+        """The camera's motion from the processor's depth image (``self.depth``) to ``depth``, the next frame of the same
+        camera (one ppf_depth_motion call), applied to every pose of ``frame_poses``: pose <- T pose, so the
+        next ``RefineFrame(depth)`` starts from where the camera's motion has carried the objects.  CameraIntr: default
+        PrepareFrame's; params: fields of DepthMotionParams.  Sets ``camera_motion`` (T), ``motion_info``, ``motion_stats`` and
+        ``timings["track_camera"]``; returns (T, status).  On LOST or STEP the poses stay as they are and T is the identity.
+        ``self.depth`` is left alone: RefineFrame(depth) replaces it."""
+        intr = self.frame_intr if CameraIntr is None else CameraIntr
+        if self.depth is None or intr is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "TrackCamera needs the previous depth image and the camera intrinsics")
+        t0 = time.perf_counter()
+        T, self.motion_info, self.motion_stats = depth_motion(self.depth, np.ascontiguousarray(depth, dtype=np.float32), intr,
+                                                              depth_scale=depth_scale, z_min=z_min, z_max=z_max, params=params,
+                                                              return_info=True, return_stats=True)
+        self.timings["track_camera"] = time.perf_counter() - t0
+        status = int(self.motion_stats["status"])
+        if status in (_capi.PPF_MOTION_LOST, _capi.PPF_MOTION_STEP):
+            T = np.eye(4)
+        else:
+            for plist in self.frame_poses:
+                for p in plist:
+                    _pose_premultiply(p, T)
+        self.camera_motion = T
+        return T, status
 
     def _match_frame(self, labels, step, dist, top: int = 5) -> List[Optional[Pose3D]]:
         dets = (FrameDetection * max(len(labels), 1))()

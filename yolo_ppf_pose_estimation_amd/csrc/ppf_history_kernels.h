@@ -41,12 +41,13 @@ struct HistoryArgs {
   int32_t* counters;    /* DH_N_COUNTERS, preset to 0 */
 };
 
-/* a lane's four input pixels as z, 0 where the pixel is not kept or lies past the row's end */
+/* a lane's four input pixels as z, 0 where the pixel is not kept or lies past the row's end; in_vec: the whole-lane load is
+ * aligned (decided on the host from pointer and pitch).  Shared with ppf_motion_kernels.h. */
 template <class T>
-__device__ __forceinline__ void history_load(const DepthArgs& a, const HistoryArgs& ha, int v, int u0, float (&z)[DH_PX]) {
+__device__ __forceinline__ void history_load(const DepthArgs& a, int in_vec, int v, int u0, float (&z)[DH_PX]) {
   const T* row = reinterpret_cast<const T*>(a.img + (size_t)v * a.pitch) + u0;
   T px[DH_PX];
-  if (ha.in_vec && u0 + DH_PX <= a.cols) {
+  if (in_vec && u0 + DH_PX <= a.cols) {
     struct alignas(sizeof(T) * DH_PX) Quad { T e[DH_PX]; };
     const Quad q = *reinterpret_cast<const Quad*>(row);
 #pragma unroll
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(DH_BLOCK) void k_history_push(DepthArgs a, HistoryA
     float s[DH_PX][K];
     {
       float z[DH_PX];
-      history_load<T>(a, ha, v, u0, z);
+      history_load<T>(a, ha.in_vec, v, u0, z);
 #pragma unroll
       for (int j = 0; j < DH_PX; j++) {
         s[j][0] = z[j];
