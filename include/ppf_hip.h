@@ -373,6 +373,32 @@ ppf_status ppf_debug_accumulators_ws(const ppf_model* m, ppf_workspace* ws, cons
 /* Size of the cached device block a request of `bytes` is served from (host only, no device needed): classes of 1/8
  * octave, so at most 12.5 % more than asked for.  Test surface of the block cache's keying. */
 size_t ppf_debug_block_size(size_t bytes);
+/* Guard mode of the device block cache: finds stores outside a scratch or result buffer and reads of scratch that was
+ * never written, which the cache otherwise hides (a request is rounded up to a size class, so a store a few bytes too far
+ * lands in slack nobody reads, and a reused block still holds the previous call's bytes).  mode 0: off (the default);
+ * 1, 2: every block acquired from now on gets a 256-byte zone in front of it and a zone of at least 4 KiB right behind
+ * the bytes asked for, both filled with 0xA5, and its usable bytes are filled with the 32-bit word 0 (mode 1) or 1
+ * (mode 2): a result that differs between the two modes, or from the guard-off result, read memory nobody wrote.  The
+ * zones are read back when a block is released and by ppf_debug_pool_check (the first 4 KiB of the back zone).  Switching
+ * trims the cache; blocks already live keep the mode they were acquired in.  Sub-buffers a stage carves out of one block
+ * itself have no zones between them.  PPF_POOL_GUARD=1|2 in the environment turns the mode on from the first allocation
+ * and prints each violation to stderr ("ppf pool guard: ...") when it is found.  PPF_ERR_INVALID for any other mode,
+ * PPF_ERR_HIP without a device.  Debug / test surface: every acquire waits for the device. */
+ppf_status ppf_debug_pool_guard(int mode);
+typedef struct ppf_debug_pool_violation {
+  uint64_t requested_bytes; /* what the block's reserve asked for */
+  int64_t first_offset;     /* of the first damaged byte from the block's usable start: < 0 in the front zone, >= requested_bytes behind */
+  uint64_t n_bytes_damaged; /* in both zones together */
+} ppf_debug_pool_violation;
+typedef struct ppf_debug_pool_report {
+  uint64_t n_blocks_live;    /* guarded blocks in use */
+  uint64_t n_blocks_checked; /* the live ones, and those released since the last check */
+  uint64_t n_violations;     /* damaged blocks among them */
+  ppf_debug_pool_violation first[8];
+} ppf_debug_pool_report;
+/* Waits for the device, checks the zones of every live guarded block, adds the violations found at releases since the
+ * last check and forgets those. */
+ppf_status ppf_debug_pool_check(ppf_debug_pool_report* r);
 /* Evaluate include/ppf_detmath.h on the device: fn 0 acos(x), 1 sin(x), 2 cos(x), 3 atan2(x, y), 4 sqrt(x),
  * 5 x / y.  The bit patterns must equal the host's (tests/test_gpu_detmath.py). */
 ppf_status ppf_debug_device_math(int fn, const double* x, const double* y, double* out, int n);

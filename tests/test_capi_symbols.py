@@ -34,15 +34,17 @@ def test_struct_layouts_match_the_header(tmp_path):
     """sizeof() of every struct as a C compiler sees include/ppf_hip.h == the ctypes mirror."""
     import subprocess
     src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ppf_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\\n",'
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ppf_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n",'
                    'sizeof(ppf_pose),sizeof(ppf_vote),sizeof(ppf_train_params),sizeof(ppf_match_params),'
                    'sizeof(ppf_model_info),sizeof(ppf_match_stats),sizeof(ppf_batch_stats),'
-                   'offsetof(ppf_match_stats, n_lds_atomics),offsetof(ppf_match_params, vote_mode));return 0;}\n')
+                   'offsetof(ppf_match_stats, n_lds_atomics),offsetof(ppf_match_params, vote_mode),'
+                   'sizeof(ppf_debug_pool_violation),sizeof(ppf_debug_pool_report),offsetof(ppf_debug_pool_report, first));return 0;}\n')
     exe = tmp_path / "sz"
     subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     want = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
     got = [C.sizeof(t) for t in (_capi.Pose, _capi.Vote, TrainParams, MatchParams, _capi.ModelInfo, _capi.MatchStats,
-                                 _capi.BatchStats)] + [_capi.MatchStats.n_lds_atomics.offset, MatchParams.vote_mode.offset]
+                                 _capi.BatchStats)] + [_capi.MatchStats.n_lds_atomics.offset, MatchParams.vote_mode.offset,
+                                                     C.sizeof(_capi.PoolViolation), C.sizeof(_capi.PoolReport), _capi.PoolReport.first.offset]
     assert got == want
 
 
@@ -148,6 +150,18 @@ def test_block_cache_size_classes():
         assert g >= prev
         prev = g
     assert len({f(n) for n in range(256, 4096)}) <= 8 * 4 + 1  # four octaves, eight classes each
+
+
+def test_pool_guard_arguments_are_checked_before_the_device():
+    """ppf_debug_pool_guard / ppf_debug_pool_check: a mode outside 0..2 and a NULL report are PPF_ERR_INVALID; without a device
+    a valid call is PPF_ERR_HIP, as the compute entries are"""
+    assert lib().ppf_debug_pool_guard(3) == _capi.PPF_ERR_INVALID and "mode" in _capi.last_error()
+    assert lib().ppf_debug_pool_guard(-1) == _capi.PPF_ERR_INVALID
+    assert lib().ppf_debug_pool_check(None) == _capi.PPF_ERR_INVALID
+    if lib().ppf_device_count() == 0:
+        r = _capi.PoolReport()
+        assert lib().ppf_debug_pool_guard(1) == _capi.PPF_ERR_HIP and "no HIP device" in _capi.last_error()
+        assert lib().ppf_debug_pool_check(C.byref(r)) == _capi.PPF_ERR_HIP
 
 
 def test_workspace_options_are_checked_on_the_host():

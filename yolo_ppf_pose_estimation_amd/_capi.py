@@ -72,6 +72,15 @@ class MatchStats(C.Structure):
                 ("n_acc32_items", C.c_uint64), ("n_tables", C.c_uint64), ("phase_clocks", C.c_uint64 * 8)]
 
 
+class PoolViolation(C.Structure):
+    _fields_ = [("requested_bytes", C.c_uint64), ("first_offset", C.c_int64), ("n_bytes_damaged", C.c_uint64)]
+
+
+class PoolReport(C.Structure):
+    _fields_ = [("n_blocks_live", C.c_uint64), ("n_blocks_checked", C.c_uint64), ("n_violations", C.c_uint64),
+                ("first", PoolViolation * 8)]
+
+
 def stats_dict(st):
     """A stats structure as a plain dict (array fields as lists)."""
     out = {}
@@ -416,6 +425,8 @@ _SIGNATURES = {
                                             C.c_int, C.POINTER(MatchParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     "ppf_debug_block_size": (C.c_size_t, [C.c_size_t]),
     "ppf_debug_device_math": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "ppf_debug_pool_guard": (C.c_int, [C.c_int]),
+    "ppf_debug_pool_check": (C.c_int, [C.POINTER(PoolReport)]),
     "ppf_workspace_device_poses": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     "ppf_workspace_copy_top_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ppf_workspace_copy_raw_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

@@ -393,7 +393,7 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
     }
     va.odd_epoch = ws->odd_epoch;
 #if PPF_ABL_GROUP != 1 /* attribution builds of k_group store no payload: the later kernels read zeros, never stale values */
-    HIPCHK(hipMemsetAsync(ws->s_a64.p, 0, ws->s_a64.bytes(), st));
+    HIPCHK(hipMemsetAsync(ws->s_a64.p, 0, ws->s_a64.cap * sizeof(*ws->s_a64.p), st));
 #endif
     /* a thread per reference point, and enough threads for its look at the paired points (40 waves walking 50,000 points: 10 us) */
     k_frames<<<dim3(std::max((va.n_ref + 63) / 64, std::min((va.paired.n + 63) / 64, 1024))), dim3(64), 0, st>>>(va);
@@ -674,6 +674,21 @@ ppf_status ppf_debug_accumulators(const ppf_model* m, const float* scene, int ns
 /* the block cache's size class for a request (host only): what DevBuf is granted for `bytes` */
 size_t ppf_debug_block_size(size_t bytes) {
   return DevPool::class_size(DevPool::class_of(std::max<size_t>(bytes, 256)));
+}
+
+/* the block cache's guard mode (ppf_device_mem.h) */
+ppf_status ppf_debug_pool_guard(int mode) {
+  if (mode < 0 || mode > 2) return fail(PPF_ERR_INVALID, "ppf_debug_pool_guard: mode is 0 (off), 1 or 2");
+  if (!have_device()) return fail(PPF_ERR_HIP, "ppf_debug_pool_guard: no HIP device");
+  DevPool::get().set_guard(mode);
+  return PPF_OK;
+}
+
+ppf_status ppf_debug_pool_check(ppf_debug_pool_report* r) {
+  if (!r) return fail(PPF_ERR_INVALID, "ppf_debug_pool_check: NULL");
+  if (!have_device()) return fail(PPF_ERR_HIP, "ppf_debug_pool_check: no HIP device");
+  HIPCHK(DevPool::get().check(r));
+  return PPF_OK;
 }
 
 ppf_status ppf_debug_device_math(int fn, const double* x, const double* y, double* out, int n) {
