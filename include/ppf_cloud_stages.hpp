@@ -524,6 +524,7 @@ class Cloud {
   };
   template <class P>
   static P orDefaults(const P* given, void (*defaults)(P*)) { P p; if (given) p = *given; else defaults(&p); return p; }
+  friend class DepthVolume; /* its extract() returns a Cloud */
   explicit Cloud(ppf_cloud* c) : h_(c, [](ppf_cloud* p) { ppf_cloud_release(p); }) {}
   static Cloud fromDepthImage(const void* depth, int format, double scale, int rows, int cols, double fx, double fy, double ppx,
                               double ppy, float zMin, float zMax, bool fp64, size_t rowPitchBytes,
@@ -724,6 +725,142 @@ class DepthOdometry {
   int frames_;
   double intr_[4], pose_[16];
   std::vector<float> prev_;
+};
+
+/* ppf_depth_volume: a truncated signed distance volume on the device that posed depth images are fused into.
+ * A pose is 16 doubles, row-major, world -> camera, as DepthOdometry::pose() is; intr = {fx, fy, ppx, ppy}.  integrate adds a
+ * frame seen from a pose; raycast gives the volume's float32 depth image (0 where no surface is hit) from any pose, which
+ * filterDepth, Cloud::fromDepth, depthMotion and every frame stage take; extract returns the zero surface as a Cloud with
+ * normals, which train takes.  Copies share the volume. */
+class DepthVolume {
+ public:
+  static ppf_depth_volume_params defaultParams() {
+    ppf_depth_volume_params p;
+    ppf_default_depth_volume_params(&p);
+    return p;
+  }
+  DepthVolume() {}
+  explicit DepthVolume(const ppf_depth_volume_params& params) {
+    ppf_depth_volume* v = nullptr;
+    ppf_match_3d::check(ppf_depth_volume_create(&params, &v));
+    h_ = std::shared_ptr<ppf_depth_volume>(v, [](ppf_depth_volume* p) { ppf_depth_volume_release(p); });
+  }
+  ppf_depth_volume* handle() const { return h_.get(); }
+  void reset() { ppf_match_3d::check(ppf_depth_volume_reset(need())); }
+  ppf_depth_volume_desc info() const {
+    ppf_depth_volume_desc d;
+    ppf_match_3d::check(ppf_depth_volume_info(need(), &d));
+    return d;
+  }
+  /* float32 metres in; rowPitchBytes 0: packed rows */
+  ppf_depth_volume_integrate_stats integrate(const float* depth, int rows, int cols, const double* intr, const double* pose16, float zMin = 0.f,
+                                             float zMax = 0.f, size_t rowPitchBytes = 0) {
+    return run(depth, PPF_DEPTH_F32, 0.001, rows, cols, intr, pose16, zMin, zMax, rowPitchBytes);
+  }
+  /* a 16-bit sensor image: z = d * scale metres (0.001 for millimetres) */
+  ppf_depth_volume_integrate_stats integrateU16(const uint16_t* depth, int rows, int cols, double scale, const double* intr,
+                                                const double* pose16, float zMin = 0.f, float zMax = 0.f, size_t rowPitchBytes = 0) {
+    return run(depth, PPF_DEPTH_U16, scale, rows, cols, intr, pose16, zMin, zMax, rowPitchBytes);
+  }
+  /* the packed rows x cols depth image; normals: 0, or it receives the packed rows x cols x 3 normals in camera coordinates */
+  std::vector<float> raycast(int rows, int cols, const double* intr, const double* pose16, const ppf_depth_volume_raycast_params* params = 0,
+                             std::vector<float>* normals = 0, ppf_depth_volume_raycast_stats* stats = 0) const {
+    ppf_depth_volume_raycast_params rp;
+    if (params) rp = *params; else ppf_default_depth_volume_raycast_params(&rp);
+    const size_t n = (size_t)(rows > 0 ? rows : 0) * (size_t)(cols > 0 ? cols : 0);
+    std::vector<float> out(n + 1), nr(normals ? n * 3 + 1 : 1);
+    ppf_match_3d::check(ppf_depth_volume_raycast(need(), rows, cols, intr, pose16, &rp, &out[0], normals ? &nr[0] : 0, stats));
+    out.resize(n);
+    if (normals) {
+      nr.resize(n * 3);
+      normals->swap(nr);
+    }
+    return out;
+  }
+  Cloud extract(const ppf_depth_volume_extract_params* params = 0, ppf_depth_volume_extract_stats* stats = 0) const {
+    ppf_depth_volume_extract_params ep;
+    if (params) ep = *params; else ppf_default_depth_volume_extract_params(&ep);
+    ppf_cloud* c = nullptr;
+    ppf_match_3d::check(ppf_depth_volume_extract(need(), &ep, &c, stats));
+    return Cloud(c);
+  }
+  /* every voxel, x fastest: nx * ny * nz records */
+  std::vector<ppf_depth_volume_voxel> read() const {
+    const ppf_depth_volume_desc d = info();
+    std::vector<ppf_depth_volume_voxel> out((size_t)d.dims[0] * (size_t)d.dims[1] * (size_t)d.dims[2]);
+    ppf_match_3d::check(ppf_depth_volume_read(need(), &out[0], out.size()));
+    return out;
+  }
+
+ private:
+  ppf_depth_volume* need() const {
+    if (!h_) throw ppf_match_3d::Error(PPF_ERR_INVALID, "prep::DepthVolume: empty handle");
+    return h_.get();
+  }
+  ppf_depth_volume_integrate_stats run(const void* depth, int format, double scale, int rows, int cols, const double* intr, const double* pose16,
+                                       float zMin, float zMax, size_t rowPitchBytes) {
+    const ppf_depth_params dp = depthParams(format, scale, zMin, zMax);
+    ppf_depth_volume_integrate_stats st;
+    ppf_match_3d::check(ppf_depth_volume_integrate(need(), depth, rows, cols, rowPitchBytes, intr, &dp, pose16, &st));
+    return st;
+  }
+  std::shared_ptr<ppf_depth_volume> h_;
+};
+
+/* Frame-to-model camera tracking and fusion on float32 depth images: the first push integrates the frame at the identity; every
+ * later push raycasts the volume from pose(), runs depthMotion(prev = that image, cur = the frame), sets pose() to T * pose()
+ * (summed as ppf_mat44_mul sums it) and integrates the frame there.  When the motion is not found, pose() and the volume stay as
+ * they were.  modelDepth() is the last raycast image.  The volume's world is the first frame's camera. */
+class DepthFusion {
+ public:
+  DepthFusion(int rows, int cols, const double* intr, const DepthVolume& volume, const ppf_depth_motion_params* motion = 0,
+              const ppf_depth_volume_raycast_params* raycast = 0, float zMin = 0.f, float zMax = 0.f)
+      : rows_(rows), cols_(cols), vol_(volume), mp_(motion ? *motion : defaultDepthMotionParams()), zMin_(zMin), zMax_(zMax), frames_(0) {
+    for (int i = 0; i < 4; i++) intr_[i] = intr[i];
+    if (raycast) rp_ = *raycast; else ppf_default_depth_volume_raycast_params(&rp_);
+    for (int i = 0; i < 16; i++) pose_[i] = (i % 5 == 0) ? 1.0 : 0.0;
+  }
+  const double* pose() const { return pose_; }
+  int frames() const { return frames_; }
+  const std::vector<float>& modelDepth() const { return model_; }
+  DepthVolume& volume() { return vol_; }
+  /* updated: 0, or it receives the integration's counters (zero when nothing was integrated) */
+  DepthMotion push(const float* depth, ppf_depth_volume_integrate_stats* updated = 0) {
+    DepthMotion m = DepthMotion();
+    ppf_depth_volume_integrate_stats st = ppf_depth_volume_integrate_stats();
+    if (frames_ == 0) {
+      for (int i = 0; i < 16; i++) m.T[i] = (i % 5 == 0) ? 1.0 : 0.0;
+      m.status = PPF_MOTION_NONE;
+      st = vol_.integrate(depth, rows_, cols_, intr_, pose_, zMin_, zMax_);
+    } else {
+      model_ = vol_.raycast(rows_, cols_, intr_, pose_, &rp_);
+      m = depthMotion(&model_[0], depth, rows_, cols_, intr_, &mp_, 0, zMin_, zMax_);
+      if (m.found()) {
+        double next[16];
+        for (int i = 0; i < 4; i++)
+          for (int j = 0; j < 4; j++) {
+            double s = 0;
+            for (int k = 0; k < 4; k++) s += m.T[i * 4 + k] * pose_[k * 4 + j];
+            next[i * 4 + j] = s;
+          }
+        for (int i = 0; i < 16; i++) pose_[i] = next[i];
+        st = vol_.integrate(depth, rows_, cols_, intr_, pose_, zMin_, zMax_);
+      }
+    }
+    frames_++;
+    if (updated) *updated = st;
+    return m;
+  }
+
+ private:
+  int rows_, cols_;
+  DepthVolume vol_;
+  ppf_depth_motion_params mp_;
+  ppf_depth_volume_raycast_params rp_;
+  float zMin_, zMax_;
+  int frames_;
+  double intr_[4], pose_[16];
+  std::vector<float> model_;
 };
 
 /* ppf_depth_segments: the depth image's connected surfaces labelled in image space.  Returns the label image

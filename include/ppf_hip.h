@@ -903,6 +903,172 @@ ppf_status ppf_depth_motion_device(const void* d_prev, size_t prev_pitch_bytes, 
                                    const double* init16, void* stream, double* pose16, ppf_depth_motion_level* level_rows,
                                    ppf_depth_motion_stats* stats);
 
+/* ---- posed depth images fused into a truncated signed distance volume: integrate, raycast, extract ---- */
+#define PPF_VOLUME_MAX_DIM 1024
+#define PPF_VOLUME_MAX_WEIGHT 65535
+#define PPF_VOLUME_MAX_STEPS 4096 /* samples of a raycast walk */
+#define PPF_VOLUME_MAX_TILES 16777215 /* 16 x 16 pixel tiles of a raycast image: ceil(rows / 16) * ceil(cols / 16) */
+typedef struct ppf_depth_volume_params {
+  int32_t dims[3];    /* nx, ny, nz, each 1..1024; default 256 each */
+  float voxel;        /* metres, finite, > 0; default 0.004 */
+  double origin[3];   /* finite: world coordinates of the centre of voxel (0, 0, 0); default {-0.510, -0.510, 0.302}: a 1.024 m cube on
+                         the optical axis that starts 0.3 m out */
+  float trunc;        /* metres, finite, >= voxel; default 0.016 */
+  int32_t max_weight; /* 1..65535; default 64 */
+  int32_t flags;      /* 0 */
+  int32_t reserved[4];
+} ppf_depth_volume_params;
+typedef struct ppf_depth_volume_voxel {
+  float d;   /* the truncated signed distance in units of trunc, -1..1: > 0 in front of the surface */
+  int32_t w; /* observations, capped at max_weight; 0: unobserved, d = 1.0f */
+} ppf_depth_volume_voxel;
+typedef struct ppf_depth_volume_desc {
+  int32_t dims[3];
+  float voxel;
+  double origin[3];
+  float trunc;
+  int32_t max_weight;
+  int64_t integrations; /* successful integrations since creation or the last reset */
+  uint64_t device_bytes;
+  int32_t reserved[4];
+} ppf_depth_volume_desc;
+typedef struct ppf_depth_volume_integrate_stats {
+  int64_t n_updated;    /* voxels the call updated */
+  int32_t n_launches;   /* 1 */
+  int32_t n_host_syncs; /* 1 */
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_depth_volume_integrate_stats;
+typedef struct ppf_depth_volume_raycast_params {
+  float z_near, z_far; /* metres along the optical axis, finite, 0 < z_near < z_far; default 0.3, 1.5 */
+  float ray_step;      /* the step as a share of trunc, in (0, 1]; default 0.5 */
+  int32_t min_weight;  /* >= 1; default 1 */
+  int32_t flags;       /* 0 */
+  int32_t reserved[4];
+} ppf_depth_volume_raycast_params;
+typedef struct ppf_depth_volume_raycast_stats {
+  int32_t n_hits;
+  int32_t n_interpolated; /* the hits whose bracket came from tri */
+  int32_t n_launches;     /* 1 */
+  int32_t n_host_syncs;   /* 1 */
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_depth_volume_raycast_stats;
+typedef struct ppf_depth_volume_extract_params {
+  int32_t min_weight; /* >= 1; default 1 */
+  int32_t flags;      /* 0 */
+  int32_t reserved[4];
+} ppf_depth_volume_extract_params;
+typedef struct ppf_depth_volume_extract_stats {
+  int64_t n_crossings;  /* sign changes between two observed, unsaturated neighbours */
+  int64_t n_rows;       /* those with a normal: the cloud's rows */
+  int32_t n_launches;   /* 7 */
+  int32_t n_host_syncs; /* 2: the read-back that sizes the cloud, and the end */
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_depth_volume_extract_stats;
+typedef struct ppf_depth_volume ppf_depth_volume;
+/* dims 256 256 256, voxel 0.004, origin -0.510 -0.510 0.302, trunc 0.016, max_weight 64, flags 0 */
+void ppf_default_depth_volume_params(ppf_depth_volume_params* p);
+/* z_near 0.3, z_far 1.5, ray_step 0.5, min_weight 1, flags 0 */
+void ppf_default_depth_volume_raycast_params(ppf_depth_volume_raycast_params* p);
+/* min_weight 1, flags 0 */
+void ppf_default_depth_volume_extract_params(ppf_depth_volume_extract_params* p);
+/* A ppf_depth_volume is nx * ny * nz records {float d; int32_t w} on the device, x fastest: voxel (i, j, k) is record
+ * (k * ny + j) * nx + i and its centre lies at origin_a + (double)index_a * (double)voxel.  Creation and reset set every record
+ * to d = 1.0f, w = 0: unobserved.  A pose argument is pose16: row-major 4 x 4 doubles T, all finite, world -> camera; R and t
+ * are its rotation and translation.  Everything below is fp64 as written, left to right, nothing fused; voxel and trunc enter
+ * as (double) of the floats; z(p) and "kept" are ppf_cloud_from_depth's; dp->flags is ignored.
+ *
+ * INTEGRATE, per voxel (i, j, k):
+ *  1. P0 = origin[0] + (double)i * voxel, P1 and P2 likewise with j and k.
+ *  2. p_r = ((T[r][0] P0 + T[r][1] P1) + T[r][2] P2) + T[r][3].
+ *  3. The voxel is skipped unless p2 > 0; uf = floor((p0 * fx / p2 + ppx) + 0.5) and vf likewise with p1, fy, ppy satisfy, as
+ *     doubles, 0 <= uf < cols and 0 <= vf < rows (a NaN satisfies nothing); and the pixel (uf, vf) is kept.  Z = (double)z.
+ *  4. sdf = Z - p2; the voxel is skipped when sdf < -trunc.
+ *  5. dn = sdf / trunc, and 1.0 when that is larger than 1.0.
+ *  6. d <- (float)(((double)d * (double)w + dn) / (double)(w + 1)); w <- min(w + 1, max_weight).
+ * A skipped voxel keeps its bytes.  n_updated counts the others.
+ *
+ * RAYCAST makes an image of the caller's rows, cols and intr, which need not be an input's.  step = (double)ray_step * trunc,
+ * K = ceil(((double)z_far - (double)z_near) / step); K > PPF_VOLUME_MAX_STEPS is an argument error.  Per image
+ * c_a = -((R[0][a] t0 + R[1][a] t1) + R[2][a] t2).  Per pixel (u, v): dc = (((double)u - ppx) / fx, ((double)v - ppy) / fy, 1),
+ * dw_a = (R[0][a] dc0 + R[1][a] dc1) + R[2][a] dc2, point(s)_a = c_a + s * dw_a: s is the camera-frame depth.
+ *   near(P): the voxel floor((P_a - origin_a) / voxel + 0.5) per axis; "none" when it is outside the volume (compared as
+ *     doubles) or its w < min_weight, else (double)d.
+ *   tri(P): g_a = (P_a - origin_a) / voxel, b_a = floor(g_a), f_a = g_a - b_a; "none" unless all eight voxels b + {0,1}^3 are
+ *     inside the volume with w >= min_weight; else seven lerps lo + f * (hi - lo): four along x (f_0), then two along y of
+ *     those, then one along z.
+ * The walk: s_k = z_near + (double)k * step for k = 0 .. K - 1; a sample is front when near gives a value > 0, back when it
+ * gives a value <= 0, neither when it gives none.  The walk ends at the first back sample k; the pixel is a hit iff k >= 1
+ * and sample k - 1 was front.  For a hit a0 = tri(point(s_{k-1})), a1 = tri(point(s_k)); when both exist and a0 > 0 >= a1 they
+ * are (f0, f1) and the hit counts in n_interpolated, else the two near values are.  s* = s_{k-1} + step * f0 / (f0 - f1); the
+ * depth written is (float)s*, every other pixel gets 0.0f: a PPF_DEPTH_F32 image for every depth stage.  The optional normals
+ * image (packed rows x cols x 3 floats) is, with P* = point(s*): g_a = tri(P* + voxel e_a) - tri(P* - voxel e_a),
+ * len = sqrt((g0 g0 + g1 g1) + g2 g2); zeros when any of the six is none or len is 0 (or the pixel is no hit); else
+ * n_w = g / len and n_r = (R[r][0] n_w0 + R[r][1] n_w1) + R[r][2] n_w2 cast to float: camera coordinates, nothing flipped.
+ *
+ * EXTRACT, for every voxel in linear order and for the axes x, y, z in that order: m is the voxel one step along the axis and
+ * must be inside the volume; both have w >= min_weight and fabs((double)d) < 1 (saturated free space is no surface); and
+ * (d0 > 0) != (d1 > 0): a crossing.  t = (double)d0 / ((double)d0 - (double)d1); the point is the voxel's centre with
+ * t * voxel added along the axis.  The gradient at a lattice voxel is (double)d(+e_a) - (double)d(-e_a) per axis and needs its
+ * six neighbours inside the volume with w >= min_weight (nothing else is asked of them); g = g(voxel) + t * (g(m) - g(voxel)),
+ * len = sqrt((g0 g0 + g1 g1) + g2 g2), the normal g / len.  A crossing gives no row when either gradient is undefined or len
+ * is 0.  The cloud's rows are x y z nx ny nz as floats in world coordinates, curvature 0, in (linear voxel index, axis) order;
+ * no row gives an empty cloud.
+ *
+ * Calls on one volume are serialised inside the library; different volumes may be used from different threads.
+ *
+ * create: out, then vp NULL; dims; voxel; origin; trunc; max_weight; flags -- PPF_ERR_INVALID in this order, before any
+ * device work; then PPF_ERR_HIP without a device; a volume that cannot be allocated is PPF_ERR_NOMEM.  *out is NULL on any
+ * error. */
+ppf_status ppf_depth_volume_create(const ppf_depth_volume_params* vp, ppf_depth_volume** out);
+/* A test surface: create's argument checks and a handle that holds the params and no device memory, made without asking for a
+ * device.  _info and _release take it; every other entry checks its arguments as on a real volume and then, where a real one
+ * would start its device work, is PPF_ERR_HIP without a device and PPF_ERR_INVALID with one. */
+ppf_status ppf_debug_depth_volume_shell(const ppf_depth_volume_params* vp, ppf_depth_volume** out);
+ppf_status ppf_depth_volume_release(ppf_depth_volume* v);
+/* every record back to {1.0f, 0}, integrations to 0 */
+ppf_status ppf_depth_volume_reset(ppf_depth_volume* v);
+/* the params of creation, the integrations since the last reset and the device memory held */
+ppf_status ppf_depth_volume_info(const ppf_depth_volume* v, ppf_depth_volume_desc* info);
+/* the nx * ny * nz records to HOST memory in linear order: a plain blocking copy.  n_voxels must be nx * ny * nz. */
+ppf_status ppf_depth_volume_read(const ppf_depth_volume* v, ppf_depth_volume_voxel* out, size_t n_voxels);
+/* Integrate a HOST image with the pointer, pitch and alignment rules of ppf_cloud_from_depth; intr = {fx, fy, ppx, ppy}.
+ * Checked in this order, all PPF_ERR_INVALID before any device work: v NULL; pose16 NULL; dp or intr NULL; the image as
+ * ppf_cloud_from_depth checks it (depth NULL, size, format, pitch, alignment, depth_scale, z range); the intrinsics; pose16
+ * finite.  Then PPF_ERR_HIP without a device.  One launch and one blocking wait whatever the image holds.  On any error the
+ * volume keeps its bytes, its integrations do not advance and *stats is zero. */
+ppf_status ppf_depth_volume_integrate(ppf_depth_volume* v, const void* depth, int rows, int cols, size_t row_pitch_bytes,
+                                      const double* intr, const ppf_depth_params* dp, const double* pose16,
+                                      ppf_depth_volume_integrate_stats* stats /* may be NULL */);
+/* the same from a DEVICE image: enqueued on `stream` (a hipStream_t, NULL: default stream), returns when the volume is
+ * complete.  After the checks above: an image the current device cannot read, one that runs past the end of its allocation
+ * or one that overlaps the volume is PPF_ERR_INVALID before anything is launched. */
+ppf_status ppf_depth_volume_integrate_device(ppf_depth_volume* v, const void* d_depth, int rows, int cols, size_t row_pitch_bytes,
+                                             const double* intr, const ppf_depth_params* dp, const double* pose16, void* stream,
+                                             ppf_depth_volume_integrate_stats* stats /* may be NULL */);
+/* Raycast into HOST memory: depth_out packed rows x cols floats, normals_out packed rows x cols x 3 floats or NULL.  Checked in
+ * this order, all PPF_ERR_INVALID before any device work: v; depth_out; pose16; rp; intr NULL; rows, cols; the intrinsics;
+ * pose16 finite; z_near and z_far; ray_step; min_weight; flags; K; more than PPF_VOLUME_MAX_TILES tiles (a launch holds fewer
+ * than 2^32 lanes).  Then PPF_ERR_HIP without a device.  One launch and one
+ * blocking wait whatever the volume holds.  On any error the outputs are not touched and *stats is zero. */
+ppf_status ppf_depth_volume_raycast(ppf_depth_volume* v, int rows, int cols, const double* intr, const double* pose16,
+                                    const ppf_depth_volume_raycast_params* rp, float* depth_out, float* normals_out /* may be NULL */,
+                                    ppf_depth_volume_raycast_stats* stats /* may be NULL */);
+/* the same into DEVICE buffers, on `stream`.  After the checks above: an output the current device cannot write or that runs
+ * past the end of its allocation (the depth output, then the normals), an output that overlaps the volume, or the normals
+ * overlapping the depth output, is PPF_ERR_INVALID before anything is launched. */
+ppf_status ppf_depth_volume_raycast_device(ppf_depth_volume* v, int rows, int cols, const double* intr, const double* pose16,
+                                           const ppf_depth_volume_raycast_params* rp, float* d_depth, float* d_normals /* may be NULL */,
+                                           void* stream, ppf_depth_volume_raycast_stats* stats /* may be NULL */);
+/* The zero surface as a ppf_cloud, as ppf_cloud_from_depth_normals returns one (release it with ppf_cloud_release): what
+ * the cloud stages take, and downloaded what ppf_model_train takes.  Checked in this order: out; v; ep NULL; min_weight; flags (PPF_ERR_INVALID),
+ * then PPF_ERR_HIP without a device.  Seven launches and two blocking waits whatever the volume holds.  On any error *out is
+ * NULL and *stats is zero. */
+ppf_status ppf_depth_volume_extract(ppf_depth_volume* v, const ppf_depth_volume_extract_params* ep, ppf_cloud** out,
+                                    ppf_depth_volume_extract_stats* stats /* may be NULL */);
+
 /* ---- a depth image's surfaces labelled in image space: proposals without leaving the image ----------- */
 #define PPF_SEGMENT_EIGHT 1      /* flags: 8-connectivity instead of 4 */
 #define PPF_SEGMENT_UNORIENTED 2 /* flags: normals agree on |dot|, as PPF_REGION_UNORIENTED */

@@ -193,6 +193,43 @@ PPF_MOTION_MAX_LEVELS, PPF_MOTION_MAX_ITERS = 4, 64
  PPF_MOTION_SKIPPED) = range(6)  # DepthMotionLevel.status
 
 
+class DepthVolumeParams(C.Structure):
+    _fields_ = [("dims", C.c_int32 * 3), ("voxel", C.c_float), ("origin", C.c_double * 3), ("trunc", C.c_float),
+                ("max_weight", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class DepthVolumeDesc(C.Structure):
+    _fields_ = [("dims", C.c_int32 * 3), ("voxel", C.c_float), ("origin", C.c_double * 3), ("trunc", C.c_float),
+                ("max_weight", C.c_int32), ("integrations", C.c_int64), ("device_bytes", C.c_uint64), ("reserved", C.c_int32 * 4)]
+
+
+class DepthVolumeIntegrateStats(C.Structure):
+    _fields_ = [("n_updated", C.c_int64), ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32), ("ms_wall", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
+class DepthVolumeRaycastParams(C.Structure):
+    _fields_ = [("z_near", C.c_float), ("z_far", C.c_float), ("ray_step", C.c_float), ("min_weight", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class DepthVolumeRaycastStats(C.Structure):
+    _fields_ = [("n_hits", C.c_int32), ("n_interpolated", C.c_int32), ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32),
+                ("ms_wall", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+class DepthVolumeExtractParams(C.Structure):
+    _fields_ = [("min_weight", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class DepthVolumeExtractStats(C.Structure):
+    _fields_ = [("n_crossings", C.c_int64), ("n_rows", C.c_int64), ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32),
+                ("ms_wall", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+PPF_VOLUME_MAX_DIM, PPF_VOLUME_MAX_WEIGHT, PPF_VOLUME_MAX_STEPS, PPF_VOLUME_MAX_TILES = 1024, 65535, 4096, 16777215
+
+
 class SegmentParams(C.Structure):
     _fields_ = [("depth_abs", C.c_float), ("depth_quad", C.c_float), ("normal_cos", C.c_float), ("curvature_threshold", C.c_float),
                 ("min_size", C.c_int32), ("max_size", C.c_int32), ("max_segments", C.c_int32), ("flags", C.c_int32),
@@ -496,6 +533,27 @@ _SIGNATURES = {
     "ppf_depth_motion_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_double),
                                           C.POINTER(DepthParams), C.POINTER(DepthMotionParams), C.POINTER(C.c_double), C.c_void_p,
                                           C.POINTER(C.c_double), C.POINTER(DepthMotionLevel), C.POINTER(DepthMotionStats)]),
+    "ppf_default_depth_volume_params": (None, [C.POINTER(DepthVolumeParams)]),
+    "ppf_default_depth_volume_raycast_params": (None, [C.POINTER(DepthVolumeRaycastParams)]),
+    "ppf_default_depth_volume_extract_params": (None, [C.POINTER(DepthVolumeExtractParams)]),
+    "ppf_depth_volume_create": (C.c_int, [C.POINTER(DepthVolumeParams), C.POINTER(C.c_void_p)]),
+    "ppf_debug_depth_volume_shell": (C.c_int, [C.POINTER(DepthVolumeParams), C.POINTER(C.c_void_p)]),
+    "ppf_depth_volume_release": (C.c_int, [C.c_void_p]),
+    "ppf_depth_volume_reset": (C.c_int, [C.c_void_p]),
+    "ppf_depth_volume_info": (C.c_int, [C.c_void_p, C.POINTER(DepthVolumeDesc)]),
+    "ppf_depth_volume_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ppf_depth_volume_integrate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_double),
+                                             C.POINTER(DepthParams), C.POINTER(C.c_double), C.POINTER(DepthVolumeIntegrateStats)]),
+    "ppf_depth_volume_integrate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_double),
+                                                    C.POINTER(DepthParams), C.POINTER(C.c_double), C.c_void_p,
+                                                    C.POINTER(DepthVolumeIntegrateStats)]),
+    "ppf_depth_volume_raycast": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                           C.POINTER(DepthVolumeRaycastParams), C.c_void_p, C.c_void_p, C.POINTER(DepthVolumeRaycastStats)]),
+    "ppf_depth_volume_raycast_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                  C.POINTER(DepthVolumeRaycastParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(DepthVolumeRaycastStats)]),
+    "ppf_depth_volume_extract": (C.c_int, [C.c_void_p, C.POINTER(DepthVolumeExtractParams), C.POINTER(C.c_void_p),
+                                           C.POINTER(DepthVolumeExtractStats)]),
     "ppf_default_segment_params": (None, [C.POINTER(SegmentParams)]),
     "ppf_depth_segments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(DepthParams), C.c_void_p,
                                      C.POINTER(SegmentParams), C.c_void_p, C.POINTER(SegmentInfo), C.POINTER(C.c_int32),

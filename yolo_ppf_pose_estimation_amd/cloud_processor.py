@@ -893,6 +893,183 @@ class DepthOdometry:
         return T, status
 
 
+# ppf_depth_volume_voxel as a numpy record
+VOLUME_VOXEL = np.dtype([("d", "<f4"), ("w", "<i4")])
+
+
+def _pose16(pose):
+    m = np.ascontiguousarray(pose, dtype=np.float64)
+    if m.size != 16:
+        raise PPFError(_capi.PPF_ERR_INVALID, "pose must be a 4 x 4 matrix")
+    return (C.c_double * 16)(*m.reshape(-1).tolist())
+
+
+class DepthVolume:
+    """A truncated signed distance volume on the device that posed depth images are fused into (ppf_depth_volume, DESIGN.md
+    §30): ``integrate`` adds a frame seen from a pose, ``raycast`` gives the model depth image from any pose -- a float32
+    image every depth stage takes, the denoised and hole-filled frame of a moving camera, and with ``depth_motion`` the
+    drift-free frame-to-model tracking of ``DepthFusion`` -- and ``extract`` the zero surface as a ``DeviceCloud`` with normals,
+    which ``PPF3DDetector.trainModel`` takes.  dims: (nx, ny, nz); voxel: metres; origin: world coordinates of the centre of
+    voxel (0, 0, 0); trunc: metres, None: 4 voxels; a pose is a 4 x 4 world -> camera matrix, as ``DepthOdometry.pose`` is."""
+
+    def __init__(self, dims, voxel: float, origin, trunc: Optional[float] = None, max_weight: int = 64):
+        self._ptr = None
+        prm = _capi.DepthVolumeParams()
+        lib().ppf_default_depth_volume_params(C.byref(prm))
+        dims, origin = [int(v) for v in dims], [float(v) for v in origin]
+        if len(dims) != 3 or len(origin) != 3:
+            raise PPFError(_capi.PPF_ERR_INVALID, "a depth volume takes dims (nx, ny, nz) and an origin (x, y, z)")
+        prm.dims[:], prm.origin[:] = dims, origin
+        prm.voxel = float(voxel)
+        prm.trunc = float(np.float32(4) * np.float32(voxel)) if trunc is None else float(trunc)
+        prm.max_weight = int(max_weight)
+        self.params = prm
+        ptr = C.c_void_p()
+        check(lib().ppf_depth_volume_create(C.byref(prm), C.byref(ptr)))
+        self._ptr = ptr
+        self.dims = tuple(dims)
+
+    def __del__(self):
+        try:
+            if self._ptr is not None:
+                lib().ppf_depth_volume_release(self._ptr)
+                self._ptr = None
+        except Exception:
+            pass
+
+    def reset(self) -> None:
+        """every voxel unobserved again"""
+        check(lib().ppf_depth_volume_reset(self._ptr))
+
+    def info(self) -> dict:
+        """dims, voxel, origin, trunc, max_weight, integrations (since the last reset) and device_bytes"""
+        d = _capi.DepthVolumeDesc()
+        check(lib().ppf_depth_volume_info(self._ptr, C.byref(d)))
+        out = {k: v for k, v in _capi.stats_dict(d).items() if not k.startswith("reserved")}
+        out["dims"], out["origin"] = tuple(d.dims), tuple(d.origin)
+        return out
+
+    def read(self):
+        """(d float32, w int32), each of shape (nz, ny, nx): a blocking copy of every voxel"""
+        nx, ny, nz = self.dims
+        rec = np.empty(nx * ny * nz, VOLUME_VOXEL)
+        check(lib().ppf_depth_volume_read(self._ptr, rec.ctypes.data, rec.size))
+        return rec["d"].reshape(nz, ny, nx).copy(), rec["w"].reshape(nz, ny, nx).copy()
+
+    def integrate(self, depth, intr, pose, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0,
+                  return_stats: bool = False):
+        """Fuse one frame seen from ``pose``.  depth: a 2-D numpy float32 (metres) or uint16 (units of depth_scale metres)
+        array, rows read at its stride; or such a torch tensor on the GPU, read in place on ``torch.cuda.current_stream()``
+        (ppf_depth_volume_integrate_device).  intr: (fx, fy, ppx, ppy) or the 3x3 camera matrix.  Returns the number of
+        voxels updated, or the call's counters with return_stats."""
+        inp = _DepthInput(depth, "depth must be a 2-D float32 or uint16 {kind}")
+        dp = _depth_params(depth_scale, z_min, z_max)
+        dp.format = inp.format
+        it, T, st = (C.c_double * 4)(*_intr4(intr)), _pose16(pose), _capi.DepthVolumeIntegrateStats()
+        with inp.device():
+            if inp.is_device:
+                check(lib().ppf_depth_volume_integrate_device(self._ptr, inp.ptr, inp.rows, inp.cols, inp.pitch, it, C.byref(dp), T,
+                                                              inp.stream(), C.byref(st)))
+            else:
+                check(lib().ppf_depth_volume_integrate(self._ptr, inp.ptr, inp.rows, inp.cols, inp.pitch, it, C.byref(dp), T, C.byref(st)))
+        return _capi.stats_dict(st) if return_stats else int(st.n_updated)
+
+    def raycast(self, shape, intr, pose, params=None, out=None, return_normals: bool = False, return_stats: bool = False):
+        """The volume's depth image (float32 metres, 0 where no surface is hit) of ``shape`` = (rows, cols) seen through
+        ``intr`` from ``pose``; neither needs to be an input's.  params: a DepthVolumeRaycastParams, a dict of its fields
+        (z_near, z_far, ray_step, min_weight) or None.  out: None (a new numpy image), a contiguous float32 numpy array of
+        that shape, or such a torch tensor on the GPU, which is written in place on ``torch.cuda.current_stream()``
+        (ppf_depth_volume_raycast_device) and makes the normals a tensor too.  return_normals adds the (rows, cols, 3) normals
+        in camera coordinates (zeros where there is none), return_stats the counters: (image[, normals][, stats])."""
+        prm = _params(_capi.DepthVolumeRaycastParams, "ppf_default_depth_volume_raycast_params", params, "depth volume raycast")
+        shape = (int(shape[0]), int(shape[1]))
+        it, T, st = (C.c_double * 4)(*_intr4(intr)), _pose16(pose), _capi.DepthVolumeRaycastStats()
+        on_device = type(out).__module__.startswith("torch") and out.is_cuda
+        if on_device:
+            torch, _ = _torch_formats()
+            if not (out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()):
+                raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous float32 tensor of shape {shape}")
+            nrm = torch.empty(shape + (3,), dtype=torch.float32, device=out.device) if return_normals else None
+            stream = torch.cuda.current_stream(out.device).cuda_stream
+            with torch.cuda.device(out.device):
+                check(lib().ppf_depth_volume_raycast_device(self._ptr, shape[0], shape[1], it, T, C.byref(prm), C.c_void_p(out.data_ptr()),
+                                                            C.c_void_p(nrm.data_ptr()) if return_normals else None,
+                                                            C.c_void_p(stream) if stream else None, C.byref(st)))
+        else:
+            if out is None:
+                out = np.empty(shape, np.float32)
+            elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == shape and out.flags.c_contiguous
+                      and out.flags.writeable):
+                raise PPFError(_capi.PPF_ERR_INVALID, f"out must be a contiguous float32 array of shape {shape}")
+            nrm = np.empty(shape + (3,), np.float32) if return_normals else None
+            check(lib().ppf_depth_volume_raycast(self._ptr, shape[0], shape[1], it, T, C.byref(prm), out.ctypes.data,
+                                                 nrm.ctypes.data if return_normals else None, C.byref(st)))
+        res = (out,) + ((nrm,) if return_normals else ()) + ((_capi.stats_dict(st),) if return_stats else ())
+        return res if len(res) > 1 else out
+
+    def extract(self, params=None, return_stats: bool = False):
+        """The zero surface as a ``DeviceCloud``: rows x y z nx ny nz in world coordinates, one per sign change between two
+        observed neighbours that has a normal.  params: a DepthVolumeExtractParams, a dict (min_weight) or None."""
+        prm = _params(_capi.DepthVolumeExtractParams, "ppf_default_depth_volume_extract_params", params, "depth volume extract")
+        out, st = C.c_void_p(), _capi.DepthVolumeExtractStats()
+        check(lib().ppf_depth_volume_extract(self._ptr, C.byref(prm), C.byref(out), C.byref(st)))
+        cloud = DeviceCloud(out)
+        return (cloud, _capi.stats_dict(st)) if return_stats else cloud
+
+
+class DepthFusion:
+    """Frame-to-model camera tracking and fusion: every pushed frame is aligned to the image ``volume`` gives from the current
+    ``pose`` (``depth_motion(prev = raycast, cur = frame)``), which does not accumulate drift as ``DepthOdometry``'s chain does,
+    and is then integrated at the new pose.  rows, cols, intr: fixed for the stream; volume: a ``DepthVolume``, whose world is
+    the first frame's camera; motion_params, raycast_params: as ``depth_motion`` and ``DepthVolume.raycast`` take them;
+    depth_scale, z_min, z_max: the frames'.  A uint16 frame is tracked as float32 metres, z = (float)((double)d * depth_scale)."""
+
+    def __init__(self, rows: int, cols: int, intr, volume: DepthVolume, *, motion_params=None, raycast_params=None,
+                 depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0):
+        self.shape = (int(rows), int(cols))
+        self.intr = _intr4(intr)
+        self.volume = volume
+        self.motion_params, self.raycast_params = motion_params, raycast_params
+        self._kw = dict(depth_scale=depth_scale, z_min=z_min, z_max=z_max)
+        self.pose = np.eye(4)
+        self.frames = 0
+        self.model_depth = None
+        self.last_info = None
+        self.last_stats: Dict[str, object] = {}
+
+    def _metres(self, depth):
+        is_torch = type(depth).__module__.startswith("torch")
+        if is_torch:
+            torch, _ = _torch_formats()
+            return depth if depth.dtype == torch.float32 else (depth.to(torch.float64) * self._kw["depth_scale"]).to(torch.float32)
+        depth = np.asarray(depth)
+        return depth if depth.dtype == np.float32 else (depth.astype(np.float64) * np.float64(self._kw["depth_scale"])).astype(np.float32)
+
+    def push(self, depth):
+        """(T, status): the motion from the model's image to this frame and PPF_MOTION_* of the call; the first push
+        integrates at the identity and gives the identity and PPF_MOTION_NONE.  On LOST or STEP ``pose`` and the volume stay
+        as they were and T is the identity."""
+        if tuple(depth.shape) != self.shape:
+            raise PPFError(_capi.PPF_ERR_INVALID, f"depth must have the shape {self.shape}")
+        if self.frames == 0:
+            self.volume.integrate(depth, self.intr, self.pose, **self._kw)
+            self.frames = 1
+            return np.eye(4), _capi.PPF_MOTION_NONE
+        cur = self._metres(depth)
+        on_device = type(cur).__module__.startswith("torch") and cur.is_cuda
+        out = _torch_formats()[0].empty(self.shape, dtype=cur.dtype, device=cur.device) if on_device else None
+        self.model_depth = self.volume.raycast(self.shape, self.intr, self.pose, params=self.raycast_params, out=out)
+        T, self.last_info, self.last_stats = depth_motion(self.model_depth, cur, self.intr, z_min=self._kw["z_min"], z_max=self._kw["z_max"],
+                                                          params=self.motion_params, return_info=True, return_stats=True)
+        status = int(self.last_stats["status"])
+        self.frames += 1
+        if status in (_capi.PPF_MOTION_LOST, _capi.PPF_MOTION_STEP):
+            return np.eye(4), status
+        self.pose = _mat44_mul(T, self.pose)
+        self.volume.integrate(depth, self.intr, self.pose, **self._kw)
+        return T, status
+
+
 # ppf_segment_info as a numpy record
 SEGMENT_INFO =np.dtype([("n_pixels", "<i4"), ("n_border", "<i4"), ("first_pixel", "<i4"), ("box_xywh", "<i4", 4), ("z_lo", "<f4"),
                          ("z_hi", "<f4"), ("reserved", "<i4", 3)])
@@ -1077,6 +1254,9 @@ class CloudProcessor:
         self.camera_motion: Optional[np.ndarray] = None
         self.motion_info = None
         self.motion_stats: Dict[str, object] = {}
+        # FuseVolume: the DepthFusion the processor owns and its fused world -> camera pose
+        self._depth_fusion: Optional[DepthFusion] = None
+        self.camera_pose: Optional[np.ndarray] = None
         # ProposeSegments: the info rows of the image's segments, its label image and the counters
         self.segment_info: Optional[np.ndarray] = None
         self.segment_labels: Optional[np.ndarray] = None
@@ -1400,6 +1580,44 @@ class CloudProcessor:
                 for p in plist:
                     _pose_premultiply(p, T)
         self.camera_motion = T
+        return T, status
+
+    def FuseVolume(self, depth, CameraIntr=None, volume: Optional[DepthVolume] = None, **fusion):
+        """The next frame of a moving camera tracked against, and fused into, a volume the processor owns (``DepthFusion.push``,
+        DESIGN.md §30), and the motion applied to every pose of ``frame_poses`` exactly as ``TrackCamera`` does: pose <- T pose.
+        CameraIntr: default PrepareFrame's.  The first call makes the ``DepthFusion`` -- on ``volume``, default a
+        ``DepthVolume`` of the C defaults, with ``fusion`` (motion_params, raycast_params, depth_scale, z_min, z_max) -- and
+        integrates the frame.  Later calls take neither: ``fusion`` keywords are refused once the ``DepthFusion`` exists, and a
+        frame of another shape is refused too (the volume holds the first camera's world).  Giving another ``volume`` starts
+        afresh on it, with the ``fusion`` keywords given beside it.  Sets
+        ``camera_motion`` (T), ``camera_pose`` (the fused world -> camera pose), ``motion_info``, ``motion_stats`` and
+        ``timings["fuse_volume"]``; returns (T, status).  On LOST or STEP the poses and the volume stay as they are.
+        ``self.depth`` is left alone: RefineFrame(depth) replaces it."""
+        intr = self.frame_intr if CameraIntr is None else CameraIntr
+        if depth is None or not hasattr(depth, "shape") or len(depth.shape) != 2 or intr is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "FuseVolume needs a 2-D depth image and the camera intrinsics")
+        t0 = time.perf_counter()
+        f = self._depth_fusion
+        afresh = f is None or (volume is not None and volume is not f.volume)
+        if not afresh and fusion:
+            raise PPFError(_capi.PPF_ERR_INVALID, f"FuseVolume: {', '.join(sorted(fusion))} can only be given with the first frame or a new volume")
+        if not afresh and f.shape != tuple(depth.shape):
+            raise PPFError(_capi.PPF_ERR_INVALID, f"FuseVolume: the frame is {tuple(depth.shape)}, the volume was started with {f.shape} frames; "
+                                                  "give a new volume to start afresh")
+        if afresh:
+            if volume is None:
+                prm = _capi.DepthVolumeParams()
+                lib().ppf_default_depth_volume_params(C.byref(prm))
+                volume = DepthVolume(tuple(prm.dims), prm.voxel, tuple(prm.origin), prm.trunc, prm.max_weight)
+            f = self._depth_fusion = DepthFusion(depth.shape[0], depth.shape[1], intr, volume, **fusion)
+        T, status = f.push(depth)
+        self.motion_info, self.motion_stats = f.last_info, f.last_stats
+        self.timings["fuse_volume"] = time.perf_counter() - t0
+        if status not in (_capi.PPF_MOTION_NONE, _capi.PPF_MOTION_LOST, _capi.PPF_MOTION_STEP):
+            for plist in self.frame_poses:
+                for p in plist:
+                    _pose_premultiply(p, T)
+        self.camera_motion, self.camera_pose = T, f.pose.copy()
         return T, status
 
     def _match_frame(self, labels, step, dist, top: int = 5) -> List[Optional[Pose3D]]:
