@@ -373,6 +373,30 @@ ppf_status ppf_debug_accumulators_ws(const ppf_model* m, ppf_workspace* ws, cons
 /* Size of the cached device block a request of `bytes` is served from (host only, no device needed): classes of 1/8
  * octave, so at most 12.5 % more than asked for.  Test surface of the block cache's keying. */
 size_t ppf_debug_block_size(size_t bytes);
+/* How a match call is cut into batches of reference points and how big its hit pools and LDS areas are (host only, no
+ * device needed): the engine's own sizing function, which a call runs once, after the cold count if there is one.  A
+ * pure function of these numbers, so its corners (the worst-case single stripe, the 32,768-row grid limit, the 64-hit
+ * floor, capacities near 2^32) are reached without a scene of that size.  Test surface. */
+typedef struct ppf_debug_match_plan_in {
+  int32_t n_ref, n_paired;   /* reference points voted by the call, rows of the paired cloud: both >= 1 */
+  double hit_frac, run_frac, tbl_frac; /* expected hits per scene pair, runs per hit, count tables per hit */
+  int32_t count_tables;      /* != 0: many-hit runs vote through count tables (vote_mode, alpha range and num_angles allow it) */
+  int32_t batch_refs_cap, round_buckets_cap, run_seg_cap; /* PPF_OPT_BATCH_REFS, _GROUP_ROUND_BUCKETS, _RUN_STAGING; 0 = none */
+  uint32_t n_buckets;        /* ppf_model_info::n_buckets, ::tile_refs, ::num_angles of the model */
+  int32_t tile_refs, num_angles;
+} ppf_debug_match_plan_in;
+typedef struct ppf_debug_match_plan_out {
+  int32_t pair_chunks;       /* pair-kernel workgroups per reference point */
+  int32_t n_rounds, round_buckets; /* grouping rounds, buckets counted per round */
+  int32_t batch, n_batches;  /* reference points per batch, batches of the call */
+  int32_t stripe_bits;       /* log2 of the raw hit pool's stripes */
+  uint32_t stripe_cap, sorted_cap, run_cap, table_cap; /* capacity of a stripe, of the sorted pool, the run table, the count-table pool */
+  int32_t run_seg;           /* the vote kernel's staging area, in runs of 24 bytes */
+  uint64_t vote_lds, group_lds; /* dynamic LDS of the vote and the grouping kernel, bytes */
+} ppf_debug_match_plan_out;
+/* PPF_ERR_INVALID for a NULL or out-of-range argument, and -- as the match call itself -- for a model tile that leaves
+ * the vote kernel's least staging no LDS and for more paired points than one call can group; `out` is then all zero. */
+ppf_status ppf_debug_match_plan(const ppf_debug_match_plan_in* in, ppf_debug_match_plan_out* out);
 /* Guard mode of the device block cache: finds stores outside a scratch or result buffer and reads of scratch that was
  * never written, which the cache otherwise hides (a request is rounded up to a size class, so a store a few bytes too far
  * lands in slack nobody reads, and a reused block still holds the previous call's bytes).  mode 0: off (the default);

@@ -320,3 +320,28 @@ def test_skip_clustering_shards_add_up(det, crop, oracle_crop):
     for g, w in zip(got, full["poses"]):
         assert int(g["num_votes"]) == w.numVotes
         np.testing.assert_array_equal(g["pose"].reshape(4, 4), w.pose)
+
+
+def test_batch_repeats_a_match_whose_pools_were_too_small(det, bottle):
+    """The overflow retry inside ppf_batch_run.  One lane, one model, two crops: the first is 2,000 points scattered over a box
+    a hundred model diameters wide, where next to no pair is a hit, so the lane's cold count learns the least hit fraction; the
+    second, an ordinary scene of 2,000 points, then runs with pools far too small, raises the overflow word and is repeated
+    with grown pools after the lane has drained.  Both crops must come out as a match of that crop alone does."""
+    from yolo_ppf_pose_estimation_amd.device import BatchMatcher
+    rng = np.random.default_rng(5)
+    sparse = np.zeros((2000, 6), dtype=np.float32)
+    sparse[:, :3] = rng.uniform(-15.0, 15.0, size=(2000, 3))
+    nn = rng.normal(size=(2000, 3))
+    sparse[:, 3:] = nn / np.linalg.norm(nn, axis=1, keepdims=True)
+    scene = synth.make_scene(bottle, n_points=2000, seed=21)[0]
+    crops = [sparse, scene]
+    top_k = 5
+    res = BatchMatcher(lanes=1).run([det], crops, STEP, 0.05, presampled=True, top_k=top_k)
+    assert res["n_matches"] == 2 and res["n_retries"] >= 1
+    for c, cloud in enumerate(crops):
+        want = det.match(cloud, STEP, 0.05, presampled=True)[:top_k]
+        got = res["poses"][c][0]
+        assert [p.numVotes for p in got] == [p.numVotes for p in want], c
+        for g, w in zip(got, want):
+            np.testing.assert_allclose(g.pose, w.pose, rtol=0, atol=1e-9)
+    assert len(res["poses"][1][0]) >= 1 and res["poses"][1][0][0].numVotes > 0

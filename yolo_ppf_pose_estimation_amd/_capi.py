@@ -81,6 +81,22 @@ class PoolReport(C.Structure):
                 ("first", PoolViolation * 8)]
 
 
+class MatchPlanIn(C.Structure):
+    """ppf_debug_match_plan_in: what the sizing of a match call depends on"""
+    _fields_ = [("n_ref", C.c_int32), ("n_paired", C.c_int32), ("hit_frac", C.c_double), ("run_frac", C.c_double),
+                ("tbl_frac", C.c_double), ("count_tables", C.c_int32), ("batch_refs_cap", C.c_int32),
+                ("round_buckets_cap", C.c_int32), ("run_seg_cap", C.c_int32), ("n_buckets", C.c_uint32),
+                ("tile_refs", C.c_int32), ("num_angles", C.c_int32)]
+
+
+class MatchPlanOut(C.Structure):
+    """ppf_debug_match_plan_out: batches, pool capacities, LDS sizes"""
+    _fields_ = [("pair_chunks", C.c_int32), ("n_rounds", C.c_int32), ("round_buckets", C.c_int32), ("batch", C.c_int32),
+                ("n_batches", C.c_int32), ("stripe_bits", C.c_int32), ("stripe_cap", C.c_uint32), ("sorted_cap", C.c_uint32),
+                ("run_cap", C.c_uint32), ("table_cap", C.c_uint32), ("run_seg", C.c_int32), ("vote_lds", C.c_uint64),
+                ("group_lds", C.c_uint64)]
+
+
 def stats_dict(st):
     """A stats structure as a plain dict (array fields as lists)."""
     out = {}
@@ -461,6 +477,7 @@ _SIGNATURES = {
     "ppf_debug_accumulators_ws": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                             C.c_int, C.POINTER(MatchParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     "ppf_debug_block_size": (C.c_size_t, [C.c_size_t]),
+    "ppf_debug_match_plan": (C.c_int, [C.POINTER(MatchPlanIn), C.POINTER(MatchPlanOut)]),
     "ppf_debug_device_math": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "ppf_debug_pool_guard": (C.c_int, [C.c_int]),
     "ppf_debug_pool_check": (C.c_int, [C.POINTER(PoolReport)]),

@@ -184,15 +184,9 @@ ppf_status ppf_batch_run(ppf_batch* b, const ppf_model* const* models, int n_mod
         /* bigger pools than this (crop, model) match had (the flag says which one was short): match_prepared looks the
          * model's fractions up itself */
         workspace_hold_model(ws, nullptr);
-        ppf_workspace::Learned* fm = workspace_learned(ws, models[k], true);
-        const uint32_t flags = meta[idx * 2 + 1];
-        at_full = fm->hit >= 1.0;
-        if (flags & 3u) fm->hit = std::min(1.0, 2.0 * fm->hit);
-        if (flags & 4u) fm->run = std::min(1.0, 2.0 * fm->run);
-        if (flags & 8u) {
-          if ((flags & 3u) == 0 && fm->tbl >= TBL_FRAC_MAX) fm->hit = std::min(1.0, 2.0 * fm->hit);
-          fm->tbl = std::min(TBL_FRAC_MAX, 2.0 * fm->tbl);
-        }
+        PoolFractions& frac = workspace_learned(ws, models[k], true)->frac;
+        at_full = frac.hit >= 1.0;
+        frac.grow(meta[idx * 2 + 1]);
         s = enqueue_pair(lane, c, k);
         if (s != PPF_OK) return s;
         HIPCHK(hipStreamSynchronize(b->streams[lane]));
@@ -218,24 +212,16 @@ ppf_status ppf_batch_run(ppf_batch* b, const ppf_model* const* models, int n_mod
     for (int k = 0; k < n_models; k++) {
       const double fh = lane_hit[(size_t)l * n_models + k], fr = lane_run[(size_t)l * n_models + k], ft = lane_tbl[(size_t)l * n_models + k];
       if (!(fh > 0)) continue;
-      const double hit = std::min(1.0, std::max(1e-3, 1.06 * fh)), run = std::min(1.0, std::max(0.02, 1.10 * fr));
-      ppf_workspace::Learned* fm = workspace_learned(ws, models[k], true);
-      fm->hit = hit; fm->run = run; fm->tbl = std::min(TBL_FRAC_MAX, std::max(1e-4, 1.15 * ft));
+      PoolFractions& frac = workspace_learned(ws, models[k], true)->frac;
+      frac.learn_hit(fh, 1.0); frac.learn_run(fr, 1.0); frac.learn_tbl(ft, 1.0);
     }
   }
   if (out) HIPCHK(hipMemcpy(out, b->d_out.p, n_match * cap * sizeof(ppf_pose), hipMemcpyDeviceToHost));
   if (n_out)
     for (size_t idx = 0; idx < n_match; idx++) n_out[idx] = (int)std::min<uint32_t>(meta[idx * 2], (uint32_t)cap);
   for (const TimedCall& tc : timed) { /* kernel times of every match (retries after an overflow included) */
-    ppf_workspace* ws = b->ws[tc.lane];
-    for (int bi = 0; bi < tc.n_batches; bi++) {
-      const size_t e0 = tc.ev_base + (size_t)bi * 4;
-      float t0 = 0, t1 = 0, t2 = 0;
-      HIPCHK(hipEventElapsedTime(&t0, ws->batch_ev[e0 + 0], ws->batch_ev[e0 + 1]));
-      HIPCHK(hipEventElapsedTime(&t1, ws->batch_ev[e0 + 1], ws->batch_ev[e0 + 2]));
-      HIPCHK(hipEventElapsedTime(&t2, ws->batch_ev[e0 + 2], ws->batch_ev[e0 + 3]));
-      st.ms_pair_kernel += t0; st.ms_group_kernel += t1; st.ms_vote_kernel += t2;
-    }
+    const ppf_status s = add_batch_ms(b->ws[tc.lane], tc.ev_base, tc.n_batches, &st.ms_pair_kernel, &st.ms_group_kernel, &st.ms_vote_kernel);
+    if (s != PPF_OK) return s;
   }
   for (auto* w : b->ws) w->ev_base = 0;
   st.n_matches = (int)n_match;

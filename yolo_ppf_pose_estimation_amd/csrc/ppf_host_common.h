@@ -209,6 +209,37 @@ struct ppf_model {
   ~ppf_model();
 };
 
+/* What a workspace expects of a call on one model, per scene pair and per hit: match_plan sizes the hit pools from it.
+ * Every number of the three rules below -- learning from a call's totals, the cold count, growing after an overflow --
+ * stands here and nowhere else. */
+struct PoolFractions {
+  double hit = 0.25;           /* hits per scene pair */
+  double run = 0.4;            /* runs (distinct buckets hit by a reference point) per hit */
+  double tbl = TBL_FRAC_START; /* count tables per hit, at most TBL_FRAC_MAX */
+  /* a measured ratio num / den with its margin, clamped (a batch passes the largest ratio of its crops over 1) */
+  void learn_hit(double num, double den) { hit = std::min(1.0, std::max(1e-3, 1.06 * num / den)); }
+  void learn_run(double num, double den) { run = std::min(1.0, std::max(0.02, 1.10 * num / den)); }
+  void learn_tbl(double num, double den) { tbl = std::min(TBL_FRAC_MAX, std::max(1e-4, 1.15 * num / den)); }
+  /* from a finished call's totals (votes, pairs, LDS operations, hits, runs, ., ., count tables) */
+  void learn(const unsigned long long* tot) {
+    if (tot[1]) learn_hit((double)tot[3], (double)tot[1]);
+    if (tot[3]) learn_run((double)tot[4], (double)tot[3]);
+    if (tot[3]) learn_tbl((double)tot[7], (double)tot[3]);
+  }
+  /* from the cold counting pass */
+  void learn_hits(unsigned long long hits, double pairs) { learn_hit((double)hits, std::max(1.0, pairs)); }
+  /* after a call whose pools overflowed (the word at CUR_OVERFLOW): double what was short.  Whether hit was already 1,
+   * the worst case no growth helps, is the caller's to ask before it grows. */
+  void grow(uint32_t overflow) {
+    if (overflow & 3u) hit = std::min(1.0, hit * 2.0); /* raw or sorted hit pool */
+    if (overflow & 4u) run = std::min(1.0, run * 2.0); /* run table */
+    if (overflow & 8u) {                               /* count-table pool */
+      if ((overflow & 3u) == 0 && tbl >= TBL_FRAC_MAX) hit = std::min(1.0, hit * 2.0); /* more hits than expected, then */
+      tbl = std::min(TBL_FRAC_MAX, tbl * 2.0);
+    }
+  }
+};
+
 struct ppf_workspace {
   CloudDev surf, edge;
   DevBuf<float> staging;
@@ -254,12 +285,10 @@ struct ppf_workspace {
   bool checked = false;                  /* the overflow flag of the pending call has been read */
   bool pools_failed = false;             /* a call ran out of hit pools at their worst-case size: the context is dropped, not kept warm */
   bool has_edge = false;
-  double hit_frac = 0.25;                /* expected hits per scene pair: sizes the hit pools, learned from every call */
+  PoolFractions frac;                    /* of the current model: sizes the hit pools, learned from every call */
   bool frac_known = false;               /* false: the next call first COUNTS its hits (one extra pair pass and one wait) */
-  double run_frac = 0.4;                 /* expected runs (distinct buckets hit by a reference point) per hit, learned likewise */
-  double tbl_frac = TBL_FRAC_START;      /* expected count tables per hit, learned likewise (at most TBL_FRAC_MAX) */
-  struct Learned { uint64_t model_serial; double hit, run, tbl; };
-  std::vector<Learned> frac_by_model;    /* the three fractions remembered per model, at most 16 (batches alternate models): workspace_learned() */
+  struct Learned { uint64_t model_serial; PoolFractions frac; };
+  std::vector<Learned> frac_by_model;    /* the fractions remembered per model, at most 16 (batches alternate models): workspace_learned() */
   int batch_refs_cap = 0;                /* 0 = what the scratch budget holds; tests lower it to force several batches per call */
   int run_seg_cap = 0;                   /* 0 = what the LDS holds (vote_run_seg, in runs of 24 bytes: vote_item_seg item records); tests lower it to force several staging segments per reference point */
   int round_buckets_cap = 0;             /* 0 = GROUP_MAX_BUCKETS; tests lower it to force several k_group rounds */

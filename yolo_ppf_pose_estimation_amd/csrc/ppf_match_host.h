@@ -24,7 +24,7 @@ ppf_status ppf_workspace_set_option(ppf_workspace* ws, int option, double value)
   switch (option) {
     case PPF_OPT_HIT_FRACTION:
       if (!(value > 0 && value <= 1)) return fail(PPF_ERR_INVALID, "ppf_workspace_set_option: hit fraction must be in (0, 1]");
-      ws->hit_frac = value;
+      ws->frac.hit = value;
       ws->frac_known = true;
       return PPF_OK;
     case PPF_OPT_GROUP_ROUND_BUCKETS:
@@ -51,7 +51,7 @@ ppf_status ppf_workspace_set_option(ppf_workspace* ws, int option, double value)
       return PPF_OK;
     case PPF_OPT_TABLE_FRACTION:
       if (!(value > 0 && value <= 1)) return fail(PPF_ERR_INVALID, "ppf_workspace_set_option: table fraction must be in (0, 1]");
-      ws->tbl_frac = std::min(TBL_FRAC_MAX, value);
+      ws->frac.tbl = std::min(TBL_FRAC_MAX, value);
       return PPF_OK;
     default:
       return fail(PPF_ERR_INVALID, "ppf_workspace_set_option: unknown option %d", option);
@@ -117,15 +117,14 @@ static ppf_workspace::Learned* workspace_learned(ppf_workspace* ws, const ppf_mo
     if (fm.model_serial == m->serial) return &fm;
   if (!create) return nullptr;
   if (ws->frac_by_model.size() >= 16) ws->frac_by_model.erase(ws->frac_by_model.begin());
-  ws->frac_by_model.push_back({m->serial, 0.25, 0.4, TBL_FRAC_START});
+  ws->frac_by_model.push_back({m->serial, PoolFractions()});
   return &ws->frac_by_model.back();
 }
 
-/* store the current model's learned hit fraction */
+/* store the current model's learned fractions */
 static void workspace_remember_frac(ppf_workspace* ws) {
   if (!ws->model || !ws->frac_known) return;
-  ppf_workspace::Learned* fm = workspace_learned(ws, ws->model, true);
-  fm->hit = ws->hit_frac; fm->run = ws->run_frac; fm->tbl = ws->tbl_frac;
+  workspace_learned(ws, ws->model, true)->frac = ws->frac;
 }
 
 /* the workspace keeps the model alive until its next call (or its destruction): results are fetched later.  A context
@@ -152,35 +151,129 @@ ppf_workspace::~ppf_workspace() {
 /* bytes of hit scratch one hit costs: raw {bucket, j} + sorted payload alpha_s + its share of the run table (+ 2 bytes for the
  * cell the payload no longer carries: kept, so that the batches of reference points stay the size they were tuned at) */
 constexpr double HIT_SCRATCH_BYTES = 8.0 + 8.0 + 2.0 + 16.0 / 6.0;
+/* match_plan lets a batch of more than one reference point expect at most HIT_BYTES_BUDGET / HIT_SCRATCH_BYTES hits (a batch
+ * of one has at most its paired points, an int), so every offset into the hit pools fits 32 bits */
+static_assert((double)HIT_BYTES_BUDGET / HIT_SCRATCH_BYTES < 2.0e9, "a batch's expected hits must leave 32-bit pool offsets room");
+
+/* two run-time switches as compile-time ones: calls f(std::bool_constant<a>, std::bool_constant<b>) */
+extern "C++" template <typename F>
+void bools_typed(bool a, bool b, F&& f) {
+  if (a && b) f(std::true_type{}, std::true_type{});
+  else if (a) f(std::true_type{}, std::false_type{});
+  else if (b) f(std::false_type{}, std::true_type{});
+  else f(std::false_type{}, std::false_type{});
+}
 
 /* k_pairs<pair feature, surface-to-boundary>: same_cloud == 0 is match_S2B (the paired points come from the edge cloud) */
 static void launch_pairs(const MatchArgs& va, bool darboux, hipStream_t st) {
   const dim3 grid(va.pair_chunks, va.n_ref), block(PAIR_BLOCK);
   const dim3 ogrid((unsigned)std::min(va.n_ref, 1024)), oblock(256); /* k_pairs_odd: adds up hit_count, then returns at once unless k_frames raised its flag */
-  if (darboux) {
-    if (va.same_cloud) k_pairs<true, false><<<grid, block, 0, st>>>(va);
-    else k_pairs<true, true><<<grid, block, 0, st>>>(va);
-    if (!va.count_only) { if (va.same_cloud) k_pairs_odd<true, false><<<ogrid, oblock, 0, st>>>(va); else k_pairs_odd<true, true><<<ogrid, oblock, 0, st>>>(va); }
-  } else {
-    if (va.same_cloud) k_pairs<false, false><<<grid, block, 0, st>>>(va);
-    else k_pairs<false, true><<<grid, block, 0, st>>>(va);
-    if (!va.count_only) { if (va.same_cloud) k_pairs_odd<false, false><<<ogrid, oblock, 0, st>>>(va); else k_pairs_odd<false, true><<<ogrid, oblock, 0, st>>>(va); }
-  }
+  bools_typed(darboux, !va.same_cloud, [&](auto D, auto S) {
+    constexpr bool DARBOUX = decltype(D)::value, S2B = decltype(S)::value;
+    k_pairs<DARBOUX, S2B><<<grid, block, 0, st>>>(va);
+    if (!va.count_only) k_pairs_odd<DARBOUX, S2B><<<ogrid, oblock, 0, st>>>(va);
+  });
 }
 
-/* everything after A2: frames -> pairs -> group -> rank -> vote -> finalize -> cluster, on the clouds held by ws.
- * Nothing here waits for the device: the hit pools are sized from ws->hit_frac (hits per scene pair, learned from the
- * previous calls); a pool that turns out too small raises a device flag, which the first accessor of the results reads
- * (workspace_finish) and answers by repeating the call with bigger pools. */
-static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const ppf_match_params* params, hipStream_t st, bool retry) {
-  ppf_status s = PPF_OK;
-  const bool d_edge = ws->has_edge;
+/* k_vote<alpha over 2 pi, 32-bit cells> */
+static void launch_vote(const MatchArgs& va, bool wrap, bool acc32, dim3 grid, size_t lds, hipStream_t st) {
+  bools_typed(wrap, acc32, [&](auto W, auto A) { k_vote<decltype(W)::value, decltype(A)::value><<<grid, dim3(VOTE_BLOCK), lds, st>>>(va); });
+}
+
+/* k_vote (every instantiation) and k_group may take the whole LDS: said once per process */
+static hipError_t match_kernel_attributes() {
+  static std::once_flag once;
+  static hipError_t attr_err = hipSuccess;
+  std::call_once(once, [] {
+    auto set = [](const void* f, int bytes) {
+      if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    };
+    for (bool acc32 : {false, true})
+      for (bool wrap : {false, true})
+        bools_typed(wrap, acc32, [&](auto W, auto A) { set(reinterpret_cast<const void*>(&k_vote<decltype(W)::value, decltype(A)::value>), LDS_BYTES); });
+    set(reinterpret_cast<const void*>(&k_group), LDS_BYTES - 1024);
+  });
+  return attr_err;
+}
+
+/* ---- the plan of a call: how many reference points per batch, how big each hit pool, how much LDS ---------------------- */
+/* inputs and outputs are the two plain records of include/ppf_hip.h, which ppf_debug_match_plan hands through as they are */
+typedef ppf_debug_match_plan_in MatchPlanIn;
+typedef ppf_debug_match_plan_out MatchPlan;
+
+/* k_pairs workgroups that cover the paired points of one reference point */
+static int pair_chunks_of(int n_paired) { return (n_paired + PAIR_BLOCK * PAIRS_PER_THREAD - 1) / (PAIR_BLOCK * PAIRS_PER_THREAD); }
+
+/* A pure function of a handful of numbers (no HIP call, no workspace): ppf_debug_match_plan exposes it to the tests. */
+static ppf_status match_plan(const MatchPlanIn& in, MatchPlan* plan) {
+  MatchPlan p{};
+  p.pair_chunks = pair_chunks_of(in.n_paired);
+  const uint32_t round_cap = in.round_buckets_cap > 0 ? (uint32_t)std::min(in.round_buckets_cap, GROUP_MAX_BUCKETS) : (uint32_t)GROUP_MAX_BUCKETS;
+  p.n_rounds = std::max(1, (int)((in.n_buckets + round_cap - 1) / round_cap));
+  p.round_buckets = (int)std::min<uint32_t>(std::max<uint32_t>(in.n_buckets, 1u), round_cap);
+  /* batch of reference points: its expected hits fit the scratch budget */
+  const double frac = std::min(1.0, std::max(in.hit_frac, 1e-3));
+  const double hits_per_ref = std::max(64.0, frac * (double)in.n_paired);
+  const double tbl_frac = !in.count_tables ? 0.0 : frac >= 1.0 ? TBL_FRAC_MAX : std::min(TBL_FRAC_MAX, in.tbl_frac);
+  int batch = (int)std::min<double>((double)in.n_ref, std::max(1.0, (double)HIT_BYTES_BUDGET / (hits_per_ref * (HIT_SCRATCH_BYTES + tbl_frac * TBL_BYTES))));
+  batch = std::min(batch, 32768); /* grid.y of k_pairs */
+  if (in.batch_refs_cap > 0) batch = std::min(batch, in.batch_refs_cap);
+  p.batch = batch;
+  p.n_batches = (in.n_ref + batch - 1) / batch;
+  const bool worst_case = frac >= 1.0;
+  const double est = hits_per_ref * (double)batch;
+  /* a stripe receives whole workgroups of up to PAIR_BLOCK*PAIRS_PER_THREAD hits; at worst-case size every workgroup of
+   * the batch could be full and land anywhere, otherwise 4 % + two workgroups of slack over an even share */
+  const uint32_t wg_hits = PAIR_BLOCK * PAIRS_PER_THREAD;
+  p.stripe_bits = 6; /* 64 stripes, fewer while a stripe would average over less than 512 workgroups */
+  while (p.stripe_bits > 0 && ((size_t)batch * p.pair_chunks >> p.stripe_bits) < 512) p.stripe_bits--;
+  if (worst_case) p.stripe_bits = 0; /* one stripe that holds every pair of the batch: nothing can overflow */
+  const uint32_t n_stripes = 1u << p.stripe_bits;
+  p.stripe_cap = worst_case ? (uint32_t)std::min<double>(4.0e9 / n_stripes, (double)batch * p.pair_chunks * wg_hits)
+                            : (uint32_t)(est / n_stripes * 1.04) + 2 * wg_hits;
+  p.sorted_cap = (uint32_t)std::min(4.0e9, est + 4096.0);
+  p.run_cap = worst_case ? p.sorted_cap : (uint32_t)std::min<double>((double)p.sorted_cap, std::max(est * std::min(1.0, in.run_frac), 64.0 * batch) + 1024.0);
+  /* count tables: a run of c >= agg_min_hits hits takes ceil(c / AGG_SUB), so TBL_FRAC_MAX per hit is the ceiling */
+  p.table_cap = !in.count_tables ? 1u : (uint32_t)std::min(1.0e9, std::max(est * (worst_case ? TBL_FRAC_MAX : tbl_frac), 4.0 * batch) + 256.0);
+  /* the item staging gets the LDS this model's accumulator tile leaves (its least size is what the tile was sized against) */
+  const size_t acc_words = (size_t)vote_lds_words(in.tile_refs, in.num_angles);
+  p.run_seg = vote_run_seg(acc_words, (size_t)LDS_BYTES);
+  if (in.run_seg_cap > 0) p.run_seg = std::max(64, std::min(p.run_seg, in.run_seg_cap / 64 * 64)); /* test knob: PPF_OPT_RUN_STAGING */
+  p.vote_lds = vote_lds_fixed(p.run_seg) + acc_words * 4;
+  if (p.vote_lds > (size_t)LDS_BYTES) return fail(PPF_ERR_INVALID, "match: model tile of %d reference points does not fit the LDS accumulator", in.tile_refs);
+  /* k_group's dynamic LDS: one counter per bucket of a round, the prefix of the pool pieces */
+  p.group_lds = (size_t)((p.round_buckets + 1) & ~1) * sizeof(uint32_t) + (size_t)((p.pair_chunks + 2) & ~1) * sizeof(uint32_t) * 2;
+  if (p.group_lds + 2048 > (size_t)LDS_BYTES) return fail(PPF_ERR_INVALID, "match: %d paired points are more than one call can group", in.n_paired);
+  *plan = p;
+  return PPF_OK;
+}
+
+ppf_status ppf_debug_match_plan(const ppf_debug_match_plan_in* in, ppf_debug_match_plan_out* out) {
+  if (!in || !out) return fail(PPF_ERR_INVALID, "ppf_debug_match_plan: NULL");
+  memset(out, 0, sizeof(*out));
+  if (in->n_ref < 1 || in->n_paired < 1 || in->tile_refs < 1 || in->num_angles < 1 || in->batch_refs_cap < 0 || in->round_buckets_cap < 0 ||
+      in->run_seg_cap < 0)
+    return fail(PPF_ERR_INVALID, "ppf_debug_match_plan: bad argument");
+  return match_plan(*in, out);
+}
+
+/* ---- the steps of match_prepared ------------------------------------------------------------------------------------ */
+
+/* 16-bit cells first, 32-bit cells for the (reference point, tile)s whose cells overflow -- until a call casts more than
+ * PPF_ACC32_SWITCH of its votes twice that way: from then on 32-bit cells for everything (what they cost extra is less than
+ * what the repeats cost: profiles/r04_c4_acc32_policies.md).  PPF_OPT_ACC32 = 3 instead sends the items that will cast at
+ * least ws->heavy_votes votes straight to the 32-bit launch, decided on the device, per item, for THIS scene, before a vote
+ * is cast (measured on C4: slower than either, the vote count of an item says little about its fullest cell). */
+static bool acc32_for_all(const ppf_workspace* ws) { return ws->force_acc32 || (ws->acc32 && ws->acc32_policy == 0); }
+
+/* the state of the call: model and its learned fractions, parameters, stream, the reference points it votes, zeroed stats */
+static ppf_status match_reset(const ppf_model* m, ppf_workspace* ws, const ppf_match_params* params, hipStream_t st, bool retry) {
   if (ws->model != m) { /* another model: its own hit density (remembered if it has been here before) */
     workspace_remember_frac(ws);
     ws->acc32 = false;
     ws->heavy_votes = ~0ull; /* another table: its own limit, learned from its first call on */
     if (const ppf_workspace::Learned* fm = workspace_learned(ws, m, false)) {
-      ws->hit_frac = fm->hit; ws->run_frac = fm->run; ws->tbl_frac = fm->tbl;
+      ws->frac = fm->frac;
       ws->frac_known = true;
     } else if (!ws->frac_by_model.empty()) {
       ws->frac_known = false; /* a model this workspace has not met: count first */
@@ -206,12 +299,17 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
   ws->n_ref = n_ref;
   ws->n_batches = 0;
   ws->stats.n_scene_sampled = rows;
-  ws->stats.n_paired = d_edge ? ws->edge.n : rows;
+  ws->stats.n_paired = ws->has_edge ? ws->edge.n : rows;
   ws->stats.n_ref = n_ref;
   ws->pending = true;
-  if (n_ref == 0) return PPF_OK;
+  return PPF_OK;
+}
 
-  const int T = m->info.n_tiles;
+/* what the call keeps per reference point (and tile): reserved, cleared where a kernel accumulates, and named in va */
+static ppf_status match_call_buffers(ppf_workspace* ws, MatchArgs& va) {
+  const ppf_model* m = ws->model;
+  const int n_ref = ws->n_ref, T = m->info.n_tiles;
+  hipStream_t st = ws->stream;
   HIPCHK(ws->partial.reserve((size_t)n_ref * T * 2));
   HIPCHK(ws->half_edge.reserve((size_t)n_ref * T * 2));
   HIPCHK(ws->ovf_items.reserve((size_t)n_ref * T));
@@ -231,19 +329,6 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
     HIPCHK(hipMemsetAsync(ws->need_hist.p, 0, 2 * ACC_HIST * sizeof(unsigned long long), st));
     HIPCHK(hipMemsetAsync(ws->item_votes.p, 0, (size_t)n_ref * T * sizeof(unsigned long long), st));
   }
-
-  MatchArgs va;
-  memset(&va, 0, sizeof(va));
-  va.surf = ws->surf.view();
-  va.paired = d_edge ? ws->edge.view() : ws->surf.view();
-  va.same_cloud = d_edge ? 0 : 1;
-  va.scene_step = scene_step; va.ref_offset = params->ref_offset; va.ref_stride = params->ref_stride;
-  va.slotmap = m->slotmap.p; va.slot_mask = m->info.slots - 1;
-  va.key_lut = m->key_lut.p; va.kd = m->kd;
-  va.bucket_off = m->bucket_off.p; va.n_buckets = (int)m->info.n_buckets;
-  va.records = m->records.p;
-  va.n_tiles = T; va.tile_refs = m->info.tile_refs; va.num_angles = m->info.num_angles; va.n_model = m->info.n_ref;
-  va.angle_step = m->info.angle_step; va.dist_step = m->info.distance_step;
   va.partial = ws->partial.p;
   va.edge = ws->half_edge.p;
   va.ovf_items = ws->ovf_items.p;
@@ -251,191 +336,163 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
   va.pairs = ws->counters.p + (size_t)n_ref * T;
   va.tally = ws->counters.p + (size_t)n_ref * T + n_ref + 2;
   va.acc_dump = ws->acc_dump;
+  va.item_votes = (!acc32_for_all(ws) && ws->acc32_policy == 3) ? ws->item_votes.p : nullptr;
+  va.heavy_votes = ws->heavy_votes;
+  va.n_counters = n_cnt;
+  va.n_ovf_items = (unsigned long long)n_ref * T;
+  return PPF_OK;
+}
+
+/* the clouds, the model's tables and the call's parameters; the cursors */
+static ppf_status match_args(ppf_workspace* ws, MatchArgs& va) {
+  const ppf_model* m = ws->model;
+  const ppf_match_params* params = &ws->params;
+  va.surf = ws->surf.view();
+  va.paired = ws->has_edge ? ws->edge.view() : ws->surf.view();
+  va.same_cloud = ws->has_edge ? 0 : 1;
+  va.scene_step = (int)(1.0 / params->relative_scene_sample_step); va.ref_offset = params->ref_offset; va.ref_stride = params->ref_stride;
+  va.slotmap = m->slotmap.p; va.slot_mask = m->info.slots - 1;
+  va.key_lut = m->key_lut.p; va.kd = m->kd;
+  va.bucket_off = m->bucket_off.p; va.n_buckets = (int)m->info.n_buckets;
+  va.records = m->records.p;
+  va.n_tiles = m->info.n_tiles; va.tile_refs = m->info.tile_refs; va.num_angles = m->info.num_angles; va.n_model = m->info.n_ref;
+  va.angle_step = m->info.angle_step; va.dist_step = m->info.distance_step;
   va.bucket_total = m->bucket_total.p;
   va.bucket_mid = m->bucket_mid.p;
   va.grp_records = m->n_grp_records ? m->grp_records.p : nullptr;
   va.grp_hdr = m->n_grp_records ? m->grp_hdr.p : nullptr;
   va.key_exact = m->params.key_equality == PPF_KEY_EXACT;
-  /* 16-bit cells first, 32-bit cells for the (reference point, tile)s whose cells overflow -- until a call casts more than
-   * PPF_ACC32_SWITCH of its votes twice that way: from then on 32-bit cells for everything (what they cost extra is less than
-   * what the repeats cost: profiles/r04_c4_acc32_policies.md).  PPF_OPT_ACC32 = 3 instead sends the items that will cast at
-   * least ws->heavy_votes votes straight to the 32-bit launch, decided on the device, per item, for THIS scene, before a vote
-   * is cast (measured on C4: slower than either, the vote count of an item says little about its fullest cell). */
-  const bool acc32_all = ws->force_acc32 || (ws->acc32 && ws->acc32_policy == 0);
-  va.item_votes = (!acc32_all && ws->acc32_policy == 3) ? ws->item_votes.p : nullptr;
-  va.heavy_votes = ws->heavy_votes;
-  const bool darboux = m->params.feature == PPF_FEATURE_DARBOUX;
   va.pair_radius = params->pair_radius;
+  va.pair_chunks = pair_chunks_of(va.paired.n);
   va.agg_min_hits = (params->vote_mode == PPF_VOTE_DIRECT || params->alpha_range_2pi || m->info.num_angles > AGG_MAX_ANGLES) ? 0 : PPF_AGG_MIN_HITS;
-  const int n_paired = va.paired.n;
-  va.pair_chunks = (n_paired + PAIR_BLOCK * PAIRS_PER_THREAD - 1) / (PAIR_BLOCK * PAIRS_PER_THREAD);
-  const uint32_t round_cap = ws->round_buckets_cap > 0 ? (uint32_t)std::min(ws->round_buckets_cap, GROUP_MAX_BUCKETS) : (uint32_t)GROUP_MAX_BUCKETS;
-  va.n_rounds = std::max(1, (int)((m->info.n_buckets + round_cap - 1) / round_cap));
-  va.round_buckets = (int)std::min<uint32_t>(std::max<uint32_t>(m->info.n_buckets, 1u), round_cap);
-
   const bool cursors_new = !ws->cursors.p;
   HIPCHK(ws->cursors.reserve(CUR_WORDS));
   va.cursors = ws->cursors.p;
-  if (cursors_new) HIPCHK(hipMemsetAsync(ws->cursors.p, 0, CUR_WORDS * sizeof(uint32_t), st)); /* k_frames never clears cursors[CUR_ODDVALUES]: a fresh block must not hold a launch's number by chance (see odd_epoch; 0, which the cold pass and the wrap below write, is no launch's number) */
-  va.n_counters = n_cnt;
-  va.n_ovf_items = (unsigned long long)n_ref * T;
-  if (!ws->frac_known) {
-    /* Cold workspace: nothing is known about this scene's hit density, so the pair kernel first only counts its hits
-     * (same arithmetic, nothing stored) and the pools are sized from the exact number.  Costs one extra pair pass and
-     * one wait for the device, once: later calls size their pools from what the previous call saw. */
-    HIPCHK(hipMemsetAsync(ws->cursors.p, 0, CUR_WORDS * sizeof(uint32_t), st));
-    va.count_only = 1;
-    va.stripe_bits = 6;
-    for (int base = 0; base < n_ref; base += 32768) {
-      va.ref_base = base;
-      va.n_ref = std::min(32768, n_ref - base);
-      launch_pairs(va, darboux, st);
-      HIPCHK(hipGetLastError());
-    }
-    va.count_only = 0;
-    std::vector<uint32_t> cw(CUR_SORTED);
-    HIPCHK(hipMemcpyAsync(cw.data(), ws->cursors.p, cw.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(host_stream_sync(st));
-    unsigned long long hits = 0;
-    for (int sidx = 0; sidx < POOL_STRIPES; sidx++)
-      hits += (unsigned long long)cw[sidx * CUR_STRIDE] | ((unsigned long long)cw[sidx * CUR_STRIDE + 1] << 32);
-    const double pairs_total = (double)n_ref * (double)n_paired;
-    ws->hit_frac = std::min(1.0, std::max(1e-3, 1.06 * (double)hits / std::max(1.0, pairs_total)));
-    ws->frac_known = true;
+  if (cursors_new) HIPCHK(hipMemsetAsync(ws->cursors.p, 0, CUR_WORDS * sizeof(uint32_t), ws->stream)); /* k_frames never clears cursors[CUR_ODDVALUES]: a fresh block must not hold a launch's number by chance (see odd_epoch; 0, which the cold pass and the wrap below write, is no launch's number) */
+  return PPF_OK;
+}
+
+/* Cold workspace: nothing is known about this scene's hit density, so the pair kernel first only counts its hits
+ * (same arithmetic, nothing stored) and the pools are sized from the exact number.  Costs one extra pair pass and
+ * one wait for the device, once: later calls size their pools from what the previous call saw. */
+static ppf_status match_cold_count(ppf_workspace* ws, MatchArgs& va, bool darboux) {
+  hipStream_t st = ws->stream;
+  const int n_ref = ws->n_ref;
+  HIPCHK(hipMemsetAsync(ws->cursors.p, 0, CUR_WORDS * sizeof(uint32_t), st));
+  va.count_only = 1;
+  va.stripe_bits = 6;
+  for (int base = 0; base < n_ref; base += 32768) {
+    va.ref_base = base;
+    va.n_ref = std::min(32768, n_ref - base);
+    launch_pairs(va, darboux, st);
+    HIPCHK(hipGetLastError());
   }
-  /* batch of reference points: its expected hits fit the scratch budget (and 32-bit pool offsets) */
-  const double frac = std::min(1.0, std::max(ws->hit_frac, 1e-3));
-  const double hits_per_ref = std::max(64.0, frac * (double)n_paired);
-  const double tbl_frac = !va.agg_min_hits ? 0.0 : frac >= 1.0 ? TBL_FRAC_MAX : std::min(TBL_FRAC_MAX, ws->tbl_frac);
-  int batch = (int)std::min<double>((double)n_ref, std::max(1.0, (double)HIT_BYTES_BUDGET / (hits_per_ref * (HIT_SCRATCH_BYTES + tbl_frac * TBL_BYTES))));
-  batch = (int)std::min<double>((double)batch, std::max(1.0, 2.0e9 / hits_per_ref));
-  batch = std::min(batch, 32768); /* grid.y of k_pairs */
-  if (ws->batch_refs_cap > 0) batch = std::min(batch, ws->batch_refs_cap);
-  const bool worst_case = frac >= 1.0;
-  const double est = hits_per_ref * (double)batch;
-  /* a stripe receives whole workgroups of up to PAIR_BLOCK*PAIRS_PER_THREAD hits; at worst-case size every workgroup of
-   * the batch could be full and land anywhere, otherwise 4 % + two workgroups of slack over an even share */
-  const uint32_t wg_hits = PAIR_BLOCK * PAIRS_PER_THREAD;
-  int stripe_bits = 6; /* 64 stripes, fewer while a stripe would average over less than 512 workgroups */
-  while (stripe_bits > 0 && ((size_t)batch * va.pair_chunks >> stripe_bits) < 512) stripe_bits--;
-  if (worst_case) stripe_bits = 0; /* one stripe that holds every pair of the batch: nothing can overflow */
-  const uint32_t n_stripes = 1u << stripe_bits;
-  const uint32_t stripe_cap = worst_case ? (uint32_t)std::min<double>(4.0e9 / n_stripes, (double)batch * va.pair_chunks * wg_hits)
-                                         : (uint32_t)(est / n_stripes * 1.04) + 2 * wg_hits;
-  const uint32_t sorted_cap = (uint32_t)std::min(4.0e9, est + 4096.0);
-  const uint32_t run_cap = worst_case ? sorted_cap : (uint32_t)std::min<double>((double)sorted_cap, std::max(est * std::min(1.0, ws->run_frac), 64.0 * batch) + 1024.0);
-  HIPCHK(ws->frames.reserve((size_t)batch * 12));
-  HIPCHK(ws->raw.fit((size_t)stripe_cap * n_stripes));
-  HIPCHK(ws->chunk_desc.reserve((size_t)batch * va.pair_chunks));
-  HIPCHK(ws->hit_count.reserve(batch));
-  HIPCHK(ws->s_a64.fit(sorted_cap));
-  /* count tables: a run of c >= agg_min_hits hits takes ceil(c / AGG_SUB), so TBL_FRAC_MAX per hit is the ceiling */
-  const uint32_t table_cap = !va.agg_min_hits ? 1u : (uint32_t)std::min(1.0e9, std::max(est * (worst_case ? TBL_FRAC_MAX : tbl_frac), 4.0 * batch) + 256.0);
-  HIPCHK(ws->runs.fit(run_cap));
-  HIPCHK(ws->tables.fit((size_t)table_cap * TBL_BYTES));
-  HIPCHK(ws->table_desc.fit(table_cap));
-  HIPCHK(ws->run_blocks.reserve((size_t)batch * va.n_rounds));
-  HIPCHK(ws->work.reserve(batch));
-  HIPCHK(ws->perm.reserve(batch));
-  HIPCHK(ws->perm_group.reserve(batch));
-  HIPCHK(ws->ovf_list.reserve((size_t)batch * T));
-  va.ovf_list = ws->ovf_list.p;
+  va.count_only = 0;
+  std::vector<uint32_t> cw(CUR_SORTED);
+  HIPCHK(hipMemcpyAsync(cw.data(), ws->cursors.p, cw.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(host_stream_sync(st));
+  unsigned long long hits = 0;
+  for (int sidx = 0; sidx < POOL_STRIPES; sidx++)
+    hits += (unsigned long long)cw[sidx * CUR_STRIDE] | ((unsigned long long)cw[sidx * CUR_STRIDE + 1] << 32);
+  ws->frac.learn_hits(hits, (double)n_ref * (double)va.paired.n);
+  ws->frac_known = true;
+  return PPF_OK;
+}
+
+/* the hit scratch of one batch, sized by the plan, and the plan's numbers into va */
+static ppf_status match_reserve(ppf_workspace* ws, const MatchPlan& p, MatchArgs& va) {
+  HIPCHK(ws->frames.reserve((size_t)p.batch * 12));
+  HIPCHK(ws->raw.fit((size_t)p.stripe_cap << p.stripe_bits));
+  HIPCHK(ws->chunk_desc.reserve((size_t)p.batch * p.pair_chunks));
+  HIPCHK(ws->hit_count.reserve(p.batch));
+  HIPCHK(ws->s_a64.fit(p.sorted_cap));
+  HIPCHK(ws->runs.fit(p.run_cap));
+  HIPCHK(ws->tables.fit((size_t)p.table_cap * TBL_BYTES));
+  HIPCHK(ws->table_desc.fit(p.table_cap));
+  HIPCHK(ws->run_blocks.reserve((size_t)p.batch * p.n_rounds));
+  HIPCHK(ws->work.reserve(p.batch));
+  HIPCHK(ws->perm.reserve(p.batch));
+  HIPCHK(ws->perm_group.reserve(p.batch));
+  HIPCHK(ws->ovf_list.reserve((size_t)p.batch * va.n_tiles));
   ws->stats.scratch_bytes = ws->frames.bytes() + ws->raw.bytes() + ws->cursors.bytes() + ws->chunk_desc.bytes() + ws->hit_count.bytes() +
                             ws->s_a64.bytes() + ws->runs.bytes() + ws->run_blocks.bytes() + ws->tables.bytes() + ws->table_desc.bytes() +
                             ws->work.bytes() + ws->perm.bytes() + ws->perm_group.bytes();
+  va.n_rounds = p.n_rounds; va.round_buckets = p.round_buckets; va.run_seg = p.run_seg;
+  va.ovf_list = ws->ovf_list.p;
   va.frames = ws->frames.p;
-  va.raw = ws->raw.p; va.stripe_cap = stripe_cap; va.stripe_bits = stripe_bits;
+  va.raw = ws->raw.p; va.stripe_cap = p.stripe_cap; va.stripe_bits = p.stripe_bits;
   va.chunk_desc = ws->chunk_desc.p; va.hit_count = ws->hit_count.p;
-  va.s_a64 = ws->s_a64.p; va.sorted_cap = sorted_cap;
-  va.runs = ws->runs.p; va.run_cap = run_cap; va.run_blocks = ws->run_blocks.p;
-  va.tables = ws->tables.p; va.table_desc = ws->table_desc.p; va.table_cap = table_cap;
+  va.s_a64 = ws->s_a64.p; va.sorted_cap = p.sorted_cap;
+  va.runs = ws->runs.p; va.run_cap = p.run_cap; va.run_blocks = ws->run_blocks.p;
+  va.tables = ws->tables.p; va.table_desc = ws->table_desc.p; va.table_cap = p.table_cap;
   va.work = ws->work.p; va.perm = ws->perm.p; va.perm_group = ws->perm_group.p;
-
-  /* the item staging gets the LDS this model's accumulator tile leaves (its least size is what the tile was sized against) */
-  const size_t acc_words = (size_t)vote_lds_words(m->info.tile_refs, m->info.num_angles);
-  va.run_seg = vote_run_seg(acc_words, (size_t)LDS_BYTES);
-  if (ws->run_seg_cap > 0) va.run_seg = std::max(64, std::min(va.run_seg, ws->run_seg_cap / 64 * 64)); /* test knob: PPF_OPT_RUN_STAGING */
-  const size_t lds = vote_lds_fixed(va.run_seg) + acc_words * 4;
-  if (lds > (size_t)LDS_BYTES) return fail(PPF_ERR_INVALID, "match: model tile of %d reference points does not fit the LDS accumulator", m->info.tile_refs);
-  /* k_group's dynamic LDS: one counter per bucket of a round, the prefix of the pool pieces */
-  const size_t group_lds = (size_t)((va.round_buckets + 1) & ~1) * sizeof(uint32_t) + (size_t)((va.pair_chunks + 2) & ~1) * sizeof(uint32_t) * 2;
-  if (group_lds + 2048 > (size_t)LDS_BYTES) return fail(PPF_ERR_INVALID, "match: %d paired points are more than one call can group", n_paired);
-  static std::once_flag once;
-  static hipError_t attr_err = hipSuccess;
-  std::call_once(once, [] {
-    const void* votes[4] = {reinterpret_cast<const void*>(&k_vote<false, false>), reinterpret_cast<const void*>(&k_vote<true, false>),
-                            reinterpret_cast<const void*>(&k_vote<false, true>), reinterpret_cast<const void*>(&k_vote<true, true>)};
-    for (const void* f : votes)
-      if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (attr_err == hipSuccess)
-      attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_group), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES - 1024);
-  });
-  HIPCHK(attr_err);
-  const int n_batches = (n_ref + batch - 1) / batch;
-  ws->n_batches = n_batches;
-  ws->stats.n_batches = n_batches;
+  ws->n_batches = p.n_batches;
+  ws->stats.n_batches = p.n_batches;
   if (ws->timing)
-    while (ws->batch_ev.size() < ws->ev_base + (size_t)n_batches * 4) {
+    while (ws->batch_ev.size() < ws->ev_base + (size_t)p.n_batches * 4) {
       hipEvent_t e = nullptr;
       HIPCHK(hipEventCreate(&e));
       ws->batch_ev.push_back(e);
     }
-  for (int bi = 0; bi < n_batches; bi++) {
-    const int base = bi * batch;
-    va.ref_base = base;
-    va.n_ref = std::min(batch, n_ref - base);
-    /* k_frames clears the batch's cursors and table_desc on the side, for the first batch also the call's counters, ovf_items and
-     * the overflow word (which lives on through the later batches); it raises "odd values" by writing this launch's own number */
-    va.first_batch = bi == 0;
-    if (++ws->odd_epoch == 0u) { /* wrapped: a word left by the launch 2^32 before this one must not match */
-      HIPCHK(hipMemsetAsync(ws->cursors.p + CUR_ODDVALUES, 0, sizeof(uint32_t), st));
-      ws->odd_epoch = 1u;
-    }
-    va.odd_epoch = ws->odd_epoch;
-#if PPF_ABL_GROUP != 1 /* attribution builds of k_group store no payload: the later kernels read zeros, never stale values */
-    HIPCHK(hipMemsetAsync(ws->s_a64.p, 0, ws->s_a64.cap * sizeof(*ws->s_a64.p), st));
-#endif
-    /* a thread per reference point, and enough threads for its look at the paired points (40 waves walking 50,000 points: 10 us) */
-    k_frames<<<dim3(std::max((va.n_ref + 63) / 64, std::min((va.paired.n + 63) / 64, 1024))), dim3(64), 0, st>>>(va);
-    HIPCHK(hipGetLastError());
-    if (ws->timing) HIPCHK(hipEventRecord(ws->batch_ev[ws->ev_base + bi * 4 + 0], st));
-    launch_pairs(va, darboux, st);
-    HIPCHK(hipGetLastError());
-    if (ws->timing) HIPCHK(hipEventRecord(ws->batch_ev[ws->ev_base + bi * 4 + 1], st));
-    /* k_group takes the reference points with the most hits first */
-    k_rank<<<dim3((va.n_ref + RANK_KEYS - 1) / RANK_KEYS), dim3(256), 0, st>>>(va.hit_count, va.n_ref, nullptr, ws->perm_group.p, nullptr);
-    k_group<<<dim3(va.n_ref), dim3(GROUP_BLOCK), group_lds, st>>>(va);
-    HIPCHK(hipGetLastError());
-    if (va.agg_min_hits) { /* the count tables of the batch's many-hit runs, once per run */
-      k_tables<<<dim3((table_cap + TABLE_BLOCK / 64 - 1) / (TABLE_BLOCK / 64)), dim3(TABLE_BLOCK), 0, st>>>(va);
-      HIPCHK(hipGetLastError());
-    }
-    /* k_vote takes the reference points that will cast the most votes first */
-    k_rank<<<dim3((va.n_ref + RANK_KEYS - 1) / RANK_KEYS), dim3(256), 0, st>>>(va.work, va.n_ref, nullptr, va.perm, nullptr);
-    HIPCHK(hipGetLastError());
-    if (ws->timing) HIPCHK(hipEventRecord(ws->batch_ev[ws->ev_base + bi * 4 + 2], st));
-    const dim3 grid16((unsigned)((size_t)va.n_ref * T)), grid32((unsigned)((size_t)va.n_ref * T * 2));
-    if (!acc32_all) {
-      va.acc32 = 0;
-      if (params->alpha_range_2pi) k_vote<true, false><<<grid16, dim3(VOTE_BLOCK), lds, st>>>(va);
-      else k_vote<false, false><<<grid16, dim3(VOTE_BLOCK), lds, st>>>(va);
-      HIPCHK(hipGetLastError());
-    }
-    va.acc32 = acc32_all ? 1 : 2; /* 2: the (reference point, tile)s the 16-bit launch listed, over a grid that does not depend on their number */
-    const dim3 g32 = acc32_all ? grid32 : dim3(std::min(grid32.x, 256u)); /* one workgroup per CU walks the list (a launch of 1,024 with nothing to do: 10 us) */
-    if (params->alpha_range_2pi) k_vote<true, true><<<g32, dim3(VOTE_BLOCK), lds, st>>>(va);
-    else k_vote<false, true><<<g32, dim3(VOTE_BLOCK), lds, st>>>(va);
-    va.acc32 = 0;
-    HIPCHK(hipGetLastError());
-    if (ws->timing) HIPCHK(hipEventRecord(ws->batch_ev[ws->ev_base + bi * 4 + 3], st));
-  }
+  return PPF_OK;
+}
 
+/* One batch of reference points, va.ref_base .. + va.n_ref: frames, pairs, rank, group, tables, rank, vote16, vote32.
+ * `ev` is the batch's four events (timing on) or NULL. */
+static ppf_status match_enqueue_batch(ppf_workspace* ws, MatchArgs& va, const MatchPlan& p, bool darboux, const hipEvent_t* ev) {
+  hipStream_t st = ws->stream;
+#if PPF_ABL_GROUP != 1 /* attribution builds of k_group store no payload: the later kernels read zeros, never stale values */
+  HIPCHK(hipMemsetAsync(ws->s_a64.p, 0, ws->s_a64.cap * sizeof(*ws->s_a64.p), st));
+#endif
+  /* k_frames clears the batch's cursors and table_desc on the side, for the first batch also the call's counters, ovf_items and
+   * the overflow word (which lives on through the later batches); it raises "odd values" by writing this launch's own number.
+   * A thread per reference point, and enough threads for its look at the paired points (40 waves walking 50,000 points: 10 us) */
+  k_frames<<<dim3(std::max((va.n_ref + 63) / 64, std::min((va.paired.n + 63) / 64, 1024))), dim3(64), 0, st>>>(va);
+  HIPCHK(hipGetLastError());
+  if (ev) HIPCHK(hipEventRecord(ev[0], st));
+  launch_pairs(va, darboux, st);
+  HIPCHK(hipGetLastError());
+  if (ev) HIPCHK(hipEventRecord(ev[1], st));
+  /* k_group takes the reference points with the most hits first */
+  k_rank<<<dim3((va.n_ref + RANK_KEYS - 1) / RANK_KEYS), dim3(256), 0, st>>>(va.hit_count, va.n_ref, nullptr, ws->perm_group.p, nullptr);
+  k_group<<<dim3(va.n_ref), dim3(GROUP_BLOCK), p.group_lds, st>>>(va);
+  HIPCHK(hipGetLastError());
+  if (va.agg_min_hits) { /* the count tables of the batch's many-hit runs, once per run */
+    k_tables<<<dim3((p.table_cap + TABLE_BLOCK / 64 - 1) / (TABLE_BLOCK / 64)), dim3(TABLE_BLOCK), 0, st>>>(va);
+    HIPCHK(hipGetLastError());
+  }
+  /* k_vote takes the reference points that will cast the most votes first */
+  k_rank<<<dim3((va.n_ref + RANK_KEYS - 1) / RANK_KEYS), dim3(256), 0, st>>>(va.work, va.n_ref, nullptr, va.perm, nullptr);
+  HIPCHK(hipGetLastError());
+  if (ev) HIPCHK(hipEventRecord(ev[2], st));
+  const bool acc32_all = acc32_for_all(ws), wrap = ws->params.alpha_range_2pi != 0;
+  const dim3 grid16((unsigned)((size_t)va.n_ref * va.n_tiles)), grid32((unsigned)((size_t)va.n_ref * va.n_tiles * 2));
+  if (!acc32_all) {
+    va.acc32 = 0;
+    launch_vote(va, wrap, false, grid16, p.vote_lds, st);
+    HIPCHK(hipGetLastError());
+  }
+  va.acc32 = acc32_all ? 1 : 2; /* 2: the (reference point, tile)s the 16-bit launch listed, over a grid that does not depend on their number */
+  /* one workgroup per CU walks the list (a launch of 1,024 with nothing to do: 10 us) */
+  launch_vote(va, wrap, true, acc32_all ? grid32 : dim3(std::min(grid32.x, 256u)), p.vote_lds, st);
+  va.acc32 = 0;
+  HIPCHK(hipGetLastError());
+  if (ev) HIPCHK(hipEventRecord(ev[3], st));
+  return PPF_OK;
+}
+
+/* after the last batch: the poses of the reference points, their clusters, and the summary the host reads first */
+static ppf_status match_enqueue_tail(ppf_workspace* ws, const MatchArgs& va) {
+  const ppf_model* m = ws->model;
+  const ppf_match_params* params = &ws->params;
+  hipStream_t st = ws->stream;
+  const int n_ref = ws->n_ref, T = m->info.n_tiles;
   FinalArgs fa;
   fa.surf = ws->surf.view(); fa.model = m->cloud.view();
-  fa.scene_step = scene_step; fa.ref_offset = params->ref_offset; fa.ref_stride = params->ref_stride; fa.n_ref = n_ref;
+  fa.scene_step = va.scene_step; fa.ref_offset = params->ref_offset; fa.ref_stride = params->ref_stride; fa.n_ref = n_ref;
   fa.n_tiles = T; fa.tile_refs = m->info.tile_refs; fa.num_angles = m->info.num_angles;
   fa.alpha_2pi = params->alpha_range_2pi != 0;
-  fa.acc32 = acc32_all ? 1 : 0; fa.ovf_items = ws->ovf_items.p; fa.edge = ws->half_edge.p;
+  fa.acc32 = acc32_for_all(ws) ? 1 : 0; fa.ovf_items = ws->ovf_items.p; fa.edge = ws->half_edge.p;
   fa.partial = ws->partial.p; fa.cellsum = va.cellsum; fa.pairs = va.pairs;
   fa.votes = ws->votes.p; fa.poses = ws->raw_poses.p;
   fa.totals = ws->counters.p + (size_t)n_ref * T + n_ref;
@@ -452,8 +509,8 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
     resolve_thresholds(m, params, &pos, &rot);
     /* the reference clusters sampled.rows / sceneSamplingStep poses (integer division: the lowest-voted
      * pose is dropped when the stride does not divide the row count); a shard clusters its own share */
-    const int num = (params->ref_stride == 1 && params->ref_offset == 0) ? rows / scene_step : n_ref;
-    s = enqueue_cluster(ws, ws->raw_poses.p, n_ref, num, pos, rot, params->use_weighted_avg != 0, st, params->rot_metric_relative != 0, true);
+    const int num = (params->ref_stride == 1 && params->ref_offset == 0) ? ws->rows / va.scene_step : n_ref;
+    const ppf_status s = enqueue_cluster(ws, ws->raw_poses.p, n_ref, num, pos, rot, params->use_weighted_avg != 0, st, params->rot_metric_relative != 0, true);
     if (s != PPF_OK) return s;
     ws->clustered = true;
   }
@@ -465,104 +522,138 @@ static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const pp
   return PPF_OK;
 }
 
+/* everything after A2: frames -> pairs -> group -> rank -> vote -> finalize -> cluster, on the clouds held by ws.
+ * Nothing here waits for the device: the hit pools are sized by match_plan from ws->frac (learned from the previous
+ * calls); a pool that turns out too small raises a device flag, which the first accessor of the results reads
+ * (workspace_finish) and answers by repeating the call with bigger pools. */
+static ppf_status match_prepared(const ppf_model* m, ppf_workspace* ws, const ppf_match_params* params, hipStream_t st, bool retry) {
+  ppf_status s = match_reset(m, ws, params, st, retry);
+  if (s != PPF_OK || ws->n_ref == 0) return s;
+  const bool darboux = m->params.feature == PPF_FEATURE_DARBOUX;
+  MatchArgs va;
+  memset(&va, 0, sizeof(va));
+  if ((s = match_call_buffers(ws, va)) != PPF_OK) return s;
+  if ((s = match_args(ws, va)) != PPF_OK) return s;
+  if (!ws->frac_known && (s = match_cold_count(ws, va, darboux)) != PPF_OK) return s;
+  MatchPlan plan;
+  const MatchPlanIn in = {ws->n_ref, va.paired.n, ws->frac.hit, ws->frac.run, ws->frac.tbl, va.agg_min_hits != 0, ws->batch_refs_cap,
+                          ws->round_buckets_cap, ws->run_seg_cap, m->info.n_buckets, m->info.tile_refs, m->info.num_angles};
+  if ((s = match_plan(in, &plan)) != PPF_OK) return s;
+  if ((s = match_reserve(ws, plan, va)) != PPF_OK) return s;
+  HIPCHK(match_kernel_attributes());
+  for (int bi = 0; bi < plan.n_batches; bi++) {
+    va.ref_base = bi * plan.batch;
+    va.n_ref = std::min(plan.batch, ws->n_ref - va.ref_base);
+    va.first_batch = bi == 0;
+    if (++ws->odd_epoch == 0u) { /* wrapped: a word left by the launch 2^32 before this one must not match */
+      HIPCHK(hipMemsetAsync(ws->cursors.p + CUR_ODDVALUES, 0, sizeof(uint32_t), st));
+      ws->odd_epoch = 1u;
+    }
+    va.odd_epoch = ws->odd_epoch;
+    if ((s = match_enqueue_batch(ws, va, plan, darboux, ws->timing ? &ws->batch_ev[ws->ev_base + (size_t)bi * 4] : nullptr)) != PPF_OK) return s;
+  }
+  return match_enqueue_tail(ws, va);
+}
+
+/* the batch events of a call (four per batch from `base`: pairs start / end, vote start / end) as milliseconds, added to the three sums */
+static ppf_status add_batch_ms(const ppf_workspace* ws, size_t base, int n_batches, float* pair, float* group, float* vote) {
+  for (int b = 0; b < n_batches; b++) {
+    const hipEvent_t* e = &ws->batch_ev[base + (size_t)b * 4];
+    float t0 = 0, t1 = 0, t2 = 0;
+    HIPCHK(hipEventElapsedTime(&t0, e[0], e[1]));
+    HIPCHK(hipEventElapsedTime(&t1, e[1], e[2]));
+    HIPCHK(hipEventElapsedTime(&t2, e[2], e[3]));
+    *pair += t0; *group += t1; *vote += t2;
+  }
+  return PPF_OK;
+}
+
+/* PPF_OPT_ACC32 = 3, the limit of the next call: k_finalize filed the votes of every (reference point, tile) under its size
+ * class, as "needed 32-bit cells" (a cell beyond 65,535; hist[class]) or "did not" (hist[ACC_HIST + class]).  An item sent to
+ * 32-bit cells costs about PPF_ACC32_COST of what 16-bit cells cost it; one that overflows 16-bit cells costs
+ * 1 + PPF_ACC32_COST.  The class boundary that makes the sum smallest becomes the limit (none above every class: the scene
+ * needs no 32-bit cells). */
+static unsigned long long acc32_heavy_votes(const unsigned long long* hist) {
+  double best = -1;
+  int best_k = ACC_HIST;
+  double above = 0, below = 0; /* cost of the classes >= k (sent to 32-bit cells) / < k (tried with 16-bit cells) */
+  for (int b = 0; b < ACC_HIST; b++) below += (double)hist[ACC_HIST + b] + (1.0 + PPF_ACC32_COST) * (double)hist[b];
+  for (int k = ACC_HIST; k >= 0; k--) {
+    if (k < ACC_HIST) {
+      const double need = (double)hist[k], rest = (double)hist[ACC_HIST + k];
+      above += PPF_ACC32_COST * (need + rest);
+      below -= rest + (1.0 + PPF_ACC32_COST) * need;
+    }
+    const double cost = above + below;
+    if (best < 0 || cost < best) { best = cost; best_k = k; }
+  }
+  const unsigned long long heavy_votes = best_k >= ACC_HIST ? ~0ull : acc_hist_lower(best_k);
+  if (getenv("PPF_DEBUG_ACC32")) {
+    for (int b = 0; b < ACC_HIST; b++)
+      if (hist[b] || hist[ACC_HIST + b])
+        fprintf(stderr, "acc32 class %3d (>= %llu votes): needed %llu  not needed %llu\n", b, acc_hist_lower(b), hist[b], hist[ACC_HIST + b]);
+    fprintf(stderr, "acc32 limit -> class %d (%llu votes)\n", best_k, heavy_votes);
+  }
+  return heavy_votes;
+}
+
 /* Wait for the workspace's pending call and make sure it ran with big enough hit pools: when a pool overflowed (device
- * flag), the call is repeated on the same stream with a doubled estimate, until it fits (at hit_frac == 1 the pools
- * hold every scene pair).  Also reads the counters and learns hit_frac for the next call. */
+ * flag), the call is repeated on the same stream with grown fractions, until it fits (at frac.hit == 1 the pools
+ * hold every scene pair).  Then reads the counters and learns the fractions for the next call. */
 static ppf_status workspace_finish(ppf_workspace* ws) {
   if (!ws->pending) return fail(PPF_ERR_INVALID, "no call in this workspace");
   HIPCHK(host_stream_sync(ws->stream));
   if (ws->checked || ws->n_ref == 0) { ws->checked = true; return PPF_OK; }
+  unsigned long long tot[16];
   for (;;) {
-    const int T = ws->model->info.n_tiles;
-    unsigned long long tot[16];
     uint32_t ovf = 0;
     if (ws->sum_valid) { /* k_summary wrote them into pinned memory as the call's last act */
       memcpy(tot, ws->h_sum, sizeof(tot));
       ovf = (uint32_t)ws->h_sum[16];
     } else {
-      HIPCHK(host_read(tot, ws->counters.p + (size_t)ws->n_ref * T + ws->n_ref, sizeof(tot)));
+      HIPCHK(host_read(tot, ws->counters.p + (size_t)ws->n_ref * ws->model->info.n_tiles + ws->n_ref, sizeof(tot)));
       HIPCHK(host_read(&ovf, ws->cursors.p + CUR_OVERFLOW, sizeof(ovf)));
     }
-    if (!ovf) {
-      ws->stats.n_votes = tot[0];
-      ws->stats.n_pairs = tot[1];
-      ws->stats.n_lds_atomics = tot[2];
-      ws->stats.n_hits = tot[3];
-      ws->stats.n_acc32_items = tot[5];
-      /* The limit of the next call: k_finalize filed the votes of every (reference point, tile) under its size class, as
-       * "needed 32-bit cells" (a cell beyond 65,535) or "did not".  An item sent to 32-bit cells costs about PPF_ACC32_COST of
-       * what 16-bit cells cost it; one that overflows 16-bit cells costs 1 + PPF_ACC32_COST.  The class boundary that makes
-       * the sum smallest becomes the limit (none above every class: the scene needs no 32-bit cells). */
-      if (!ws->acc32 && ws->acc32_policy == 0 && (double)tot[6] > PPF_ACC32_SWITCH * (double)tot[0]) ws->acc32 = true;
-      if (!ws->force_acc32 && ws->acc32_policy == 3) {
-        unsigned long long hist[2 * ACC_HIST];
-        HIPCHK(host_read(hist, ws->need_hist.p, sizeof(hist)));
-        double best = -1;
-        int best_k = ACC_HIST;
-        double above = 0, below = 0; /* cost of the classes >= k (sent to 32-bit cells) / < k (tried with 16-bit cells) */
-        for (int b = 0; b < ACC_HIST; b++) below += (double)hist[ACC_HIST + b] + (1.0 + PPF_ACC32_COST) * (double)hist[b];
-        for (int k = ACC_HIST; k >= 0; k--) {
-          if (k < ACC_HIST) {
-            const double need = (double)hist[k], rest = (double)hist[ACC_HIST + k];
-            above += PPF_ACC32_COST * (need + rest);
-            below -= rest + (1.0 + PPF_ACC32_COST) * need;
-          }
-          const double cost = above + below;
-          if (best < 0 || cost < best) { best = cost; best_k = k; }
-        }
-        ws->heavy_votes = best_k >= ACC_HIST ? ~0ull : acc_hist_lower(best_k);
-        if (getenv("PPF_DEBUG_ACC32")) {
-          for (int b = 0; b < ACC_HIST; b++)
-            if (hist[b] || hist[ACC_HIST + b])
-              fprintf(stderr, "acc32 class %3d (>= %llu votes): needed %llu  not needed %llu\n", b, acc_hist_lower(b), hist[b], hist[ACC_HIST + b]);
-          fprintf(stderr, "acc32 limit -> class %d (%llu votes)\n", best_k, ws->heavy_votes);
-        }
-      }
-      if (tot[1]) ws->hit_frac = std::min(1.0, std::max(1e-3, 1.06 * (double)tot[3] / (double)tot[1]));
-      if (tot[3]) ws->run_frac = std::min(1.0, std::max(0.02, 1.10 * (double)tot[4] / (double)tot[3]));
-      if (tot[3]) ws->tbl_frac = std::min(TBL_FRAC_MAX, std::max(1e-4, 1.15 * (double)tot[7] / (double)tot[3]));
-      ws->stats.n_tables = tot[7];
-      for (int k = 0; k < 8; k++) ws->stats.phase_clocks[k] = tot[8 + k];
-      ws->frac_known = true;
-      if (ws->clustered) {
-        uint32_t nf = 0;
-        if (ws->sum_valid) nf = (uint32_t)ws->h_sum[17];
-        else HIPCHK(host_read(&nf, ws->cl_u32.p, sizeof(uint32_t)));
-        ws->stats.n_poses = (int)nf;
-      }
-      if (ws->timing) {
-        float pr = 0, gr = 0, vo = 0;
-        for (int b = 0; b < ws->n_batches; b++) {
-          float t0 = 0, t1 = 0, t2 = 0;
-          const size_t e0 = ws->ev_base + (size_t)b * 4;
-          HIPCHK(hipEventElapsedTime(&t0, ws->batch_ev[e0 + 0], ws->batch_ev[e0 + 1]));
-          HIPCHK(hipEventElapsedTime(&t1, ws->batch_ev[e0 + 1], ws->batch_ev[e0 + 2]));
-          HIPCHK(hipEventElapsedTime(&t2, ws->batch_ev[e0 + 2], ws->batch_ev[e0 + 3]));
-          pr += t0; gr += t1; vo += t2;
-        }
-        ws->stats.ms_pair_kernel = pr; ws->stats.ms_group_kernel = gr; ws->stats.ms_vote_kernel = vo;
-        HIPCHK(hipEventElapsedTime(&ws->stats.ms_total_device, ws->ev[0], ws->ev[1]));
-      }
-      ws->checked = true;
-      return PPF_OK;
-    }
-    if (ws->hit_frac >= 1.0) {
+    if (!ovf) break;
+    if (ws->frac.hit >= 1.0) {
       ws->pools_failed = true; /* not the caller's output buffer: a context in this state is not kept (HostLoan) */
       return fail(PPF_ERR_CAPACITY, "match: hit pools overflowed at worst-case size (flags %u)", ovf);
     }
-    if (ovf & 3u) ws->hit_frac = std::min(1.0, ws->hit_frac * 2.0); /* raw or sorted hit pool */
-    if (ovf & 4u) ws->run_frac = std::min(1.0, ws->run_frac * 2.0); /* run table */
-    if (ovf & 8u) { /* count-table pool */
-      if ((ovf & 3u) == 0 && ws->tbl_frac >= TBL_FRAC_MAX) ws->hit_frac = std::min(1.0, ws->hit_frac * 2.0); /* more hits than expected, then */
-      ws->tbl_frac = std::min(TBL_FRAC_MAX, ws->tbl_frac * 2.0);
-    }
+    ws->frac.grow(ovf);
     ws->stats.n_retries++;
     const ppf_match_params p = ws->params;
-    ppf_model* m = ws->model;
-    ppf_status s = match_prepared(m, ws, &p, ws->stream, true);
+    ppf_status s = match_prepared(ws->model, ws, &p, ws->stream, true);
     if (s != PPF_OK) return s;
     HIPCHK(host_stream_sync(ws->stream));
   }
+  ws->stats.n_votes = tot[0];
+  ws->stats.n_pairs = tot[1];
+  ws->stats.n_lds_atomics = tot[2];
+  ws->stats.n_hits = tot[3];
+  ws->stats.n_acc32_items = tot[5];
+  ws->stats.n_tables = tot[7];
+  for (int k = 0; k < 8; k++) ws->stats.phase_clocks[k] = tot[8 + k];
+  if (ws->clustered) {
+    uint32_t nf = 0;
+    if (ws->sum_valid) nf = (uint32_t)ws->h_sum[17];
+    else HIPCHK(host_read(&nf, ws->cl_u32.p, sizeof(uint32_t)));
+    ws->stats.n_poses = (int)nf;
+  }
+  ws->frac.learn(tot);
+  ws->frac_known = true;
+  if (!ws->acc32 && ws->acc32_policy == 0 && (double)tot[6] > PPF_ACC32_SWITCH * (double)tot[0]) ws->acc32 = true;
+  if (!ws->force_acc32 && ws->acc32_policy == 3) {
+    unsigned long long hist[2 * ACC_HIST];
+    HIPCHK(host_read(hist, ws->need_hist.p, sizeof(hist)));
+    ws->heavy_votes = acc32_heavy_votes(hist);
+  }
+  if (ws->timing) {
+    const ppf_status s = add_batch_ms(ws, ws->ev_base, ws->n_batches, &ws->stats.ms_pair_kernel, &ws->stats.ms_group_kernel, &ws->stats.ms_vote_kernel);
+    if (s != PPF_OK) return s;
+    HIPCHK(hipEventElapsedTime(&ws->stats.ms_total_device, ws->ev[0], ws->ev[1]));
+  }
+  ws->checked = true;
+  return PPF_OK;
 }
 
 ppf_status ppf_workspace_results(ppf_workspace* ws, ppf_vote* votes, ppf_pose* raw_poses, int cap_ref, int* n_ref,
