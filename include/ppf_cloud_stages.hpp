@@ -108,6 +108,23 @@ class Cloud {
     return fromDepthImage(depth, PPF_DEPTH_U16, scale, rows, cols, fx, fy, ppx, ppy, zMin, zMax, fp64, rowPitchBytes, &normals);
   }
 
+  static ppf_mesh_sample_params defaultMeshSampleParams() {
+    ppf_mesh_sample_params p;
+    ppf_default_mesh_sample_params(&p);
+    return p;
+  }
+  /* A model cloud sampled from a triangle mesh (ppf_cloud_from_mesh): on average one row per spacing^2 of surface, without
+   * the rows none of 26 views can see and with the normals turned outward; what train takes once downloaded.  vertices:
+   * nVertices rows of vstride floats, x y z first and, with normalOffset >= 0, a normal there; triangles: nTriangles index
+   * triples.  params == 0: defaultMeshSampleParams() (spacing 4 mm, face normals, visibility and orient on). */
+  static Cloud fromMesh(const float* vertices, int nVertices, int vstride, int normalOffset, const int32_t* triangles, int nTriangles,
+                        const ppf_mesh_sample_params* params = 0, ppf_mesh_sample_stats* stats = 0) {
+    const ppf_mesh_sample_params mp = params ? *params : defaultMeshSampleParams();
+    ppf_cloud* c = nullptr;
+    ppf_match_3d::check(ppf_cloud_from_mesh(vertices, nVertices, vstride, normalOffset, triangles, nTriangles, &mp, &c, stats));
+    return Cloud(c);
+  }
+
   bool empty() const { return size() == 0; }
   int size() const {
     if (!h_) return 0;

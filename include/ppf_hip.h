@@ -1093,6 +1093,91 @@ ppf_status ppf_depth_volume_raycast_device(ppf_depth_volume* v, int rows, int co
 ppf_status ppf_depth_volume_extract(ppf_depth_volume* v, const ppf_depth_volume_extract_params* ep, ppf_cloud** out,
                                     ppf_depth_volume_extract_stats* stats /* may be NULL */);
 
+/* ---- a model cloud sampled from a triangle mesh ------------------------------------------------------
+ * The CAD side of "where does the model come from": rows x y z nx ny nz drawn on the surface of a triangle mesh, one per
+ * spacing^2 on average, without the faces no camera can see and with the normals turned outward.  Everything below is evaluated
+ * in fp64 exactly as written (no contraction), so a row's bytes are a function of the arguments alone.
+ *
+ * mix(x):  x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35; x ^= x >> 16          (uint32, mod 2^32)
+ * h(seed, k, c) = mix(mix(mix(seed + 0x9e3779b9) ^ k) ^ c)                        (k the triangle, c a counter, uint32)
+ * 1. Triangle k = (i0, i1, i2): v = (double) of the vertices' floats, e1 = v1 - v0, e2 = v2 - v0,
+ *    c = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), L = sqrt((c0 c0 + c1 c1) + c2 c2).  The triangle is
+ *    degenerate iff !(L > 0) or L is not finite (a non-finite vertex makes it so): it is counted in n_degenerate, gives no
+ *    rows and draws nothing.  area = the sum of 0.5 L in any order (reported only).
+ * 2. q = (0.5 L) / ((double)spacing * (double)spacing), f = floor(q),
+ *    n_k = f + ((h(seed, k, 0) >> 8) < (uint32)floor((q - f) * 16777216.0) ? 1 : 0).  q >= max_rows for one triangle, or
+ *    the sum of the n_k above max_rows, is PPF_ERR_CAPACITY before any row is made.
+ * 3. Row j of triangle k: u = ((double)(h(seed, k, 2j + 1) >> 8) + 0.5) / 16777216.0, v likewise from 2j + 2 (counters
+ *    mod 2^32); if u + v > 1.0 then u = 1.0 - u and v = 1.0 - v.  p = (float)((v0 + u e1) + v e2) per component.
+ *    PPF_MESH_NORMALS_FACE: n = (float)(c / L).  PPF_MESH_NORMALS_VERTEX: with n0, n1, n2 the (double) vertex normals and
+ *    w = (1.0 - u) - v, m = (w n0 + u n1) + v n2 per component and l = sqrt((m0 m0 + m1 m1) + m2 m2): n = (float)(m / l)
+ *    when l > 0 and l is finite, the face normal otherwise.
+ * 4. Views (visibility only): the 26 directions d are the non-zero vectors of {-1, 0, 1}^3 in lexicographic order with x
+ *    slowest, each times 1.0 / sqrt(1.0 | 2.0 | 3.0) by its count of non-zero components.  e = the coordinate axis of the
+ *    smallest |d| component (the first on ties), t = d x e, a = t / sqrt((t0 t0 + t1 t1) + t2 t2), b = d x a (cross
+ *    products as in 1).  lo, hi = the minima and maxima of the floats of the vertices of non-degenerate triangles (-0 below
+ *    +0), ctr = 0.5 (lo + hi), g = hi - lo, r = 0.5 sqrt((g0 g0 + g1 g1) + g2 g2), px = 2.0 r / (double)(R - 2), R = map_size.
+ *    A point p maps to X = dot(p - ctr, a) / px + 0.5 R, Y the same with b, D = dot(p - ctr, d) + r; dot(s, t) =
+ *    (s0 t0 + s1 t1) + s2 t2.
+ * 5. Depth maps: R x R uint32 per view, empty = 0xffffffff.  Every non-degenerate triangle is drawn in every view from the
+ *    X, Y and (float)D of its three vertices by the rule of ppf_depth_register's triangles: x0 = ceil(min X), x1 = floor(max X),
+ *    y likewise, clamped to 0 .. R - 1, nothing when empty; area2 = (bx - ax)(cy - ay) - (by - ay)(cx - ax), nothing when it
+ *    is 0; a pixel (i, j) (X = i, Y = j) is covered iff w0 = (cx - bx)(j - by) - (cy - by)(i - bx), w1 = (ax - cx)(j - cy) -
+ *    (ay - cy)(i - cx), w2 = (bx - ax)(j - ay) - (by - ay)(i - ax) are all >= 0 or all <= 0; its value is
+ *    z = (float)(((w0 Da + w1 Db) + w2 Dc) / area2), stored as the unsigned minimum of the bit pattern of (z > 0 ? z : +0).
+ *    There is no pixel cap.
+ * 6. A row is tested with the float p and n it outputs.  Per view: fi = floor(X + 0.5), fj = floor(Y + 0.5); the row is
+ *    seen iff (fi, fj) is not a pixel of the map, the pixel is empty, or (double)(float)D <= (double)z + tol, tol =
+ *    depth_tol > 0 ? (double)depth_tol : 2.0 px.  seen counts those views, front those of them with dot(n, d) < 0, back
+ *    those with > 0.  The row is kept iff seen >= max(1, min_views).  With orient, a kept row with back > front has its
+ *    three normal components negated and is counted in n_flipped.
+ * 7. Kept rows leave in (k, j) order; curvature is 0.  n_sampled = sum n_k, n_hidden = n_sampled - n_rows.
+ *
+ * Checked in this order, all PPF_ERR_INVALID before any device work: out NULL (then *out = NULL); p NULL; vertices or
+ * triangles NULL; n_vertices < 1 or n_triangles < 1; vstride < 3; normal_offset other than -1 or 3 .. vstride - 3; spacing
+ * not finite or <= 0; normals not 0 or 1; PPF_MESH_NORMALS_VERTEX without a normal offset; visibility not 0 or 1; orient
+ * not 0 or 1; orient without visibility; map_size not 0 or 16 .. 1024; min_views outside 0 .. 26; depth_tol not finite or
+ * < 0; max_rows < 0; reserved != 0; with visibility, 26 n_triangles >= 2^32; the first triangle with an index outside
+ * [0, n_vertices).  Then, for a mesh of at most PPF_MESH_HOST_COUNT triangles, the rows are counted on the host and more
+ * than max_rows is PPF_ERR_CAPACITY; then PPF_ERR_HIP without a device; larger meshes are counted on the device
+ * (PPF_ERR_CAPACITY after the first wait).  Host arrays in, a device-resident cloud out (release it with ppf_cloud_release),
+ * which holds the memory of n_sampled rows.  On the null stream; two threads may call at once.  8 launches without
+ * visibility, 17 with it, and two blocking waits whatever the mesh holds.  On any error *out is NULL and *stats is zero. */
+#define PPF_MESH_NORMALS_FACE 0
+#define PPF_MESH_NORMALS_VERTEX 1
+#define PPF_MESH_VIEWS 26
+#define PPF_MESH_HOST_COUNT 1024
+typedef struct ppf_mesh_sample_params {
+  float spacing;      /* metres, > 0: on average one row per spacing^2 of surface; default 0.004 */
+  uint32_t seed;      /* default 0 */
+  int32_t normals;    /* PPF_MESH_NORMALS_FACE | PPF_MESH_NORMALS_VERTEX (needs normal_offset >= 0); default FACE */
+  int32_t visibility; /* 0: every sampled row; 1: only rows some view can see; default 1 */
+  int32_t map_size;   /* R, side of a view's depth map; 0 = 256; 16..1024 */
+  int32_t min_views;  /* 0 = 1; 1..26 */
+  float depth_tol;    /* metres; 0 = two map pixels */
+  int32_t orient;     /* 1: a row seen more often from behind has its normal negated (needs visibility); default 1 */
+  int32_t max_rows;   /* 0 = 1 << 24; more sampled rows than this is PPF_ERR_CAPACITY before any row is made */
+  int32_t reserved[4];
+} ppf_mesh_sample_params;
+typedef struct ppf_mesh_sample_stats {
+  int64_t n_triangles;
+  int64_t n_degenerate;
+  int64_t n_sampled;
+  int64_t n_hidden;
+  int64_t n_flipped;
+  int64_t n_rows;
+  int64_t n_large;      /* triangle-view pairs drawn by the large path: a non-empty clamped box of more than 16 pixels a
+                           side and area2 != 0 */
+  int32_t n_launches;
+  int32_t n_host_syncs;
+  double area;          /* the mesh's surface, exempt from byte parity: its summation order is free */
+  int32_t reserved[4];
+} ppf_mesh_sample_stats;
+void ppf_default_mesh_sample_params(ppf_mesh_sample_params* p);
+ppf_status ppf_cloud_from_mesh(const float* vertices, int n_vertices, int vstride, int normal_offset /* -1: none */,
+                               const int32_t* triangles, int n_triangles, const ppf_mesh_sample_params* p, ppf_cloud** out,
+                               ppf_mesh_sample_stats* stats /* may be NULL */);
+
 /* ---- a depth image's surfaces labelled in image space: proposals without leaving the image ----------- */
 #define PPF_SEGMENT_EIGHT 1      /* flags: 8-connectivity instead of 4 */
 #define PPF_SEGMENT_UNORIENTED 2 /* flags: normals agree on |dot|, as PPF_REGION_UNORIENTED */

@@ -246,6 +246,21 @@ class DepthVolumeExtractStats(C.Structure):
 PPF_VOLUME_MAX_DIM, PPF_VOLUME_MAX_WEIGHT, PPF_VOLUME_MAX_STEPS, PPF_VOLUME_MAX_TILES = 1024, 65535, 4096, 16777215
 
 
+class MeshSampleParams(C.Structure):
+    _fields_ = [("spacing", C.c_float), ("seed", C.c_uint32), ("normals", C.c_int32), ("visibility", C.c_int32), ("map_size", C.c_int32),
+                ("min_views", C.c_int32), ("depth_tol", C.c_float), ("orient", C.c_int32), ("max_rows", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class MeshSampleStats(C.Structure):
+    _fields_ = [("n_triangles", C.c_int64), ("n_degenerate", C.c_int64), ("n_sampled", C.c_int64), ("n_hidden", C.c_int64),
+                ("n_flipped", C.c_int64), ("n_rows", C.c_int64), ("n_large", C.c_int64), ("n_launches", C.c_int32),
+                ("n_host_syncs", C.c_int32), ("area", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+PPF_MESH_NORMALS_FACE, PPF_MESH_NORMALS_VERTEX, PPF_MESH_VIEWS, PPF_MESH_HOST_COUNT = 0, 1, 26, 1024
+
+
 class SegmentParams(C.Structure):
     _fields_ = [("depth_abs", C.c_float), ("depth_quad", C.c_float), ("normal_cos", C.c_float), ("curvature_threshold", C.c_float),
                 ("min_size", C.c_int32), ("max_size", C.c_int32), ("max_segments", C.c_int32), ("flags", C.c_int32),
@@ -571,6 +586,9 @@ _SIGNATURES = {
                                                   C.POINTER(DepthVolumeRaycastStats)]),
     "ppf_depth_volume_extract": (C.c_int, [C.c_void_p, C.POINTER(DepthVolumeExtractParams), C.POINTER(C.c_void_p),
                                            C.POINTER(DepthVolumeExtractStats)]),
+    "ppf_default_mesh_sample_params": (None, [C.POINTER(MeshSampleParams)]),
+    "ppf_cloud_from_mesh": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(MeshSampleParams),
+                                      C.POINTER(C.c_void_p), C.POINTER(MeshSampleStats)]),
     "ppf_default_segment_params": (None, [C.POINTER(SegmentParams)]),
     "ppf_depth_segments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(DepthParams), C.c_void_p,
                                      C.POINTER(SegmentParams), C.c_void_p, C.POINTER(SegmentInfo), C.POINTER(C.c_int32),

@@ -83,6 +83,36 @@ class DeviceCloud:
             check(getattr(lib(), name)(inp.ptr, inp.rows, inp.cols, inp.pitch, it, C.byref(prm), *tail, C.byref(out)))
         return cls(out)
 
+    @classmethod
+    def from_mesh(cls, vertices, triangles, spacing: float, *, seed: int = 0, normals: str = "face", visibility: bool = True,
+                  orient: bool = True, map_size: int = 0, min_views: int = 0, depth_tol: float = 0.0, max_rows: int = 0,
+                  return_stats: bool = False, normal_offset: Optional[int] = None):
+        """A model cloud sampled from a triangle mesh (ppf_cloud_from_mesh): on average one row per
+        spacing^2 of surface, rows ``x y z nx ny nz``.  vertices: (N, 3) float32, or (N, >= 6) with the vertex normals in
+        the last three columns (or at column normal_offset); triangles: (M, 3) int32.  normals: "face", or "vertex" to interpolate the vertex normals.
+        visibility: drop the rows none of 26 orthographic views of map_size^2 pixels (0: 256) can see -- inner walls, double
+        shells -- keeping those seen by at least min_views (0: 1) within depth_tol metres (0: two map pixels); orient: turn
+        a normal that more views see from behind, which mends inconsistent winding.  More than max_rows (0: 2^24) sampled
+        rows is PPF_ERR_CAPACITY.  The rows depend on the arguments alone: a seed names a cloud."""
+        V = np.ascontiguousarray(vertices, dtype=np.float32)
+        T = np.ascontiguousarray(triangles, dtype=np.int32)
+        if V.ndim != 2 or T.ndim != 2 or T.shape[1] != 3:
+            raise PPFError(_capi.PPF_ERR_INVALID, "from_mesh: vertices must be (N, 3 | >= 6) float32 and triangles (M, 3) int32")
+        if normals not in ("face", "vertex"):
+            raise PPFError(_capi.PPF_ERR_INVALID, f"from_mesh: normals must be 'face' or 'vertex', not {normals!r}")
+        prm = _capi.MeshSampleParams()
+        lib().ppf_default_mesh_sample_params(C.byref(prm))
+        prm.spacing, prm.seed = float(spacing), int(seed) & 0xFFFFFFFF
+        prm.normals = _capi.PPF_MESH_NORMALS_VERTEX if normals == "vertex" else _capi.PPF_MESH_NORMALS_FACE
+        prm.visibility, prm.orient = int(bool(visibility)), int(bool(orient))
+        prm.map_size, prm.min_views, prm.depth_tol, prm.max_rows = int(map_size), int(min_views), float(depth_tol), int(max_rows)
+        noff = int(normal_offset) if normal_offset is not None else (V.shape[1] - 3 if V.shape[1] >= 6 else -1)
+        out, st = C.c_void_p(), _capi.MeshSampleStats()
+        check(lib().ppf_cloud_from_mesh(V.ctypes.data, V.shape[0], V.shape[1], noff,
+                                        T.ctypes.data, T.shape[0], C.byref(prm), C.byref(out), C.byref(st)))
+        cloud = cls(out)
+        return (cloud, _capi.stats_dict(st)) if return_stats else cloud
+
     def __del__(self):
         try:
             if self._ptr:
@@ -1668,6 +1698,27 @@ class CloudProcessor:
         self.if_trained.append(False)
         self.label_to_id[label], self.id_to_label[idx] = idx, label
         self.detectors.append(PPF3DDetector(self.relativeSamplingStep, self.relativeDistanceStep))
+
+    def LoadMeshModel(self, mesh_or_path, label: str, spacing: Optional[float] = None, **kw):
+        """A model from a triangle mesh: a PLY path (``ply.load_ply_mesh``) or (vertices, triangles), sampled by
+        ``DeviceCloud.from_mesh(vertices, triangles, spacing, **kw)`` and stored as LoadSingleModel stores rows.  spacing
+        None: half the voxel the trainer will sample with, 0.5 x relativeSamplingStep x the diagonal of the vertices' box.
+        Returns the sampling's stats."""
+        if isinstance(mesh_or_path, (str, bytes)) or hasattr(mesh_or_path, "__fspath__"):
+            from .ply import load_ply_mesh
+            vertices, triangles = load_ply_mesh(mesh_or_path)
+        else:
+            vertices, triangles = mesh_or_path
+        vertices = np.ascontiguousarray(vertices, dtype=np.float32)
+        if spacing is None:
+            if vertices.ndim != 2 or vertices.shape[0] < 1 or vertices.shape[1] < 3:
+                raise PPFError(_capi.PPF_ERR_INVALID, "LoadMeshModel: vertices must be (N, 3 | >= 6) float32")
+            xyz = vertices[:, :3].astype(np.float64)
+            spacing = 0.5 * self.relativeSamplingStep * float(np.linalg.norm(xyz.max(axis=0) - xyz.min(axis=0)))
+        kw.pop("return_stats", None)
+        cloud, stats = DeviceCloud.from_mesh(vertices, triangles, spacing, return_stats=True, **kw)
+        self.LoadSingleModel(cloud.rows(), label)
+        return stats
 
     def TrainDetector(self, relativeSamplingStep_train: float = 0.025, relativeDistanceStep_train: float = 0.5):
         for i, model in enumerate(self.models):
