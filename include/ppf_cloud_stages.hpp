@@ -744,6 +744,16 @@ class DepthOdometry {
   std::vector<float> prev_;
 };
 
+/* what DepthVolume::mesh returns (ppf_depth_volume_mesh): vertices are rows x y z nx ny nz in world coordinates (a
+ * normal of 0 0 0 where the volume gives none), triangles three vertex indices each, counter-clockwise seen from free space:
+ * what Cloud::fromMesh(&vertices[0], nVertices(), 6, 3, &triangles[0], nTriangles(), ...) takes. */
+struct VolumeMesh {
+  std::vector<float> vertices;
+  std::vector<int32_t> triangles;
+  int nVertices() const { return (int)(vertices.size() / 6); }
+  int nTriangles() const { return (int)(triangles.size() / 3); }
+};
+
 /* ppf_depth_volume: a truncated signed distance volume on the device that posed depth images are fused into.
  * A pose is 16 doubles, row-major, world -> camera, as DepthOdometry::pose() is; intr = {fx, fy, ppx, ppy}.  integrate adds a
  * frame seen from a pose; raycast gives the volume's float32 depth image (0 where no surface is hit) from any pose, which
@@ -806,6 +816,27 @@ class DepthVolume {
     const ppf_depth_volume_desc d = info();
     std::vector<ppf_depth_volume_voxel> out((size_t)d.dims[0] * (size_t)d.dims[1] * (size_t)d.dims[2]);
     ppf_match_3d::check(ppf_depth_volume_read(need(), &out[0], out.size()));
+    return out;
+  }
+  /* the inverse of read: nx * ny * nz records replace every voxel (w in 0 .. max_weight, d finite in [-1, 1]) */
+  void write(const std::vector<ppf_depth_volume_voxel>& records) {
+    ppf_match_3d::check(ppf_depth_volume_write(need(), records.empty() ? 0 : &records[0], records.size()));
+  }
+  /* the zero surface as a triangle mesh by marching tetrahedra, downloaded */
+  VolumeMesh mesh(int minWeight = 1, ppf_depth_volume_mesh_stats* stats = 0) const {
+    ppf_depth_volume_mesh_params mp;
+    ppf_default_depth_volume_mesh_params(&mp);
+    mp.min_weight = minWeight;
+    ppf_volume_mesh* m = nullptr;
+    ppf_match_3d::check(ppf_depth_volume_mesh(need(), &mp, &m, stats));
+    std::shared_ptr<ppf_volume_mesh> hold(m, [](ppf_volume_mesh* p) { ppf_volume_mesh_release(p); });
+    ppf_volume_mesh_desc d;
+    ppf_match_3d::check(ppf_volume_mesh_info(m, &d));
+    VolumeMesh out;
+    out.vertices.resize((size_t)d.n_vertices * 6);
+    out.triangles.resize((size_t)d.n_triangles * 3);
+    ppf_match_3d::check(ppf_volume_mesh_read(m, out.vertices.empty() ? 0 : &out.vertices[0], (size_t)d.n_vertices,
+                                             out.triangles.empty() ? 0 : &out.triangles[0], (size_t)d.n_triangles));
     return out;
   }
 

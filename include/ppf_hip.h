@@ -1092,6 +1092,75 @@ ppf_status ppf_depth_volume_raycast_device(ppf_depth_volume* v, int rows, int co
  * NULL and *stats is zero. */
 ppf_status ppf_depth_volume_extract(ppf_depth_volume* v, const ppf_depth_volume_extract_params* ep, ppf_cloud** out,
                                     ppf_depth_volume_extract_stats* stats /* may be NULL */);
+/* The inverse of _read: nx * ny * nz records from HOST memory in linear order replace the volume's, a plain blocking copy
+ * under the volume's lock: a saved scan restored, or a chosen state for a test.  Checked on the host in this order, all
+ * PPF_ERR_INVALID before any device work: v NULL; in NULL; n_voxels != nx * ny * nz; the first record with w outside
+ * 0 .. max_weight or with d not finite or outside [-1, 1] (the message names its linear index).  Then PPF_ERR_HIP without a
+ * device.  On any error the volume keeps its bytes; integrations is not changed by a write. */
+ppf_status ppf_depth_volume_write(ppf_depth_volume* v, const ppf_depth_volume_voxel* in, size_t n_voxels);
+
+/* ---- the volume's zero surface as a triangle mesh, by marching tetrahedra ------------------------------ */
+typedef struct ppf_depth_volume_mesh_params {
+  int32_t min_weight; /* >= 1; default 1 */
+  int32_t flags;      /* 0 */
+  int32_t reserved[4];
+} ppf_depth_volume_mesh_params;
+typedef struct ppf_depth_volume_mesh_stats {
+  int64_t n_cells;      /* active cubes */
+  int64_t n_vertices;
+  int64_t n_triangles;
+  int64_t n_no_normal;  /* vertices whose normal is 0 0 0 */
+  int32_t n_launches;   /* 14 */
+  int32_t n_host_syncs; /* 2: the read-back that sizes the mesh, and the end */
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_depth_volume_mesh_stats;
+typedef struct ppf_volume_mesh ppf_volume_mesh; /* vertices and triangles, resident on the device */
+typedef struct ppf_volume_mesh_desc {
+  int64_t n_vertices;
+  int64_t n_triangles;
+  uint64_t device_bytes;
+  int32_t reserved[4];
+} ppf_volume_mesh_desc;
+/* min_weight 1, flags 0 */
+void ppf_default_depth_volume_mesh_params(ppf_depth_volume_mesh_params* p);
+/* MESH.  Everything is fp64 as written, left to right, nothing fused.  A voxel is valid iff w >= min_weight and
+ * fabs((double)d) < 1, and positive iff (double)d > 0.  A cube is (i, j, k) with 0 <= i < nx - 1, 0 <= j < ny - 1,
+ * 0 <= k < nz - 1 (a volume with a dimension of 1 has none); its corner c in 0..7 is the voxel
+ * (i + (c & 1), j + ((c >> 1) & 1), k + ((c >> 2) & 1)).  A cube is active iff all eight corners are valid; only active cubes
+ * give triangles.
+ *   Each cube has six tetrahedra, the monotone paths 0 -> 7 of the axis permutations in lexicographic order; corners
+ *   (t0, t1, t2, t3): (0,1,3,7) (0,1,5,7) (0,2,3,7) (0,2,6,7) (0,4,5,7) (0,4,6,7).
+ *   In a tetrahedron P is the set of positive corners and N the rest, both in path order.  |P| of 0 or 4 gives nothing.  A lone
+ *   corner a (|P| = 1 or |N| = 1) with the others b1, b2, b3 gives one triangle (E(a,b1), E(a,b2), E(a,b3)).  N = {a1, a2} and
+ *   P = {b1, b2} give two, in this order: (E(a1,b1), E(a1,b2), E(a2,b2)) and (E(a1,b1), E(a2,b2), E(a2,b1)).
+ *   Orientation: with every E at its edge's midpoint in the unit cube and m = mean of the P corners - mean of the N corners,
+ *   v1 and v2 are swapped when ((v1 - v0) x (v2 - v0)) . m < 0 (it is never 0: the midpoint surface is the zero set of the
+ *   affine function that is +1 on P and -1 on N).  Triangles are counter-clockwise seen from the free-space side.
+ *   E(ca, cb), the bits of ca inside those of cb, lies on the edge owned by the voxel at corner ca; the edge's type is
+ *   e = (ca ^ cb) - 1: 0 x, 1 y, 2 xy, 3 z, 4 xz, 5 yz, 6 xyz.  The vertex (p, e) exists iff a triangle names it, which is
+ *   exactly when the edge's two end voxels differ in `positive` and at least one active cube contains the edge.
+ *   With d0 = (double)d(p), d1 = (double)d of the other end and t = d0 / (d0 - d1), the position is the centre of p with
+ *   t * voxel added to every axis the direction has a 1 in, and the normal is EXTRACT's: g = g(p) + t * (g(end) - g(p)) from
+ *   the lattice gradients (six neighbours inside the volume with w >= min_weight), len = sqrt((g0 g0 + g1 g1) + g2 g2), g / len;
+ *   0 0 0 when either gradient is undefined or len is not > 0, counted in n_no_normal.
+ * Vertices are rows x y z nx ny nz as floats in world coordinates, in (owner's linear voxel index, type) order; triangles are
+ * three int32 vertex indices each, in (cube's corner-0 linear voxel index, tetrahedron, triangle) order.  No atomic decides a
+ * place.
+ *
+ * Checked in this order: out NULL (otherwise *out = NULL); v; mp NULL; min_weight < 1; flags != 0 (PPF_ERR_INVALID), then
+ * PPF_ERR_HIP without a device.  More than INT32_MAX vertices or triangles is PPF_ERR_NOMEM, decided by 64-bit counts.
+ * Fourteen launches and two blocking waits (the read-back that sizes the mesh, and the end) whatever the volume holds.  On any
+ * error *out is NULL and *stats is zero.  An empty result is a valid mesh of 0 vertices and 0 triangles. */
+ppf_status ppf_depth_volume_mesh(ppf_depth_volume* v, const ppf_depth_volume_mesh_params* mp, ppf_volume_mesh** out,
+                                 ppf_depth_volume_mesh_stats* stats /* may be NULL */);
+/* the counts and the device memory held; m or info NULL is PPF_ERR_INVALID */
+ppf_status ppf_volume_mesh_info(const ppf_volume_mesh* m, ppf_volume_mesh_desc* info);
+/* vertices (n_vertices x 6 floats) and triangles (n_triangles x 3 int32) to HOST memory: plain blocking copies.  Checked in
+ * this order, PPF_ERR_INVALID: m NULL; the counts are not the mesh's; vertices NULL with n_vertices > 0; triangles NULL with
+ * n_triangles > 0.  An empty mesh accepts NULL pointers. */
+ppf_status ppf_volume_mesh_read(const ppf_volume_mesh* m, float* vertices, size_t n_vertices, int32_t* triangles, size_t n_triangles);
+ppf_status ppf_volume_mesh_release(ppf_volume_mesh* m);
 
 /* ---- a model cloud sampled from a triangle mesh ------------------------------------------------------
  * The CAD side of "where does the model come from": rows x y z nx ny nz drawn on the surface of a triangle mesh, one per

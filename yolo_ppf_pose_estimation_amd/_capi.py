@@ -243,6 +243,19 @@ class DepthVolumeExtractStats(C.Structure):
                 ("ms_wall", C.c_float), ("reserved", C.c_int32 * 4)]
 
 
+class DepthVolumeMeshParams(C.Structure):
+    _fields_ = [("min_weight", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class DepthVolumeMeshStats(C.Structure):
+    _fields_ = [("n_cells", C.c_int64), ("n_vertices", C.c_int64), ("n_triangles", C.c_int64), ("n_no_normal", C.c_int64),
+                ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32), ("ms_wall", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+class VolumeMeshDesc(C.Structure):
+    _fields_ = [("n_vertices", C.c_int64), ("n_triangles", C.c_int64), ("device_bytes", C.c_uint64), ("reserved", C.c_int32 * 4)]
+
+
 PPF_VOLUME_MAX_DIM, PPF_VOLUME_MAX_WEIGHT, PPF_VOLUME_MAX_STEPS, PPF_VOLUME_MAX_TILES = 1024, 65535, 4096, 16777215
 
 
@@ -586,6 +599,13 @@ _SIGNATURES = {
                                                   C.POINTER(DepthVolumeRaycastStats)]),
     "ppf_depth_volume_extract": (C.c_int, [C.c_void_p, C.POINTER(DepthVolumeExtractParams), C.POINTER(C.c_void_p),
                                            C.POINTER(DepthVolumeExtractStats)]),
+    "ppf_depth_volume_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ppf_default_depth_volume_mesh_params": (None, [C.POINTER(DepthVolumeMeshParams)]),
+    "ppf_depth_volume_mesh": (C.c_int, [C.c_void_p, C.POINTER(DepthVolumeMeshParams), C.POINTER(C.c_void_p),
+                                        C.POINTER(DepthVolumeMeshStats)]),
+    "ppf_volume_mesh_info": (C.c_int, [C.c_void_p, C.POINTER(VolumeMeshDesc)]),
+    "ppf_volume_mesh_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "ppf_volume_mesh_release": (C.c_int, [C.c_void_p]),
     "ppf_default_mesh_sample_params": (None, [C.POINTER(MeshSampleParams)]),
     "ppf_cloud_from_mesh": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(MeshSampleParams),
                                       C.POINTER(C.c_void_p), C.POINTER(MeshSampleStats)]),

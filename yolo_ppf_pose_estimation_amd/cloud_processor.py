@@ -1047,6 +1047,70 @@ class DepthVolume:
         return (cloud, _capi.stats_dict(st)) if return_stats else cloud
 
 
+    def write(self, d, w) -> None:
+        """The inverse of ``read``: d float32 and w int32 of shape (nz, ny, nx) (or flat, in linear order) replace every voxel
+        (ppf_depth_volume_write): a saved scan restored.  w must lie in 0 .. max_weight and d be finite in [-1, 1]."""
+        nx, ny, nz = self.dims
+        d, w = np.asarray(d), np.asarray(w)
+        if d.size != nx * ny * nz or w.size != d.size:
+            raise PPFError(_capi.PPF_ERR_INVALID, f"write takes d and w of {nx * ny * nz} voxels each")
+        rec = np.empty(d.size, VOLUME_VOXEL)
+        rec["d"], rec["w"] = d.reshape(-1), w.reshape(-1)
+        check(lib().ppf_depth_volume_write(self._ptr, rec.ctypes.data, rec.size))
+
+    def mesh(self, params=None, return_stats: bool = False):
+        """The zero surface as a ``VolumeMesh``: a triangle mesh by marching tetrahedra over the cubes whose eight voxels are
+        all observed and unsaturated (ppf_depth_volume_mesh).  params: a DepthVolumeMeshParams, a dict
+        (min_weight) or None."""
+        prm = _params(_capi.DepthVolumeMeshParams, "ppf_default_depth_volume_mesh_params", params, "depth volume mesh")
+        out, st = C.c_void_p(), _capi.DepthVolumeMeshStats()
+        check(lib().ppf_depth_volume_mesh(self._ptr, C.byref(prm), C.byref(out), C.byref(st)))
+        m = VolumeMesh(out)
+        return (m, _capi.stats_dict(st)) if return_stats else m
+
+
+class VolumeMesh:
+    """The triangle mesh ``DepthVolume.mesh`` made, resident on the device (ppf_volume_mesh): vertices are rows
+    x y z nx ny nz in world coordinates, triangles three vertex indices each, counter-clockwise seen from free space."""
+
+    def __init__(self, ptr):
+        self._ptr = ptr
+        d = _capi.VolumeMeshDesc()
+        check(lib().ppf_volume_mesh_info(self._ptr, C.byref(d)))
+        self.n_vertices, self.n_triangles, self.device_bytes = int(d.n_vertices), int(d.n_triangles), int(d.device_bytes)
+        self._host = None
+
+    def __del__(self):
+        try:
+            if self._ptr is not None:
+                lib().ppf_volume_mesh_release(self._ptr)
+                self._ptr = None
+        except Exception:
+            pass
+
+    def _read(self):
+        if self._host is None:
+            v, t = np.empty((self.n_vertices, 6), np.float32), np.empty((self.n_triangles, 3), np.int32)
+            check(lib().ppf_volume_mesh_read(self._ptr, v.ctypes.data if v.size else None, self.n_vertices,
+                                             t.ctypes.data if t.size else None, self.n_triangles))
+            self._host = (v, t)
+        return self._host
+
+    def vertices(self) -> np.ndarray:
+        """(N, 6) float32: x y z nx ny nz; a normal of 0 0 0 where the volume gives none"""
+        return self._read()[0].copy()
+
+    def triangles(self) -> np.ndarray:
+        """(M, 3) int32 vertex indices"""
+        return self._read()[1].copy()
+
+    def save_ply(self, path) -> None:
+        """an ASCII PLY that ``ply.load_ply_mesh`` and ``CloudProcessor.LoadMeshModel`` read"""
+        from .ply import write_ply_mesh
+        v, t = self._read()
+        write_ply_mesh(v, t, path)
+
+
 class DepthFusion:
     """Frame-to-model camera tracking and fusion: every pushed frame is aligned to the image ``volume`` gives from the current
     ``pose`` (``depth_motion(prev = raycast, cur = frame)``), which does not accumulate drift as ``DepthOdometry``'s chain does,
@@ -1649,6 +1713,20 @@ class CloudProcessor:
                     _pose_premultiply(p, T)
         self.camera_motion, self.camera_pose = T, f.pose.copy()
         return T, status
+
+    def MeshVolume(self, path=None) -> "VolumeMesh":
+        """The triangle mesh of the volume ``FuseVolume`` has filled (``DepthVolume.mesh``), written to ``path``
+        as a PLY when a path is given.  A scan is an open surface: give ``LoadMeshModel(path, label, normals="vertex",
+        orient=False)`` so that the normals seen through the open back are not flipped.  Refused before the first
+        ``FuseVolume``."""
+        if self._depth_fusion is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "MeshVolume: there is no volume yet; call FuseVolume first")
+        t0 = time.perf_counter()
+        m = self._depth_fusion.volume.mesh()
+        if path is not None:
+            m.save_ply(path)
+        self.timings["mesh_volume"] = time.perf_counter() - t0
+        return m
 
     def _match_frame(self, labels, step, dist, top: int = 5) -> List[Optional[Pose3D]]:
         dets = (FrameDetection * max(len(labels), 1))()

@@ -26,7 +26,7 @@
  *             ppf_depth_kernels.h  ppf_depth_normals_kernels.h  ppf_verify_kernels.h  ppf_render_kernels.h  ppf_select_kernels.h  ppf_refine_kernels.h
  *             ppf_register_kernels.h  ppf_plane_kernels.h  ppf_label_kernels.h  ppf_cluster_kernels.h  ppf_region_kernels.h  ppf_filter_kernels.h
  *             ppf_segment_kernels.h  ppf_recognize_kernels.h  ppf_history_kernels.h  ppf_motion_kernels.h
- *             ppf_volume_kernels.h  ppf_mesh_kernels.h
+ *             ppf_volume_kernels.h  ppf_volume_mesh_kernels.h  ppf_mesh_kernels.h
  *   host      ppf_device_mem.h (errors, block cache)  ppf_host_common.h (scans, sorts, model / workspace structs)
  *             ppf_model_host.h  ppf_match_host.h  ppf_batch_host.h  ppf_icp_host.h  ppf_prep_host.h (the segmented
  *             preparation stages; ppf_prep_* = one segment)  ppf_frame_host.h (ppf_prep_frame = their chain)
@@ -76,6 +76,7 @@
 #include "ppf_refine_kernels.h" /* k_rfn_refine */
 #include "ppf_motion_kernels.h" /* k_motion_level0, k_motion_down, k_motion_maps, k_motion_eval, k_motion_group, k_motion_tail */
 #include "ppf_volume_kernels.h" /* k_volume_fill, k_volume_integrate, k_volume_raycast, k_volume_cross */
+#include "ppf_volume_mesh_kernels.h" /* k_vmesh_cells, k_vmesh_edges, k_vmesh_vertices, k_vmesh_triangles */
 #include "ppf_mesh_kernels.h" /* k_mesh_tri, k_mesh_area, k_mesh_sample, k_mesh_draw_small / _large, k_mesh_visible, k_mesh_scatter */
 #include "ppf_register_kernels.h" /* k_reg_rays, k_reg_clear, k_reg_draw, k_reg_resolve */
 #include "ppf_plane_kernels.h" /* k_pln_hyp, k_pln_count, k_pln_best, k_pln_sum / _finish, k_pln_flags, k_pln_compact, k_pln_gather */
@@ -107,7 +108,7 @@
 #include "ppf_filter_host.h"      /* a depth image without flying pixels, smoothed inside each surface: ppf_depth_filter */
 #include "ppf_history_host.h"     /* a camera's last frames fused into one depth image: ppf_depth_history_* */
 #include "ppf_motion_host.h"      /* the camera's motion between two depth images: ppf_depth_motion */
-#include "ppf_volume_host.h"      /* posed depth images fused into a TSDF volume: ppf_depth_volume_* */
+#include "ppf_volume_host.h"      /* posed depth images fused into a TSDF volume: ppf_depth_volume_*, ppf_volume_mesh_* */
 #include "ppf_mesh_host.h"        /* a model cloud sampled from a triangle mesh: ppf_cloud_from_mesh */
 #include "ppf_segment_host.h"     /* a depth image's surfaces labelled in image space: ppf_depth_segments */
 #include "ppf_recognize_host.h"   /* which trained models a proposal can be a view of: ppf_recognizer_*, ppf_recognize_frame */

@@ -8,6 +8,9 @@
  *   raycast    an 8-byte clear of the counters, k_volume_raycast -- one launch -- and one blocking wait.
  *   extract    k_volume_cross<0>, the five launches of frame_scan, k_volume_cross<1> -- seven launches -- and two blocking
  *              waits: the read-back that sizes the cloud, and the end.
+ *   mesh       a 32-byte clear of the counters, k_vmesh_cells, k_vmesh_edges, two frame_scans, k_vmesh_vertices,
+ *              k_vmesh_triangles (ppf_volume_mesh_kernels.h) -- fourteen launches -- and two blocking waits: the read-back
+ *              that sizes the mesh, and the end.
  * whatever the images and the volume hold.  The host entries add the upload of the image or the read-back of the outputs
  * behind the same wait.  The volume and its counters belong to the handle, whose mutex serialises every call on it.
  */
@@ -21,6 +24,13 @@ struct ppf_depth_volume {
   std::mutex mu;
   DevBuf<VolVoxel> vox;
   DevBuf<unsigned long long> counters; /* 2: [0] n_updated or the crossings; as int32: n_hits, n_interpolated */
+};
+
+/* vertices (rows x y z nx ny nz) and triangles (three vertex indices each), resident on the device */
+struct ppf_volume_mesh {
+  int64_t nv = 0, nt = 0;
+  DevBuf<float> verts;
+  DevBuf<int32_t> tris;
 };
 
 namespace {
@@ -292,6 +302,72 @@ ppf_status volume_extract(const char* who, ppf_depth_volume* v, const ppf_depth_
   return PPF_OK;
 }
 
+/* ---- mesh ---------------------------------------------------------------------------------------------------------- */
+ppf_status volume_mesh(const char* who, ppf_depth_volume* v, const ppf_depth_volume_mesh_params* mp, ppf_volume_mesh** out,
+                       ppf_depth_volume_mesh_stats& st) {
+  if (!out) return fail(PPF_ERR_INVALID, "%s: out is NULL", who);
+  *out = nullptr;
+  if (!v) return fail(PPF_ERR_INVALID, "%s: the volume is NULL", who);
+  if (!mp) return fail(PPF_ERR_INVALID, "%s: the mesh params are NULL", who);
+  if (mp->min_weight < 1) return fail(PPF_ERR_INVALID, "%s: min_weight must be >= 1", who);
+  if (mp->flags != 0) return fail(PPF_ERR_INVALID, "%s: unknown mesh flags 0x%x", who, (unsigned)mp->flags);
+  ppf_status s;
+  if ((s = volume_device(who, v)) != PPF_OK) return s;
+  std::lock_guard<std::mutex> lock(v->mu);
+  const VolArgs V = volume_args(v);
+  const uint32_t n_tiles = (uint32_t)((v->n + VM_BLOCK - 1) / VM_BLOCK); /* at most 2^22 */
+  FrameRun fr;
+  uint32_t *tcnt, *toff, *vcnt, *voff;
+  uint8_t *cell, *mask; /* 1 + 1 + 2 = 4 bytes of scratch per voxel */
+  uint16_t* rank;
+  unsigned long long* ctr;
+  if ((s = fr.get((size_t)n_tiles + 1, &tcnt)) != PPF_OK || (s = fr.get((size_t)n_tiles + 1, &toff)) != PPF_OK ||
+      (s = fr.get((size_t)n_tiles + 1, &vcnt)) != PPF_OK || (s = fr.get((size_t)n_tiles + 1, &voff)) != PPF_OK ||
+      (s = fr.get(v->n, &cell)) != PPF_OK || (s = fr.get(v->n, &mask)) != PPF_OK || (s = fr.get(v->n, &rank)) != PPF_OK ||
+      (s = fr.get((size_t)VM_COUNTERS, &ctr)) != PPF_OK)
+    return s;
+  std::unique_ptr<ppf_volume_mesh> m(new (std::nothrow) ppf_volume_mesh());
+  if (!m) return fail(PPF_ERR_NOMEM, "%s: out of host memory", who);
+  unsigned long long c[VM_COUNTERS] = {0, 0, 0, 0};
+  auto run = [&]() -> ppf_status {
+    const dim3 grid(n_tiles), block(VM_BLOCK);
+    HIPCHK(hipMemsetAsync(ctr, 0, sizeof(c), fr.st));
+    FRAME_LAUNCH(fr, k_vmesh_cells, grid, block, V, mp->min_weight, v->n, n_tiles, cell, tcnt, ctr);
+    FRAME_LAUNCH(fr, k_vmesh_edges, grid, block, V, v->n, n_tiles, cell, mask, rank, vcnt, ctr);
+    HIPCHK(hipGetLastError());
+    ppf_status r;
+    if ((r = frame_scan(fr, tcnt, toff, (size_t)n_tiles + 1)) != PPF_OK || (r = frame_scan(fr, vcnt, voff, (size_t)n_tiles + 1)) != PPF_OK) return r;
+    HIPCHK(hipMemcpyAsync(c, ctr, sizeof(c), hipMemcpyDeviceToHost, fr.st));
+    HIPCHK(host_stream_sync(fr.st)); /* the sizing read-back */
+    fr.syncs++;
+    /* the 64-bit counts decide: a scan total that wrapped is never looked at */
+    if (c[VM_N_VERTICES] > 0x7fffffffull || c[VM_N_TRIANGLES] > 0x7fffffffull)
+      return fail(PPF_ERR_NOMEM, "%s: %llu vertices and %llu triangles exceed INT32_MAX, the most a mesh holds", who, c[VM_N_VERTICES],
+                  c[VM_N_TRIANGLES]);
+    m->nv = (int64_t)c[VM_N_VERTICES];
+    m->nt = (int64_t)c[VM_N_TRIANGLES];
+    if (m->verts.reserve((size_t)std::max<int64_t>(m->nv, 1) * 6) != hipSuccess || m->tris.reserve((size_t)std::max<int64_t>(m->nt, 1) * 3) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(PPF_ERR_NOMEM, "%s: a mesh of %lld vertices and %lld triangles cannot be allocated", who, (long long)m->nv, (long long)m->nt);
+    }
+    FRAME_LAUNCH(fr, k_vmesh_vertices, grid, block, V, mp->min_weight, v->n, mask, rank, voff, (uint32_t)m->nv, m->verts.p, ctr);
+    FRAME_LAUNCH(fr, k_vmesh_triangles, grid, block, V, v->n, cell, mask, rank, voff, toff, (uint32_t)m->nt, m->tris.p);
+    HIPCHK(hipGetLastError());
+    return PPF_OK;
+  };
+  s = depth_finish(who, run(), fr.st, {{"counters", ctr, sizeof(c), c}}); /* the end: the scratch goes back to the block cache at scope exit */
+  if (s != PPF_OK) return s;
+  fr.syncs++;
+  st.n_cells = (int64_t)c[VM_N_CELLS];
+  st.n_vertices = m->nv;
+  st.n_triangles = m->nt;
+  st.n_no_normal = (int64_t)c[VM_N_NO_NORMAL];
+  st.n_launches = fr.launches;
+  st.n_host_syncs = fr.syncs;
+  *out = m.release();
+  return PPF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -320,6 +396,13 @@ void ppf_default_depth_volume_raycast_params(ppf_depth_volume_raycast_params* p)
 }
 
 void ppf_default_depth_volume_extract_params(ppf_depth_volume_extract_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->min_weight = 1;
+  p->flags = 0;
+}
+
+void ppf_default_depth_volume_mesh_params(ppf_depth_volume_mesh_params* p) {
   if (!p) return;
   std::memset(p, 0, sizeof(*p));
   p->min_weight = 1;
@@ -422,6 +505,24 @@ ppf_status ppf_depth_volume_read(const ppf_depth_volume* v, ppf_depth_volume_vox
   return PPF_OK;
 }
 
+ppf_status ppf_depth_volume_write(ppf_depth_volume* v, const ppf_depth_volume_voxel* in, size_t n_voxels) {
+  static const char* who = "ppf_depth_volume_write";
+  if (!v) return fail(PPF_ERR_INVALID, "%s: the volume is NULL", who);
+  if (!in) return fail(PPF_ERR_INVALID, "%s: in is NULL", who);
+  if (n_voxels != v->n) return fail(PPF_ERR_INVALID, "%s: in holds %zu records, the volume has %zu voxels", who, n_voxels, v->n);
+  for (size_t q = 0; q < n_voxels; q++) {
+    const ppf_depth_volume_voxel& r = in[q];
+    if (r.w < 0 || r.w > v->vp.max_weight || !(std::isfinite(r.d) && r.d >= -1.f && r.d <= 1.f))
+      return fail(PPF_ERR_INVALID, "%s: record %zu has w = %d and d = %g: w must be in 0..%d and d finite in [-1, 1]", who, q, (int)r.w,
+                  (double)r.d, (int)v->vp.max_weight);
+  }
+  const ppf_status s = volume_device(who, v);
+  if (s != PPF_OK) return s;
+  std::lock_guard<std::mutex> lock(v->mu);
+  HIPCHK(hipMemcpy(v->vox.p, in, v->n * sizeof(VolVoxel), hipMemcpyHostToDevice));
+  return PPF_OK;
+}
+
 ppf_status ppf_depth_volume_integrate(ppf_depth_volume* v, const void* depth, int rows, int cols, size_t row_pitch_bytes, const double* intr,
                                       const ppf_depth_params* dp, const double* pose16, ppf_depth_volume_integrate_stats* stats) {
   return depth_entry(stats, depth_clear_stats<ppf_depth_volume_integrate_stats>, [&](ppf_depth_volume_integrate_stats& st) {
@@ -464,6 +565,44 @@ ppf_status ppf_depth_volume_extract(ppf_depth_volume* v, const ppf_depth_volume_
         if (failed && out) *out = nullptr;
       },
       [&](ppf_depth_volume_extract_stats& st) { return volume_extract("ppf_depth_volume_extract", v, ep, out, st); });
+}
+
+ppf_status ppf_depth_volume_mesh(ppf_depth_volume* v, const ppf_depth_volume_mesh_params* mp, ppf_volume_mesh** out,
+                                 ppf_depth_volume_mesh_stats* stats) {
+  return depth_entry(
+      stats,
+      [&](ppf_depth_volume_mesh_stats& st, bool failed) {
+        std::memset(&st, 0, sizeof(st));
+        if (failed && out) *out = nullptr;
+      },
+      [&](ppf_depth_volume_mesh_stats& st) { return volume_mesh("ppf_depth_volume_mesh", v, mp, out, st); });
+}
+
+ppf_status ppf_volume_mesh_info(const ppf_volume_mesh* m, ppf_volume_mesh_desc* info) {
+  if (info) std::memset(info, 0, sizeof(*info));
+  if (!m || !info) return fail(PPF_ERR_INVALID, "ppf_volume_mesh_info: the mesh and info must not be NULL");
+  info->n_vertices = m->nv;
+  info->n_triangles = m->nt;
+  info->device_bytes = m->verts.bytes() + m->tris.bytes();
+  return PPF_OK;
+}
+
+ppf_status ppf_volume_mesh_read(const ppf_volume_mesh* m, float* vertices, size_t n_vertices, int32_t* triangles, size_t n_triangles) {
+  static const char* who = "ppf_volume_mesh_read";
+  if (!m) return fail(PPF_ERR_INVALID, "%s: the mesh is NULL", who);
+  if (n_vertices != (size_t)m->nv || n_triangles != (size_t)m->nt)
+    return fail(PPF_ERR_INVALID, "%s: the buffers hold %zu vertices and %zu triangles, the mesh has %lld and %lld", who, n_vertices, n_triangles,
+                (long long)m->nv, (long long)m->nt);
+  if (n_vertices && !vertices) return fail(PPF_ERR_INVALID, "%s: vertices is NULL", who);
+  if (n_triangles && !triangles) return fail(PPF_ERR_INVALID, "%s: triangles is NULL", who);
+  if (n_vertices) HIPCHK(hipMemcpy(vertices, m->verts.p, n_vertices * 6 * sizeof(float), hipMemcpyDeviceToHost));
+  if (n_triangles) HIPCHK(hipMemcpy(triangles, m->tris.p, n_triangles * 3 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return PPF_OK;
+}
+
+ppf_status ppf_volume_mesh_release(ppf_volume_mesh* m) {
+  delete m; /* the call that made it has waited for its kernels: the buffers go back to the block cache */
+  return PPF_OK;
 }
 
 }  // extern "C"
