@@ -752,6 +752,69 @@ struct VolumeMesh {
   std::vector<int32_t> triangles;
   int nVertices() const { return (int)(vertices.size() / 6); }
   int nTriangles() const { return (int)(triangles.size() / 3); }
+
+  /* ppf_volume_mesh_components: the mesh's connected pieces ranked by area, and the mesh of those that are kept */
+  static ppf_mesh_component_params defaultComponentParams() {
+    ppf_mesh_component_params p;
+    ppf_default_mesh_component_params(&p);
+    return p;
+  }
+  /* a mesh from any arrays, checked as ppf_volume_mesh_upload checks them: rows of vstride floats that begin with x y z, the
+   * normal at normalOffset (-1: none, the rows get 0 0 0) */
+  static VolumeMesh fromArrays(const float* verts, int nVerts, int vstride, int normalOffset, const int32_t* tris, int nTris) {
+    ppf_volume_mesh* m = nullptr;
+    ppf_match_3d::check(ppf_volume_mesh_upload(verts, nVerts, vstride, normalOffset, tris, nTris, &m));
+    return download(m);
+  }
+  /* info: 0, or it receives the records of the maxInfo largest components, largest first; labels: 0, or it receives every
+   * vertex's rank (-1: no triangle names it).  This mesh is not changed */
+  VolumeMesh components(const ppf_mesh_component_params* params = 0, std::vector<ppf_mesh_component_info>* info = 0, int maxInfo = 64,
+                        std::vector<int32_t>* labels = 0, ppf_mesh_component_stats* stats = 0) const {
+    ppf_mesh_component_params cp;
+    if (params) cp = *params; else ppf_default_mesh_component_params(&cp);
+    ppf_volume_mesh* in = nullptr;
+    ppf_match_3d::check(ppf_volume_mesh_upload(vertices.empty() ? 0 : &vertices[0], nVertices(), 6, 3, triangles.empty() ? 0 : &triangles[0],
+                                               nTriangles(), &in));
+    std::shared_ptr<ppf_volume_mesh> hold(in, [](ppf_volume_mesh* p) { ppf_volume_mesh_release(p); });
+    const int cap = info && maxInfo > 0 ? maxInfo : 0;
+    std::vector<ppf_mesh_component_info> rec((size_t)cap + 1);
+    std::vector<int32_t> lab(labels ? (size_t)nVertices() + 1 : 1);
+    ppf_mesh_component_stats st;
+    ppf_volume_mesh* out = nullptr;
+    ppf_match_3d::check(ppf_volume_mesh_components(in, &cp, &out, labels ? &lab[0] : 0, cap ? &rec[0] : 0, cap, &st));
+    const VolumeMesh kept = download(out);
+    if (info) {
+      rec.resize((size_t)(st.n_components < cap ? st.n_components : cap));
+      info->swap(rec);
+    }
+    if (labels) {
+      lab.resize((size_t)nVertices());
+      labels->swap(lab);
+    }
+    if (stats) *stats = st;
+    return kept;
+  }
+  /* the k largest pieces among those of at least minTriangles triangles */
+  VolumeMesh largest(int k = 1, int minTriangles = 1, std::vector<ppf_mesh_component_info>* info = 0, ppf_mesh_component_stats* stats = 0) const {
+    ppf_mesh_component_params cp = defaultComponentParams();
+    cp.rank_hi = k;
+    cp.min_triangles = minTriangles;
+    return components(&cp, info, 64, 0, stats);
+  }
+
+ private:
+  /* the arrays of a device mesh, which is released */
+  static VolumeMesh download(ppf_volume_mesh* m) {
+    std::shared_ptr<ppf_volume_mesh> hold(m, [](ppf_volume_mesh* p) { ppf_volume_mesh_release(p); });
+    ppf_volume_mesh_desc d;
+    ppf_match_3d::check(ppf_volume_mesh_info(m, &d));
+    VolumeMesh out;
+    out.vertices.resize((size_t)d.n_vertices * 6);
+    out.triangles.resize((size_t)d.n_triangles * 3);
+    ppf_match_3d::check(ppf_volume_mesh_read(m, out.vertices.empty() ? 0 : &out.vertices[0], (size_t)d.n_vertices,
+                                             out.triangles.empty() ? 0 : &out.triangles[0], (size_t)d.n_triangles));
+    return out;
+  }
 };
 
 /* ppf_depth_volume: a truncated signed distance volume on the device that posed depth images are fused into.

@@ -1162,6 +1162,90 @@ ppf_status ppf_volume_mesh_info(const ppf_volume_mesh* m, ppf_volume_mesh_desc* 
 ppf_status ppf_volume_mesh_read(const ppf_volume_mesh* m, float* vertices, size_t n_vertices, int32_t* triangles, size_t n_triangles);
 ppf_status ppf_volume_mesh_release(ppf_volume_mesh* m);
 
+/* ---- a mesh's connected components: counted, measured, ranked by area, scraps removed ------------------- */
+typedef struct ppf_mesh_component_params {
+  int32_t min_triangles; /* >= 1; default 1 */
+  float min_area;        /* m^2, finite and >= 0; default 0 */
+  int32_t rank_lo;       /* >= 0; default 0 */
+  int32_t rank_hi;       /* >= rank_lo; default INT32_MAX */
+  int32_t flags;         /* 0 */
+  int32_t reserved[3];
+} ppf_mesh_component_params;
+typedef struct ppf_mesh_component_info {
+  int32_t n_vertices;
+  int32_t n_triangles;         /* degenerate ones included */
+  int32_t n_degenerate;
+  int32_t n_edges;             /* distinct edges of the non-degenerate triangles */
+  int32_t n_boundary_edges;    /* held by one triangle; 0: the component is closed */
+  int32_t n_nonmanifold_edges; /* held by more than two */
+  int32_t first_vertex;        /* the component's smallest vertex index */
+  int32_t kept;                /* 0 | 1 */
+  double area;                 /* m^2: area_q * 2^-40 */
+  float lo[3], hi[3];          /* the bounds of the vertex positions */
+  int32_t reserved[2];
+} ppf_mesh_component_info;
+typedef struct ppf_mesh_component_stats {
+  int64_t n_components;
+  int64_t n_kept;
+  int64_t n_unreferenced;  /* vertices that no triangle names */
+  int64_t n_bad_area;      /* triangles whose area has no integer form */
+  int64_t n_vertices_out;  /* of the output mesh, also when out is NULL */
+  int64_t n_triangles_out;
+  int32_t n_launches;      /* 82, or 80 when out is NULL */
+  int32_t n_host_syncs;    /* 2: the read-back that sizes the output, and the end */
+  float ms_wall;
+  int32_t reserved[5];
+} ppf_mesh_component_stats;
+
+/* A ppf_volume_mesh from HOST arrays, so that a loaded PLY can be cleaned and a test can state a mesh: n_vertices rows of
+ * vstride floats whose first three are x y z and whose floats normal_offset .. normal_offset + 2 are the normal (-1: no
+ * normals, the rows get 0 0 0), and n_triangles x 3 int32 vertex indices.  The mesh's rows are x y z nx ny nz, every float as
+ * given.  Checked on the host in this order, all PPF_ERR_INVALID with a message that names the first offender: out NULL
+ * (otherwise *out = NULL); a negative count, or one above INT32_MAX; vertices NULL with n_vertices > 0, triangles NULL with
+ * n_triangles > 0; vstride < 3, or normal_offset < -1 or normal_offset + 3 > vstride; the first row with a position that is not
+ * finite (its index is named); the first triangle with an index outside [0, n_vertices) (the triangle is named).  Then
+ * PPF_ERR_HIP without a device.  0 vertices and 0 triangles are a valid empty mesh and accept NULL pointers. */
+ppf_status ppf_volume_mesh_upload(const float* vertices, int64_t n_vertices, int32_t vstride, int32_t normal_offset,
+                                  const int32_t* triangles, int64_t n_triangles, ppf_volume_mesh** out);
+/* A test surface, like ppf_debug_depth_volume_shell: a handle that holds the counts and no device memory, made without asking
+ * for a device.  _info and _release take it; ppf_volume_mesh_components checks its arguments as on a real mesh and then is
+ * PPF_ERR_HIP without a device and PPF_ERR_INVALID with one. */
+ppf_status ppf_debug_volume_mesh_shell(int64_t n_vertices, int64_t n_triangles, ppf_volume_mesh** out);
+/* min_triangles 1, min_area 0, rank_lo 0, rank_hi INT32_MAX, flags 0: everything is kept */
+void ppf_default_mesh_component_params(ppf_mesh_component_params* p);
+/* COMPONENTS.  A triangle is degenerate when two of its three indices are equal.  A vertex is referenced when any triangle
+ * names it, degenerate ones included.  The components are the classes of the smallest equivalence on the referenced vertices in
+ * which every triangle's three vertices are equivalent; a triangle belongs to its vertices' component; first_vertex is the
+ * component's smallest vertex index.  An unreferenced vertex belongs to no component: its label is -1, it counts in
+ * n_unreferenced and never reaches the output.
+ *   Area.  Per triangle in fp64 exactly as written, nothing fused: a = (double)p1 - (double)p0 and b = (double)p2 - (double)p0
+ *   per axis, c = (ay*bz - az*by, az*bx - ax*bz, ax*by - ay*bx), A = 0.5 * sqrt((cx*cx + cy*cy) + cz*cz).  Its integer form is
+ *   q = (uint64)floor(A * 2^40); when A is not finite or A * 2^40 >= 2^63, q is 0 and the triangle counts in n_bad_area.  A
+ *   component's area_q is the sum of its triangles' q in uint64 (it wraps at 2^24 m^2), and area = (double)area_q * 2^-40.  The
+ *   sum is over integers so that it does not depend on the order and needs no float atomic.
+ *   Edges.  The edges of a non-degenerate triangle are the unordered pairs {i0,i1} {i1,i2} {i2,i0}; an edge's multiplicity is
+ *   the number of non-degenerate triangles that hold it.  n_edges counts the distinct edges, n_boundary_edges those of
+ *   multiplicity 1, n_nonmanifold_edges those above 2.  A component is closed iff n_boundary_edges == 0, and its Euler
+ *   characteristic is n_vertices - n_edges + n_triangles (without the degenerate ones, where there are any).
+ *   lo / hi.  The minima and maxima of the component's vertex positions as floats, -0 below +0.
+ *   Rank.  The components ordered by (area_q descending, first_vertex ascending) have the ranks 0 .. C - 1.
+ *   Kept.  A component is kept iff rank_lo <= rank < rank_hi, n_triangles >= min_triangles and area >= (double)min_area.
+ *   Output.  The kept components' vertex rows in input order, every byte unchanged, normals included; the kept triangles in
+ *   input order, each index replaced by the number of kept vertices before it.  No atomic decides a place.  With everything
+ *   kept and no unreferenced vertex the output equals the input byte for byte.
+ *   labels[v] is the rank of v's component, or -1.  info[r] describes the component of rank r, for r below min(C, cap_info);
+ *   the records from C on are left as they are.
+ *
+ * Checked in this order, PPF_ERR_INVALID: out, when given, gets *out = NULL; m NULL; p NULL; min_triangles < 1; min_area
+ * negative or not finite; rank_lo < 0; rank_hi < rank_lo; flags != 0; cap_info < 0; info NULL with cap_info > 0.  Then
+ * PPF_ERR_HIP without a device.  out NULL measures only: labels, info and stats are as with an output, the two passes that
+ * write it are not launched.  82 launches (80 with out NULL) and two blocking waits (the read-back that sizes the output, and
+ * the end) whatever the mesh holds.  The input mesh is never written.  On any error *out is NULL and *stats is zero.  Nothing
+ * kept is a valid mesh of 0 vertices and 0 triangles. */
+ppf_status ppf_volume_mesh_components(const ppf_volume_mesh* m, const ppf_mesh_component_params* p, ppf_volume_mesh** out /* NULL: measure only */,
+                                      int32_t* labels /* HOST, n_vertices; may be NULL */, ppf_mesh_component_info* info /* HOST, cap_info */,
+                                      int cap_info, ppf_mesh_component_stats* stats /* may be NULL */);
+
 /* ---- a model cloud sampled from a triangle mesh ------------------------------------------------------
  * The CAD side of "where does the model come from": rows x y z nx ny nz drawn on the surface of a triangle mesh, one per
  * spacing^2 on average, without the faces no camera can see and with the normals turned outward.  Everything below is evaluated

@@ -256,6 +256,23 @@ class VolumeMeshDesc(C.Structure):
     _fields_ = [("n_vertices", C.c_int64), ("n_triangles", C.c_int64), ("device_bytes", C.c_uint64), ("reserved", C.c_int32 * 4)]
 
 
+class MeshComponentParams(C.Structure):
+    _fields_ = [("min_triangles", C.c_int32), ("min_area", C.c_float), ("rank_lo", C.c_int32), ("rank_hi", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class MeshComponentInfo(C.Structure):
+    _fields_ = [("n_vertices", C.c_int32), ("n_triangles", C.c_int32), ("n_degenerate", C.c_int32), ("n_edges", C.c_int32),
+                ("n_boundary_edges", C.c_int32), ("n_nonmanifold_edges", C.c_int32), ("first_vertex", C.c_int32), ("kept", C.c_int32),
+                ("area", C.c_double), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("reserved", C.c_int32 * 2)]
+
+
+class MeshComponentStats(C.Structure):
+    _fields_ = [("n_components", C.c_int64), ("n_kept", C.c_int64), ("n_unreferenced", C.c_int64), ("n_bad_area", C.c_int64),
+                ("n_vertices_out", C.c_int64), ("n_triangles_out", C.c_int64), ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32),
+                ("ms_wall", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
 PPF_VOLUME_MAX_DIM, PPF_VOLUME_MAX_WEIGHT, PPF_VOLUME_MAX_STEPS, PPF_VOLUME_MAX_TILES = 1024, 65535, 4096, 16777215
 
 
@@ -606,6 +623,11 @@ _SIGNATURES = {
     "ppf_volume_mesh_info": (C.c_int, [C.c_void_p, C.POINTER(VolumeMeshDesc)]),
     "ppf_volume_mesh_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "ppf_volume_mesh_release": (C.c_int, [C.c_void_p]),
+    "ppf_volume_mesh_upload": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
+    "ppf_debug_volume_mesh_shell": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "ppf_default_mesh_component_params": (None, [C.POINTER(MeshComponentParams)]),
+    "ppf_volume_mesh_components": (C.c_int, [C.c_void_p, C.POINTER(MeshComponentParams), C.POINTER(C.c_void_p), C.c_void_p,
+                                             C.POINTER(MeshComponentInfo), C.c_int, C.POINTER(MeshComponentStats)]),
     "ppf_default_mesh_sample_params": (None, [C.POINTER(MeshSampleParams)]),
     "ppf_cloud_from_mesh": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(MeshSampleParams),
                                       C.POINTER(C.c_void_p), C.POINTER(MeshSampleStats)]),

@@ -1110,6 +1110,72 @@ class VolumeMesh:
         v, t = self._read()
         write_ply_mesh(v, t, path)
 
+    @classmethod
+    def from_arrays(cls, vertices, triangles) -> "VolumeMesh":
+        """A mesh from host arrays (ppf_volume_mesh_upload), so that a loaded PLY can be cleaned by ``components``: vertices
+        (N, 3) float32, or (N, >= 6) with the normals in the last three columns; triangles (M, 3) int32."""
+        V = np.ascontiguousarray(vertices, dtype=np.float32)
+        T = np.ascontiguousarray(triangles, dtype=np.int32)
+        if V.size == 0:
+            V = V.reshape(0, 3)
+        if T.size == 0:
+            T = T.reshape(0, 3)
+        if V.ndim != 2 or T.ndim != 2 or T.shape[1] != 3 or V.shape[1] in (4, 5):
+            raise PPFError(_capi.PPF_ERR_INVALID, "from_arrays: vertices must be (N, 3 | >= 6) float32 and triangles (M, 3) int32")
+        out = C.c_void_p()
+        check(lib().ppf_volume_mesh_upload(V.ctypes.data if V.size else None, V.shape[0], max(V.shape[1], 3),
+                                           V.shape[1] - 3 if V.shape[1] >= 6 else -1, T.ctypes.data if T.size else None, T.shape[0],
+                                           C.byref(out)))
+        return cls(out)
+
+    def components(self, min_triangles: int = 1, min_area: float = 0.0, rank_lo: int = 0, rank_hi: Optional[int] = None, *,
+                   labels: bool = False, max_info: int = 64, return_stats: bool = False, measure_only: bool = False):
+        """The mesh's connected components, ranked by area, and the mesh of those that are kept
+        (ppf_volume_mesh_components): a component is kept iff rank_lo <= rank < rank_hi (None: no upper end),
+        it has at least min_triangles triangles and at least min_area square metres.  Returns (VolumeMesh, [info dicts of the
+        max_info largest components]), then the per-vertex labels (rank, or -1) with labels=True, then the stats with
+        return_stats=True.  measure_only: no output mesh is made and the first item is None.  This mesh is not changed."""
+        prm = _params(_capi.MeshComponentParams, "ppf_default_mesh_component_params",
+                      {"min_triangles": int(min_triangles), "min_area": float(min_area), "rank_lo": int(rank_lo),
+                       "rank_hi": 0x7FFFFFFF if rank_hi is None else int(rank_hi)})
+        cap = int(max_info)
+        info = (_capi.MeshComponentInfo * max(cap, 1))()
+        lab = np.empty(self.n_vertices, np.int32) if labels else None
+        out, st = C.c_void_p(), _capi.MeshComponentStats()
+        check(lib().ppf_volume_mesh_components(self._ptr, C.byref(prm), None if measure_only else C.byref(out),
+                                               lab.ctypes.data if lab is not None and lab.size else None, info if cap > 0 else None, cap,
+                                               C.byref(st)))
+        res = [None if measure_only else VolumeMesh(out),
+               [_component_info(info[r]) for r in range(min(int(st.n_components), max(cap, 0)))]]
+        if labels:
+            res.append(lab)
+        if return_stats:
+            res.append(_capi.stats_dict(st))
+        return tuple(res)
+
+    def largest(self, k: int = 1, **kw):
+        """``components`` keeping the k largest pieces (rank_hi = k) among those that pass min_triangles and min_area"""
+        return self.components(rank_lo=0, rank_hi=int(k), **kw)
+
+    def split(self, k: int, **kw) -> list:
+        """The k largest pieces, one ``VolumeMesh`` each (rank_lo = r, rank_hi = r + 1; a rank that fails min_triangles or
+        min_area gives an empty mesh).  Fewer than k when the mesh has fewer components."""
+        kw = {key: v for key, v in kw.items() if key in ("min_triangles", "min_area")}
+        pieces = []
+        for r in range(int(k)):
+            m, _, st = self.components(rank_lo=r, rank_hi=r + 1, max_info=0, return_stats=True, **kw)
+            if r >= st["n_components"]:
+                break
+            pieces.append(m)
+        return pieces
+
+
+def _component_info(rec) -> dict:
+    """a ppf_mesh_component_info as a plain dict (lo / hi as tuples)"""
+    d = {name: getattr(rec, name) for name, _ in rec._fields_ if name != "reserved"}
+    d["lo"], d["hi"] = tuple(rec.lo), tuple(rec.hi)
+    return d
+
 
 class DepthFusion:
     """Frame-to-model camera tracking and fusion: every pushed frame is aligned to the image ``volume`` gives from the current
@@ -1714,19 +1780,36 @@ class CloudProcessor:
         self.camera_motion, self.camera_pose = T, f.pose.copy()
         return T, status
 
-    def MeshVolume(self, path=None) -> "VolumeMesh":
+    def MeshVolume(self, path=None, *, keep_largest: Optional[int] = None, min_triangles: Optional[int] = None) -> "VolumeMesh":
         """The triangle mesh of the volume ``FuseVolume`` has filled (``DepthVolume.mesh``), written to ``path``
         as a PLY when a path is given.  A scan is an open surface: give ``LoadMeshModel(path, label, normals="vertex",
-        orient=False)`` so that the normals seen through the open back are not flipped.  Refused before the first
-        ``FuseVolume``."""
+        orient=False)`` so that the normals seen through the open back are not flipped.  keep_largest and / or min_triangles
+        pass the mesh through ``VolumeMesh.components`` first: only the keep_largest largest pieces, without
+        those of fewer than min_triangles triangles; ``mesh_components`` then holds their info.  Both None: the mesh as the
+        volume gives it.  Refused before the first ``FuseVolume``."""
         if self._depth_fusion is None:
             raise PPFError(_capi.PPF_ERR_INVALID, "MeshVolume: there is no volume yet; call FuseVolume first")
         t0 = time.perf_counter()
         m = self._depth_fusion.volume.mesh()
+        if keep_largest is not None or min_triangles is not None:
+            m, self.mesh_components = m.components(min_triangles=1 if min_triangles is None else min_triangles, rank_hi=keep_largest)
         if path is not None:
             m.save_ply(path)
         self.timings["mesh_volume"] = time.perf_counter() - t0
         return m
+
+    def MeshVolumeObjects(self, k: int, min_triangles: int = 1) -> list:
+        """The k largest pieces of the volume's mesh that have at least min_triangles triangles, largest first, as
+        (vertices, triangles) pairs (``VolumeMesh.split``): a scan of several objects becomes one model each
+        through ``LoadMeshModel((vertices, triangles), label, normals="vertex", orient=False)``.  Refused before the first
+        ``FuseVolume``."""
+        if self._depth_fusion is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "MeshVolumeObjects: there is no volume yet; call FuseVolume first")
+        t0 = time.perf_counter()
+        pieces = self._depth_fusion.volume.mesh().split(k, min_triangles=min_triangles)
+        out = [(p.vertices(), p.triangles()) for p in pieces if p.n_triangles > 0]
+        self.timings["mesh_volume_objects"] = time.perf_counter() - t0
+        return out
 
     def _match_frame(self, labels, step, dist, top: int = 5) -> List[Optional[Pose3D]]:
         dets = (FrameDetection * max(len(labels), 1))()

@@ -26,14 +26,14 @@
  *             ppf_depth_kernels.h  ppf_depth_normals_kernels.h  ppf_verify_kernels.h  ppf_render_kernels.h  ppf_select_kernels.h  ppf_refine_kernels.h
  *             ppf_register_kernels.h  ppf_plane_kernels.h  ppf_label_kernels.h  ppf_cluster_kernels.h  ppf_region_kernels.h  ppf_filter_kernels.h
  *             ppf_segment_kernels.h  ppf_recognize_kernels.h  ppf_history_kernels.h  ppf_motion_kernels.h
- *             ppf_volume_kernels.h  ppf_volume_mesh_kernels.h  ppf_mesh_kernels.h
+ *             ppf_volume_kernels.h  ppf_volume_mesh_kernels.h  ppf_mesh_kernels.h  ppf_mesh_components_kernels.h
  *   host      ppf_device_mem.h (errors, block cache)  ppf_host_common.h (scans, sorts, model / workspace structs)
  *             ppf_model_host.h  ppf_match_host.h  ppf_batch_host.h  ppf_icp_host.h  ppf_prep_host.h (the segmented
  *             preparation stages; ppf_prep_* = one segment)  ppf_frame_host.h (ppf_prep_frame = their chain)
  *             ppf_match_frame_host.h  ppf_depth_host.h  ppf_posetable_host.h  ppf_verify_host.h  ppf_render_host.h
  *             ppf_select_host.h  ppf_refine_host.h  ppf_register_host.h  ppf_plane_host.h  ppf_cluster_host.h  ppf_region_host.h
  *             ppf_filter_host.h  ppf_segment_host.h  ppf_recognize_host.h  ppf_history_host.h  ppf_motion_host.h
- *             ppf_volume_host.h  ppf_mesh_host.h  (the C-ABI)
+ *             ppf_volume_host.h  ppf_mesh_components_host.h  ppf_mesh_host.h  (the C-ABI)
  *
  * Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see __graft_entry__.build()).
  * No CPU fallback exists: without a HIP device the compute entry points return PPF_ERR_HIP.
@@ -81,6 +81,7 @@
 #include "ppf_register_kernels.h" /* k_reg_rays, k_reg_clear, k_reg_draw, k_reg_resolve */
 #include "ppf_plane_kernels.h" /* k_pln_hyp, k_pln_count, k_pln_best, k_pln_sum / _finish, k_pln_flags, k_pln_compact, k_pln_gather */
 #include "ppf_label_kernels.h" /* uf_find, uf_unite, uf_root, cells_lower_bound, wave_max_by_key: no kernel */
+#include "ppf_mesh_components_kernels.h" /* k_mc_init, k_mc_unite, k_mc_flatten, k_mc_tris, k_mc_edges, k_mc_comps, k_mc_rank, k_mc_flags, k_mc_write_* */
 #include "ppf_cluster_kernels.h" /* k_clu_bounds, k_clu_grid, k_clu_keys, k_clu_runs, k_clu_cells, k_clu_link, k_clu_flatten ... k_clu_reduce */
 #include "ppf_segment_kernels.h" /* k_seg_classify, k_seg_tile, k_seg_merge, k_seg_flatten, k_seg_valid, k_seg_rank, k_seg_labels */
 #include "ppf_recognize_kernels.h" /* k_rec_dmax, k_rec_build, k_rec_popcount, k_rec_score, k_rec_finish */
@@ -109,6 +110,7 @@
 #include "ppf_history_host.h"     /* a camera's last frames fused into one depth image: ppf_depth_history_* */
 #include "ppf_motion_host.h"      /* the camera's motion between two depth images: ppf_depth_motion */
 #include "ppf_volume_host.h"      /* posed depth images fused into a TSDF volume: ppf_depth_volume_*, ppf_volume_mesh_* */
+#include "ppf_mesh_components_host.h" /* a mesh's connected components, scraps removed: ppf_volume_mesh_upload, ppf_volume_mesh_components */
 #include "ppf_mesh_host.h"        /* a model cloud sampled from a triangle mesh: ppf_cloud_from_mesh */
 #include "ppf_segment_host.h"     /* a depth image's surfaces labelled in image space: ppf_depth_segments */
 #include "ppf_recognize_host.h"   /* which trained models a proposal can be a view of: ppf_recognizer_*, ppf_recognize_frame */
