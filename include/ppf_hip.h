@@ -397,6 +397,41 @@ typedef struct ppf_debug_match_plan_out {
 /* PPF_ERR_INVALID for a NULL or out-of-range argument, and -- as the match call itself -- for a model tile that leaves
  * the vote kernel's least staging no LDS and for more paired points than one call can group; `out` is then all zero. */
 ppf_status ppf_debug_match_plan(const ppf_debug_match_plan_in* in, ppf_debug_match_plan_out* out);
+/* How one launch sequence of the batched ICP lays its jobs out in the shared scratch arrays, schedules their levels and
+ * sizes its launches and its pinned block (host only, no device needed): the engine's own planning function, which
+ * every ppf_icp_refine*, ppf_icp_register and ppf_match_frame call runs once per launch sequence.  A pure function of
+ * the jobs' row counts and four parameters, so its corners (chunks of 64, row blocks of 8,192, steps that are no power
+ * of two, the 32,768-row staging limit, rows per wave of the neighbour search) are reached without a device.  A launch
+ * sequence holds up to 256 jobs and a call up to 30 levels; this record holds 8 of each, and reports the first and the
+ * last job.  Test surface. */
+typedef struct ppf_debug_icp_plan_in {
+  int32_t n[8], nd_all[8];   /* rows of each job's source and destination cloud: all >= 1 */
+  int32_t jobs;              /* 1 .. 8 */
+  int32_t uniform;           /* != 0: every job has the same two clouds and the same layout (so equal n and nd_all) */
+  int32_t iterations;        /* ppf_icp_params: >= 0 */
+  float tolerance, rejection_scale;
+  int32_t num_levels;        /* 0 .. 8 */
+} ppf_debug_icp_plan_in;
+typedef struct ppf_debug_icp_plan_out {
+  uint64_t t_src, t_dst, t_sel, t_parts, t_sums, t_sumd; /* all jobs' rows of either cloud, selections, chunk partials, chunk sums */
+  uint64_t g_start, g_cur, g_box2, g_box1u, state, bb_parts; /* elements of the arrays with a fixed pitch per job, of the states, of the extents per chunk */
+  uint64_t table_bytes, levels_off;  /* both device tables, where the level table starts */
+  uint64_t h_done_off, h_state_off, h_tables_off, pinned_bytes; /* the pinned block: the tick counter is at 0 */
+  uint64_t first_off[8], last_off[8]; /* job 0's and the last job's o_src0, o_dst0, o_best, o_owner, o_sel, o_parts, o_sums, o_sumd */
+  int32_t max_chunks, max_rows_blocks, max_dst_blocks; /* grid extents of the set-up launches */
+  int32_t robust;            /* rejection_scale > 0 */
+  int32_t n_levels, pad0;    /* entries used below, [level] */
+  double tol_p[8];
+  int64_t sum_ns[8];
+  uint64_t tail_lds[8];      /* dynamic LDS of k_icp2_tail, bytes */
+  int32_t max_iter[8], max_ns[8], nn_rows[8];
+  uint32_t nn_blocks[8], begin_blocks[8];
+  int32_t first_level[8][5], last_level[8][5]; /* job 0's and the last job's step, ns, nd, step_shift, staged */
+  int32_t uni[8][7];         /* uniform: ns, nd, step, step_shift, staged, n, nd_all handed to the per-pass kernels; else 0 */
+  uint64_t uni_p_sel[8], uni_p_parts[8]; /* ... and their pitches of sel and parts */
+} ppf_debug_icp_plan_out;
+/* PPF_ERR_INVALID for a NULL or out-of-range argument (uniform with unequal jobs included); `out` is then all zero. */
+ppf_status ppf_debug_icp_plan(const ppf_debug_icp_plan_in* in, ppf_debug_icp_plan_out* out);
 /* Guard mode of the device block cache: finds stores outside a scratch or result buffer and reads of scratch that was
  * never written, which the cache otherwise hides (a request is rounded up to a size class, so a store a few bytes too far
  * lands in slack nobody reads, and a reused block still holds the previous call's bytes).  mode 0: off (the default);

@@ -97,6 +97,25 @@ class MatchPlanOut(C.Structure):
                 ("group_lds", C.c_uint64)]
 
 
+class IcpPlanIn(C.Structure):
+    """ppf_debug_icp_plan_in: the jobs' row counts and the four parameters the planning of a launch sequence reads"""
+    _fields_ = [("n", C.c_int32 * 8), ("nd_all", C.c_int32 * 8), ("jobs", C.c_int32), ("uniform", C.c_int32),
+                ("iterations", C.c_int32), ("tolerance", C.c_float), ("rejection_scale", C.c_float), ("num_levels", C.c_int32)]
+
+
+class IcpPlanOut(C.Structure):
+    """ppf_debug_icp_plan_out: scratch totals, table and pinned-block layout, launch shapes per level"""
+    _fields_ = [(f, C.c_uint64) for f in ("t_src", "t_dst", "t_sel", "t_parts", "t_sums", "t_sumd", "g_start", "g_cur", "g_box2",
+                                          "g_box1u", "state", "bb_parts", "table_bytes", "levels_off", "h_done_off",
+                                          "h_state_off", "h_tables_off", "pinned_bytes")] + \
+               [("first_off", C.c_uint64 * 8), ("last_off", C.c_uint64 * 8), ("max_chunks", C.c_int32),
+                ("max_rows_blocks", C.c_int32), ("max_dst_blocks", C.c_int32), ("robust", C.c_int32), ("n_levels", C.c_int32),
+                ("pad0", C.c_int32), ("tol_p", C.c_double * 8), ("sum_ns", C.c_int64 * 8), ("tail_lds", C.c_uint64 * 8),
+                ("max_iter", C.c_int32 * 8), ("max_ns", C.c_int32 * 8), ("nn_rows", C.c_int32 * 8), ("nn_blocks", C.c_uint32 * 8),
+                ("begin_blocks", C.c_uint32 * 8), ("first_level", C.c_int32 * 5 * 8), ("last_level", C.c_int32 * 5 * 8),
+                ("uni", C.c_int32 * 7 * 8), ("uni_p_sel", C.c_uint64 * 8), ("uni_p_parts", C.c_uint64 * 8)]
+
+
 def stats_dict(st):
     """A stats structure as a plain dict (array fields as lists)."""
     out = {}
@@ -523,6 +542,7 @@ _SIGNATURES = {
                                             C.c_int, C.POINTER(MatchParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     "ppf_debug_block_size": (C.c_size_t, [C.c_size_t]),
     "ppf_debug_match_plan": (C.c_int, [C.POINTER(MatchPlanIn), C.POINTER(MatchPlanOut)]),
+    "ppf_debug_icp_plan": (C.c_int, [C.POINTER(IcpPlanIn), C.POINTER(IcpPlanOut)]),
     "ppf_debug_device_math": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "ppf_debug_pool_guard": (C.c_int, [C.c_int]),
     "ppf_debug_pool_check": (C.c_int, [C.POINTER(PoolReport)]),
