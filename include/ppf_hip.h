@@ -432,6 +432,13 @@ typedef struct ppf_debug_icp_plan_out {
 } ppf_debug_icp_plan_out;
 /* PPF_ERR_INVALID for a NULL or out-of-range argument (uniform with unequal jobs included); `out` is then all zero. */
 ppf_status ppf_debug_icp_plan(const ppf_debug_icp_plan_in* in, ppf_debug_icp_plan_out* out);
+/* The group records ppf_model_load derives from a model's pair records (host only, no device needed): `model_bytes` is a
+ * model file's byte stream, validated exactly like ppf_model_load_mem (PPF_ERR_IO).  grp_records takes records of four
+ * words {row_a, row_b, cells_a, cells_b}, grp_hdr entries of two {first group record, group records}, one per 32 pair
+ * records; the capacities count records and entries.  Either buffer may be NULL; the counts are always reported, and a
+ * buffer that is too small is PPF_ERR_CAPACITY.  A model that votes through no count table reports 0 and 0.  Test surface. */
+ppf_status ppf_debug_model_row_groups(const void* model_bytes, size_t size, uint32_t* grp_records, size_t cap_records,
+                                      uint32_t* grp_hdr, size_t cap_hdr, uint64_t* n_records_out, uint64_t* n_hdr_out);
 /* Guard mode of the device block cache: finds stores outside a scratch or result buffer and reads of scratch that was
  * never written, which the cache otherwise hides (a request is rounded up to a size class, so a store a few bytes too far
  * lands in slack nobody reads, and a reused block still holds the previous call's bytes).  mode 0: off (the default);

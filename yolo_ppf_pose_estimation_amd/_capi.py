@@ -543,6 +543,8 @@ _SIGNATURES = {
     "ppf_debug_block_size": (C.c_size_t, [C.c_size_t]),
     "ppf_debug_match_plan": (C.c_int, [C.POINTER(MatchPlanIn), C.POINTER(MatchPlanOut)]),
     "ppf_debug_icp_plan": (C.c_int, [C.POINTER(IcpPlanIn), C.POINTER(IcpPlanOut)]),
+    "ppf_debug_model_row_groups": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "ppf_debug_device_math": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "ppf_debug_pool_guard": (C.c_int, [C.c_int]),
     "ppf_debug_pool_check": (C.c_int, [C.POINTER(PoolReport)]),

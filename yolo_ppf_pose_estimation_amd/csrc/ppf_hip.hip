@@ -34,6 +34,9 @@
  *             ppf_select_host.h  ppf_refine_host.h  ppf_register_host.h  ppf_plane_host.h  ppf_cluster_host.h  ppf_region_host.h
  *             ppf_filter_host.h  ppf_segment_host.h  ppf_recognize_host.h  ppf_history_host.h  ppf_motion_host.h
  *             ppf_volume_host.h  ppf_mesh_components_host.h  ppf_mesh_host.h  (the C-ABI)
+ *   model host (ppf_model_host.h): model_plan (parameters -> steps, slots, tiles; pure), build_table (training's device
+ *             passes in named steps), ModelImage (what a model file holds: read + validate, write, download, upload),
+ *             row_groups (the group records; pure), model_finish (what training and loading derive once the table stands)
  *
  * Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see __graft_entry__.build()).
  * No CPU fallback exists: without a HIP device the compute entry points return PPF_ERR_HIP.

@@ -195,7 +195,7 @@ struct ppf_model {
   DevBuf<uint32_t> bucket_mid;   /* n_tiles * n_buckets: see k_bucket_mid */
   DevBuf<uint4> records;          /* pair records, see place_entry */
   DevBuf<int32_t> key_lut;        /* quantised key -> bucket, see k_build_key_lut */
-  DevBuf<uint4> grp_records;      /* group records of the buckets that can vote through count tables, see build_row_groups */
+  DevBuf<uint4> grp_records;      /* group records of the buckets that can vote through count tables, see row_groups (ppf_model_host.h) */
   DevBuf<uint2> grp_hdr;          /* n_records / 32 + 1: a chunk's slice of them */
   uint64_t n_grp_records = 0;
   KeyDims kd{};

@@ -234,7 +234,7 @@ constexpr int AGG_SCRATCH = ((AGG_Q + 1) * AGG_ROW + 15) / 16 * 16; /* per-wave 
  * k_vote casts the counted atomics of the set columns only (see agg_pair) */
 constexpr int AGG_OFF_COLS = (AGG_Q + 1) * AGG_ROW;
 constexpr uint32_t AGG_COLS_ALL = (2u << AGG_NY) - 1u; /* all 17 columns */
-/* Group records (build_row_groups): the entries of a (tile, bucket) that share accumulator row and count-table shift X cast
+/* Group records (row_groups, ppf_model_host.h): the entries of a (tile, bucket) that share accumulator row and count-table shift X cast
  * their counted adds at the same words, so a lane adds up the table rows of up to AGG_GROUP_CELLS of them as packed bytes and
  * casts one set of adds.  A table whose largest count is at most AGG_NARROW_MAX (bit AGG_COLS_NARROW of its mask word) can be
  * summed that way without a carry between bytes; any other table votes entry by entry (agg_pair<true>). */
@@ -380,7 +380,7 @@ struct MatchArgs {
   int n_rounds, round_buckets; /* k_group sorts round_buckets bucket ids per pass over the reference point's hits */
   const uint32_t* bucket_total; /* [n_buckets] entries of a bucket over all tiles */
   const uint32_t* bucket_mid;   /* [n_tiles][n_buckets] entries of low-half rows = the first dealing positions of the bucket (k_bucket_mid) */
-  const uint4* grp_records;     /* group records {row_a, row_b, cells_a, cells_b}: the (row, X)-sorted view of the (tile, bucket)s that can vote through count tables (build_row_groups); NULL: none */
+  const uint4* grp_records;     /* group records {row_a, row_b, cells_a, cells_b}: the (row, X)-sorted view of the (tile, bucket)s that can vote through count tables (row_groups); NULL: none */
   const uint2* grp_hdr;         /* [records / 32] {first group record, group records} of the chunk of pair records that starts in this block of 32 */
   unsigned long long* work;     /* [n_ref] votes the reference point will cast (sum of its hits' bucket sizes) */
   uint32_t* perm;               /* [n_ref] reference points ordered by work, heaviest first (k_rank) */
