@@ -148,6 +148,18 @@ def test_launches_and_syncs_do_not_depend_on_the_box_count(frame):
     assert pairs == [] and s0["n_launches"] == 0
 
 
+def test_the_waits_of_a_call_are_three_and_two_when_no_box_holds_a_point(frame):
+    """crop, voxel grid, the end; a frame whose boxes crop nothing stops after the crop's read-back and ends like every call"""
+    xyz, depth, box, intr = frame
+    boxes = frame_boxes(frame)[:3]
+    _, _, st = DeviceCloud.upload(xyz).prep_frame(boxes, depth, intr, DEFAULTS, return_info=True)
+    assert st["n_host_syncs"] == 3
+    far = DeviceCloud.upload(xyz[:1000] + np.float32([1000.0, 0.0, 0.0]))
+    pairs, rows, st = far.prep_frame(boxes, depth, intr, DEFAULTS, return_info=True)
+    assert (st["n_host_syncs"], st["n_launches"]) == (2, 6) and not np.asarray(rows).any()      # k_frame_crop_flags and one scan
+    assert all(len(o) == 0 and len(e) == 0 for o, e in pairs)
+
+
 def _raw_frame(scene, boxes, depth, intr, p):
     b = np.ascontiguousarray(np.asarray(boxes, np.int32))
     prm = FrameParams()

@@ -1,14 +1,15 @@
 /*
  * ppf_cluster_host.h — host side of ppf_prep_clusters: the connected blobs of up to 256 plane-free clouds in one pass
- * (DESIGN.md §20).  Kernels: ppf_cluster_kernels.h.  Included by ppf_hip.hip after ppf_prep_host.h (ppf_cloud, FrameRun,
- * frame_scan, frame_sort, frame_sort_segmented).
+ * (DESIGN.md §20).  Kernels: ppf_cluster_kernels.h.  Included by ppf_hip.hip after ppf_stage_host.h (FrameRun, frame_scan,
+ * frame_sort, stage_entry) and ppf_prep_host.h (ppf_cloud, frame_sort_segmented).
  *
  * Per call: one upload of the segment table before any device work, then k_clu_bounds, k_clu_grid, k_clu_keys, the sort by
  * (segment, cell) (five digit passes of seven launches and one gather), k_clu_runs, the scan, k_clu_cells, k_clu_link,
  * k_clu_flatten, k_clu_valid, the ranking's sort (the same five passes), k_clu_rank, k_clu_labels, the gather's sort (three
  * passes), k_clu_gather and k_clu_reduce: 110 launches whatever the clouds hold, none when no cloud has a row.
- * The sequence is cut in three shared pieces (clu_begin, clu_cells, clu_finish) that ppf_prep_regions runs too, around kernels
- * of its own (ppf_region_host.h), inside the same entry body (clu_entry).
+ * The sequence is cut in three shared pieces (clu_begin, clu_cells, clu_rank) that ppf_prep_regions runs too, around kernels
+ * of its own (ppf_region_host.h), inside the same call (clu_run: the table, the run, the one wait, clu_results) and the same
+ * entry body (clu_entry).
  * Nothing the device counts (cells, components, clusters) comes to the host before the end: grids are sized for the rows and
  * workgroups past a device-side count leave.  The host waits once, for the cluster heads, the reductions, the counts, the
  * grids and the labels; the outputs are views into one block sized for the input, so nothing is allocated after that wait.
@@ -41,7 +42,8 @@ float cluster_smallest_tolerance(double extent) {
 /* What ppf_prep_clusters and ppf_prep_regions (ppf_region_host.h) share: the segment table, the scratch, one zeroed block
  * (the bounds, the counts, the cluster heads, the reductions and `extra` words of the entry's own) and the output block.
  * clu_begin runs up to the sort by (segment, cell), the entry its k_*_runs, clu_cells the scan and the table of cells, the
- * entry its link and flatten passes (root[], size[] final), clu_finish the ranking, the gather, the one wait and the results. */
+ * entry its link and flatten passes (root[], size[] final), clu_rank the ranking and the gather; after the one wait
+ * clu_results reads what came back. */
 struct CluWork {
   const char* who;
   int K, MC, n;
@@ -58,11 +60,8 @@ struct CluWork {
   double tol;
 };
 
-/* fr and blk belong to the caller: on an error they outlive the wait for what was launched.  w.N == 0 on PPF_OK: no cloud has
- * a row, nothing was launched and nothing is to be done */
-template <bool NORMALS>
-ppf_status clu_begin(FrameRun& fr, CluWork& w, std::shared_ptr<DevBuf<float>>& blk, const char* who, const ppf_cloud* const* in, int K, int MC,
-                     float tolerance, size_t extra) {
+/* the segment table, before any device work.  w.N == 0 on PPF_OK: no cloud has a row, nothing is to be done */
+ppf_status clu_table(CluWork& w, const char* who, const ppf_cloud* const* in, int K, int MC) {
   w.who = who;
   w.K = K;
   w.MC = MC;
@@ -74,24 +73,25 @@ ppf_status clu_begin(FrameRun& fr, CluWork& w, std::shared_ptr<DevBuf<float>>& b
     if (N >= 0x7fffffffull) return fail(PPF_ERR_INVALID, "%s: the clouds hold more than INT32_MAX rows together", who);
   }
   w.N = N;
-  if (N == 0) return PPF_OK; /* no cloud has a row: no cluster, no launch */
+  return PPF_OK;
+}
+
+/* the scratch, the upload of the table and the launches up to the sort by (segment, cell); w.N > 0 */
+template <bool NORMALS>
+ppf_status clu_begin(FrameRun& fr, CluWork& w, DevBuf<float>& blk, float tolerance, size_t extra) {
+  const int K = w.K, MC = w.MC;
+  const size_t N = w.N;
   const int n = w.n = (int)N, nblk = (n + RS_BLOCK - 1) / RS_BLOCK;
   const size_t slots = (size_t)K * MC;
   uint32_t *k1, *k2, *v1, *v2;
   w.z_mm = 0; w.z_fin = w.z_mm + (size_t)K * 6; w.z_cnt = w.z_fin + K; w.z_head = w.z_cnt + (size_t)K * 2; w.z_acc = w.z_head + slots * 2;
   w.z_extra = w.z_acc + slots * CLU_ACC;
   w.z_words = (w.z_extra + extra + 3) & ~(size_t)3;
-  ppf_status s;
-  if ((s = fr.get(K, &w.d_tab)) != PPF_OK || (s = fr.get(K, &w.d_grid)) != PPF_OK || (s = fr.get(w.z_words, &w.zero)) != PPF_OK ||
-      (s = fr.get(N, &w.pts)) != PPF_OK || (s = fr.get(N + 1, &w.ckey)) != PPF_OK || (s = fr.get(N, &w.lkey)) != PPF_OK ||
-      (s = fr.get(N, &w.skey)) != PPF_OK || (s = fr.get(N, &k1)) != PPF_OK || (s = fr.get(N, &k2)) != PPF_OK || (s = fr.get(N, &v1)) != PPF_OK ||
-      (s = fr.get(N, &v2)) != PPF_OK || (s = fr.get((size_t)256 * nblk, &w.hist)) != PPF_OK || (s = fr.get((size_t)256 * nblk, &w.offs)) != PPF_OK ||
-      (s = fr.get(N, &w.parent)) != PPF_OK || (s = fr.get(N, &w.size)) != PPF_OK || (s = fr.get(N, &w.root)) != PPF_OK ||
-      (s = fr.get(N + 1, &w.flags)) != PPF_OK || (s = fr.get(N + 1, &w.runid)) != PPF_OK || (s = fr.get(N + 2, &w.cstart)) != PPF_OK ||
-      (s = fr.get(N, &w.rank)) != PPF_OK || (s = fr.get(N, &w.d_labels)) != PPF_OK)
-    return s;
-  blk.reset(new DevBuf<float>());
-  HIPCHK(blk->reserve(N * 7)); /* [rows | curvature] */
+  const ppf_status s = fr.get(K, &w.d_tab, K, &w.d_grid, w.z_words, &w.zero, N, &w.pts, N + 1, &w.ckey, N, &w.lkey, N, &w.skey, N, &k1, N, &k2, N, &v1,
+                              N, &v2, (size_t)256 * nblk, &w.hist, (size_t)256 * nblk, &w.offs, N, &w.parent, N, &w.size, N, &w.root, N + 1, &w.flags,
+                              N + 1, &w.runid, N + 2, &w.cstart, N, &w.rank, N, &w.d_labels);
+  if (s != PPF_OK) return s;
+  HIPCHK(blk.reserve(N * 7)); /* [rows | curvature] */
   HIPCHK(hipMemcpy(w.d_tab, w.tab.data(), w.tab.size() * sizeof(CluSeg), hipMemcpyHostToDevice));
   HIPCHK(hipMemsetAsync(w.zero, 0, w.z_words * sizeof(uint32_t), nullptr));
   uint32_t *mm = w.zero + w.z_mm, *fin = w.zero + w.z_fin;
@@ -117,21 +117,17 @@ ppf_status clu_cells(FrameRun& fr, CluWork& w) {
   return PPF_OK;
 }
 
-/* counts: [K][stride] = {output, valid, all, then the entry's `extra` words per cloud} */
-ppf_status clu_finish(FrameRun& fr, CluWork& w, std::shared_ptr<DevBuf<float>>& blk, int min_size, int max_size, const double* intr,
-                      int image_rows, int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts, int stride,
-                      int32_t* const* labels, ppf_cluster_stats& st) {
-  const char* who = w.who;
+/* root[] and size[] are final: the ranking, the labels, the gather into blk and the reductions */
+ppf_status clu_rank(FrameRun& fr, CluWork& w, DevBuf<float>& blk, int min_size, int max_size, const double* intr, int image_rows,
+                    int image_cols) {
   const int K = w.K, MC = w.MC, n = w.n;
-  const size_t N = w.N, slots = (size_t)K * MC, z_mm = w.z_mm, z_cnt = w.z_cnt, z_head = w.z_head, z_acc = w.z_acc, z_words = w.z_words;
-  const std::vector<CluSeg>& tab = w.tab;
+  const size_t N = w.N;
   CluSeg* d_tab = w.d_tab;
-  CluGrid* d_grid = w.d_grid;
-  uint32_t *zero = w.zero, *skey = w.skey, *hist = w.hist, *offs = w.offs, *size = w.size, *root = w.root;
+  uint32_t *skey = w.skey, *hist = w.hist, *offs = w.offs, *size = w.size, *root = w.root;
   uint32_t *&ka = w.ka, *&va = w.va, *&kb = w.kb, *&vb = w.vb;
   int32_t *rank = w.rank, *d_labels = w.d_labels;
-  uint32_t *cnt = zero + z_cnt, *acc = zero + z_acc;
-  int32_t* head = reinterpret_cast<int32_t*>(zero + w.z_head);
+  uint32_t *cnt = w.zero + w.z_cnt, *acc = w.zero + w.z_acc;
+  int32_t* head = reinterpret_cast<int32_t*>(w.zero + w.z_head);
   const dim3 b256(CLU_BLOCK), rows_grid = w.rows_grid;
   CluIntr cam = {0.0, 0.0, 0.0, 0.0, image_rows, image_cols, intr ? 1 : 0};
   if (intr) { cam.fx = intr[0]; cam.fy = intr[1]; cam.ppx = intr[2]; cam.ppy = intr[3]; }
@@ -145,24 +141,22 @@ ppf_status clu_finish(FrameRun& fr, CluWork& w, std::shared_ptr<DevBuf<float>>& 
   HIPCHK(hipGetLastError());
   static const int shifts3[3] = {0, 8, 16};
   if ((s = frame_sort(fr, ka, va, kb, vb, n, hist, offs, shifts3, 3)) != PPF_OK) return s;
-  FRAME_LAUNCH(fr, k_clu_gather, rows_grid, b256, d_tab, (uint32_t)N, ka, va, blk->p, blk->p + N * 6);
+  FRAME_LAUNCH(fr, k_clu_gather, rows_grid, b256, d_tab, (uint32_t)N, ka, va, blk.p, blk.p + N * 6);
   FRAME_LAUNCH(fr, k_clu_reduce, rows_grid, b256, d_tab, (uint32_t)N, ka, va, cam, MC, acc);
   HIPCHK(hipGetLastError());
+  return PPF_OK;
+}
 
-  /* the one wait */
-  std::vector<uint32_t> z(z_words);
-  std::vector<CluGrid> grid((size_t)K);
-  std::vector<int32_t> lab;
-  bool want_labels = false;
-  for (int i = 0; labels && i < K; i++) want_labels = want_labels || labels[i];
-  HIPCHK(hipMemcpyAsync(z.data(), zero, z_words * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
-  HIPCHK(hipMemcpyAsync(grid.data(), d_grid, grid.size() * sizeof(CluGrid), hipMemcpyDeviceToHost, nullptr));
-  if (want_labels) {
-    lab.resize(N);
-    HIPCHK(hipMemcpyAsync(lab.data(), d_labels, N * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
-  }
-  fr.syncs++;
-  HIPCHK(hipStreamSynchronize(nullptr));
+/* after the one wait: z is the zeroed block and grid the grids as the device left them, lab the labels when any were asked
+ * for.  counts: [K][stride] = {output, valid, all, then the entry's `extra` words per cloud} */
+ppf_status clu_results(const CluWork& w, const std::vector<uint32_t>& z, const std::vector<CluGrid>& grid, const std::vector<int32_t>& lab,
+                       const std::shared_ptr<DevBuf<float>>& blk, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts, int stride,
+                       int32_t* const* labels) {
+  const char* who = w.who;
+  const int K = w.K, MC = w.MC;
+  const size_t N = w.N, slots = (size_t)K * MC, z_mm = w.z_mm, z_cnt = w.z_cnt, z_head = w.z_head, z_acc = w.z_acc;
+  const std::vector<CluSeg>& tab = w.tab;
+  const bool want_labels = !lab.empty();
   for (int i = 0; i < K; i++) {
     if (grid[i].ok) continue;
     const uint32_t* m = &z[z_mm + (size_t)i * 6];
@@ -204,75 +198,85 @@ ppf_status clu_finish(FrameRun& fr, CluWork& w, std::shared_ptr<DevBuf<float>>& 
     if (want_labels && labels[i] && tab[i].n) std::memcpy(labels[i], lab.data() + tab[i].off, (size_t)tab[i].n * sizeof(int32_t));
   }
   for (size_t k = 0; k < slots; k++) out[k] = res[k].release();
-  st.n_launches = fr.launches;
-  st.n_host_syncs = fr.syncs;
   return PPF_OK;
 }
 
-ppf_status clusters_enqueue(FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, const ppf_cloud* const* in, int K, const ppf_cluster_params& p,
-                            const double* intr, int image_rows, int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts,
-                            int32_t* const* labels, ppf_cluster_stats& st) {
-  CluWork w;
-  ppf_status s = clu_begin<false>(fr, w, blk, "ppf_prep_clusters", in, K, p.max_clusters, p.tolerance, 0);
-  if (s != PPF_OK || w.N == 0) return s;
-  const dim3 b256(CLU_BLOCK);
-  FRAME_LAUNCH(fr, k_clu_runs, w.rows1_grid, b256, w.d_tab, K, (uint32_t)w.N, w.va, w.lkey, w.skey, w.pts, w.flags);
-  HIPCHK(hipGetLastError());
-  if ((s = clu_cells(fr, w)) != PPF_OK) return s;
-  FRAME_LAUNCH(fr, k_clu_link, dim3((unsigned)w.N), dim3(64), w.pts, w.ckey, w.cstart, w.runid + w.N, w.tol * w.tol, w.parent);
-  FRAME_LAUNCH(fr, k_clu_flatten, w.rows_grid, b256, (uint32_t)w.N, w.lkey, w.parent, w.root, w.size);
-  return clu_finish(fr, w, blk, p.min_size, p.max_size, intr, image_rows, image_cols, out, info, counts, 3, labels, st);
+/* One call of ppf_prep_clusters or ppf_prep_regions: the table, the scratch and the launches (clu_begin, the entry's `link`
+ * -- its k_*_runs, clu_cells, its link and flatten passes -- and clu_rank), the one wait, the results.
+ * link(fr, w) -> ppf_status */
+template <bool NORMALS, class Link>
+ppf_status clu_run(const char* who, const ppf_cloud* const* in, int K, int MC, float tolerance, size_t extra, int min_size, int max_size,
+                   const double* intr, int image_rows, int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts, int stride,
+                   int32_t* const* labels, ppf_cluster_stats& st, Link link) {
+  CluWork w{};
+  ppf_status s = clu_table(w, who, in, K, MC);
+  if (s != PPF_OK || w.N == 0) return s; /* no cloud has a row: no cluster, no launch */
+  FrameRun fr;
+  std::shared_ptr<DevBuf<float>> blk(new DevBuf<float>());
+  auto run = [&]() -> ppf_status {
+    ppf_status r;
+    if ((r = clu_begin<NORMALS>(fr, w, *blk, tolerance, extra)) != PPF_OK || (r = link(fr, w)) != PPF_OK) return r;
+    return clu_rank(fr, w, *blk, min_size, max_size, intr, image_rows, image_cols);
+  };
+  const ppf_status ran = run(); /* before w is read */
+  bool want_labels = false;
+  for (int i = 0; labels && i < K; i++) want_labels = want_labels || labels[i];
+  std::vector<uint32_t> z(ran == PPF_OK ? w.z_words : 0);
+  std::vector<CluGrid> grid((size_t)K);
+  std::vector<int32_t> lab(want_labels ? w.N : 0);
+  s = fr.finish(who, ran, {{"counters", w.zero, z.size() * sizeof(uint32_t), z.data()},
+                           {"grids", w.d_grid, grid.size() * sizeof(CluGrid), grid.data()},
+                           {"labels", w.d_labels, w.N * sizeof(int32_t), want_labels ? lab.data() : nullptr}});
+  if (s != PPF_OK || (s = clu_results(w, z, grid, lab, blk, out, info, counts, stride, labels)) != PPF_OK) return s;
+  fr.report(st);
+  return PPF_OK;
 }
 
-/* The body of the C entries ppf_prep_clusters and ppf_prep_regions: the outputs cleared, the argument checks in the order the
- * entries document, one FrameRun and one output block around `enqueue`, the outputs cleared again on an error.
+/* between clu_begin and clu_rank: the runs of the sorted order, the table of cells, the links and the flattening */
+ppf_status clusters_link(FrameRun& fr, CluWork& w) {
+  const dim3 b256(CLU_BLOCK);
+  FRAME_LAUNCH(fr, k_clu_runs, w.rows1_grid, b256, w.d_tab, w.K, (uint32_t)w.N, w.va, w.lkey, w.skey, w.pts, w.flags);
+  HIPCHK(hipGetLastError());
+  const ppf_status s = clu_cells(fr, w);
+  if (s != PPF_OK) return s;
+  FRAME_LAUNCH(fr, k_clu_link, dim3((unsigned)w.N), dim3(64), w.pts, w.ckey, w.cstart, w.runid + w.N, w.tol * w.tol, w.parent);
+  FRAME_LAUNCH(fr, k_clu_flatten, w.rows_grid, b256, (uint32_t)w.N, w.lkey, w.parent, w.root, w.size);
+  return PPF_OK;
+}
+
+/* The body of the C entries ppf_prep_clusters and ppf_prep_regions: one stage_entry whose clear zeroes the stats and the
+ * outputs, around the argument checks in the order the entries document and `run`.
  * max_shown: the entry's max_clusters / max_regions clamped to 1 .. PPF_CLUSTER_MAX_CLUSTERS (1: no params), the length of a
  * cloud's part of out and info; stride: the words a cloud has in counts.  check_params() -> ppf_status;
- * enqueue(fr, blk, st) -> ppf_status runs the call up to its results */
-template <class Check, class Enqueue>
+ * run(st) -> ppf_status is the entry's clu_run */
+template <class Check, class Run>
 ppf_status clu_entry(const char* who, const ppf_cloud* const* in, int n_clouds, int max_shown, int stride, const double* intr, int image_rows,
                      int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts, ppf_cluster_stats* stats, Check check_params,
-                     Enqueue enqueue) {
-  const auto t0 = std::chrono::steady_clock::now();
-  ppf_cluster_stats local;
-  ppf_cluster_stats& st = stats ? *stats : local;
-  std::memset(&st, 0, sizeof(st));
+                     Run run) {
   const bool count_ok = n_clouds >= 0 && n_clouds <= FRAME_MAX_BOXES;
   const size_t slots = count_ok ? (size_t)n_clouds * (size_t)max_shown : 0;
-  auto clear = [&]() {
+  auto clear = [&](ppf_cluster_stats& st, bool) {
+    std::memset(&st, 0, sizeof(st));
     for (size_t k = 0; out && k < slots; k++) out[k] = nullptr;
     if (info && slots) std::memset(info, 0, slots * sizeof(ppf_cluster_info));
     if (counts && count_ok && n_clouds) std::memset(counts, 0, (size_t)n_clouds * stride * sizeof(int32_t));
   };
-  clear();
-  if (!count_ok) return fail(PPF_ERR_INVALID, "%s: n_clouds is %d (0..%d)", who, n_clouds, FRAME_MAX_BOXES);
-  if (!in || !out || !info || !counts) return fail(PPF_ERR_INVALID, "%s: in, out, info and counts must not be NULL", who);
-  ppf_status s = check_params();
-  if (s != PPF_OK) return s;
-  if (intr) {
-    for (int k = 0; k < 4; k++)
-      if (!std::isfinite(intr[k])) return fail(PPF_ERR_INVALID, "%s: the intrinsics are not finite", who);
-    if (image_rows < 1 || image_cols < 1) return fail(PPF_ERR_INVALID, "%s: the image is %d x %d", who, image_rows, image_cols);
-  }
-  for (int i = 0; i < n_clouds; i++)
-    if (!in[i]) return fail(PPF_ERR_INVALID, "%s: in[%d] is NULL", who, i);
-  if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
-  st.n_clouds = n_clouds;
-  if (n_clouds > 0) {
-    FrameRun fr;
-    std::shared_ptr<DevBuf<float>> blk;
-    s = enqueue(fr, blk, st);
-    /* kernels of a failed call may still run: wait before its scratch and the output block go back to the block cache,
-     * where another host thread could be handed them */
-    if (s != PPF_OK) (void)hipDeviceSynchronize();
-  }
-  if (s != PPF_OK) {
-    clear();
-    std::memset(&st, 0, sizeof(st));
-    return s;
-  }
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PPF_OK;
+  return stage_entry(stats, clear, [&](ppf_cluster_stats& st) -> ppf_status {
+    if (!count_ok) return fail(PPF_ERR_INVALID, "%s: n_clouds is %d (0..%d)", who, n_clouds, FRAME_MAX_BOXES);
+    if (!in || !out || !info || !counts) return fail(PPF_ERR_INVALID, "%s: in, out, info and counts must not be NULL", who);
+    const ppf_status s = check_params();
+    if (s != PPF_OK) return s;
+    if (intr) {
+      for (int k = 0; k < 4; k++)
+        if (!std::isfinite(intr[k])) return fail(PPF_ERR_INVALID, "%s: the intrinsics are not finite", who);
+      if (image_rows < 1 || image_cols < 1) return fail(PPF_ERR_INVALID, "%s: the image is %d x %d", who, image_rows, image_cols);
+    }
+    for (int i = 0; i < n_clouds; i++)
+      if (!in[i]) return fail(PPF_ERR_INVALID, "%s: in[%d] is NULL", who, i);
+    if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
+    st.n_clouds = n_clouds;
+    return n_clouds > 0 ? run(st) : PPF_OK;
+  });
 }
 inline int clu_max_shown(int max_components) { return std::min(std::max(max_components, 1), PPF_CLUSTER_MAX_CLUSTERS); }
 
@@ -296,8 +300,9 @@ ppf_status ppf_prep_clusters(const ppf_cloud* const* in, int n_clouds, const ppf
   return clu_entry(
       who, in, n_clouds, p ? clu_max_shown(p->max_clusters) : 1, 3, intr, image_rows, image_cols, out, info, counts, stats,
       [&]() { return cluster_params_check(who, p); },
-      [&](FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, ppf_cluster_stats& st) {
-        return clusters_enqueue(fr, blk, in, n_clouds, *p, intr, image_rows, image_cols, out, info, counts, labels, st);
+      [&](ppf_cluster_stats& st) {
+        return clu_run<false>(who, in, n_clouds, p->max_clusters, p->tolerance, 0, p->min_size, p->max_size, intr, image_rows, image_cols, out, info,
+                              counts, 3, labels, st, clusters_link);
       });
 }
 

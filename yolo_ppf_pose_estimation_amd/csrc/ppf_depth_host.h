@@ -137,7 +137,7 @@ ppf_status ppf_cloud_from_depth_device(const void* d_depth, int rows, int cols, 
                                        const ppf_depth_params* p, void* stream, ppf_cloud** out) {
   static const char* who = "ppf_cloud_from_depth_device";
   DepthArgs a;
-  DepthBuf image;
+  StageBuf image;
   ppf_status s = cloud_depth_check(who, d_depth, rows, cols, row_pitch_bytes, intr, p, out, &a);
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
@@ -173,7 +173,7 @@ ppf_status ppf_cloud_from_depth_normals_device(const void* d_depth, int rows, in
   static const char* who = "ppf_cloud_from_depth_normals_device";
   DepthArgs a;
   DepthNormalArgs na;
-  DepthBuf image;
+  StageBuf image;
   ppf_status s = cloud_depth_check(who, d_depth, rows, cols, row_pitch_bytes, intr, p, out, &a);
   if (s != PPF_OK || (s = depth_normal_check(who, np, rows, cols, &na)) != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);

@@ -1,11 +1,12 @@
 /*
  * ppf_depthimage_host.h — the host front end of every stage that takes a depth image: ppf_cloud_from_depth,
  * ppf_cloud_from_depth_normals, ppf_depth_register, ppf_depth_filter, ppf_depth_segments and ppf_depth_history.  No kernel and
- * no entry of its own.  Included by ppf_hip.hip after ppf_prep_host.h and before ppf_depth_host.h, the first of those stages.
+ * no entry of its own.  Included by ppf_hip.hip after ppf_stage_host.h (StageBuf, stage_finish, stage_entry) and ppf_prep_host.h,
+ * before ppf_depth_host.h, the first of those stages.
  *
  * A stage's host or device function is, in this order: its own NULL checks, depth_image_check, its parameter checks,
- * have_device(), depth_bind_host or depth_bind_device (+ depth_outputs_check), its enqueue, depth_finish, its stats.  Its
- * extern "C" entry is one depth_entry.  What is left in the stage's file is what only that stage knows.
+ * have_device(), depth_bind_host or depth_bind_device (+ depth_outputs_check), its enqueue, stage_finish (FrameRun::finish where
+ * the stage owns a FrameRun), its stats.  Its extern "C" entry is one stage_entry.  What is left in the stage's file is what only that stage knows.
  */
 #ifndef PPF_DEPTHIMAGE_HOST_H
 #define PPF_DEPTHIMAGE_HOST_H
@@ -125,16 +126,7 @@ ppf_status depth_device_range(const char* who, const char* what, const void* d_p
   return PPF_OK;
 }
 
-/* a device buffer of a call: its name in messages, its extent, and where depth_finish copies it (NULL: nowhere).  A NULL dev
- * is an optional buffer the caller left out. */
-struct DepthBuf {
-  const char* what;
-  const void* dev;
-  size_t bytes;
-  void* host;
-};
-
-bool ranges_overlap(const DepthBuf& p, const DepthBuf& q) {
+bool ranges_overlap(const StageBuf& p, const StageBuf& q) {
   const uintptr_t a = (uintptr_t)p.dev, b = (uintptr_t)q.dev;
   return a < b + q.bytes && b < a + p.bytes;
 }
@@ -153,7 +145,7 @@ ppf_status depth_bind_host(const void* depth, int format, DevBuf<unsigned char>&
 }
 
 /* the image of a device entry is read where it is: memory the current device reads directly, whole inside its allocation */
-ppf_status depth_bind_device(const char* who, const void* d_depth, int format, DepthArgs* a, DepthBuf* image) {
+ppf_status depth_bind_device(const char* who, const void* d_depth, int format, DepthArgs* a, StageBuf* image) {
   const size_t rows = (size_t)(a->n / a->cols);
   *image = {"image", d_depth, (rows - 1) * a->pitch + (size_t)a->cols * depth_elem_size(format), nullptr};
   a->img = static_cast<const unsigned char*>(d_depth);
@@ -161,58 +153,16 @@ ppf_status depth_bind_device(const char* who, const void* d_depth, int format, D
 }
 
 /* the outputs of a device entry: each inside its allocation, then none of them over the image or over an earlier one */
-ppf_status depth_outputs_check(const char* who, const DepthBuf& image, std::initializer_list<DepthBuf> outs) {
+ppf_status depth_outputs_check(const char* who, const StageBuf& image, std::initializer_list<StageBuf> outs) {
   ppf_status s;
-  for (const DepthBuf& o : outs)
+  for (const StageBuf& o : outs)
     if (o.dev && (s = depth_device_range(who, o.what, o.dev, o.bytes)) != PPF_OK) return s;
-  for (const DepthBuf* o = outs.begin(); o != outs.end(); ++o) {
+  for (const StageBuf* o = outs.begin(); o != outs.end(); ++o) {
     if (!o->dev) continue;
     if (ranges_overlap(*o, image)) return fail(PPF_ERR_INVALID, "%s: the %s overlaps the %s", who, o->what, image.what);
-    for (const DepthBuf* q = outs.begin(); q != o; ++q)
+    for (const StageBuf* q = outs.begin(); q != o; ++q)
       if (q->dev && ranges_overlap(*o, *q)) return fail(PPF_ERR_INVALID, "%s: the %s overlaps the %s", who, o->what, q->what);
   }
-  return PPF_OK;
-}
-
-/* The one wait of a call.  `enqueued` is what the stage's enqueue returned; when it is PPF_OK the buffers of `back` that have
- * a host address are read back behind the kernels on `st` and the host waits once, for all of it.
- *
- * The rule, for every stage: from its first enqueue on, a call returns only through here.  Its scratch (DevBuf, FrameRun)
- * goes back to the block cache when the caller's scope ends, and the next call may be handed it at once; so when the enqueue,
- * a read-back or the wait has failed, kernels of this call may still be queued on that scratch, and the call waits for the
- * whole device before it returns. */
-ppf_status depth_finish(const char* who, ppf_status enqueued, hipStream_t st, std::initializer_list<DepthBuf> back) {
-  ppf_status s = enqueued;
-  if (s == PPF_OK) {
-    hipError_t e = hipSuccess;
-    for (const DepthBuf& b : back)
-      if (e == hipSuccess && b.host) e = hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = host_stream_sync(st);
-    if (e != hipSuccess) s = fail(PPF_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-  }
-  if (s != PPF_OK) (void)hipDeviceSynchronize();
-  return s;
-}
-
-template <class Stats>
-void depth_clear_stats(Stats& st, bool) {
-  std::memset(&st, 0, sizeof(st));
-}
-
-/* The body of an extern "C" entry: the caller's stats or a local, cleared; the call; cleared again when it failed, ms_wall
- * when it did not.  clear(st, failed) is the stage's: it zeroes the stats and whatever else a failed call must leave zero. */
-template <class Stats, class Clear, class Call>
-ppf_status depth_entry(Stats* stats, Clear clear, Call call) {
-  const auto t0 = std::chrono::steady_clock::now();
-  Stats local;
-  Stats& st = stats ? *stats : local;
-  clear(st, false);
-  const ppf_status s = call(st);
-  if (s != PPF_OK) {
-    clear(st, true);
-    return s;
-  }
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return PPF_OK;
 }
 

@@ -1,7 +1,7 @@
 /*
  * ppf_filter_host.h — host side of ppf_depth_filter / ppf_depth_filter_device: a depth image without its unsupported pixels,
  * smoothed inside each surface.  Kernel: ppf_filter_kernels.h.  Included by ppf_hip.hip after
- * ppf_depthimage_host.h (the image check, the bindings, depth_outputs_check, depth_finish, depth_entry, depth_typed).
+ * ppf_depthimage_host.h (the image check, the bindings, depth_outputs_check, stage_finish, stage_entry, depth_typed).
  *
  * Per call: an 8-byte clear of the counters, k_depth_filter -- one launch -- and one blocking wait, whatever the image
  * holds.  The host entry adds one upload of the image and reads the image and the counters back behind that one wait.
@@ -71,7 +71,7 @@ ppf_status filter_host(const char* who, const void* depth, int rows, int cols, s
   HIPCHK(buf.reserve(n + DF_N_COUNTERS));
   fa.counters = reinterpret_cast<int32_t*>(buf.p + n);
   int32_t c[DF_N_COUNTERS];
-  s = depth_finish(who, filter_enqueue(a, fa, dp->format, buf.p, nullptr), nullptr,
+  s = stage_finish(who, filter_enqueue(a, fa, dp->format, buf.p, nullptr), nullptr,
                    {{"output", buf.p, n * sizeof(float), out}, {"counters", fa.counters, sizeof(c), c}});
   if (s == PPF_OK) filter_fill_stats(st, c);
   return s;
@@ -81,7 +81,7 @@ ppf_status filter_device(const char* who, const void* d_depth, int rows, int col
                          const ppf_depth_filter_params* fp, float* d_out, hipStream_t stream, ppf_depth_filter_stats& st) {
   DepthArgs a;
   DepthFilterArgs fa;
-  DepthBuf image;
+  StageBuf image;
   ppf_status s = filter_check(who, d_depth, rows, cols, row_pitch_bytes, dp, fp, d_out, &a, &fa);
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
@@ -92,7 +92,7 @@ ppf_status filter_device(const char* who, const void* d_depth, int rows, int col
   HIPCHK(counters.reserve(DF_N_COUNTERS));
   fa.counters = counters.p;
   int32_t c[DF_N_COUNTERS];
-  s = depth_finish(who, filter_enqueue(a, fa, dp->format, d_out, stream), stream, {{"counters", counters.p, sizeof(c), c}});
+  s = stage_finish(who, filter_enqueue(a, fa, dp->format, d_out, stream), stream, {{"counters", counters.p, sizeof(c), c}});
   if (s == PPF_OK) filter_fill_stats(st, c);
   return s;
 }
@@ -115,14 +115,14 @@ void ppf_default_depth_filter_params(ppf_depth_filter_params* p) {
 
 ppf_status ppf_depth_filter(const void* depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
                             const ppf_depth_filter_params* fp, float* out, ppf_depth_filter_stats* stats) {
-  return depth_entry(stats, depth_clear_stats<ppf_depth_filter_stats>, [&](ppf_depth_filter_stats& st) {
+  return stage_entry(stats, stage_clear_stats<ppf_depth_filter_stats>, [&](ppf_depth_filter_stats& st) {
     return filter_host("ppf_depth_filter", depth, rows, cols, row_pitch_bytes, dp, fp, out, st);
   });
 }
 
 ppf_status ppf_depth_filter_device(const void* d_depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
                                    const ppf_depth_filter_params* fp, float* d_out, void* stream, ppf_depth_filter_stats* stats) {
-  return depth_entry(stats, depth_clear_stats<ppf_depth_filter_stats>, [&](ppf_depth_filter_stats& st) {
+  return stage_entry(stats, stage_clear_stats<ppf_depth_filter_stats>, [&](ppf_depth_filter_stats& st) {
     return filter_device("ppf_depth_filter_device", d_depth, rows, cols, row_pitch_bytes, dp, fp, d_out, static_cast<hipStream_t>(stream), st);
   });
 }

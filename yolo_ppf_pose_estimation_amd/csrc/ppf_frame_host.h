@@ -3,14 +3,15 @@
  * reference's CloudProcessor returns one cloud per detection from every stage, CloudProcessing.h:263-427).  It is the
  * chain of the segmented stage functions of ppf_prep_host.h (frame_crop ... frame_to_mat; the per-cloud ppf_prep_*
  * entries are the same functions with one segment).  Kernels: ppf_prep_kernels.h.  Included by ppf_hip.hip after
- * ppf_prep_host.h.
+ * ppf_stage_host.h (FrameRun) and ppf_prep_host.h.
  *
  * Each stage works on the concatenation of the K boxes' clouds, with a device table {off, n} per segment.  Counts stay
- * on the device; the host reads back three times, the same for every K:
+ * on the device; the host reads back three times, the same for every K (boxes that crop nothing: the first, and the end's
+ * wait with nothing to read):
  *   1. after the crop: the cropped total (sizes the voxel grid's buffers)
  *   2. after the voxel grid: cells per box, the finite total and the overflow flag (sizes everything after it, and
  *      fails the call before any output exists)
- *   3. at the end: rows per box and stage, and where each box's rows lie in the shared output block.
+ *   3. at the end (FrameRun::finish): rows per box and stage, and where each box's rows lie in the shared output block.
  * Scans run a fixed three-level launch sequence and the voxel sort a fixed number of digit passes, so the launch
  * count does not depend on K either.  The one upload (the K crop-plane sets) happens before any device work.
  */
@@ -18,20 +19,28 @@ namespace {
 
 ppf_status frame_run(FrameRun& fr, const ppf_cloud* scene, const CropPlanes* h_planes, int K, const ppf_frame_params& prm,
                      ppf_cloud** objects, ppf_cloud** edges, int32_t* stage_rows) {
-  ppf_status s;
   SegCloud crop, vox, sor, nrm, edge;
-  if ((s = frame_crop(fr, scene->rows.p, scene->curv.p, scene->n, h_planes, K, nullptr, &crop)) != PPF_OK) return s; /* host sync 1 */
-  if (crop.cap > 0) {
+  std::vector<uint32_t> rep((size_t)K * 6, 0u);
+  uint32_t* d_rep = nullptr;
+  std::shared_ptr<DevBuf<float>> blk;
+  int V = 0;
+  auto run = [&]() -> ppf_status {
+    ppf_status s;
+    if ((s = frame_crop(fr, scene->rows.p, scene->curv.p, scene->n, h_planes, K, nullptr, &crop)) != PPF_OK) return s; /* host sync 1 */
+    if (crop.cap == 0) return PPF_OK;
     uint32_t overflow;
     if ((s = frame_voxel(fr, crop, prm.leaf, nullptr, &vox, &overflow)) != PPF_OK) return s; /* host sync 2 */
     if (overflow != 0xFFFFFFFFu)
       return fail(PPF_ERR_INVALID, "ppf_prep_frame: box %u: leaf size is too small for the cloud (index overflow)", overflow);
-  }
-  const int V = vox.cap;
-  std::vector<uint32_t> rep((size_t)K * 6, 0u);
-  uint32_t* d_rep;
-  std::shared_ptr<DevBuf<float>> blk;
-  if (V > 0) {
+    V = vox.cap;
+    s = fr.get((size_t)K * 6, &d_rep);
+    if (s != PPF_OK) return s;
+    if (V == 0) {
+      /* every box lost all its points in the voxel grid: its crop counts are the only non-zero numbers */
+      FRAME_LAUNCH(fr, k_frame_report, dim3(1), dim3(FRAME_MAX_BOXES), crop.seg, crop.seg, crop.seg, crop.seg, K, d_rep);
+      HIPCHK(hipGetLastError());
+      return PPF_OK;
+    }
     if ((s = frame_outliers(fr, vox, prm.mean_k, prm.stddev_mul, nullptr, &sor, nullptr)) != PPF_OK ||
         (s = frame_normals(fr, sor, prm.normal_k, nullptr, &nrm, nullptr)) != PPF_OK ||
         (s = frame_edges(fr, nrm, prm.curvature_threshold, nullptr, &edge)) != PPF_OK)
@@ -40,20 +49,17 @@ ppf_status frame_run(FrameRun& fr, const ppf_cloud* scene, const CropPlanes* h_p
     blk.reset(new DevBuf<float>());
     HIPCHK(blk->reserve((size_t)V * 14));
     float* const b = blk->p;
-    if ((s = frame_to_mat(fr, nrm, b, b + (size_t)V * 6)) != PPF_OK || (s = frame_to_mat(fr, edge, b + (size_t)V * 7, b + (size_t)V * 13)) != PPF_OK ||
-        (s = fr.get((size_t)K * 6, &d_rep)) != PPF_OK)
+    if ((s = frame_to_mat(fr, nrm, b, b + (size_t)V * 6)) != PPF_OK || (s = frame_to_mat(fr, edge, b + (size_t)V * 7, b + (size_t)V * 13)) != PPF_OK)
       return s;
     FRAME_LAUNCH(fr, k_frame_report, dim3(1), dim3(FRAME_MAX_BOXES), crop.seg, vox.seg, sor.seg, edge.seg, K, d_rep);
     HIPCHK(hipGetLastError());
-    if ((s = fr.read(rep.data(), d_rep, rep.size() * sizeof(uint32_t))) != PPF_OK) return s; /* host sync 3 */
-  } else if (crop.cap > 0) {
-    /* every box lost all its points in the voxel grid: its crop counts are the only non-zero numbers */
-    if ((s = fr.get((size_t)K * 6, &d_rep)) != PPF_OK) return s;
-    FRAME_LAUNCH(fr, k_frame_report, dim3(1), dim3(FRAME_MAX_BOXES), crop.seg, crop.seg, crop.seg, crop.seg, K, d_rep);
-    HIPCHK(hipGetLastError());
-    if ((s = fr.read(rep.data(), d_rep, rep.size() * sizeof(uint32_t))) != PPF_OK) return s;
+    return PPF_OK;
+  };
+  const ppf_status ran = run(); /* before d_rep is read */
+  const ppf_status s = fr.finish("ppf_prep_frame", ran, {{"report", d_rep, rep.size() * sizeof(uint32_t), d_rep ? rep.data() : nullptr}}); /* host sync 3 */
+  if (s != PPF_OK) return s;
+  if (V == 0)
     for (int b = 0; b < K; b++) for (int c = 1; c < 6; c++) rep[(size_t)b * 6 + c] = 0;
-  }
   /* ---- the handles: views into the shared block (none is created before every check has passed) ---- */
   std::vector<std::unique_ptr<ppf_cloud>> obj(K), edg(K);
   for (int b = 0; b < K; b++) {
@@ -124,8 +130,7 @@ ppf_status ppf_prep_frame(const ppf_cloud* scene, const int* boxes_xywh, int n_b
   ppf_status s = n_boxes ? frame_run(fr, scene, planes.data(), n_boxes, prm, objects, edges, stage_rows) : PPF_OK;
   if (stats) {
     stats->n_boxes = n_boxes;
-    stats->n_launches = fr.launches;
-    stats->n_host_syncs = fr.syncs;
+    fr.report(*stats);
     stats->ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   return s;

@@ -28,9 +28,10 @@
  *             ppf_segment_kernels.h  ppf_recognize_kernels.h  ppf_history_kernels.h  ppf_motion_kernels.h
  *             ppf_volume_kernels.h  ppf_volume_mesh_kernels.h  ppf_mesh_kernels.h  ppf_mesh_components_kernels.h
  *   host      ppf_device_mem.h (errors, block cache)  ppf_host_common.h (scans, sorts, model / workspace structs)
- *             ppf_model_host.h  ppf_match_host.h  ppf_batch_host.h  ppf_icp_host.h  ppf_prep_host.h (the segmented
- *             preparation stages; ppf_prep_* = one segment)  ppf_frame_host.h (ppf_prep_frame = their chain)
- *             ppf_match_frame_host.h  ppf_depth_host.h  ppf_posetable_host.h  ppf_verify_host.h  ppf_render_host.h
+ *             ppf_model_host.h  ppf_match_host.h  ppf_batch_host.h  ppf_icp_host.h  ppf_stage_host.h (what every stage call
+ *             shares: FrameRun, stage_finish, stage_entry)  ppf_prep_host.h (the segmented preparation stages; ppf_prep_* = one
+ *             segment)  ppf_frame_host.h (ppf_prep_frame = their chain)
+ *             ppf_match_frame_host.h  ppf_depthimage_host.h  ppf_depth_host.h  ppf_posetable_host.h  ppf_verify_host.h  ppf_render_host.h
  *             ppf_select_host.h  ppf_refine_host.h  ppf_register_host.h  ppf_plane_host.h  ppf_cluster_host.h  ppf_region_host.h
  *             ppf_filter_host.h  ppf_segment_host.h  ppf_recognize_host.h  ppf_history_host.h  ppf_motion_host.h
  *             ppf_volume_host.h  ppf_mesh_components_host.h  ppf_mesh_host.h  (the C-ABI)
@@ -95,10 +96,11 @@
 #include "ppf_match_host.h"    /* C-ABI: workspaces, ppf_match_device, ppf_match, ppf_raw_votes, clustering */
 #include "ppf_batch_host.h"    /* C-ABI: crops x models */
 #include "ppf_icp_host.h"      /* row N2: ICP refinement, host side */
-#include "ppf_prep_host.h"     /* row N4: the segmented cloud stages, FrameRun, ppf_prep_* (one segment each) */
+#include "ppf_stage_host.h"    /* what every stage call shares: FrameRun, frame_scan, frame_sort, stage_finish, stage_entry */
+#include "ppf_prep_host.h"     /* row N4: the segmented cloud stages, ppf_prep_* (one segment each) */
 #include "ppf_frame_host.h"    /* row N4 for all boxes of a frame: ppf_prep_frame, the chain of those stages */
 #include "ppf_match_frame_host.h" /* match + ICP for all detections of a frame: ppf_match_frame */
-#include "ppf_depthimage_host.h"  /* what the stages on a depth image share: checks, bindings, the one wait, the entry body */
+#include "ppf_depthimage_host.h"  /* what the stages on a depth image share: checks, bindings, the outputs check */
 #include "ppf_depth_host.h"       /* the scene cloud from a depth image: ppf_cloud_from_depth */
 #include "ppf_posetable_host.h"   /* what the stages on a frame's pose table share: checks, render jobs, clears */
 #include "ppf_verify_host.h"      /* pose verification of every detection of a frame: ppf_verify_frame */

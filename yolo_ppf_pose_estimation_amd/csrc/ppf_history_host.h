@@ -1,7 +1,7 @@
 /*
  * ppf_history_host.h — host side of ppf_depth_history: a device-resident ring of a camera's last `window` depth images and
  * the fused image every pushed frame gives.  Kernel: ppf_history_kernels.h.  Included by ppf_hip.hip after
- * ppf_depthimage_host.h (the image check, the bindings, depth_outputs_check, depth_finish, depth_entry, depth_typed).
+ * ppf_depthimage_host.h (the image check, the bindings, depth_outputs_check, stage_finish, stage_entry, depth_typed).
  *
  * Per push: a 20-byte clear of the counters, k_history_push -- one launch -- and one blocking wait, whatever the image and
  * the history hold.  The host entry adds one upload of the image and reads the images and the counters back behind that one
@@ -106,7 +106,7 @@ ppf_status history_push_host(const char* who, ppf_depth_history* h, const void* 
   std::vector<float> o(n);
   std::vector<uint8_t> sv(state ? n : 0);
   int32_t c[DH_N_COUNTERS];
-  s = depth_finish(who, history_enqueue(h, a, ha, nullptr), nullptr,
+  s = stage_finish(who, history_enqueue(h, a, ha, nullptr), nullptr,
                    {{"output", buf.p, n * sizeof(float), o.data()},
                     {"state image", sbuf.p, n, state ? sv.data() : nullptr},
                     {"counters", ha.counters, sizeof(c), c}});
@@ -123,7 +123,7 @@ ppf_status history_push_device(const char* who, ppf_depth_history* h, const void
   if (!h) return fail(PPF_ERR_INVALID, "%s: the history is NULL", who);
   if (!d_out) return fail(PPF_ERR_INVALID, "%s: out is NULL", who);
   DepthArgs a;
-  DepthBuf image;
+  StageBuf image;
   ppf_status s = depth_image_check(who, d_depth, h->rows, h->cols, row_pitch_bytes, &h->dp, DEPTH_FLAGS_IGNORED, &a);
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
@@ -134,7 +134,7 @@ ppf_status history_push_device(const char* who, ppf_depth_history* h, const void
   std::lock_guard<std::mutex> lock(h->mu);
   const HistoryArgs ha = history_args(h, a, d_out, d_state);
   int32_t c[DH_N_COUNTERS];
-  s = depth_finish(who, history_enqueue(h, a, ha, stream), stream, {{"counters", ha.counters, sizeof(c), c}});
+  s = stage_finish(who, history_enqueue(h, a, ha, stream), stream, {{"counters", ha.counters, sizeof(c), c}});
   if (s != PPF_OK) return s;
   history_fill_stats(st, c, h);
   h->t++;
@@ -198,14 +198,14 @@ ppf_status ppf_depth_history_create(int rows, int cols, const ppf_depth_params* 
 
 ppf_status ppf_depth_history_push(ppf_depth_history* h, const void* depth, size_t row_pitch_bytes, float* out, uint8_t* state,
                                   ppf_depth_history_stats* stats) {
-  return depth_entry(stats, depth_clear_stats<ppf_depth_history_stats>, [&](ppf_depth_history_stats& st) {
+  return stage_entry(stats, stage_clear_stats<ppf_depth_history_stats>, [&](ppf_depth_history_stats& st) {
     return history_push_host("ppf_depth_history_push", h, depth, row_pitch_bytes, out, state, st);
   });
 }
 
 ppf_status ppf_depth_history_push_device(ppf_depth_history* h, const void* d_depth, size_t row_pitch_bytes, float* d_out, uint8_t* d_state,
                                          void* stream, ppf_depth_history_stats* stats) {
-  return depth_entry(stats, depth_clear_stats<ppf_depth_history_stats>, [&](ppf_depth_history_stats& st) {
+  return stage_entry(stats, stage_clear_stats<ppf_depth_history_stats>, [&](ppf_depth_history_stats& st) {
     return history_push_device("ppf_depth_history_push_device", h, d_depth, row_pitch_bytes, d_out, d_state, static_cast<hipStream_t>(stream), st);
   });
 }

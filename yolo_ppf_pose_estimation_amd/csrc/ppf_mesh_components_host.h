@@ -1,8 +1,8 @@
 /*
  * ppf_mesh_components_host.h — host side of ppf_volume_mesh_upload and ppf_volume_mesh_components: a triangle mesh from host
  * arrays, and a mesh's connected components counted, measured, ranked by area and filtered.  Kernels:
- * ppf_mesh_components_kernels.h.  Included by ppf_hip.hip after ppf_volume_host.h (ppf_volume_mesh) and ppf_prep_host.h
- * (FrameRun, frame_scan, frame_sort).
+ * ppf_mesh_components_kernels.h.  Included by ppf_hip.hip after ppf_stage_host.h (FrameRun, frame_scan, frame_sort, stage_entry)
+ * and ppf_volume_host.h (ppf_volume_mesh, mesh_alloc).
  *
  *   components  two clears (the sums and the counters: zeros; the edge table's keys and the lower bounds: all ones), k_mc_init,
  *               k_mc_unite, k_mc_flatten, k_mc_tris, k_mc_edges, a frame_scan, k_mc_comps, eight radix passes over ~area_q
@@ -15,18 +15,6 @@
 #define PPF_MESH_COMPONENTS_HOST_H
 
 namespace {
-
-ppf_status mesh_alloc(const char* who, std::unique_ptr<ppf_volume_mesh>& m, int64_t nv, int64_t nt) {
-  m.reset(new (std::nothrow) ppf_volume_mesh());
-  if (!m) return fail(PPF_ERR_NOMEM, "%s: out of host memory", who);
-  m->nv = nv;
-  m->nt = nt;
-  if (m->verts.reserve((size_t)std::max<int64_t>(nv, 1) * 6) != hipSuccess || m->tris.reserve((size_t)std::max<int64_t>(nt, 1) * 3) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(PPF_ERR_NOMEM, "%s: a mesh of %lld vertices and %lld triangles cannot be allocated", who, (long long)nv, (long long)nt);
-  }
-  return PPF_OK;
-}
 
 ppf_status mesh_components(const char* who, const ppf_volume_mesh* m, const ppf_mesh_component_params* p, ppf_volume_mesh** out, int32_t* labels,
                            ppf_mesh_component_info* info, int cap_info, ppf_mesh_component_stats& st) {
@@ -58,15 +46,10 @@ ppf_status mesh_components(const char* who, const ppf_volume_mesh* m, const ppf_
       *tkeep, *tpos;
   int32_t* dlabels;
   ppf_mesh_component_info* dinfo;
-  if ((s = fr.get(z64, &zero64)) != PPF_OK || (s = fr.get(z32, &zero32)) != PPF_OK || (s = fr.get(slots, &ones64)) != PPF_OK ||
-      (s = fr.get(o32, &ones32)) != PPF_OK || (s = fr.get(np, &parent)) != PPF_OK || (s = fr.get(np, &root)) != PPF_OK ||
-      (s = fr.get(np + 1, &flags)) != PPF_OK || (s = fr.get(np + 1, &cid)) != PPF_OK || (s = fr.get(np, &comp_root)) != PPF_OK ||
-      (s = fr.get(np, &klo)) != PPF_OK || (s = fr.get(np, &khi)) != PPF_OK || (s = fr.get(np, &kb)) != PPF_OK || (s = fr.get(np, &va)) != PPF_OK ||
-      (s = fr.get(np, &vb)) != PPF_OK || (s = fr.get((size_t)256 * nblk, &hist)) != PPF_OK || (s = fr.get((size_t)256 * nblk, &offs)) != PPF_OK ||
-      (s = fr.get(np, &rank_of)) != PPF_OK || (s = fr.get(np, &keep_of)) != PPF_OK || (s = fr.get(np + 1, &vkeep)) != PPF_OK ||
-      (s = fr.get(np + 1, &vpos)) != PPF_OK || (s = fr.get((size_t)nt + 1, &tkeep)) != PPF_OK || (s = fr.get((size_t)nt + 1, &tpos)) != PPF_OK ||
-      (s = fr.get(np, &dlabels)) != PPF_OK || (s = fr.get((size_t)std::max<uint32_t>(cap, 1), &dinfo)) != PPF_OK)
-    return s;
+  s = fr.get(z64, &zero64, z32, &zero32, slots, &ones64, o32, &ones32, np, &parent, np, &root, np + 1, &flags, np + 1, &cid, np, &comp_root, np, &klo,
+             np, &khi, np, &kb, np, &va, np, &vb, (size_t)256 * nblk, &hist, (size_t)256 * nblk, &offs, np, &rank_of, np, &keep_of, np + 1, &vkeep,
+             np + 1, &vpos, (size_t)nt + 1, &tkeep, (size_t)nt + 1, &tpos, np, &dlabels, (size_t)std::max<uint32_t>(cap, 1), &dinfo);
+  if (s != PPF_OK) return s;
   McAcc acc;
   acc.area_q = zero64;
   unsigned long long* ctr = zero64 + np;
@@ -117,11 +100,8 @@ ppf_status mesh_components(const char* who, const ppf_volume_mesh* m, const ppf_
                  dlabels);
     HIPCHK(hipGetLastError());
     if ((r = frame_scan(fr, vkeep, vpos, (size_t)nv + 1)) != PPF_OK || (r = frame_scan(fr, tkeep, tpos, (size_t)nt + 1)) != PPF_OK) return r;
-    HIPCHK(hipMemcpyAsync(&nv_out, vpos + nv, sizeof(nv_out), hipMemcpyDeviceToHost, fr.st));
-    HIPCHK(hipMemcpyAsync(&nt_out, tpos + nt, sizeof(nt_out), hipMemcpyDeviceToHost, fr.st));
-    HIPCHK(hipMemcpyAsync(c, ctr, sizeof(c), hipMemcpyDeviceToHost, fr.st));
-    HIPCHK(host_stream_sync(fr.st)); /* the sizing read-back */
-    fr.syncs++;
+    r = fr.sizing({{"vertices kept", vpos + nv, sizeof(nv_out), &nv_out}, {"triangles kept", tpos + nt, sizeof(nt_out), &nt_out}, {"counters", ctr, sizeof(c), c}});
+    if (r != PPF_OK) return r;
     if (!out) return PPF_OK;
     if ((r = mesh_alloc(who, o, nv_out, nt_out)) != PPF_OK) return r;
     FRAME_LAUNCH(fr, k_mc_write_vertices, grid_for((size_t)nv * 6, MC_BLOCK), block, (size_t)nv * 6, reinterpret_cast<const uint32_t*>(m->verts.p),
@@ -133,19 +113,16 @@ ppf_status mesh_components(const char* who, const ppf_volume_mesh* m, const ppf_
   const ppf_status ran = run();
   const size_t n_info = ran == PPF_OK ? (size_t)std::min<unsigned long long>(c[MC_N_COMPONENTS], cap) : 0;
   /* the end: the scratch goes back to the block cache at scope exit */
-  s = depth_finish(who, ran, fr.st,
-                   {{"labels", dlabels, (size_t)nv * sizeof(int32_t), nv ? labels : nullptr},
-                    {"info", dinfo, n_info * sizeof(*dinfo), n_info ? info : nullptr}});
+  s = fr.finish(who, ran, {{"labels", dlabels, (size_t)nv * sizeof(int32_t), nv ? labels : nullptr},
+                           {"info", dinfo, n_info * sizeof(*dinfo), n_info ? info : nullptr}});
   if (s != PPF_OK) return s;
-  fr.syncs++;
   st.n_components = (int64_t)c[MC_N_COMPONENTS];
   st.n_kept = (int64_t)c[MC_N_KEPT];
   st.n_unreferenced = (int64_t)c[MC_N_UNREFERENCED];
   st.n_bad_area = (int64_t)c[MC_N_BAD_AREA];
   st.n_vertices_out = nv_out;
   st.n_triangles_out = nt_out;
-  st.n_launches = fr.launches;
-  st.n_host_syncs = fr.syncs;
+  fr.report(st);
   if (out) *out = o.release();
   return PPF_OK;
 }
@@ -219,7 +196,7 @@ ppf_status ppf_debug_volume_mesh_shell(int64_t n_vertices, int64_t n_triangles, 
 
 ppf_status ppf_volume_mesh_components(const ppf_volume_mesh* m, const ppf_mesh_component_params* p, ppf_volume_mesh** out, int32_t* labels,
                                       ppf_mesh_component_info* info, int cap_info, ppf_mesh_component_stats* stats) {
-  return depth_entry(
+  return stage_entry(
       stats,
       [&](ppf_mesh_component_stats& st, bool failed) {
         std::memset(&st, 0, sizeof(st));

@@ -1,7 +1,7 @@
 /*
  * ppf_mesh_host.h — host side of ppf_cloud_from_mesh: a model cloud sampled from a triangle mesh.
- * Kernels: ppf_mesh_kernels.h.  Included by ppf_hip.hip after ppf_prep_host.h (ppf_cloud, FrameRun, frame_scan) and
- * ppf_depthimage_host.h (depth_finish: the one way out of a call once it has enqueued).
+ * Kernels: ppf_mesh_kernels.h.  Included by ppf_hip.hip after ppf_stage_host.h (FrameRun, frame_scan, stage_entry;
+ * FrameRun::finish is the one way out of a call once it has enqueued) and ppf_prep_host.h (ppf_cloud).
  *
  *   without visibility   k_mesh_tri, k_mesh_area, frame_scan (5), k_mesh_sample: 8 launches
  *   with visibility      those, then k_mesh_draw_small, k_mesh_draw_large, k_mesh_visible, frame_scan (5), k_mesh_scatter: 17
@@ -129,10 +129,9 @@ ppf_status mesh_sample(const char* who, const float* vertices, int n_vertices, i
   uint8_t* live;
   double* area_part;
   MeshCounters* d_C;
-  if ((s = fr.get(n_vfloats, &d_vert)) != PPF_OK || (s = fr.get((size_t)nt * 3, &d_tri)) != PPF_OK || (s = fr.get((size_t)nt + 1, &nk)) != PPF_OK ||
-      (s = fr.get((size_t)nt + 1, &offs)) != PPF_OK || (s = fr.get((size_t)nt, &live)) != PPF_OK ||
-      (s = fr.get((size_t)tri_grid.x, &area_part)) != PPF_OK || (s = fr.get((size_t)1, &d_C)) != PPF_OK)
-    return s;
+  s = fr.get(n_vfloats, &d_vert, (size_t)nt * 3, &d_tri, (size_t)nt + 1, &nk, (size_t)nt + 1, &offs, (size_t)nt, &live, (size_t)tri_grid.x, &area_part,
+             (size_t)1, &d_C);
+  if (s != PPF_OK) return s;
   std::unique_ptr<ppf_cloud> c;
   MeshCounters C;
   MeshViews W;
@@ -148,9 +147,7 @@ ppf_status mesh_sample(const char* who, const float* vertices, int n_vertices, i
     HIPCHK(hipGetLastError());
     ppf_status r = frame_scan(fr, nk, offs, (size_t)nt + 1);
     if (r != PPF_OK) return r;
-    HIPCHK(hipMemcpyAsync(&C, d_C, sizeof(C), hipMemcpyDeviceToHost, fr.st));
-    HIPCHK(host_stream_sync(fr.st)); /* the sizing read-back */
-    fr.syncs++;
+    if ((r = fr.sizing({{"counters", d_C, sizeof(C), &C}})) != PPF_OK) return r;
     if (C.over || (double)C.total > max_rows)
       return fail(PPF_ERR_CAPACITY, "%s: the mesh gives more than max_rows = %.0f rows at spacing %g", who, max_rows, (double)p->spacing);
     total = (uint32_t)C.total; /* at most max_rows <= INT32_MAX: the scan of the n_k did not wrap */
@@ -167,10 +164,8 @@ ppf_status mesh_sample(const char* who, const float* vertices, int n_vertices, i
     MeshViews* d_W;
     uint32_t *maps, *list, *keep;
     float* rows;
-    if ((r = fr.get((size_t)1, &d_W)) != PPF_OK || (r = fr.get(map_px, &maps)) != PPF_OK ||
-        (r = fr.get((size_t)nt * PPF_MESH_VIEWS, &list)) != PPF_OK || (r = fr.get((size_t)total * 6, &rows)) != PPF_OK ||
-        (r = fr.get((size_t)total + 1, &keep)) != PPF_OK || (r = fr.get((size_t)total + 1, &pos)) != PPF_OK)
-      return r;
+    r = fr.get((size_t)1, &d_W, map_px, &maps, (size_t)nt * PPF_MESH_VIEWS, &list, (size_t)total * 6, &rows, (size_t)total + 1, &keep, (size_t)total + 1, &pos);
+    if (r != PPF_OK) return r;
     HIPCHK(hipMemcpyAsync(d_W, &W, sizeof(W), hipMemcpyHostToDevice, fr.st));
     HIPCHK(hipMemsetAsync(maps, 0xff, map_px * sizeof(uint32_t), fr.st));
     FRAME_LAUNCH(fr, k_mesh_sample, row_grid, blk, d_vert, vstride, noff, d_tri, nt, offs, total, p->seed, rows, (float*)nullptr);
@@ -185,11 +180,9 @@ ppf_status mesh_sample(const char* who, const float* vertices, int n_vertices, i
   };
   const ppf_status enq = run();
   const bool vis = enq == PPF_OK && p->visibility;
-  s = depth_finish(who, enq, fr.st,
-                   {{"kept rows", vis ? pos + total : nullptr, sizeof(n_rows), vis ? &n_rows : nullptr},
-                    {"counters", d_C, sizeof(C), vis ? &C : nullptr}}); /* the end: the scratch goes back at scope exit */
+  s = fr.finish(who, enq, {{"kept rows", vis ? pos + total : nullptr, sizeof(n_rows), vis ? &n_rows : nullptr},
+                           {"counters", d_C, sizeof(C), vis ? &C : nullptr}}); /* the end: the scratch goes back at scope exit */
   if (s != PPF_OK) return s;
-  fr.syncs++;
   c->n = (int)n_rows;
   st.n_triangles = n_triangles;
   st.n_degenerate = (int64_t)C.degenerate;
@@ -198,8 +191,7 @@ ppf_status mesh_sample(const char* who, const float* vertices, int n_vertices, i
   st.n_hidden = (int64_t)total - (int64_t)n_rows;
   st.n_flipped = (int64_t)C.flipped;
   st.n_large = (int64_t)C.large;
-  st.n_launches = fr.launches;
-  st.n_host_syncs = fr.syncs;
+  fr.report(st);
   st.area = C.area;
   *out = c.release();
   return PPF_OK;
@@ -220,15 +212,15 @@ void ppf_default_mesh_sample_params(ppf_mesh_sample_params* p) {
 
 ppf_status ppf_cloud_from_mesh(const float* vertices, int n_vertices, int vstride, int normal_offset, const int32_t* triangles, int n_triangles,
                                const ppf_mesh_sample_params* p, ppf_cloud** out, ppf_mesh_sample_stats* stats) {
-  ppf_mesh_sample_stats local;
-  ppf_mesh_sample_stats& st = stats ? *stats : local;
-  std::memset(&st, 0, sizeof(st));
-  const ppf_status s = mesh_sample("ppf_cloud_from_mesh", vertices, n_vertices, vstride, normal_offset, triangles, n_triangles, p, out, st);
-  if (s != PPF_OK) {
-    std::memset(&st, 0, sizeof(st));
-    if (out) *out = nullptr;
-  }
-  return s;
+  return stage_entry(
+      stats,
+      [&](ppf_mesh_sample_stats& st, bool failed) {
+        std::memset(&st, 0, sizeof(st));
+        if (failed && out) *out = nullptr;
+      },
+      [&](ppf_mesh_sample_stats& st) {
+        return mesh_sample("ppf_cloud_from_mesh", vertices, n_vertices, vstride, normal_offset, triangles, n_triangles, p, out, st);
+      });
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 /*
  * ppf_motion_host.h — host side of ppf_depth_motion / ppf_depth_motion_device: the camera's motion between two depth images
  * (DESIGN.md §28).  Kernels: ppf_motion_kernels.h.  Included by ppf_hip.hip after ppf_depthimage_host.h (the image check, the
- * bindings, depth_finish, depth_entry, depth_typed).
+ * bindings, stage_finish, stage_entry, depth_typed).
  *
  * Per call: k_motion_level0, levels - 1 k_motion_down, levels k_motion_maps, then per level from the coarsest and per
  * evaluation k < iters[l]: k_motion_eval, k_motion_group while more than DM_TAIL_MAX partial rows are left (and once when
@@ -222,7 +222,7 @@ ppf_status motion_host(const char* who, const void* prev, size_t prev_pitch, con
   double T0[16];
   motion_start(init16, T0);
   MotionState S;
-  s = depth_finish(who, motion_enqueue(a0, a1, dp->format, mp, T0, P, scratch.p, nullptr), nullptr,
+  s = stage_finish(who, motion_enqueue(a0, a1, dp->format, mp, T0, P, scratch.p, nullptr), nullptr,
                    {{"state", scratch.p + P.o_state, sizeof(S), &S}});
   if (s == PPF_OK) motion_report(S, P, pose16, level_rows, st);
   return s;
@@ -232,7 +232,7 @@ ppf_status motion_device(const char* who, const void* d_prev, size_t prev_pitch,
                          const double* intr, const ppf_depth_params* dp, const ppf_depth_motion_params* mp, const double* init16,
                          hipStream_t stream, double* pose16, ppf_depth_motion_level* level_rows, ppf_depth_motion_stats& st) {
   DepthArgs a0, a1;
-  DepthBuf image0, image1;
+  StageBuf image0, image1;
   ppf_status s = motion_check(who, d_prev, prev_pitch, d_cur, cur_pitch, rows, cols, intr, dp, mp, init16, pose16, &a0, &a1);
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
@@ -248,7 +248,7 @@ ppf_status motion_device(const char* who, const void* d_prev, size_t prev_pitch,
   double T0[16];
   motion_start(init16, T0);
   MotionState S;
-  s = depth_finish(who, motion_enqueue(a0, a1, dp->format, mp, T0, P, scratch.p, stream), stream,
+  s = stage_finish(who, motion_enqueue(a0, a1, dp->format, mp, T0, P, scratch.p, stream), stream,
                    {{"state", scratch.p + P.o_state, sizeof(S), &S}});
   if (s == PPF_OK) motion_report(S, P, pose16, level_rows, st);
   return s;
@@ -292,7 +292,7 @@ void ppf_default_depth_motion_params(ppf_depth_motion_params* p) {
 ppf_status ppf_depth_motion(const void* prev, size_t prev_pitch_bytes, const void* cur, size_t cur_pitch_bytes, int rows, int cols,
                             const double* intr, const ppf_depth_params* dp, const ppf_depth_motion_params* mp, const double* init16,
                             double* pose16, ppf_depth_motion_level* level_rows, ppf_depth_motion_stats* stats) {
-  return depth_entry(
+  return stage_entry(
       stats,
       [&](ppf_depth_motion_stats& st, bool failed) {
         std::memset(&st, 0, sizeof(st));
@@ -307,7 +307,7 @@ ppf_status ppf_depth_motion_device(const void* d_prev, size_t prev_pitch_bytes, 
                                    int cols, const double* intr, const ppf_depth_params* dp, const ppf_depth_motion_params* mp,
                                    const double* init16, void* stream, double* pose16, ppf_depth_motion_level* level_rows,
                                    ppf_depth_motion_stats* stats) {
-  return depth_entry(
+  return stage_entry(
       stats,
       [&](ppf_depth_motion_stats& st, bool failed) {
         std::memset(&st, 0, sizeof(st));

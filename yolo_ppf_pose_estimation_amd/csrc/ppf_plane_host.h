@@ -1,7 +1,7 @@
 /*
  * ppf_plane_host.h — host side of ppf_prep_planes and ppf_prep_planes_apply: the support planes of up to 256 clouds found
- * and removed in one pass.  Kernels: ppf_plane_kernels.h.  Included by ppf_hip.hip after ppf_prep_host.h
- * (ppf_cloud, FrameRun, frame_scan, frame_compact, one_segment).
+ * and removed in one pass.  Kernels: ppf_plane_kernels.h.  Included by ppf_hip.hip after ppf_stage_host.h
+ * (FrameRun, frame_scan, stage_entry) and ppf_prep_host.h (ppf_cloud, frame_compact, one_segment).
  *
  * Per call: one upload of the segment table before any device work, then k_pln_load, per round
  *   k_pln_hyp, k_pln_count, k_pln_best, [k_pln_sum<3>, k_pln_finish<3>, k_pln_sum<6>, k_pln_finish<6>, k_pln_recount,
@@ -32,9 +32,8 @@ ppf_status plane_params_check(const char* who, const ppf_plane_params* p) {
   return PPF_OK;
 }
 
-/* fr and blk belong to the caller: on an error they outlive the wait for what was launched */
-ppf_status planes_enqueue(FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, const ppf_cloud* const* in, int K, const ppf_plane_params& p,
-                          ppf_cloud** out, ppf_plane_info* info, uint8_t* const* labels, ppf_plane_stats& st) {
+ppf_status planes_run(const ppf_cloud* const* in, int K, const ppf_plane_params& p, ppf_cloud** out, ppf_plane_info* info,
+                      uint8_t* const* labels, ppf_plane_stats& st) {
   static const char* who = "ppf_prep_planes";
   const int R = p.max_planes, H = p.n_hypotheses;
   std::vector<PlnSeg> tab((size_t)K);
@@ -62,57 +61,53 @@ ppf_status planes_enqueue(FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, con
   double *hyp, *part, *ta, *tb;
   uint32_t *cnt, *flags, *pos;
   const size_t tree = (T / 64 + (size_t)K + 1) * 6;
-  ppf_status s;
-  if ((s = fr.get(K, &d_tab)) != PPF_OK || (s = fr.get(K, &d_work)) != PPF_OK || (s = fr.get((size_t)K * R, &d_info)) != PPF_OK ||
-      (s = fr.get(N, &lpa)) != PPF_OK || (s = fr.get(N, &lpb)) != PPF_OK || (s = fr.get(N, &d_labels)) != PPF_OK ||
-      (s = fr.get((size_t)K * H * 4, &hyp)) != PPF_OK || (s = fr.get((size_t)K * H, &cnt)) != PPF_OK || (s = fr.get(T * 6, &part)) != PPF_OK ||
-      (s = fr.get(tree, &ta)) != PPF_OK || (s = fr.get(tree, &tb)) != PPF_OK || (s = fr.get(N + 1, &flags)) != PPF_OK ||
-      (s = fr.get(N + 1, &pos)) != PPF_OK)
-    return s;
-  blk.reset(new DevBuf<float>());
+  FrameRun fr;
+  std::shared_ptr<DevBuf<float>> blk(new DevBuf<float>());
+  ppf_status s = fr.get(K, &d_tab, K, &d_work, (size_t)K * R, &d_info, N, &lpa, N, &lpb, N, &d_labels, (size_t)K * H * 4, &hyp, (size_t)K * H, &cnt,
+                        T * 6, &part, tree, &ta, tree, &tb, N + 1, &flags, N + 1, &pos);
+  if (s != PPF_OK) return s;
   HIPCHK(blk->reserve(N * 7)); /* [rows | curvature] */
   HIPCHK(hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(PlnSeg), hipMemcpyHostToDevice));
-  HIPCHK(hipMemsetAsync(d_work, 0, (size_t)K * sizeof(PlnWork), nullptr));
-  HIPCHK(hipMemsetAsync(d_info, 0, (size_t)K * R * sizeof(ppf_plane_info), nullptr));
-
-  const dim3 tiles((unsigned)T), blk256(PLN_BLOCK), hyp_blocks((unsigned)((H + PLN_BLOCK - 1) / PLN_BLOCK));
-  const double thr = (double)p.distance_threshold;
-  const int behind = (p.flags & PPF_PLANE_REMOVE_BEHIND) ? 1 : 0;
-  FRAME_LAUNCH(fr, k_pln_load, tiles, blk256, d_tab, K, lpa, d_labels, d_work);
-  for (int r = 0; r < R; r++) {
-    FRAME_LAUNCH(fr, k_pln_hyp, dim3(hyp_blocks.x, (unsigned)K), blk256, d_tab, d_work, lpa, r, p.seed, H, hyp, cnt);
-    FRAME_LAUNCH(fr, k_pln_count, dim3((unsigned)(T * PLN_SPANS), hyp_blocks.x), blk256, d_tab, K, d_work, lpa, hyp, H, thr, cnt);
-    FRAME_LAUNCH(fr, k_pln_best, dim3((unsigned)K), blk256, d_work, hyp, cnt, H, (int)p.min_inliers, (double)p.min_inlier_share, r, R, d_info);
-    if (!(p.flags & PPF_PLANE_NO_REFIT)) {
-      FRAME_LAUNCH(fr, k_pln_sum<3>, tiles, blk256, d_tab, K, d_work, lpa, thr, part);
-      FRAME_LAUNCH(fr, k_pln_finish<3>, dim3((unsigned)K), blk256, d_tab, d_work, part, ta, tb);
-      FRAME_LAUNCH(fr, k_pln_sum<6>, tiles, blk256, d_tab, K, d_work, lpa, thr, part);
-      FRAME_LAUNCH(fr, k_pln_finish<6>, dim3((unsigned)K), blk256, d_tab, d_work, part, ta, tb);
-      FRAME_LAUNCH(fr, k_pln_recount, tiles, blk256, d_tab, K, d_work, lpa, thr);
-      FRAME_LAUNCH(fr, k_pln_choose, dim3(1), dim3(FRAME_MAX_BOXES), d_work, K, r, R, d_info);
+  auto run = [&]() -> ppf_status {
+    HIPCHK(hipMemsetAsync(d_work, 0, (size_t)K * sizeof(PlnWork), nullptr));
+    HIPCHK(hipMemsetAsync(d_info, 0, (size_t)K * R * sizeof(ppf_plane_info), nullptr));
+    const dim3 tiles((unsigned)T), blk256(PLN_BLOCK), hyp_blocks((unsigned)((H + PLN_BLOCK - 1) / PLN_BLOCK));
+    const double thr = (double)p.distance_threshold;
+    const int behind = (p.flags & PPF_PLANE_REMOVE_BEHIND) ? 1 : 0;
+    FRAME_LAUNCH(fr, k_pln_load, tiles, blk256, d_tab, K, lpa, d_labels, d_work);
+    for (int r = 0; r < R; r++) {
+      FRAME_LAUNCH(fr, k_pln_hyp, dim3(hyp_blocks.x, (unsigned)K), blk256, d_tab, d_work, lpa, r, p.seed, H, hyp, cnt);
+      FRAME_LAUNCH(fr, k_pln_count, dim3((unsigned)(T * PLN_SPANS), hyp_blocks.x), blk256, d_tab, K, d_work, lpa, hyp, H, thr, cnt);
+      FRAME_LAUNCH(fr, k_pln_best, dim3((unsigned)K), blk256, d_work, hyp, cnt, H, (int)p.min_inliers, (double)p.min_inlier_share, r, R, d_info);
+      if (!(p.flags & PPF_PLANE_NO_REFIT)) {
+        FRAME_LAUNCH(fr, k_pln_sum<3>, tiles, blk256, d_tab, K, d_work, lpa, thr, part);
+        FRAME_LAUNCH(fr, k_pln_finish<3>, dim3((unsigned)K), blk256, d_tab, d_work, part, ta, tb);
+        FRAME_LAUNCH(fr, k_pln_sum<6>, tiles, blk256, d_tab, K, d_work, lpa, thr, part);
+        FRAME_LAUNCH(fr, k_pln_finish<6>, dim3((unsigned)K), blk256, d_tab, d_work, part, ta, tb);
+        FRAME_LAUNCH(fr, k_pln_recount, tiles, blk256, d_tab, K, d_work, lpa, thr);
+        FRAME_LAUNCH(fr, k_pln_choose, dim3(1), dim3(FRAME_MAX_BOXES), d_work, K, r, R, d_info);
+      }
+      FRAME_LAUNCH(fr, k_pln_flags, tiles, blk256, d_tab, K, d_work, lpa, thr, behind, r, R, (uint32_t)N, flags, d_labels, d_info);
+      HIPCHK(hipGetLastError());
+      const ppf_status q = frame_scan(fr, flags, pos, N + 1);
+      if (q != PPF_OK) return q;
+      FRAME_LAUNCH(fr, k_pln_compact, tiles, blk256, d_tab, K, d_work, lpa, flags, pos, lpb);
+      std::swap(lpa, lpb);
     }
-    FRAME_LAUNCH(fr, k_pln_flags, tiles, blk256, d_tab, K, d_work, lpa, thr, behind, r, R, (uint32_t)N, flags, d_labels, d_info);
+    FRAME_LAUNCH(fr, k_pln_gather, tiles, blk256, d_tab, K, d_work, lpa, blk->p, blk->p + N * 6);
     HIPCHK(hipGetLastError());
-    if ((s = frame_scan(fr, flags, pos, N + 1)) != PPF_OK) return s;
-    FRAME_LAUNCH(fr, k_pln_compact, tiles, blk256, d_tab, K, d_work, lpa, flags, pos, lpb);
-    std::swap(lpa, lpb);
-  }
-  FRAME_LAUNCH(fr, k_pln_gather, tiles, blk256, d_tab, K, d_work, lpa, blk->p, blk->p + N * 6);
-  HIPCHK(hipGetLastError());
-
-  /* the one wait: the rows kept per cloud, the info rows, the labels */
+    return PPF_OK;
+  };
+  const ppf_status ran = run();
+  /* the one wait: the rows kept per cloud, the info rows, the labels (their host arrays are made while the kernels run) */
   std::vector<PlnWork> work((size_t)K);
-  std::vector<uint8_t> lab;
   bool want_labels = false;
   for (int i = 0; labels && i < K; i++) want_labels = want_labels || labels[i];
-  HIPCHK(hipMemcpyAsync(work.data(), d_work, work.size() * sizeof(PlnWork), hipMemcpyDeviceToHost, nullptr));
-  HIPCHK(hipMemcpyAsync(info, d_info, (size_t)K * R * sizeof(ppf_plane_info), hipMemcpyDeviceToHost, nullptr));
-  if (want_labels) {
-    lab.resize(N);
-    HIPCHK(hipMemcpyAsync(lab.data(), d_labels, N, hipMemcpyDeviceToHost, nullptr));
-  }
-  fr.syncs++;
-  HIPCHK(hipStreamSynchronize(nullptr));
+  std::vector<uint8_t> lab(want_labels ? N : 0);
+  s = fr.finish(who, ran, {{"work", d_work, work.size() * sizeof(PlnWork), work.data()},
+                             {"info", d_info, (size_t)K * R * sizeof(ppf_plane_info), info},
+                             {"labels", d_labels, N, want_labels ? lab.data() : nullptr}});
+  if (s != PPF_OK) return s;
   for (int i = 0; i < K; i++) {
     res[i].reset(new ppf_cloud());
     res[i]->n = (int)work[i].m;
@@ -122,20 +117,8 @@ ppf_status planes_enqueue(FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, con
     if (want_labels && labels[i] && tab[i].n) std::memcpy(labels[i], lab.data() + tab[i].off, tab[i].n);
   }
   for (int i = 0; i < K; i++) out[i] = res[i].release();
-  st.n_launches = fr.launches;
-  st.n_host_syncs = fr.syncs;
+  fr.report(st);
   return PPF_OK;
-}
-
-ppf_status planes_run(const ppf_cloud* const* in, int K, const ppf_plane_params& p, ppf_cloud** out, ppf_plane_info* info,
-                      uint8_t* const* labels, ppf_plane_stats& st) {
-  FrameRun fr;
-  std::shared_ptr<DevBuf<float>> blk;
-  const ppf_status s = planes_enqueue(fr, blk, in, K, p, out, info, labels, st);
-  /* kernels of a failed call may still run: wait before its scratch and the output block go back to the block cache,
-   * where another host thread could be handed them */
-  if (s != PPF_OK) (void)hipDeviceSynchronize();
-  return s;
 }
 
 }  // namespace
@@ -156,33 +139,24 @@ void ppf_default_plane_params(ppf_plane_params* p) {
 ppf_status ppf_prep_planes(const ppf_cloud* const* in, int n_clouds, const ppf_plane_params* p, ppf_cloud** out, ppf_plane_info* info,
                            uint8_t* const* labels, ppf_plane_stats* stats) {
   static const char* who = "ppf_prep_planes";
-  const auto t0 = std::chrono::steady_clock::now();
-  ppf_plane_stats local;
-  ppf_plane_stats& st = stats ? *stats : local;
-  std::memset(&st, 0, sizeof(st));
   const bool count_ok = n_clouds >= 0 && n_clouds <= FRAME_MAX_BOXES;
   const size_t info_rows = count_ok ? (size_t)n_clouds * (size_t)(p ? std::min(std::max(p->max_planes, 1), PPF_PLANE_MAX_PLANES) : 1) : 0;
-  auto clear = [&]() {
+  auto clear = [&](ppf_plane_stats& st, bool) {
+    std::memset(&st, 0, sizeof(st));
     for (int i = 0; out && count_ok && i < n_clouds; i++) out[i] = nullptr;
     if (info && info_rows) std::memset(info, 0, info_rows * sizeof(ppf_plane_info));
   };
-  clear();
-  if (!count_ok) return fail(PPF_ERR_INVALID, "%s: n_clouds is %d (0..%d)", who, n_clouds, FRAME_MAX_BOXES);
-  if (!in || !out || !info) return fail(PPF_ERR_INVALID, "%s: in, out and info must not be NULL", who);
-  ppf_status s = plane_params_check(who, p);
-  if (s != PPF_OK) return s;
-  for (int i = 0; i < n_clouds; i++)
-    if (!in[i]) return fail(PPF_ERR_INVALID, "%s: in[%d] is NULL", who, i);
-  if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
-  st.n_clouds = n_clouds;
-  if (n_clouds > 0) s = planes_run(in, n_clouds, *p, out, info, labels, st);
-  if (s != PPF_OK) {
-    clear();
-    std::memset(&st, 0, sizeof(st));
-    return s;
-  }
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PPF_OK;
+  return stage_entry(stats, clear, [&](ppf_plane_stats& st) -> ppf_status {
+    if (!count_ok) return fail(PPF_ERR_INVALID, "%s: n_clouds is %d (0..%d)", who, n_clouds, FRAME_MAX_BOXES);
+    if (!in || !out || !info) return fail(PPF_ERR_INVALID, "%s: in, out and info must not be NULL", who);
+    const ppf_status s = plane_params_check(who, p);
+    if (s != PPF_OK) return s;
+    for (int i = 0; i < n_clouds; i++)
+      if (!in[i]) return fail(PPF_ERR_INVALID, "%s: in[%d] is NULL", who, i);
+    if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
+    st.n_clouds = n_clouds;
+    return n_clouds > 0 ? planes_run(in, n_clouds, *p, out, info, labels, st) : PPF_OK;
+  });
 }
 
 ppf_status ppf_prep_planes_apply(const ppf_cloud* in, const ppf_plane_info* planes, int n_planes, const ppf_plane_params* p,
@@ -210,12 +184,17 @@ ppf_status ppf_prep_planes_apply(const ppf_cloud* in, const ppf_plane_info* plan
   FrameRun fr;
   SegCloud seg, res;
   uint32_t* flags;
-  if ((s = one_segment(fr, in, &seg)) != PPF_OK || (s = fr.get((size_t)in->n + 1, &flags)) != PPF_OK) return s;
-  FRAME_LAUNCH(fr, k_pln_apply_flags, grid_for((size_t)in->n + 1, PLN_BLOCK), dim3(PLN_BLOCK), in->rows.p, in->n, pl, (double)p->distance_threshold,
-               (p->flags & PPF_PLANE_REMOVE_BEHIND) ? 1 : 0, flags);
-  HIPCHK(hipGetLastError());
-  if ((s = frame_compact(fr, seg, flags, c.get(), &res)) != PPF_OK) return s;
-  HIPCHK(hipDeviceSynchronize());
+  s = fr.get((size_t)in->n + 1, &flags);
+  if (s != PPF_OK) return s;
+  auto run = [&]() -> ppf_status {
+    const ppf_status r = one_segment(fr, in, &seg);
+    if (r != PPF_OK) return r;
+    FRAME_LAUNCH(fr, k_pln_apply_flags, grid_for((size_t)in->n + 1, PLN_BLOCK), dim3(PLN_BLOCK), in->rows.p, in->n, pl, (double)p->distance_threshold,
+                 (p->flags & PPF_PLANE_REMOVE_BEHIND) ? 1 : 0, flags);
+    HIPCHK(hipGetLastError());
+    return frame_compact(fr, seg, flags, c.get(), &res);
+  };
+  if ((s = fr.finish(who, run(), {})) != PPF_OK) return s;
   *out = c.release();
   return PPF_OK;
 }

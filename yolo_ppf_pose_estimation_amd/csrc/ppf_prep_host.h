@@ -1,10 +1,11 @@
 /*
  * ppf_prep_host.h — host side of the stages that produce the matcher's input (row N4): the device-resident ppf_cloud,
  * the segmented stage functions (crop, voxel grid, outlier removal, normals, edges, to-Mat over K segments of one
- * concatenated cloud; frame_knn, frame_scan, frame_sort and frame_compact beneath them), the C-ABI entry points ppf_cloud_* and
+ * concatenated cloud; frame_knn and frame_compact beneath them), the C-ABI entry points ppf_cloud_* and
  * ppf_prep_* (each stage function with one segment) and the resident ppf_match_clouds / ppf_icp_refine_clouds.
  * ppf_prep_frame chains the same functions for all boxes of a frame (ppf_frame_host.h).  Kernels: ppf_prep_kernels.h.
- * Included by ppf_hip.hip (one translation unit: shares DevBuf, fail(), HIPCHK and the scan and radix-sort kernels).
+ * Included by ppf_hip.hip after ppf_stage_host.h (FrameRun, FRAME_LAUNCH, frame_scan, frame_sort, grid_for; one translation
+ * unit: shares DevBuf, fail(), HIPCHK and the scan and radix-sort kernels).
  */
 /* ============================================================================================ */
 /* Pre-processing stages (row N4; kernels in ppf_prep_kernels.h)                                  */
@@ -32,8 +33,6 @@ struct ppf_cloud {
 #define PPF_KNN_GDIV 4.0
 #endif
 namespace {
-
-inline dim3 grid_for(size_t items, int block) { return dim3((unsigned)std::max<size_t>((items + block - 1) / block, 1)); }
 
 ppf_status cloud_reserve(ppf_cloud* c, int n) {
   c->n = n;
@@ -90,77 +89,7 @@ bool crop_planes(const int* box_xywh, const float* depth, int depth_rows, int de
   return true;
 }
 
-/* ---- the segmented stages ---------------------------------------------------------------------------------------- */
-/* one call's launches, counted, on one stream (the null stream unless the entry has a stream argument), and its scratch,
- * from the block cache; it lives until the call returns (after the last read-back) */
-struct FrameRun {
-  hipStream_t st = nullptr;
-  int launches = 0, syncs = 0;
-  struct Holder {
-    virtual ~Holder() {}
-  };
-  template <class T>
-  struct Buf : Holder {
-    DevBuf<T> b;
-  };
-  std::vector<std::unique_ptr<Holder>> keep;
-  template <class T>
-  ppf_status get(size_t n, T** out) {
-    std::unique_ptr<Buf<T>> h(new Buf<T>());
-    HIPCHK(h->b.reserve(std::max<size_t>(n, 1)));
-    *out = h->b.p;
-    keep.push_back(std::move(h));
-    return PPF_OK;
-  }
-  /* a blocking read-back (counted), on the null stream: the stages that run on a caller's stream never call it */
-  ppf_status read(void* dst, const void* src, size_t bytes) {
-    syncs++;
-    HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-    return PPF_OK;
-  }
-};
-
-#define FRAME_LAUNCH(fr, kern, grid, block, ...)        \
-  do {                                                  \
-    kern<<<(grid), (block), 0, (fr).st>>>(__VA_ARGS__); \
-    (fr).launches++;                                    \
-  } while (0)
-
-/* exclusive scan of n u32 in five launches whatever n is (device_exclusive_scan picks its launches by n and waits for
- * its scratch; here the scratch lives in `fr`) */
-ppf_status frame_scan(FrameRun& fr, const uint32_t* in, uint32_t* out, size_t n) {
-  const size_t nb1 = std::max<size_t>((n + 1023) / 1024, 1), nb2 = (nb1 + 1023) / 1024;
-  uint32_t *s1, *s1x, *s2, *s2x;
-  ppf_status s;
-  if ((s = fr.get(nb1, &s1)) != PPF_OK || (s = fr.get(nb1, &s1x)) != PPF_OK || (s = fr.get(nb2, &s2)) != PPF_OK ||
-      (s = fr.get(nb2, &s2x)) != PPF_OK)
-    return s;
-  FRAME_LAUNCH(fr, k_scan_block, dim3((unsigned)nb1), dim3(256), in, out, s1, n);
-  FRAME_LAUNCH(fr, k_scan_block, dim3((unsigned)nb2), dim3(256), s1, s1x, s2, nb1);
-  FRAME_LAUNCH(fr, k_scan_one, dim3(1), dim3(1024), s2, s2x, nb2);
-  FRAME_LAUNCH(fr, k_scan_add, grid_for(nb1, 256), dim3(256), s1x, s2x, nb1);
-  FRAME_LAUNCH(fr, k_scan_add, grid_for(n, 256), dim3(256), out, s1x, n);
-  HIPCHK(hipGetLastError());
-  return PPF_OK;
-}
-
-/* the frame-level radix sort: stable LSD passes over the digits at `shifts` of keys ka (values va), seven launches a pass
- * whatever n is (hist and offs: 256 words per RS_BLOCK rows each); the sorted arrays end in ka / va */
-ppf_status frame_sort(FrameRun& fr, uint32_t*& ka, uint32_t*& va, uint32_t*& kb, uint32_t*& vb, int n, uint32_t* hist, uint32_t* offs,
-                      const int* shifts, int passes) {
-  const int nblk = (n + RS_BLOCK - 1) / RS_BLOCK;
-  ppf_status s;
-  for (int pass = 0; pass < passes; pass++) {
-    FRAME_LAUNCH(fr, k_rs_hist, dim3(nblk), dim3(RS_BLOCK), ka, n, shifts[pass], nblk, hist);
-    HIPCHK(hipGetLastError());
-    if ((s = frame_scan(fr, hist, offs, (size_t)256 * nblk)) != PPF_OK) return s;
-    FRAME_LAUNCH(fr, k_rs_scatter, dim3(nblk), dim3(RS_BLOCK), ka, va, n, shifts[pass], nblk, offs, kb, vb);
-    HIPCHK(hipGetLastError());
-    std::swap(ka, kb);
-    std::swap(va, vb);
-  }
-  return PPF_OK;
-}
+/* ---- the segmented stages (FrameRun, frame_scan and frame_sort: ppf_stage_host.h) ------------------------------- */
 /* by a 32-bit key, then by segment (skey[row], below 256): a segment's rows end up together, in key order, equal keys in row
  * order.  Five passes and one gather */
 ppf_status frame_sort_segmented(FrameRun& fr, uint32_t*& ka, uint32_t*& va, uint32_t*& kb, uint32_t*& vb, int n, uint32_t* hist,
@@ -185,9 +114,9 @@ struct SegCloud {
 
 /* where a stage writes its n result rows: scratch of the run, or the fresh cloud `own` that the caller hands out */
 ppf_status frame_rows(FrameRun& fr, ppf_cloud* own, int n, float** rows, float** curv) {
-  ppf_status s;
-  if (!own) return (s = fr.get((size_t)n * 6, rows)) != PPF_OK ? s : fr.get(n, curv);
-  if ((s = cloud_reserve(own, n)) != PPF_OK) return s;
+  if (!own) return fr.get((size_t)n * 6, rows, n, curv);
+  const ppf_status s = cloud_reserve(own, n);
+  if (s != PPF_OK) return s;
   *rows = own->rows.p;
   *curv = own->curv.p;
   return PPF_OK;
@@ -200,10 +129,8 @@ ppf_status frame_crop(FrameRun& fr, const float* rows, const float* curv, int n,
   CropPlanes* planes;
   uint32_t *cflags, *cpos;
   FrameSeg* seg_c;
-  ppf_status s;
-  if ((s = fr.get(K, &planes)) != PPF_OK || (s = fr.get((size_t)K * n + 1, &cflags)) != PPF_OK ||
-      (s = fr.get((size_t)K * n + 1, &cpos)) != PPF_OK || (s = fr.get(K, &seg_c)) != PPF_OK)
-    return s;
+  ppf_status s = fr.get(K, &planes, (size_t)K * n + 1, &cflags, (size_t)K * n + 1, &cpos, K, &seg_c);
+  if (s != PPF_OK) return s;
   HIPCHK(hipMemcpy(planes, h_planes, (size_t)K * sizeof(CropPlanes), hipMemcpyHostToDevice));
   FRAME_LAUNCH(fr, k_frame_crop_flags, dim3(grid_for(n, 256).x, K), dim3(256), rows, n, K, planes, cflags);
   HIPCHK(hipGetLastError());
@@ -229,13 +156,9 @@ ppf_status frame_voxel(FrameRun& fr, const SegCloud& in, double leaf, ppf_cloud*
   uint32_t *mm, *fin, *err, *k1, *k2, *v1, *v2, *lkey, *skey, *rflags, *runid, *starts, *d_head;
   VoxelGridDims* dims;
   FrameSeg* seg_v;
-  ppf_status s;
-  if ((s = fr.get((size_t)K * 6, &mm)) != PPF_OK || (s = fr.get(K, &fin)) != PPF_OK || (s = fr.get(1, &err)) != PPF_OK ||
-      (s = fr.get(K, &dims)) != PPF_OK || (s = fr.get(C, &k1)) != PPF_OK || (s = fr.get(C, &k2)) != PPF_OK ||
-      (s = fr.get(C, &v1)) != PPF_OK || (s = fr.get(C, &v2)) != PPF_OK || (s = fr.get(C, &lkey)) != PPF_OK ||
-      (s = fr.get(C, &skey)) != PPF_OK || (s = fr.get((size_t)C + 1, &rflags)) != PPF_OK || (s = fr.get((size_t)C + 1, &runid)) != PPF_OK ||
-      (s = fr.get(C, &starts)) != PPF_OK || (s = fr.get((size_t)K + 3, &d_head)) != PPF_OK || (s = fr.get(K, &seg_v)) != PPF_OK)
-    return s;
+  ppf_status s = fr.get((size_t)K * 6, &mm, K, &fin, 1, &err, K, &dims, C, &k1, C, &k2, C, &v1, C, &v2, C, &lkey, C, &skey, (size_t)C + 1, &rflags,
+                        (size_t)C + 1, &runid, C, &starts, (size_t)K + 3, &d_head, K, &seg_v);
+  if (s != PPF_OK) return s;
   FRAME_LAUNCH(fr, k_frame_bounds, dim3(K), dim3(256), in.rows, in.seg, mm, fin);
   FRAME_LAUNCH(fr, k_frame_voxel_dims, dim3(1), dim3(FRAME_MAX_BOXES), mm, fin, K, 1.0f / (float)leaf, dims, err);
   FRAME_LAUNCH(fr, k_frame_voxel_keys, grid_for(C, 256), dim3(256), in.rows, C, in.seg, K, dims, k1, lkey, skey, v1);
@@ -243,7 +166,8 @@ ppf_status frame_voxel(FrameRun& fr, const SegCloud& in, double leaf, ppf_cloud*
   /* by the local cell index (< 2^31; non-finite points ~0), then by the segment */
   const int nblk = (C + RS_BLOCK - 1) / RS_BLOCK;
   uint32_t *hist, *offs;
-  if ((s = fr.get((size_t)256 * nblk, &hist)) != PPF_OK || (s = fr.get((size_t)256 * nblk, &offs)) != PPF_OK) return s;
+  s = fr.get((size_t)256 * nblk, &hist, (size_t)256 * nblk, &offs);
+  if (s != PPF_OK) return s;
   uint32_t *ka = k1, *va = v1, *kb = k2, *vb = v2;
   if ((s = frame_sort_segmented(fr, ka, va, kb, vb, C, hist, offs, skey)) != PPF_OK) return s;
   FRAME_LAUNCH(fr, k_frame_voxel_runs, grid_for((size_t)C + 1, 256), dim3(256), va, lkey, skey, C, rflags);
@@ -294,12 +218,9 @@ ppf_status frame_knn(FrameRun& fr, const SegCloud& in, int mode, int k, int kstr
   uint32_t *zeroed, *cell_base, *keys, *cell_begin;
   KnnGrid* grids;
   float4* pts;
-  ppf_status s;
-  if ((s = fr.get(cells_cap + 1 + (size_t)K * 7, &zeroed)) != PPF_OK || (s = fr.get(K, &grids)) != PPF_OK ||
-      (s = fr.get(K + 1, &cell_base)) != PPF_OK || (s = fr.get(K, &out->keff)) != PPF_OK || (s = fr.get(K + 1, &out->chunk_base)) != PPF_OK ||
-      (s = fr.get(cap, &keys)) != PPF_OK || (s = fr.get(cells_cap + 1, &cell_begin)) != PPF_OK || (s = fr.get(cap, &pts)) != PPF_OK || (s = fr.get(cap, &out->q4)) != PPF_OK ||
-      (s = fr.get((size_t)cap * kstride, &out->idx)) != PPF_OK || (s = fr.get((size_t)cap * kstride, &out->d2)) != PPF_OK)
-    return s;
+  ppf_status s = fr.get(cells_cap + 1 + (size_t)K * 7, &zeroed, K, &grids, K + 1, &cell_base, K, &out->keff, K + 1, &out->chunk_base, cap, &keys,
+                        cells_cap + 1, &cell_begin, cap, &pts, cap, &out->q4, (size_t)cap * kstride, &out->idx, (size_t)cap * kstride, &out->d2);
+  if (s != PPF_OK) return s;
   /* one fill zeroes the cell counts and, behind them, the bounds that the workgroups of a segment combine */
   uint32_t *const cell_count = zeroed, *const mm = zeroed + cells_cap + 1;
   out->fin = mm + (size_t)K * 6;
@@ -323,8 +244,8 @@ ppf_status frame_compact(FrameRun& fr, const SegCloud& in, const uint32_t* flags
   uint32_t* pos;
   FrameSeg* seg_out;
   float *orows, *ocurv;
-  ppf_status s;
-  if ((s = fr.get((size_t)in.cap + 1, &pos)) != PPF_OK || (s = fr.get(in.K, &seg_out)) != PPF_OK) return s;
+  ppf_status s = fr.get((size_t)in.cap + 1, &pos, in.K, &seg_out);
+  if (s != PPF_OK) return s;
   if ((s = frame_scan(fr, flags, pos, (size_t)in.cap + 1)) != PPF_OK) return s;
   uint32_t kept = (uint32_t)in.cap;
   if (own && (s = fr.read(&kept, pos + in.cap, sizeof(uint32_t))) != PPF_OK) return s;
@@ -346,9 +267,8 @@ ppf_status frame_outliers(FrameRun& fr, const SegCloud& in, int mean_k, double s
   double *parts, *thr;
   ppf_status s;
   if ((s = frame_knn(fr, in, 0, mean_k, mean_k + 1, &nn)) != PPF_OK) return s;
-  if ((s = fr.get(V, &dist)) != PPF_OK || (s = fr.get((size_t)cap_chunks * 2, &parts)) != PPF_OK || (s = fr.get(K, &thr)) != PPF_OK ||
-      (s = fr.get((size_t)V + 1, &oflags)) != PPF_OK)
-    return s;
+  s = fr.get(V, &dist, (size_t)cap_chunks * 2, &parts, K, &thr, (size_t)V + 1, &oflags);
+  if (s != PPF_OK) return s;
   FRAME_LAUNCH(fr, k_frame_sor_dist, grid_for(V, 256), dim3(256), nn.d2, V, in.seg, K, nn.keff, mean_k, dist);
   FRAME_LAUNCH(fr, k_frame_sor_chunks, grid_for(cap_chunks, 64), dim3(64), dist, cap_chunks, in.seg, K, nn.chunk_base, parts);
   FRAME_LAUNCH(fr, k_frame_sor_threshold, dim3(K), dim3(64), parts, in.seg, nn.chunk_base, stddev_mul, thr);
@@ -377,8 +297,8 @@ ppf_status frame_normals(FrameRun& fr, const SegCloud& in, int k, ppf_cloud* own
 /* EdgeExtraction: segmented compaction on curvature */
 ppf_status frame_edges(FrameRun& fr, const SegCloud& in, float curvature_threshold, ppf_cloud* own, SegCloud* out) {
   uint32_t* eflags;
-  ppf_status s;
-  if ((s = fr.get((size_t)in.cap + 1, &eflags)) != PPF_OK) return s;
+  const ppf_status s = fr.get((size_t)in.cap + 1, &eflags);
+  if (s != PPF_OK) return s;
   FRAME_LAUNCH(fr, k_frame_curv_flags, grid_for((size_t)in.cap + 1, 256), dim3(256), in.curv, in.cap, in.seg, in.K, curvature_threshold, eflags);
   HIPCHK(hipGetLastError());
   return frame_compact(fr, in, eflags, own, out);
@@ -404,12 +324,9 @@ ppf_status one_segment(FrameRun& fr, const ppf_cloud* in, SegCloud* c) {
   return PPF_OK;
 }
 
-/* the segmented search skips a segment that holds non-finite rows; a single cloud reports it.  The read-back is also
- * the stage's closing wait for the device */
-ppf_status prep_all_finite(FrameRun& fr, const uint32_t* fin, int n) {
-  uint32_t finite = 0;
-  ppf_status s = fr.read(&finite, fin, sizeof(uint32_t));
-  if (s != PPF_OK) return s;
+/* the segmented search skips a segment that holds non-finite rows; a single cloud reports it.  `finite` is the count the
+ * stage's closing wait brought back */
+ppf_status prep_all_finite(uint32_t finite, int n) {
   if (finite != (uint32_t)n) return fail(PPF_ERR_INVALID, "neighbour search: the cloud holds non-finite points (crop or voxel-grid it first)");
   return PPF_OK;
 }
@@ -489,8 +406,7 @@ ppf_status ppf_prep_crop(const ppf_cloud* in, const int* box_xywh, const float* 
   std::unique_ptr<ppf_cloud> c(new ppf_cloud());
   FrameRun fr;
   SegCloud res;
-  if ((s = frame_crop(fr, in->rows.p, in->curv.p, in->n, &pl, 1, c.get(), &res)) != PPF_OK) return s;
-  HIPCHK(hipDeviceSynchronize());
+  if ((s = fr.finish("ppf_prep_crop", frame_crop(fr, in->rows.p, in->curv.p, in->n, &pl, 1, c.get(), &res), {})) != PPF_OK) return s;
   *out = c.release();
   return PPF_OK;
 }
@@ -504,10 +420,14 @@ ppf_status ppf_prep_voxel_grid(const ppf_cloud* in, double leaf, ppf_cloud** out
   std::unique_ptr<ppf_cloud> c(new ppf_cloud());
   FrameRun fr;
   SegCloud seg, res;
-  uint32_t overflow;
-  if ((s = one_segment(fr, in, &seg)) != PPF_OK || (s = frame_voxel(fr, seg, leaf, c.get(), &res, &overflow)) != PPF_OK) return s;
-  if (overflow != 0xFFFFFFFFu) return fail(PPF_ERR_INVALID, "ppf_prep_voxel_grid: leaf size is too small for the cloud (index overflow)");
-  HIPCHK(hipDeviceSynchronize());
+  auto run = [&]() -> ppf_status {
+    uint32_t overflow;
+    ppf_status r;
+    if ((r = one_segment(fr, in, &seg)) != PPF_OK || (r = frame_voxel(fr, seg, leaf, c.get(), &res, &overflow)) != PPF_OK) return r;
+    if (overflow != 0xFFFFFFFFu) return fail(PPF_ERR_INVALID, "ppf_prep_voxel_grid: leaf size is too small for the cloud (index overflow)");
+    return PPF_OK;
+  };
+  if ((s = fr.finish("ppf_prep_voxel_grid", run(), {})) != PPF_OK) return s;
   *out = c.release();
   return PPF_OK;
 }
@@ -520,15 +440,19 @@ ppf_status ppf_prep_knn(const ppf_cloud* in, int k, int* idx, float* d2) {
   if (n == 0) return PPF_OK;
   FrameRun fr;
   SegCloud seg;
-  FrameKnn nn;
-  ppf_status s;
-  if ((s = one_segment(fr, in, &seg)) != PPF_OK || (s = frame_knn(fr, seg, 1, k, ke, &nn)) != PPF_OK ||
-      (s = prep_all_finite(fr, nn.fin, n)) != PPF_OK)
-    return s;
+  FrameKnn nn = {};
   std::vector<int> hi((size_t)n * ke);
   std::vector<float> hd((size_t)n * ke);
-  HIPCHK(hipMemcpy(hi.data(), nn.idx, hi.size() * sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(hd.data(), nn.d2, hd.size() * sizeof(float), hipMemcpyDeviceToHost));
+  uint32_t finite = 0;
+  auto run = [&]() -> ppf_status {
+    const ppf_status r = one_segment(fr, in, &seg);
+    return r != PPF_OK ? r : frame_knn(fr, seg, 1, k, ke, &nn);
+  };
+  const ppf_status ran = run(); /* before nn is read */
+  ppf_status s = fr.finish("ppf_prep_knn", ran, {{"finite rows", nn.fin, sizeof(finite), &finite},
+                                                 {"indices", nn.idx, hi.size() * sizeof(int), hi.data()},
+                                                 {"distances", nn.d2, hd.size() * sizeof(float), hd.data()}});
+  if (s != PPF_OK || (s = prep_all_finite(finite, n)) != PPF_OK) return s;
   for (int i = 0; i < n; i++)
     for (int m = 0; m < k; m++) {
       idx[(size_t)i * k + m] = m < ke ? hi[(size_t)i * ke + m] : -1;
@@ -546,13 +470,17 @@ ppf_status ppf_prep_outlier_removal(const ppf_cloud* in, int mean_k, double stdd
   std::unique_ptr<ppf_cloud> c(new ppf_cloud());
   FrameRun fr;
   SegCloud seg, res;
-  const uint32_t* fin;
-  if ((s = one_segment(fr, in, &seg)) != PPF_OK || (s = frame_outliers(fr, seg, mean_k, stddev_mul, c.get(), &res, &fin)) != PPF_OK) return s;
-  if (in->n > mean_k) {
-    if ((s = prep_all_finite(fr, fin, in->n)) != PPF_OK) return s;
-  } else { /* nothing is measured and every row is kept; the search's launches still run, with k_eff = 0 and no cells */
-    HIPCHK(hipDeviceSynchronize());
-  }
+  const uint32_t* fin = nullptr;
+  uint32_t finite = 0;
+  auto run = [&]() -> ppf_status {
+    const ppf_status r = one_segment(fr, in, &seg);
+    return r != PPF_OK ? r : frame_outliers(fr, seg, mean_k, stddev_mul, c.get(), &res, &fin);
+  };
+  /* with n <= meanK nothing is measured and every row is kept; the search's launches still run, with k_eff = 0 and no cells */
+  const bool searched = in->n > mean_k;
+  const ppf_status ran = run(); /* before fin is read */
+  s = fr.finish("ppf_prep_outlier_removal", ran, {{"finite rows", fin, sizeof(finite), searched ? &finite : nullptr}});
+  if (s != PPF_OK || (searched && (s = prep_all_finite(finite, in->n)) != PPF_OK)) return s;
   *out = c.release();
   return PPF_OK;
 }
@@ -566,10 +494,15 @@ ppf_status ppf_prep_normals(const ppf_cloud* in, int k, ppf_cloud** out) {
   std::unique_ptr<ppf_cloud> c(new ppf_cloud());
   FrameRun fr;
   SegCloud seg, res;
-  const uint32_t* fin;
-  if ((s = one_segment(fr, in, &seg)) != PPF_OK || (s = frame_normals(fr, seg, k, c.get(), &res, &fin)) != PPF_OK ||
-      (s = prep_all_finite(fr, fin, in->n)) != PPF_OK)
-    return s;
+  const uint32_t* fin = nullptr;
+  uint32_t finite = 0;
+  auto run = [&]() -> ppf_status {
+    const ppf_status r = one_segment(fr, in, &seg);
+    return r != PPF_OK ? r : frame_normals(fr, seg, k, c.get(), &res, &fin);
+  };
+  const ppf_status ran = run(); /* before fin is read */
+  s = fr.finish("ppf_prep_normals", ran, {{"finite rows", fin, sizeof(finite), &finite}});
+  if (s != PPF_OK || (s = prep_all_finite(finite, in->n)) != PPF_OK) return s;
   *out = c.release();
   return PPF_OK;
 }
@@ -582,8 +515,11 @@ ppf_status ppf_prep_edges(const ppf_cloud* in, float curvature_threshold, ppf_cl
   std::unique_ptr<ppf_cloud> c(new ppf_cloud());
   FrameRun fr;
   SegCloud seg, res;
-  if ((s = one_segment(fr, in, &seg)) != PPF_OK || (s = frame_edges(fr, seg, curvature_threshold, c.get(), &res)) != PPF_OK) return s;
-  HIPCHK(hipDeviceSynchronize());
+  auto run = [&]() -> ppf_status {
+    const ppf_status r = one_segment(fr, in, &seg);
+    return r != PPF_OK ? r : frame_edges(fr, seg, curvature_threshold, c.get(), &res);
+  };
+  if ((s = fr.finish("ppf_prep_edges", run(), {})) != PPF_OK) return s;
   *out = c.release();
   return PPF_OK;
 }
@@ -596,10 +532,12 @@ ppf_status ppf_prep_to_mat(const ppf_cloud* in, ppf_cloud** out) {
   std::unique_ptr<ppf_cloud> c;
   FrameRun fr;
   SegCloud seg;
-  if ((s = cloud_alloc(c, in->n)) != PPF_OK || (s = one_segment(fr, in, &seg)) != PPF_OK ||
-      (s = frame_to_mat(fr, seg, c->rows.p, c->curv.p)) != PPF_OK)
-    return s;
-  HIPCHK(hipDeviceSynchronize());
+  if ((s = cloud_alloc(c, in->n)) != PPF_OK) return s;
+  auto run = [&]() -> ppf_status {
+    const ppf_status r = one_segment(fr, in, &seg);
+    return r != PPF_OK ? r : frame_to_mat(fr, seg, c->rows.p, c->curv.p);
+  };
+  if ((s = fr.finish("ppf_prep_to_mat", run(), {})) != PPF_OK) return s;
   *out = c.release();
   return PPF_OK;
 }

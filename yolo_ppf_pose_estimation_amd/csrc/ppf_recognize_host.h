@@ -1,7 +1,7 @@
 /*
  * ppf_recognize_host.h — host side of ppf_recognizer_* and ppf_recognize_frame: per proposal cloud a shortlist of the trained
- * models it can be a view of.  Kernels: ppf_recognize_kernels.h.  Included by ppf_hip.hip after ppf_prep_host.h
- * (ppf_cloud, FrameRun, FRAME_LAUNCH, grid_for) and ppf_model_host.h.
+ * models it can be a view of.  Kernels: ppf_recognize_kernels.h.  Included by ppf_hip.hip after ppf_stage_host.h
+ * (FrameRun, FRAME_LAUNCH, stage_entry), ppf_prep_host.h (ppf_cloud) and ppf_model_host.h.
  *
  * Create, per model: k_rec_dmax, one read-back (the bitmap's size), k_rec_build, k_rec_popcount, one read-back (the bitmap and
  * n_keys).  A frame call: one work list built from the row counts (a cloud handle knows its size), one upload, one memset of the
@@ -91,10 +91,8 @@ ppf_status recognizer_create(const ppf_model* const* models, int n_models, ppf_r
     rec->sets.emplace_back(new ppf_recognizer::Set());
     ppf_recognizer::Set& s = *rec->sets.back();
     const ppf_status st = recognizer_build_set(m, s);
-    if (st != PPF_OK) {
-      (void)hipDeviceSynchronize(); /* kernels of the failed build may still run on blocks that now return to the cache */
-      return st;
-    }
+    /* kernels of the failed build may still run on blocks that now return to the cache: stage_finish drains the device */
+    if (st != PPF_OK) return stage_finish("ppf_recognizer_create", st, nullptr, {});
     RecModel& t = table[(size_t)i];
     t.bits = s.bits.p; t.words = s.words; t.n_a = s.n_a; t.n_d = s.n_d; t.lds = s.lds; t.pad = 0;
     t.angle_step = m->info.angle_step; t.dist_step = m->info.distance_step;
@@ -180,10 +178,9 @@ ppf_status recognize_frame(const ppf_recognizer* rec, const ppf_cloud* const* cl
   const size_t z_head = (z_counts + z_used + 7) / 8 * 8, z_bytes = z_head + std::max<size_t>(hit_words, 1) * sizeof(uint32_t);
   FrameRun fr;
   unsigned char *d_blob, *d_zero;
-  ppf_status s;
-  if ((s = fr.get(blob.size(), &d_blob)) != PPF_OK || (s = fr.get(z_bytes, &d_zero)) != PPF_OK) return s;
+  ppf_status s = fr.get(blob.size(), &d_blob, z_bytes, &d_zero);
+  if (s != PPF_OK) return s;
   HIPCHK(hipMemcpy(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemsetAsync(d_zero, 0, z_bytes, fr.st));
   const RecCloud* d_clouds = reinterpret_cast<const RecCloud*>(d_blob);
   const unsigned long long* d_off = reinterpret_cast<const unsigned long long*>(d_blob + b_clouds);
   const RecItem* d_items = reinterpret_cast<const RecItem*>(d_blob + b_clouds + b_off);
@@ -191,19 +188,19 @@ ppf_status recognize_frame(const ppf_recognizer* rec, const ppf_cloud* const* cl
   int32_t* d_used = reinterpret_cast<int32_t*>(d_zero + z_counts);
   uint32_t* d_hits = reinterpret_cast<uint32_t*>(d_zero + z_head);
   const int n_items = (int)h_items.size();
-  k_rec_score<<<dim3((unsigned)std::max(n_items, 1)), dim3(REC_BLOCK), lds_bytes, fr.st>>>(d_items, n_items, d_clouds, rec->d_models.p, row_cap,
-                                                                                          rec->lds_words, d_hits, d_off, d_counts, d_used);
-  fr.launches++;
-  FRAME_LAUNCH(fr, k_rec_finish, dim3((unsigned)std::max<size_t>(n_pairs, 1)), dim3(REC_BLOCK), (int)n_pairs, M, rec->d_models.p, d_hits, d_off, d_counts);
-  std::vector<unsigned char> back(z_head);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(back.data(), d_zero, z_head, hipMemcpyDeviceToHost, fr.st);
-  if (e == hipSuccess) e = host_stream_sync(fr.st);
-  if (e != hipSuccess) {
-    s = fail(PPF_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    (void)hipDeviceSynchronize(); /* kernels of a failed call may still run: wait before its scratch goes back to the block cache */
-    return s;
-  }
+  auto run = [&]() -> ppf_status {
+    HIPCHK(hipMemsetAsync(d_zero, 0, z_bytes, fr.st));
+    /* dynamic LDS, which FRAME_LAUNCH does not pass: counted by hand */
+    k_rec_score<<<dim3((unsigned)std::max(n_items, 1)), dim3(REC_BLOCK), lds_bytes, fr.st>>>(d_items, n_items, d_clouds, rec->d_models.p, row_cap,
+                                                                                            rec->lds_words, d_hits, d_off, d_counts, d_used);
+    fr.launches++;
+    FRAME_LAUNCH(fr, k_rec_finish, dim3((unsigned)std::max<size_t>(n_pairs, 1)), dim3(REC_BLOCK), (int)n_pairs, M, rec->d_models.p, d_hits, d_off, d_counts);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? PPF_OK : fail(PPF_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+  };
+  const ppf_status ran = run();
+  std::vector<unsigned char> back(z_head); /* filled while the kernels run */
+  if ((s = fr.finish(who, ran, {{"counters", d_zero, z_head, back.data()}})) != PPF_OK) return s;
   const unsigned long long* r_counts = reinterpret_cast<const unsigned long long*>(back.data());
   const int32_t* r_used = reinterpret_cast<const int32_t*>(back.data() + z_counts);
   std::vector<ppf_recognize_score> all((size_t)M);
@@ -238,8 +235,7 @@ ppf_status recognize_frame(const ppf_recognizer* rec, const ppf_cloud* const* cl
   }
   st.n_clouds = n_clouds;
   st.n_models = M;
-  st.n_launches = fr.launches;
-  st.n_host_syncs = 1;
+  fr.report(st);
   return PPF_OK;
 }
 
@@ -323,17 +319,8 @@ ppf_status ppf_recognizer_keys(const ppf_recognizer* rec, int i, int32_t* keys4,
 
 ppf_status ppf_recognize_frame(const ppf_recognizer* rec, const ppf_cloud* const* clouds, int n_clouds, const ppf_recognize_params* p,
                                int32_t* n_used, uint64_t* counts, ppf_recognize_score* ranked, int32_t* n_ranked, ppf_recognize_stats* stats) {
-  const auto t0 = std::chrono::steady_clock::now();
-  ppf_recognize_stats local;
-  ppf_recognize_stats& st = stats ? *stats : local;
-  recognize_clear(rec, n_clouds, p, n_used, counts, ranked, n_ranked, st);
-  const ppf_status s = recognize_frame(rec, clouds, n_clouds, p, n_used, counts, ranked, n_ranked, st);
-  if (s != PPF_OK) {
-    recognize_clear(rec, n_clouds, p, n_used, counts, ranked, n_ranked, st);
-    return s;
-  }
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PPF_OK;
+  return stage_entry(stats, [&](ppf_recognize_stats& st, bool) { recognize_clear(rec, n_clouds, p, n_used, counts, ranked, n_ranked, st); },
+                     [&](ppf_recognize_stats& st) { return recognize_frame(rec, clouds, n_clouds, p, n_used, counts, ranked, n_ranked, st); });
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
 /*
  * ppf_refine_host.h — host side of ppf_refine_frame: projective point-to-plane refinement of every pose of every detection
  * of a frame against the depth image.  Kernel: ppf_refine_kernels.h.  Included by ppf_hip.hip after
- * ppf_icp_host.h (icp_set_pose), ppf_frame_host.h (FrameRun, FRAME_LAUNCH) and ppf_posetable_host.h (the checks of a pose
- * table, the depth upload).
+ * ppf_icp_host.h (icp_set_pose), ppf_stage_host.h (FrameRun, FRAME_LAUNCH, stage_entry) and ppf_posetable_host.h (the checks
+ * of a pose table, the depth upload).
  *
  * Per call with at least one pose and max_iters > 0: two uploads (the job table, the depth image), one launch
  * (k_rfn_refine: a persistent workgroup per pose runs the centre, every iteration and the info row) and one read-back (the
@@ -39,10 +39,12 @@ void refine_clear(int n_dets, int top, const ppf_pose* poses, ppf_pose* out, ppf
   if (info) std::memset(info, 0, n * sizeof(ppf_refine_info));
 }
 
-/* the job table -> k_rfn_refine -> one read-back; dev[j] = the matrix and info row of job j, (i, k) order */
+/* the job table -> k_rfn_refine -> the one wait; dev[j] = the matrix and info row of job j, (i, k) order.  st gets the counts
+ * of a failed run too */
 ppf_status refine_run(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top, const float* depth,
                       int depth_rows, int depth_cols, const double* intr, const ppf_refine_params* p, std::vector<RfnOut>& dev,
-                      FrameRun& fr) {
+                      ppf_refine_stats& st) {
+  FrameRun fr;
   std::vector<RfnJob> hj;
   size_t n_parts = 0;
   for (int i = 0; i < n_dets; i++) {
@@ -62,10 +64,9 @@ ppf_status refine_run(const ppf_frame_detection* dets, int n_dets, const ppf_pos
   RfnArgs a;
   RfnJob* d_jobs;
   float* d_depth;
-  ppf_status s;
-  if ((s = fr.get(hj.size(), &d_jobs)) != PPF_OK || (s = fr.get(n_parts, &a.parts)) != PPF_OK || (s = fr.get(hj.size(), &a.out)) != PPF_OK ||
-      (s = frame_upload_depth(fr, depth, depth_rows, depth_cols, &d_depth)) != PPF_OK)
-    return s;
+  ppf_status s = fr.get(hj.size(), &d_jobs, n_parts, &a.parts, hj.size(), &a.out);
+  if (s == PPF_OK) s = frame_upload_depth(fr, depth, depth_rows, depth_cols, &d_depth);
+  if (s != PPF_OK) return s;
   HIPCHK(hipMemcpy(d_jobs, hj.data(), hj.size() * sizeof(RfnJob), hipMemcpyHostToDevice));
   a.jobs = d_jobs;
   a.depth = d_depth;
@@ -81,10 +82,16 @@ ppf_status refine_run(const ppf_frame_detection* dets, int n_dets, const ppf_pos
   a.min_pairs = p->min_pairs;
   a.max_iters = p->max_iters;
   a.step = p->model_step;
-  FRAME_LAUNCH(fr, k_rfn_refine, dim3((unsigned)hj.size()), dim3(RFN_BLOCK), a);
-  HIPCHK(hipGetLastError());
-  dev.resize(hj.size());
-  return fr.read(dev.data(), a.out, hj.size() * sizeof(RfnOut));
+  auto run = [&]() -> ppf_status {
+    FRAME_LAUNCH(fr, k_rfn_refine, dim3((unsigned)hj.size()), dim3(RFN_BLOCK), a);
+    HIPCHK(hipGetLastError());
+    return PPF_OK;
+  };
+  const ppf_status ran = run();
+  dev.resize(hj.size()); /* while the kernel runs */
+  s = fr.finish("ppf_refine_frame", ran, {{"results", a.out, hj.size() * sizeof(RfnOut), dev.data()}});
+  fr.report(st);
+  return s;
 }
 
 }  // namespace
@@ -110,48 +117,44 @@ ppf_status ppf_refine_frame(const ppf_frame_detection* dets, int n_dets, const p
                             const float* depth, int depth_rows, int depth_cols, const double* intr, const ppf_refine_params* params,
                             ppf_pose* out, ppf_refine_info* info, ppf_refine_stats* stats) {
   static const char* who = "ppf_refine_frame";
-  const auto t0 = std::chrono::steady_clock::now();
-  ppf_refine_stats local;
-  ppf_refine_stats& st = stats ? *stats : local;
-  std::memset(&st, 0, sizeof(st));
-  /* on any error out is a copy of poses and every info row is zero: what the valid part of the arguments lets us reach */
-  refine_clear(n_dets, top, poses, out, info);
-  ppf_status s = refine_check(dets, n_dets, poses, n_poses, top, depth, depth_rows, depth_cols, intr, params, out, who);
-  if (s != PPF_OK) return s;
-  st.n_dets = n_dets;
-  if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
-  int n_jobs;
-  if ((s = table_check_models(dets, n_dets, n_poses, TABLE_N_POSES, who, &n_jobs)) != PPF_OK) return s;
-  if (n_jobs > 0 && params->max_iters == 0) {
-    /* nothing is evaluated: the poses as given */
-    for (int i = 0; i < n_dets; i++)
-      for (int k = 0; k < n_poses[i] && info; k++) {
-        ppf_refine_info& r = info[(size_t)i * top + k];
-        r.status = PPF_REFINE_MAX_ITERS;
-        r.n_rows = (int32_t)(((long long)dets[i].model_cloud->n + params->model_step - 1) / params->model_step);
-      }
-  } else if (n_jobs > 0) {
-    std::vector<RfnOut> dev;
-    {
-      FrameRun fr; /* the scratch goes back to the block cache after the read-back */
-      s = refine_run(dets, n_dets, poses, n_poses, top, depth, depth_rows, depth_cols, intr, params, dev, fr);
-      st.n_launches = fr.launches;
-      st.n_host_syncs = fr.syncs;
-      if (s != PPF_OK) return s;
+  /* on any error out is a copy of poses and every info row is zero: what the valid part of the arguments lets us reach.  The
+   * stats of a failed call keep n_dets and the launch counts of the run */
+  auto clear = [&](ppf_refine_stats& st, bool failed) {
+    if (failed) return;
+    std::memset(&st, 0, sizeof(st));
+    refine_clear(n_dets, top, poses, out, info);
+  };
+  return stage_entry(stats, clear, [&](ppf_refine_stats& st) -> ppf_status {
+    ppf_status s = refine_check(dets, n_dets, poses, n_poses, top, depth, depth_rows, depth_cols, intr, params, out, who);
+    if (s != PPF_OK) return s;
+    st.n_dets = n_dets;
+    if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
+    int n_jobs;
+    if ((s = table_check_models(dets, n_dets, n_poses, TABLE_N_POSES, who, &n_jobs)) != PPF_OK) return s;
+    if (n_jobs > 0 && params->max_iters == 0) {
+      /* nothing is evaluated: the poses as given */
+      for (int i = 0; i < n_dets; i++)
+        for (int k = 0; k < n_poses[i] && info; k++) {
+          ppf_refine_info& r = info[(size_t)i * top + k];
+          r.status = PPF_REFINE_MAX_ITERS;
+          r.n_rows = (int32_t)(((long long)dets[i].model_cloud->n + params->model_step - 1) / params->model_step);
+        }
+    } else if (n_jobs > 0) {
+      std::vector<RfnOut> dev;
+      if ((s = refine_run(dets, n_dets, poses, n_poses, top, depth, depth_rows, depth_cols, intr, params, dev, st)) != PPF_OK) return s;
+      size_t j = 0;
+      for (int i = 0; i < n_dets; i++)
+        for (int k = 0; k < n_poses[i]; k++, j++) {
+          ppf_pose& o = out[(size_t)i * top + k];
+          /* a pose no step was applied to keeps its record (the matrix is the one given); only the residual is new */
+          if (dev[j].info.iterations > 0) icp_set_pose(&o, dev[j].T, (double)dev[j].info.rmse_last);
+          else o.residual = (double)dev[j].info.rmse_last;
+          if (info) info[(size_t)i * top + k] = dev[j].info;
+        }
     }
-    size_t j = 0;
-    for (int i = 0; i < n_dets; i++)
-      for (int k = 0; k < n_poses[i]; k++, j++) {
-        ppf_pose& o = out[(size_t)i * top + k];
-        /* a pose no step was applied to keeps its record (the matrix is the one given); only the residual is new */
-        if (dev[j].info.iterations > 0) icp_set_pose(&o, dev[j].T, (double)dev[j].info.rmse_last);
-        else o.residual = (double)dev[j].info.rmse_last;
-        if (info) info[(size_t)i * top + k] = dev[j].info;
-      }
-  }
-  st.n_jobs = n_jobs;
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PPF_OK;
+    st.n_jobs = n_jobs;
+    return PPF_OK;
+  });
 }
 
 }  // extern "C"

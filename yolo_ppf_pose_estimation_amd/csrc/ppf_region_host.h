@@ -1,10 +1,10 @@
 /*
  * ppf_region_host.h — host side of ppf_prep_regions: the smooth surface regions of up to 256 clouds in one pass (DESIGN.md
  * §22).  Kernels: ppf_region_kernels.h.  Included by ppf_hip.hip after ppf_cluster_host.h, whose clu_begin, clu_cells and
- * clu_finish it runs around its own four kernels, inside that file's entry body (clu_entry).
+ * clu_rank it runs around its own four kernels, inside that file's call (clu_run) and entry body (clu_entry).
  *
  * Per call: clu_begin<true> (k_clu_bounds, k_clu_grid and k_clu_keys over the eligible rows, the sort by (segment, cell)),
- * k_reg_runs, clu_cells, k_reg_link, k_reg_flatten, k_reg_attach, clu_finish: 111 launches whatever the clouds hold -- one more
+ * k_reg_runs, clu_cells, k_reg_link, k_reg_flatten, k_reg_attach, clu_rank: 111 launches whatever the clouds hold -- one more
  * than ppf_prep_clusters, the attach pass -- and none when no cloud has a row.  One upload before any device work, one wait.
  */
 #ifndef PPF_REGION_HOST_H
@@ -25,15 +25,11 @@ ppf_status region_params_check(const char* who, const ppf_region_params* p) {
   return PPF_OK;
 }
 
-/* fr and blk belong to the caller, as in clusters_enqueue */
-ppf_status regions_enqueue(FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, const ppf_cloud* const* in, int K, const ppf_region_params& p,
-                           const double* intr, int image_rows, int image_cols, ppf_cloud** out, ppf_cluster_info* info, int32_t* counts,
-                           int32_t* const* labels, ppf_cluster_stats& st) {
-  CluWork w;
-  ppf_status s = clu_begin<true>(fr, w, blk, "ppf_prep_regions", in, K, p.max_regions, p.tolerance, (size_t)K /* attached border rows */);
-  if (s != PPF_OK || w.N == 0) return s;
+/* between clu_begin<true> and clu_rank, as clusters_link */
+ppf_status regions_link(FrameRun& fr, CluWork& w, const ppf_region_params& p) {
   float4* nrm;
-  if ((s = fr.get(w.N, &nrm)) != PPF_OK) return s;
+  ppf_status s = fr.get(w.N, &nrm);
+  if (s != PPF_OK) return s;
   const dim3 b256(CLU_BLOCK);
   const double tol2 = w.tol * w.tol, cosv = (double)p.normal_cos;
   const int unoriented = (p.flags & PPF_REGION_UNORIENTED) ? 1 : 0;
@@ -44,7 +40,7 @@ ppf_status regions_enqueue(FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, co
   FRAME_LAUNCH(fr, k_reg_flatten, w.rows_grid, b256, (uint32_t)w.N, w.pts, nrm, w.parent, w.root, w.size);
   FRAME_LAUNCH(fr, k_reg_attach, w.rows_grid, b256, (uint32_t)w.N, w.pts, nrm, w.lkey, w.skey, w.ckey, w.cstart, w.runid + w.N, tol2, cosv,
                unoriented, w.root, w.size, w.zero + w.z_extra);
-  return clu_finish(fr, w, blk, p.min_size, p.max_size, intr, image_rows, image_cols, out, info, counts, 4, labels, st);
+  return PPF_OK;
 }
 
 }  // namespace
@@ -69,8 +65,10 @@ ppf_status ppf_prep_regions(const ppf_cloud* const* in, int n_clouds, const ppf_
   return clu_entry(
       who, in, n_clouds, p ? clu_max_shown(p->max_regions) : 1, 4, intr, image_rows, image_cols, out, info, counts, stats,
       [&]() { return region_params_check(who, p); },
-      [&](FrameRun& fr, std::shared_ptr<DevBuf<float>>& blk, ppf_cluster_stats& st) {
-        return regions_enqueue(fr, blk, in, n_clouds, *p, intr, image_rows, image_cols, out, info, counts, labels, st);
+      [&](ppf_cluster_stats& st) {
+        return clu_run<true>(who, in, n_clouds, p->max_regions, p->tolerance, (size_t)n_clouds /* attached border rows */, p->min_size, p->max_size,
+                             intr, image_rows, image_cols, out, info, counts, 4, labels, st,
+                             [&](FrameRun& fr, CluWork& w) { return regions_link(fr, w, *p); });
       });
 }
 

@@ -2,7 +2,7 @@
  * ppf_register_host.h — host side of the camera entries (ppf_camera_project / _unproject / _map_boxes, host only), of
  * ppf_depth_map and of ppf_depth_register / ppf_depth_register_device: a raw sensor depth image aligned to the colour
  * camera.  Kernels: ppf_register_kernels.h; arithmetic: include/ppf_camera_math.h.  Included by
- * ppf_hip.hip after ppf_depthimage_host.h (the image check, the bindings, depth_outputs_check, depth_finish, depth_entry,
+ * ppf_hip.hip after ppf_depthimage_host.h (the image check, the bindings, depth_outputs_check, stage_finish, stage_entry,
  * depth_typed).
  *
  * Per call: k_reg_clear, k_reg_draw, k_reg_resolve -- three launches -- and one blocking wait, whatever the sizes.  The
@@ -123,7 +123,7 @@ ppf_status register_host(const char* who, const ppf_depth_map* map, const void* 
   HIPCHK(buf.reserve(n_out + REG_N_COUNTERS));
   int32_t* counters = reinterpret_cast<int32_t*>(buf.p + n_out);
   int32_t c[REG_N_COUNTERS];
-  s = depth_finish(who, register_enqueue(map, a, dp->format, rp, buf.p, reinterpret_cast<float*>(buf.p), counters, nullptr), nullptr,
+  s = stage_finish(who, register_enqueue(map, a, dp->format, rp, buf.p, reinterpret_cast<float*>(buf.p), counters, nullptr), nullptr,
                    {{"output", buf.p, n_out * sizeof(float), out}, {"counters", counters, sizeof(c), c}});
   if (s == PPF_OK) register_fill_stats(st, c);
   return s;
@@ -133,7 +133,7 @@ ppf_status register_device(const char* who, const ppf_depth_map* map, const void
                            const ppf_depth_params* dp, const ppf_register_params* rp, float* d_out, hipStream_t stream,
                            ppf_register_stats& st) {
   RegArgs a;
-  DepthBuf image;
+  StageBuf image;
   ppf_status s = register_check(who, map, d_depth, row_pitch_bytes, dp, rp, d_out, &a.d);
   if (s != PPF_OK) return s;
   if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
@@ -143,7 +143,7 @@ ppf_status register_device(const char* who, const ppf_depth_map* map, const void
   DevBuf<int32_t> counters;
   HIPCHK(counters.reserve(REG_N_COUNTERS));
   int32_t c[REG_N_COUNTERS];
-  s = depth_finish(who, register_enqueue(map, a, dp->format, rp, reinterpret_cast<uint32_t*>(d_out), d_out, counters.p, stream), stream,
+  s = stage_finish(who, register_enqueue(map, a, dp->format, rp, reinterpret_cast<uint32_t*>(d_out), d_out, counters.p, stream), stream,
                    {{"counters", counters.p, sizeof(c), c}});
   if (s == PPF_OK) register_fill_stats(st, c);
   return s;
@@ -274,14 +274,14 @@ ppf_status ppf_depth_register(const ppf_depth_map* map, const void* depth, size_
     std::memset(&st, 0, sizeof(st));
     if (failed && map && out) std::memset(out, 0, (size_t)map->c_rows * map->c_cols * sizeof(float));
   };
-  return depth_entry(stats, clear, [&](ppf_register_stats& st) {
+  return stage_entry(stats, clear, [&](ppf_register_stats& st) {
     return register_host("ppf_depth_register", map, depth, row_pitch_bytes, dp, rp, out, st);
   });
 }
 
 ppf_status ppf_depth_register_device(const ppf_depth_map* map, const void* d_depth, size_t row_pitch_bytes, const ppf_depth_params* dp,
                                      const ppf_register_params* rp, float* d_out, void* stream, ppf_register_stats* stats) {
-  return depth_entry(stats, depth_clear_stats<ppf_register_stats>, [&](ppf_register_stats& st) {
+  return stage_entry(stats, stage_clear_stats<ppf_register_stats>, [&](ppf_register_stats& st) {
     return register_device("ppf_depth_register_device", map, d_depth, row_pitch_bytes, dp, rp, d_out, static_cast<hipStream_t>(stream), st);
   });
 }

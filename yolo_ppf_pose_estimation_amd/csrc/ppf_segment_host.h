@@ -1,8 +1,7 @@
 /*
  * ppf_segment_host.h — host side of ppf_depth_segments / ppf_depth_segments_device: a depth image's surfaces labelled in image
- * space.  Kernels: ppf_segment_kernels.h.  Included by ppf_hip.hip after ppf_depthimage_host.h (the image
- * check, the bindings, depth_outputs_check, depth_finish, depth_entry, depth_typed) and ppf_prep_host.h (FrameRun, frame_scan,
- * frame_sort).
+ * space.  Kernels: ppf_segment_kernels.h.  Included by ppf_hip.hip after ppf_stage_host.h (FrameRun, frame_scan,
+ * frame_sort, stage_entry) and ppf_depthimage_host.h (the image check, the bindings, depth_outputs_check, depth_typed).
  *
  * Per call, all on the caller's stream (FrameRun::st): with a normals cloud k_depth_count and a five-launch scan; then k_seg_classify,
  * k_seg_tile, k_seg_merge, k_seg_flatten, k_seg_valid, the ranking's sort (four digit passes of seven launches), k_seg_rank
@@ -70,14 +69,10 @@ ppf_status segment_enqueue(FrameRun& fr, SegWork& w, const DepthArgs& a, const S
   w.z_head = SEG_N_COUNTERS;
   w.z_acc = w.z_head + (size_t)MC * SEG_HEAD;
   w.z_words = w.z_acc + (size_t)MC * SEG_ACC;
-  ppf_status s;
-  if ((s = fr.get(w.z_words, &w.zero)) != PPF_OK || (s = fr.get(N, &rec)) != PPF_OK || (s = fr.get(N, &cls)) != PPF_OK ||
-      (s = fr.get(N, &parent)) != PPF_OK || (s = fr.get(N, &size)) != PPF_OK || (s = fr.get(N, &nbord)) != PPF_OK ||
-      (s = fr.get(N, &root)) != PPF_OK || (s = fr.get(N, &rank)) != PPF_OK || (s = fr.get(N, &ka)) != PPF_OK ||
-      (s = fr.get(N, &va)) != PPF_OK || (s = fr.get(N, &kb)) != PPF_OK || (s = fr.get(N, &vb)) != PPF_OK ||
-      (s = fr.get((size_t)256 * nblk, &hist)) != PPF_OK || (s = fr.get((size_t)256 * nblk, &offs)) != PPF_OK)
-    return s;
-  if (sa.nrm_rows && ((s = fr.get((size_t)n_dt + 1, &tcnt)) != PPF_OK || (s = fr.get((size_t)n_dt + 1, &toff)) != PPF_OK)) return s;
+  ppf_status s = fr.get(w.z_words, &w.zero, N, &rec, N, &cls, N, &parent, N, &size, N, &nbord, N, &root, N, &rank, N, &ka, N, &va, N, &kb, N, &vb,
+                        (size_t)256 * nblk, &hist, (size_t)256 * nblk, &offs);
+  if (s == PPF_OK && sa.nrm_rows) s = fr.get((size_t)n_dt + 1, &tcnt, (size_t)n_dt + 1, &toff);
+  if (s != PPF_OK) return s;
   HIPCHK(hipMemsetAsync(w.zero, 0, w.z_words * sizeof(uint32_t), fr.st));
   const dim3 bd(DEPTH_BLOCK), bs(SEG_BLOCK), g_dt((unsigned)n_dt), g_tiles((unsigned)n_tiles), g_px = grid_for(N, SEG_BLOCK);
   if (sa.nrm_rows) {
@@ -126,8 +121,7 @@ ppf_status segment_results(const char* who, const std::vector<uint32_t>& z, cons
   st.n_eligible = (int32_t)z[SEG_C_ELIGIBLE];
   st.n_smooth = (int32_t)z[SEG_C_SMOOTH];
   st.n_attached = (int32_t)z[SEG_C_ATTACHED];
-  st.n_launches = fr.launches;
-  st.n_host_syncs = 1;
+  fr.report(st);
   return PPF_OK;
 }
 
@@ -145,12 +139,12 @@ ppf_status segment_host(const char* who, const void* depth, int rows, int cols, 
   DevBuf<unsigned char> img;
   int32_t* d_labels;
   if ((s = depth_bind_host(depth, dp->format, img, &a)) != PPF_OK) return s;
-  if ((s = fr.get(n, &d_labels)) != PPF_OK) return s;
+  s = fr.get(n, &d_labels);
+  if (s != PPF_OK) return s;
   std::vector<int32_t> lab(n); /* labels stay untouched when the wait brings an error */
   std::vector<uint32_t> z;
   if ((s = segment_enqueue(fr, w, a, sa, dp->format, *sp, d_labels)) == PPF_OK) z.resize(w.z_words);
-  s = depth_finish(who, s, fr.st, {{"label buffer", d_labels, n * sizeof(int32_t), lab.data()},
-                                   {"counters", w.zero, w.z_words * sizeof(uint32_t), z.data()}});
+  s = fr.finish(who, s, {{"label buffer", d_labels, n * sizeof(int32_t), lab.data()}, {"counters", w.zero, w.z_words * sizeof(uint32_t), z.data()}});
   if (s != PPF_OK || (s = segment_results(who, z, w, fr, normals, *sp, info, counts, st)) != PPF_OK) return s;
   std::memcpy(labels, lab.data(), n * sizeof(int32_t));
   return PPF_OK;
@@ -161,7 +155,7 @@ ppf_status segment_device(const char* who, const void* d_depth, int rows, int co
                           int32_t* counts, ppf_segment_stats& st) {
   DepthArgs a;
   SegArgs sa;
-  DepthBuf image;
+  StageBuf image;
   ppf_status s = segment_check(who, d_depth, rows, cols, row_pitch_bytes, dp, normals, sp, d_labels, info, counts, &a, &sa);
   if (s != PPF_OK) return s;
   if ((uintptr_t)d_labels % sizeof(int32_t) != 0) return fail(PPF_ERR_INVALID, "%s: the label buffer is not aligned to 4 bytes", who);
@@ -174,7 +168,7 @@ ppf_status segment_device(const char* who, const void* d_depth, int rows, int co
   fr.st = stream;
   std::vector<uint32_t> z;
   if ((s = segment_enqueue(fr, w, a, sa, dp->format, *sp, d_labels)) == PPF_OK) z.resize(w.z_words);
-  s = depth_finish(who, s, fr.st, {{"counters", w.zero, w.z_words * sizeof(uint32_t), z.data()}});
+  s = fr.finish(who, s, {{"counters", w.zero, w.z_words * sizeof(uint32_t), z.data()}});
   return s != PPF_OK ? s : segment_results(who, z, w, fr, normals, *sp, info, counts, st);
 }
 
@@ -206,7 +200,7 @@ void ppf_default_segment_params(ppf_segment_params* p) {
 ppf_status ppf_depth_segments(const void* depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
                               const ppf_cloud* normals, const ppf_segment_params* sp, int32_t* labels, ppf_segment_info* info,
                               int32_t* counts, ppf_segment_stats* stats) {
-  return depth_entry(stats, [&](ppf_segment_stats& st, bool) { segment_clear(sp, info, counts, st); }, [&](ppf_segment_stats& st) {
+  return stage_entry(stats, [&](ppf_segment_stats& st, bool) { segment_clear(sp, info, counts, st); }, [&](ppf_segment_stats& st) {
     return segment_host("ppf_depth_segments", depth, rows, cols, row_pitch_bytes, dp, normals, sp, labels, info, counts, st);
   });
 }
@@ -214,7 +208,7 @@ ppf_status ppf_depth_segments(const void* depth, int rows, int cols, size_t row_
 ppf_status ppf_depth_segments_device(const void* d_depth, int rows, int cols, size_t row_pitch_bytes, const ppf_depth_params* dp,
                                      const ppf_cloud* normals, const ppf_segment_params* sp, int32_t* d_labels, void* stream,
                                      ppf_segment_info* info, int32_t* counts, ppf_segment_stats* stats) {
-  return depth_entry(stats, [&](ppf_segment_stats& st, bool) { segment_clear(sp, info, counts, st); }, [&](ppf_segment_stats& st) {
+  return stage_entry(stats, [&](ppf_segment_stats& st, bool) { segment_clear(sp, info, counts, st); }, [&](ppf_segment_stats& st) {
     return segment_device("ppf_depth_segments_device", d_depth, rows, cols, row_pitch_bytes, dp, normals, sp, d_labels,
                           static_cast<hipStream_t>(stream), info, counts, st);
   });

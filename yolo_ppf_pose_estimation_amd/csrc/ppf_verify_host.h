@@ -1,8 +1,8 @@
 /*
  * ppf_verify_host.h — host side of ppf_verify_frame: score every refined pose of every detection of a frame against its
  * object cloud and, optionally, the depth image (what the reference leaves as `// TODO: Pose Validation`,
- * CloudProcessing.h:477-479, :530-532).  Kernels: ppf_verify_kernels.h.  Included by ppf_hip.hip after ppf_frame_host.h
- * (FrameRun, FRAME_LAUNCH, frame_scan) and ppf_posetable_host.h (the checks, clears and score scatter of a pose table).
+ * CloudProcessing.h:477-479, :530-532).  Kernels: ppf_verify_kernels.h.  Included by ppf_hip.hip after ppf_stage_host.h
+ * (FrameRun, FRAME_LAUNCH, frame_scan, stage_entry) and ppf_posetable_host.h (the checks, clears and score scatter of a pose table).
  *
  * Per call with at least one pose: three uploads (the detection and job tables, the depth image when given), then
  * k_vfy_grid_count, a five-launch scan, k_vfy_grid_scatter, k_vfy_score, k_vfy_finish -- nine launches whatever the number
@@ -81,10 +81,8 @@ ppf_status verify_tables(const ppf_frame_detection* dets, int n_dets, const ppf_
   t.nj = (int)hj.size();
   t.max_nb = max_nb;
   uint32_t *counts, *rank;
-  ppf_status s;
-  if ((s = fr.get(t.nd, &t.d_dets)) != PPF_OK || (s = fr.get(t.nj, &t.d_jobs)) != PPF_OK || (s = fr.get(slots + 1, &counts)) != PPF_OK ||
-      (s = fr.get(slots + 1, &t.start)) != PPF_OK || (s = fr.get(rows, &rank)) != PPF_OK || (s = fr.get(rows, &t.pts)) != PPF_OK)
-    return s;
+  ppf_status s = fr.get(t.nd, &t.d_dets, t.nj, &t.d_jobs, slots + 1, &counts, slots + 1, &t.start, rows, &rank, rows, &t.pts);
+  if (s != PPF_OK) return s;
   HIPCHK(hipMemcpy(t.d_dets, hd.data(), hd.size() * sizeof(VfyDet), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(t.d_jobs, hj.data(), hj.size() * sizeof(VfyJob), hipMemcpyHostToDevice));
   HIPCHK(hipMemsetAsync(counts, 0, (slots + 1) * sizeof(uint32_t), nullptr));
@@ -121,24 +119,40 @@ VfyArgs verify_args(const VfyTables& t, const float* d_depth, int depth_rows, in
   return a;
 }
 
-/* grids -> scores -> one read-back; dev[j] = the score row of job j on the host */
+/* the scratch of the scoring that follows the tables: the partial sums, the score rows, the depth image when given */
+ppf_status verify_scratch(FrameRun& fr, const VfyTables& t, const float* depth, int depth_rows, int depth_cols, VfyPartial** part,
+                          ppf_pose_score** d_out, float** d_depth) {
+  const ppf_status s = fr.get((size_t)t.nj * t.max_nb, part, t.nj, d_out);
+  if (s != PPF_OK || !depth) return s;
+  return frame_upload_depth(fr, depth, depth_rows, depth_cols, d_depth);
+}
+
+/* grids -> scores -> the one wait; dev[j] = the score row of job j on the host.  st gets the counts of a failed run too */
 ppf_status verify_run(const ppf_frame_detection* dets, int n_dets, const ppf_pose* poses, const int* n_poses, int top, const float* depth,
                       int depth_rows, int depth_cols, const double* intr, const ppf_verify_params* p, std::vector<ppf_pose_score>& dev,
-                      FrameRun& fr) {
-  VfyTables t;
-  ppf_status s = verify_tables(dets, n_dets, poses, n_poses, top, p, "ppf_verify_frame", t, fr);
-  if (s != PPF_OK) return s;
-  VfyPartial* part;
-  ppf_pose_score* d_out;
-  float* d_depth = nullptr;
-  if ((s = fr.get((size_t)t.nj * t.max_nb, &part)) != PPF_OK || (s = fr.get(t.nj, &d_out)) != PPF_OK) return s;
-  if (depth && (s = frame_upload_depth(fr, depth, depth_rows, depth_cols, &d_depth)) != PPF_OK) return s;
-  const VfyArgs a = verify_args(t, d_depth, depth_rows, depth_cols, intr, p);
-  FRAME_LAUNCH(fr, k_vfy_score, dim3((unsigned)t.max_nb, (unsigned)t.nj), dim3(VFY_BLOCK), a, part);
-  FRAME_LAUNCH(fr, k_vfy_finish, dim3((unsigned)t.nj), dim3(64), t.d_jobs, part, t.max_nb, depth ? 1 : 0, d_out);
-  HIPCHK(hipGetLastError());
-  dev.resize((size_t)t.nj);
-  return fr.read(dev.data(), d_out, (size_t)t.nj * sizeof(ppf_pose_score));
+                      ppf_verify_stats& st) {
+  static const char* who = "ppf_verify_frame";
+  FrameRun fr;
+  ppf_pose_score* d_out = nullptr;
+  auto run = [&]() -> ppf_status {
+    VfyTables t;
+    VfyPartial* part;
+    float* d_depth = nullptr;
+    ppf_status s;
+    if ((s = verify_tables(dets, n_dets, poses, n_poses, top, p, who, t, fr)) != PPF_OK ||
+        (s = verify_scratch(fr, t, depth, depth_rows, depth_cols, &part, &d_out, &d_depth)) != PPF_OK)
+      return s;
+    const VfyArgs a = verify_args(t, d_depth, depth_rows, depth_cols, intr, p);
+    FRAME_LAUNCH(fr, k_vfy_score, dim3((unsigned)t.max_nb, (unsigned)t.nj), dim3(VFY_BLOCK), a, part);
+    FRAME_LAUNCH(fr, k_vfy_finish, dim3((unsigned)t.nj), dim3(64), t.d_jobs, part, t.max_nb, depth ? 1 : 0, d_out);
+    HIPCHK(hipGetLastError());
+    dev.resize((size_t)t.nj);
+    return PPF_OK;
+  };
+  const ppf_status ran = run(); /* before d_out and dev are read */
+  const ppf_status s = fr.finish(who, ran, {{"scores", d_out, dev.size() * sizeof(ppf_pose_score), dev.data()}});
+  fr.report(st);
+  return s;
 }
 
 }  // namespace
@@ -159,32 +173,26 @@ ppf_status ppf_verify_frame(const ppf_frame_detection* dets, int n_dets, const p
                             const float* depth, int depth_rows, int depth_cols, const double* intr, const ppf_verify_params* params,
                             ppf_pose_score* scores, int* best, ppf_verify_stats* stats) {
   static const char* who = "ppf_verify_frame";
-  const auto t0 = std::chrono::steady_clock::now();
-  ppf_verify_stats local;
-  ppf_verify_stats& st = stats ? *stats : local;
-  std::memset(&st, 0, sizeof(st));
-  /* on any error every score row is zero and every best[i] is -1: clear what the valid part of the arguments lets us reach */
-  table_clear_scores(n_dets, top, scores, best);
-  ppf_status s = verify_check(dets, n_dets, poses, n_poses, top, depth, depth_rows, depth_cols, intr, params, scores, best, who);
-  if (s != PPF_OK) return s;
-  st.n_dets = n_dets;
-  if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
-  int n_jobs;
-  if ((s = table_check_models(dets, n_dets, n_poses, TABLE_N_POSES, who, &n_jobs)) != PPF_OK) return s;
-  if (n_jobs > 0) {
+  /* on any error every score row is zero and every best[i] is -1: clear what the valid part of the arguments lets us reach.
+   * The stats of a failed call keep n_dets and the launch counts of the run */
+  auto clear = [&](ppf_verify_stats& st, bool failed) {
+    if (failed) return;
+    std::memset(&st, 0, sizeof(st));
+    table_clear_scores(n_dets, top, scores, best);
+  };
+  return stage_entry(stats, clear, [&](ppf_verify_stats& st) -> ppf_status {
+    ppf_status s = verify_check(dets, n_dets, poses, n_poses, top, depth, depth_rows, depth_cols, intr, params, scores, best, who);
+    if (s != PPF_OK) return s;
+    st.n_dets = n_dets;
+    if (!have_device()) return fail(PPF_ERR_HIP, "%s: no HIP device (this engine has no CPU fallback)", who);
+    int n_jobs;
+    if ((s = table_check_models(dets, n_dets, n_poses, TABLE_N_POSES, who, &n_jobs)) != PPF_OK || n_jobs == 0) return s;
     std::vector<ppf_pose_score> dev;
-    {
-      FrameRun fr; /* the scratch goes back to the block cache after the read-back */
-      s = verify_run(dets, n_dets, poses, n_poses, top, depth, depth_rows, depth_cols, intr, params, dev, fr);
-      st.n_launches = fr.launches;
-      st.n_host_syncs = fr.syncs;
-      if (s != PPF_OK) return s;
-    }
+    if ((s = verify_run(dets, n_dets, poses, n_poses, top, depth, depth_rows, depth_cols, intr, params, dev, st)) != PPF_OK) return s;
     table_scatter_scores(dev, n_dets, n_poses, top, scores, best);
     st.n_jobs = n_jobs;
-  }
-  st.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PPF_OK;
+    return PPF_OK;
+  });
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
 /*
  * ppf_volume_host.h — host side of ppf_depth_volume: posed depth images fused into a truncated signed distance volume that
  * stays on the device, the model depth image it gives from any pose, and its zero surface as a ppf_cloud.
- * Kernels: ppf_volume_kernels.h.  Included by ppf_hip.hip after ppf_depthimage_host.h (the image check, the bindings,
- * depth_outputs_check, depth_finish, depth_entry, depth_typed) and ppf_prep_host.h (ppf_cloud, FrameRun, frame_scan).
+ * Kernels: ppf_volume_kernels.h.  Included by ppf_hip.hip after ppf_stage_host.h (FrameRun, frame_scan, stage_finish, stage_entry),
+ * ppf_prep_host.h (ppf_cloud) and ppf_depthimage_host.h (the image check, the bindings, depth_outputs_check, depth_typed).
  *
  *   integrate  an 8-byte clear of the counter, k_volume_integrate -- one launch -- and one blocking wait.
  *   raycast    an 8-byte clear of the counters, k_volume_raycast -- one launch -- and one blocking wait.
@@ -47,7 +47,7 @@ VolArgs volume_args(const ppf_depth_volume* v) {
   return V;
 }
 
-DepthBuf volume_range(const ppf_depth_volume* v) { return {"volume", v->vox.p, v->n * sizeof(VolVoxel), nullptr}; }
+StageBuf volume_range(const ppf_depth_volume* v) { return {"volume", v->vox.p, v->n * sizeof(VolVoxel), nullptr}; }
 
 ppf_status volume_pose_check(const char* who, const double* pose16) {
   for (int i = 0; i < 16; i++)
@@ -120,7 +120,7 @@ ppf_status volume_integrate_host(const char* who, ppf_depth_volume* v, const voi
   DevBuf<unsigned char> img;
   if ((s = depth_bind_host(depth, dp->format, img, &a)) != PPF_OK) return s;
   unsigned long long n = 0;
-  s = depth_finish(who, volume_integrate_enqueue(v, a, dp->format, rows, pose16, nullptr), nullptr,
+  s = stage_finish(who, volume_integrate_enqueue(v, a, dp->format, rows, pose16, nullptr), nullptr,
                    {{"counter", v->counters.p, sizeof(n), &n}});
   return s != PPF_OK ? s : volume_integrate_done(v, n, st);
 }
@@ -129,7 +129,7 @@ ppf_status volume_integrate_device(const char* who, ppf_depth_volume* v, const v
                                    const double* intr, const ppf_depth_params* dp, const double* pose16, hipStream_t stream,
                                    ppf_depth_volume_integrate_stats& st) {
   DepthArgs a;
-  DepthBuf image;
+  StageBuf image;
   ppf_status s = volume_integrate_check(who, v, d_depth, rows, cols, pitch, intr, dp, pose16, &a);
   if (s != PPF_OK) return s;
   if ((s = volume_device(who, v)) != PPF_OK) return s;
@@ -137,7 +137,7 @@ ppf_status volume_integrate_device(const char* who, ppf_depth_volume* v, const v
   if (ranges_overlap(image, volume_range(v))) return fail(PPF_ERR_INVALID, "%s: the image overlaps the volume", who);
   std::lock_guard<std::mutex> lock(v->mu);
   unsigned long long n = 0;
-  s = depth_finish(who, volume_integrate_enqueue(v, a, dp->format, rows, pose16, stream), stream,
+  s = stage_finish(who, volume_integrate_enqueue(v, a, dp->format, rows, pose16, stream), stream,
                    {{"counter", v->counters.p, sizeof(n), &n}});
   return s != PPF_OK ? s : volume_integrate_done(v, n, st);
 }
@@ -222,7 +222,7 @@ ppf_status volume_raycast_host(const char* who, ppf_depth_volume* v, int rows, i
   /* into staging first: the outputs are only written once everything has succeeded */
   std::vector<float> d(n), nr(normals_out ? n * 3 : 0);
   int32_t c[2];
-  s = depth_finish(who, volume_raycast_enqueue(v, Q, dbuf.p, normals_out ? nbuf.p : nullptr, nullptr), nullptr,
+  s = stage_finish(who, volume_raycast_enqueue(v, Q, dbuf.p, normals_out ? nbuf.p : nullptr, nullptr), nullptr,
                    {{"depth output", dbuf.p, n * sizeof(float), d.data()},
                     {"normals output", nbuf.p, n * 3 * sizeof(float), normals_out ? nr.data() : nullptr},
                     {"counters", v->counters.p, sizeof(c), c}});
@@ -247,7 +247,7 @@ ppf_status volume_raycast_device(const char* who, ppf_depth_volume* v, int rows,
     return s;
   std::lock_guard<std::mutex> lock(v->mu);
   int32_t c[2];
-  s = depth_finish(who, volume_raycast_enqueue(v, Q, d_depth, d_normals, stream), stream, {{"counters", v->counters.p, sizeof(c), c}});
+  s = stage_finish(who, volume_raycast_enqueue(v, Q, d_depth, d_normals, stream), stream, {{"counters", v->counters.p, sizeof(c), c}});
   if (s != PPF_OK) return s;
   volume_raycast_done(c, st);
   return PPF_OK;
@@ -269,7 +269,8 @@ ppf_status volume_extract(const char* who, ppf_depth_volume* v, const ppf_depth_
   const uint32_t n_tiles = (uint32_t)((v->n + DV_X_BLOCK - 1) / DV_X_BLOCK); /* at most 2^22 */
   FrameRun fr;
   uint32_t *counts, *offs;
-  if ((s = fr.get((size_t)n_tiles + 1, &counts)) != PPF_OK || (s = fr.get((size_t)n_tiles + 1, &offs)) != PPF_OK) return s;
+  s = fr.get((size_t)n_tiles + 1, &counts, (size_t)n_tiles + 1, &offs);
+  if (s != PPF_OK) return s;
   std::unique_ptr<ppf_cloud> c;
   uint32_t total = 0;
   unsigned long long n_cross = 0;
@@ -280,10 +281,7 @@ ppf_status volume_extract(const char* who, ppf_depth_volume* v, const ppf_depth_
     HIPCHK(hipGetLastError());
     ppf_status r = frame_scan(fr, counts, offs, (size_t)n_tiles + 1);
     if (r != PPF_OK) return r;
-    HIPCHK(hipMemcpyAsync(&total, offs + n_tiles, sizeof(total), hipMemcpyDeviceToHost, fr.st));
-    HIPCHK(hipMemcpyAsync(&n_cross, v->counters.p, sizeof(n_cross), hipMemcpyDeviceToHost, fr.st));
-    HIPCHK(host_stream_sync(fr.st)); /* the sizing read-back */
-    fr.syncs++;
+    if ((r = fr.sizing({{"rows", offs + n_tiles, sizeof(total), &total}, {"crossings", v->counters.p, sizeof(n_cross), &n_cross}})) != PPF_OK) return r;
     if (total > 0x7fffffffu) return fail(PPF_ERR_NOMEM, "%s: %u rows exceed INT32_MAX, the most a cloud holds", who, total);
     if ((r = cloud_alloc(c, (int)total)) != PPF_OK) return r;
     FRAME_LAUNCH(fr, k_volume_cross<1>, dim3(n_tiles), dim3(DV_X_BLOCK), V, ep->min_weight, v->n, n_tiles, nullptr, nullptr, offs, c->rows.p,
@@ -291,18 +289,28 @@ ppf_status volume_extract(const char* who, ppf_depth_volume* v, const ppf_depth_
     HIPCHK(hipGetLastError());
     return PPF_OK;
   };
-  s = depth_finish(who, run(), fr.st, {}); /* the end: the scratch goes back to the block cache at scope exit */
+  s = fr.finish(who, run(), {}); /* the end: the scratch goes back to the block cache at scope exit */
   if (s != PPF_OK) return s;
-  fr.syncs++;
   st.n_crossings = (int64_t)n_cross;
   st.n_rows = (int64_t)total;
-  st.n_launches = fr.launches;
-  st.n_host_syncs = fr.syncs;
+  fr.report(st);
   *out = c.release();
   return PPF_OK;
 }
 
 /* ---- mesh ---------------------------------------------------------------------------------------------------------- */
+ppf_status mesh_alloc(const char* who, std::unique_ptr<ppf_volume_mesh>& m, int64_t nv, int64_t nt) {
+  m.reset(new (std::nothrow) ppf_volume_mesh());
+  if (!m) return fail(PPF_ERR_NOMEM, "%s: out of host memory", who);
+  m->nv = nv;
+  m->nt = nt;
+  if (m->verts.reserve((size_t)std::max<int64_t>(nv, 1) * 6) != hipSuccess || m->tris.reserve((size_t)std::max<int64_t>(nt, 1) * 3) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(PPF_ERR_NOMEM, "%s: a mesh of %lld vertices and %lld triangles cannot be allocated", who, (long long)nv, (long long)nt);
+  }
+  return PPF_OK;
+}
+
 ppf_status volume_mesh(const char* who, ppf_depth_volume* v, const ppf_depth_volume_mesh_params* mp, ppf_volume_mesh** out,
                        ppf_depth_volume_mesh_stats& st) {
   if (!out) return fail(PPF_ERR_INVALID, "%s: out is NULL", who);
@@ -321,13 +329,10 @@ ppf_status volume_mesh(const char* who, ppf_depth_volume* v, const ppf_depth_vol
   uint8_t *cell, *mask; /* 1 + 1 + 2 = 4 bytes of scratch per voxel */
   uint16_t* rank;
   unsigned long long* ctr;
-  if ((s = fr.get((size_t)n_tiles + 1, &tcnt)) != PPF_OK || (s = fr.get((size_t)n_tiles + 1, &toff)) != PPF_OK ||
-      (s = fr.get((size_t)n_tiles + 1, &vcnt)) != PPF_OK || (s = fr.get((size_t)n_tiles + 1, &voff)) != PPF_OK ||
-      (s = fr.get(v->n, &cell)) != PPF_OK || (s = fr.get(v->n, &mask)) != PPF_OK || (s = fr.get(v->n, &rank)) != PPF_OK ||
-      (s = fr.get((size_t)VM_COUNTERS, &ctr)) != PPF_OK)
-    return s;
-  std::unique_ptr<ppf_volume_mesh> m(new (std::nothrow) ppf_volume_mesh());
-  if (!m) return fail(PPF_ERR_NOMEM, "%s: out of host memory", who);
+  s = fr.get((size_t)n_tiles + 1, &tcnt, (size_t)n_tiles + 1, &toff, (size_t)n_tiles + 1, &vcnt, (size_t)n_tiles + 1, &voff, v->n, &cell, v->n, &mask,
+             v->n, &rank, (size_t)VM_COUNTERS, &ctr);
+  if (s != PPF_OK) return s;
+  std::unique_ptr<ppf_volume_mesh> m;
   unsigned long long c[VM_COUNTERS] = {0, 0, 0, 0};
   auto run = [&]() -> ppf_status {
     const dim3 grid(n_tiles), block(VM_BLOCK);
@@ -337,33 +342,24 @@ ppf_status volume_mesh(const char* who, ppf_depth_volume* v, const ppf_depth_vol
     HIPCHK(hipGetLastError());
     ppf_status r;
     if ((r = frame_scan(fr, tcnt, toff, (size_t)n_tiles + 1)) != PPF_OK || (r = frame_scan(fr, vcnt, voff, (size_t)n_tiles + 1)) != PPF_OK) return r;
-    HIPCHK(hipMemcpyAsync(c, ctr, sizeof(c), hipMemcpyDeviceToHost, fr.st));
-    HIPCHK(host_stream_sync(fr.st)); /* the sizing read-back */
-    fr.syncs++;
+    if ((r = fr.sizing({{"counters", ctr, sizeof(c), c}})) != PPF_OK) return r;
     /* the 64-bit counts decide: a scan total that wrapped is never looked at */
     if (c[VM_N_VERTICES] > 0x7fffffffull || c[VM_N_TRIANGLES] > 0x7fffffffull)
       return fail(PPF_ERR_NOMEM, "%s: %llu vertices and %llu triangles exceed INT32_MAX, the most a mesh holds", who, c[VM_N_VERTICES],
                   c[VM_N_TRIANGLES]);
-    m->nv = (int64_t)c[VM_N_VERTICES];
-    m->nt = (int64_t)c[VM_N_TRIANGLES];
-    if (m->verts.reserve((size_t)std::max<int64_t>(m->nv, 1) * 6) != hipSuccess || m->tris.reserve((size_t)std::max<int64_t>(m->nt, 1) * 3) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(PPF_ERR_NOMEM, "%s: a mesh of %lld vertices and %lld triangles cannot be allocated", who, (long long)m->nv, (long long)m->nt);
-    }
+    if ((r = mesh_alloc(who, m, (int64_t)c[VM_N_VERTICES], (int64_t)c[VM_N_TRIANGLES])) != PPF_OK) return r;
     FRAME_LAUNCH(fr, k_vmesh_vertices, grid, block, V, mp->min_weight, v->n, mask, rank, voff, (uint32_t)m->nv, m->verts.p, ctr);
     FRAME_LAUNCH(fr, k_vmesh_triangles, grid, block, V, v->n, cell, mask, rank, voff, toff, (uint32_t)m->nt, m->tris.p);
     HIPCHK(hipGetLastError());
     return PPF_OK;
   };
-  s = depth_finish(who, run(), fr.st, {{"counters", ctr, sizeof(c), c}}); /* the end: the scratch goes back to the block cache at scope exit */
+  s = fr.finish(who, run(), {{"counters", ctr, sizeof(c), c}}); /* the end: the scratch goes back to the block cache at scope exit */
   if (s != PPF_OK) return s;
-  fr.syncs++;
   st.n_cells = (int64_t)c[VM_N_CELLS];
   st.n_vertices = m->nv;
   st.n_triangles = m->nt;
   st.n_no_normal = (int64_t)c[VM_N_NO_NORMAL];
-  st.n_launches = fr.launches;
-  st.n_host_syncs = fr.syncs;
+  fr.report(st);
   *out = m.release();
   return PPF_OK;
 }
@@ -525,7 +521,7 @@ ppf_status ppf_depth_volume_write(ppf_depth_volume* v, const ppf_depth_volume_vo
 
 ppf_status ppf_depth_volume_integrate(ppf_depth_volume* v, const void* depth, int rows, int cols, size_t row_pitch_bytes, const double* intr,
                                       const ppf_depth_params* dp, const double* pose16, ppf_depth_volume_integrate_stats* stats) {
-  return depth_entry(stats, depth_clear_stats<ppf_depth_volume_integrate_stats>, [&](ppf_depth_volume_integrate_stats& st) {
+  return stage_entry(stats, stage_clear_stats<ppf_depth_volume_integrate_stats>, [&](ppf_depth_volume_integrate_stats& st) {
     return volume_integrate_host("ppf_depth_volume_integrate", v, depth, rows, cols, row_pitch_bytes, intr, dp, pose16, st);
   });
 }
@@ -533,7 +529,7 @@ ppf_status ppf_depth_volume_integrate(ppf_depth_volume* v, const void* depth, in
 ppf_status ppf_depth_volume_integrate_device(ppf_depth_volume* v, const void* d_depth, int rows, int cols, size_t row_pitch_bytes,
                                              const double* intr, const ppf_depth_params* dp, const double* pose16, void* stream,
                                              ppf_depth_volume_integrate_stats* stats) {
-  return depth_entry(stats, depth_clear_stats<ppf_depth_volume_integrate_stats>, [&](ppf_depth_volume_integrate_stats& st) {
+  return stage_entry(stats, stage_clear_stats<ppf_depth_volume_integrate_stats>, [&](ppf_depth_volume_integrate_stats& st) {
     return volume_integrate_device("ppf_depth_volume_integrate_device", v, d_depth, rows, cols, row_pitch_bytes, intr, dp, pose16,
                                    static_cast<hipStream_t>(stream), st);
   });
@@ -542,7 +538,7 @@ ppf_status ppf_depth_volume_integrate_device(ppf_depth_volume* v, const void* d_
 ppf_status ppf_depth_volume_raycast(ppf_depth_volume* v, int rows, int cols, const double* intr, const double* pose16,
                                     const ppf_depth_volume_raycast_params* rp, float* depth_out, float* normals_out,
                                     ppf_depth_volume_raycast_stats* stats) {
-  return depth_entry(stats, depth_clear_stats<ppf_depth_volume_raycast_stats>, [&](ppf_depth_volume_raycast_stats& st) {
+  return stage_entry(stats, stage_clear_stats<ppf_depth_volume_raycast_stats>, [&](ppf_depth_volume_raycast_stats& st) {
     return volume_raycast_host("ppf_depth_volume_raycast", v, rows, cols, intr, pose16, rp, depth_out, normals_out, st);
   });
 }
@@ -550,7 +546,7 @@ ppf_status ppf_depth_volume_raycast(ppf_depth_volume* v, int rows, int cols, con
 ppf_status ppf_depth_volume_raycast_device(ppf_depth_volume* v, int rows, int cols, const double* intr, const double* pose16,
                                            const ppf_depth_volume_raycast_params* rp, float* d_depth, float* d_normals, void* stream,
                                            ppf_depth_volume_raycast_stats* stats) {
-  return depth_entry(stats, depth_clear_stats<ppf_depth_volume_raycast_stats>, [&](ppf_depth_volume_raycast_stats& st) {
+  return stage_entry(stats, stage_clear_stats<ppf_depth_volume_raycast_stats>, [&](ppf_depth_volume_raycast_stats& st) {
     return volume_raycast_device("ppf_depth_volume_raycast_device", v, rows, cols, intr, pose16, rp, d_depth, d_normals,
                                  static_cast<hipStream_t>(stream), st);
   });
@@ -558,7 +554,7 @@ ppf_status ppf_depth_volume_raycast_device(ppf_depth_volume* v, int rows, int co
 
 ppf_status ppf_depth_volume_extract(ppf_depth_volume* v, const ppf_depth_volume_extract_params* ep, ppf_cloud** out,
                                     ppf_depth_volume_extract_stats* stats) {
-  return depth_entry(
+  return stage_entry(
       stats,
       [&](ppf_depth_volume_extract_stats& st, bool failed) {
         std::memset(&st, 0, sizeof(st));
@@ -569,7 +565,7 @@ ppf_status ppf_depth_volume_extract(ppf_depth_volume* v, const ppf_depth_volume_
 
 ppf_status ppf_depth_volume_mesh(ppf_depth_volume* v, const ppf_depth_volume_mesh_params* mp, ppf_volume_mesh** out,
                                  ppf_depth_volume_mesh_stats* stats) {
-  return depth_entry(
+  return stage_entry(
       stats,
       [&](ppf_depth_volume_mesh_stats& st, bool failed) {
         std::memset(&st, 0, sizeof(st));
