@@ -26,6 +26,7 @@
  *   (nothing: the frames of a fixed camera fused)     ->  DepthHistory::push / pushU16
  *   (nothing: the camera stands still there)          ->  depthMotion / depthMotionU16 / DepthOdometry::push  (the camera's motion between two depth frames)
  *   (nothing: the boxes come from YOLO)               ->  segmentDepth / segmentDepthU16  (the depth image's surfaces as labels and boxes)
+ *   EdgeExtraction    :406 (on a depth-normals cloud) ->  depthEdges / depthEdgesU16  (the image's occluding and boundary pixels: mask and edge cloud)
  *   (nothing: the labels come from YOLO)              ->  Recognizer::recognize  (per proposal cloud the trained models it can be a view of)
  *
  * Every stage returns a new Cloud that stays in HBM; only toMat()/download() copy to the host.  A maintainer replaces
@@ -542,6 +543,9 @@ class Cloud {
   template <class P>
   static P orDefaults(const P* given, void (*defaults)(P*)) { P p; if (given) p = *given; else defaults(&p); return p; }
   friend class DepthVolume; /* its extract() returns a Cloud */
+  friend std::vector<uint8_t> depthEdgesImage(const void* depth, int format, double scale, int rows, int cols, const double* intr,
+                                              const Cloud* normals, const ppf_depth_edge_params* params, Cloud* edgeCloud, float zMin,
+                                              float zMax, bool fp64, size_t rowPitchBytes, ppf_depth_edge_stats* stats); /* fills a Cloud */
   explicit Cloud(ppf_cloud* c) : h_(c, [](ppf_cloud* p) { ppf_cloud_release(p); }) {}
   static Cloud fromDepthImage(const void* depth, int format, double scale, int rows, int cols, double fx, double fy, double ppx,
                               double ppy, float zMin, float zMax, bool fp64, size_t rowPitchBytes,
@@ -1009,6 +1013,44 @@ inline std::vector<int32_t> segmentDepthU16(const uint16_t* depth, int rows, int
                                             const Cloud* normals = 0, const ppf_segment_params* params = 0, float zMin = 0.f, float zMax = 0.f,
                                             size_t rowPitchBytes = 0, int32_t* counts = 0, ppf_segment_stats* stats = 0) {
   return segmentDepthImage(depth, PPF_DEPTH_U16, scale, rows, cols, normals, params, info, zMin, zMax, rowPitchBytes, counts, stats);
+}
+
+/* ppf_depth_edges: where the depth image says a surface ends.  Returns the mask (packed rows x cols: the OR of
+ * PPF_EDGE_OCCLUDING, _OCCLUDED, _BOUNDARY and, with normals, _CURVATURE; 0 at pixels that are not kept) and, when edgeCloud is
+ * given, fills it with the pixels whose mask meets params->select in row-major order: what matchS2B and the frame stages take
+ * as the edge cloud.  normals: 0, or the cloud Cloud::fromDepth gives for this image with ppf_depth_normal_params (no
+ * PPF_DEPTH_NORMALS_DROP) and the same zMin / zMax; the edge cloud's rows are then that cloud's rows and intr is not read.
+ * Without normals the rows are x y z 0 0 0 and intr = {fx, fy, ppx, ppy} is needed for a cloud. */
+inline ppf_depth_edge_params defaultDepthEdgeParams() {
+  ppf_depth_edge_params p;
+  ppf_default_depth_edge_params(&p);
+  return p;
+}
+inline std::vector<uint8_t> depthEdgesImage(const void* depth, int format, double scale, int rows, int cols, const double* intr,
+                                            const Cloud* normals, const ppf_depth_edge_params* params, Cloud* edgeCloud, float zMin,
+                                            float zMax, bool fp64, size_t rowPitchBytes, ppf_depth_edge_stats* stats) {
+  const ppf_depth_params dp = depthParams(format, scale, zMin, zMax, fp64 ? PPF_DEPTH_FP64 : 0);
+  const ppf_depth_edge_params ep = params ? *params : defaultDepthEdgeParams();
+  std::vector<uint8_t> mask((rows > 0 && cols > 0 ? (size_t)rows * (size_t)cols : 0) + 1);
+  ppf_cloud* c = nullptr;
+  ppf_match_3d::check(ppf_depth_edges(depth, rows, cols, rowPitchBytes, intr, &dp, normals ? normals->handle() : 0, &ep, &mask[0],
+                                      edgeCloud ? &c : 0, stats));
+  if (edgeCloud) *edgeCloud = Cloud(c);
+  mask.resize(mask.size() - 1);
+  return mask;
+}
+/* float32 metres in; rowPitchBytes 0: packed rows; params 0: the defaults; edgeCloud 0: the mask alone */
+inline std::vector<uint8_t> depthEdges(const float* depth, int rows, int cols, const double* intr = 0, const Cloud* normals = 0,
+                                       const ppf_depth_edge_params* params = 0, Cloud* edgeCloud = 0, float zMin = 0.f, float zMax = 0.f,
+                                       bool fp64 = false, size_t rowPitchBytes = 0, ppf_depth_edge_stats* stats = 0) {
+  return depthEdgesImage(depth, PPF_DEPTH_F32, 0.001, rows, cols, intr, normals, params, edgeCloud, zMin, zMax, fp64, rowPitchBytes, stats);
+}
+/* a 16-bit sensor image: z = d * scale metres (0.001 for millimetres) */
+inline std::vector<uint8_t> depthEdgesU16(const uint16_t* depth, int rows, int cols, double scale, const double* intr = 0,
+                                          const Cloud* normals = 0, const ppf_depth_edge_params* params = 0, Cloud* edgeCloud = 0,
+                                          float zMin = 0.f, float zMax = 0.f, bool fp64 = false, size_t rowPitchBytes = 0,
+                                          ppf_depth_edge_stats* stats = 0) {
+  return depthEdgesImage(depth, PPF_DEPTH_U16, scale, rows, cols, intr, normals, params, edgeCloud, zMin, zMax, fp64, rowPitchBytes, stats);
 }
 
 /* ppf_recognizer / ppf_recognize_frame: which trained models a proposal cloud can be a view of, from the models'

@@ -1438,6 +1438,77 @@ ppf_status ppf_depth_segments_device(const void* d_depth, int rows, int cols, si
                                      const ppf_cloud* normals /* may be NULL */, const ppf_segment_params* sp, int32_t* d_labels,
                                      void* stream, ppf_segment_info* info, int32_t* counts, ppf_segment_stats* stats /* may be NULL */);
 
+/* ---- a depth image's occluding and boundary edges: the edge cloud of the depth route ------------------ */
+#define PPF_EDGE_OCCLUDING 1  /* p is the near side of a depth step */
+#define PPF_EDGE_OCCLUDED  2  /* p is the far side */
+#define PPF_EDGE_BOUNDARY  4  /* p borders unmeasured pixels with nothing kept behind them */
+#define PPF_EDGE_CURVATURE 8  /* with normals: curvature > curvature_threshold (ppf_prep_edges' rule) */
+#define PPF_DEPTH_EDGE_MAX_GAP 8
+typedef struct ppf_depth_edge_params {
+  float depth_abs;           /* finite, >= 0, metres; default 0.02 */
+  float depth_quad;          /* finite, >= 0, 1/metres; default 0 */
+  int32_t max_gap;           /* 0..8 not-kept pixels a direction may cross; default 2 */
+  float curvature_threshold; /* >= 0, +inf allowed, not NaN; default 0.03; ignored without normals */
+  int32_t select;            /* non-zero subset of the four bits: which pixels go to the cloud;
+                                default OCCLUDING|BOUNDARY|CURVATURE */
+  int32_t flags;             /* none defined: 0 */
+  int32_t reserved[4];
+} ppf_depth_edge_params;
+typedef struct ppf_depth_edge_stats {
+  int32_t n_kept, n_occluding, n_occluded, n_boundary, n_curvature; /* pixels carrying each bit */
+  int32_t n_edge;       /* mask != 0 */
+  int32_t n_selected;   /* mask & select != 0 */
+  int32_t n_no_normal;  /* selected, normals given, normal not finite: left out of the cloud */
+  int32_t n_rows;       /* rows of *out_cloud; 0 when out_cloud is NULL */
+  int32_t n_launches, n_host_syncs;
+  float ms_wall;
+  int32_t reserved[4];
+} ppf_depth_edge_stats;
+/* depth_abs 0.02, depth_quad 0, max_gap 2, curvature_threshold 0.03, select OCCLUDING | BOUNDARY | CURVATURE, flags 0 */
+void ppf_default_depth_edge_params(ppf_depth_edge_params* p);
+/* Where the image says a surface ends, as a closed specification.  Every operation is fp64 as written, nothing fused; z(p) and
+ * "kept" are ppf_cloud_from_depth's, Z = (double)z.
+ *   jump(p, q) iff fabs(Zq - Zp) > (double)depth_abs + (double)depth_quad * (Zp * Zq): the negation of ppf_depth_segments'
+ *   step(p, q), so with equal depth_abs / depth_quad two adjacent kept pixels are an edge pair here iff the segments stage
+ *   refuses to link them without normals.
+ *   The walk.  For a kept p the 8 directions d = (dv, du) are visited in the order (-1,-1) (-1,0) (-1,1) (0,-1) (0,1) (1,-1)
+ *   (1,0) (1,1), with q_j = p + j d.  When q_1 is outside the image the direction gives nothing: the image border is no edge,
+ *   as in the filter.  Otherwise j runs 1 .. max_gap + 1 and stops at the first kept q_j: when jump(p, q_j) the direction
+ *   gives PPF_EDGE_OCCLUDING if Zq > Zp and PPF_EDGE_OCCLUDED if Zq < Zp, and nothing when it does not jump (a hole inside
+ *   one surface is no edge).  When the walk leaves the image at some j >= 2, or ends without a kept pixel, the direction
+ *   gives PPF_EDGE_BOUNDARY.  The pixel's mask is the OR over the 8 directions; with max_gap 0 every kept pixel beside a
+ *   not-kept pixel inside the image is BOUNDARY.
+ *   normals != NULL: the cloud must be what ppf_cloud_from_depth_normals gives for this image and this dp without
+ *   PPF_DEPTH_NORMALS_DROP: row k belongs to the k-th kept pixel in row-major order.  PPF_EDGE_CURVATURE is set iff the row's
+ *   curvature > curvature_threshold (a float comparison: NaN does not set it).
+ * edges: packed rows x cols uint8, 0 at pixels that are not kept.  *out_cloud: the pixels with mask & select != 0 in row-major
+ * pixel order (np.nonzero(mask & select) names them); release it with ppf_cloud_release.  With normals a row is the normals
+ * cloud's row of that pixel byte for byte -- x y z, the normal, the curvature -- intr is not read and may be NULL, and a
+ * selected pixel whose nx, ny, nz are not all finite is left out: it stays in the mask and counts in n_no_normal.  Without
+ * normals a row is ppf_cloud_from_depth's row of that pixel, x y z 0 0 0 with curvature 0: dp->flags of 0 | PPF_DEPTH_FP64 is
+ * honoured and intr is required.  An empty selection gives an empty cloud.
+ *   Checked in this order, all PPF_ERR_INVALID before any device work: out_cloud, when given, gets *out_cloud = NULL; edges
+ *   and out_cloud both NULL; ep NULL; intr NULL where it is required; then ppf_cloud_from_depth's checks of depth, the size,
+ *   dp, the format, dp->flags (an unknown flag), the pitch, the alignment and depth_scale, of intr where it is required, and
+ *   of the z range; then depth_abs, depth_quad, max_gap, curvature_threshold, select (zero, or bits beyond the four), flags.
+ *   Without a device the call is PPF_ERR_HIP.  A normals cloud whose row count is not n_kept is PPF_ERR_INVALID, found at
+ *   the call's first wait.  On any error *out_cloud is NULL, *stats is zero and edges is untouched.
+ * A mask-only call without normals is one launch and one blocking wait.  Normals add the scan of the kept ranks and one pass
+ * (7 launches); a cloud adds the scan of the selected ranks, the wait that sizes the cloud and the pass that writes it
+ * (7 launches and 2 waits without normals, 13 and 2 with them).  The counts depend on nothing but normals != NULL and
+ * out_cloud != NULL.  No atomic decides a place.  Two threads may call at once. */
+ppf_status ppf_depth_edges(const void* depth, int rows, int cols, size_t row_pitch_bytes, const double* intr /* may be NULL, see above */,
+                           const ppf_depth_params* dp, const ppf_cloud* normals /* may be NULL */, const ppf_depth_edge_params* ep,
+                           uint8_t* edges /* may be NULL */, ppf_cloud** out_cloud /* may be NULL */, ppf_depth_edge_stats* stats /* may be NULL */);
+/* the same between DEVICE buffers, as ppf_depth_filter_device: enqueued on `stream` (a hipStream_t, NULL: default stream),
+ * returns when the mask and the cloud are complete; stats stays HOST memory.  A pointer the current device cannot read, a
+ * buffer that runs past the end of its allocation, or d_edges overlapping the depth image is PPF_ERR_INVALID before anything
+ * is launched; after any other error the content of d_edges is unspecified. */
+ppf_status ppf_depth_edges_device(const void* d_depth, int rows, int cols, size_t row_pitch_bytes, const double* intr /* may be NULL */,
+                                  const ppf_depth_params* dp, const ppf_cloud* normals /* may be NULL */, const ppf_depth_edge_params* ep,
+                                  uint8_t* d_edges /* may be NULL */, void* stream, ppf_cloud** out_cloud /* may be NULL */,
+                                  ppf_depth_edge_stats* stats /* may be NULL */);
+
 /* ---- which trained models a proposal can be a view of: labels for detections nobody named ------------ */
 #define PPF_RECOGNIZE_MAX_MODELS 64
 #define PPF_RECOGNIZE_MAX_CLOUDS 256

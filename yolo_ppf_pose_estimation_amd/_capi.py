@@ -329,6 +329,22 @@ class SegmentStats(C.Structure):
 PPF_SEGMENT_EIGHT, PPF_SEGMENT_UNORIENTED = 1, 2  # SegmentParams.flags bits
 
 
+class DepthEdgeParams(C.Structure):
+    _fields_ = [("depth_abs", C.c_float), ("depth_quad", C.c_float), ("max_gap", C.c_int32), ("curvature_threshold", C.c_float),
+                ("select", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class DepthEdgeStats(C.Structure):
+    _fields_ = [("n_kept", C.c_int32), ("n_occluding", C.c_int32), ("n_occluded", C.c_int32), ("n_boundary", C.c_int32),
+                ("n_curvature", C.c_int32), ("n_edge", C.c_int32), ("n_selected", C.c_int32), ("n_no_normal", C.c_int32),
+                ("n_rows", C.c_int32), ("n_launches", C.c_int32), ("n_host_syncs", C.c_int32), ("ms_wall", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
+PPF_EDGE_OCCLUDING, PPF_EDGE_OCCLUDED, PPF_EDGE_BOUNDARY, PPF_EDGE_CURVATURE = 1, 2, 4, 8  # the edge mask's bits
+PPF_DEPTH_EDGE_MAX_GAP = 8
+
+
 class RecognizerInfo(C.Structure):
     _fields_ = [("n_rows", C.c_int32), ("n_bins", C.c_int32 * 4), ("in_lds", C.c_int32), ("n_keys", C.c_uint64),
                 ("bytes", C.c_uint64), ("reserved", C.c_int32 * 4)]
@@ -660,6 +676,12 @@ _SIGNATURES = {
     "ppf_depth_segments_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(DepthParams), C.c_void_p,
                                             C.POINTER(SegmentParams), C.c_void_p, C.c_void_p, C.POINTER(SegmentInfo),
                                             C.POINTER(C.c_int32), C.POINTER(SegmentStats)]),
+    "ppf_default_depth_edge_params": (None, [C.POINTER(DepthEdgeParams)]),
+    "ppf_depth_edges": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_double), C.POINTER(DepthParams), C.c_void_p,
+                                  C.POINTER(DepthEdgeParams), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(DepthEdgeStats)]),
+    "ppf_depth_edges_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_double), C.POINTER(DepthParams),
+                                         C.c_void_p, C.POINTER(DepthEdgeParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                         C.POINTER(DepthEdgeStats)]),
     "ppf_recognizer_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]),
     "ppf_recognizer_retain": (C.c_int, [C.c_void_p]),
     "ppf_recognizer_release": (C.c_int, [C.c_void_p]),

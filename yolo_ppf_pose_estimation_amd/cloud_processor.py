@@ -45,7 +45,7 @@ class DeviceCloud:
 
     @classmethod
     def from_depth(cls, depth, intr, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0,
-                   fp64: bool = False, normals: Optional[dict] = None, filter: Optional[dict] = None) -> "DeviceCloud":
+                   fp64: bool = False, normals: Optional[dict] = None, filter: Optional[dict] = None, edges: Optional[dict] = None):
         """The organised scene cloud of a depth image, back-projected on the device (ppf_cloud_from_depth): rows
         ``x y z 0 0 0`` of every pixel with a finite z > 0 inside [z_min, z_max] (z_max 0: no upper bound), in row-major
         pixel order.  depth: a 2-D numpy float32 (metres) or uint16 (units of depth_scale metres) array, rows read at its
@@ -57,7 +57,9 @@ class DeviceCloud:
         min_neighbours neighbours gets NaNs, or with drop=True no row.  filter: None, or a dict of ppf_depth_filter_params
         fields ({}: the defaults): the image goes through ``filter_depth`` first -- on the device and the
         current stream for a GPU tensor -- and the cloud is built from the filtered float32 image with the same z_min and
-        z_max."""
+        z_max.  edges: None, or a dict of ppf_depth_edge_params fields ({}: the defaults): the result is then
+        ``(cloud, edge_cloud)``, the second being ``depth_edges``' cloud of the same (filtered) image, with
+        the cloud as its normals when ``normals`` is given without drop."""
         if filter is not None:
             depth = filter_depth(depth, depth_scale=depth_scale, z_min=z_min, z_max=z_max, params=filter)
         K = np.asarray(intr, dtype=np.float64)
@@ -81,7 +83,12 @@ class DeviceCloud:
         with inp.device():
             tail = (() if nprm is None else (C.byref(nprm),)) + ((inp.stream(),) if inp.is_device else ())
             check(getattr(lib(), name)(inp.ptr, inp.rows, inp.cols, inp.pitch, it, C.byref(prm), *tail, C.byref(out)))
-        return cls(out)
+        made = cls(out)
+        if edges is None:
+            return made
+        nrm = made if nprm is not None and not nprm.flags & _capi.PPF_DEPTH_NORMALS_DROP else None
+        _, edge = depth_edges(depth, intr, depth_scale=depth_scale, z_min=z_min, z_max=z_max, fp64=fp64, normals=nrm, params=edges, cloud=True)
+        return made, edge
 
     @classmethod
     def from_mesh(cls, vertices, triangles, spacing: float, *, seed: int = 0, normals: str = "face", visibility: bool = True,
@@ -1278,6 +1285,41 @@ def segment_depth(depth, *, depth_scale: float = 0.001, z_min: float = 0.0, z_ma
     return result(out)
 
 
+def depth_edges(depth, intr=None, *, depth_scale: float = 0.001, z_min: float = 0.0, z_max: float = 0.0, fp64: bool = False,
+                normals=None, params=None, cloud: bool = False, out=None, return_stats: bool = False):
+    """Where the depth image says a surface ends (ppf_depth_edges): a uint8 image of the same shape whose bits
+    are PPF_EDGE_OCCLUDING (the near side of a depth step of more than ``depth_abs + depth_quad * Zp * Zq``, looked for in 8
+    directions across up to ``max_gap`` unmeasured pixels), PPF_EDGE_OCCLUDED (the far side), PPF_EDGE_BOUNDARY (unmeasured
+    pixels with nothing behind them) and -- with ``normals``, the DeviceCloud that ``DeviceCloud.from_depth(depth, ...,
+    normals={...})`` gives for this image (no ``drop``) -- PPF_EDGE_CURVATURE (curvature > ``curvature_threshold``).  With
+    ``cloud=True`` also the edge cloud, a DeviceCloud of the pixels whose mask meets ``select`` in row-major order, which
+    ``Matching_S2B`` and the frame stages take: the normals cloud's rows with normals, else ``x y z 0 0 0`` from ``intr``
+    ((fx, fy, ppx, ppy) or the 3x3 matrix; ``fp64`` as in ``from_depth``).  depth: a 2-D numpy float32 (metres) or uint16
+    (units of depth_scale metres) array, rows read at its stride, which gives a numpy mask; or such a torch tensor on the
+    GPU, read in place on ``torch.cuda.current_stream()`` (ppf_depth_edges_device), which gives a uint8 tensor on the same
+    device (or fills ``out``, which must not overlap the input).  params: a DepthEdgeParams, a dict of its fields or None
+    (the defaults).  Returns the mask, then the cloud with ``cloud``, then the stats with ``return_stats``."""
+    prm = _params(_capi.DepthEdgeParams, "ppf_default_depth_edge_params", params, "depth edge")
+    dp = _depth_params(depth_scale, z_min, z_max, _capi.PPF_DEPTH_FP64 if fp64 else 0)
+    if normals is not None and not isinstance(normals, DeviceCloud):
+        raise PPFError(_capi.PPF_ERR_INVALID, "normals must be a DeviceCloud or None")
+    nrm = normals._ptr if normals is not None else None
+    it = (C.c_double * 4)(*_intr4(intr)) if intr is not None else None
+    st = _capi.DepthEdgeStats()
+    found = C.c_void_p()
+    inp = _DepthInput(depth, "depth must be a 2-D float32 or uint16 {kind}")
+    dp.format = inp.format
+    out, optr = inp.output(out, np.uint8)
+    tail = (C.byref(found) if cloud else None, C.byref(st))
+    with inp.device():
+        if inp.is_device:
+            check(lib().ppf_depth_edges_device(inp.ptr, inp.rows, inp.cols, inp.pitch, it, C.byref(dp), nrm, C.byref(prm), optr, inp.stream(), *tail))
+        else:
+            check(lib().ppf_depth_edges(inp.ptr, inp.rows, inp.cols, inp.pitch, it, C.byref(dp), nrm, C.byref(prm), optr, *tail))
+    res = [out] + ([DeviceCloud(found)] if cloud else []) + ([_capi.stats_dict(st)] if return_stats else [])
+    return out if len(res) == 1 else tuple(res)
+
+
 # ppf_recognize_score as a numpy record
 RECOGNIZE_SCORE = np.dtype([("model", "<i4"), ("reserved", "<i4"), ("n_known", "<u8"), ("n_keys_hit", "<u8"), ("precision", "<f8"),
                             ("recall", "<f8"), ("score", "<f8")])
@@ -1422,6 +1464,9 @@ class CloudProcessor:
         self.segment_labels: Optional[np.ndarray] = None
         self.segment_stats: Dict[str, object] = {}
         self._depth_normals_of: tuple = (None, None)  # the (scene, depth) pair Deprojection(normals=...) last made
+        # EdgeExtractionDepth: the edge mask of the depth image and the ppf_depth_edges counters
+        self.depth_edge_mask: Optional[np.ndarray] = None
+        self.depth_edge_stats: Dict[str, object] = {}
         # RecognizeFrame: per detection its (label, score, precision, recall) candidates, best first, and the counters
         self.frame_candidates: List[List[tuple]] = []
         self.recognize_stats: Dict[str, object] = {}
@@ -1541,6 +1586,23 @@ class CloudProcessor:
     def EdgeExtraction(self, curvThreshold: float) -> List[DeviceCloud]:
         self.objects_edges += [o.edges(curvThreshold) for o in self.objects_with_normals]
         return self.objects_edges
+
+    def EdgeExtractionDepth(self, params=None, CameraIntr=None) -> DeviceCloud:
+        """EdgeExtraction for the depth route: the edge cloud of ``self.depth`` itself (``depth_edges``, ppf_depth_edges) --
+        its occluding and boundary pixels, which the curvature of depth normals never marks.  When ``self.scene`` is what
+        ``Deprojection(normals=...)`` gave for this depth image it serves as the normals cloud, so the rows carry its normals
+        and the curvature edges join; otherwise the rows are ``x y z 0 0 0`` and CameraIntr (the 3x3 matrix) is needed.
+        params: the fields of ppf_depth_edge_params (depth_abs, depth_quad, max_gap, curvature_threshold, select).  Sets
+        ``depth_edge_mask`` and ``depth_edge_stats``; appends the cloud to ``objects_edges``, where EdgeExtraction leaves the
+        clouds that Matching_S2B takes as ``edge``, and returns it."""
+        if self.depth is None:
+            raise PPFError(_capi.PPF_ERR_INVALID, "EdgeExtractionDepth needs a depth image")
+        made = self.scene is not None and self.scene is self._depth_normals_of[0] and self.depth is self._depth_normals_of[1]
+        intr = None if CameraIntr is None else np.asarray(CameraIntr, dtype=np.float64)
+        self.depth_edge_mask, edge, self.depth_edge_stats = depth_edges(self.depth, intr, normals=self.scene if made else None,
+                                                                        params=params, cloud=True, return_stats=True)
+        self.objects_edges.append(edge)
+        return edge
 
     @staticmethod
     def PointCloudXYZNormalToMat(pcl_cloud: DeviceCloud, resident: bool = False):

@@ -25,7 +25,7 @@
  *             k_group / k_vote)  ppf_pose_kernels.h (k_finalize, k_rank, clustering)  ppf_icp_kernels.h  ppf_prep_kernels.h
  *             ppf_depth_kernels.h  ppf_depth_normals_kernels.h  ppf_verify_kernels.h  ppf_render_kernels.h  ppf_select_kernels.h  ppf_refine_kernels.h
  *             ppf_register_kernels.h  ppf_plane_kernels.h  ppf_label_kernels.h  ppf_cluster_kernels.h  ppf_region_kernels.h  ppf_filter_kernels.h
- *             ppf_segment_kernels.h  ppf_recognize_kernels.h  ppf_history_kernels.h  ppf_motion_kernels.h
+ *             ppf_segment_kernels.h  ppf_edge_kernels.h  ppf_recognize_kernels.h  ppf_history_kernels.h  ppf_motion_kernels.h
  *             ppf_volume_kernels.h  ppf_volume_mesh_kernels.h  ppf_mesh_kernels.h  ppf_mesh_components_kernels.h
  *   host      ppf_device_mem.h (errors, block cache)  ppf_host_common.h (scans, sorts, model / workspace structs)
  *             ppf_model_host.h  ppf_match_host.h  ppf_batch_host.h  ppf_icp_host.h  ppf_stage_host.h (what every stage call
@@ -33,7 +33,7 @@
  *             segment)  ppf_frame_host.h (ppf_prep_frame = their chain)
  *             ppf_match_frame_host.h  ppf_depthimage_host.h  ppf_depth_host.h  ppf_posetable_host.h  ppf_verify_host.h  ppf_render_host.h
  *             ppf_select_host.h  ppf_refine_host.h  ppf_register_host.h  ppf_plane_host.h  ppf_cluster_host.h  ppf_region_host.h
- *             ppf_filter_host.h  ppf_segment_host.h  ppf_recognize_host.h  ppf_history_host.h  ppf_motion_host.h
+ *             ppf_filter_host.h  ppf_segment_host.h  ppf_edge_host.h  ppf_recognize_host.h  ppf_history_host.h  ppf_motion_host.h
  *             ppf_volume_host.h  ppf_mesh_components_host.h  ppf_mesh_host.h  (the C-ABI)
  *   model host (ppf_model_host.h): model_plan (parameters -> steps, slots, tiles; pure), build_table (training's device
  *             passes in named steps), ModelImage (what a model file holds: read + validate, write, download, upload),
@@ -73,6 +73,7 @@
 #include "ppf_depth_kernels.h" /* k_depth_count, k_depth_scatter */
 #include "ppf_depth_normals_kernels.h" /* k_depth_normals, k_depthn_count, k_depthn_scatter */
 #include "ppf_filter_kernels.h" /* k_depth_filter */
+#include "ppf_edge_kernels.h" /* k_depth_edges, k_edge_select, k_edge_write */
 #include "ppf_history_kernels.h" /* k_history_push */
 #include "ppf_verify_kernels.h" /* k_vfy_grid_count / _grid_scatter, k_vfy_score, k_vfy_finish */
 #include "ppf_render_kernels.h" /* k_rnd_window, k_rnd_splat, k_rnd_vfy_score, k_rnd_splat_frame, k_rnd_resolve */
@@ -118,4 +119,5 @@
 #include "ppf_mesh_components_host.h" /* a mesh's connected components, scraps removed: ppf_volume_mesh_upload, ppf_volume_mesh_components */
 #include "ppf_mesh_host.h"        /* a model cloud sampled from a triangle mesh: ppf_cloud_from_mesh */
 #include "ppf_segment_host.h"     /* a depth image's surfaces labelled in image space: ppf_depth_segments */
+#include "ppf_edge_host.h"        /* a depth image's occluding and boundary edges, mask and edge cloud: ppf_depth_edges */
 #include "ppf_recognize_host.h"   /* which trained models a proposal can be a view of: ppf_recognizer_*, ppf_recognize_frame */
